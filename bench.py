@@ -2,8 +2,17 @@
 """
 bench.py -- images/sec end-to-end of the predict_on_batch path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--dtype f16x3|f32|bf16x3|f16|bf16] [--all-dtypes]
+    python bench.py --gpus N --steps K --warmup W [--dtype f16x3|f32|bf16x3|f16|bf16] [--full [--all-dtypes]] [--dump-outputs DIR]
     (N > 1: launched by the driver under torch.distributed.run, one rank per GPU)
+
+A plain run does what the headline needs and nothing else: it builds the plan, warms up, times the K steps, writes the
+outputs of the last timed step if --dump-outputs is given, and prints the line (`value`, `ms_per_step`, the roofline of the
+dominant kernel from HIP events inside the timed steps).  Everything measured or checked beyond that -- the float32 leg and
+the parity ledgers, the ledgers against the committed oracle fixtures, the CPU baseline and its bit-exact replay, the other
+types, the host-fed legs, the batch-1 latency, the repeats -- runs only under --full (the --no-* options thin out a --full run).
+--dump-outputs DIR: the eight result arrays of the last timed step (the plan's output buffers, what predict_on_batch returns;
+frames 0 .. B-1 of this rank) as DIR/<name>.npy, float32 or float64 (integer outputs), and on N > 1 ranks the gathered packed
+detections; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 A step = one predict_on_batch-equivalent pass (ResNet-50 + FPN + heads + decode/NMS + ground-plane
 polling, 1k-plane database) over a batch of 8 synthetic 1242x375 frames per GPU, already resized to
@@ -17,8 +26,8 @@ utils/ledger.REFERENCE_BARS): float32 storage, every float32 product as three IE
 v_mfma_f32_16x16x32_f16 (11 + 11 significant bits per operand, ~2^-22 per product; float32: 2^-24), float32 accumulation.
 f32 = the reference's own arithmetic type (float32 operands on v_mfma_f32_16x16x4_f32, 1/16 of the 16-bit matrix rate);
 bf16x3 (three bf16 products, ~2^-16), f16, bf16 = faster types that do NOT meet the tolerance with these weights and are therefore
-never the headline: `--all-dtypes` measures them on the same frames with their ledgers (config.other_types_same_frames).
-Decode and polling are float32 / int32 in every mode.  A single-GPU run ALSO measures the float32 path on the same frames
+never the headline: `--full --all-dtypes` measures them on the same frames with their ledgers (config.other_types_same_frames).
+Decode and polling are float32 / int32 in every mode.  A single-GPU --full run ALSO measures the float32 path on the same frames
 (config.f32_images_per_s) and checks its own headline against it (config.parity_ledger, config.parity_bars_met); a headline
 that misses a bar makes the run exit non-zero after printing the line.
 
@@ -26,7 +35,7 @@ The JSON line also carries
   roofline      the dominant kernel = conv_igemm_kernel on the 3x3 512->512 regression-tower layers
                 (45 % of all FLOPs): algorithmic FLOPs per launch / mean launch duration measured with
                 HIP events inside the timed region, against the dense MFMA peak of the operand type
-  cpu_baseline  the CPU oracle (torch float32 restatement + NumPy decode + C polling) timed on this
+  cpu_baseline  (--full) the CPU oracle (torch float32 restatement + NumPy decode + C polling) timed on this
                 host on a bounded sample -- "CPU restatement, not TF1" (TF1 cannot be installed); the same leg replays
                 decode + polling of the GPU's own head tensors of the last timed step and reports whether they agree
                 bit for bit (config.gpu_decode_polling_replay_bit_exact)
@@ -56,6 +65,8 @@ PROFILE_ROUNDS = ('r6', 'r5', 'r4', 'r3')      # the PMC file of the newest roun
 # 2 bytes per element for the 16-bit storage types, 4 for the float32-sized maps of f32 / bf16x3 / f16x3
 ALGORITHMIC_MB = {'bf16': 192.1, 'f16': 192.1, 'f32': 384.2, 'bf16x3': 384.2, 'f16x3': 384.2}
 RESIDENT_BATCHES = 6      # the timed steps rotate over this many distinct resident batches (6 x 51 MB > the 256 MB Infinity Cache)
+OUTPUT_NAMES = ('boxes', 'dimensions', 'scores', 'labels', 'orientations', 'keypoints', 'keyplanes', 'residuals')     # model.outputs() order
+DUMP_LIMIT_BYTES = 64 << 20
 
 
 def parse():
@@ -67,16 +78,27 @@ def parse():
     p.add_argument('--backbone', default='resnet50')
     p.add_argument('--planes', default='1k')
     p.add_argument('--dtype', default='f16x3', choices=['bf16', 'f16', 'f32', 'bf16x3', 'f16x3'])
-    p.add_argument('--all-dtypes', action='store_true', help='also measure the other types on the same frames, with their ledgers')
-    p.add_argument('--no-cpu-baseline', action='store_true')
-    p.add_argument('--no-f32-leg', action='store_true', help='skip the float32 leg + parity ledger of a 16-bit run')
-    p.add_argument('--no-host-fed', action='store_true', help='skip the host-fed (PCIe-inclusive) legs')
+    p.add_argument('--full', action='store_true',
+                   help='also run every leg beyond the headline: float32 leg + parity ledgers, oracle-fixture ledgers, CPU baseline + replay, '
+                        'host-fed legs, batch-1 latency, repeats (off: set up, warm up, time the K steps, print the line)')
+    p.add_argument('--dump-outputs', metavar='DIR', help='write the outputs of the last timed step to DIR/<name>.npy (float32 / float64)')
+    p.add_argument('--all-dtypes', action='store_true', help='(--full) also measure the other types on the same frames, with their ledgers')
+    p.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baseline and its replay')
+    p.add_argument('--no-f32-leg', action='store_true', help='(--full) skip the float32 leg + parity ledger of a 16-bit run')
+    p.add_argument('--no-host-fed', action='store_true', help='(--full) skip the host-fed (PCIe-inclusive) legs')
     p.add_argument('--cpu-images', type=int, default=4, help='frames of the bounded CPU-baseline sample (about 3.5 s each on 128 host threads)')
-    p.add_argument('--no-b1', action='store_true', help='skip the batch-1 synchronous latency leg (config.b1)')
-    p.add_argument('--repeats', type=int, default=3, help='further timed repeats of the K steps after the headline loop (config.repeat_images_per_s)')
+    p.add_argument('--no-b1', action='store_true', help='(--full) skip the batch-1 synchronous latency leg (config.b1)')
+    p.add_argument('--repeats', type=int, default=3, help='(--full) further timed repeats of the K steps after the headline loop (config.repeat_images_per_s)')
     p.add_argument('--dry-launch', action='store_true',
                    help='rehearse the rank launcher without a GPU: every rank joins a gloo group, gathers a packed (B,100,35) tensor and exits')
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error('--steps must be at least 1')
+    if args.warmup < 0:
+        p.error('--warmup must not be negative')
+    if args.all_dtypes and not args.full:
+        p.error('--all-dtypes is a leg of --full')
+    return args
 
 
 def launch_ranks(args):
@@ -244,6 +266,17 @@ def cpu_baseline(n_images, backbone, planes, replay=None):
     return rec, exact
 
 
+def dump_outputs(directory, arrays):
+    """ name -> host array as directory/<name>.npy: float32 and float64 as they are, integer outputs (labels, orientations) as float64 (exact) """
+    arrays = {k: a if a.dtype in (np.float32, np.float64) else a.astype(np.float64) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit('--dump-outputs: {} bytes of outputs, more than the {} allowed'.format(total, DUMP_LIMIT_BYTES))
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + '.npy'), a)
+
+
 def unfuse(reg, n_base=12):
     """ fused conv layout (B, P, 144) -> reference layout (B, A, 12) """
     B, P, _ = reg.shape
@@ -393,6 +426,14 @@ def main():
     # the bracket: 0.4 % of a 100-step region, 1 % of the 30-step default; the repeats below never had it, hence their higher rates in those rounds' lines)
     monitor.__exit__(None, None, None)
     device_state = monitor.summary()
+    # outputs + head tensors of the last timed step (host copies): what --dump-outputs writes, the ledgers' run under test, the oracle's replay input
+    main_outs = [t.cpu().numpy() for t in model.outputs(plan)]
+    main_anchor, main_plane = plan.anchor_index.cpu().numpy(), plan.best_index.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        arrays = dict(zip(OUTPUT_NAMES, main_outs))
+        if out is not None:
+            arrays['gathered_detections'] = out.cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
     per_rank = None
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device='cuda')
@@ -437,7 +478,7 @@ def main():
     # the line's own error bar (reported, never `value`): the same K steps timed again --repeats times, same bracket (barrier +
     # synchronize on both sides, max over ranks), same rotation over the resident batches, the dominant kernel's events read per repeat
     repeat_rates, repeat_fracs = [], []
-    for _ in range(max(0, args.repeats)):
+    for _ in range(max(0, args.repeats) if args.full else 0):
         if distributed:
             dist.barrier()
         torch.cuda.synchronize()
@@ -493,11 +534,8 @@ def main():
     if out is None:
         out = D.pack_outputs(model.outputs(plan))
     dets = int((out[:, :, 15] > 0.05).sum().item())
-    extras = rank == 0 and world == 1
+    extras = rank == 0 and world == 1 and args.full
 
-    # outputs + head tensors of the last timed step (host copies): the ledger's run under test, the oracle's replay input
-    main_outs = [t.cpu().numpy() for t in model.outputs(plan)]
-    main_anchor, main_plane = plan.anchor_index.cpu().numpy(), plan.best_index.cpu().numpy()
     replay = None
     if extras and not args.no_cpu_baseline:
         nrep = min(2, B)
@@ -532,7 +570,7 @@ def main():
     # THE bars (utils/ledger.REFERENCE_BARS) are measured against it; f32 = one float32 CPU evaluation, informational
     oracle_ledgers = {}
     fixture = os.path.join(ROOT, 'tests', 'golden', 'fullsize_{}_{}_{{}}.npz'.format(args.backbone, args.planes))
-    if rank == 0 and world == 1 and os.path.isfile(fixture.format('f64')):
+    if extras and os.path.isfile(fixture.format('f64')):
         for prec in ('f64', 'f32'):
             g = np.load(fixture.format(prec))
             if len(g['frames']) >= B:
@@ -667,6 +705,7 @@ def main():
                        # through model.fetch, which would have reacted) -- an activation beyond +-65504 would have been clamped; must be 0
                        'f16x3_range_events_in_run': model.x3_range_events() if args.dtype == 'f16x3' else None,
                        'resident_batches_rotated': RESIDENT_BATCHES,
+                       'full': args.full,        # False: the legs of --full were not run, their fields are null
                        'side_stream_launches': dict(getattr(plan, 'side_lanes', {}), decode=bool(getattr(plan, 'decode_overlap', False))),
                        'multi_gpu_diagnosis': per_rank,
                        'step_contents_note': 'a 1-GPU step is the plan alone (its eight result arrays are the plan\'s output buffers); an N > 1 step adds '
@@ -717,7 +756,7 @@ def main():
             rec['roofline']['device_during_timed_region'] = device_state
             if device_state.get('sclk_mhz_median'):
                 rec['roofline']['frac_at_the_steps_median_clock'] = round(achieved / (PEAK_TFLOPS[args.dtype] * device_state['sclk_mhz_median'] / 2400.0), 4)
-        if world == 1 and not args.no_cpu_baseline:
+        if extras and not args.no_cpu_baseline:
             rec['cpu_baseline'], exact = cpu_baseline(args.cpu_images, args.backbone, planes, replay)
             rec['config']['gpu_decode_polling_replay_bit_exact'] = exact
             if exact is False:

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--cpu-images', '1',
-                          '--all-dtypes'],
+                          '--full', '--all-dtypes'],
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
@@ -57,6 +57,35 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     b1 = cfg['b1']
     assert 0.5 < b1['plan_only_ms_median'] < b1['sync_ms_median'] < 20.0 and b1['sync_ms_p90'] >= b1['sync_ms_median'] and b1['detections_last_call'] > 0
     assert set(b1['stages_ms']) == {'stem+backbone', 'fpn', 'heads+selection', 'emit+polling'} and b1['floor_ms'] < b1['plan_only_ms_median']
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """ without --full: the headline alone (no leg beyond it), and --dump-outputs writes the eight arrays of the last timed step -- frames
+    0 .. 7, the same detections as the float64 oracle fixture of those frames """
+    import numpy as np
+    dump = tmp_path / 'outputs'
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '1', '--dump-outputs', str(dump)],
+                         stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=900, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec['steps'] == 4 and rec['warmup'] == 1 and rec['dtype'] == 'f16x3' and rec['unit'] == 'images/s' and rec['higher_is_better'] is True
+    assert abs(rec['value'] - 8 * 4 / (rec['ms_per_step'] * 4e-3)) < 0.01 * rec['value']
+    cfg = rec['config']
+    assert cfg['full'] is False and 'cpu_baseline' not in rec and cfg['f32_images_per_s'] is None and cfg['parity_ledger'] is None
+    assert cfg['parity_ledger_vs_f64_oracle'] is None and cfg['repeat_images_per_s'] is None and cfg['b1'] is None
+    assert cfg['host_fed_streaming_images_per_s'] is None and rec['roofline']['launches_timed'] == 6      # steps 0 and 3 of 4
+    shapes = {'boxes': (8, 100, 12), 'dimensions': (8, 100, 3), 'scores': (8, 100), 'labels': (8, 100), 'orientations': (8, 100),
+              'keypoints': (8, 100, 4, 3), 'keyplanes': (8, 100, 1, 4), 'residuals': (8, 100)}
+    assert sorted(p.name for p in dump.iterdir()) == sorted(n + '.npy' for n in shapes)
+    got = {n: np.load(str(dump / (n + '.npy'))) for n in shapes}
+    for n, shape in shapes.items():
+        assert got[n].shape == shape and got[n].dtype in (np.float32, np.float64), (n, got[n].shape, got[n].dtype)
+    g = np.load(os.path.join(ROOT, 'tests', 'golden', 'fullsize_resnet50_1k_f64.npz'))
+    assert np.abs(np.sort(got['scores'], axis=1) - np.sort(g['scores'][:8], axis=1)).max() < 1e-5
+    assert (np.sort(got['labels'], axis=1) == np.sort(g['labels'][:8], axis=1)).all()
 
 
 @pytest.mark.gpu

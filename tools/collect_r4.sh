@@ -2,10 +2,10 @@
 # Everything profiles/r4 holds, with ONE build of the library, in one gpurun call.   usage: bash tools/collect_r4.sh   (on the GPU box)
 o=gpurun_out/r4/final; mkdir -p $o
 step() { echo "== $1"; }
-step bench;        python bench.py --steps 100 --warmup 10 > $o/bench_default_run.json 2> $o/bench_default_run.err; tail -c 300 $o/bench_default_run.json; echo
-step bench_c4;     python bench.py --backbone resnet101 --planes 10k --steps 40 --no-host-fed --no-cpu-baseline > $o/bench_c4_f16x3.json 2> /dev/null
-step bench_c5;     python bench.py --backbone resnet152 --planes 22k --batch 4 --steps 40 --no-host-fed --no-cpu-baseline > $o/bench_c5_f16x3.json 2> /dev/null
-step all_dtypes;   python bench.py --steps 30 --all-dtypes --no-cpu-baseline --no-host-fed > $o/bench_all_dtypes.json 2> /dev/null
+step bench;        python bench.py --full --steps 100 --warmup 10 > $o/bench_default_run.json 2> $o/bench_default_run.err; tail -c 300 $o/bench_default_run.json; echo
+step bench_c4;     python bench.py --full --backbone resnet101 --planes 10k --steps 40 --no-host-fed --no-cpu-baseline > $o/bench_c4_f16x3.json 2> /dev/null
+step bench_c5;     python bench.py --full --backbone resnet152 --planes 22k --batch 4 --steps 40 --no-host-fed --no-cpu-baseline > $o/bench_c5_f16x3.json 2> /dev/null
+step all_dtypes;   python bench.py --full --steps 30 --all-dtypes --no-cpu-baseline --no-host-fed > $o/bench_all_dtypes.json 2> /dev/null
 step profile;      bash tools/profile_bench.sh $o/prof f16x3 > $o/profile_bench.log 2>&1; tail -4 $o/profile_bench.log
 step timeline;     bash tools/profile_default_plan.sh $o/prof_default f16x3 > /dev/null 2>&1; tail -1 $o/prof_default/timeline.txt
 step pmc;          bash tools/pmc_bench.sh $o/pmc f16x3 > $o/pmc_bench.log 2>&1; tail -12 $o/pmc_bench.log

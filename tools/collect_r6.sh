@@ -6,10 +6,10 @@ part=${1:-a}
 o=gpurun_out/r6/final; mkdir -p $o
 step() { echo "== $1"; }
 if [ "$part" = a ] || [ "$part" = a1 ]; then
-step bench;        python bench.py --steps 100 --warmup 10 > $o/bench_default_run.json 2> $o/bench_default_run.err; tail -c 300 $o/bench_default_run.json; echo
-step driver_style; python bench.py > $o/bench_driver_style.json 2> $o/bench_driver_style.err; tail -c 200 $o/bench_driver_style.json; echo
-step bench_c4;     python bench.py --backbone resnet101 --planes 10k --steps 40 --no-host-fed --no-cpu-baseline --no-b1 > $o/bench_c4_f16x3.json 2> /dev/null
-step bench_c5;     python bench.py --backbone resnet152 --planes 22k --batch 4 --steps 40 --no-host-fed --no-cpu-baseline --no-b1 > $o/bench_c5_f16x3.json 2> /dev/null
+step bench;        python bench.py --full --steps 100 --warmup 10 > $o/bench_default_run.json 2> $o/bench_default_run.err; tail -c 300 $o/bench_default_run.json; echo
+step driver_style; python bench.py --full > $o/bench_driver_style.json 2> $o/bench_driver_style.err; tail -c 200 $o/bench_driver_style.json; echo
+step bench_c4;     python bench.py --full --backbone resnet101 --planes 10k --steps 40 --no-host-fed --no-cpu-baseline --no-b1 > $o/bench_c4_f16x3.json 2> /dev/null
+step bench_c5;     python bench.py --full --backbone resnet152 --planes 22k --batch 4 --steps 40 --no-host-fed --no-cpu-baseline --no-b1 > $o/bench_c5_f16x3.json 2> /dev/null
 step b1;           python tools/b1_latency.py --n 100 > $o/b1_latency_default_plan.json 2> $o/b1_latency.err; GPP_PLAN=latency python tools/b1_latency.py --n 100 > $o/b1_latency_latency_plan.json 2>> $o/b1_latency.err; tail -c 300 $o/b1_latency_latency_plan.json; echo
 step b1_floors;    python tools/fill_floor_table.py f16x3 resnet50 1 2>/dev/null > $o/b1_per_layer.txt; tail -1 $o/b1_per_layer.txt
 fi
