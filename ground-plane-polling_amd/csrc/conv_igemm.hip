@@ -407,3 +407,107 @@ extern "C" int gpp_conv2d_autotune(gpp_conv_desc* desc, int iters, void* stream,
     if (best_us) *best_us = best;
     return rc;
 }
+
+// ---- gpp_conv2d_preact: the 1 x 1 convolution of a DenseNet layer with its input's BatchNormalization + ReLU as a prologue
+// (conv_igemm_impl.h: PRE).  Scope: 1 x 1, stride 1, pad 0 (a padded zero would become relu(shift)), float32-sized input map that is
+// not pre-split, GPP_F32 / GPP_F16X3 / GPP_BF16X3.
+namespace {
+
+static const int kPreactTiles[] = {0, 64064, 128064, 64128, 128128, 192128};
+
+int preact_validate(gpp_conv_desc& d, const float* in_scale, const float* in_shift)
+{
+    for (int g = 0; g < GPP_MAX_GROUPS; ++g) d.groups[g].row_begin = 0;
+    int rc = validate(d);
+    if (rc != GPP_OK) return rc;
+    if (d.dtype != GPP_F32 && !is_x3(d.dtype)) return GPP_ERR_UNSUPPORTED;
+    if (!in_scale || !in_shift) return GPP_ERR_BAD_ARG;
+    if (((uintptr_t)in_scale | (uintptr_t)in_shift) & 15) return GPP_ERR_ALIGN;
+    if (d.KH != 1 || d.KW != 1 || d.stride != 1 || d.pad_top != 0 || d.pad_left != 0) return GPP_ERR_UNSUPPORTED;
+    if (d.x3_split & GPP_X3_IN) return GPP_ERR_UNSUPPORTED;
+    if (d.C_in > 4096) return GPP_ERR_UNSUPPORTED;               // the scale / shift table lives in LDS beside the ring
+    return GPP_OK;
+}
+
+int preact_run(gpp_conv_desc& d, const float* in_scale, const float* in_shift, hipStream_t st)
+{
+    int rc = fill_range_counter(d);
+    if (rc != GPP_OK) return rc;
+    if (d.split_k == 0) d.split_k = split_rule(d);
+    switch (d.dtype) {
+        case GPP_BF16X3: return gpp_preact_dispatch_bf16x3(d, in_scale, in_shift, st);
+        case GPP_F16X3: return gpp_preact_dispatch_f16x3(d, in_scale, in_shift, st);
+        default: return gpp_preact_dispatch_f32(d, in_scale, in_shift, st);
+    }
+}
+
+}  // namespace
+
+extern "C" int gpp_conv2d_preact(const gpp_conv_desc* host_desc, const float* in_scale, const float* in_shift, void* stream)
+{
+    if (!host_desc) return GPP_ERR_BAD_ARG;
+    gpp_conv_desc d = *host_desc;
+    const int rc = preact_validate(d, in_scale, in_shift);
+    if (rc != GPP_OK) return rc;
+    return preact_run(d, in_scale, in_shift, (hipStream_t)stream);
+}
+
+extern "C" int gpp_conv2d_preact_tile_candidates(const gpp_conv_desc* desc, int* tiles, int capacity, int* count)
+{
+    if (!desc || !count || capacity < 0 || (capacity > 0 && !tiles)) return GPP_ERR_BAD_ARG;
+    gpp_conv_desc d = *desc;
+    static const float probe[4] __attribute__((aligned(16))) = {0.f, 0.f, 0.f, 0.f};     // (the tables are not read here)
+    const int rc = preact_validate(d, probe, probe);
+    if (rc != GPP_OK) return rc;
+    int n = 0;
+    for (int tile : kPreactTiles) {
+        if (n < capacity) tiles[n] = tile;
+        ++n;
+    }
+    *count = n;
+    return GPP_OK;
+}
+
+extern "C" int gpp_conv2d_preact_autotune(gpp_conv_desc* desc, const float* in_scale, const float* in_shift, int iters, void* stream,
+                                          float* best_us)
+{
+    if (!desc || iters < 1) return GPP_ERR_BAD_ARG;
+    {
+        gpp_conv_desc d = *desc;
+        const int rc = preact_validate(d, in_scale, in_shift);
+        if (rc != GPP_OK) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipEvent_t e0, e1;
+    hipError_t e = hipEventCreate(&e0);
+    if (e != hipSuccess) return (int)e;
+    e = hipEventCreate(&e1);
+    if (e != hipSuccess) { (void)hipEventDestroy(e0); return (int)e; }
+    const int tile_in = desc->tile_hint;
+    float best = 1e30f;
+    int best_tile = tile_in, rc = GPP_OK;
+    for (int tile : kPreactTiles) {
+        desc->tile_hint = tile;
+        int r = gpp_conv2d_preact(desc, in_scale, in_shift, stream);      // warm-up (and validity of this choice)
+        if (r != GPP_OK) { if (tile == 0) { rc = r; break; } continue; }
+        float t_best = 1e30f;
+        for (int rep = 0; rep < 2 && r == GPP_OK; ++rep) {
+            (void)hipEventRecord(e0, st);
+            for (int i = 0; i < iters; ++i) (void)gpp_conv2d_preact(desc, in_scale, in_shift, stream);
+            (void)hipEventRecord(e1, st);
+            const hipError_t s = hipEventSynchronize(e1);
+            if (s != hipSuccess) { r = (int)s; break; }
+            float ms = 0.0f;
+            (void)hipEventElapsedTime(&ms, e0, e1);
+            t_best = ms < t_best ? ms : t_best;
+        }
+        if (r != GPP_OK) { rc = r; break; }
+        const float us = t_best * 1000.0f / iters;
+        if (us < best) { best = us; best_tile = tile; }
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    desc->tile_hint = rc == GPP_OK ? best_tile : tile_in;
+    if (best_us) *best_us = best;
+    return rc;
+}

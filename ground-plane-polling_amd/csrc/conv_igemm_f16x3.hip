@@ -8,6 +8,11 @@ __device__ unsigned long long g_x3_range_events = 0;
 
 int gpp_conv_dispatch_f16x3(gpp_conv_desc& d, hipStream_t st) { return dispatch<GPP_F16X3>(d, st); }
 
+int gpp_preact_dispatch_f16x3(gpp_conv_desc& d, const float* in_scale, const float* in_shift, hipStream_t st)
+{
+    return dispatch_preact<GPP_F16X3>(d, in_scale, in_shift, st);
+}
+
 int gpp_tail_dispatch_f16x3(gpp_conv_desc& d1, gpp_conv_desc& d2, int tile_rows, hipStream_t st)
 {
     return dispatch_tail_x3<GPP_F16X3>(d1, d2, tile_rows, st);

@@ -3,3 +3,8 @@
 #include "conv_igemm_types.h"
 
 int gpp_conv_dispatch_f32(gpp_conv_desc& d, hipStream_t st) { return dispatch<GPP_F32>(d, st); }
+
+int gpp_preact_dispatch_f32(gpp_conv_desc& d, const float* in_scale, const float* in_shift, hipStream_t st)
+{
+    return dispatch_preact<GPP_F32>(d, in_scale, in_shift, st);
+}

@@ -464,10 +464,16 @@ constexpr int stage_rows(int BM, int NW) { return (BM + 8 * NW - 1) / (8 * NW) *
 
 // XIN (GPP_BF16X3 only): the input map is pre-split (gpp_conv_desc.x3_split & GPP_X3_IN) -- a compile-time property of the kernel, so
 // that the loop of either form carries no trace of the other (the 256 x 256 tile has no registers to spare for both)
-template <int DT, int BM, int BN, int WM, int WN, int STAGES, bool PIPE, bool XIN = false>
-__device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const int block_x, const int grid_x)
+// PRE (gpp_conv2d_preact: 1 x 1, stride 1, float32-sized input maps that are not pre-split, plain loop): every activation is replaced by
+// max(x * pre_s[c] + pre_t[c], 0) where its fragment leaves LDS -- the BatchNormalization + ReLU of a DenseNet layer that belongs to the
+// CONSUMER of a concatenation (it cannot be folded into any producer).  The two per-channel tables are copied to LDS behind the ring
+// (2 * C_in float32) before the first tile load; the K order, and so every bit of the result, is that of the plain loop.
+template <int DT, int BM, int BN, int WM, int WN, int STAGES, bool PIPE, bool XIN = false, bool PRE = false>
+__device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const int block_x, const int grid_x, const float* pre_s = nullptr,
+                                                const float* pre_t = nullptr)
 {
     static_assert(!XIN || kX3<DT>, "pre-split input maps: GPP_BF16X3 / GPP_F16X3");
+    static_assert(!PRE || (!PIPE && !XIN && kF32Storage<DT>), "pre-activation: float32-sized input maps, plain loop");
     using E = Elem<DT>;
     using vec8 = typename E::vec8;
     using frag = typename E::frag;
@@ -697,6 +703,20 @@ __device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const in
         if (pad == -12345) acc[0][0][0] = 1.0f;
     }
 #endif
+    // PRE: scale at [0, C_in), shift at [C_in, 2 C_in) of the table behind the ring (visible after the first K-step's barrier)
+    const float* pre_tab = (const float*)(smem + STAGES * STAGE);
+    if constexpr (PRE) {
+        float* tab = (float*)(smem + STAGES * STAGE);
+        for (int c = tid; c < d.C_in; c += 64 * NW) {
+            tab[c] = pre_s[c];
+            tab[d.C_in + c] = pre_t[c];
+        }
+    }
+    auto preact = [&](f32x4 x, const f32x4 s, const f32x4 t) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) x[e] = fmaxf(__builtin_fmaf(x[e], s[e], t[e]), 0.0f);
+        return x;
+    };
     GPP_STAMP(1);
     // ---- main loop.  Ring of STAGES buffers, PF = STAGES-1 K-steps of LDS-DMA in flight; one raw
     // s_barrier per K-step.  At the top of step ks a counted vmcnt retires this wave's loads of
@@ -1067,6 +1087,15 @@ __device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const in
                         ah[i] = *(const xh8*)(sbase + a_rd[0] + i * 16 * kRowBytes);
                         al[i] = *(const xh8*)(sbase + a_rd[1] + i * 16 * kRowBytes);
                     }
+                } else if constexpr (PRE) {
+                    // this lane's 8 K values are channels 8 fq .. 8 fq + 7 of the K-step (1 x 1: K-step = channel chunk)
+                    const int c0 = (ks0 + ks) * CK + 8 * fq;
+                    const f32x4 s0 = *(const f32x4*)(pre_tab + c0), s1 = *(const f32x4*)(pre_tab + c0 + 4);
+                    const f32x4 t0 = *(const f32x4*)(pre_tab + d.C_in + c0), t1 = *(const f32x4*)(pre_tab + d.C_in + c0 + 4);
+#pragma unroll
+                    for (int i = 0; i < MF; ++i)
+                        Elem<DT>::split(preact(*(const f32x4*)(sbase + a_rdx[0] + i * 16 * kRowBytes), s0, t0),
+                                        preact(*(const f32x4*)(sbase + a_rdx[1] + i * 16 * kRowBytes), s1, t1), ah[i], al[i]);
                 } else {
 #pragma unroll
                     for (int i = 0; i < MF; ++i)
@@ -1097,6 +1126,13 @@ __device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const in
                 for (int kk = 0; kk < 2; ++kk) {
                     frag af[MF], bfr[NF];
                     load_frags(af, bfr, cbuf, kk);
+                    if constexpr (PRE) {
+                        // GPP_F32: a fragment is channels 16 kk + 4 fq .. + 3 of the K-step
+                        const int c0 = (ks0 + ks) * CK + 16 * kk + 4 * fq;
+                        const f32x4 s = *(const f32x4*)(pre_tab + c0), t = *(const f32x4*)(pre_tab + d.C_in + c0);
+#pragma unroll
+                        for (int i = 0; i < MF; ++i) af[i] = preact(af[i], s, t);
+                    }
                     mfma_all(af, bfr);
                 }
             }
@@ -1225,6 +1261,14 @@ template <int DT, int BM, int BN, int WM, int WN, int STAGES, bool PIPE, bool XI
 __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_kernel(const gpp_conv_desc d)
 {
     conv_igemm_body<DT, BM, BN, WM, WN, STAGES, PIPE, XIN>(d, blockIdx.x, gridDim.x);
+}
+
+// gpp_conv2d_preact: the plain loop with the pre-activation prologue (PRE above); kernels of their own, so that conv_igemm_kernel and its
+// instantiations stay exactly what they are
+template <int DT, int BM, int BN, int WM, int WN>
+__global__ __launch_bounds__(64 * WM * WN, 2) void conv_preact_kernel(const gpp_conv_desc d, const float* in_scale, const float* in_shift)
+{
+    conv_igemm_body<DT, BM, BN, WM, WN, 2, false, false, true>(d, blockIdx.x, gridDim.x, in_scale, in_shift);
 }
 
 // A layer whose C_out is an odd multiple of 128 (the fused tower inputs: 896 = 3 x 256 + 128) in ONE grid of two tile
@@ -2207,6 +2251,57 @@ int launch(gpp_conv_desc& d, hipStream_t st)
     }
     hipError_t e = hipGetLastError();
     return e == hipSuccess ? GPP_OK : (int)e;
+}
+
+// gpp_conv2d_preact: one tile configuration of the pre-activation form (two-buffer ring + the 2 * C_in float32 scale / shift table)
+template <int DT, int BM, int BN, int WM, int WN>
+int launch_preact(gpp_conv_desc& d, const float* in_scale, const float* in_shift, hipStream_t st)
+{
+    constexpr int BMS = stage_rows(BM, WM * WN);
+    constexpr int ring = 2 * (BMS + BN) * kRowBytes;
+    constexpr int CK = kRowBytes / Elem<DT>::ESZ;
+    constexpr int kMaxLds = 160 * 1024;
+    const int lds = ring + 2 * d.C_in * 4;
+    if (lds > kMaxLds) return GPP_ERR_UNSUPPORTED;
+    static DeviceOnce once;
+    auto kernel = conv_preact_kernel<DT, BM, BN, WM, WN>;
+    int rc = once.configure(kernel, kMaxLds);
+    if (rc != GPP_OK) return rc;
+    const int tiles = prepare<BM, BN>(d);
+    if (tiles < 0) return tiles;
+    const int n_tiles = (d.C_out + BN - 1) / BN;
+    const int nk = d.C_in / CK;
+    int nsplit = 1;
+    if (d.split_k > 1) {
+        nsplit = d.split_k;
+        if (nk / nsplit < 1) return GPP_ERR_BAD_ARG;
+        const int64_t slab = (int64_t)tiles * BM * n_tiles * BN * 4;
+        if (!d.partial || slab * nsplit > (int64_t)d.partial_bytes) return GPP_ERR_WORKSPACE;
+    }
+    kernel<<<dim3((unsigned)(tiles * n_tiles), (unsigned)nsplit), dim3(64 * WM * WN), lds, st>>>(d, in_scale, in_shift);
+    if (nsplit > 1) {
+        const int64_t total = (int64_t)d.partial_rows * ((d.C_out + 7) / 8);
+        splitk_reduce_kernel<DT><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(d, BM, n_tiles * BN, nsplit);
+    }
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? GPP_OK : (int)e;
+}
+
+// the tiles of the pre-activation form (gpp_conv2d_preact_tile_candidates lists the same codes); 0 = 128 x 128, or 128 x 64 for
+// C_out <= 64
+template <int DT>
+int dispatch_preact(gpp_conv_desc& d, const float* in_scale, const float* in_shift, hipStream_t st)
+{
+    switch (d.tile_hint) {
+        case 0: return d.C_out <= 64 ? launch_preact<DT, 128, 64, 2, 2>(d, in_scale, in_shift, st)
+                                     : launch_preact<DT, 128, 128, 2, 2>(d, in_scale, in_shift, st);
+        case 64064: return launch_preact<DT, 64, 64, 2, 2>(d, in_scale, in_shift, st);
+        case 128064: return launch_preact<DT, 128, 64, 2, 2>(d, in_scale, in_shift, st);
+        case 64128: return launch_preact<DT, 64, 128, 2, 2>(d, in_scale, in_shift, st);
+        case 128128: return launch_preact<DT, 128, 128, 2, 2>(d, in_scale, in_shift, st);
+        case 192128: return launch_preact<DT, 192, 128, 2, 2>(d, in_scale, in_shift, st);
+        default: return GPP_ERR_BAD_ARG;
+    }
 }
 
 // conv_igemm_dual_kernel: C_out = 256 k + 128.  The caller's descriptor is split into the two column blocks here.

@@ -193,6 +193,21 @@ extern "C" int gpp_plan_run(const gpp_plan_op* ops, int n_ops, void* stream, voi
             rc = gpp_bottleneck_block(d->conv1x1_a, d->conv3x3_b, d->conv1x1_c, d->tile, stream);
             break;
         }
+        case GPP_OP_CONV_PREACT: {
+            const gpp_preact_desc* d = (const gpp_preact_desc*)op.desc;
+            rc = gpp_conv2d_preact(d->conv, d->in_scale, d->in_shift, stream);
+            break;
+        }
+        case GPP_OP_MAXPOOL_PAD: {
+            const gpp_dense_pool_desc* d = (const gpp_dense_pool_desc*)op.desc;
+            rc = gpp_maxpool3x3s2_pad_f32(d->in, d->out, d->B, d->H, d->W, d->C, d->pad, d->out_pitch, stream);
+            break;
+        }
+        case GPP_OP_AVGPOOL: {
+            const gpp_dense_pool_desc* d = (const gpp_dense_pool_desc*)op.desc;
+            rc = gpp_avgpool2x2_f32(d->in, d->out, d->B, d->H, d->W, d->C, d->out_pitch, stream);
+            break;
+        }
         case GPP_OP_RELU: {
             const gpp_relu_desc* d = (const gpp_relu_desc*)op.desc;
             rc = gpp_relu_strided(d->in, d->in_bstride, d->out, d->out_bstride, d->dtype, d->B, d->count, stream);

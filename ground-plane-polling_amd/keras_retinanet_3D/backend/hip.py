@@ -95,6 +95,17 @@ def _declare(lib):
     lib.gpp_stem_pool_fused_mfma.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
     lib.gpp_maxpool3x3s2_same.restype = c_int
     lib.gpp_maxpool3x3s2_same.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]
+    # DenseNet (include/gpp.h): the pre-activation 1x1 conv and the two pools that write into a channel slice
+    lib.gpp_conv2d_preact.restype = c_int
+    lib.gpp_conv2d_preact.argtypes = [ctypes.POINTER(ConvDesc), c_void_p, c_void_p, c_void_p]
+    lib.gpp_conv2d_preact_tile_candidates.restype = c_int
+    lib.gpp_conv2d_preact_tile_candidates.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_int)]
+    lib.gpp_conv2d_preact_autotune.restype = c_int
+    lib.gpp_conv2d_preact_autotune.argtypes = [ctypes.POINTER(ConvDesc), c_void_p, c_void_p, c_int, c_void_p, ctypes.POINTER(c_float)]
+    lib.gpp_maxpool3x3s2_pad_f32.restype = c_int
+    lib.gpp_maxpool3x3s2_pad_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
+    lib.gpp_avgpool2x2_f32.restype = c_int
+    lib.gpp_avgpool2x2_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]
     lib.gpp_relu.restype = c_int
     lib.gpp_relu.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_void_p]
     lib.gpp_preprocess_u8_bgr.restype = c_int

@@ -38,6 +38,8 @@ def backbone(backbone_name):
     """ Returns a backbone object for the given backbone (reference models/__init__.py:42-56). """
     if 'resnet' in backbone_name:
         from .resnet import ResNetBackbone as b
+    elif 'densenet' in backbone_name:
+        from .densenet import DenseNetBackbone as b
     else:
         raise NotImplementedError('Backbone class for  \'{}\' not implemented.'.format(backbone_name))
     return b(backbone_name)
@@ -49,6 +51,8 @@ def load_model(filepath, backbone_name='resnet50', convert=False, nms=True, clas
 
     `convert` is accepted for signature compatibility: every model this function returns already
     contains the decode / NMS / ground-plane-polling stages (`retinanet_bbox`, retinanet.py:359-422).
+    `backbone_name`: 'resnet50' | 'resnet101' | 'resnet152' | 'densenet121' | 'densenet169' | 'densenet201' (DenseNet: dtype 'f32',
+    'f16x3' or 'bf16x3' only).
     `dtype` (not in the reference; None = the environment's GPP_DTYPE, else 'f16x3'):
         'f16x3' (default)  float32-sized storage, every float32 product as three IEEE-half matrix products: the fastest type whose
                            detections, plane indices and 3-D corners stay within BASELINE's tolerance of the float32 path

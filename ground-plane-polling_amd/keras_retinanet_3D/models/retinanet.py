@@ -72,6 +72,15 @@ class PollDesc(ctypes.Structure):
                 ('planes_batched', ctypes.c_int32), ('thr', ctypes.c_float), ('reserved', ctypes.c_int32)]
 
 
+class PreactDesc(ctypes.Structure):
+    _fields_ = [('conv', ctypes.c_void_p), ('in_scale', ctypes.c_void_p), ('in_shift', ctypes.c_void_p)]
+
+
+class DensePoolDesc(ctypes.Structure):
+    _fields_ = [('inp', ctypes.c_void_p), ('out', ctypes.c_void_p), ('B', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32),
+                ('C', ctypes.c_int32), ('pad', ctypes.c_int32), ('out_pitch', ctypes.c_int32)]
+
+
 class PlanOp(ctypes.Structure):
     _fields_ = [('kind', ctypes.c_int32), ('tag', ctypes.c_int32), ('desc', ctypes.c_void_p)]
 
@@ -89,6 +98,7 @@ OP_BLOCK = 16
 OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT = 8, 9, 10
 OP_DETECT_OSF = 12
 OP_STEM_POOL = 13
+OP_MAXPOOL_PAD, OP_AVGPOOL, OP_CONV_PREACT = 17, 18, 32         # DenseNet (include/gpp.h)
 DETECT_OPS = (OP_DETECT, OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT, 12)
 OP_JOIN, OP_SYNC = 0x10000, 0x20000
 
@@ -173,13 +183,13 @@ class Plan(object):
     @staticmethod
     def stage_of(kind, name):
         """ include/gpp.h GPP_OP_STAGE: 1 stem, 2 backbone, 3 FPN, 4 heads, 5 decode, 6 polling (roctx ranges under GPP_ROCTX=1) """
-        if kind in (OP_STEM, OP_MAXPOOL, OP_STEM_POOL):
+        if kind in (OP_STEM, OP_MAXPOOL, OP_STEM_POOL, OP_MAXPOOL_PAD):
             return 1
         if kind in DETECT_OPS:
             return 5
         if kind == OP_POLL:
             return 6
-        if name.startswith('res'):
+        if name.startswith('res') or kind in (OP_CONV_PREACT, OP_AVGPOOL) or name.startswith(('conv2_', 'conv3_', 'conv4_', 'conv5_')):
             return 2
         if name.startswith('pyramid_'):
             return 4
@@ -193,7 +203,7 @@ class Plan(object):
 
 
 class RetinaNet3D(object):
-    """ Inference model: ResNet-50/101/152 + FPN + heads + decode + ground-plane polling. """
+    """ Inference model: ResNet-50/101/152 or DenseNet-121/169/201 + FPN + heads + decode + ground-plane polling. """
 
     def __init__(self, weights, backbone_name='resnet50', dtype='f16x3', nms=True, class_specific_filter=True,
                  orientation_specific_filter=False, name='retinanet-bbox', on_range_event=None, plan=None):
@@ -220,10 +230,14 @@ class RetinaNet3D(object):
         self.nms = bool(nms)
         self.name = name
         self.backbone_name = backbone_name.split('_')[0]
-        if self.backbone_name not in W.BLOCKS:
-            raise ValueError('Backbone (\'{}\') not in allowed backbones ({}).'.format(backbone_name, sorted(W.BLOCKS)))
+        self.densenet = W.is_densenet(self.backbone_name)
+        if self.backbone_name not in W.BLOCKS and not self.densenet:
+            raise ValueError('Backbone (\'{}\') not in allowed backbones ({}).'.format(backbone_name, sorted(W.BLOCKS) + sorted(W.DENSENET_BLOCKS)))
         if dtype not in ('bf16', 'f16', 'f32', 'bf16x3', 'f16x3'):
             raise ValueError("dtype must be 'bf16', 'f16', 'f32', 'bf16x3' or 'f16x3', got {!r}".format(dtype))
+        if self.densenet and dtype not in ('f32', 'f16x3', 'bf16x3'):
+            # the concatenation buffers and the pre-activation 1x1 conv (gpp_conv2d_preact) exist for float32 storage only
+            raise ValueError("a DenseNet backbone runs with dtype 'f32', 'f16x3' or 'bf16x3', got {!r}".format(dtype))
         self.dtype = dtype
         self.esz = C.elem_size(dtype)
         self.tdtype = C.torch_dtype(dtype)
@@ -250,7 +264,9 @@ class RetinaNet3D(object):
             if self.dtype == 'f16x3':        # the inverse of the per-channel power of two the packed weights carry (layers/conv.py)
                 self.conv_scale[name] = C.out_scale_of(kernel, dev)
 
-        for conv, bn, kh, kw, cin, cout, _ in W.backbone_layers(self.backbone_name):
+        if self.densenet:
+            self._upload_densenet(weights, put)
+        for conv, bn, kh, kw, cin, cout, _ in (() if self.densenet else W.backbone_layers(self.backbone_name)):
             k, b = W.folded_conv(weights, conv, bn)
             if k.shape != (kh, kw, cin, cout):
                 raise ValueError('weight {} has shape {}, expected {}'.format(conv, k.shape, (kh, kw, cin, cout)))
@@ -266,7 +282,7 @@ class RetinaNet3D(object):
                 self.stem_b = torch.as_tensor(b).to(dev).contiguous()
             else:
                 put(conv, k, b)
-        for name, k_, cin, cout, _ in W.fpn_layers():
+        for name, k_, cin, cout, _ in W.fpn_layers(self.backbone_name):
             k, b = W.folded_conv(weights, name)
             put(name, k, b)
         for name, cin, cout, kind in W.head_layers():
@@ -279,11 +295,43 @@ class RetinaNet3D(object):
         k, b = W.fused_tower_inputs(weights)
         put('pyramid_towers_0', k, b)
 
+    def _upload_densenet(self, weights, put):
+        """ DenseNet: conv1/conv with conv1/bn folded (the stem kernels), every _1_conv with its _1_bn folded (+ ReLU epilogue), _2_conv and
+        the transition convs as they are (no bias), and the BatchNormalization in front of every 1x1 conv as a (scale, shift) pair for the
+        prologue of gpp_conv2d_preact: it belongs to the consumer of a concatenation and cannot be folded into any producer """
+        torch, dev, eps = self.torch, self.device, W.DENSENET_BN_EPSILON
+        self.preact = {}
+        k, b = W.folded_conv(weights, 'conv1/conv', 'conv1/bn', eps=eps)
+        if self.dtype in C.X3_TYPES and os.environ.get('GPP_X3_STEM', 'mfma') != 'valu':
+            self.stem_w = hip.pack_stem_weights_x3(k.reshape(147, 64), dev)
+            self.stem_x3 = True
+        else:
+            self.stem_w = torch.as_tensor(np.ascontiguousarray(k.reshape(147, 64), dtype=np.float32)).to(dev).contiguous()
+        self.stem_b = torch.as_tensor(b).to(dev).contiguous()
+        pending = None
+        for kind, name, shape in W.densenet_layers(self.backbone_name):
+            if kind == 'bn':
+                if name.endswith('_0_bn') or (name.startswith('pool') and name.endswith('_bn')):
+                    pending = name
+                continue
+            if name == 'conv1/conv':
+                continue
+            if name.endswith('_1_conv'):
+                k, b = W.folded_conv(weights, name, name[:-len('_1_conv')] + '_1_bn', eps=eps)
+            else:
+                k, b = np.asarray(weights[name + '/kernel'], dtype=np.float32), np.zeros((shape[3],), np.float32)
+            put(name, k, b)
+            if shape[0] == 1:                   # the 1x1 convs: _1_conv and the transitions, behind the BN + ReLU just seen
+                s, t = W.bn_affine(weights, pending, eps)
+                self.preact[name] = (torch.as_tensor(s).to(dev).contiguous(), torch.as_tensor(t).to(dev).contiguous())
+
     # ------------------------------------------------------------------ plan
-    def _anchor_table(self, hw):
-        if hw not in self._anchors:
-            self._anchors[hw] = self.torch.as_tensor(anchor_utils.anchors_for_image(hw)).to(self.device).contiguous()
-        return self._anchors[hw]
+    def _anchor_table(self, hw, shapes=None):
+        key = hw if shapes is None else (hw, tuple(shapes))
+        if key not in self._anchors:
+            a = anchor_utils.anchors_for_image(hw) if shapes is None else anchor_utils.anchors_for_shapes(shapes)
+            self._anchors[key] = self.torch.as_tensor(a).to(self.device).contiguous()
+        return self._anchors[key]
 
     def _desc(self, plan, name, inputs, outputs, K, stride=1, pad=None, relu=False, residuals=None, out_f32=False, lane=0):
         wt, bias, shape = self.conv_w[name]
@@ -339,6 +387,64 @@ class RetinaNet3D(object):
         plan.io_parts.setdefault(name, []).append(([x], [y], [shortcut]))
         plan.touch(t, [Plan.span(x), Plan.span(shortcut)], [Plan.span(y)])
 
+    def _preact(self, plan, name, inputs, outputs, relu=False):
+        """ a 1x1 conv behind its input's BatchNormalization + ReLU (gpp_conv2d_preact): DenseNet's _1_conv and transition convs """
+        d = self._desc(plan, name, inputs, outputs, 1, relu=relu)
+        s, t = self.preact[name]
+        pd = PreactDesc(ctypes.addressof(d), s.data_ptr(), t.data_ptr())
+        plan.keep.append(d)
+        plan.preact_conv[id(pd)] = d
+        plan.op_batch[id(pd)] = inputs[0].B
+        plan.add(OP_CONV_PREACT, pd, name, flops=C.conv_flops(d))
+        plan.io[name] = (inputs, outputs, None)
+        plan.io_parts.setdefault(name, []).append((inputs, outputs, None))
+        plan.touch(pd, [Plan.span(f) for f in inputs], [Plan.span(f) for f in outputs])
+
+    def _densenet_backbone(self, plan, B, H, Wd, fmap, bmap):
+        """ conv1 .. conv5_block{N}_concat of keras' DenseNet (reference models/densenet.py:62-94) -> the four block concatenations.
+        One float32 buffer per dense block at its final width: the block input (pool1 / the transition's average pool) is written into
+        channels [0, C0), layer I's 32 channels into [C0 + 32 (I - 1), C0 + 32 I), and layer I's _1_conv reads the prefix [0, C0 + 32 (I - 1))
+        through in_pitch.  The 128-channel map between _1_conv and _2_conv is pre-split for the x3 types.  The whole batch on lane 0. """
+        widths = W.densenet_widths(self.backbone_name)
+        H1, W1 = (H + 6 - 7) // 2 + 1, (Wd + 6 - 7) // 2 + 1
+        stem = fmap(H1, W1, 64)
+        stem_x3 = getattr(self, 'stem_x3', False)
+        d = StemDesc(plan.images.data_ptr(), self.stem_w.data_ptr(), self.stem_b.data_ptr(), stem.buf.data_ptr(),
+                     hip.GPP_F16X3 if stem_x3 else hip.GPP_F32, B, H, Wd, plan.range_slot.data_ptr() if self.dtype == 'f16x3' else None)
+        plan.add(OP_STEM, d, 'conv1', flops=2.0 * B * H1 * W1 * 147 * 64)
+        plan.touch(d, [Plan.span_of(plan.images)], [Plan.span(stem)])
+        plan.stem_out = stem
+        h, w = (H1 - 1) // 2 + 1, (W1 - 1) // 2 + 1
+        cats = []
+        for stage in range(4):
+            cats.append(fmap(h, w, widths[stage]))
+            h, w = h // 2, w // 2
+        pd = DensePoolDesc(stem.buf.data_ptr(), cats[0].buf.data_ptr(), B, H1, W1, 64, 1, cats[0].pitch)
+        plan.add(OP_MAXPOOL_PAD, pd, 'pool1')
+        plan.touch(pd, [Plan.span(stem)], [Plan.span(C.FMap(cats[0].buf, B, cats[0].H, cats[0].W, 64, pitch=cats[0].pitch))])
+        plan.pool_out = cats[0]
+        c0 = 64
+        for stage, n in enumerate(W.DENSENET_BLOCKS[self.backbone_name]):
+            cat = cats[stage]
+            for i in range(1, n + 1):
+                nm = 'conv{}_block{}'.format(stage + 2, i)
+                cin = c0 + W.DENSENET_GROWTH * (i - 1)
+                mid = bmap(cat.H, cat.W, W.DENSENET_BOTTLENECK)
+                self._preact(plan, nm + '_1_conv', [C.FMap(cat.buf, B, cat.H, cat.W, cin, pitch=cat.pitch)], [mid], relu=True)
+                self._conv(plan, nm + '_2_conv', [mid], [C.FMap(cat.buf, B, cat.H, cat.W, W.DENSENET_GROWTH, off=cin, pitch=cat.pitch)], 3,
+                           pad=(1, 1))
+            if stage == 3:
+                break
+            nm = 'pool{}'.format(stage + 2)
+            t = fmap(cat.H, cat.W, widths[stage] // 2)
+            self._preact(plan, nm + '_conv', [cat], [t])
+            nxt = cats[stage + 1]
+            pd = DensePoolDesc(t.buf.data_ptr(), nxt.buf.data_ptr(), B, t.H, t.W, t.C, 0, nxt.pitch)
+            plan.add(OP_AVGPOOL, pd, nm + '_pool')
+            plan.touch(pd, [Plan.span(t)], [Plan.span(C.FMap(nxt.buf, B, nxt.H, nxt.W, t.C, pitch=nxt.pitch))])
+            c0 = t.C
+        return cats
+
     def _build(self, B, H, Wd, n_planes, planes_batched):
         torch, dev, dt = self.torch, self.device, self.tdtype
         plan = Plan()
@@ -353,6 +459,7 @@ class RetinaNet3D(object):
         half_stages = set(int(v) for v in os.environ.get('GPP_HALF_LANES', '0,1,2,3').split(',') if v.strip()) if B >= 2 else set()
         br1_lane = os.environ.get('GPP_BR1_LANE', '1') != '0'         # measured +0.4 % on the f16x3 step (same box, alternating)
         plan.conv_descs, plan.ws_need = [], {}
+        plan.preact_conv = {}        # id(gpp_preact_desc) -> its gpp_conv_desc (DenseNet)
         # dtype='f16x3': the 8-byte counter every launch of THIS plan adds its range events to (gpp_conv_desc.range_counter, gpp_stem_desc.range_counter),
         # never reset by anyone but x3_range_events(reset=True) of this model; range_seen = its value when a result of the plan was last fetched
         plan.range_slot = torch.zeros((1,), dtype=torch.int64, device=dev)
@@ -376,128 +483,133 @@ class RetinaNet3D(object):
         plan.P_inv = torch.empty((B, 4, 3), dtype=torch.float32, device=dev)
         plan.planes = torch.empty((B, n_planes, 4) if planes_batched else (n_planes, 4), dtype=torch.float32, device=dev)
 
-        # ---- stem: conv1 + bn_conv1 + relu, pool1
-        H1, W1 = (H + 6 - 7) // 2 + 1, (Wd + 6 - 7) // 2 + 1
-        H2, W2 = (H1 + 1) // 2, (W1 + 1) // 2
-        x = fmap(H2, W2, 64)
-        stem_x3 = getattr(self, 'stem_x3', False)
-        if (self.esz == 2 or stem_x3) and os.environ.get('GPP_FUSE_STEM_POOL', '1') != '0':
-            # conv1 + bn_conv1 + relu + pool1 in one launch, the (B, H1, W1, 64) conv map is never stored (bit-identical to the two launches:
-            # tests/test_stem_gpu.py).  16-bit types since round 2; the x3 types since round 6 (gpp_stem_pool_fused_x3: the float32 conv map was
-            # 274 MB written + read back at B = 8)
-            d = StemDesc(plan.images.data_ptr(), self.stem_w.data_ptr(), self.stem_b.data_ptr(), x.buf.data_ptr(),
-                         hip.GPP_F16X3 if stem_x3 else C.gpp_storage_dtype(self.dtype), B, H, Wd,
-                         plan.range_slot.data_ptr() if self.dtype == 'f16x3' else None)
-            plan.add(OP_STEM_POOL, d, 'conv1+pool1', flops=2.0 * B * H1 * W1 * 147 * 64)
-            plan.touch(d, [Plan.span_of(plan.images)], [Plan.span(x)])
-            plan.stem_out = None
+        lane_open = False
+        if self.densenet:
+            feats = self._densenet_backbone(plan, B, H, Wd, fmap, bmap)
         else:
-            stem = fmap(H1, W1, 64)
-            d = StemDesc(plan.images.data_ptr(), self.stem_w.data_ptr(), self.stem_b.data_ptr(), stem.buf.data_ptr(),
-                         hip.GPP_F16X3 if stem_x3 else C.gpp_storage_dtype(self.dtype), B, H, Wd,
-                         plan.range_slot.data_ptr() if self.dtype == 'f16x3' else None)
-            plan.add(OP_STEM, d, 'conv1', flops=2.0 * B * H1 * W1 * 147 * 64)
-            plan.touch(d, [Plan.span_of(plan.images)], [Plan.span(stem)])
-            plan.stem_out = stem
-            pool_d = PoolDesc(stem.buf.data_ptr(), x.buf.data_ptr(), C.gpp_storage_dtype(self.dtype), B, H1, W1, 64, 0)
-            plan.add(OP_MAXPOOL, pool_d, 'pool1')
-            plan.touch(pool_d, [Plan.span(stem)], [Plan.span(x)])
-        plan.pool_out = x
+            # ---- stem: conv1 + bn_conv1 + relu, pool1
+            H1, W1 = (H + 6 - 7) // 2 + 1, (Wd + 6 - 7) // 2 + 1
+            H2, W2 = (H1 + 1) // 2, (W1 + 1) // 2
+            x = fmap(H2, W2, 64)
+            stem_x3 = getattr(self, 'stem_x3', False)
+            if (self.esz == 2 or stem_x3) and os.environ.get('GPP_FUSE_STEM_POOL', '1') != '0':
+                # conv1 + bn_conv1 + relu + pool1 in one launch, the (B, H1, W1, 64) conv map is never stored (bit-identical to the two launches:
+                # tests/test_stem_gpu.py).  16-bit types since round 2; the x3 types since round 6 (gpp_stem_pool_fused_x3: the float32 conv map was
+                # 274 MB written + read back at B = 8)
+                d = StemDesc(plan.images.data_ptr(), self.stem_w.data_ptr(), self.stem_b.data_ptr(), x.buf.data_ptr(),
+                             hip.GPP_F16X3 if stem_x3 else C.gpp_storage_dtype(self.dtype), B, H, Wd,
+                             plan.range_slot.data_ptr() if self.dtype == 'f16x3' else None)
+                plan.add(OP_STEM_POOL, d, 'conv1+pool1', flops=2.0 * B * H1 * W1 * 147 * 64)
+                plan.touch(d, [Plan.span_of(plan.images)], [Plan.span(x)])
+                plan.stem_out = None
+            else:
+                stem = fmap(H1, W1, 64)
+                d = StemDesc(plan.images.data_ptr(), self.stem_w.data_ptr(), self.stem_b.data_ptr(), stem.buf.data_ptr(),
+                             hip.GPP_F16X3 if stem_x3 else C.gpp_storage_dtype(self.dtype), B, H, Wd,
+                             plan.range_slot.data_ptr() if self.dtype == 'f16x3' else None)
+                plan.add(OP_STEM, d, 'conv1', flops=2.0 * B * H1 * W1 * 147 * 64)
+                plan.touch(d, [Plan.span_of(plan.images)], [Plan.span(stem)])
+                plan.stem_out = stem
+                pool_d = PoolDesc(stem.buf.data_ptr(), x.buf.data_ptr(), C.gpp_storage_dtype(self.dtype), B, H1, W1, 64, 0)
+                plan.add(OP_MAXPOOL, pool_d, 'pool1')
+                plan.touch(pool_d, [Plan.span(stem)], [Plan.span(x)])
+            plan.pool_out = x
 
-        # ---- bottleneck stages (keras_resnet bottleneck_2d: stride on the first 1x1).
-        # A stage can be run chunk of images by chunk of images (GPP_STAGE_CHUNKS="2,4,8,8") to keep a chunk's
-        # working set inside the 256 MiB Infinity Cache; measured on MI355X at B = 8 this LOSES 1-6 % (the smaller
-        # launches cost more than the on-die re-reads save), so the default is the whole batch per launch.
-        env_chunks = os.environ.get('GPP_STAGE_CHUNKS')
-        # widths whose branch2b + branch2c run as one launch (GPP_FUSE_TAIL=0 for none).  Measured at B = 8, same box,
-        # whole step: none 1553, res3 only 1562, res2 + res3 1571 images/s (in isolation the fused res2 launch is no
-        # faster than its two layers -- 122 us vs 36 + 80 -- but the step is: 69 MB less through HBM per block)
-        fuse_tail = [int(v) for v in os.environ.get('GPP_FUSE_TAIL', '64,128').split(',') if v.strip() and int(v) > 0]
-        if self.dtype in C.X3_TYPES:
-            # the x3 form of the fused tail (bottleneck_tail_x3_kernel): pre-split maps, C = 64 (res2) only -- at C = 128 its LDS
-            # footprint leaves one workgroup per CU
-            fuse_tail = [v for v in fuse_tail if v == 64] if x3_level >= 2 else []
-        elif self.esz == 4:
-            fuse_tail = []              # float32 operands: no fused tail
-        # widths whose IDENTITY blocks (branch2a + 2b + 2c + shortcut) run as one launch (gpp_bottleneck_block; x3 types on pre-split maps): res2 (C = 64:
-        # 4-wavefront workgroups, two per CU; x in once, y out once: 245 -> 212 us per block at B = 8) and res3 (C = 128: 8 wavefronts, one per CU;
-        # at parity with its three launches in isolation, half their fabric bytes).  Same-box A/B of the step (profiles/r6/ab_fuse_block_*.txt):
-        # B = 8: 780 -> 793 images/s (+1.7 %) with both, +0.9 % with res2 alone; B = 4 +1.2 %, B = 2 +0.7 %, batch-1 plan 2.67 -> 2.65 ms.
-        # GPP_FUSE_BLOCK="" for the separate launches (bit-identical either way).  Projection blocks (GPP_FUSE_BLOCK_PROJ=1) measured -0.6 %: off.
-        fuse_block = [int(v) for v in os.environ.get('GPP_FUSE_BLOCK', '64,128').split(',') if v.strip()] if (self.dtype in C.X3_TYPES and x3_level >= 2) else []
-        fuse_block_proj = os.environ.get('GPP_FUSE_BLOCK_PROJ', '0') != '0'      # block 0 of a stage too (its shortcut is the projection launch's map)
+            # ---- bottleneck stages (keras_resnet bottleneck_2d: stride on the first 1x1).
+            # A stage can be run chunk of images by chunk of images (GPP_STAGE_CHUNKS="2,4,8,8") to keep a chunk's
+            # working set inside the 256 MiB Infinity Cache; measured on MI355X at B = 8 this LOSES 1-6 % (the smaller
+            # launches cost more than the on-die re-reads save), so the default is the whole batch per launch.
+            env_chunks = os.environ.get('GPP_STAGE_CHUNKS')
+            # widths whose branch2b + branch2c run as one launch (GPP_FUSE_TAIL=0 for none).  Measured at B = 8, same box,
+            # whole step: none 1553, res3 only 1562, res2 + res3 1571 images/s (in isolation the fused res2 launch is no
+            # faster than its two layers -- 122 us vs 36 + 80 -- but the step is: 69 MB less through HBM per block)
+            fuse_tail = [int(v) for v in os.environ.get('GPP_FUSE_TAIL', '64,128').split(',') if v.strip() and int(v) > 0]
+            if self.dtype in C.X3_TYPES:
+                # the x3 form of the fused tail (bottleneck_tail_x3_kernel): pre-split maps, C = 64 (res2) only -- at C = 128 its LDS
+                # footprint leaves one workgroup per CU
+                fuse_tail = [v for v in fuse_tail if v == 64] if x3_level >= 2 else []
+            elif self.esz == 4:
+                fuse_tail = []              # float32 operands: no fused tail
+            # widths whose IDENTITY blocks (branch2a + 2b + 2c + shortcut) run as one launch (gpp_bottleneck_block; x3 types on pre-split maps): res2 (C = 64:
+            # 4-wavefront workgroups, two per CU; x in once, y out once: 245 -> 212 us per block at B = 8) and res3 (C = 128: 8 wavefronts, one per CU;
+            # at parity with its three launches in isolation, half their fabric bytes).  Same-box A/B of the step (profiles/r6/ab_fuse_block_*.txt):
+            # B = 8: 780 -> 793 images/s (+1.7 %) with both, +0.9 % with res2 alone; B = 4 +1.2 %, B = 2 +0.7 %, batch-1 plan 2.67 -> 2.65 ms.
+            # GPP_FUSE_BLOCK="" for the separate launches (bit-identical either way).  Projection blocks (GPP_FUSE_BLOCK_PROJ=1) measured -0.6 %: off.
+            fuse_block = [int(v) for v in os.environ.get('GPP_FUSE_BLOCK', '64,128').split(',') if v.strip()] if (self.dtype in C.X3_TYPES and x3_level >= 2) else []
+            fuse_block_proj = os.environ.get('GPP_FUSE_BLOCK_PROJ', '0') != '0'      # block 0 of a stage too (its shortcut is the projection launch's map)
 
-        def sub(fm, c0, nb):
-            return C.FMap(fm.buf, nb, fm.H, fm.W, fm.C, off=fm.off + c0 * fm.bstride, bstride=fm.bstride, pitch=fm.pitch, split=fm.split, half=fm.half)
+            def sub(fm, c0, nb):
+                return C.FMap(fm.buf, nb, fm.H, fm.W, fm.C, off=fm.off + c0 * fm.bstride, bstride=fm.bstride, pitch=fm.pitch, split=fm.split, half=fm.half)
 
-        feats = []
-        lane_open = False            # a stage that ran as two half batches leaves its second half on side lane 1: whatever reads the whole
-        #                              batch next (a stage that is NOT split, or the FPN) has to join it first
-        for stage, n_blocks in enumerate(W.BLOCKS[self.backbone_name]):
-            f = 64 * 2 ** stage
-            blocks = []
-            xin = x
-            for block in range(n_blocks):
-                nm = W.block_name(self.backbone_name, stage, block)
-                stride = 2 if (block == 0 and stage > 0) else 1
-                ho, wo = (x.H - 1) // stride + 1, (x.W - 1) // stride + 1
-                fused = f in fuse_tail and f in (64, 128)
-                rec = {'nm': nm, 'stride': stride, 'a': bmap(ho, wo, f), 'b': None if fused else bmap(ho, wo, f),
-                       'sc': bmap(ho, wo, 4 * f) if block == 0 else None, 'y': bmap(ho, wo, 4 * f)}
-                blocks.append(rec)
-                x = rec['y']
-            chunk = max(1, min(B, int(env_chunks.split(',')[stage]))) if env_chunks else B
-            # GPP_HALF_LANES (default "0,1,2,3" = res2 .. res5): the stage as two half batches, the second half on a side stream beside
-            # the first.  A launch of these stages fills the 256 CUs 0.7 - 1.4 times and is bound by tile fills and first-touch latency;
-            # two independent chains in flight overlap one's prologue / epilogue / barrier waits with the other's main loop (f16x3 step,
-            # same box, alternating: 775 -> 793 images/s).  An image's result does not depend on its batch (section 4.4): same bytes.
-            # The halves stay apart until the FPN's first layer joins them; the per-block shortcut stream is not used inside them.
-            halves = stage in half_stages and B >= 2 and chunk >= B       # (a stage that is chunked runs its chunks one after the other)
-            # (three parts on three streams, measured: 801 against 811 images/s for two)
-            parts = [(B // 2, B - B // 2, 1), (0, B // 2, 0)] if halves else [(c0, min(chunk, B - c0), 0) for c0 in range(0, B, chunk)]
-            xs_of = {c0: sub(xin, c0, nb) for c0, nb, _ in parts}
-            for rec, (c0, nb, ln) in ([(r, p) for r in blocks for p in parts] if halves else [(r, p) for p in parts for r in blocks]):
-                    xs = xs_of[c0]
-                    nm, stride = rec['nm'], rec['stride']
-                    a_, y_ = sub(rec['a'], c0, nb), sub(rec['y'], c0, nb)
-                    # the projection shortcut of a stage's first block is independent of branch2a / 2b: on a side stream it runs beside them
-                    # and branch2c (or the fused tail) joins it (GPP_BR1_LANE=0: serial, behind branch2a)
-                    join_halves = lane_open and not halves       # first launch of a whole-batch stage behind a split one
-                    side = br1_lane and rec['sc'] is not None and not halves and not join_halves
-                    if side:
-                        sc_ = sub(rec['sc'], c0, nb)
-                        self._conv(plan, 'res{}_branch1'.format(nm), [xs], [sc_], 1, stride=stride, lane=1)
-                    rec['block'] = f in fuse_block and f in (64, 128) and (rec['sc'] is None or fuse_block_proj) and xs.split     # (res2a reads the pooled map, which is float32)
-                    b_or_a = sub(rec['b'], c0, nb) if rec['b'] is not None else a_       # (a stage with fused tails has no branch2b map: the descriptors borrow branch2a's -- neither is written)
-                    if rec['block'] and rec['sc'] is None:
-                        self._block(plan, nm, xs, a_, b_or_a, y_, xs, join=join_halves, lane=ln)
-                    elif not rec['block']:
-                        self._conv(plan, 'res{}_branch2a'.format(nm), [xs], [a_], 1, stride=stride, relu=True, lane=ln, join=join_halves)
-                    if rec['sc'] is not None and not side:
-                        sc_ = sub(rec['sc'], c0, nb)
-                        self._conv(plan, 'res{}_branch1'.format(nm), [xs], [sc_], 1, stride=stride, lane=ln, join=join_halves and rec['block'])
-                    elif rec['sc'] is None:
-                        sc_ = xs
-                    if join_halves:
-                        lane_open = False
-                    if rec['block'] and rec['sc'] is not None:           # a projection block: the shortcut map first (side lane or in line), then the whole block
-                        self._block(plan, nm, xs, a_, b_or_a, y_, sc_, stride=stride, join=side, lane=ln)
-                    if rec['block']:
-                        pass
-                    elif rec['b'] is None:
-                        self._tail(plan, nm, a_, y_, sc_, join=side, lane=ln)
-                    else:
-                        b_ = sub(rec['b'], c0, nb)
-                        self._conv(plan, 'res{}_branch2b'.format(nm), [a_], [b_], 3, pad=(1, 1), relu=True, lane=ln)
-                        self._conv(plan, 'res{}_branch2c'.format(nm), [b_], [y_], 1, relu=True, residuals=[sc_], join=side, lane=ln)
-                    xs_of[c0] = y_
-            lane_open = lane_open or halves
-            feats.append(x)
+            feats = []
+            lane_open = False            # a stage that ran as two half batches leaves its second half on side lane 1: whatever reads the whole
+            #                              batch next (a stage that is NOT split, or the FPN) has to join it first
+            for stage, n_blocks in enumerate(W.BLOCKS[self.backbone_name]):
+                f = 64 * 2 ** stage
+                blocks = []
+                xin = x
+                for block in range(n_blocks):
+                    nm = W.block_name(self.backbone_name, stage, block)
+                    stride = 2 if (block == 0 and stage > 0) else 1
+                    ho, wo = (x.H - 1) // stride + 1, (x.W - 1) // stride + 1
+                    fused = f in fuse_tail and f in (64, 128)
+                    rec = {'nm': nm, 'stride': stride, 'a': bmap(ho, wo, f), 'b': None if fused else bmap(ho, wo, f),
+                           'sc': bmap(ho, wo, 4 * f) if block == 0 else None, 'y': bmap(ho, wo, 4 * f)}
+                    blocks.append(rec)
+                    x = rec['y']
+                chunk = max(1, min(B, int(env_chunks.split(',')[stage]))) if env_chunks else B
+                # GPP_HALF_LANES (default "0,1,2,3" = res2 .. res5): the stage as two half batches, the second half on a side stream beside
+                # the first.  A launch of these stages fills the 256 CUs 0.7 - 1.4 times and is bound by tile fills and first-touch latency;
+                # two independent chains in flight overlap one's prologue / epilogue / barrier waits with the other's main loop (f16x3 step,
+                # same box, alternating: 775 -> 793 images/s).  An image's result does not depend on its batch (section 4.4): same bytes.
+                # The halves stay apart until the FPN's first layer joins them; the per-block shortcut stream is not used inside them.
+                halves = stage in half_stages and B >= 2 and chunk >= B       # (a stage that is chunked runs its chunks one after the other)
+                # (three parts on three streams, measured: 801 against 811 images/s for two)
+                parts = [(B // 2, B - B // 2, 1), (0, B // 2, 0)] if halves else [(c0, min(chunk, B - c0), 0) for c0 in range(0, B, chunk)]
+                xs_of = {c0: sub(xin, c0, nb) for c0, nb, _ in parts}
+                for rec, (c0, nb, ln) in ([(r, p) for r in blocks for p in parts] if halves else [(r, p) for p in parts for r in blocks]):
+                        xs = xs_of[c0]
+                        nm, stride = rec['nm'], rec['stride']
+                        a_, y_ = sub(rec['a'], c0, nb), sub(rec['y'], c0, nb)
+                        # the projection shortcut of a stage's first block is independent of branch2a / 2b: on a side stream it runs beside them
+                        # and branch2c (or the fused tail) joins it (GPP_BR1_LANE=0: serial, behind branch2a)
+                        join_halves = lane_open and not halves       # first launch of a whole-batch stage behind a split one
+                        side = br1_lane and rec['sc'] is not None and not halves and not join_halves
+                        if side:
+                            sc_ = sub(rec['sc'], c0, nb)
+                            self._conv(plan, 'res{}_branch1'.format(nm), [xs], [sc_], 1, stride=stride, lane=1)
+                        rec['block'] = f in fuse_block and f in (64, 128) and (rec['sc'] is None or fuse_block_proj) and xs.split     # (res2a reads the pooled map, which is float32)
+                        b_or_a = sub(rec['b'], c0, nb) if rec['b'] is not None else a_       # (a stage with fused tails has no branch2b map: the descriptors borrow branch2a's -- neither is written)
+                        if rec['block'] and rec['sc'] is None:
+                            self._block(plan, nm, xs, a_, b_or_a, y_, xs, join=join_halves, lane=ln)
+                        elif not rec['block']:
+                            self._conv(plan, 'res{}_branch2a'.format(nm), [xs], [a_], 1, stride=stride, relu=True, lane=ln, join=join_halves)
+                        if rec['sc'] is not None and not side:
+                            sc_ = sub(rec['sc'], c0, nb)
+                            self._conv(plan, 'res{}_branch1'.format(nm), [xs], [sc_], 1, stride=stride, lane=ln, join=join_halves and rec['block'])
+                        elif rec['sc'] is None:
+                            sc_ = xs
+                        if join_halves:
+                            lane_open = False
+                        if rec['block'] and rec['sc'] is not None:           # a projection block: the shortcut map first (side lane or in line), then the whole block
+                            self._block(plan, nm, xs, a_, b_or_a, y_, sc_, stride=stride, join=side, lane=ln)
+                        if rec['block']:
+                            pass
+                        elif rec['b'] is None:
+                            self._tail(plan, nm, a_, y_, sc_, join=side, lane=ln)
+                        else:
+                            b_ = sub(rec['b'], c0, nb)
+                            self._conv(plan, 'res{}_branch2b'.format(nm), [a_], [b_], 3, pad=(1, 1), relu=True, lane=ln)
+                            self._conv(plan, 'res{}_branch2c'.format(nm), [b_], [y_], 1, relu=True, residuals=[sc_], join=side, lane=ln)
+                        xs_of[c0] = y_
+                lane_open = lane_open or halves
+                feats.append(x)
         _, C3, C4, C5 = feats
         plan.features = {'stem': plan.stem_out, 'C2': feats[0], 'C3': C3, 'C4': C4, 'C5': C5}
 
-        # ---- FPN into one pyramid tensor (B, sum(H_l*W_l), 512)
-        shapes = anchor_utils.pyramid_shapes((H, Wd))
+        # ---- FPN into one pyramid tensor (B, sum(H_l*W_l), 512); a DenseNet's pyramid has the sizes of its own C3 .. C5 (floor pools)
+        shapes = anchor_utils.pyramid_shapes_of_features([(C3.H, C3.W), (C4.H, C4.W), (C5.H, C5.W)]) if self.densenet else \
+            anchor_utils.pyramid_shapes((H, Wd))
         if (C3.H, C3.W) != shapes[0] or (C4.H, C4.W) != shapes[1] or (C5.H, C5.W) != shapes[2]:
             raise RuntimeError('backbone / pyramid shape mismatch: {} vs {}'.format([(C3.H, C3.W), (C4.H, C4.W), (C5.H, C5.W)], shapes))
         pix = [h * w for h, w in shapes]
@@ -633,7 +745,8 @@ class RetinaNet3D(object):
         size_fn = hip.lib().gpp_detect_osf_workspace_bytes if self.osf else hip.lib().gpp_detect_workspace_bytes
         hip.check(size_fn(B, plan.n_anchors, need), 'gpp_detect_workspace_bytes')
         plan.detect_ws = torch.empty((int(need.value),), dtype=torch.uint8, device=dev)
-        anchors = self._anchor_table((H, Wd))
+        anchors = self._anchor_table((H, Wd), shapes if self.densenet else None)
+        plan.anchors = anchors
         dd = DetectDesc(plan.cls_logits.data_ptr(), plan.regression.data_ptr(), plan.regression_dim.data_ptr(),
                         anchors.data_ptr(), plan.boxes.data_ptr(), plan.dimensions.data_ptr(), plan.scores.data_ptr(),
                         plan.labels.data_ptr(), plan.orientations.data_ptr(), plan.anchor_index.data_ptr(),
@@ -751,6 +864,29 @@ class RetinaNet3D(object):
             if kind in DETECT_OPS or kind == OP_POLL:
                 continue
             self.run_op(plan, index)
+            if kind == OP_CONV_PREACT:
+                # DenseNet's pre-activation 1x1 convs: their own tile list (gpp_conv2d_preact_tile_candidates), timed the same way
+                cd = plan.preact_conv[id(desc)]
+                key = (name, B, H, Wd)
+                if rnd is not None:
+                    tiles, count = (ctypes.c_int * 16)(), ctypes.c_int(0)
+                    hip.check(hip.lib().gpp_conv2d_preact_tile_candidates(ctypes.byref(cd), tiles, 16, ctypes.byref(count)),
+                              'gpp_conv2d_preact_tile_candidates')
+                    cd.tile_hint = rnd.choice(list(tiles[:count.value]))
+                    plan.tuning[name] = (int(cd.tile_hint), 0.0)
+                    self.run_op(plan, index)
+                    continue
+                if key not in self._tuned:
+                    slow = self.dtype == 'f32'
+                    iters = (2 if slow else 6) if flops > 5e10 else (4 if slow else 16)
+                    hip.check(hip.lib().gpp_conv2d_preact_autotune(ctypes.byref(cd), desc.in_scale, desc.in_shift, iters, hip.stream_ptr(),
+                                                                   ctypes.byref(best)), 'gpp_conv2d_preact_autotune')
+                    self._tuned[key] = (int(cd.tile_hint), round(float(best.value), 2))
+                    fresh = True
+                cd.tile_hint = self._tuned[key][0]
+                plan.tuning[name] = self._tuned[key]
+                plan.tuning_parts.setdefault(name, []).append(self._tuned[key])
+                continue
             if rnd is not None and kind in (OP_TAIL, OP_CONV):
                 if kind == OP_CONV:
                     tiles, count = (ctypes.c_int * 32)(), ctypes.c_int(0)

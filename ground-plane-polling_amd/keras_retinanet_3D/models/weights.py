@@ -57,10 +57,95 @@ def backbone_layers(backbone):
     return layers
 
 
-def fpn_layers():
-    """ [(name, K, C_in, C_out, stride)] models/retinanet.py:170-205 (feature_size = 512) """
-    return [('C5_reduced', 1, 2048, 512, 1), ('P5', 3, 512, 512, 1), ('C4_reduced', 1, 1024, 512, 1), ('P4', 3, 512, 512, 1),
-            ('C3_reduced', 1, 512, 512, 1), ('P3', 3, 512, 512, 1), ('P6', 3, 2048, 512, 2), ('P7', 3, 512, 512, 2)]
+def fpn_layers(backbone=None):
+    """ [(name, K, C_in, C_out, stride)] models/retinanet.py:170-205 (feature_size = 512); the input widths are those of the backbone's
+    C3 / C4 / C5 (no argument: the ResNet table) """
+    c3, c4, c5 = densenet_widths(backbone)[1:] if is_densenet(backbone) else (512, 1024, 2048)
+    return [('C5_reduced', 1, c5, 512, 1), ('P5', 3, 512, 512, 1), ('C4_reduced', 1, c4, 512, 1), ('P4', 3, 512, 512, 1),
+            ('C3_reduced', 1, c3, 512, 1), ('P3', 3, 512, 512, 1), ('P6', 3, c5, 512, 2), ('P7', 3, 512, 512, 2)]
+
+
+# ---- DenseNet-121/169/201 (keras.applications.densenet.DenseNet, reference models/densenet.py:24,62-94); Keras layer names:
+#   conv1/conv (7x7 s2, no bias) conv1/bn; dense layer convS_blockI: _0_bn, _1_conv (1x1 -> 128), _1_bn, _2_conv (3x3 -> 32), _concat;
+#   transition poolS: _bn, _conv (1x1 -> C/2), _pool.  Every BatchNormalization has epsilon 1.001e-5, no convolution has a bias.
+DENSENET_BLOCKS = {'densenet121': (6, 12, 24, 16), 'densenet169': (6, 12, 32, 32), 'densenet201': (6, 12, 48, 32)}
+DENSENET_BN_EPSILON = 1.001e-5
+DENSENET_GROWTH = 32
+DENSENET_BOTTLENECK = 4 * DENSENET_GROWTH
+
+
+def is_densenet(backbone):
+    return backbone is not None and backbone.split('_')[0] in DENSENET_BLOCKS
+
+
+def bn_epsilon(backbone):
+    return DENSENET_BN_EPSILON if is_densenet(backbone) else BN_EPSILON
+
+
+def densenet_widths(backbone):
+    """ channels of the concatenation at the end of dense blocks conv2 .. conv5 (C2, C3, C4, C5) """
+    c, out = 64, []
+    for n in DENSENET_BLOCKS[backbone]:
+        c += DENSENET_GROWTH * n
+        out.append(c)
+        c //= 2
+    return out
+
+
+def densenet_layers(backbone):
+    """ [(kind, name, shape)] of the backbone in execution order, kind 'conv' (shape = Keras HWIO kernel) or 'bn' (shape = (C,)),
+    up to the last concatenation (the final 'bn' of keras' DenseNet is not part of the reference's backbone: models/densenet.py:82-85) """
+    g, mid = DENSENET_GROWTH, DENSENET_BOTTLENECK
+    out = [('conv', 'conv1/conv', (7, 7, 3, 64)), ('bn', 'conv1/bn', (64,))]
+    c = 64
+    for stage, n in enumerate(DENSENET_BLOCKS[backbone]):
+        for i in range(1, n + 1):
+            nm = 'conv{}_block{}'.format(stage + 2, i)
+            out += [('bn', nm + '_0_bn', (c,)), ('conv', nm + '_1_conv', (1, 1, c, mid)), ('bn', nm + '_1_bn', (mid,)),
+                    ('conv', nm + '_2_conv', (3, 3, mid, g))]
+            c += g
+        if stage < 3:
+            out += [('bn', 'pool{}_bn'.format(stage + 2), (c,)), ('conv', 'pool{}_conv'.format(stage + 2), (1, 1, c, c // 2))]
+            c //= 2
+    return out
+
+
+def backbone_parameter_count(backbone):
+    """ parameters of the backbone as Keras counts them (BatchNormalization: 4 per channel, moving statistics included) """
+    return sum(int(np.prod(shape)) * (4 if kind == 'bn' else 1) for kind, _, shape in densenet_layers(backbone))
+
+
+def _densenet_backbone_weights(w, backbone, seed, family):
+    """ He-normal kernels, BatchNormalization close to the identity (every activation O(1)); family 'trained': every channel of the
+    128-channel bottleneck map of a dense layer gets its own scale, log-uniform over TRAINED_CHANNEL_SPREAD (its _1_bn gamma and beta
+    x s_c, the _2_conv kernel's input channel / s_c), TRAINED_DEAD_FRACTION of them dead -- ReLU commutes with a positive scale, so the
+    function is the base draw's up to rounding """
+    for kind, name, shape in densenet_layers(backbone):
+        if kind == 'conv':
+            kh, kw, cin, _ = shape
+            w[name + '/kernel'] = _normal(seed, name, shape, np.sqrt(2.0 / (kh * kw * cin)))
+        else:
+            r = _rng(seed, name)
+            c = shape[0]
+            w[name + '/gamma'] = (np.abs(1.0 + 0.1 * r.standard_normal(c)) + 0.05).astype(np.float32)
+            w[name + '/beta'] = (0.05 * r.standard_normal(c)).astype(np.float32)
+            w[name + '/moving_mean'] = (0.05 * r.standard_normal(c)).astype(np.float32)
+            w[name + '/moving_variance'] = (1.0 + 0.2 * r.random(c)).astype(np.float32)
+    w['conv1/conv/kernel'] *= np.float32(1.0 / 64.0)          # the image arrives un-normalised (BGR - mean, +-128)
+    if family == 'trained':
+        r = _rng(seed, 'trained_like')
+        lo, hi = np.log(TRAINED_CHANNEL_SPREAD[0]), np.log(TRAINED_CHANNEL_SPREAD[1])
+        f32 = np.float32
+        for kind, name, shape in densenet_layers(backbone):
+            if kind != 'bn' or not name.endswith('_1_bn'):
+                continue
+            c = shape[0]
+            s = np.exp(r.uniform(lo, hi, c)).astype(f32)
+            dead = r.random(c) < TRAINED_DEAD_FRACTION
+            w[name + '/gamma'] = np.where(dead, f32(0.0), w[name + '/gamma'] * s).astype(f32)
+            w[name + '/beta'] = np.where(dead, f32(-0.05), w[name + '/beta'] * s).astype(f32)
+            conv = name[:-len('_1_bn')] + '_2_conv/kernel'
+            w[conv] = (w[conv] / s[None, None, :, None]).astype(f32)
 
 
 def head_layers():
@@ -94,6 +179,9 @@ SYN_REG_OUT_GAIN = 0.31       # regression deltas ~ N(0, 1)
 SYN_DIM_OUT_GAIN = 0.18       # dimension deltas ~ N(0, 1)
 # the deeper backbones end with somewhat larger pyramid features: same calibration target, measured the same way
 SYN_BACKBONE_OUT_SCALE = {'resnet50': 1.0, 'resnet101': 0.676, 'resnet152': 0.52}
+# DenseNet (tests/test_densenet_cpu.py::test_synthetic_calibration: the float32 oracle on a 402x1333 noise frame)
+# (1262 / 1082 / 1026 anchors of 132912 above 0.05 with seed 1234)
+SYN_BACKBONE_OUT_SCALE.update({'densenet121': 0.84, 'densenet169': 0.81, 'densenet201': 0.89})
 
 
 def synthetic_weights(backbone='resnet50', seed=1234, family='he'):
@@ -103,8 +191,10 @@ def synthetic_weights(backbone='resnet50', seed=1234, family='he'):
     if family not in ('he', 'trained'):
         raise ValueError("family must be 'he' or 'trained', got {!r}".format(family))
     w = {}
-    stage_blocks = {str(stage + 2): n for stage, n in enumerate(BLOCKS[backbone])}
-    for conv, bn, kh, kw, cin, cout, _ in backbone_layers(backbone):
+    if is_densenet(backbone):
+        _densenet_backbone_weights(w, backbone, seed, family)
+    stage_blocks = {str(stage + 2): n for stage, n in enumerate(BLOCKS.get(backbone, ()))}
+    for conv, bn, kh, kw, cin, cout, _ in (() if is_densenet(backbone) else backbone_layers(backbone)):
         w[conv + '/kernel'] = _normal(seed, conv, (kh, kw, cin, cout), np.sqrt(2.0 / (kh * kw * cin)))
         r = _rng(seed, bn)
         gamma = (1.0 + 0.1 * r.standard_normal(cout)).astype(np.float32)
@@ -119,8 +209,9 @@ def synthetic_weights(backbone='resnet50', seed=1234, family='he'):
         w[bn + '/moving_mean'] = (0.05 * r.standard_normal(cout)).astype(np.float32)
         w[bn + '/moving_variance'] = (1.0 + 0.2 * r.random(cout)).astype(np.float32)
     # the image arrives un-normalised (BGR - mean, +-128): bring conv1 to unit scale
-    w['conv1/kernel'] *= np.float32(1.0 / 64.0)
-    for name, k, cin, cout, _ in fpn_layers():
+    if not is_densenet(backbone):
+        w['conv1/kernel'] *= np.float32(1.0 / 64.0)
+    for name, k, cin, cout, _ in fpn_layers(backbone):
         w[name + '/kernel'] = _normal(seed, name, (k, k, cin, cout), np.sqrt(1.0 / (k * k * cin)))
         w[name + '/bias'] = _normal(seed, name + '/bias', (cout,), 0.01)
     for name, cin, cout, kind in head_layers():
@@ -134,7 +225,7 @@ def synthetic_weights(backbone='resnet50', seed=1234, family='he'):
             w[name + '/bias'] = np.zeros((cout,), np.float32)
     # initializers.PriorProbability(0.01): bias = -log((1 - p) / p)   (initializers.py:23-39)
     w['pyramid_classification/bias'][:] = np.float32(-np.log((1.0 - 0.01) / 0.01))
-    if family == 'trained':
+    if family == 'trained' and not is_densenet(backbone):
         trained_like(w, backbone, seed)
     return w
 
@@ -193,11 +284,15 @@ def parse_synthetic(spec):
 def expected_arrays(backbone):
     """ {array name: shape} of every array the graph of `backbone` + FPN + heads needs (Keras names and layouts) """
     exp = {}
-    for conv, bn, kh, kw, cin, cout, _ in backbone_layers(backbone):
+    if is_densenet(backbone):
+        for kind, name, shape in densenet_layers(backbone):
+            for part in (('kernel',) if kind == 'conv' else ('gamma', 'beta', 'moving_mean', 'moving_variance')):
+                exp['{}/{}'.format(name, part)] = shape
+    for conv, bn, kh, kw, cin, cout, _ in (() if is_densenet(backbone) else backbone_layers(backbone)):
         exp[conv + '/kernel'] = (kh, kw, cin, cout)
         for part in ('gamma', 'beta', 'moving_mean', 'moving_variance'):
             exp['{}/{}'.format(bn, part)] = (cout,)
-    for name, k, cin, cout, _ in fpn_layers():
+    for name, k, cin, cout, _ in fpn_layers(backbone):
         exp[name + '/kernel'], exp[name + '/bias'] = (k, k, cin, cout), (cout,)
     for name, cin, cout, _ in head_layers():
         exp[name + '/kernel'], exp[name + '/bias'] = (3, 3, cin, cout), (cout,)
@@ -238,10 +333,21 @@ def _array_key(dataset_path):
     return '{}/{}'.format(parts[-2], parts[-1].split(':')[0])
 
 
+def _weight_key(layer, weight_name):
+    """ key of a variable listed in a layer group's weight_names: Keras names it '<layer>/<variable>:0', and the layer name itself may
+    hold '/' (DenseNet: 'conv1/conv/kernel:0') -- keyed by the layer name the file gives, not by the last two path components.  Any other
+    form (sub-model groups: the weight name starts with the nested layer's name) keeps the last-two-components rule. """
+    wn = weight_name.split(':')[0]
+    if '/' in layer and wn.startswith(layer + '/') and '/' not in wn[len(layer) + 1:]:
+        return wn
+    return _array_key(layer + '/' + weight_name)
+
+
 def _collect(path, named_arrays):
     out = {}
-    for name, arr in named_arrays:
-        key = _array_key(name)
+    for item in named_arrays:
+        name, arr = item[0], item[1]
+        key = _weight_key(item[2], item[3]) if len(item) == 4 else _array_key(name)
         if key in out:          # nested sub-models must not overwrite each other silently
             raise ValueError('{}: array {} appears twice (second time at {})'.format(path, key, name))
         out[key] = np.asarray(arr, dtype=np.float32)
@@ -268,7 +374,7 @@ def load_keras_h5(path):
                     g = root[layer]
                     for wn in g.attrs['weight_names']:
                         wn = wn.decode() if isinstance(wn, bytes) else str(wn)
-                        found.append((layer + '/' + wn, g[wn][()]))
+                        found.append((layer + '/' + wn, g[wn][()], layer, wn))
             else:
                 root.visititems(lambda name, obj: found.append((name, obj[()])) if isinstance(obj, h5py.Dataset) else None)
         return _collect(path, found)
@@ -285,7 +391,7 @@ def load_keras_h5(path):
                 if names is None:
                     raise ValueError('{}: layer group {} has no weight_names attribute'.format(path, group))
                 for wn in names:
-                    found.append((layer + '/' + wn.decode(), f.read(group + '/' + wn.decode())))
+                    found.append((layer + '/' + wn.decode(), f.read(group + '/' + wn.decode()), layer, wn.decode()))
         else:
             found = sorted(f.datasets(root).items())
     return _collect(path, found)
@@ -333,13 +439,20 @@ def save_weights(path, weights):
     np.savez(path, **weights)
 
 
-def folded_conv(weights, conv, bn=None):
+def bn_affine(weights, bn, eps=BN_EPSILON):
+    """ frozen BatchNormalization as y = x * scale + shift: (scale, shift) float32 (DenseNet: the pre-activation of gpp_conv2d_preact) """
+    s = weights[bn + '/gamma'].astype(np.float64) / np.sqrt(weights[bn + '/moving_variance'].astype(np.float64) + eps)
+    t = weights[bn + '/beta'].astype(np.float64) - weights[bn + '/moving_mean'].astype(np.float64) * s
+    return s.astype(np.float32), t.astype(np.float32)
+
+
+def folded_conv(weights, conv, bn=None, eps=BN_EPSILON):
     """ (kernel HWIO f32, bias f32) of a convolution with its frozen BatchNormalization folded in:
         y = gamma * (conv(x) - mean) / sqrt(var + eps) + beta  =  conv(x, k * s) + (beta - mean * s) """
     k = np.asarray(weights[conv + '/kernel'], dtype=np.float32)
     if bn is None:
         return k, np.asarray(weights[conv + '/bias'], dtype=np.float32)
-    s = weights[bn + '/gamma'].astype(np.float64) / np.sqrt(weights[bn + '/moving_variance'].astype(np.float64) + BN_EPSILON)
+    s = weights[bn + '/gamma'].astype(np.float64) / np.sqrt(weights[bn + '/moving_variance'].astype(np.float64) + eps)
     bias = weights[bn + '/beta'].astype(np.float64) - weights[bn + '/moving_mean'].astype(np.float64) * s
     return (k.astype(np.float64) * s[None, None, None, :]).astype(np.float32), bias.astype(np.float32)
 

@@ -26,6 +26,45 @@ def pyramid_shapes(image_hw):
     return [(-(-int(image_hw[0]) // 2 ** l), -(-int(image_hw[1]) // 2 ** l)) for l in PYRAMID_LEVELS]
 
 
+def pyramid_shapes_of_features(c3_c4_c5):
+    """ (H, W) of P3..P7 from the backbone's actual C3, C4, C5 maps, as the reference's Anchors layers take them from the feature maps
+    (models/retinanet.py:284-311): P3..P5 have the sizes of C3..C5, P6 / P7 are 3x3 stride-2 'same' convolutions (ceil(size / 2)).
+    For the ResNet backbones this is pyramid_shapes(image); a DenseNet's average pools floor instead (402x1333: C5 12x41, not 13x42). """
+    shapes = [(int(h), int(w)) for h, w in c3_c4_c5]
+    for _ in range(2):
+        h, w = shapes[-1]
+        shapes.append((-(-h // 2), -(-w // 2)))
+    return shapes
+
+
+def anchors_for_shapes(shapes):
+    """ (A, 4) float32 anchors x1 y1 x2 y2 for the given (H, W) of P3..P7 (anchors_for_image for any backbone) """
+    chunks = []
+    for (fh, fw), size, stride in zip(shapes, SIZES, STRIDES):
+        base = base_anchors(size)
+        cx = (np.arange(fw, dtype=np.float32) + np.float32(0.5)) * np.float32(stride)
+        cy = (np.arange(fh, dtype=np.float32) + np.float32(0.5)) * np.float32(stride)
+        centre = np.empty((fh, fw, 1, 4), dtype=np.float32)
+        centre[..., 0, 0] = cx[None, :]
+        centre[..., 0, 1] = cy[:, None]
+        centre[..., 0, 2] = cx[None, :]
+        centre[..., 0, 3] = cy[:, None]
+        chunks.append((centre + base[None, None]).reshape(-1, 4))
+    return np.ascontiguousarray(np.concatenate(chunks, axis=0), dtype=np.float32)
+
+
+def densenet_feature_shapes(image_hw):
+    """ (H, W) of a DenseNet's C3, C4, C5 for an input of image_hw: conv1 7x7/2 on the 3-padded image, ZeroPadding2D(1) + 3x3/2 max pool,
+    then 2x2/2 average pools (floor) in front of dense blocks 3, 4, 5 """
+    out = []
+    h, w = (int(image_hw[0]) - 1) // 2 + 1, (int(image_hw[1]) - 1) // 2 + 1
+    h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    for _ in range(3):
+        h, w = h // 2, w // 2
+        out.append((h, w))
+    return out
+
+
 def base_anchors(size):
     """ the 12 reference windows of one level, centred on the origin, float32 """
     scales = np.asarray(np.asarray(SCALES, dtype=np.float32), dtype=np.float64)   # floatx constants

@@ -258,6 +258,29 @@ int gpp_x3_range_snapshot_of(const uint64_t* counter, uint64_t* device_count, vo
 int gpp_conv2d_flops(const gpp_conv_desc* host_desc, double* flops);
 
 /* ------------------------------------------------------------------------------------------
+ * DenseNet-121/169/201 backbone (keras.applications.densenet.DenseNet, used at /root/reference/keras_retinanet_3D/models/densenet.py:
+ * 62-94).  A dense layer "convS_blockI" is _0_bn -> ReLU -> _1_conv (1x1) -> _1_bn -> ReLU -> _2_conv (3x3) -> concatenation; a
+ * transition "poolS" is _bn -> ReLU -> _conv (1x1) -> AveragePooling2D(2, 2).  The BatchNormalization in front of each 1x1 belongs to the
+ * CONSUMER of a concatenation, so it cannot be folded into any producer's weights: it runs as the prologue of the 1x1 conv.
+ *
+ * gpp_conv2d_preact: gpp_conv2d_igemm with every input activation x of channel c replaced by max(x * in_scale[c] + in_shift[c], 0)
+ *     out = act( W . max(in (.) in_scale + in_shift, 0) + bias [+ residual] )
+ *   in_scale / in_shift: [C_in] float32 device arrays, 16-byte aligned (the folded frozen BN: gamma / sqrt(var + eps), beta - mean * scale).
+ *   Scope: 1 x 1, stride 1, pad 0 (a padded zero would become relu(in_shift)), an input map that is NOT pre-split (x3_split & GPP_X3_IN == 0;
+ *   in_pitch > C_in reads a channel prefix of a wider map), C_in <= 4096; GPP_F32 / GPP_F16X3 / GPP_BF16X3 (other types:
+ *   GPP_ERR_UNSUPPORTED).  The output may be pre-split (GPP_X3_OUT).  Same K order as gpp_conv2d_igemm, split-K by the same rule;
+ *   tile_hint: 0 (128 x 128, 128 x 64 for C_out <= 64), 64064, 128064, 64128, 128128, 192128 -- every tile gives the same bytes. */
+int gpp_conv2d_preact(const gpp_conv_desc* host_desc, const float* in_scale, const float* in_shift, void* stream);
+int gpp_conv2d_preact_tile_candidates(const gpp_conv_desc* host_desc, int* tiles, int capacity, int* count);
+/* times the candidates (iters launches each) and stores the fastest in desc->tile_hint; synchronises the stream */
+int gpp_conv2d_preact_autotune(gpp_conv_desc* desc, const float* in_scale, const float* in_shift, int iters, void* stream, float* best_us);
+/* ZeroPadding2D(pad) + MaxPooling2D(3, strides=2) 'pool1' (pad 0 or 1, symmetric): in (B, H, W, C) float32 dense, out pixel (b, y, x) at
+   out + (b*Ho*Wo + y*Wo + x)*out_pitch, Ho = (H + 2 pad - 3)/2 + 1.  Padding never wins (-inf).  C % 4 == 0, out_pitch % 4 == 0. */
+int gpp_maxpool3x3s2_pad_f32(const float* in, float* out, int B, int H, int W, int C, int pad, int out_pitch, void* stream);
+/* AveragePooling2D(2, strides=2), valid: Ho = H/2, Wo = W/2 (floor); ((x00 + x01) + x10) + x11, then * 0.25.  Layout as above. */
+int gpp_avgpool2x2_f32(const float* in, float* out, int B, int H, int W, int C, int out_pitch, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * ResNet stem and small element-wise helpers.
  * gpp_stem_conv7x7_bn_relu replaces keras_resnet's ZeroPadding2D(3) + conv1 (7x7, stride 2,
  * no bias) + bn_conv1 (frozen, eps 1e-5) + ReLU (instantiated at models/resnet.py:88-93):
@@ -404,6 +427,9 @@ int gpp_pack_detections(const float* boxes, const float* dims, const float* scor
 #define GPP_OP_DETECT_OSF 12             /* gpp_detect_desc -> gpp_detect_osf_f32 */
 #define GPP_OP_STEM_POOL 13              /* gpp_stem_desc with out = the pooled map -> gpp_stem_pool_fused_mfma (GPP_BF16 / GPP_F16) / gpp_stem_pool_fused_x3 (GPP_F16X3 / GPP_BF16X3) */
 #define GPP_OP_BOTTLENECK_BLOCK 16       /* gpp_block_desc -> gpp_bottleneck_block */
+#define GPP_OP_MAXPOOL_PAD 17            /* gpp_dense_pool_desc -> gpp_maxpool3x3s2_pad_f32 (DenseNet pool1) */
+#define GPP_OP_AVGPOOL 18                /* gpp_dense_pool_desc -> gpp_avgpool2x2_f32 (DenseNet transitions) */
+#define GPP_OP_CONV_PREACT 32            /* gpp_preact_desc -> gpp_conv2d_preact (DenseNet); kinds 0..255 exist */
 /* (14, 15: the Winograd F(2, 3) form of the tower layers of round 5 -- built, measured at -2 % of the step, shelved in round 6:
    tools/experiments/winograd/) */
 /* Optional concurrency inside a plan: `kind | GPP_OP_LANE(l)` (l = 1, 2) enqueues the op on a library-owned side stream
@@ -454,6 +480,9 @@ typedef struct gpp_poll_desc {
 
 typedef struct gpp_tail_desc { const gpp_conv_desc* conv3x3; const gpp_conv_desc* conv1x1; int32_t tile_rows, reserved; } gpp_tail_desc;
 typedef struct gpp_block_desc { const gpp_conv_desc* conv1x1_a; const gpp_conv_desc* conv3x3_b; const gpp_conv_desc* conv1x1_c; int32_t tile, reserved; } gpp_block_desc;
+
+typedef struct gpp_preact_desc { const gpp_conv_desc* conv; const float* in_scale; const float* in_shift; } gpp_preact_desc;
+typedef struct gpp_dense_pool_desc { const float* in; float* out; int32_t B, H, W, C, pad, out_pitch; } gpp_dense_pool_desc;   /* pad: max-pool only */
 
 typedef struct gpp_plan_op { int32_t kind; int32_t tag; const void* desc; } gpp_plan_op;
 
