@@ -28,6 +28,7 @@ Every bit of a result is a function of (image, weights, dtype) alone: block tile
 a result, and split-K follows a rule of the layer alone (gpp_conv2d_split_rule) -- not of the batch size or the rank.
 """
 
+import collections
 import ctypes
 import json
 import os
@@ -103,6 +104,32 @@ DETECT_OPS = (OP_DETECT, OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT,
 OP_JOIN, OP_SYNC = 0x10000, 0x20000
 
 
+# the effective plan switches of one (model, batch), read from the GPP_* variables by RetinaNet3D._plan_options
+PlanOptions = collections.namedtuple('PlanOptions', 'x3_level fuse_stem_pool stage_chunks half_stages fuse_tail fuse_block fuse_block_proj '
+                                                    'br1_lane fpn_lanes p4_lane head_lanes decode_overlap cls_lane autotune tune_key')
+
+
+def block_form(opts, width, projection, split_input, halves, join):
+    """ how one bottleneck runs: (launch, shortcut).
+    launch: 'block' (branch2a + 2b + 2c + shortcut as one launch, gpp_bottleneck_block: pre-split input maps only), 'tail' (branch2a, then
+    2b + 2c as one launch, gpp_bottleneck_tail) or 'convs' (three launches).
+    shortcut: 'identity' (the block's input), 'side' (the projection on side lane 1, beside branch2a / 2b, joined by the launch that adds
+    it) or 'inline' (the projection on the block's own lane: GPP_BR1_LANE=0, half-batch stages, and the first block behind a split stage,
+    whose first launch joins the half-batch lanes). """
+    if width in opts.fuse_block and (not projection or opts.fuse_block_proj) and split_input:    # (res2a reads the pooled map: float32)
+        launch = 'block'
+    else:
+        launch = 'tail' if width in opts.fuse_tail else 'convs'
+    if not projection:
+        return launch, 'identity'
+    return launch, 'side' if opts.br1_lane and not halves and not join else 'inline'
+
+
+def part_of(fm, c0, nb):
+    """ images [c0, c0 + nb) of a map """
+    return C.FMap(fm.buf, nb, fm.H, fm.W, fm.C, off=fm.off + c0 * fm.bstride, bstride=fm.bstride, pitch=fm.pitch, split=fm.split, half=fm.half)
+
+
 class Plan(object):
     """ Everything one (batch, H, W, N planes) configuration needs: buffers, descriptors, op array. """
 
@@ -114,24 +141,39 @@ class Plan(object):
         self.ops = []           # (kind, tag, desc, name, flops)
         self.oracle_names = {}  # fused ops: reference layer name of each output map (per-layer parity tests)
         self.lanes = []         # per op: side-stream lane << 8 | join flag (include/gpp.h GPP_OP_LANE / GPP_OP_JOIN)
-        self.op_batch = {}      # id(descriptor) -> images the launch covers where that is not the plan's batch (half-batch launches)
-        self.access = {}        # id(descriptor) -> (byte intervals read, byte intervals written): check_stream_ordering
+        self.access = []        # per op: (byte intervals read, byte intervals written): check_stream_ordering
+        self.inner = {}         # id(descriptor) -> the gpp_conv_desc records a fused or pre-activation launch points to
+        self.open_lanes = set()  # side lanes forked and not joined by the ops recorded so far
+        self.conv_descs = []    # (gpp_conv_desc, stream lane): the split-K workspace of each lane is bound once every op is known
+        self.ws_need = {}       # stream lane -> the largest split-K workspace one of its conv descriptors needs
         self.array = None
         self.flops = 0.0
 
-    def add(self, kind, desc, name, tag=0, flops=0.0, lane=0, join=False, sync=False):
-        self.keep.append(desc)
+    def emit(self, kind, desc, name, reads=(), writes=(), tag=0, flops=0.0, lane=0, join=False, sync=False, io=None, inner=()):
+        """ record one launch.  reads / writes: the FMaps and tensors it reads and writes (check_stream_ordering); io: its
+        (inputs, outputs, residuals) FMaps for the per-layer tests; inner: the conv descriptors its descriptor points to """
+        self.keep += list(inner) + [desc]
+        if inner:
+            self.inner[id(desc)] = tuple(inner)
         self.ops.append((kind, tag, desc, name, flops))
         self.lanes.append((int(lane) << 8) | (OP_JOIN if join else 0) | (OP_SYNC if sync else 0))
+        self.access.append((self.spans(reads), self.spans(writes)))
         self.flops += flops
+        if lane:
+            self.open_lanes.add(lane)
+        elif join:
+            self.open_lanes.clear()
+        if io is not None:
+            self.io[name] = io
+            self.io_parts.setdefault(name, []).append(io)
 
-    # ---- who reads and writes what: the byte intervals (one per image) every launch touches, by descriptor.  check_stream_ordering()
-    # replays gpp_plan_run's fork / join rules over them: the plan builder places launches on side streams by hand, and a missing
-    # join is a race that shows up once in a while, at full size only (round 4 found one between a split and an unsplit stage)
+    # ---- who reads and writes what: the byte intervals (one per image) every launch touches.  check_stream_ordering() replays
+    # gpp_plan_run's fork / join rules over them: the plan builder places launches on side streams by hand, and a missing join is
+    # a race that shows up once in a while, at full size only (round 4 found one between a split and an unsplit stage)
     @staticmethod
-    def span(fm, esz=None):
+    def span(fm):
         """ byte intervals of an FMap, one per image """
-        e = fm.buf.element_size() if esz is None else esz
+        e = fm.buf.element_size()
         base = fm.buf.data_ptr() + fm.off * e
         size = ((fm.H * fm.W - 1) * fm.pitch + fm.C) * e
         return [(base + b * fm.bstride * e, base + b * fm.bstride * e + size) for b in range(fm.B)]
@@ -140,9 +182,10 @@ class Plan(object):
     def span_of(tensor):
         return [(tensor.data_ptr(), tensor.data_ptr() + tensor.numel() * tensor.element_size())]
 
-    def touch(self, desc, reads=(), writes=(), kind=None):
-        """ kind: for descriptors shared by several ops (the three decode stages), the op kind the accesses belong to """
-        self.access[id(desc) if kind is None else (id(desc), kind)] = ([iv for r in reads for iv in r], [iv for w in writes for iv in w])
+    @staticmethod
+    def spans(items):
+        """ byte intervals of a list of FMaps and tensors """
+        return [iv for x in items for iv in (Plan.span(x) if isinstance(x, C.FMap) else Plan.span_of(x))]
 
     def check_stream_ordering(self):
         """ every pair of launches on DIFFERENT streams that touch overlapping bytes (at least one of them writing) must be ordered by a
@@ -164,7 +207,7 @@ class Plan(object):
             elif join:
                 joins.append(pos)
                 active = {}
-            reads, writes = self.access.get((id(desc), kind)) or self.access.get(id(desc), ((), ()))
+            reads, writes = self.access[pos]
             for p0, l0, n0, r0, w0 in seen:
                 if l0 == lane or not (overlap(w0, reads) or overlap(w0, writes) or overlap(r0, writes)):
                     continue
@@ -247,6 +290,7 @@ class RetinaNet3D(object):
         self._plans = {}
         self._anchors = {}
         self._tuned = {}             # (layer, B, H, W) -> (tile_hint, split_k, us): see _autotune
+        self.stem_x3 = False         # conv1 on the matrix pipe, input and weights split into two IEEE halves (_upload)
         self._load_tune_cache()
         self._upload(weights)
         self.tag_names = []          # filled by the plan builder: names of event-tagged ops
@@ -352,25 +396,16 @@ class RetinaNet3D(object):
     def _conv(self, plan, name, inputs, outputs, K, stride=1, pad=None, relu=False, residuals=None, out_f32=False, tag=0, lane=0,
               join=False, sync=False):
         d = self._desc(plan, name, inputs, outputs, K, stride, pad, relu, residuals, out_f32, lane)
-        plan.op_batch[id(d)] = inputs[0].B
-        plan.add(OP_CONV, d, name, tag=tag, flops=C.conv_flops(d), lane=lane, join=join, sync=sync)
-        plan.io[name] = (inputs, outputs, residuals)          # FMaps per op (introspection: per-layer parity tests)
-        plan.io_parts.setdefault(name, []).append((inputs, outputs, residuals))
-        plan.touch(d, [Plan.span(f) for f in list(inputs) + list(residuals or [])], [Plan.span(f, 4 if out_f32 else None) for f in outputs])
+        plan.emit(OP_CONV, d, name, list(inputs) + list(residuals or []), outputs, tag=tag, flops=C.conv_flops(d), lane=lane, join=join,
+                  sync=sync, io=(inputs, outputs, residuals))
 
     def _tail(self, plan, nm, a, y, shortcut, join=False, lane=0):
         """ branch2b (3x3) + branch2c (1x1, + shortcut, ReLU) of one bottleneck as ONE launch
         (gpp_bottleneck_tail): the intermediate map never reaches HBM.  Bit-identical to the two layers. """
         d1 = self._desc(plan, 'res{}_branch2b'.format(nm), [a], [a], 3, pad=(1, 1), relu=True)       # its `out` is never written
         d2 = self._desc(plan, 'res{}_branch2c'.format(nm), [a], [y], 1, relu=True, residuals=[shortcut])
-        plan.keep += [d1, d2]
-        t = TailDesc(ctypes.addressof(d1), ctypes.addressof(d2), 0, 0)
-        plan.op_batch[id(t)] = a.B
-        name = 'res{}_branch2b+2c'.format(nm)
-        plan.add(OP_TAIL, t, name, flops=C.conv_flops(d1) + C.conv_flops(d2), join=join, lane=lane)
-        plan.io[name] = ([a], [y], [shortcut])
-        plan.io_parts.setdefault(name, []).append(([a], [y], [shortcut]))
-        plan.touch(t, [Plan.span(a), Plan.span(shortcut)], [Plan.span(y)])
+        plan.emit(OP_TAIL, TailDesc(ctypes.addressof(d1), ctypes.addressof(d2), 0, 0), 'res{}_branch2b+2c'.format(nm), [a, shortcut], [y],
+                  flops=C.conv_flops(d1) + C.conv_flops(d2), join=join, lane=lane, io=([a], [y], [shortcut]), inner=(d1, d2))
 
     def _block(self, plan, nm, x, a, bmap, y, shortcut, stride=1, join=False, lane=0):
         """ a whole bottleneck -- branch2a, branch2b, branch2c (+ shortcut, ReLU) -- as ONE launch (gpp_bottleneck_block): neither intermediate map
@@ -378,51 +413,109 @@ class RetinaNet3D(object):
         d1 = self._desc(plan, 'res{}_branch2a'.format(nm), [x], [a], 1, stride=stride, relu=True)
         d2 = self._desc(plan, 'res{}_branch2b'.format(nm), [a], [bmap], 3, pad=(1, 1), relu=True)
         d3 = self._desc(plan, 'res{}_branch2c'.format(nm), [bmap], [y], 1, relu=True, residuals=[shortcut])
-        plan.keep += [d1, d2, d3]
         t = BlockDesc(ctypes.addressof(d1), ctypes.addressof(d2), ctypes.addressof(d3), 0, 0)
-        plan.op_batch[id(t)] = x.B
-        name = 'res{}_branch2a+2b+2c'.format(nm)
-        plan.add(OP_BLOCK, t, name, flops=C.conv_flops(d1) + C.conv_flops(d2) + C.conv_flops(d3), join=join, lane=lane)
-        plan.io[name] = ([x], [y], [shortcut])
-        plan.io_parts.setdefault(name, []).append(([x], [y], [shortcut]))
-        plan.touch(t, [Plan.span(x), Plan.span(shortcut)], [Plan.span(y)])
+        plan.emit(OP_BLOCK, t, 'res{}_branch2a+2b+2c'.format(nm), [x, shortcut], [y], flops=C.conv_flops(d1) + C.conv_flops(d2) + C.conv_flops(d3),
+                  join=join, lane=lane, io=([x], [y], [shortcut]), inner=(d1, d2, d3))
 
     def _preact(self, plan, name, inputs, outputs, relu=False):
         """ a 1x1 conv behind its input's BatchNormalization + ReLU (gpp_conv2d_preact): DenseNet's _1_conv and transition convs """
         d = self._desc(plan, name, inputs, outputs, 1, relu=relu)
         s, t = self.preact[name]
-        pd = PreactDesc(ctypes.addressof(d), s.data_ptr(), t.data_ptr())
-        plan.keep.append(d)
-        plan.preact_conv[id(pd)] = d
-        plan.op_batch[id(pd)] = inputs[0].B
-        plan.add(OP_CONV_PREACT, pd, name, flops=C.conv_flops(d))
-        plan.io[name] = (inputs, outputs, None)
-        plan.io_parts.setdefault(name, []).append((inputs, outputs, None))
-        plan.touch(pd, [Plan.span(f) for f in inputs], [Plan.span(f) for f in outputs])
+        plan.emit(OP_CONV_PREACT, PreactDesc(ctypes.addressof(d), s.data_ptr(), t.data_ptr()), name, inputs, outputs, flops=C.conv_flops(d),
+                  io=(inputs, outputs, None), inner=(d,))
 
-    def _densenet_backbone(self, plan, B, H, Wd, fmap, bmap):
+    def _stem(self, plan, opts, B, H, Wd, fmap, x):
+        """ conv1 + bn + relu (7x7 / 2) and pool1 (3x3 / 2) into x.  opts.fuse_stem_pool: one launch, the (B, H1, W1, 64) conv map is never
+        stored (bit-identical to the two launches: tests/test_stem_gpu.py; 16-bit types since round 2, the x3 types since round 6 --
+        gpp_stem_pool_fused_x3: the float32 conv map was 274 MB written + read back at B = 8).  Else the conv map is stored and pooled by a
+        second launch: ResNet's max pool, or DenseNet's zero-padded one into the channel prefix of its first concatenation buffer. """
+        H1, W1 = (H + 6 - 7) // 2 + 1, (Wd + 6 - 7) // 2 + 1
+        conv = x if opts.fuse_stem_pool else fmap(H1, W1, 64)
+        d = StemDesc(plan.images.data_ptr(), self.stem_w.data_ptr(), self.stem_b.data_ptr(), conv.buf.data_ptr(),
+                     hip.GPP_F16X3 if self.stem_x3 else C.gpp_storage_dtype(self.dtype), B, H, Wd,
+                     plan.range_slot.data_ptr() if self.dtype == 'f16x3' else None)
+        flops = 2.0 * B * H1 * W1 * 147 * 64
+        plan.stem_out, plan.pool_out = (None if opts.fuse_stem_pool else conv), x
+        if opts.fuse_stem_pool:
+            plan.emit(OP_STEM_POOL, d, 'conv1+pool1', [plan.images], [x], flops=flops)
+            return
+        plan.emit(OP_STEM, d, 'conv1', [plan.images], [conv], flops=flops)
+        pooled = C.FMap(x.buf, B, x.H, x.W, 64, pitch=x.pitch)
+        if self.densenet:
+            pd = DensePoolDesc(conv.buf.data_ptr(), x.buf.data_ptr(), B, H1, W1, 64, 1, x.pitch)
+            plan.emit(OP_MAXPOOL_PAD, pd, 'pool1', [conv], [pooled])
+        else:
+            pd = PoolDesc(conv.buf.data_ptr(), x.buf.data_ptr(), C.gpp_storage_dtype(self.dtype), B, H1, W1, 64, 0)
+            plan.emit(OP_MAXPOOL, pd, 'pool1', [conv], [pooled])
+
+    def _resnet_backbone(self, plan, opts, B, H, Wd, fmap, bmap):
+        """ conv1 .. res5 of keras_resnet (bottleneck_2d: stride on the first 1x1) -> [C2, C3, C4, C5].  A stage runs as two half
+        batches (opts.half_stages), the second half on side lane 1 beside the first, or chunk of images by chunk of images
+        (opts.stage_chunks), one chunk after the other; the halves stay apart until the next whole-batch launch joins them. """
+        H1, W1 = (H + 6 - 7) // 2 + 1, (Wd + 6 - 7) // 2 + 1
+        x = fmap((H1 + 1) // 2, (W1 + 1) // 2, 64)
+        self._stem(plan, opts, B, H, Wd, fmap, x)
+        feats = []
+        for stage, n_blocks in enumerate(W.BLOCKS[self.backbone_name]):
+            f, xin, blocks = 64 * 2 ** stage, x, []
+            for block in range(n_blocks):
+                stride = 2 if (block == 0 and stage > 0) else 1
+                ho, wo = (x.H - 1) // stride + 1, (x.W - 1) // stride + 1
+                # (fused tails have no branch2b map: a fused block's descriptors borrow branch2a's -- neither is written)
+                a, b = bmap(ho, wo, f), None if f in opts.fuse_tail else bmap(ho, wo, f)
+                sc = bmap(ho, wo, 4 * f) if block == 0 else None
+                x = bmap(ho, wo, 4 * f)
+                blocks.append((W.block_name(self.backbone_name, stage, block), stride, a, b, sc, x))
+            chunk = opts.stage_chunks[stage]
+            halves = stage in opts.half_stages and chunk >= B       # (a stage that is chunked runs its chunks one after the other)
+            parts = [(B // 2, B - B // 2, 1), (0, B // 2, 0)] if halves else [(c0, min(chunk, B - c0), 0) for c0 in range(0, B, chunk)]
+            xs_of = {c0: part_of(xin, c0, nb) for c0, nb, _ in parts}
+            for (nm, stride, a, b, sc, y), (c0, nb, lane) in ([(k, p) for k in blocks for p in parts] if halves else
+                                                              [(k, p) for p in parts for k in blocks]):
+                xs = xs_of[c0]
+                join = not halves and bool(plan.open_lanes)          # the first launch of a whole-batch stage behind a split one
+                form = block_form(opts, f, sc is not None, xs.split, halves, join)
+                xs_of[c0] = part_of(y, c0, nb)
+                self._bottleneck(plan, nm, form, stride, xs, part_of(a, c0, nb), b and part_of(b, c0, nb),
+                                 part_of(sc, c0, nb) if sc else xs, xs_of[c0], lane, join)
+            feats.append(x)
+        return feats
+
+    def _bottleneck(self, plan, nm, form, stride, x, a, b, sc, y, lane, join):
+        """ one bottleneck (of one batch part) in the form block_form chose.  join: its first launch closes the side lanes of the stage
+        before; a projection shortcut on side lane 1 is joined by the launch that adds it. """
+        launch, shortcut = form
+        branch1 = 'res{}_branch1'.format(nm)
+        if shortcut == 'side':
+            self._conv(plan, branch1, [x], [sc], 1, stride=stride, lane=1)
+        if launch == 'block':
+            if shortcut == 'inline':         # a projection block: the shortcut map first, in line, then the whole block
+                self._conv(plan, branch1, [x], [sc], 1, stride=stride, lane=lane, join=join)
+                join = False
+            self._block(plan, nm, x, a, b or a, y, sc, stride=stride, join=join or shortcut == 'side', lane=lane)
+            return
+        self._conv(plan, 'res{}_branch2a'.format(nm), [x], [a], 1, stride=stride, relu=True, lane=lane, join=join)
+        if shortcut == 'inline':
+            self._conv(plan, branch1, [x], [sc], 1, stride=stride, lane=lane)
+        if launch == 'tail':
+            self._tail(plan, nm, a, y, sc, join=shortcut == 'side', lane=lane)
+        else:
+            self._conv(plan, 'res{}_branch2b'.format(nm), [a], [b], 3, pad=(1, 1), relu=True, lane=lane)
+            self._conv(plan, 'res{}_branch2c'.format(nm), [b], [y], 1, relu=True, residuals=[sc], join=shortcut == 'side', lane=lane)
+
+    def _densenet_backbone(self, plan, opts, B, H, Wd, fmap, bmap):
         """ conv1 .. conv5_block{N}_concat of keras' DenseNet (reference models/densenet.py:62-94) -> the four block concatenations.
         One float32 buffer per dense block at its final width: the block input (pool1 / the transition's average pool) is written into
         channels [0, C0), layer I's 32 channels into [C0 + 32 (I - 1), C0 + 32 I), and layer I's _1_conv reads the prefix [0, C0 + 32 (I - 1))
         through in_pitch.  The 128-channel map between _1_conv and _2_conv is pre-split for the x3 types.  The whole batch on lane 0. """
         widths = W.densenet_widths(self.backbone_name)
         H1, W1 = (H + 6 - 7) // 2 + 1, (Wd + 6 - 7) // 2 + 1
-        stem = fmap(H1, W1, 64)
-        stem_x3 = getattr(self, 'stem_x3', False)
-        d = StemDesc(plan.images.data_ptr(), self.stem_w.data_ptr(), self.stem_b.data_ptr(), stem.buf.data_ptr(),
-                     hip.GPP_F16X3 if stem_x3 else hip.GPP_F32, B, H, Wd, plan.range_slot.data_ptr() if self.dtype == 'f16x3' else None)
-        plan.add(OP_STEM, d, 'conv1', flops=2.0 * B * H1 * W1 * 147 * 64)
-        plan.touch(d, [Plan.span_of(plan.images)], [Plan.span(stem)])
-        plan.stem_out = stem
         h, w = (H1 - 1) // 2 + 1, (W1 - 1) // 2 + 1
         cats = []
         for stage in range(4):
             cats.append(fmap(h, w, widths[stage]))
             h, w = h // 2, w // 2
-        pd = DensePoolDesc(stem.buf.data_ptr(), cats[0].buf.data_ptr(), B, H1, W1, 64, 1, cats[0].pitch)
-        plan.add(OP_MAXPOOL_PAD, pd, 'pool1')
-        plan.touch(pd, [Plan.span(stem)], [Plan.span(C.FMap(cats[0].buf, B, cats[0].H, cats[0].W, 64, pitch=cats[0].pitch))])
-        plan.pool_out = cats[0]
+        self._stem(plan, opts, B, H, Wd, fmap, cats[0])
         c0 = 64
         for stage, n in enumerate(W.DENSENET_BLOCKS[self.backbone_name]):
             cat = cats[stage]
@@ -440,298 +533,66 @@ class RetinaNet3D(object):
             self._preact(plan, nm + '_conv', [cat], [t])
             nxt = cats[stage + 1]
             pd = DensePoolDesc(t.buf.data_ptr(), nxt.buf.data_ptr(), B, t.H, t.W, t.C, 0, nxt.pitch)
-            plan.add(OP_AVGPOOL, pd, nm + '_pool')
-            plan.touch(pd, [Plan.span(t)], [Plan.span(C.FMap(nxt.buf, B, nxt.H, nxt.W, t.C, pitch=nxt.pitch))])
+            plan.emit(OP_AVGPOOL, pd, nm + '_pool', [t], [C.FMap(nxt.buf, B, nxt.H, nxt.W, t.C, pitch=nxt.pitch)])
             c0 = t.C
         return cats
 
-    def _build(self, B, H, Wd, n_planes, planes_batched):
-        torch, dev, dt = self.torch, self.device, self.tdtype
-        plan = Plan()
-        plan.shape = (B, H, Wd, n_planes, planes_batched)
-        # split-K partial tiles of the deep-K layers with a tiny per-image grid (res5 branch2b, P5..P7); one workspace per
-        # stream lane (concurrent launches must not share partial tiles), sized from the descriptors at the end of _build
-        head_lanes = os.environ.get('GPP_HEAD_LANES', '0') != '0'
-        # res2 .. res5 run as two half batches, the second half on a side stream beside the first (GPP_HALF_LANES="" for whole batches).  res2 joined the
-        # list in round 6: with its identity blocks as one two-per-CU launch each (gpp_bottleneck_block) two half-batch chains overlap the HBM-bound phases
-        # of one with the matrix phase of the other -- same box, alternating: B = 8 812.8 -> 818.7 images/s (+0.7 %), B = 4 +1.1 %, B = 2 +1.1 %
-        # (profiles/r6/ab_half_lanes_with_blocks.txt); before (rounds 4 - 5, separate launches) it lost
-        half_stages = set(int(v) for v in os.environ.get('GPP_HALF_LANES', '0,1,2,3').split(',') if v.strip()) if B >= 2 else set()
-        br1_lane = os.environ.get('GPP_BR1_LANE', '1') != '0'         # measured +0.4 % on the f16x3 step (same box, alternating)
-        plan.conv_descs, plan.ws_need = [], {}
-        plan.preact_conv = {}        # id(gpp_preact_desc) -> its gpp_conv_desc (DenseNet)
-        # dtype='f16x3': the 8-byte counter every launch of THIS plan adds its range events to (gpp_conv_desc.range_counter, gpp_stem_desc.range_counter),
-        # never reset by anyone but x3_range_events(reset=True) of this model; range_seen = its value when a result of the plan was last fetched
-        plan.range_slot = torch.zeros((1,), dtype=torch.int64, device=dev)
-        plan.range_seen = 0
-
-        def fmap(h, w, c, dtype=None):
-            f = C.FMap.empty(B, h, w, c, dtype or dt, dev, half=self.dtype if self.dtype in C.X3_TYPES else 'bf16x3')
-            plan.keep.append(f.buf)
-            return f
-
-        # dtype='bf16x3': maps written and read by convolutions only are stored PRE-SPLIT ([32 bf16 hi | 32 bf16 lo] per 32 channels,
-        # gpp_conv_desc.x3_split): GPP_X3_SPLIT=2 (default) every such map, 1 = only the maps between the FPN / head layers, 0 = none
-        x3_level = int(os.environ.get('GPP_X3_SPLIT', '2')) if self.dtype in C.X3_TYPES else 0
-
-        def bmap(h, w, c):
-            f = fmap(h, w, c)
-            return f.mark_split() if x3_level >= 2 else f
-
-        # ---- inputs
-        plan.images = torch.empty((B, H, Wd, 3), dtype=torch.float32, device=dev)
-        plan.P_inv = torch.empty((B, 4, 3), dtype=torch.float32, device=dev)
-        plan.planes = torch.empty((B, n_planes, 4) if planes_batched else (n_planes, 4), dtype=torch.float32, device=dev)
-
-        lane_open = False
-        if self.densenet:
-            feats = self._densenet_backbone(plan, B, H, Wd, fmap, bmap)
-        else:
-            # ---- stem: conv1 + bn_conv1 + relu, pool1
-            H1, W1 = (H + 6 - 7) // 2 + 1, (Wd + 6 - 7) // 2 + 1
-            H2, W2 = (H1 + 1) // 2, (W1 + 1) // 2
-            x = fmap(H2, W2, 64)
-            stem_x3 = getattr(self, 'stem_x3', False)
-            if (self.esz == 2 or stem_x3) and os.environ.get('GPP_FUSE_STEM_POOL', '1') != '0':
-                # conv1 + bn_conv1 + relu + pool1 in one launch, the (B, H1, W1, 64) conv map is never stored (bit-identical to the two launches:
-                # tests/test_stem_gpu.py).  16-bit types since round 2; the x3 types since round 6 (gpp_stem_pool_fused_x3: the float32 conv map was
-                # 274 MB written + read back at B = 8)
-                d = StemDesc(plan.images.data_ptr(), self.stem_w.data_ptr(), self.stem_b.data_ptr(), x.buf.data_ptr(),
-                             hip.GPP_F16X3 if stem_x3 else C.gpp_storage_dtype(self.dtype), B, H, Wd,
-                             plan.range_slot.data_ptr() if self.dtype == 'f16x3' else None)
-                plan.add(OP_STEM_POOL, d, 'conv1+pool1', flops=2.0 * B * H1 * W1 * 147 * 64)
-                plan.touch(d, [Plan.span_of(plan.images)], [Plan.span(x)])
-                plan.stem_out = None
-            else:
-                stem = fmap(H1, W1, 64)
-                d = StemDesc(plan.images.data_ptr(), self.stem_w.data_ptr(), self.stem_b.data_ptr(), stem.buf.data_ptr(),
-                             hip.GPP_F16X3 if stem_x3 else C.gpp_storage_dtype(self.dtype), B, H, Wd,
-                             plan.range_slot.data_ptr() if self.dtype == 'f16x3' else None)
-                plan.add(OP_STEM, d, 'conv1', flops=2.0 * B * H1 * W1 * 147 * 64)
-                plan.touch(d, [Plan.span_of(plan.images)], [Plan.span(stem)])
-                plan.stem_out = stem
-                pool_d = PoolDesc(stem.buf.data_ptr(), x.buf.data_ptr(), C.gpp_storage_dtype(self.dtype), B, H1, W1, 64, 0)
-                plan.add(OP_MAXPOOL, pool_d, 'pool1')
-                plan.touch(pool_d, [Plan.span(stem)], [Plan.span(x)])
-            plan.pool_out = x
-
-            # ---- bottleneck stages (keras_resnet bottleneck_2d: stride on the first 1x1).
-            # A stage can be run chunk of images by chunk of images (GPP_STAGE_CHUNKS="2,4,8,8") to keep a chunk's
-            # working set inside the 256 MiB Infinity Cache; measured on MI355X at B = 8 this LOSES 1-6 % (the smaller
-            # launches cost more than the on-die re-reads save), so the default is the whole batch per launch.
-            env_chunks = os.environ.get('GPP_STAGE_CHUNKS')
-            # widths whose branch2b + branch2c run as one launch (GPP_FUSE_TAIL=0 for none).  Measured at B = 8, same box,
-            # whole step: none 1553, res3 only 1562, res2 + res3 1571 images/s (in isolation the fused res2 launch is no
-            # faster than its two layers -- 122 us vs 36 + 80 -- but the step is: 69 MB less through HBM per block)
-            fuse_tail = [int(v) for v in os.environ.get('GPP_FUSE_TAIL', '64,128').split(',') if v.strip() and int(v) > 0]
-            if self.dtype in C.X3_TYPES:
-                # the x3 form of the fused tail (bottleneck_tail_x3_kernel): pre-split maps, C = 64 (res2) only -- at C = 128 its LDS
-                # footprint leaves one workgroup per CU
-                fuse_tail = [v for v in fuse_tail if v == 64] if x3_level >= 2 else []
-            elif self.esz == 4:
-                fuse_tail = []              # float32 operands: no fused tail
-            # widths whose IDENTITY blocks (branch2a + 2b + 2c + shortcut) run as one launch (gpp_bottleneck_block; x3 types on pre-split maps): res2 (C = 64:
-            # 4-wavefront workgroups, two per CU; x in once, y out once: 245 -> 212 us per block at B = 8) and res3 (C = 128: 8 wavefronts, one per CU;
-            # at parity with its three launches in isolation, half their fabric bytes).  Same-box A/B of the step (profiles/r6/ab_fuse_block_*.txt):
-            # B = 8: 780 -> 793 images/s (+1.7 %) with both, +0.9 % with res2 alone; B = 4 +1.2 %, B = 2 +0.7 %, batch-1 plan 2.67 -> 2.65 ms.
-            # GPP_FUSE_BLOCK="" for the separate launches (bit-identical either way).  Projection blocks (GPP_FUSE_BLOCK_PROJ=1) measured -0.6 %: off.
-            fuse_block = [int(v) for v in os.environ.get('GPP_FUSE_BLOCK', '64,128').split(',') if v.strip()] if (self.dtype in C.X3_TYPES and x3_level >= 2) else []
-            fuse_block_proj = os.environ.get('GPP_FUSE_BLOCK_PROJ', '0') != '0'      # block 0 of a stage too (its shortcut is the projection launch's map)
-
-            def sub(fm, c0, nb):
-                return C.FMap(fm.buf, nb, fm.H, fm.W, fm.C, off=fm.off + c0 * fm.bstride, bstride=fm.bstride, pitch=fm.pitch, split=fm.split, half=fm.half)
-
-            feats = []
-            lane_open = False            # a stage that ran as two half batches leaves its second half on side lane 1: whatever reads the whole
-            #                              batch next (a stage that is NOT split, or the FPN) has to join it first
-            for stage, n_blocks in enumerate(W.BLOCKS[self.backbone_name]):
-                f = 64 * 2 ** stage
-                blocks = []
-                xin = x
-                for block in range(n_blocks):
-                    nm = W.block_name(self.backbone_name, stage, block)
-                    stride = 2 if (block == 0 and stage > 0) else 1
-                    ho, wo = (x.H - 1) // stride + 1, (x.W - 1) // stride + 1
-                    fused = f in fuse_tail and f in (64, 128)
-                    rec = {'nm': nm, 'stride': stride, 'a': bmap(ho, wo, f), 'b': None if fused else bmap(ho, wo, f),
-                           'sc': bmap(ho, wo, 4 * f) if block == 0 else None, 'y': bmap(ho, wo, 4 * f)}
-                    blocks.append(rec)
-                    x = rec['y']
-                chunk = max(1, min(B, int(env_chunks.split(',')[stage]))) if env_chunks else B
-                # GPP_HALF_LANES (default "0,1,2,3" = res2 .. res5): the stage as two half batches, the second half on a side stream beside
-                # the first.  A launch of these stages fills the 256 CUs 0.7 - 1.4 times and is bound by tile fills and first-touch latency;
-                # two independent chains in flight overlap one's prologue / epilogue / barrier waits with the other's main loop (f16x3 step,
-                # same box, alternating: 775 -> 793 images/s).  An image's result does not depend on its batch (section 4.4): same bytes.
-                # The halves stay apart until the FPN's first layer joins them; the per-block shortcut stream is not used inside them.
-                halves = stage in half_stages and B >= 2 and chunk >= B       # (a stage that is chunked runs its chunks one after the other)
-                # (three parts on three streams, measured: 801 against 811 images/s for two)
-                parts = [(B // 2, B - B // 2, 1), (0, B // 2, 0)] if halves else [(c0, min(chunk, B - c0), 0) for c0 in range(0, B, chunk)]
-                xs_of = {c0: sub(xin, c0, nb) for c0, nb, _ in parts}
-                for rec, (c0, nb, ln) in ([(r, p) for r in blocks for p in parts] if halves else [(r, p) for p in parts for r in blocks]):
-                        xs = xs_of[c0]
-                        nm, stride = rec['nm'], rec['stride']
-                        a_, y_ = sub(rec['a'], c0, nb), sub(rec['y'], c0, nb)
-                        # the projection shortcut of a stage's first block is independent of branch2a / 2b: on a side stream it runs beside them
-                        # and branch2c (or the fused tail) joins it (GPP_BR1_LANE=0: serial, behind branch2a)
-                        join_halves = lane_open and not halves       # first launch of a whole-batch stage behind a split one
-                        side = br1_lane and rec['sc'] is not None and not halves and not join_halves
-                        if side:
-                            sc_ = sub(rec['sc'], c0, nb)
-                            self._conv(plan, 'res{}_branch1'.format(nm), [xs], [sc_], 1, stride=stride, lane=1)
-                        rec['block'] = f in fuse_block and f in (64, 128) and (rec['sc'] is None or fuse_block_proj) and xs.split     # (res2a reads the pooled map, which is float32)
-                        b_or_a = sub(rec['b'], c0, nb) if rec['b'] is not None else a_       # (a stage with fused tails has no branch2b map: the descriptors borrow branch2a's -- neither is written)
-                        if rec['block'] and rec['sc'] is None:
-                            self._block(plan, nm, xs, a_, b_or_a, y_, xs, join=join_halves, lane=ln)
-                        elif not rec['block']:
-                            self._conv(plan, 'res{}_branch2a'.format(nm), [xs], [a_], 1, stride=stride, relu=True, lane=ln, join=join_halves)
-                        if rec['sc'] is not None and not side:
-                            sc_ = sub(rec['sc'], c0, nb)
-                            self._conv(plan, 'res{}_branch1'.format(nm), [xs], [sc_], 1, stride=stride, lane=ln, join=join_halves and rec['block'])
-                        elif rec['sc'] is None:
-                            sc_ = xs
-                        if join_halves:
-                            lane_open = False
-                        if rec['block'] and rec['sc'] is not None:           # a projection block: the shortcut map first (side lane or in line), then the whole block
-                            self._block(plan, nm, xs, a_, b_or_a, y_, sc_, stride=stride, join=side, lane=ln)
-                        if rec['block']:
-                            pass
-                        elif rec['b'] is None:
-                            self._tail(plan, nm, a_, y_, sc_, join=side, lane=ln)
-                        else:
-                            b_ = sub(rec['b'], c0, nb)
-                            self._conv(plan, 'res{}_branch2b'.format(nm), [a_], [b_], 3, pad=(1, 1), relu=True, lane=ln)
-                            self._conv(plan, 'res{}_branch2c'.format(nm), [b_], [y_], 1, relu=True, residuals=[sc_], join=side, lane=ln)
-                        xs_of[c0] = y_
-                lane_open = lane_open or halves
-                feats.append(x)
-        _, C3, C4, C5 = feats
-        plan.features = {'stem': plan.stem_out, 'C2': feats[0], 'C3': C3, 'C4': C4, 'C5': C5}
-
-        # ---- FPN into one pyramid tensor (B, sum(H_l*W_l), 512); a DenseNet's pyramid has the sizes of its own C3 .. C5 (floor pools)
-        shapes = anchor_utils.pyramid_shapes_of_features([(C3.H, C3.W), (C4.H, C4.W), (C5.H, C5.W)]) if self.densenet else \
-            anchor_utils.pyramid_shapes((H, Wd))
-        if (C3.H, C3.W) != shapes[0] or (C4.H, C4.W) != shapes[1] or (C5.H, C5.W) != shapes[2]:
-            raise RuntimeError('backbone / pyramid shape mismatch: {} vs {}'.format([(C3.H, C3.W), (C4.H, C4.W), (C5.H, C5.W)], shapes))
+    def _pyramid(self, plan, opts, B, H, Wd, C3, C4, C5):
+        """ the layout of every FPN / head tensor: the five levels back to back per image, (B, sum(H_l*W_l), C), so that one grouped
+        launch covers all levels; a DenseNet's pyramid has the sizes of its own C3 .. C5 (floor pools).
+        Returns (level shapes, pyramid(c, dtype=None) -> (buffer, its five level FMaps)). """
+        got = [(C3.H, C3.W), (C4.H, C4.W), (C5.H, C5.W)]
+        shapes = anchor_utils.pyramid_shapes_of_features(got) if self.densenet else anchor_utils.pyramid_shapes((H, Wd))
+        if got != [tuple(s) for s in shapes[:3]]:
+            raise RuntimeError('backbone / pyramid shape mismatch: {} vs {}'.format(got, shapes))
         pix = [h * w for h, w in shapes]
         total = sum(pix)
-        lvl_off = [sum(pix[:i]) for i in range(5)]
         plan.n_anchors = total * anchor_utils.NUM_BASE_ANCHORS
-
-        # dtype='bf16x3': the maps between the FPN / head layers -- 80 % of the FLOPs, all of them matrix-pipe bound -- are stored
-        # PRE-SPLIT ([32 bf16 hi | 32 bf16 lo] per 32 channels, gpp_conv_desc.x3_split): written that way by the producing layer's
-        # epilogue, read by the consumers without the per-fragment split on the vector ALU (GPP_X3_SPLIT=0: plain float32 maps).
-        # The backbone maps stay float32: its layers are bound by their tile fill, not by the matrix pipe.
-        x3s = x3_level >= 1
+        x3s = opts.x3_level >= 1
 
         def pyramid(c, dtype=None):
-            buf = torch.empty((B, total, c), dtype=dtype or dt, device=dev)
+            buf = self.torch.empty((B, total, c), dtype=dtype or self.tdtype, device=self.device)
             plan.keep.append(buf)
             sp = x3s and dtype is None
-            return buf, [C.FMap(buf, B, shapes[i][0], shapes[i][1], c, off=lvl_off[i] * c, bstride=total * c, split=sp,
-                                half=self.dtype if sp else 'bf16x3') for i in range(5)]
+            return buf, [C.FMap(buf, B, h, w, c, off=sum(pix[:i]) * c, bstride=total * c, split=sp, half=self.dtype if sp else 'bf16x3')
+                         for i, (h, w) in enumerate(shapes)]
+        return shapes, pyramid
 
-        def smap(h, w, c):
-            f = fmap(h, w, c)
-            return f.mark_split() if x3s else f
-
-        pyr, P = pyramid(512)
+    def _fpn(self, plan, opts, C3, C4, C5, pyramid, smap):
+        """ P3 .. P7 into one pyramid tensor (512 channels); returns its five level maps.  P5 and the P6 -> ReLU -> P7 chain are small
+        launches (a few dozen tiles) independent of the C4 / C3 chain: with opts.fpn_lanes they run on the side streams underneath the
+        C4_reduced / P4 launches (182 workgroups each: 74 CUs idle), joined by the fused first tower layer (measured +0.8 % on the f16x3
+        step).  P4 (182 workgroups of 192 x 256: 71 % of the CUs) only feeds the towers: with opts.p4_lane it runs behind P5 on its side
+        stream (re-forked: it needs T4), beside C3_reduced / P3. """
+        _, P = pyramid(512)
+        l_p5, l_p6 = (1, 2) if opts.fpn_lanes else (0, 0)
         T5 = smap(C5.H, C5.W, 512)
-        # P5 and the P6 -> ReLU -> P7 chain are small launches (a few dozen tiles) independent of the C4 / C3 chain:
-        # they run on the side streams underneath the C4_reduced / P4 launches (182 workgroups each: 74 CUs idle), joined by the
-        # fused first tower layer (GPP_FPN_LANES=0: serial)
-        fpn_lanes = head_lanes or os.environ.get('GPP_FPN_LANES', '1') != '0'      # measured +0.8 % on the f16x3 step
-        l_p5, l_p6 = (1, 2) if fpn_lanes else (0, 0)
-        self._conv(plan, 'C5_reduced', [C5], [T5], 1, join=lane_open)
+        self._conv(plan, 'C5_reduced', [C5], [T5], 1, join=bool(plan.open_lanes))
         self._conv(plan, 'P5', [T5], [P[2]], 3, pad=(1, 1), lane=l_p5)
         self._conv(plan, 'P6', [C5], [P[3]], 3, stride=2, pad=(C.same_pad(C5.H, 3, 2)[1], C.same_pad(C5.W, 3, 2)[1]), lane=l_p6)
-        R6 = smap(shapes[3][0], shapes[3][1], 512)
-        relu_d = ReluDesc(pyr.data_ptr() + P[3].off * self.esz, R6.buf.data_ptr(), P[3].bstride, R6.bstride,
-                          pix[3] * 512, C.gpp_dtype(self.dtype) if x3s else C.gpp_storage_dtype(self.dtype), B)
-        plan.add(OP_RELU, relu_d, 'C6_relu', lane=l_p6)
-        plan.touch(relu_d, [Plan.span(P[3])], [Plan.span(R6)])
+        R6 = smap(P[3].H, P[3].W, 512)
+        relu_d = ReluDesc(P[3].buf.data_ptr() + P[3].off * self.esz, R6.buf.data_ptr(), P[3].bstride, R6.bstride, P[3].H * P[3].W * 512,
+                          C.gpp_dtype(self.dtype) if opts.x3_level >= 1 else C.gpp_storage_dtype(self.dtype), P[3].B)
+        plan.emit(OP_RELU, relu_d, 'C6_relu', [P[3]], [R6], lane=l_p6)
         plan.relu_io = (P[3], R6)
-        self._conv(plan, 'P7', [R6], [P[4]], 3, stride=2,
-                   pad=(C.same_pad(shapes[3][0], 3, 2)[1], C.same_pad(shapes[3][1], 3, 2)[1]), lane=l_p6)
+        self._conv(plan, 'P7', [R6], [P[4]], 3, stride=2, pad=(C.same_pad(P[3].H, 3, 2)[1], C.same_pad(P[3].W, 3, 2)[1]), lane=l_p6)
         T4 = smap(C4.H, C4.W, 512)
         self._conv(plan, 'C4_reduced', [C4], [T4], 1, residuals=[T5])          # + UpsampleLike(P5, C4), fused
-        # P4 (182 workgroups of 192 x 256: 71 % of the CUs) only feeds the towers: behind P5 on its side stream (re-forked: it needs T4), it
-        # runs beside C3_reduced / P3 (GPP_P4_LANE=0: serial)
-        p4_lane = 1 if (fpn_lanes and os.environ.get('GPP_P4_LANE', '1') != '0') else 0
-        self._conv(plan, 'P4', [T4], [P[1]], 3, pad=(1, 1), lane=p4_lane, sync=bool(p4_lane))
+        self._conv(plan, 'P4', [T4], [P[1]], 3, pad=(1, 1), lane=opts.p4_lane, sync=bool(opts.p4_lane))
         T3 = smap(C3.H, C3.W, 512)
         self._conv(plan, 'C3_reduced', [C3], [T3], 1, residuals=[T4])          # + UpsampleLike(P4, C3), fused
         self._conv(plan, 'P3', [T3], [P[0]], 3, pad=(1, 1))
+        return P
 
-        plan.features.update({'P{}'.format(i + 3): P[i] for i in range(5)})
-
-        # ---- heads: every layer is one grouped launch over the five levels
-        # layer 0 of the three towers shares its input: one fused launch (C_out = 896) into a wide
-        # tensor; layers 1..3 read their channel slice of it (in_pitch > C_in)
-        wide, wide_maps = pyramid(896)
-        def slice_of(maps, c0, c):
-            return [C.FMap(m.buf, B, m.H, m.W, c, off=m.off + c0, bstride=m.bstride, pitch=m.pitch, split=m.split, half=m.half) for m in maps]
-
-        # (measured and rejected: the half-empty fourth 256-column tile of this 896-wide layer as its own 128-column launch
-        # on a side stream -- the two launches do not pack into each other's partial rounds, no gain)
-        self._conv(plan, 'pyramid_towers_0', P, wide_maps, 3, pad=(1, 1), relu=True, join=True)
-
-        def tower(prefix, width, src, tag=0, lane=0):
-            for i in range(1, 4):
-                _, dst = pyramid(width)
-                name = '{}_{}'.format(prefix, i)
-                self._conv(plan, name, src, dst, 3, pad=(1, 1), relu=True, tag=tag, lane=lane)
-                src = dst
-            return src
-
-        # the three towers are independent chains: optionally (GPP_HEAD_LANES=1) the two small ones run on side
-        # streams, forked after the fused first layer and joined by the decode, so that their launches fill the
-        # ramp-up / tail phases of the big regression-tower kernels
-        l_dim, l_cls = (1, 2) if head_lanes else (0, 0)
-        # Launch order (default, GPP_DECODE_OVERLAP=1): classification tower, regression tower, dimension tower.
-        # The detection selection (threshold + sort + greedy NMS: one workgroup per image, latency-bound, 8 of the
-        # 256 CUs) only needs the classification logits and the corner regressions, so it runs on a side stream
-        # underneath the dimension tower; the full decode of the <= 100 survivors joins when every head is done.
-        overlap = os.environ.get('GPP_DECODE_OVERLAP', '1') != '0' and not head_lanes and not self.osf
-        plan.decode_overlap = overlap
-        plan.side_lanes = {'fpn': fpn_lanes, 'branch1': br1_lane, 'p4': bool(p4_lane), 'half_batch_stages': sorted(half_stages)}
-
-        def dim_tower():
-            dim_t = tower('pyramid_regression_dim', 128, slice_of(wide_maps, 768, 128), lane=l_dim)
-            plan.regression_dim, dim_o = pyramid(36, torch.float32)
-            self._conv(plan, 'pyramid_regression_dim', dim_t, dim_o, 3, pad=(1, 1), out_f32=True, lane=l_dim)
-
-        # GPP_CLS_LANE (default: on for B <= 2): the classification tower (+ the candidate pass behind it) on side lane 2 BESIDE the regression
-        # tower instead of in front of it.  At batch 1 a tower launch fields 0.9 - 1.9 rounds of workgroups of one wavefront per SIMD: two
-        # independent chains in flight fill the other half of every SIMD (measured: profiles/r5/b1_latency.json, field `plan_variants`).  `pyramid_regression_ops`
-        # joins the lane, so the selection that follows sees the candidate keys; at batch 8 every launch fills the chip on its own (off).
-        cls_lane = 2 if (overlap and os.environ.get('GPP_CLS_LANE', '1' if B <= 2 else '0') != '0') else 0
-        plan.side_lanes['cls_tower'] = bool(cls_lane)
-
-        def cls_tower():
-            cls_t = tower('pyramid_classification', 256, slice_of(wide_maps, 512, 256), lane=l_cls or cls_lane)
-            plan.cls_logits, cls_o = pyramid(96, torch.float32)
-            self._conv(plan, 'pyramid_classification', cls_t, cls_o, 3, pad=(1, 1), out_f32=True, lane=l_cls or cls_lane)
-
-        def reg_tower():
-            reg_t = tower('pyramid_regression', 512, slice_of(wide_maps, 0, 512), tag=1)
-            plan.regression, reg_o = pyramid(144, torch.float32)
-            self._conv(plan, 'pyramid_regression_ops', reg_t, reg_o, 3, pad=(1, 1), out_f32=True, join=bool(cls_lane))
-
-        detect_at = {}
-        if overlap:
-            cls_tower()
-            detect_at['candidates'] = len(plan.ops)
-            reg_tower()
-            detect_at['select'] = len(plan.ops)
-            dim_tower()
-        else:
-            dim_tower()
-            cls_tower()
-            reg_tower()
-
-        # ---- decode + NMS (RegressBoxes, RegressDims, FilterDetections)
-        D = MAX_DETECTIONS
+    def _detect(self, plan, B, anchors, pyramid):
+        """ decode + NMS (RegressBoxes, RegressDims, FilterDetections): the three head outputs (float32 pyramids), the detection outputs,
+        the workspace and the one descriptor the decode launches share, allocated before the towers are emitted.
+        Returns ((classification, regression, dimension) output maps, decode(kind, name, **flags): records one decode launch). """
+        torch, dev, D = self.torch, self.device, MAX_DETECTIONS
         f32, i32 = torch.float32, torch.int32
+        plan.cls_logits, cls_o = pyramid(96, f32)
+        plan.regression, reg_o = pyramid(144, f32)
+        plan.regression_dim, dim_o = pyramid(36, f32)
         plan.boxes = torch.empty((B, D, 12), dtype=f32, device=dev)
         plan.dimensions = torch.empty((B, D, 3), dtype=f32, device=dev)
         plan.scores = torch.empty((B, D), dtype=f32, device=dev)
@@ -744,56 +605,180 @@ class RetinaNet3D(object):
             raise ValueError('orientation_specific_filter=True handles at most 16 images per batch')
         size_fn = hip.lib().gpp_detect_osf_workspace_bytes if self.osf else hip.lib().gpp_detect_workspace_bytes
         hip.check(size_fn(B, plan.n_anchors, need), 'gpp_detect_workspace_bytes')
-        plan.detect_ws = torch.empty((int(need.value),), dtype=torch.uint8, device=dev)
-        anchors = self._anchor_table((H, Wd), shapes if self.densenet else None)
+        plan.detect_ws = ws = torch.empty((int(need.value),), dtype=torch.uint8, device=dev)
         plan.anchors = anchors
         dd = DetectDesc(plan.cls_logits.data_ptr(), plan.regression.data_ptr(), plan.regression_dim.data_ptr(),
                         anchors.data_ptr(), plan.boxes.data_ptr(), plan.dimensions.data_ptr(), plan.scores.data_ptr(),
                         plan.labels.data_ptr(), plan.orientations.data_ptr(), plan.anchor_index.data_ptr(),
-                        plan.counts.data_ptr(), plan.detect_ws.data_ptr(), plan.detect_ws.numel(), plan.n_anchors,
+                        plan.counts.data_ptr(), ws.data_ptr(), ws.numel(), plan.n_anchors,
                         B, anchor_utils.NUM_BASE_ANCHORS, 1, D, SCORE_THRESHOLD, NMS_THRESHOLD if self.nms else 2.0)
-        # what the decode stages touch (one shared descriptor: logged per op kind)
-        sp = Plan.span_of
-        det_out = [sp(t) for t in (plan.boxes, plan.dimensions, plan.scores, plan.labels, plan.orientations, plan.anchor_index)]
-        heads_in = [sp(plan.cls_logits), sp(plan.regression), sp(plan.regression_dim)]
-        plan.touch(dd, [sp(plan.cls_logits)], [sp(plan.detect_ws), sp(plan.counts)], kind=OP_DETECT_CANDIDATES)
-        plan.touch(dd, [sp(plan.detect_ws), sp(plan.regression)], [sp(plan.detect_ws)], kind=OP_DETECT_SELECT)
-        plan.touch(dd, heads_in + [sp(plan.detect_ws)], det_out, kind=OP_DETECT_EMIT)
-        for whole in (OP_DETECT, OP_DETECT_OSF):
-            plan.touch(dd, heads_in, det_out + [sp(plan.detect_ws), sp(plan.counts)], kind=whole)
-        if overlap:
-            # spliced in where their inputs are complete (the descriptors need the buffers allocated above)
-            at = detect_at['select']
-            plan.ops.insert(at, (OP_DETECT_SELECT, 0, dd, 'filtered_detections/select', 0.0))
-            plan.lanes.insert(at, (1 << 8) | OP_SYNC)
-            at = detect_at['candidates']
-            plan.ops.insert(at, (OP_DETECT_CANDIDATES, 0, dd, 'filtered_detections/candidates', 0.0))
-            plan.lanes.insert(at, (cls_lane or 1) << 8)             # behind the classification tower: on its lane when it has one
-            plan.add(OP_DETECT_EMIT, dd, 'filtered_detections', join=True)
-        else:
-            plan.add(OP_DETECT_OSF if self.osf else OP_DETECT, dd, 'filtered_detections', join=True)
+        heads = [plan.cls_logits, plan.regression, plan.regression_dim]
+        dets = [plan.boxes, plan.dimensions, plan.scores, plan.labels, plan.orientations, plan.anchor_index]
+        access = {OP_DETECT_CANDIDATES: ([plan.cls_logits], [ws, plan.counts]), OP_DETECT_SELECT: ([ws, plan.regression], [ws]),
+                  OP_DETECT_EMIT: (heads + [ws], dets)}
 
-        # ---- ground-plane polling (FitRoadPlanes)
-        plan.keypoints = torch.empty((B, D, 4, 3), dtype=f32, device=dev)
-        plan.keyplanes = torch.empty((B, D, 1, 4), dtype=f32, device=dev)
-        plan.residuals = torch.empty((B, D), dtype=f32, device=dev)
-        plan.best_index = torch.empty((B, D), dtype=i32, device=dev)
+        def decode(kind, name='filtered_detections', **flags):
+            reads, writes = access.get(kind, (heads, dets + [ws, plan.counts]))          # (OP_DETECT / OP_DETECT_OSF: the whole decode)
+            plan.emit(kind, dd, name, reads, writes, **flags)
+        return (cls_o, reg_o, dim_o), decode
+
+    def _heads(self, plan, opts, P, pyramid, outs, decode):
+        """ the three towers (every layer one grouped launch over the five levels; layer 0 of the three shares its input: one fused
+        launch, C_out = 896, whose channel slices layers 1..3 read) and the decode launches where their inputs are complete.
+        opts.decode_overlap: classification, regression, dimension tower; the detection selection (one workgroup per image, 8 of the
+        256 CUs) only needs the logits and the corner regressions, so it runs on a side stream underneath the dimension tower, and the
+        decode of the <= 100 survivors joins when every head is done.  opts.head_lanes: the two small towers on side streams, filling
+        the ramp-up / tail phases of the big regression-tower kernels.  opts.cls_lane: the classification tower (+ the candidate pass)
+        on side lane 2 BESIDE the regression tower, whose last layer joins it. """
+        cls_o, reg_o, dim_o = outs
+        _, wide = pyramid(896)
+        # (measured and rejected: the half-empty fourth 256-column tile of this 896-wide layer as its own 128-column launch
+        # on a side stream -- the two launches do not pack into each other's partial rounds, no gain)
+        self._conv(plan, 'pyramid_towers_0', P, wide, 3, pad=(1, 1), relu=True, join=True)
+
+        def tower(prefix, width, c0, out_name, out, tag=0, lane=0, join=False):
+            src = [C.FMap(m.buf, m.B, m.H, m.W, width, off=m.off + c0, bstride=m.bstride, pitch=m.pitch, split=m.split, half=m.half)
+                   for m in wide]
+            for i in range(1, 4):
+                _, dst = pyramid(width)
+                self._conv(plan, '{}_{}'.format(prefix, i), src, dst, 3, pad=(1, 1), relu=True, tag=tag, lane=lane)
+                src = dst
+            self._conv(plan, out_name, src, out, 3, pad=(1, 1), out_f32=True, lane=lane, join=join)
+
+        l_dim, l_cls = (1, 2) if opts.head_lanes else (0, 0)
+        towers = {'cls': ('pyramid_classification', 256, 512, 'pyramid_classification', cls_o, 0, l_cls or opts.cls_lane),
+                  'reg': ('pyramid_regression', 512, 0, 'pyramid_regression_ops', reg_o, 1, 0, bool(opts.cls_lane)),
+                  'dim': ('pyramid_regression_dim', 128, 768, 'pyramid_regression_dim', dim_o, 0, l_dim)}
+        if opts.decode_overlap:
+            tower(*towers['cls'])
+            decode(OP_DETECT_CANDIDATES, 'filtered_detections/candidates', lane=opts.cls_lane or 1)     # on the tower's lane when it has one
+            tower(*towers['reg'])
+            decode(OP_DETECT_SELECT, 'filtered_detections/select', lane=1, sync=True)
+            tower(*towers['dim'])
+            decode(OP_DETECT_EMIT, join=True)
+        else:
+            for t in ('dim', 'cls', 'reg'):
+                tower(*towers[t])
+            decode(OP_DETECT_OSF if self.osf else OP_DETECT, join=True)
+
+    def _poll(self, plan, B, n_planes, planes_batched):
+        """ ground-plane polling (FitRoadPlanes) of the detections """
+        torch, dev, D = self.torch, self.device, MAX_DETECTIONS
+        plan.keypoints = torch.empty((B, D, 4, 3), dtype=torch.float32, device=dev)
+        plan.keyplanes = torch.empty((B, D, 1, 4), dtype=torch.float32, device=dev)
+        plan.residuals = torch.empty((B, D), dtype=torch.float32, device=dev)
+        plan.best_index = torch.empty((B, D), dtype=torch.int32, device=dev)
+        need = hip.c_size_t(0)
         hip.check(hip.lib().gpp_poll_workspace_bytes(B, n_planes, int(planes_batched), need), 'gpp_poll_workspace_bytes')
         plan.poll_ws = torch.empty((max(int(need.value), 16),), dtype=torch.uint8, device=dev)
         pd = PollDesc(plan.boxes.data_ptr(), plan.dimensions.data_ptr(), plan.orientations.data_ptr(), plan.P_inv.data_ptr(),
                       plan.planes.data_ptr(), plan.keypoints.data_ptr(), plan.keyplanes.data_ptr(), plan.residuals.data_ptr(),
                       plan.best_index.data_ptr(), plan.poll_ws.data_ptr(), plan.poll_ws.numel(), B, D, n_planes,
                       int(planes_batched), POLL_THRESHOLD, 0)
-        plan.add(OP_POLL, pd, 'fit_road_planes', tag=2, flops=162.0 * B * D * n_planes)      # tag 2: bench.py times it live too
-        plan.touch(pd, [Plan.span_of(t) for t in (plan.boxes, plan.dimensions, plan.orientations, plan.P_inv, plan.planes)],
-                   [Plan.span_of(t) for t in (plan.keypoints, plan.keyplanes, plan.residuals, plan.best_index, plan.poll_ws)])
-        plan.workspaces = {lane: torch.empty((max(need_, 16),), dtype=torch.uint8, device=dev) for lane, need_ in plan.ws_need.items()}
+        plan.emit(OP_POLL, pd, 'fit_road_planes', [plan.boxes, plan.dimensions, plan.orientations, plan.P_inv, plan.planes],
+                  [plan.keypoints, plan.keyplanes, plan.residuals, plan.best_index, plan.poll_ws], tag=2,    # tag 2: bench.py times it live too
+                  flops=162.0 * B * D * n_planes)
+
+    def _bind_workspaces(self, plan):
+        """ split-K partial tiles of the deep-K layers with a tiny per-image grid (res5 branch2b, P5..P7): one workspace per stream lane
+        (concurrent launches must not share partial tiles), sized from the descriptors of the whole plan """
+        plan.workspaces = {lane: self.torch.empty((max(need, 16),), dtype=self.torch.uint8, device=self.device)
+                           for lane, need in plan.ws_need.items()}
         for d, lane in plan.conv_descs:
             d.partial = plan.workspaces[lane].data_ptr()
             d.partial_bytes = plan.workspaces[lane].numel()
+
+    def _plan_options(self, B):
+        """ every GPP_* switch of the plan builder, read once per plan (at the start of _build), as its effective value for this model
+        and batch (PlanOptions) """
+        env = os.environ.get
+        x3 = self.dtype in C.X3_TYPES
+        # x3 types: maps written and read by convolutions only are stored PRE-SPLIT ([32 hi | 32 lo] halves per 32 channels,
+        # gpp_conv_desc.x3_split): GPP_X3_SPLIT=2 (default) every such map, 1 = only the maps between the FPN / head layers -- 80 % of the
+        # FLOPs, all of them matrix-pipe bound -- 0 = none.  Written that way by the producing layer's epilogue, read by the consumers
+        # without the per-fragment split on the vector ALU.
+        x3_level = int(env('GPP_X3_SPLIT', '2')) if x3 else 0
+        # GPP_STAGE_CHUNKS="2,4,8,8": a stage chunk of images by chunk of images, to keep a chunk's working set inside the 256 MiB Infinity
+        # Cache; measured on MI355X at B = 8 this LOSES 1-6 % (the smaller launches cost more than the on-die re-reads save): off
+        chunks = env('GPP_STAGE_CHUNKS')
+        # GPP_FUSE_TAIL: widths whose branch2b + branch2c run as one launch ("" or 0 for none).  Measured at B = 8, same box, whole step:
+        # none 1553, res3 only 1562, res2 + res3 1571 images/s (in isolation the fused res2 launch is no faster than its two layers --
+        # 122 us vs 36 + 80 -- but the step is: 69 MB less through HBM per block).  The x3 form (bottleneck_tail_x3_kernel) reads
+        # pre-split maps at C = 64 (res2) only -- at C = 128 its LDS footprint leaves one workgroup per CU; float32 operands: none
+        fuse_tail = [int(v) for v in env('GPP_FUSE_TAIL', '64,128').split(',') if v.strip() and int(v) > 0]
+        if x3:
+            fuse_tail = [v for v in fuse_tail if v == 64] if x3_level >= 2 else []
+        elif self.esz == 4:
+            fuse_tail = []
+        # GPP_FUSE_BLOCK: widths whose IDENTITY blocks (branch2a + 2b + 2c + shortcut) run as one launch (gpp_bottleneck_block; x3 types on
+        # pre-split maps): res2 (C = 64: 4-wavefront workgroups, two per CU; x in once, y out once: 245 -> 212 us per block at B = 8) and
+        # res3 (C = 128: 8 wavefronts, one per CU; at parity with its three launches in isolation, half their fabric bytes).  Same-box A/B
+        # of the step (profiles/r6/ab_fuse_block_*.txt): B = 8: 780 -> 793 images/s (+1.7 %) with both, +0.9 % with res2 alone; B = 4
+        # +1.2 %, B = 2 +0.7 %, batch-1 plan 2.67 -> 2.65 ms.  "" for the separate launches (bit-identical either way).  Projection
+        # blocks too (GPP_FUSE_BLOCK_PROJ=1) measured -0.6 %: off.
+        fuse_block = [int(v) for v in env('GPP_FUSE_BLOCK', '64,128').split(',') if v.strip()] if (x3 and x3_level >= 2) else []
+        head_lanes = env('GPP_HEAD_LANES', '0') != '0'
+        fpn_lanes = head_lanes or env('GPP_FPN_LANES', '1') != '0'
+        overlap = env('GPP_DECODE_OVERLAP', '1') != '0' and not head_lanes and not self.osf
+        return PlanOptions(
+            x3_level=x3_level,
+            fuse_stem_pool=not self.densenet and (self.esz == 2 or self.stem_x3) and env('GPP_FUSE_STEM_POOL', '1') != '0',
+            stage_chunks=tuple(max(1, min(B, int(v))) for v in chunks.split(',')) if chunks else (B,) * 4,
+            # GPP_HALF_LANES (default "0,1,2,3" = res2 .. res5; "" for whole batches): a launch of these stages fills the 256 CUs 0.7 - 1.4
+            # times and is bound by tile fills and first-touch latency; two half-batch chains in flight overlap one's prologue / epilogue /
+            # barrier waits with the other's main loop (f16x3 step, same box: 775 -> 793 images/s; three parts: 801 against 811).  res2
+            # since round 6, with fused identity blocks: B = 8 +0.7 %, B = 4 +1.1 %, B = 2 +1.1 % (profiles/r6/ab_half_lanes_with_blocks.txt)
+            half_stages=frozenset(int(v) for v in env('GPP_HALF_LANES', '0,1,2,3').split(',') if v.strip()) if B >= 2 else frozenset(),
+            fuse_tail=tuple(v for v in fuse_tail if v in (64, 128)),
+            fuse_block=tuple(v for v in fuse_block if v in (64, 128)),
+            fuse_block_proj=env('GPP_FUSE_BLOCK_PROJ', '0') != '0',
+            br1_lane=env('GPP_BR1_LANE', '1') != '0',           # measured +0.4 % on the f16x3 step (same box, alternating)
+            fpn_lanes=fpn_lanes,
+            p4_lane=1 if (fpn_lanes and env('GPP_P4_LANE', '1') != '0') else 0,
+            head_lanes=head_lanes,
+            decode_overlap=overlap,
+            # GPP_CLS_LANE (default: on for B <= 2): at batch 1 a tower launch fields 0.9 - 1.9 rounds of workgroups of one wavefront per
+            # SIMD: two independent chains in flight fill the other half of every SIMD (measured: profiles/r5/b1_latency.json, field
+            # `plan_variants`); at batch 8 every launch fills the chip on its own (off)
+            cls_lane=2 if (overlap and env('GPP_CLS_LANE', '1' if B <= 2 else '0') != '0') else 0,
+            autotune=env('GPP_AUTOTUNE', '1') != '0',
+            tune_key='x3split={};fuse={}/{};plan={}{}'.format(env('GPP_X3_SPLIT', '2'), env('GPP_FUSE_TAIL', '64,128'), env('GPP_FUSE_BLOCK', '64,128'),
+                                                              self.plan_mode, C.latency_split_config() if self.plan_mode == 'latency' else ''))
+
+    def _build(self, B, H, Wd, n_planes, planes_batched):
+        torch, dev = self.torch, self.device
+        opts = self._plan_options(B)
+        plan = Plan()
+        plan.shape = (B, H, Wd, n_planes, planes_batched)
+        plan.side_lanes = {'fpn': opts.fpn_lanes, 'branch1': opts.br1_lane, 'p4': bool(opts.p4_lane),
+                           'half_batch_stages': sorted(opts.half_stages), 'cls_tower': bool(opts.cls_lane)}
+        plan.decode_overlap = opts.decode_overlap
+        # dtype='f16x3': the 8-byte counter every launch of THIS plan adds its range events to (gpp_conv_desc.range_counter, gpp_stem_desc.range_counter),
+        # never reset by anyone but x3_range_events(reset=True) of this model; range_seen = its value when a result of the plan was last fetched
+        plan.range_slot = torch.zeros((1,), dtype=torch.int64, device=dev)
+        plan.range_seen = 0
+        plan.images = torch.empty((B, H, Wd, 3), dtype=torch.float32, device=dev)
+        plan.P_inv = torch.empty((B, 4, 3), dtype=torch.float32, device=dev)
+        plan.planes = torch.empty((B, n_planes, 4) if planes_batched else (n_planes, 4), dtype=torch.float32, device=dev)
+
+        def fmap(h, w, c, split=False):
+            f = C.FMap.empty(B, h, w, c, self.tdtype, dev, half=self.dtype if self.dtype in C.X3_TYPES else 'bf16x3')
+            plan.keep.append(f.buf)
+            return f.mark_split() if split else f
+
+        backbone = self._densenet_backbone if self.densenet else self._resnet_backbone
+        C2, C3, C4, C5 = backbone(plan, opts, B, H, Wd, fmap, lambda h, w, c: fmap(h, w, c, opts.x3_level >= 2))
+        plan.features = {'stem': plan.stem_out, 'C2': C2, 'C3': C3, 'C4': C4, 'C5': C5}
+        shapes, pyramid = self._pyramid(plan, opts, B, H, Wd, C3, C4, C5)
+        P = self._fpn(plan, opts, C3, C4, C5, pyramid, lambda h, w, c: fmap(h, w, c, opts.x3_level >= 1))
+        plan.features.update({'P{}'.format(i + 3): P[i] for i in range(5)})
+        outs, decode = self._detect(plan, B, self._anchor_table((H, Wd), shapes if self.densenet else None), pyramid)
+        self._heads(plan, opts, P, pyramid, outs, decode)
+        self._poll(plan, B, n_planes, planes_batched)
+        self._bind_workspaces(plan)
         plan.finalize()
         plan.tagged = [name for _, tag, _, name, _ in plan.ops if tag]
-        if os.environ.get('GPP_AUTOTUNE', '1') != '0':
+        if opts.autotune:
             self._autotune(plan)
         return plan
 
@@ -804,10 +789,10 @@ class RetinaNet3D(object):
     def _tune_config(self):
         """ what a cached tile choice is valid for besides (backbone, type, layer, batch, image size): the build of the library (tile codes
         come and go with it: gpp_version() carries a hash of the kernel sources) and the plan options that change which maps are
-        pre-split or fused -- a tile timed on a float32 map may not even exist for the pre-split form of the same layer """
+        pre-split or fused (PlanOptions.tune_key, the same at every batch) -- a tile timed on a float32 map may not even exist for the
+        pre-split form of the same layer """
         ver = hip.lib().gpp_version().decode().split('src:')[-1]
-        return 'v2;{};x3split={};fuse={};plan={}{}'.format(ver, os.environ.get('GPP_X3_SPLIT', '2'), os.environ.get('GPP_FUSE_TAIL', '64,128') + '/' + os.environ.get('GPP_FUSE_BLOCK', '64,128'), self.plan_mode,
-                                                           C.latency_split_config() if self.plan_mode == 'latency' else '')
+        return 'v2;{};{}'.format(ver, self._plan_options(1).tune_key)
 
     def _load_tune_cache(self):
         path = self._tune_cache_path()
@@ -847,11 +832,11 @@ class RetinaNet3D(object):
         and is cheap to measure.  The tile NEVER changes a result (same K order per output element,
         test_every_tile_gives_identical_results), so ranks and plans may choose differently without any effect on the
         outputs; split-K, which would, is not tuned (gpp_conv2d_split_rule).  Choices are remembered per (layer, batch,
-        image size) and can be persisted with GPP_TUNE_CACHE=<file.json>.  GPP_AUTOTUNE=0 keeps the library heuristic. """
-        torch = self.torch
-        B, H, Wd = plan.shape[:3]
+        image size) and can be persisted with GPP_TUNE_CACHE=<file.json>.  GPP_AUTOTUNE=0 keeps the library heuristic.
+        The fused tails choose their row count (tile_rows), DenseNet's pre-activation convs the tile of their inner conv. """
+        self._require_hip()
+        H, Wd = plan.shape[1:3]
         plan.images.uniform_(-120.0, 130.0)
-        best = ctypes.c_float(0.0)
         fresh = False
         plan.tuning = {}
         # GPP_TUNE_RANDOM=<seed> (tests / tools/first_run_stress.py): every layer takes a RANDOM tile among those the library
@@ -864,87 +849,76 @@ class RetinaNet3D(object):
             if kind in DETECT_OPS or kind == OP_POLL:
                 continue
             self.run_op(plan, index)
-            if kind == OP_CONV_PREACT:
-                # DenseNet's pre-activation 1x1 convs: their own tile list (gpp_conv2d_preact_tile_candidates), timed the same way
-                cd = plan.preact_conv[id(desc)]
-                key = (name, B, H, Wd)
-                if rnd is not None:
-                    tiles, count = (ctypes.c_int * 16)(), ctypes.c_int(0)
-                    hip.check(hip.lib().gpp_conv2d_preact_tile_candidates(ctypes.byref(cd), tiles, 16, ctypes.byref(count)),
-                              'gpp_conv2d_preact_tile_candidates')
-                    cd.tile_hint = rnd.choice(list(tiles[:count.value]))
-                    plan.tuning[name] = (int(cd.tile_hint), 0.0)
-                    self.run_op(plan, index)
-                    continue
-                if key not in self._tuned:
-                    slow = self.dtype == 'f32'
-                    iters = (2 if slow else 6) if flops > 5e10 else (4 if slow else 16)
-                    hip.check(hip.lib().gpp_conv2d_preact_autotune(ctypes.byref(cd), desc.in_scale, desc.in_shift, iters, hip.stream_ptr(),
-                                                                   ctypes.byref(best)), 'gpp_conv2d_preact_autotune')
-                    self._tuned[key] = (int(cd.tile_hint), round(float(best.value), 2))
-                    fresh = True
-                cd.tile_hint = self._tuned[key][0]
-                plan.tuning[name] = self._tuned[key]
-                plan.tuning_parts.setdefault(name, []).append(self._tuned[key])
+            if kind not in (OP_CONV, OP_TAIL, OP_CONV_PREACT):
                 continue
-            if rnd is not None and kind in (OP_TAIL, OP_CONV):
-                if kind == OP_CONV:
-                    tiles, count = (ctypes.c_int * 32)(), ctypes.c_int(0)
-                    hip.check(hip.lib().gpp_conv2d_tile_candidates(ctypes.byref(desc), tiles, 32, ctypes.byref(count)), 'gpp_conv2d_tile_candidates')
-                    ok = []
-                    for tile in tiles[:count.value]:         # a candidate the launcher refuses for this shape is skipped, as the autotuner does
-                        desc.tile_hint = tile
-                        if hip.lib().gpp_plan_run(ctypes.byref(plan.array, index * ctypes.sizeof(PlanOp)), 1, hip.stream_ptr(), None, 0) == 0:
-                            ok.append(tile)
-                    desc.tile_hint = rnd.choice(ok)
-                    plan.tuning[name] = (int(desc.tile_hint), 0.0)
-                else:
-                    desc.tile_rows = rnd.choice((64, 96, 128, 160) if self.dtype in C.X3_TYPES else (96, 128, 160))
-                    plan.tuning[name] = (int(desc.tile_rows), 0.0)
+            # where the choice is written: the conv's own descriptor, the pre-activation's inner one, the tail's row count
+            target = plan.inner[id(desc)][0] if kind == OP_CONV_PREACT else desc
+            field = 'tile_rows' if kind == OP_TAIL else 'tile_hint'
+            if rnd is not None:
+                setattr(target, field, rnd.choice(self._tile_choices(plan, index, kind, target)))
+                plan.tuning[name] = (int(getattr(target, field)), 0.0)
                 self.run_op(plan, index)
                 continue
-            if kind == OP_TAIL:
-                key = (name, plan.op_batch.get(id(desc), B), H, Wd)          # (a half-batch launch is tuned as what it is)
-                if key not in self._tuned:
-                    times = {}
-                    for rows in ((64, 96, 128, 160) if (self.dtype in C.X3_TYPES and os.environ.get('GPP_TAIL64', '1') != '0') else (96, 128, 160)):
-                        desc.tile_rows = rows
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        self.run_op(plan, index)
-                        e0.record()
-                        for _ in range(16):
-                            self.run_op(plan, index)
-                        e1.record()
-                        e1.synchronize()
-                        times[rows] = e0.elapsed_time(e1) * 1000.0 / 16
-                    rows = min(times, key=times.get)
-                    self._tuned[key] = (rows, round(times[rows], 2))
-                    fresh = True
-                desc.tile_rows = self._tuned[key][0]
-                plan.tuning[name] = self._tuned[key]
-                plan.tuning_parts.setdefault(name, []).append(self._tuned[key])
-                continue
-            if kind != OP_CONV:
-                continue
-            key = (name, plan.op_batch.get(id(desc), B), H, Wd)
-            if key in self._tuned and not self._tile_is_listed(desc, self._tuned[key][0]):
+            key = (name, (plan.inner[id(desc)][0] if kind == OP_TAIL else target).batch, H, Wd)     # (a half-batch launch is tuned as what it is)
+            if kind == OP_CONV and key in self._tuned and not self._tile_is_listed(desc, self._tuned[key][0]):
                 del self._tuned[key]                 # a remembered tile this build does not offer for this layer: time the layer again
             if key not in self._tuned:
-                # launches per candidate and repetition (the library times two repetitions and keeps the faster).  The float32 path's launches are
-                # 3 x as long as the x3 types': fewer of them.  Round 4: the x3 types used the float32 counts (2 / 4) -- a big layer's choice then rested
-                # on four launches per candidate, and one tuning run in ~60 picked a tile that cost the whole run 5 %
-                slow = self.dtype == 'f32'
-                iters = (2 if slow else 6) if flops > 5e10 else (4 if slow else 16)
-                hip.check(hip.lib().gpp_conv2d_autotune(ctypes.byref(desc), iters, hip.stream_ptr(), ctypes.byref(best)),
-                          'gpp_conv2d_autotune')
-                self._tuned[key] = (int(desc.tile_hint), round(float(best.value), 2))
+                self._tuned[key] = self._time_tiles(plan, index, kind, desc, target, flops)
                 fresh = True
-            desc.tile_hint = self._tuned[key][0]
+            setattr(target, field, self._tuned[key][0])
             plan.tuning[name] = self._tuned[key]
             plan.tuning_parts.setdefault(name, []).append(self._tuned[key])
-        torch.cuda.synchronize()
+        self.torch.cuda.synchronize()
         if fresh:
             self._save_tune_cache()
+
+    def _tile_choices(self, plan, index, kind, target):
+        """ the tiles one op can take: the fused tail's row counts, the pre-activation conv's candidates, or the conv's candidates that its
+        launcher accepts for this shape (a trial launch each: a candidate the launcher refuses is skipped, as the autotuner does) """
+        if kind == OP_TAIL:
+            return (64, 96, 128, 160) if self.dtype in C.X3_TYPES else (96, 128, 160)
+        lib, tiles, count = hip.lib(), (ctypes.c_int * 32)(), ctypes.c_int(0)
+        if kind == OP_CONV_PREACT:
+            hip.check(lib.gpp_conv2d_preact_tile_candidates(ctypes.byref(target), tiles, 16, ctypes.byref(count)),
+                      'gpp_conv2d_preact_tile_candidates')
+            return list(tiles[:min(count.value, 16)])
+        hip.check(lib.gpp_conv2d_tile_candidates(ctypes.byref(target), tiles, 32, ctypes.byref(count)), 'gpp_conv2d_tile_candidates')
+        ok = []
+        for tile in tiles[:count.value]:
+            target.tile_hint = tile
+            if lib.gpp_plan_run(ctypes.byref(plan.array, index * ctypes.sizeof(PlanOp)), 1, hip.stream_ptr(), None, 0) == 0:
+                ok.append(tile)
+        return ok
+
+    def _time_tiles(self, plan, index, kind, desc, target, flops):
+        """ (tile, us) of the fastest choice of one op: the fused tail's row counts timed here (GPP_TAIL64=0: not 64), the conv tiles by
+        the library -- fewer launches per candidate for the float32 path, whose launches are 3 x as long (round 4: the x3 types on those
+        counts rested a big layer's choice on four launches per candidate, and one tuning run in ~60 picked a tile that cost 5 %) """
+        if kind == OP_TAIL:
+            times = {}
+            for rows in self._tile_choices(plan, index, kind, target):
+                if rows == 64 and os.environ.get('GPP_TAIL64', '1') == '0':
+                    continue
+                desc.tile_rows = rows
+                e0, e1 = self.torch.cuda.Event(enable_timing=True), self.torch.cuda.Event(enable_timing=True)
+                self.run_op(plan, index)
+                e0.record()
+                for _ in range(16):
+                    self.run_op(plan, index)
+                e1.record()
+                e1.synchronize()
+                times[rows] = e0.elapsed_time(e1) * 1000.0 / 16
+            rows = min(times, key=times.get)
+            return rows, round(times[rows], 2)
+        slow = self.dtype == 'f32'
+        iters = (2 if slow else 6) if flops > 5e10 else (4 if slow else 16)
+        best = ctypes.c_float(0.0)
+        if kind == OP_CONV_PREACT:
+            hip.check(hip.lib().gpp_conv2d_preact_autotune(ctypes.byref(target), desc.in_scale, desc.in_shift, iters, hip.stream_ptr(),
+                                                           ctypes.byref(best)), 'gpp_conv2d_preact_autotune')
+        else:
+            hip.check(hip.lib().gpp_conv2d_autotune(ctypes.byref(target), iters, hip.stream_ptr(), ctypes.byref(best)), 'gpp_conv2d_autotune')
+        return int(target.tile_hint), round(float(best.value), 2)
 
     @staticmethod
     def _tile_is_listed(desc, tile):
@@ -984,12 +958,18 @@ class RetinaNet3D(object):
         return self._plans[key]
 
     # ------------------------------------------------------------------ execution
+    def _require_hip(self):          # a model built on another device (the CPU plan tests): its plans can be inspected, never run
+        if self.device.type != 'cuda':
+            raise hip.GppError('the model was built on {}: its plans do not run'.format(self.device))
+
     def run_op(self, plan, index):
         """ Enqueue ONE op of the plan (per-layer tests). """
+        self._require_hip()
         hip.check(hip.lib().gpp_plan_run(ctypes.byref(plan.array, index * ctypes.sizeof(PlanOp)), 1, hip.stream_ptr(), None, 0), 'gpp_plan_run')
 
     def run_plan(self, plan, events=None):
         """ Enqueue the whole forward on the current stream (asynchronous). """
+        self._require_hip()
         if events is None and getattr(plan, 'graph', None) is not None:
             plan.graph.replay()
             return
@@ -1004,6 +984,7 @@ class RetinaNet3D(object):
         """ Record the plan into a HIP graph (via torch's stream capture); later run_plan(plan) calls replay
         it with one launch.  Measured on MI355X: no gain (B = 1: 2.00 -> 1.98 ms, B = 8: 5.44 -> 5.43 ms) -- the plan
         is GPU-bound, kernel time is 99 % of the step -- so it is optional and off by default. """
+        self._require_hip()
         torch = self.torch
         self.run_plan(plan)                      # warm-up outside the capture (one-time kernel attribute calls)
         torch.cuda.synchronize()

@@ -47,3 +47,33 @@ def bits_equal(a, b):
     a = np.asarray(a)
     b = np.asarray(b)
     return a.shape == b.shape and bool(np.all((a == b) | (np.isnan(a) & np.isnan(b))))
+
+
+# every switch of the plan builder (GPP_* variables read by RetinaNet3D._build): the GPU test runs each against the one-stream plan
+# (tests/test_network_gpu.py), the CPU test (tests/test_plan_cpu.py) checks the stream ordering and the descriptors of each at several batches
+PLAN_OPTIONS = [{}, {'GPP_HALF_LANES': '1,2'}, {'GPP_HALF_LANES': '1'}, {'GPP_HALF_LANES': '2'}, {'GPP_HALF_LANES': '0,1,2,3'}, {'GPP_HALF_LANES': '0,2'},
+                {'GPP_HALF_LANES': ''}, {'GPP_BR1_LANE': '0'}, {'GPP_FPN_LANES': '0'}, {'GPP_P4_LANE': '0'}, {'GPP_HEAD_LANES': '1'},
+                {'GPP_DECODE_OVERLAP': '0'}, {'GPP_STAGE_CHUNKS': '4,8,8,8'}, {'GPP_STAGE_CHUNKS': '2,4,8,8', 'GPP_HALF_LANES': '2,3'},
+                {'GPP_HALF_LANES': '3', 'GPP_FPN_LANES': '0', 'GPP_BR1_LANE': '0'}, {'GPP_CLS_LANE': '1'}, {'GPP_CLS_LANE': '1', 'GPP_HALF_LANES': ''},
+                {'GPP_HALF_LANES': '1,2,3'}, {'GPP_FUSE_BLOCK': ''}, {'GPP_FUSE_BLOCK': '64,128', 'GPP_FUSE_BLOCK_PROJ': '1'}]      # (round 6: the old default; no fused blocks; projection blocks fused too)
+
+
+def plan_matrix():
+    """ the plan configurations tests/test_plan_cpu.py checks and tools/plan_fingerprint.py hashes, each as
+    (backbone, dtype, model keyword arguments, environment, B, H, W) """
+    small = (200, 333)
+    cfgs = [('resnet50', dt, {}, env, b) + small for env in PLAN_OPTIONS for dt in ('f16x3', 'bf16x3', 'f32', 'bf16', 'f16') for b in (1, 2, 3, 8)]
+    cfgs += [(bb, 'f16x3', {}, {}, 4) + small for bb in ('resnet101', 'resnet152')]
+    cfgs += [('densenet121', dt, {}, {}, b) + small for dt in ('f32', 'f16x3', 'bf16x3') for b in (1, 2)]
+    cfgs += [('resnet50', 'f16x3', kw, {}, b) + small for kw in ({'plan': 'latency'}, {'orientation_specific_filter': True}, {'nms': False})
+             for b in (1, 4)]
+    cfgs += [('resnet50', dt, {}, env, 4) + small for dt in ('f16x3', 'bf16x3', 'bf16')
+             for env in ({'GPP_X3_SPLIT': '0'}, {'GPP_X3_SPLIT': '1'}, {'GPP_FUSE_TAIL': ''}, {'GPP_FUSE_STEM_POOL': '0'})]
+    cfgs += [('resnet50', 'f16x3', {}, {}, 8, 402, 1333)]
+    return cfgs
+
+
+def plan_label(cfg):
+    bb, dt, kw, env, B, H, Wd = cfg
+    return ' '.join([bb, dt, 'B={}'.format(B), '{}x{}'.format(H, Wd)] + ['{}={}'.format(*kv) for kv in sorted(kw.items())] +
+                    ['{}={}'.format(*kv) for kv in sorted(env.items())])

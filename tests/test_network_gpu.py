@@ -217,11 +217,7 @@ def test_side_stream_lanes_do_not_change_results(dtype, monkeypatch):
             assert helpers.bits_equal(a, b)
 
 
-PLAN_OPTIONS = [{}, {'GPP_HALF_LANES': '1,2'}, {'GPP_HALF_LANES': '1'}, {'GPP_HALF_LANES': '2'}, {'GPP_HALF_LANES': '0,1,2,3'}, {'GPP_HALF_LANES': '0,2'},
-                {'GPP_HALF_LANES': ''}, {'GPP_BR1_LANE': '0'}, {'GPP_FPN_LANES': '0'}, {'GPP_P4_LANE': '0'}, {'GPP_HEAD_LANES': '1'},
-                {'GPP_DECODE_OVERLAP': '0'}, {'GPP_STAGE_CHUNKS': '4,8,8,8'}, {'GPP_STAGE_CHUNKS': '2,4,8,8', 'GPP_HALF_LANES': '2,3'},
-                {'GPP_HALF_LANES': '3', 'GPP_FPN_LANES': '0', 'GPP_BR1_LANE': '0'}, {'GPP_CLS_LANE': '1'}, {'GPP_CLS_LANE': '1', 'GPP_HALF_LANES': ''},
-                {'GPP_HALF_LANES': '1,2,3'}, {'GPP_FUSE_BLOCK': ''}, {'GPP_FUSE_BLOCK': '64,128', 'GPP_FUSE_BLOCK_PROJ': '1'}]      # (round 6: the old default; no fused blocks; projection blocks fused too)
+PLAN_OPTIONS = helpers.PLAN_OPTIONS
 
 
 # the default GPU run keeps the settings that changed a plan's shape in a way of its own (the default, the split / unsplit pattern of the round-4 race,

@@ -1,0 +1,77 @@
+""" Plans built without a GPU: the model on the CPU device (hip.require_device patched, GPP_AUTOTUNE=0) builds every plan of the matrix
+(helpers.plan_matrix: every plan switch x every type x several batches, the deeper ResNets, DenseNet, the latency plan, per-orientation
+NMS, no NMS, a full-size frame).  What the plan builder asks of the library there is host code (FLOPs, workspace sizes, the split rule).
+Each plan is checked for races between its streams, for descriptors the library would refuse, and for the host restatement of the split
+rule (layers/conv.default_split) against the library's own. """
+import ctypes
+import os
+
+import pytest
+import torch
+
+import helpers
+from keras_retinanet_3D import models
+from keras_retinanet_3D.backend import hip
+from keras_retinanet_3D.layers import conv as C
+from keras_retinanet_3D.models import retinanet as R
+from keras_retinanet_3D.models import weights as W
+
+INNER = {R.OP_TAIL: ('conv3x3', 'conv1x1'), R.OP_BLOCK: ('conv1x1_a', 'conv3x3_b', 'conv1x1_c'), R.OP_CONV_PREACT: ('conv',)}
+
+
+@pytest.fixture(scope='module')
+def cpu_model():
+    """ model_for(backbone, dtype, kwargs): one CPU model per configuration of the model, weights drawn once per backbone """
+    weights, built = {}, {}
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(hip, 'require_device', lambda: torch.device('cpu'))
+        for k in [k for k in os.environ if k.startswith('GPP_') and k != 'GPP_LIB']:
+            mp.delenv(k)
+        mp.setenv('GPP_AUTOTUNE', '0')
+
+        def model_for(bb, dt, kw):
+            key = (bb, dt, tuple(sorted(kw.items())))
+            if key not in built:
+                if bb not in weights:
+                    weights[bb] = W.synthetic_weights(bb, 1234)
+                built[key] = models.load_model(weights[bb], backbone_name=bb, dtype=dt, **kw)
+            return built[key]
+        yield model_for
+
+
+def conv_descs(plan):
+    """ every gpp_conv_desc of the plan, those inside fused and pre-activation launches included """
+    for kind, _, desc, name, _ in plan.ops:
+        if kind == R.OP_CONV:
+            yield name, desc
+        for field in INNER.get(kind, ()):
+            yield name, hip.ConvDesc.from_address(getattr(desc, field))
+
+
+@pytest.mark.parametrize('cfg', helpers.plan_matrix(), ids=helpers.plan_label)
+def test_plan_is_race_free_and_every_descriptor_is_accepted(cfg, cpu_model, monkeypatch):
+    bb, dt, kw, env, B, H, Wd = cfg
+    model = cpu_model(bb, dt, kw)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    model._plans.clear()
+    plan = model.plan_for(B, H, Wd, 100, True)
+    model._plans.clear()
+    assert plan.check_stream_ordering() == []
+    tiles, count = (ctypes.c_int * 64)(), ctypes.c_int(0)
+    n = 0
+    for name, d in conv_descs(plan):
+        assert hip.lib().gpp_conv2d_tile_candidates(ctypes.byref(d), tiles, 64, ctypes.byref(count)) == 0 and count.value > 0, name
+        if model.plan_mode == 'throughput':
+            pixels = sum(d.groups[g].H_out * d.groups[g].W_out for g in range(d.n_groups))
+            assert C.default_split(d.KH, d.KW, d.C_in, d.C_out, pixels) == C.split_rule(d), name
+        n += 1
+    assert n > 50
+
+
+def test_a_cpu_built_plan_never_reaches_a_kernel(cpu_model):
+    model = cpu_model('resnet50', 'bf16', {})
+    plan = model.plan_for(1, 96, 160, 100, True)
+    for run in (lambda: model.run_op(plan, 0), lambda: model.run_plan(plan), lambda: model.capture(plan), lambda: model._autotune(plan)):
+        with pytest.raises(hip.GppError):
+            run()
