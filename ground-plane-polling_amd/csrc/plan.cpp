@@ -79,7 +79,7 @@ struct Roctx {
     }
 };
 const char* const kStageNames[16] = {nullptr, "gpp:stem", "gpp:backbone", "gpp:fpn", "gpp:heads", "gpp:decode", "gpp:polling", "gpp:gather",
-                                     "gpp:stage8", "gpp:stage9", "gpp:stage10", "gpp:stage11", "gpp:stage12", "gpp:stage13", "gpp:stage14", "gpp:stage15"};
+                                     "gpp:pose", "gpp:stage9", "gpp:stage10", "gpp:stage11", "gpp:stage12", "gpp:stage13", "gpp:stage14", "gpp:stage15"};
 
 }  // namespace
 
@@ -245,6 +245,12 @@ extern "C" int gpp_plan_run(const gpp_plan_op* ops, int n_ops, void* stream, voi
             const gpp_poll_desc* d = (const gpp_poll_desc*)op.desc;
             rc = gpp_poll_f32(d->boxes, d->dims, d->orient, d->P_inv, d->planes, d->B, d->D, d->N, d->planes_batched, d->thr,
                               d->keypoints, d->keyplanes, d->residuals, d->best_idx, d->workspace, d->workspace_bytes, stream);
+            break;
+        }
+        case GPP_OP_POSE: {
+            const gpp_pose_desc* d = (const gpp_pose_desc*)op.desc;
+            rc = gpp_pose_f32(d->boxes, d->dims, d->scores, d->labels, d->orientations, d->keypoints, d->residuals, d->frame_info,
+                              d->B, d->D, d->score_thr, d->rows, d->counts, stream);
             break;
         }
         default:

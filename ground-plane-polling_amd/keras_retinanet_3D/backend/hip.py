@@ -39,6 +39,7 @@ GPP_F32 = 3
 GPP_BF16X3 = 4
 GPP_F16X3 = 5
 GPP_MAX_GROUPS = 5
+GPP_POSE_COLS = 36         # float32 values per row of gpp_pose_f32 (include/gpp.h)
 
 
 class GppError(RuntimeError):
@@ -79,6 +80,8 @@ def _declare(lib):
     lib.gpp_poll_f32.restype = c_int
     lib.gpp_poll_f32.argtypes = [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_float] + [c_void_p] * 4 + \
         [c_void_p, c_size_t, c_void_p]
+    lib.gpp_pose_f32.restype = c_int
+    lib.gpp_pose_f32.argtypes = [c_void_p] * 8 + [c_int, c_int, c_float] + [c_void_p] * 3
     lib.gpp_conv2d_igemm.restype = c_int
     lib.gpp_conv2d_igemm.argtypes = [ctypes.POINTER(ConvDesc), c_void_p]
     lib.gpp_stem_conv7x7_bn_relu.restype = c_int

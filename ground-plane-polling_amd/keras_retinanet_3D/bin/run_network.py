@@ -5,7 +5,7 @@ Run the network on a directory of images -- the MI355X counterpart of the refere
 tree and file formats):
 
     run_network.py model_path image_dir calib_dir plane_params_path output_dir
-                   [--kitti] [--save-images] [--backbone resnet50] [--batch-size N]
+                   [--kitti] [--save-images] [--backbone resnet50] [--batch-size N] [--device-pose]
 
     <output_dir>/<model name>/outputs/full/<image>.mat     boxes keypoints labels scores locations
                                                            angles dimensions residuals  (:291-292)
@@ -15,7 +15,8 @@ tree and file formats):
 Differences, all on the host side: images are processed in batches (--batch-size, default 1 =
 the reference's behaviour), the per-detection Python loop of :137-287 is vectorised
 (utils.gpp_utils.recover_pose), and `model_path` may be 'synthetic:<seed>' because no trained
-weights ship with the reference.
+weights ship with the reference.  With --device-pose the selection, the pose recovery and the KITTI fields are computed
+on the GPU as the last stage of the plan (csrc/pose.hip) and the files are written from its rows.
 """
 
 import argparse
@@ -53,6 +54,9 @@ def parse_args(args):
                         help='Arithmetic of the conv stack (not in the reference CLI).  Default f16x3: the fastest type whose detections, plane '
                              'indices and 3-D corners stay within 1e-3 of the float32 (reference floatx) path; f32 = floatx itself; '
                              'bf16x3 / f16 / bf16 are faster and leave that tolerance.')
+    parser.add_argument('--device-pose', action='store_true',
+                        help='Pose recovery and KITTI fields on the GPU (not in the reference CLI): the model is loaded with pose=True and '
+                             'the .mat and KITTI files are written from the rows of its pose stage; --save-images is unaffected.')
     return parser.parse_args(args)
 
 
@@ -97,12 +101,32 @@ def write_results(args, output_dir, item, det):
             print('--save-images needs OpenCV (cv2), which is not installed: skipping the composite image')
 
 
+def write_results_from_rows(args, output_dir, item, rows_b, count):
+    """ write_results for one image's rows of the device pose stage (model.predict_poses_on_batch) """
+    stem = os.path.basename(item['image_fp'])[:-3]
+    det = gpp_utils.detections_from_rows(rows_b, count)
+    outputs = {'boxes': det['boxes'][:, :4], 'keypoints': det['boxes'][:, 4:], 'labels': det['labels'], 'scores': det['scores'],
+               'locations': det['locations'], 'angles': det['angles'], 'dimensions': det['dimensions'], 'residuals': det['residuals']}
+    scipy.io.savemat(os.path.join(output_dir, 'outputs', 'full', stem + 'mat'), outputs)
+    if args.kitti:
+        with open(os.path.join(output_dir, 'outputs', 'kitti', stem + 'txt'), 'w') as f:
+            f.write(gpp_utils.kitti_lines_from_rows(rows_b, count))
+    if args.save_images:
+        try:
+            import cv2  # noqa: F401
+        except ImportError:
+            print('--save-images needs OpenCV (cv2), which is not installed: skipping the composite image')
+
+
 def main(args=None):
     if args is None:
         args = sys.argv[1:]
     args = parse_args(args)
 
-    model = models.load_model(args.model_path, backbone_name=args.backbone, dtype=args.dtype)
+    if args.device_pose:
+        model = models.load_model(args.model_path, backbone_name=args.backbone, dtype=args.dtype, pose=True)
+    else:
+        model = models.load_model(args.model_path, backbone_name=args.backbone, dtype=args.dtype)
     plane_params = scipy.io.loadmat(args.plane_params_path)['road_planes_database']
     output_dir = make_output_tree(args)
 
@@ -119,6 +143,15 @@ def main(args=None):
             P_inv = np.stack([it['P_inv'] for it in group])
             planes = np.tile(plane_params[None], (len(group), 1, 1))
             t0 = time.time()
+            if args.device_pose:
+                frames = np.stack([it['raw_image'] for it in group])
+                (rows, counts), _ = model.predict_poses_on_frames(frames, P_inv, planes)
+                dt = time.time() - t0
+                for k, it in enumerate(group):
+                    print("Image {}: frame rate: {:.2f}".format(j, len(group) / dt))
+                    j += 1
+                    write_results_from_rows(args, output_dir, it, rows[k], counts[k])
+                continue
             if on_device:
                 outputs = model.predict_on_frames(np.stack([it['raw_image'] for it in group]), P_inv, planes)[0][:8]
             else:

@@ -46,7 +46,7 @@ def backbone(backbone_name):
 
 
 def load_model(filepath, backbone_name='resnet50', convert=False, nms=True, class_specific_filter=True,
-               orientation_specific_filter=False, dtype=None, on_range_event=None, plan=None):
+               orientation_specific_filter=False, dtype=None, on_range_event=None, plan=None, pose=False):
     """ Loads a RetinaNet-3D inference model (reference models/__init__.py:59-88).
 
     `convert` is accepted for signature compatibility: every model this function returns already
@@ -70,6 +70,9 @@ def load_model(filepath, backbone_name='resnet50', convert=False, nms=True, clas
                            loop over more workgroups.  The split is a rule of (layer, plan) -- never of the batch, the tile or a timing -- so a
                            model gives byte-identical results at every batch size and on every rank WITHIN its plan mode; between the two modes
                            results differ by float32 summation order only (both inside the parity bars, tests/test_latency_plan_gpu.py)
+    `pose` (not in the reference; default False): the plan ends with the pose stage (gpp_pose_f32: what bin/run_network.py does on the host
+    after predict_on_batch, on the device) and the model has predict_poses_on_batch / predict_poses_on_frames, which return one
+    (B, 100, 36) table of rows (include/gpp.h) and the number of detections per image.  predict_on_batch is unchanged either way.
     """
     import os
     if dtype is None:
@@ -86,7 +89,7 @@ def load_model(filepath, backbone_name='resnet50', convert=False, nms=True, clas
     else:
         w = W.load_weights(filepath)
     model = RetinaNet3D(w, backbone_name=name, dtype=dtype, nms=nms, class_specific_filter=class_specific_filter,
-                        orientation_specific_filter=orientation_specific_filter, on_range_event=on_range_event, plan=plan)
+                        orientation_specific_filter=orientation_specific_filter, on_range_event=on_range_event, plan=plan, pose=pose)
     if convert:
         model.summary()
     return model

@@ -39,7 +39,7 @@ from ..backend import hip
 from ..layers import conv as C
 from ..layers.filter_detections import MAX_DETECTIONS, NMS_THRESHOLD, SCORE_THRESHOLD
 from ..utils import anchors as anchor_utils
-from ..utils.gpp_utils import POLL_THRESHOLD
+from ..utils.gpp_utils import POLL_THRESHOLD, POSE_SCORE_THRESHOLD
 from . import weights as W
 
 
@@ -73,6 +73,12 @@ class PollDesc(ctypes.Structure):
                 ('planes_batched', ctypes.c_int32), ('thr', ctypes.c_float), ('reserved', ctypes.c_int32)]
 
 
+class PoseDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ('boxes', 'dims', 'scores', 'labels', 'orientations', 'keypoints', 'residuals',
+                                               'frame_info', 'rows', 'counts')] + \
+               [('B', ctypes.c_int32), ('D', ctypes.c_int32), ('score_thr', ctypes.c_float), ('reserved', ctypes.c_int32)]
+
+
 class PreactDesc(ctypes.Structure):
     _fields_ = [('conv', ctypes.c_void_p), ('in_scale', ctypes.c_void_p), ('in_shift', ctypes.c_void_p)]
 
@@ -100,6 +106,7 @@ OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT = 8, 9, 10
 OP_DETECT_OSF = 12
 OP_STEM_POOL = 13
 OP_MAXPOOL_PAD, OP_AVGPOOL, OP_CONV_PREACT = 17, 18, 32         # DenseNet (include/gpp.h)
+OP_POSE = 19                                                    # RetinaNet3D(pose=True): gpp_pose_f32 behind the polling
 DETECT_OPS = (OP_DETECT, OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT, 12)
 OP_JOIN, OP_SYNC = 0x10000, 0x20000
 
@@ -225,13 +232,15 @@ class Plan(object):
 
     @staticmethod
     def stage_of(kind, name):
-        """ include/gpp.h GPP_OP_STAGE: 1 stem, 2 backbone, 3 FPN, 4 heads, 5 decode, 6 polling (roctx ranges under GPP_ROCTX=1) """
+        """ include/gpp.h GPP_OP_STAGE: 1 stem, 2 backbone, 3 FPN, 4 heads, 5 decode, 6 polling, 8 pose (roctx ranges under GPP_ROCTX=1) """
         if kind in (OP_STEM, OP_MAXPOOL, OP_STEM_POOL, OP_MAXPOOL_PAD):
             return 1
         if kind in DETECT_OPS:
             return 5
         if kind == OP_POLL:
             return 6
+        if kind == OP_POSE:
+            return 8
         if name.startswith('res') or kind in (OP_CONV_PREACT, OP_AVGPOOL) or name.startswith(('conv2_', 'conv3_', 'conv4_', 'conv5_')):
             return 2
         if name.startswith('pyramid_'):
@@ -249,8 +258,11 @@ class RetinaNet3D(object):
     """ Inference model: ResNet-50/101/152 or DenseNet-121/169/201 + FPN + heads + decode + ground-plane polling. """
 
     def __init__(self, weights, backbone_name='resnet50', dtype='f16x3', nms=True, class_specific_filter=True,
-                 orientation_specific_filter=False, name='retinanet-bbox', on_range_event=None, plan=None):
+                 orientation_specific_filter=False, name='retinanet-bbox', on_range_event=None, plan=None, pose=False):
         import torch
+        # pose=True: every plan ends with the pose stage (gpp_pose_f32 on the polling outputs) and predict_poses_on_batch /
+        # predict_poses_on_frames fetch its rows; a model attribute, not a plan switch: without it every plan is what it was
+        self.pose = bool(pose)
         # 'throughput' | 'latency' (models.load_model): which layers split their K loop (layers/conv.latency_split)
         self.plan_mode = plan or os.environ.get('GPP_PLAN', 'throughput')
         if self.plan_mode not in ('throughput', 'latency'):
@@ -679,6 +691,24 @@ class RetinaNet3D(object):
                   [plan.keypoints, plan.keyplanes, plan.residuals, plan.best_index, plan.poll_ws], tag=2,    # tag 2: bench.py times it live too
                   flops=162.0 * B * D * n_planes)
 
+    def _pose(self, plan, B):
+        """ 6-DoF pose + KITTI fields of the detections (what bin/run_network.py does on the host after predict_on_batch), on lane 0
+        behind the polling.  Rows, range-event snapshot and counts share ONE flat buffer, so that one copy brings a call's result to
+        the host: [B x D x 36 rows | 2 words: the plan's range counter as the stream saw it | B counts (int32 bits)]. """
+        torch, dev, D = self.torch, self.device, MAX_DETECTIONS
+        n = B * D * hip.GPP_POSE_COLS
+        plan.pose_out = torch.zeros((n + 2 + B,), dtype=torch.float32, device=dev)
+        plan.pose_rows = plan.pose_out[:n].view(B, D, hip.GPP_POSE_COLS)
+        plan.pose_counts = plan.pose_out[n + 2:].view(torch.int32)
+        # per image: the image scale, the raw image's height and width (predict_poses_*: uploaded with P_inv; a captured graph reads
+        # the buffer, not the values).  Until a caller says otherwise: the frame as it is, scale 1
+        plan.frame_info = torch.tensor([[1.0, plan.shape[1], plan.shape[2]]] * B, dtype=torch.float32, device=dev)
+        pd = PoseDesc(plan.boxes.data_ptr(), plan.dimensions.data_ptr(), plan.scores.data_ptr(), plan.labels.data_ptr(),
+                      plan.orientations.data_ptr(), plan.keypoints.data_ptr(), plan.residuals.data_ptr(), plan.frame_info.data_ptr(),
+                      plan.pose_rows.data_ptr(), plan.pose_counts.data_ptr(), B, D, POSE_SCORE_THRESHOLD, 0)
+        plan.emit(OP_POSE, pd, 'recover_pose', [plan.boxes, plan.dimensions, plan.scores, plan.labels, plan.orientations, plan.keypoints,
+                                                plan.residuals, plan.frame_info], [plan.pose_rows, plan.pose_counts])
+
     def _bind_workspaces(self, plan):
         """ split-K partial tiles of the deep-K layers with a tiny per-image grid (res5 branch2b, P5..P7): one workspace per stream lane
         (concurrent launches must not share partial tiles), sized from the descriptors of the whole plan """
@@ -775,6 +805,8 @@ class RetinaNet3D(object):
         outs, decode = self._detect(plan, B, self._anchor_table((H, Wd), shapes if self.densenet else None), pyramid)
         self._heads(plan, opts, P, pyramid, outs, decode)
         self._poll(plan, B, n_planes, planes_batched)
+        if self.pose:
+            self._pose(plan, B)
         self._bind_workspaces(plan)
         plan.finalize()
         plan.tagged = [name for _, tag, _, name, _ in plan.ops if tag]
@@ -1089,7 +1121,7 @@ class RetinaNet3D(object):
         if self._twin is None:
             self._twin = RetinaNet3D(self._weights, backbone_name=self.backbone_name, dtype='f32', nms=self.nms,
                                      class_specific_filter=self.class_specific_filter, orientation_specific_filter=self.osf,
-                                     name=self.name + '-f32-twin', plan=self.plan_mode)
+                                     name=self.name + '-f32-twin', plan=self.plan_mode, pose=self.pose)
             self._weights = None
         if B is not None:
             self._twin.plan_for(B, H, Wd, n_planes, planes_batched)
@@ -1183,6 +1215,68 @@ class RetinaNet3D(object):
         plan, scale = self.stage_frames(frames_u8, P_inv, planes)
         self.run_plan(plan)
         return self.fetch(plan), scale
+
+    # ------------------------------------------------------------------ pose rows (pose=True)
+    def _require_pose(self):
+        if not self.pose:
+            raise hip.GppError('this model has no pose stage: load it with pose=True (models.load_model(..., pose=True))')
+
+    def put_frame_info(self, plan, scales, image_shapes):
+        """ (scale, raw height, raw width) of every image of the batch into the plan's frame_info buffer (asynchronous) """
+        B = plan.shape[0]
+        info = np.empty((B, 3), np.float32)
+        info[:, 0] = np.asarray(scales, dtype=np.float64).reshape(-1)                       # one scale, or one per image
+        info[:, 1:] = np.asarray(image_shapes, dtype=np.float64).reshape(-1, len(np.atleast_2d(image_shapes)[0]))[:, :2]
+        plan.frame_info.copy_(self.torch.as_tensor(info), non_blocking=True)
+
+    def fetch_poses(self, plan):
+        """ (rows (B, 100, 36) float32, counts (B,) int32) of the plan's last run: one copy (synchronises); None in place of the result
+        when the half-range watch of dtype='f16x3' saw an event in that run (the caller re-runs on the float32 twin) """
+        B = plan.shape[0]
+        n = plan.pose_rows.numel()
+        watch = self.watches_range()
+        if watch:
+            self.range_snapshot(plan, plan.pose_out[n:n + 2])
+        flat = plan.pose_out.cpu().numpy()
+        if watch and self.note_range(plan, int(flat[n:n + 2].view(np.uint64)[0])):
+            return None
+        return flat[:n].reshape(tuple(plan.pose_rows.shape)).copy(), flat[n + 2:].view(np.int32).copy()
+
+    def predict_poses_on_batch(self, inputs, scales, image_shapes):
+        """ predict_on_batch + what bin/run_network.py does with its result on the host, on the device: inputs as predict_on_batch;
+        scales: the image scale of every image (or one for all); image_shapes: the raw images' (height, width[, 3]) (or one for all).
+        Returns (rows (B, 100, 36) float32 -- include/gpp.h, gpp_pose_f32 --, counts (B,) int32: the detections above the score
+        threshold, which are the first counts[b] rows of image b).  utils.gpp_utils.detections_from_rows / kitti_lines_from_rows
+        turn one image's rows into the dict of recover_pose / the KITTI text. """
+        self._require_pose()
+        plan = self.stage_inputs(inputs)
+        self.put_frame_info(plan, scales, image_shapes)
+        self.run_plan(plan)
+        out = self.fetch_poses(plan)
+        if out is None:          # an activation left the half range: this call's answer comes from the float32 twin
+            self._range_event_raise_or_prepare('predict_poses_on_batch')
+            return self._twin.predict_poses_on_batch([plan.images, plan.P_inv, plan.planes], scales, image_shapes)
+        return out
+
+    def predict_poses_on_frames(self, frames_u8, P_inv, planes):
+        """ predict_poses_on_batch for raw uint8 BGR frames (predict_on_frames): returns ((rows, counts), scale) """
+        self._require_pose()
+        plan, scale = self.stage_frames(frames_u8, P_inv, planes)
+        self.put_frame_info(plan, scale, tuple(frames_u8.shape[1:3]))
+        self.run_plan(plan)
+        out = self.fetch_poses(plan)
+        if out is None:
+            self._range_event_raise_or_prepare('predict_poses_on_frames')        # (the preprocessed frames are still in the plan)
+            out = self._twin.predict_poses_on_batch([plan.images, plan.P_inv, plan.planes], scale, tuple(frames_u8.shape[1:3]))
+        return out, scale
+
+    def _range_event_raise_or_prepare(self, what):
+        """ the bookkeeping of _range_event for the pose calls: count the event, raise (on_range_event='raise') or build the twin """
+        self.range_fallbacks += 1
+        if self.on_range_event == 'raise':
+            raise hip.GppError('{}: an activation left the IEEE-half range of dtype=\'f16x3\' (gpp_x3_range_events): load the model '
+                               'with dtype=\'f32\' or on_range_event=\'f32\''.format(what))
+        self.prepare_fallback()
 
     # Keras-style conveniences used by the reference's scripts
     def predict(self, inputs, batch_size=None, verbose=0):

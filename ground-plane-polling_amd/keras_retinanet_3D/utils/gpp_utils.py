@@ -10,6 +10,8 @@ Reference code restated here (citations relative to /root/reference/keras_retina
                            `else` branch :248-287 unreachable)
     cuboid_corners         bin/run_network.py:298-310
     kitti_lines            bin/run_network.py:295-330
+    recover_pose_device    bin/run_network.py:113-330 in one launch -> HIP kernel, csrc/pose.hip; detections_from_rows and
+                           kitti_lines_from_rows read its rows (include/gpp.h, gpp_pose_f32)
 """
 
 import numpy as np
@@ -17,6 +19,7 @@ import numpy as np
 from ..backend import hip
 
 POLL_THRESHOLD = 0.7      # metres, fit_road_planes.py:94
+POSE_SCORE_THRESHOLD = 0.05      # run_network.py:117
 
 
 def _as_device(x, dtype, device):
@@ -81,6 +84,67 @@ def fit_road_planes(boxes, dimensions, orientations, P_inv, planes, return_index
     if numpy_out:
         out = [o.cpu().numpy() for o in out]
     return out
+
+
+def recover_pose_device(outputs, scales, image_shapes, score_threshold=POSE_SCORE_THRESHOLD):
+    """ select_detections + recover_pose + the arithmetic of kitti_lines for a whole batch in one launch (HIP kernel, gfx950).
+
+        outputs       the 8 model outputs (boxes, dimensions, scores, labels, orientations, keypoints, keyplanes, residuals)
+        scales        the image scale of every image of the batch, or one for all
+        image_shapes  the raw images' (height, width[, channels]), one per image or one for all
+    Returns (rows (B, D, 36) float32, counts (B,) int32): row d of image b belongs to detection d, layout in include/gpp.h; a row whose
+    score is not above the threshold (or padding) is -1 everywhere; counts[b] rows of image b are above it (the first counts[b]: decode
+    emits scores in descending order).  NumPy in -> NumPy out; torch tensors in -> torch tensors (on the device) out. """
+    import torch
+    device = hip.require_device()
+    numpy_out = not isinstance(outputs[0], torch.Tensor)
+    boxes, dims, scores, labels, orient, keypoints, _, residuals = outputs[:8]
+    boxes_d = _as_device(boxes, torch.float32, device)
+    if boxes_d.dim() != 3 or boxes_d.shape[2] != 12:
+        raise ValueError('boxes must be (B, D, 12), got {}'.format(tuple(boxes_d.shape)))
+    B, D = int(boxes_d.shape[0]), int(boxes_d.shape[1])
+    dims_d, scores_d, residuals_d = (_as_device(x, torch.float32, device) for x in (dims, scores, residuals))
+    labels_d, orient_d = (_as_device(x, torch.int32, device) for x in (labels, orient))
+    keypoints_d = _as_device(keypoints, torch.float32, device)
+    if tuple(dims_d.shape) != (B, D, 3) or tuple(keypoints_d.shape) != (B, D, 4, 3) or \
+            any(tuple(t.shape) != (B, D) for t in (scores_d, labels_d, orient_d, residuals_d)):
+        raise ValueError('inconsistent shapes: dimensions {}, scores {}, labels {}, orientations {}, keypoints {}, residuals {}'.format(
+            *[tuple(t.shape) for t in (dims_d, scores_d, labels_d, orient_d, keypoints_d, residuals_d)]))
+    info = np.empty((B, 3), np.float32)
+    info[:, 0] = np.asarray(scales, dtype=np.float64).reshape(-1)
+    info[:, 1:] = np.asarray(image_shapes, dtype=np.float64).reshape(-1, len(np.atleast_2d(image_shapes)[0]))[:, :2]
+    info_d = torch.as_tensor(info).to(device)
+    rows = torch.empty((B, D, hip.GPP_POSE_COLS), dtype=torch.float32, device=device)
+    counts = torch.zeros((B,), dtype=torch.int32, device=device)
+    if B * D > 0:
+        hip.check(hip.lib().gpp_pose_f32(hip.ptr(boxes_d), hip.ptr(dims_d), hip.ptr(scores_d), hip.ptr(labels_d), hip.ptr(orient_d),
+                                         hip.ptr(keypoints_d), hip.ptr(residuals_d), hip.ptr(info_d), B, D, float(score_threshold),
+                                         hip.ptr(rows), hip.ptr(counts), hip.stream_ptr()), 'gpp_pose_f32')
+    if numpy_out:
+        return rows.cpu().numpy(), counts.cpu().numpy()
+    return rows, counts
+
+
+def detections_from_rows(rows_b, count):
+    """ one image's rows (D, 36) of recover_pose_device / predict_poses_on_batch and its count -> the dict recover_pose returns
+    (float32 arrays, int32 labels and orientations), plus the KITTI fields 'alpha', 'kitti_box', 'kitti_h', 'kitti_y', 'r_y'.
+    The 3-D 'keypoints' and the 'keyplanes' of select_detections are not part of a row: they stay in the model outputs. """
+    r = np.asarray(rows_b, dtype=np.float32)[:int(count)]
+    return {'boxes': r[:, 0:12].copy(), 'scores': r[:, 12].copy(), 'labels': r[:, 13].astype(np.int32), 'orientations': r[:, 14].astype(np.int32),
+            'residuals': r[:, 15].copy(), 'dimensions': r[:, 16:19].copy(), 'locations': r[:, 19:22].copy(), 'angles': r[:, 22:25].copy(),
+            'alpha': r[:, 25].copy(), 'kitti_box': r[:, 26:30].copy(), 'kitti_h': r[:, 30].copy(), 'kitti_y': r[:, 31].copy(), 'r_y': r[:, 32].copy()}
+
+
+KITTI_FORMAT = "Car -1 -1 %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f %.2f\n"
+KITTI_COLUMNS = (25, 26, 27, 28, 29, 30, 17, 18, 19, 31, 21, 32, 12)      # alpha, clipped box, h, w, l, x, y, z, r_y, score
+
+
+def kitti_lines_from_rows(rows_b, count):
+    """ the KITTI result text of one image from its rows: ONE format call for all of its lines, byte for byte what kitti_lines' `%` per
+    detection gives on the same float32 numbers (run_network.py:329-330) """
+    n = int(count)
+    values = np.asarray(rows_b, dtype=np.float32)[:n][:, KITTI_COLUMNS].astype(np.float64)
+    return (KITTI_FORMAT * n) % tuple(values.ravel().tolist())
 
 
 def load_calibration(calib_path, image_scale):

@@ -406,6 +406,41 @@ int gpp_pack_detections(const float* boxes, const float* dims, const float* scor
                         const float* residuals, int B, int D, float* packed, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * 6-DoF pose and KITTI fields of the detections on the device (csrc/pose.hip): what bin/run_network.py does on the host after
+ * predict_on_batch -- scale correction and selection (reference run_network.py:113-135), pose from the 3-D keypoints (:137-247),
+ * cuboid corners and the KITTI fields (:298-330).  One thread per detection; the float32 inputs are read once, every step is
+ * float64, and each value is rounded to float32 once, where it is stored.
+ *
+ *   boxes (B, D, 12), dims (B, D, 3), scores (B, D), labels (B, D), orientations (B, D), keypoints (B, D, 4, 3),
+ *   residuals (B, D): the outputs of gpp_detect_f32 / gpp_poll_f32.
+ *   frame_info (B, 3) float32, device: per image the image scale, the raw image's height and its width.
+ *   rows (B, D, GPP_POSE_COLS) float32: row d of image b belongs to detection d (no compaction).  A row whose score is not above
+ *   score_thr, or whose orientation is -1 (padding), is -1 in every column and is not counted in counts[b].
+ *
+ *   columns   content
+ *    0 -  3   box x1 y1 x2 y2 divided by the scale
+ *    4 - 11   2-D keypoints xl yl xm ym xr yr xt yt divided by the scale
+ *   12 - 15   score, label, orientation class, polling residual (passed through)
+ *   16 - 18   dimensions h w l: h = |X_t - X_m|, l = |X_s - X_m| (X_s = X_l for orientation 0 and 3, X_r for 1 and 2), w the network's
+ *   19 - 21   location (centre of the bottom face)
+ *   22 - 24   rotation vector (axis * angle) of the polar factor U V^T of [x y z]
+ *   25        alpha, in [-pi, pi)
+ *   26 - 29   the box clipped to the raw image: max(x1, 0) max(y1, 0) min(x2, width) min(y2, height)
+ *   30 - 32   KITTI height (corner Y max - min), KITTI y (corner Y max), r_y in [-pi, pi)
+ *   33 - 35   0
+ *
+ *   A KITTI result line is columns 25, 26-29, 30, 17, 18, 19, 31, 21, 32, 12 in that order.
+ *   A detection with a zero-length edge (h = 0 or l = 0: [x y z] is not finite), or one whose two edges are parallel ([x y z] is singular),
+ *   has NaN in columns 19-25 and 30-32; its other columns and every other row are as usual.
+ *   Null pointer or negative size: GPP_ERR_BAD_ARG, nothing launched.  B * D == 0: GPP_OK, nothing launched.
+ * ---------------------------------------------------------------------------------------- */
+#define GPP_POSE_COLS 36
+int gpp_pose_f32(const float* boxes, const float* dims, const float* scores, const int32_t* labels,
+                 const int32_t* orientations, const float* keypoints, const float* residuals,
+                 const float* frame_info, int B, int D, float score_thr,
+                 float* rows, int32_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Plan execution: one call enqueues a whole predict_on_batch (every kernel of the graph that
  * models/retinanet.py:359-422 `retinanet_bbox` builds) from a host array of descriptors.
  * The runner holds no state: the caller (Python) keeps the descriptors and buffers alive.
@@ -429,6 +464,7 @@ int gpp_pack_detections(const float* boxes, const float* dims, const float* scor
 #define GPP_OP_BOTTLENECK_BLOCK 16       /* gpp_block_desc -> gpp_bottleneck_block */
 #define GPP_OP_MAXPOOL_PAD 17            /* gpp_dense_pool_desc -> gpp_maxpool3x3s2_pad_f32 (DenseNet pool1) */
 #define GPP_OP_AVGPOOL 18                /* gpp_dense_pool_desc -> gpp_avgpool2x2_f32 (DenseNet transitions) */
+#define GPP_OP_POSE 19                   /* gpp_pose_desc -> gpp_pose_f32 (opt-in: RetinaNet3D(pose=True)) */
 #define GPP_OP_CONV_PREACT 32            /* gpp_preact_desc -> gpp_conv2d_preact (DenseNet); kinds 0..255 exist */
 /* (14, 15: the Winograd F(2, 3) form of the tower layers of round 5 -- built, measured at -2 % of the step, shelved in round 6:
    tools/experiments/winograd/) */
@@ -445,7 +481,7 @@ int gpp_pack_detections(const float* boxes, const float* dims, const float* scor
 #define GPP_OP_SYNC 0x20000
 
 /* Optional stage label of an op, bits 20-23 of `kind`: with GPP_ROCTX=1 in the environment gpp_plan_run opens a roctx range ("gpp:stem", "gpp:backbone",
-   "gpp:fpn", "gpp:heads", "gpp:decode", "gpp:polling") around each run of consecutive ops with the same label (rocprofv3 --marker-trace); 0 = none.
+   "gpp:fpn", "gpp:heads", "gpp:decode", "gpp:polling", "gpp:pose") around each run of consecutive ops with the same label (rocprofv3 --marker-trace); 0 = none.
    The marker library is looked up at run time; without the variable nothing is loaded.  GPP_ROCTX=2 additionally synchronises the device where a range opens and
    closes: a range's duration in the marker trace is then its stage's time on the device (tools/roctx_stages.sh); a measuring mode, not a production one. */
 #define GPP_OP_STAGE(s) (((s) & 15) << 20)
@@ -455,6 +491,7 @@ int gpp_pack_detections(const float* boxes, const float* dims, const float* scor
 #define GPP_STAGE_HEADS 4
 #define GPP_STAGE_DECODE 5
 #define GPP_STAGE_POLLING 6
+#define GPP_STAGE_POSE 8
 
 typedef struct gpp_stem_desc { const float* in; const void* weight; const float* bias; void* out;
                                int32_t dtype, B, H, W; uint64_t* range_counter; /* GPP_F16X3: see gpp_stem_conv7x7_bn_relu_x3_rc; NULL otherwise */
@@ -477,6 +514,13 @@ typedef struct gpp_poll_desc {
     int32_t B, D, N, planes_batched;
     float thr; int32_t reserved;
 } gpp_poll_desc;
+
+typedef struct gpp_pose_desc {
+    const float* boxes; const float* dims; const float* scores; const int32_t* labels; const int32_t* orientations;
+    const float* keypoints; const float* residuals; const float* frame_info; float* rows; int32_t* counts;
+    int32_t B, D;
+    float score_thr; int32_t reserved;
+} gpp_pose_desc;
 
 typedef struct gpp_tail_desc { const gpp_conv_desc* conv3x3; const gpp_conv_desc* conv1x1; int32_t tile_rows, reserved; } gpp_tail_desc;
 typedef struct gpp_block_desc { const gpp_conv_desc* conv1x1_a; const gpp_conv_desc* conv3x3_b; const gpp_conv_desc* conv1x1_c; int32_t tile, reserved; } gpp_block_desc;
