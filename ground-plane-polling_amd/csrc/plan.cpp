@@ -208,6 +208,14 @@ extern "C" int gpp_plan_run(const gpp_plan_op* ops, int n_ops, void* stream, voi
             rc = gpp_avgpool2x2_f32(d->in, d->out, d->B, d->H, d->W, d->C, d->out_pitch, stream);
             break;
         }
+        case GPP_OP_MOBILENET_STEM: {
+            const gpp_mobilenet_stem_desc* d = (const gpp_mobilenet_stem_desc*)op.desc;
+            rc = gpp_mobilenet_stem(d->in, d->weight, d->bias, d->out, d->B, d->H, d->W, d->C_out, d->out_pitch, stream);
+            break;
+        }
+        case GPP_OP_MOBILENET_BLOCK:
+            rc = gpp_mobilenet_block((const gpp_mobilenet_block_desc*)op.desc, stream);
+            break;
         case GPP_OP_RELU: {
             const gpp_relu_desc* d = (const gpp_relu_desc*)op.desc;
             rc = gpp_relu_strided(d->in, d->in_bstride, d->out, d->out_bstride, d->dtype, d->B, d->count, stream);

@@ -72,6 +72,20 @@ class ConvDesc(ctypes.Structure):
                 ('x3_split', ctypes.c_int32), ('reserved2', ctypes.c_int32), ('out_scale', c_void_p), ('range_counter', c_void_p)]
 
 
+class MobileNetBlockDesc(ctypes.Structure):
+    """ gpp_mobilenet_block_desc (include/gpp.h) """
+    _fields_ = [('inp', c_void_p), ('dw_weight', c_void_p), ('dw_bias', c_void_p), ('pw_weight', c_void_p), ('pw_bias', c_void_p),
+                ('out_scale', c_void_p), ('out', c_void_p)] + \
+               [(n, ctypes.c_int32) for n in ('dtype', 'B', 'H', 'W', 'C_in', 'C_out', 'stride', 'in_pitch', 'out_pitch', 'weight_rows',
+                                              'tile_hint', 'reserved')]
+
+
+class MobileNetStemDesc(ctypes.Structure):
+    """ gpp_mobilenet_stem_desc (include/gpp.h) """
+    _fields_ = [('inp', c_void_p), ('weight', c_void_p), ('bias', c_void_p), ('out', c_void_p)] + \
+               [(n, ctypes.c_int32) for n in ('B', 'H', 'W', 'C_out', 'out_pitch', 'reserved')]
+
+
 def _declare(lib):
     lib.gpp_version.restype = ctypes.c_char_p
     lib.gpp_version.argtypes = []
@@ -109,6 +123,17 @@ def _declare(lib):
     lib.gpp_maxpool3x3s2_pad_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
     lib.gpp_avgpool2x2_f32.restype = c_int
     lib.gpp_avgpool2x2_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]
+    # MobileNet (include/gpp.h): the fused depthwise-separable block and the 3x3 / 2 stem
+    lib.gpp_mobilenet_block.restype = c_int
+    lib.gpp_mobilenet_block.argtypes = [ctypes.POINTER(MobileNetBlockDesc), c_void_p]
+    lib.gpp_mobilenet_block_tile_candidates.restype = c_int
+    lib.gpp_mobilenet_block_tile_candidates.argtypes = [ctypes.POINTER(MobileNetBlockDesc), ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_int)]
+    lib.gpp_mobilenet_block_autotune.restype = c_int
+    lib.gpp_mobilenet_block_autotune.argtypes = [ctypes.POINTER(MobileNetBlockDesc), c_int, c_void_p, ctypes.POINTER(c_float)]
+    lib.gpp_mobilenet_stem.restype = c_int
+    lib.gpp_mobilenet_stem.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]
+    lib.gpp_mobilenet_depthwise.restype = c_int
+    lib.gpp_mobilenet_depthwise.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
     lib.gpp_relu.restype = c_int
     lib.gpp_relu.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_void_p]
     lib.gpp_preprocess_u8_bgr.restype = c_int

@@ -48,7 +48,9 @@ def parse_args(args):
     parser.add_argument('output_dir', help='Path to output directory', type=str)
     parser.add_argument('--kitti', help='Include to save results in KITTI format.', action='store_true')
     parser.add_argument('--save-images', help='Include to save result images.', action='store_true')
-    parser.add_argument('--backbone', help='The backbone of the model to load.', default='resnet50')
+    parser.add_argument('--backbone', default='resnet50',
+                        help='The backbone of the model to load: resnet50 | resnet101 | resnet152 | densenet121 | densenet169 | densenet201 | '
+                             'mobilenet{128,160,192,224}_{0.25,0.5,0.75,1.0}, e.g. mobilenet224_1.0.')
     parser.add_argument('--batch-size', help='Images per predict_on_batch call.', type=int, default=1)
     parser.add_argument('--dtype', default='f16x3', choices=['f16x3', 'f32', 'bf16x3', 'f16', 'bf16'],
                         help='Arithmetic of the conv stack (not in the reference CLI).  Default f16x3: the fastest type whose detections, plane '

@@ -40,6 +40,12 @@ def backbone(backbone_name):
         from .resnet import ResNetBackbone as b
     elif 'densenet' in backbone_name:
         from .densenet import DenseNetBackbone as b
+    elif 'mobilenet' in backbone_name and '_' in backbone_name:
+        from .mobilenet import MobileNetBackbone as b
+    elif 'mobilenet' in backbone_name:
+        # (the reference cannot build such a name either: float(backbone.split('_')[1]), its models/mobilenet.py:94)
+        raise NotImplementedError('Backbone class for  \'{}\' not implemented: a MobileNet name carries its width multiplier, '
+                                  '\'mobilenet224_1.0\' (the multiplier is missing).'.format(backbone_name))
     else:
         raise NotImplementedError('Backbone class for  \'{}\' not implemented.'.format(backbone_name))
     return b(backbone_name)
@@ -51,8 +57,8 @@ def load_model(filepath, backbone_name='resnet50', convert=False, nms=True, clas
 
     `convert` is accepted for signature compatibility: every model this function returns already
     contains the decode / NMS / ground-plane-polling stages (`retinanet_bbox`, retinanet.py:359-422).
-    `backbone_name`: 'resnet50' | 'resnet101' | 'resnet152' | 'densenet121' | 'densenet169' | 'densenet201' (DenseNet: dtype 'f32',
-    'f16x3' or 'bf16x3' only).
+    `backbone_name`: 'resnet50' | 'resnet101' | 'resnet152' | 'densenet121' | 'densenet169' | 'densenet201' |
+    'mobilenet{128,160,192,224}_{0.25,0.5,0.75,1.0}' (DenseNet and MobileNet: dtype 'f32', 'f16x3' or 'bf16x3' only).
     `dtype` (not in the reference; None = the environment's GPP_DTYPE, else 'f16x3'):
         'f16x3' (default)  float32-sized storage, every float32 product as three IEEE-half matrix products: the fastest type whose
                            detections, plane indices and 3-D corners stay within BASELINE's tolerance of the float32 path
@@ -80,7 +86,7 @@ def load_model(filepath, backbone_name='resnet50', convert=False, nms=True, clas
     from . import weights as W
     from .retinanet import RetinaNet3D
     b = backbone(backbone_name)
-    name = b.backbone.split('_')[0]
+    name = b.backbone if W.is_mobilenet(b.backbone) else b.backbone.split('_')[0]      # (a MobileNet name carries its width multiplier)
     if isinstance(filepath, dict):
         w = filepath
     elif isinstance(filepath, str) and filepath.startswith('synthetic'):

@@ -37,6 +37,7 @@ import numpy as np
 
 from ..backend import hip
 from ..layers import conv as C
+from ..layers import mobilenet as M
 from ..layers.filter_detections import MAX_DETECTIONS, NMS_THRESHOLD, SCORE_THRESHOLD
 from ..utils import anchors as anchor_utils
 from ..utils.gpp_utils import POLL_THRESHOLD, POSE_SCORE_THRESHOLD
@@ -106,6 +107,7 @@ OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT = 8, 9, 10
 OP_DETECT_OSF = 12
 OP_STEM_POOL = 13
 OP_MAXPOOL_PAD, OP_AVGPOOL, OP_CONV_PREACT = 17, 18, 32         # DenseNet (include/gpp.h)
+OP_MOBILENET_STEM, OP_MOBILENET_BLOCK = 33, 34                  # MobileNet (include/gpp.h)
 OP_POSE = 19                                                    # RetinaNet3D(pose=True): gpp_pose_f32 behind the polling
 DETECT_OPS = (OP_DETECT, OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT, 12)
 OP_JOIN, OP_SYNC = 0x10000, 0x20000
@@ -233,7 +235,7 @@ class Plan(object):
     @staticmethod
     def stage_of(kind, name):
         """ include/gpp.h GPP_OP_STAGE: 1 stem, 2 backbone, 3 FPN, 4 heads, 5 decode, 6 polling, 8 pose (roctx ranges under GPP_ROCTX=1) """
-        if kind in (OP_STEM, OP_MAXPOOL, OP_STEM_POOL, OP_MAXPOOL_PAD):
+        if kind in (OP_STEM, OP_MAXPOOL, OP_STEM_POOL, OP_MAXPOOL_PAD, OP_MOBILENET_STEM):
             return 1
         if kind in DETECT_OPS:
             return 5
@@ -241,7 +243,7 @@ class Plan(object):
             return 6
         if kind == OP_POSE:
             return 8
-        if name.startswith('res') or kind in (OP_CONV_PREACT, OP_AVGPOOL) or name.startswith(('conv2_', 'conv3_', 'conv4_', 'conv5_')):
+        if name.startswith('res') or kind in (OP_CONV_PREACT, OP_AVGPOOL, OP_MOBILENET_BLOCK) or name.startswith(('conv2_', 'conv3_', 'conv4_', 'conv5_')):
             return 2
         if name.startswith('pyramid_'):
             return 4
@@ -255,7 +257,7 @@ class Plan(object):
 
 
 class RetinaNet3D(object):
-    """ Inference model: ResNet-50/101/152 or DenseNet-121/169/201 + FPN + heads + decode + ground-plane polling. """
+    """ Inference model: ResNet-50/101/152, DenseNet-121/169/201 or MobileNet (v1) + FPN + heads + decode + ground-plane polling. """
 
     def __init__(self, weights, backbone_name='resnet50', dtype='f16x3', nms=True, class_specific_filter=True,
                  orientation_specific_filter=False, name='retinanet-bbox', on_range_event=None, plan=None, pose=False):
@@ -284,15 +286,21 @@ class RetinaNet3D(object):
         self.osf = bool(orientation_specific_filter)     # per-orientation NMS (filter_detections.py:84-98), gpp_detect_osf_f32
         self.nms = bool(nms)
         self.name = name
-        self.backbone_name = backbone_name.split('_')[0]
+        self.mobilenet = W.is_mobilenet(backbone_name)           # 'mobilenet224_1.0': the name carries the width multiplier
+        self.backbone_name = backbone_name if self.mobilenet else backbone_name.split('_')[0]
         self.densenet = W.is_densenet(self.backbone_name)
-        if self.backbone_name not in W.BLOCKS and not self.densenet:
-            raise ValueError('Backbone (\'{}\') not in allowed backbones ({}).'.format(backbone_name, sorted(W.BLOCKS) + sorted(W.DENSENET_BLOCKS)))
+        if self.backbone_name not in W.BLOCKS and not self.densenet and not self.mobilenet:
+            raise ValueError('Backbone (\'{}\') not in allowed backbones ({}).'.format(
+                backbone_name, sorted(W.BLOCKS) + sorted(W.DENSENET_BLOCKS) + ['{}_<{}>'.format(r, '|'.join(str(a) for a in W.MOBILENET_ALPHAS))
+                                                                              for r in W.MOBILENET_ROWS]))
         if dtype not in ('bf16', 'f16', 'f32', 'bf16x3', 'f16x3'):
             raise ValueError("dtype must be 'bf16', 'f16', 'f32', 'bf16x3' or 'f16x3', got {!r}".format(dtype))
         if self.densenet and dtype not in ('f32', 'f16x3', 'bf16x3'):
             # the concatenation buffers and the pre-activation 1x1 conv (gpp_conv2d_preact) exist for float32 storage only
             raise ValueError("a DenseNet backbone runs with dtype 'f32', 'f16x3' or 'bf16x3', got {!r}".format(dtype))
+        if self.mobilenet and dtype not in ('f32', 'f16x3', 'bf16x3'):
+            # the fused depthwise-separable block (gpp_mobilenet_block) and the stem exist for float32 storage only
+            raise ValueError("a MobileNet backbone runs with dtype 'f32', 'f16x3' or 'bf16x3', got {!r}".format(dtype))
         self.dtype = dtype
         self.esz = C.elem_size(dtype)
         self.tdtype = C.torch_dtype(dtype)
@@ -322,7 +330,9 @@ class RetinaNet3D(object):
 
         if self.densenet:
             self._upload_densenet(weights, put)
-        for conv, bn, kh, kw, cin, cout, _ in (() if self.densenet else W.backbone_layers(self.backbone_name)):
+        if self.mobilenet:
+            self._upload_mobilenet(weights)
+        for conv, bn, kh, kw, cin, cout, _ in (() if self.densenet or self.mobilenet else W.backbone_layers(self.backbone_name)):
             k, b = W.folded_conv(weights, conv, bn)
             if k.shape != (kh, kw, cin, cout):
                 raise ValueError('weight {} has shape {}, expected {}'.format(conv, k.shape, (kh, kw, cin, cout)))
@@ -380,6 +390,24 @@ class RetinaNet3D(object):
             if shape[0] == 1:                   # the 1x1 convs: _1_conv and the transitions, behind the BN + ReLU just seen
                 s, t = W.bn_affine(weights, pending, eps)
                 self.preact[name] = (torch.as_tensor(s).to(dev).contiguous(), torch.as_tensor(t).to(dev).contiguous())
+
+    def _upload_mobilenet(self, weights):
+        """ MobileNet: conv1 with conv1_bn folded as [27][C] float32 (gpp_mobilenet_stem), and per block the depthwise kernel with its BN
+        folded as [9][C] float32 + bias, the pointwise kernel with its BN folded, packed for the arithmetic mode (layers/mobilenet.py) """
+        torch, dev, eps = self.torch, self.device, W.MOBILENET_BN_EPSILON
+
+        def up(a):
+            return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev).contiguous()
+        k, b = W.folded_conv(weights, 'conv1', 'conv1_bn', eps=eps)
+        self.stem_w, self.stem_b = up(k.reshape(27, k.shape[3])), up(b)
+        self.mbn_w = {}
+        for i, cin, cout, _ in W.mobilenet_blocks(self.backbone_name):
+            dw = {'dw/kernel': np.transpose(weights['conv_dw_{}/depthwise_kernel'.format(i)], (0, 1, 3, 2))}      # (3, 3, 1, C): C as outputs
+            dw.update({'bn/' + p: weights['conv_dw_{}_bn/{}'.format(i, p)] for p in ('gamma', 'beta', 'moving_mean', 'moving_variance')})
+            kd, bd = W.folded_conv(dw, 'dw', 'bn', eps=eps)
+            kp, bp = W.folded_conv(weights, 'conv_pw_{}'.format(i), 'conv_pw_{}_bn'.format(i), eps=eps)
+            pw, scale = M.pack_pointwise(kp, self.dtype, dev)
+            self.mbn_w[i] = (up(M.pack_depthwise(np.transpose(kd, (0, 1, 3, 2)))), up(bd), pw, up(bp), scale)
 
     # ------------------------------------------------------------------ plan
     def _anchor_table(self, hw, shapes=None):
@@ -548,6 +576,26 @@ class RetinaNet3D(object):
             plan.emit(OP_AVGPOOL, pd, nm + '_pool', [t], [C.FMap(nxt.buf, B, nxt.H, nxt.W, t.C, pitch=nxt.pitch)])
             c0 = t.C
         return cats
+
+    def _mobilenet_backbone(self, plan, opts, B, H, Wd, fmap, bmap):
+        """ conv1 .. conv_pw_13_relu of keras' MobileNet (reference models/mobilenet.py:94-111) -> conv_pw_3 / 5 / 11 / 13 behind their
+        ReLU6 (C2 .. C5).  conv1 is one launch (gpp_mobilenet_stem), every depthwise-separable block ONE launch (gpp_mobilenet_block: the
+        depthwise map never reaches HBM).  Every map is float32, never pre-split; the whole batch on lane 0. """
+        c0 = W.mobilenet_filters(self.backbone_name)[0]
+        x = fmap(M.out_size(H, 2), M.out_size(Wd, 2), c0)
+        sd = hip.MobileNetStemDesc(plan.images.data_ptr(), self.stem_w.data_ptr(), self.stem_b.data_ptr(), x.buf.data_ptr(), B, H, Wd, c0, x.pitch, 0)
+        plan.stem_out, plan.pool_out = x, None
+        plan.emit(OP_MOBILENET_STEM, sd, 'conv1', [plan.images], [x], flops=2.0 * B * x.H * x.W * 27 * c0)
+        feats = []
+        for i, cin, cout, stride in W.mobilenet_blocks(self.backbone_name):
+            y = fmap(M.out_size(x.H, stride), M.out_size(x.W, stride), cout)
+            dw_w, dw_b, pw_w, pw_b, scale = self.mbn_w[i]
+            d = M.block_desc(x, y, dw_w, dw_b, pw_w, pw_b, scale, stride, self.dtype)
+            plan.emit(OP_MOBILENET_BLOCK, d, 'conv_pw_{}'.format(i), [x], [y], flops=M.block_flops(d), io=([x], [y], None))
+            x = y
+            if i in W.MOBILENET_TAPS:
+                feats.append(x)
+        return feats
 
     def _pyramid(self, plan, opts, B, H, Wd, C3, C4, C5):
         """ the layout of every FPN / head tensor: the five levels back to back per image, (B, sum(H_l*W_l), C), so that one grouped
@@ -752,7 +800,7 @@ class RetinaNet3D(object):
         overlap = env('GPP_DECODE_OVERLAP', '1') != '0' and not head_lanes and not self.osf
         return PlanOptions(
             x3_level=x3_level,
-            fuse_stem_pool=not self.densenet and (self.esz == 2 or self.stem_x3) and env('GPP_FUSE_STEM_POOL', '1') != '0',
+            fuse_stem_pool=not self.densenet and not self.mobilenet and (self.esz == 2 or self.stem_x3) and env('GPP_FUSE_STEM_POOL', '1') != '0',
             stage_chunks=tuple(max(1, min(B, int(v))) for v in chunks.split(',')) if chunks else (B,) * 4,
             # GPP_HALF_LANES (default "0,1,2,3" = res2 .. res5; "" for whole batches): a launch of these stages fills the 256 CUs 0.7 - 1.4
             # times and is bound by tile fills and first-touch latency; two half-batch chains in flight overlap one's prologue / epilogue /
@@ -796,7 +844,7 @@ class RetinaNet3D(object):
             plan.keep.append(f.buf)
             return f.mark_split() if split else f
 
-        backbone = self._densenet_backbone if self.densenet else self._resnet_backbone
+        backbone = self._densenet_backbone if self.densenet else self._mobilenet_backbone if self.mobilenet else self._resnet_backbone
         C2, C3, C4, C5 = backbone(plan, opts, B, H, Wd, fmap, lambda h, w, c: fmap(h, w, c, opts.x3_level >= 2))
         plan.features = {'stem': plan.stem_out, 'C2': C2, 'C3': C3, 'C4': C4, 'C5': C5}
         shapes, pyramid = self._pyramid(plan, opts, B, H, Wd, C3, C4, C5)
@@ -865,7 +913,8 @@ class RetinaNet3D(object):
         test_every_tile_gives_identical_results), so ranks and plans may choose differently without any effect on the
         outputs; split-K, which would, is not tuned (gpp_conv2d_split_rule).  Choices are remembered per (layer, batch,
         image size) and can be persisted with GPP_TUNE_CACHE=<file.json>.  GPP_AUTOTUNE=0 keeps the library heuristic.
-        The fused tails choose their row count (tile_rows), DenseNet's pre-activation convs the tile of their inner conv. """
+        The fused tails choose their row count (tile_rows), DenseNet's pre-activation convs the tile of their inner conv, MobileNet's
+        blocks their own tile_hint. """
         self._require_hip()
         H, Wd = plan.shape[1:3]
         plan.images.uniform_(-120.0, 130.0)
@@ -881,7 +930,7 @@ class RetinaNet3D(object):
             if kind in DETECT_OPS or kind == OP_POLL:
                 continue
             self.run_op(plan, index)
-            if kind not in (OP_CONV, OP_TAIL, OP_CONV_PREACT):
+            if kind not in (OP_CONV, OP_TAIL, OP_CONV_PREACT, OP_MOBILENET_BLOCK):
                 continue
             # where the choice is written: the conv's own descriptor, the pre-activation's inner one, the tail's row count
             target = plan.inner[id(desc)][0] if kind == OP_CONV_PREACT else desc
@@ -891,7 +940,7 @@ class RetinaNet3D(object):
                 plan.tuning[name] = (int(getattr(target, field)), 0.0)
                 self.run_op(plan, index)
                 continue
-            key = (name, (plan.inner[id(desc)][0] if kind == OP_TAIL else target).batch, H, Wd)     # (a half-batch launch is tuned as what it is)
+            key = (name, target.B if kind == OP_MOBILENET_BLOCK else (plan.inner[id(desc)][0] if kind == OP_TAIL else target).batch, H, Wd)     # (a half-batch launch is tuned as what it is)
             if kind == OP_CONV and key in self._tuned and not self._tile_is_listed(desc, self._tuned[key][0]):
                 del self._tuned[key]                 # a remembered tile this build does not offer for this layer: time the layer again
             if key not in self._tuned:
@@ -910,6 +959,10 @@ class RetinaNet3D(object):
         if kind == OP_TAIL:
             return (64, 96, 128, 160) if self.dtype in C.X3_TYPES else (96, 128, 160)
         lib, tiles, count = hip.lib(), (ctypes.c_int * 32)(), ctypes.c_int(0)
+        if kind == OP_MOBILENET_BLOCK:
+            hip.check(lib.gpp_mobilenet_block_tile_candidates(ctypes.byref(target), tiles, 16, ctypes.byref(count)),
+                      'gpp_mobilenet_block_tile_candidates')
+            return list(tiles[:min(count.value, 16)])
         if kind == OP_CONV_PREACT:
             hip.check(lib.gpp_conv2d_preact_tile_candidates(ctypes.byref(target), tiles, 16, ctypes.byref(count)),
                       'gpp_conv2d_preact_tile_candidates')
@@ -945,7 +998,10 @@ class RetinaNet3D(object):
         slow = self.dtype == 'f32'
         iters = (2 if slow else 6) if flops > 5e10 else (4 if slow else 16)
         best = ctypes.c_float(0.0)
-        if kind == OP_CONV_PREACT:
+        if kind == OP_MOBILENET_BLOCK:
+            hip.check(hip.lib().gpp_mobilenet_block_autotune(ctypes.byref(target), iters, hip.stream_ptr(), ctypes.byref(best)),
+                      'gpp_mobilenet_block_autotune')
+        elif kind == OP_CONV_PREACT:
             hip.check(hip.lib().gpp_conv2d_preact_autotune(ctypes.byref(target), desc.in_scale, desc.in_shift, iters, hip.stream_ptr(),
                                                            ctypes.byref(best)), 'gpp_conv2d_preact_autotune')
         else:

@@ -60,7 +60,10 @@ def backbone_layers(backbone):
 def fpn_layers(backbone=None):
     """ [(name, K, C_in, C_out, stride)] models/retinanet.py:170-205 (feature_size = 512); the input widths are those of the backbone's
     C3 / C4 / C5 (no argument: the ResNet table) """
-    c3, c4, c5 = densenet_widths(backbone)[1:] if is_densenet(backbone) else (512, 1024, 2048)
+    if is_mobilenet(backbone):
+        c3, c4, c5 = mobilenet_widths(backbone)[1:]
+    else:
+        c3, c4, c5 = densenet_widths(backbone)[1:] if is_densenet(backbone) else (512, 1024, 2048)
     return [('C5_reduced', 1, c5, 512, 1), ('P5', 3, 512, 512, 1), ('C4_reduced', 1, c4, 512, 1), ('P4', 3, 512, 512, 1),
             ('C3_reduced', 1, c3, 512, 1), ('P3', 3, 512, 512, 1), ('P6', 3, c5, 512, 2), ('P7', 3, 512, 512, 2)]
 
@@ -79,6 +82,8 @@ def is_densenet(backbone):
 
 
 def bn_epsilon(backbone):
+    if is_mobilenet(backbone):
+        return MOBILENET_BN_EPSILON
     return DENSENET_BN_EPSILON if is_densenet(backbone) else BN_EPSILON
 
 
@@ -112,7 +117,8 @@ def densenet_layers(backbone):
 
 def backbone_parameter_count(backbone):
     """ parameters of the backbone as Keras counts them (BatchNormalization: 4 per channel, moving statistics included) """
-    return sum(int(np.prod(shape)) * (4 if kind == 'bn' else 1) for kind, _, shape in densenet_layers(backbone))
+    layers = mobilenet_layers(backbone) if is_mobilenet(backbone) else densenet_layers(backbone)
+    return sum(int(np.prod(shape)) * (4 if kind == 'bn' else 1) for kind, _, shape in layers)
 
 
 def _densenet_backbone_weights(w, backbone, seed, family):
@@ -146,6 +152,114 @@ def _densenet_backbone_weights(w, backbone, seed, family):
             w[name + '/beta'] = np.where(dead, f32(-0.05), w[name + '/beta'] * s).astype(f32)
             conv = name[:-len('_1_bn')] + '_2_conv/kernel'
             w[conv] = (w[conv] / s[None, None, :, None]).astype(f32)
+
+
+# ---- MobileNet v1 (keras.applications.mobilenet.MobileNet(alpha, include_top=False), reference models/mobilenet.py:94-111); Keras layer
+#   names: conv1 (3x3 s2, no bias) conv1_bn; block i = 1..13: conv_dw_i (depthwise 3x3, variable 'depthwise_kernel' of shape (3, 3, C, 1)),
+#   conv_dw_i_bn, conv_pw_i (1x1), conv_pw_i_bn; ReLU6 behind every BatchNormalization (epsilon 1e-3, Keras' default), no bias anywhere.
+#   Backbone names are 'mobilenet<rows>_<alpha>'; <rows> only selects ImageNet weights in Keras and does not change the graph.
+MOBILENET_ROWS = ('mobilenet128', 'mobilenet160', 'mobilenet192', 'mobilenet224')
+MOBILENET_ALPHAS = (0.25, 0.5, 0.75, 1.0)
+MOBILENET_BN_EPSILON = 1e-3
+MOBILENET_FILTERS = (64, 128, 128, 256, 256, 512, 512, 512, 512, 512, 512, 1024, 1024)      # conv_pw_1 .. conv_pw_13 at alpha = 1
+MOBILENET_STRIDED = (2, 4, 6, 12)                                                           # blocks whose depthwise conv has stride 2
+MOBILENET_TAPS = (3, 5, 11, 13)                                                             # conv_pw_{}_relu = C2, C3, C4, C5
+
+
+def mobilenet_alpha(backbone):
+    """ the width multiplier of a full MobileNet name, or None when `backbone` is not 'mobilenet<rows>_<one of the four alphas>' """
+    if backbone is None or '_' not in backbone:
+        return None
+    rows, _, alpha = backbone.partition('_')
+    try:
+        alpha = float(alpha)
+    except ValueError:
+        return None
+    return alpha if rows in MOBILENET_ROWS and alpha in MOBILENET_ALPHAS else None
+
+
+def is_mobilenet(backbone):
+    return mobilenet_alpha(backbone) is not None
+
+
+def mobilenet_filters(backbone):
+    """ (conv1 width, [conv_pw_1 .. conv_pw_13 widths]): int(f * alpha) as Keras computes them """
+    alpha = mobilenet_alpha(backbone)
+    return int(32 * alpha), [int(f * alpha) for f in MOBILENET_FILTERS]
+
+
+def mobilenet_widths(backbone):
+    """ channels of conv_pw_3 / 5 / 11 / 13 (C2, C3, C4, C5) """
+    pw = mobilenet_filters(backbone)[1]
+    return [pw[i - 1] for i in MOBILENET_TAPS]
+
+
+def mobilenet_blocks(backbone):
+    """ [(i, C_in, C_out, stride)] of the 13 depthwise-separable blocks """
+    c, pw = mobilenet_filters(backbone)
+    out = []
+    for i, f in enumerate(pw, 1):
+        out.append((i, c, f, 2 if i in MOBILENET_STRIDED else 1))
+        c = f
+    return out
+
+
+def mobilenet_layers(backbone):
+    """ [(kind, name, shape)] of the backbone in execution order: kind 'conv' (Keras HWIO 'kernel'), 'dw' ('depthwise_kernel',
+    (3, 3, C, 1)) or 'bn' ((C,)) """
+    c0 = mobilenet_filters(backbone)[0]
+    out = [('conv', 'conv1', (3, 3, 3, c0)), ('bn', 'conv1_bn', (c0,))]
+    for i, cin, cout, _ in mobilenet_blocks(backbone):
+        out += [('dw', 'conv_dw_{}'.format(i), (3, 3, cin, 1)), ('bn', 'conv_dw_{}_bn'.format(i), (cin,)),
+                ('conv', 'conv_pw_{}'.format(i), (1, 1, cin, cout)), ('bn', 'conv_pw_{}_bn'.format(i), (cout,))]
+    return out
+
+
+def kernel_variable(kind):
+    return 'depthwise_kernel' if kind == 'dw' else 'kernel'
+
+
+# synthetic MobileNet draw: the stem's pre-activation standard deviation.  ReLU6 clips, so the draw is placed where the clip is alive but
+# rare: tests/test_mobilenet_cpu.py::test_synthetic_calibration states the shares of activations at 6 and below 6.
+MOBILENET_SYN_STEM_STD = 2.0
+MOBILENET_TRAINED_SPREAD = (0.1, 10.0)
+
+
+def _mobilenet_backbone_weights(w, backbone, seed, family):
+    """ He-normal kernels, BatchNormalization close to the identity, from generator streams of their own ('mobilenet/<layer>': no draw of
+    another backbone moves).  family 'trained': ReLU6 does not commute with a scale, so the re-parameterisation sits in front of the
+    BatchNormalization instead: every output channel of every convolution gets its own scale s_c, log-uniform over
+    MOBILENET_TRAINED_SPREAD, and its BatchNormalization the matching statistics (moving_mean x s_c, moving_variance -> s_c^2 (var + eps)
+    - eps): raw kernels and statistics spread over two decades, the function is the base draw's up to rounding. """
+    f32, eps = np.float32, MOBILENET_BN_EPSILON
+    for kind, name, shape in mobilenet_layers(backbone):
+        key = 'mobilenet/' + name
+        if kind == 'bn':
+            r = _rng(seed, key)
+            c = shape[0]
+            w[name + '/gamma'] = (np.abs(1.0 + 0.1 * r.standard_normal(c)) + 0.05).astype(f32)
+            w[name + '/beta'] = (0.05 * r.standard_normal(c)).astype(f32)
+            w[name + '/moving_mean'] = (0.05 * r.standard_normal(c)).astype(f32)
+            w[name + '/moving_variance'] = (1.0 + 0.2 * r.random(c)).astype(f32)
+        else:
+            kh, kw, cin, cout = shape
+            fan_in = kh * kw * (1 if kind == 'dw' else cin)
+            w['{}/{}'.format(name, kernel_variable(kind))] = _normal(seed, key, shape, np.sqrt(2.0 / fan_in))
+    # the image arrives un-normalised (BGR - mean, +-128; a noise frame: standard deviation 74 per channel)
+    w['conv1/kernel'] *= f32(MOBILENET_SYN_STEM_STD / (74.0 * np.sqrt(2.0)))
+    if family == 'trained':
+        r = _rng(seed, 'mobilenet/trained_like')
+        lo, hi = np.log(MOBILENET_TRAINED_SPREAD[0]), np.log(MOBILENET_TRAINED_SPREAD[1])
+        for kind, name, shape in mobilenet_layers(backbone):
+            if kind == 'bn':
+                continue
+            c = shape[2] if kind == 'dw' else shape[3]
+            s = np.exp(r.uniform(lo, hi, c))
+            var = kernel_variable(kind)
+            w['{}/{}'.format(name, var)] = (w['{}/{}'.format(name, var)] * (s[None, None, :, None] if kind == 'dw' else s[None, None, None, :])).astype(f32)
+            bn = name + '_bn'
+            w[bn + '/moving_mean'] = (w[bn + '/moving_mean'] * s).astype(f32)
+            w[bn + '/moving_variance'] = (s * s * (w[bn + '/moving_variance'].astype(np.float64) + eps) - eps).astype(f32)
 
 
 def head_layers():
@@ -184,6 +298,11 @@ SYN_BACKBONE_OUT_SCALE = {'resnet50': 1.0, 'resnet101': 0.676, 'resnet152': 0.52
 SYN_BACKBONE_OUT_SCALE.update({'densenet121': 0.84, 'densenet169': 0.81, 'densenet201': 0.89})
 
 
+# MobileNet, by width multiplier (tests/test_mobilenet_cpu.py::test_synthetic_calibration, measured the same way)
+# (858 / 855 / 846 / 954 anchors of 137256 above 0.05 with seed 1234)
+MOBILENET_SYN_OUT_SCALE = {0.25: 3.5, 0.5: 3.1, 0.75: 3.2, 1.0: 4.8}
+
+
 def synthetic_weights(backbone='resnet50', seed=1234, family='he'):
     """ Seeded random weights with the exact architecture of `backbone` + FPN + heads.
     family 'he': He-normal kernels, BatchNormalization close to the identity (every activation O(1)).
@@ -191,10 +310,13 @@ def synthetic_weights(backbone='resnet50', seed=1234, family='he'):
     if family not in ('he', 'trained'):
         raise ValueError("family must be 'he' or 'trained', got {!r}".format(family))
     w = {}
+    own = is_densenet(backbone) or is_mobilenet(backbone)            # backbones with a draw of their own
     if is_densenet(backbone):
         _densenet_backbone_weights(w, backbone, seed, family)
+    if is_mobilenet(backbone):
+        _mobilenet_backbone_weights(w, backbone, seed, family)
     stage_blocks = {str(stage + 2): n for stage, n in enumerate(BLOCKS.get(backbone, ()))}
-    for conv, bn, kh, kw, cin, cout, _ in (() if is_densenet(backbone) else backbone_layers(backbone)):
+    for conv, bn, kh, kw, cin, cout, _ in (() if own else backbone_layers(backbone)):
         w[conv + '/kernel'] = _normal(seed, conv, (kh, kw, cin, cout), np.sqrt(2.0 / (kh * kw * cin)))
         r = _rng(seed, bn)
         gamma = (1.0 + 0.1 * r.standard_normal(cout)).astype(np.float32)
@@ -209,7 +331,7 @@ def synthetic_weights(backbone='resnet50', seed=1234, family='he'):
         w[bn + '/moving_mean'] = (0.05 * r.standard_normal(cout)).astype(np.float32)
         w[bn + '/moving_variance'] = (1.0 + 0.2 * r.random(cout)).astype(np.float32)
     # the image arrives un-normalised (BGR - mean, +-128): bring conv1 to unit scale
-    if not is_densenet(backbone):
+    if not own:
         w['conv1/kernel'] *= np.float32(1.0 / 64.0)
     for name, k, cin, cout, _ in fpn_layers(backbone):
         w[name + '/kernel'] = _normal(seed, name, (k, k, cin, cout), np.sqrt(1.0 / (k * k * cin)))
@@ -220,12 +342,12 @@ def synthetic_weights(backbone='resnet50', seed=1234, family='he'):
             w[name + '/bias'] = np.zeros((cout,), np.float32)
         else:
             gain = SYN_CLS_OUT_GAIN if 'classification' in name else (SYN_DIM_OUT_GAIN if 'dim' in name else SYN_REG_OUT_GAIN)
-            gain *= SYN_BACKBONE_OUT_SCALE[backbone]
+            gain *= MOBILENET_SYN_OUT_SCALE[mobilenet_alpha(backbone)] if is_mobilenet(backbone) else SYN_BACKBONE_OUT_SCALE[backbone]
             w[name + '/kernel'] = _normal(seed, name, (3, 3, cin, cout), gain * np.sqrt(1.0 / (9 * cin)))
             w[name + '/bias'] = np.zeros((cout,), np.float32)
     # initializers.PriorProbability(0.01): bias = -log((1 - p) / p)   (initializers.py:23-39)
     w['pyramid_classification/bias'][:] = np.float32(-np.log((1.0 - 0.01) / 0.01))
-    if family == 'trained' and not is_densenet(backbone):
+    if family == 'trained' and not own:
         trained_like(w, backbone, seed)
     return w
 
@@ -288,7 +410,11 @@ def expected_arrays(backbone):
         for kind, name, shape in densenet_layers(backbone):
             for part in (('kernel',) if kind == 'conv' else ('gamma', 'beta', 'moving_mean', 'moving_variance')):
                 exp['{}/{}'.format(name, part)] = shape
-    for conv, bn, kh, kw, cin, cout, _ in (() if is_densenet(backbone) else backbone_layers(backbone)):
+    if is_mobilenet(backbone):
+        for kind, name, shape in mobilenet_layers(backbone):
+            for part in (('gamma', 'beta', 'moving_mean', 'moving_variance') if kind == 'bn' else (kernel_variable(kind),)):
+                exp['{}/{}'.format(name, part)] = shape
+    for conv, bn, kh, kw, cin, cout, _ in (() if is_densenet(backbone) or is_mobilenet(backbone) else backbone_layers(backbone)):
         exp[conv + '/kernel'] = (kh, kw, cin, cout)
         for part in ('gamma', 'beta', 'moving_mean', 'moving_variance'):
             exp['{}/{}'.format(bn, part)] = (cout,)
@@ -403,7 +529,7 @@ def save_keras_h5(path, weights, backbone=None):
     Carries the weights only (no model_config): it is what load_keras_h5 / load_model read back, and a fixture in the
     reference's format -- not a file `keras.models.load_model` could rebuild a graph from. """
     from . import hdf5
-    order = ('kernel', 'bias', 'gamma', 'beta', 'moving_mean', 'moving_variance')      # Keras variable order within a layer
+    order = ('kernel', 'depthwise_kernel', 'bias', 'gamma', 'beta', 'moving_mean', 'moving_variance')      # Keras variable order within a layer
     groups = {}
     for key in weights:
         layer, var = key.rsplit('/', 1)

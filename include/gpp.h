@@ -281,6 +281,42 @@ int gpp_maxpool3x3s2_pad_f32(const float* in, float* out, int B, int H, int W, i
 int gpp_avgpool2x2_f32(const float* in, float* out, int B, int H, int W, int C, int out_pitch, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * MobileNet (v1) backbone (keras.applications.mobilenet.MobileNet, include_top=False; csrc/mobilenet.hip), float32 NHWC storage.
+ * Padding of both kernels: ZeroPadding2D(1) (symmetric) + 'valid', so H_out = (H - 1) / stride + 1 and output row y reads input rows
+ * y * stride - 1 .. y * stride + 1 (NOT TensorFlow's 'same' window on an even side at stride 2).
+ *
+ * gpp_mobilenet_block: one depthwise-separable block as ONE launch; the depthwise map never reaches HBM
+ *     out = relu6( W_pw . relu6( dw3x3(in, W_dw) + dw_bias ) + pw_bias ),  relu6(v) = min(max(v, 0), 6)
+ *   in: (B, H, W) pixels of in_pitch floats, C_in channels read; out: (B, H_out, W_out) pixels of out_pitch floats, C_out written.
+ *   dw_weight [9][C_in] float32 (tap dy * 3 + dx major, frozen BN folded in), dw_bias [C_in], pw_bias [C_out] float32.
+ *   pw_weight [weight_rows][ceil(C_in / 32)][128 bytes]: row n = output channel n, zero rows up to weight_rows (a multiple of 256,
+ *   >= C_out), zero channels up to the next multiple of 32; a 128-byte chunk is 32 float32 (GPP_F32) or [32 hi | 32 lo] 16-bit halves
+ *   (GPP_F16X3 / GPP_BF16X3: hi = h(w), lo = h(w - hi); GPP_F16X3: w scaled by a per-channel power of two first, whose inverse is
+ *   out_scale [C_out] float32 -- layers/mobilenet.py pack_pointwise).  Other dtypes: GPP_ERR_UNSUPPORTED.
+ *   C_in % 4 == 0, C_out % 4 == 0, pitches % 4 == 0, every pointer 16-byte aligned, stride 1 or 2.
+ *   The depthwise sum is float32 multiplies and adds in tap order, never contracted; the K order of the pointwise product is fixed
+ *   (csrc/mobilenet.hip).  tile_hint: 0 (by C_out) or 128064, 64128, 128128, 64256 (pixels x channels): every tile gives the same bytes,
+ *   and an image's bytes do not depend on the batch.  The depthwise result is at most 6: the f16x3 form needs no range counter.
+ * gpp_mobilenet_stem: conv1 3x3 / 2, 3 -> C_out channels + folded BN + ReLU6; in (B, H, W, 3) float32 dense, weight [27][C_out] float32
+ *   (tap (dy * 3 + dx) * 3 + input channel major), float32 multiplies and adds in tap order: the same bytes in every arithmetic mode. */
+typedef struct gpp_mobilenet_block_desc {
+    const float* in; const float* dw_weight; const float* dw_bias; const void* pw_weight; const float* pw_bias; const float* out_scale;
+    float* out;
+    int32_t dtype, B, H, W, C_in, C_out, stride, in_pitch, out_pitch, weight_rows, tile_hint, reserved;
+} gpp_mobilenet_block_desc;
+typedef struct gpp_mobilenet_stem_desc { const float* in; const float* weight; const float* bias; float* out; int32_t B, H, W, C_out, out_pitch, reserved; } gpp_mobilenet_stem_desc;
+int gpp_mobilenet_block(const gpp_mobilenet_block_desc* host_desc, void* stream);
+int gpp_mobilenet_block_tile_candidates(const gpp_mobilenet_block_desc* host_desc, int* tiles, int capacity, int* count);
+/* times the candidates (iters launches each) and stores the fastest in desc->tile_hint; synchronises the stream */
+int gpp_mobilenet_block_autotune(gpp_mobilenet_block_desc* desc, int iters, void* stream, float* best_us);
+int gpp_mobilenet_stem(const float* in, const float* weight, const float* bias, float* out, int B, int H, int W, int C_out, int out_pitch,
+                       void* stream);
+/* the depthwise half of a block alone, its map stored (weight [9][C], the fused kernel's arithmetic): no plan uses it -- it exists so that
+   tools/bench_mobilenet.py can time the two-launch form of a block against the fused one */
+int gpp_mobilenet_depthwise(const float* in, const float* weight, const float* bias, float* out, int B, int H, int W, int C, int stride,
+                            int in_pitch, int out_pitch, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * ResNet stem and small element-wise helpers.
  * gpp_stem_conv7x7_bn_relu replaces keras_resnet's ZeroPadding2D(3) + conv1 (7x7, stride 2,
  * no bias) + bn_conv1 (frozen, eps 1e-5) + ReLU (instantiated at models/resnet.py:88-93):
@@ -466,6 +502,8 @@ int gpp_pose_f32(const float* boxes, const float* dims, const float* scores, con
 #define GPP_OP_AVGPOOL 18                /* gpp_dense_pool_desc -> gpp_avgpool2x2_f32 (DenseNet transitions) */
 #define GPP_OP_POSE 19                   /* gpp_pose_desc -> gpp_pose_f32 (opt-in: RetinaNet3D(pose=True)) */
 #define GPP_OP_CONV_PREACT 32            /* gpp_preact_desc -> gpp_conv2d_preact (DenseNet); kinds 0..255 exist */
+#define GPP_OP_MOBILENET_STEM 33         /* gpp_mobilenet_stem_desc -> gpp_mobilenet_stem */
+#define GPP_OP_MOBILENET_BLOCK 34        /* gpp_mobilenet_block_desc -> gpp_mobilenet_block */
 /* (14, 15: the Winograd F(2, 3) form of the tower layers of round 5 -- built, measured at -2 % of the step, shelved in round 6:
    tools/experiments/winograd/) */
 /* Optional concurrency inside a plan: `kind | GPP_OP_LANE(l)` (l = 1, 2) enqueues the op on a library-owned side stream
