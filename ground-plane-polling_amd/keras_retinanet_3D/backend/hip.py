@@ -40,6 +40,7 @@ GPP_BF16X3 = 4
 GPP_F16X3 = 5
 GPP_MAX_GROUPS = 5
 GPP_POSE_COLS = 36         # float32 values per row of gpp_pose_f32 (include/gpp.h)
+GPP_ABSMAX_F32, GPP_ABSMAX_SPLIT_F16, GPP_ABSMAX_SPLIT_BF16 = 1, 2, 3      # gpp_absmax_desc.layout (include/gpp.h)
 
 
 class GppError(RuntimeError):
@@ -84,6 +85,17 @@ class MobileNetStemDesc(ctypes.Structure):
     """ gpp_mobilenet_stem_desc (include/gpp.h) """
     _fields_ = [('inp', c_void_p), ('weight', c_void_p), ('bias', c_void_p), ('out', c_void_p)] + \
                [(n, ctypes.c_int32) for n in ('B', 'H', 'W', 'C_out', 'out_pitch', 'reserved')]
+
+
+class AbsmaxDesc(ctypes.Structure):
+    """ gpp_absmax_desc (include/gpp.h) """
+    _fields_ = [('inp', c_void_p), ('out', c_void_p), ('M', c_int64), ('pitch', c_int64)] + \
+               [(n, ctypes.c_int32) for n in ('C', 'c_off', 'layout', 'reserved')]
+
+
+class AbsmaxClearDesc(ctypes.Structure):
+    """ gpp_absmax_clear_desc (include/gpp.h) """
+    _fields_ = [('table', c_void_p), ('n', c_int64)]
 
 
 def _declare(lib):
@@ -134,6 +146,13 @@ def _declare(lib):
     lib.gpp_mobilenet_stem.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]
     lib.gpp_mobilenet_depthwise.restype = c_int
     lib.gpp_mobilenet_depthwise.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
+    # the range audit of dtype='f16x3' (include/gpp.h): per-channel abs-max of one map, and the clearing of its table
+    # (GPP_LIB may name an older build for a same-box A/B, tools/ab_bench.sh: it runs every plan but an audit model's, whose ops it refuses)
+    if hasattr(lib, 'gpp_channel_absmax'):
+        lib.gpp_channel_absmax.restype = c_int
+        lib.gpp_channel_absmax.argtypes = [ctypes.POINTER(AbsmaxDesc), c_void_p]
+        lib.gpp_absmax_clear.restype = c_int
+        lib.gpp_absmax_clear.argtypes = [c_void_p, c_int64, c_void_p]
     lib.gpp_relu.restype = c_int
     lib.gpp_relu.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_void_p]
     lib.gpp_preprocess_u8_bgr.restype = c_int
@@ -239,6 +258,13 @@ def ptr(t):
         return None
     assert t.is_contiguous(), 'gpp kernels need dense tensors'
     return ctypes.c_void_p(t.data_ptr())
+
+
+def channel_absmax(buf, M, C, pitch, c_off, layout, out, stream=None):
+    """ gpp_channel_absmax on M pixels of a device tensor (pixel m at element m * pitch, channels [c_off, c_off + C)) into the uint32
+    table `out` (an int32 tensor of >= C words, cleared by the caller: gpp_absmax_clear) """
+    d = AbsmaxDesc(buf.data_ptr(), out.data_ptr(), M, pitch, C, c_off, layout, 0)
+    check(lib().gpp_channel_absmax(ctypes.byref(d), stream or stream_ptr()), 'gpp_channel_absmax')
 
 
 def pack_stem_weights_x3(kernel_147x64, device):

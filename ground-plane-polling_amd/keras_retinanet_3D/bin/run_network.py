@@ -59,7 +59,14 @@ def parse_args(args):
     parser.add_argument('--device-pose', action='store_true',
                         help='Pose recovery and KITTI fields on the GPU (not in the reference CLI): the model is loaded with pose=True and '
                              'the .mat and KITTI files are written from the rows of its pose stage; --save-images is unaffected.')
-    return parser.parse_args(args)
+    parser.add_argument('--range-audit', action='store_true',
+                        help='Audit the lower range of --dtype f16x3 (not in the reference CLI): the model is loaded with range_audit=True, a '
+                             'call whose run left a whole conv-operand map below 2^-9 is answered by the float32 twin, and at the end the five '
+                             'smallest maps are printed and <output_dir>/<model name>/range_audit.json is written (per map, the minimum over all calls).')
+    parsed = parser.parse_args(args)
+    if parsed.range_audit and parsed.dtype != 'f16x3':
+        parser.error('--range-audit audits the IEEE-half pairs of --dtype f16x3, not {}'.format(parsed.dtype))
+    return parsed
 
 
 def make_output_tree(args):
@@ -125,10 +132,8 @@ def main(args=None):
         args = sys.argv[1:]
     args = parse_args(args)
 
-    if args.device_pose:
-        model = models.load_model(args.model_path, backbone_name=args.backbone, dtype=args.dtype, pose=True)
-    else:
-        model = models.load_model(args.model_path, backbone_name=args.backbone, dtype=args.dtype)
+    model = models.load_model(args.model_path, backbone_name=args.backbone, dtype=args.dtype, pose=args.device_pose, range_audit=args.range_audit)
+    audit = {}               # --range-audit: per map, the report of the call that left it smallest
     plane_params = scipy.io.loadmat(args.plane_params_path)['road_planes_database']
     output_dir = make_output_tree(args)
 
@@ -149,6 +154,7 @@ def main(args=None):
                 frames = np.stack([it['raw_image'] for it in group])
                 (rows, counts), _ = model.predict_poses_on_frames(frames, P_inv, planes)
                 dt = time.time() - t0
+                keep_smallest(audit, model)
                 for k, it in enumerate(group):
                     print("Image {}: frame rate: {:.2f}".format(j, len(group) / dt))
                     j += 1
@@ -159,11 +165,39 @@ def main(args=None):
             else:
                 outputs = model.predict_on_batch([np.stack([it['image'] for it in group]), P_inv, planes])[:8]
             dt = time.time() - t0
+            keep_smallest(audit, model)
             for k, it in enumerate(group):
                 print("Image {}: frame rate: {:.2f}".format(j, len(group) / dt))
                 j += 1
                 det = gpp_utils.recover_pose(gpp_utils.select_detections(outputs, it['scale'], image_index=k))
                 write_results(args, output_dir, it, det)
+
+
+    if args.range_audit:
+        write_range_audit(output_dir, model, audit)
+
+
+def keep_smallest(audit, model):
+    """ --range-audit: fold the report of the call just made into `audit` (per map, the call that left its maximum smallest) """
+    for rec in (model.last_range_audit or []) if getattr(model, 'audit', False) else []:
+        old = audit.get(rec['name'])
+        if old is None or not rec['absmax'] >= old['absmax']:          # (a NaN maximum replaces a number and stays)
+            audit[rec['name']] = rec
+
+
+def write_range_audit(output_dir, model, audit):
+    import json
+    from ..models.retinanet import RANGE_AUDIT_THRESHOLD
+    maps = sorted(audit.values(), key=lambda r: (r['absmax'] != r['absmax'], r['absmax']))
+    print('range audit: {} maps, {} flagged (call, map) pairs, {} calls answered by the float32 twin; the five smallest map maxima:'.format(
+        len(maps), model.small_magnitude_events, model.range_fallbacks))
+    for r in maps[:5]:
+        print('  {:<28} max {:<10.4g} {} bits kept, {} of {} live channels below 2^-9{}'.format(
+            r['name'], r['absmax'], r['bits'], r['small_channels'], r['live'], '  FLAGGED' if r['flagged'] else ''))
+    with open(os.path.join(output_dir, 'range_audit.json'), 'w') as f:
+        json.dump({'threshold': RANGE_AUDIT_THRESHOLD, 'small_magnitude_events': model.small_magnitude_events,
+                   'range_fallbacks': model.range_fallbacks, 'maps': maps,
+                   'unobserved': model.range_audit_unobserved() if maps else []}, f, indent=1)
 
 
 if __name__ == '__main__':

@@ -52,7 +52,7 @@ def backbone(backbone_name):
 
 
 def load_model(filepath, backbone_name='resnet50', convert=False, nms=True, class_specific_filter=True,
-               orientation_specific_filter=False, dtype=None, on_range_event=None, plan=None, pose=False):
+               orientation_specific_filter=False, dtype=None, on_range_event=None, plan=None, pose=False, range_audit=False):
     """ Loads a RetinaNet-3D inference model (reference models/__init__.py:59-88).
 
     `convert` is accepted for signature compatibility: every model this function returns already
@@ -69,6 +69,15 @@ def load_model(filepath, backbone_name='resnet50', convert=False, nms=True, clas
     when one of its activations left the IEEE-half range (beyond +-65504: clamped, counted by the kernels' epilogues) --
         'f32' (default)    the call is run again on a float32 twin of the model and THAT result is returned (the reference's answer, slower)
         'raise'            GppError;      'ignore'   the clamped result is returned (model.x3_range_events() still counts)
+    `range_audit` (not in the reference; dtype='f16x3' only, default False): the LOWER range of the type, opt-in.  Below 2^-14 the (hi, lo)
+    half pair is a fixed-point number with a quantum of 2^-24; such a model's plans also measure the largest |x| of every channel of every
+    map an x3 convolution reads (gpp_channel_absmax: one extra pass over each map, the fused bottlenecks as their separate launches; the
+    results are byte for byte those of the ordinary plans) and model.range_audit() returns the report.  A synchronous call
+    (predict_on_batch / _on_frames, predict_poses_*) whose run left the largest value of a whole MAP below 2^-9 -- the map is stored at
+    bf16x3 grade or worse -- does what `on_range_event` says ('f32': the float32 twin's result, 'raise': GppError naming the maps,
+    'ignore': the result, the report kept); model.small_magnitude_events counts such (call, map) pairs.  A sufficient condition for
+    damage, not a necessary one: a few tiny channels with huge weights inside a map of ordinary size are reported (`small_channels`) and
+    do not trigger.  FramePipeline and ShardedModel refuse an audit model.
     `plan` (not in the reference; None = the environment's GPP_PLAN, else 'throughput'): how the layers are launched --
         'throughput'       (default) the plan every batched caller wants: split-K only where a layer's grid is tiny at ANY batch
         'latency'          for callers that time ONE image per call, as the reference does (bin/run_network.py:108-111): the deep-K layers whose
@@ -95,7 +104,7 @@ def load_model(filepath, backbone_name='resnet50', convert=False, nms=True, clas
     else:
         w = W.load_weights(filepath)
     model = RetinaNet3D(w, backbone_name=name, dtype=dtype, nms=nms, class_specific_filter=class_specific_filter,
-                        orientation_specific_filter=orientation_specific_filter, on_range_event=on_range_event, plan=plan, pose=pose)
+                        orientation_specific_filter=orientation_specific_filter, on_range_event=on_range_event, plan=plan, pose=pose, range_audit=range_audit)
     if convert:
         model.summary()
     return model

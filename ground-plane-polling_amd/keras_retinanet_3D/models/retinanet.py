@@ -109,6 +109,7 @@ OP_STEM_POOL = 13
 OP_MAXPOOL_PAD, OP_AVGPOOL, OP_CONV_PREACT = 17, 18, 32         # DenseNet (include/gpp.h)
 OP_MOBILENET_STEM, OP_MOBILENET_BLOCK = 33, 34                  # MobileNet (include/gpp.h)
 OP_POSE = 19                                                    # RetinaNet3D(pose=True): gpp_pose_f32 behind the polling
+OP_ABSMAX, OP_ABSMAX_CLEAR = 35, 36                             # RetinaNet3D(range_audit=True): gpp_channel_absmax behind every audited map
 DETECT_OPS = (OP_DETECT, OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT, 12)
 OP_JOIN, OP_SYNC = 0x10000, 0x20000
 
@@ -139,6 +140,44 @@ def part_of(fm, c0, nb):
     return C.FMap(fm.buf, nb, fm.H, fm.W, fm.C, off=fm.off + c0 * fm.bstride, bstride=fm.bstride, pitch=fm.pitch, split=fm.split, half=fm.half)
 
 
+# RetinaNet3D(range_audit=True): the fused first layer of the three towers writes one 896-channel map whose slices the towers read
+TOWER_SLICES = {('pyramid_towers_0', 0): 'pyramid_regression_0', ('pyramid_towers_0', 512): 'pyramid_classification_0',
+                ('pyramid_towers_0', 768): 'pyramid_regression_dim_0'}
+# the (hi, lo) IEEE-half pair is a fixed-point number with a quantum of 2^-24: a map whose LARGEST value is below
+# 2^-9 keeps fewer than 16 significant bits of it, i.e. the whole map is stored at bf16x3 grade or worse
+RANGE_AUDIT_THRESHOLD = 2.0 ** -9
+X3_QUANTUM = 2.0 ** -24
+
+
+def audit_report(maps, table, threshold=RANGE_AUDIT_THRESHOLD):
+    """ the host side of the range audit: maps = Plan.audit_maps (name, consumers, channels, row = (first word, words)), table = the
+    uint32 abs-max table of one run.  One record per map:
+      name, consumers, channels; live = channels whose maximum is not zero; absmax = the map's largest |x| (NaN when a channel holds one);
+      absmax_min_live / absmax_median_live over the live channels; small_channels = live channels whose maximum is below the threshold
+      (INFORMATION only: every sane model has some); bits = floor(log2(absmax / 2^-24)) capped at 22: how many bits the map's largest
+      value keeps in an IEEE-half pair; flagged = 0 < absmax < threshold -- the whole MAP sits in the fixed-point regime.  That is a
+      sufficient condition for damage, not a necessary one: a few tiny channels with huge weights inside a map of ordinary size are
+      reported (small_channels) and do not trigger.  A NaN maximum is the upper-range counter's business, not flagged here. """
+    table = np.ascontiguousarray(table).view(np.uint32).reshape(-1)
+    out = []
+    for m in maps:
+        first, n = m['row']
+        bits = table[first:first + n]
+        vals = bits.view(np.float32).astype(np.float64)
+        live = vals[bits != 0]
+        finite = live[~np.isnan(live)]
+        absmax = float('nan') if len(finite) < len(live) else float(finite.max()) if len(finite) else 0.0
+        rec = {k: m[k] for k in ('name', 'consumers', 'channels') if k in m}
+        rec.update({'live': int(len(live)), 'absmax': absmax,
+                    'absmax_min_live': float(finite.min()) if len(finite) else None,
+                    'absmax_median_live': float(np.median(finite)) if len(finite) else None,
+                    'small_channels': int((finite < threshold).sum()),
+                    'bits': None if not absmax > 0 else int(min(22, max(0, np.floor(np.log2(absmax / X3_QUANTUM))))) if np.isfinite(absmax) else 22,
+                    'flagged': bool(0 < absmax < threshold)})
+        out.append(rec)
+    return out
+
+
 class Plan(object):
     """ Everything one (batch, H, W, N planes) configuration needs: buffers, descriptors, op array. """
 
@@ -151,6 +190,12 @@ class Plan(object):
         self.oracle_names = {}  # fused ops: reference layer name of each output map (per-layer parity tests)
         self.lanes = []         # per op: side-stream lane << 8 | join flag (include/gpp.h GPP_OP_LANE / GPP_OP_JOIN)
         self.access = []        # per op: (byte intervals read, byte intervals written): check_stream_ordering
+        self.atomic = []        # per op: byte intervals it only updates with order-free atomics (the abs-max rows of an audit plan)
+        self.wrote = []         # per op: the FMaps among its writes; per op: its io record (audit plans: who produces, who reads a map)
+        self.op_io = []
+        self.audit_table = None     # RetinaNet3D(range_audit=True): see RetinaNet3D._audit
+        self.audit_maps = []
+        self.audit_unobserved = []
         self.inner = {}         # id(descriptor) -> the gpp_conv_desc records a fused or pre-activation launch points to
         self.open_lanes = set()  # side lanes forked and not joined by the ops recorded so far
         self.conv_descs = []    # (gpp_conv_desc, stream lane): the split-K workspace of each lane is bound once every op is known
@@ -158,15 +203,19 @@ class Plan(object):
         self.array = None
         self.flops = 0.0
 
-    def emit(self, kind, desc, name, reads=(), writes=(), tag=0, flops=0.0, lane=0, join=False, sync=False, io=None, inner=()):
+    def emit(self, kind, desc, name, reads=(), writes=(), tag=0, flops=0.0, lane=0, join=False, sync=False, io=None, inner=(), atomic=()):
         """ record one launch.  reads / writes: the FMaps and tensors it reads and writes (check_stream_ordering); io: its
-        (inputs, outputs, residuals) FMaps for the per-layer tests; inner: the conv descriptors its descriptor points to """
+        (inputs, outputs, residuals) FMaps for the per-layer tests; inner: the conv descriptors its descriptor points to; atomic: what
+        it only updates with atomics whose result does not depend on their order (two such launches may run side by side) """
         self.keep += list(inner) + [desc]
         if inner:
             self.inner[id(desc)] = tuple(inner)
         self.ops.append((kind, tag, desc, name, flops))
         self.lanes.append((int(lane) << 8) | (OP_JOIN if join else 0) | (OP_SYNC if sync else 0))
         self.access.append((self.spans(reads), self.spans(writes)))
+        self.atomic.append(self.spans(atomic))
+        self.wrote.append([x for x in writes if isinstance(x, C.FMap)])
+        self.op_io.append(io)
         self.flops += flops
         if lane:
             self.open_lanes.add(lane)
@@ -196,6 +245,23 @@ class Plan(object):
         """ byte intervals of a list of FMaps and tensors """
         return [iv for x in items for iv in (Plan.span(x) if isinstance(x, C.FMap) else Plan.span_of(x))]
 
+    def insert_behind(self, extra):
+        """ extra: {position: [(kind, desc, name, FMaps read, tensors updated atomically)]}: records these launches directly behind the
+        op at that position, on its lane (no join, no fork of their own) -- the audit launches, placed once every reader of every map is known """
+        old = (self.ops, self.lanes, self.access, self.atomic, self.wrote, self.op_io)
+        self.ops, self.lanes, self.access, self.atomic, self.wrote, self.op_io = [], [], [], [], [], []
+        for pos, row in enumerate(zip(*old)):
+            for dst, item in zip((self.ops, self.lanes, self.access, self.atomic, self.wrote, self.op_io), row):
+                dst.append(item)
+            for kind, desc, name, reads, atomic in extra.get(pos, ()):
+                self.keep.append(desc)
+                self.ops.append((kind, 0, desc, name, 0.0))
+                self.lanes.append(row[1] & 0xff00)
+                self.access.append((self.spans(reads), []))
+                self.atomic.append(self.spans(atomic))
+                self.wrote.append([])
+                self.op_io.append(None)
+
     def check_stream_ordering(self):
         """ every pair of launches on DIFFERENT streams that touch overlapping bytes (at least one of them writing) must be ordered by a
         fork or a join, as gpp_plan_run (csrc/plan.cpp) places them: a side-lane launch forks from the caller's stream when its lane is
@@ -203,7 +269,7 @@ class Plan(object):
         Returns the list of violations [(earlier op, later op)], empty when the plan is race-free by construction. """
         def overlap(a, b):
             return any(x0 < y1 and y0 < x1 for x0, x1 in a for y0, y1 in b)
-        bad, seen = [], []                    # seen: (position, lane, name, reads, writes)
+        bad, seen = [], []                    # seen: (position, lane, name, reads, writes, atomic updates)
         active = {}
         forks, joins = {}, []                 # lane -> positions of its forks; positions of joins
         for pos, (kind, _, desc, name, _) in enumerate(self.ops):
@@ -217,8 +283,11 @@ class Plan(object):
                 joins.append(pos)
                 active = {}
             reads, writes = self.access[pos]
-            for p0, l0, n0, r0, w0 in seen:
-                if l0 == lane or not (overlap(w0, reads) or overlap(w0, writes) or overlap(r0, writes)):
+            atomic = self.atomic[pos]
+            for p0, l0, n0, r0, w0, a0 in seen:
+                # (two order-free atomic updates of the same bytes do not conflict; an atomic update and a plain access do)
+                if l0 == lane or not (overlap(w0, reads) or overlap(w0, writes) or overlap(r0, writes) or overlap(a0, reads) or
+                                      overlap(a0, writes) or overlap(w0, atomic) or overlap(r0, atomic)):
                     continue
                 j = [q for q in joins if p0 < q <= pos]                      # a join after the earlier launch, not after this one
                 if l0 == 0:
@@ -229,12 +298,12 @@ class Plan(object):
                     ok = bool(j) and any(min(j) <= f <= pos for f in forks.get(lane, []))
                 if not ok:
                     bad.append((n0, name))
-            seen.append((pos, lane, name, reads, writes))
+            seen.append((pos, lane, name, reads, writes, atomic))
         return bad
 
     @staticmethod
     def stage_of(kind, name):
-        """ include/gpp.h GPP_OP_STAGE: 1 stem, 2 backbone, 3 FPN, 4 heads, 5 decode, 6 polling, 8 pose (roctx ranges under GPP_ROCTX=1) """
+        """ include/gpp.h GPP_OP_STAGE: 1 stem, 2 backbone, 3 FPN, 4 heads, 5 decode, 6 polling, 8 pose, 9 audit (roctx ranges under GPP_ROCTX=1) """
         if kind in (OP_STEM, OP_MAXPOOL, OP_STEM_POOL, OP_MAXPOOL_PAD, OP_MOBILENET_STEM):
             return 1
         if kind in DETECT_OPS:
@@ -243,6 +312,8 @@ class Plan(object):
             return 6
         if kind == OP_POSE:
             return 8
+        if kind in (OP_ABSMAX, OP_ABSMAX_CLEAR):
+            return 9
         if name.startswith('res') or kind in (OP_CONV_PREACT, OP_AVGPOOL, OP_MOBILENET_BLOCK) or name.startswith(('conv2_', 'conv3_', 'conv4_', 'conv5_')):
             return 2
         if name.startswith('pyramid_'):
@@ -260,8 +331,19 @@ class RetinaNet3D(object):
     """ Inference model: ResNet-50/101/152, DenseNet-121/169/201 or MobileNet (v1) + FPN + heads + decode + ground-plane polling. """
 
     def __init__(self, weights, backbone_name='resnet50', dtype='f16x3', nms=True, class_specific_filter=True,
-                 orientation_specific_filter=False, name='retinanet-bbox', on_range_event=None, plan=None, pose=False):
+                 orientation_specific_filter=False, name='retinanet-bbox', on_range_event=None, plan=None, pose=False, range_audit=False):
         import torch
+        # range_audit=True (dtype='f16x3' only): every plan also measures the largest |x| of every channel of every map an x3 convolution
+        # reads (gpp_channel_absmax, _audit), and a synchronous call whose run left a whole map below RANGE_AUDIT_THRESHOLD reacts as
+        # on_range_event says.  A model attribute like `pose`: without it every plan is what it was, launch for launch
+        self.audit = bool(range_audit)
+        if self.audit and dtype != 'f16x3':
+            raise ValueError("range_audit=True watches the lower range of dtype='f16x3', got dtype={!r}: the IEEE-half pair is a fixed-point "
+                             "number with a quantum of 2^-24 below 2^-14; bf16 halves keep float32's exponent and have no such regime, "
+                             "and the other types store no split halves".format(dtype))
+        self.small_magnitude_events = 0      # flagged (call, map) pairs
+        self.last_range_audit = None         # the report of the last synchronous call of an audit model
+        self._last_plan = None
         # pose=True: every plan ends with the pose stage (gpp_pose_f32 on the polling outputs) and predict_poses_on_batch /
         # predict_poses_on_frames fetch its rows; a model attribute, not a plan switch: without it every plan is what it was
         self.pose = bool(pose)
@@ -757,6 +839,90 @@ class RetinaNet3D(object):
         plan.emit(OP_POSE, pd, 'recover_pose', [plan.boxes, plan.dimensions, plan.scores, plan.labels, plan.orientations, plan.keypoints,
                                                 plan.residuals, plan.frame_info], [plan.pose_rows, plan.pose_counts])
 
+    def _audit(self, plan):
+        """ range_audit=True: one gpp_channel_absmax launch behind every launch that writes (a part, a level or a channel slice of) a map
+        that some convolution of the plan reads as its activation operand or adds as its residual -- the maps an x3 loop splits into
+        (hi, lo) halves or reads pre-split -- on that launch's lane, into the map's row of plan.audit_table; the first op of the plan
+        clears the table on the stream.  A map is a channel range of a buffer as its READERS name it (the three towers read three
+        slices of the fused first layer's 896 channels: three maps; the five levels of a pyramid tensor: one map).  Placed once every
+        op is known: who reads what is only known then.  Operands that never exist in HBM go to plan.audit_unobserved. """
+        torch, esz = self.torch, self.esz
+        views, order = {}, []                       # (buffer, pitch, first channel, channels) -> record
+
+        def key_of(f):
+            return (f.buf.data_ptr(), f.pitch, f.off % f.pitch, f.C)
+
+        for pos, (kind, _, desc, name, _) in enumerate(plan.ops):
+            io = plan.op_io[pos]
+            if kind == OP_CONV_PREACT:
+                lo, hi = min(a for a, _ in Plan.spans(io[0])), max(b for _, b in Plan.spans(io[0]))
+                plan.audit_unobserved.append({'name': name + '/operand', 'consumers': [name], 'extent': (lo, hi),
+                                              'reason': 'max(x * scale + shift, 0) is formed after the load (gpp_conv2d_preact)'})
+            elif kind == OP_MOBILENET_BLOCK:
+                plan.audit_unobserved.append({'name': name.replace('conv_pw_', 'conv_dw_'), 'consumers': [name], 'extent': None,
+                                              'reason': 'the depthwise result lives in LDS (gpp_mobilenet_block); bounded by ReLU6'})
+            elif kind == OP_CONV:
+                for f in list(io[0]) + list(io[2] or []):
+                    k = key_of(f)
+                    if k not in views:
+                        views[k] = {'consumers': [], 'producers': [], 'channels': f.C, 'spans': [], 'fmaps': [], 'split': f.split,
+                                    'layout': 'split_f16' if f.split else 'f32'}
+                        order.append(k)
+                    if name not in views[k]['consumers']:
+                        views[k]['consumers'].append(name)
+                    views[k]['spans'] += Plan.span(f)
+                    if not any((g.off, g.B, g.H, g.W) == (f.off, f.B, f.H, f.W) for g in views[k]['fmaps']):
+                        views[k]['fmaps'].append(f)
+        offset = 0
+        for k in order:
+            views[k]['row'] = (offset, k[3])
+            offset += k[3]
+        plan.audit_table = table = torch.zeros((max(offset, 1),), dtype=torch.int32, device=self.device)       # (uint32 bit patterns)
+        extra = {}
+        for pos, (kind, _, desc, name, _) in enumerate(plan.ops):
+            for k in order:
+                ptr, pitch, c0, c = k
+                outs = [o for o in plan.wrote[pos] if o.buf.data_ptr() == ptr and o.pitch == pitch]
+                if not outs:
+                    continue
+                oc0, oc = outs[0].off % pitch, outs[0].C
+                lo, hi = max(c0, oc0), min(c0 + c, oc0 + oc)
+                if lo >= hi:
+                    continue
+                v = views[k]
+                if name not in v['producers']:
+                    v['producers'].append(name)
+                # the pixels this launch wrote, as runs of consecutive pixels of the buffer (a dense batch, the five levels of every
+                # image of a pyramid tensor: one run; one level of a pyramid tensor: one run per image)
+                runs = []
+                for start, n in sorted(((o.off - oc0 + b * o.bstride) // pitch, o.H * o.W) for o in outs for b in range(o.B)):
+                    if runs and runs[-1][0] + runs[-1][1] == start:
+                        runs[-1][1] += n
+                    else:
+                        runs.append([start, n])
+                row = table[v['row'][0] + lo - c0:v['row'][0] + hi - c0]
+                for start, n in runs:
+                    d = hip.AbsmaxDesc(ptr + start * pitch * esz, row.data_ptr(), n, pitch, hi - lo, lo,
+                                       hip.GPP_ABSMAX_SPLIT_F16 if v['split'] else hip.GPP_ABSMAX_F32, 0)
+                    extra.setdefault(pos, []).append((OP_ABSMAX, d, 'absmax:' + name, outs, [row]))
+        plan.insert_behind(extra)
+        plan.keep.append(table)
+        clear = hip.AbsmaxClearDesc(table.data_ptr(), table.numel())
+        plan.emit(OP_ABSMAX_CLEAR, clear, 'absmax:clear', [], [table])
+        for lst in (plan.ops, plan.lanes, plan.access, plan.atomic, plan.wrote, plan.op_io):       # ... as the FIRST op of the plan
+            lst.insert(0, lst.pop())
+        for k in order:
+            v = views[k]
+            names = v['producers']
+            if not names:
+                raise RuntimeError('range audit: no launch of the plan writes the operand of {}'.format(v['consumers']))
+            # a channel slice of a launch's output carries the name of the layer it is in the reference (the fused first tower layer)
+            name = TOWER_SLICES.get((names[0], k[2]), names[0]) if len(names) == 1 else \
+                '+'.join(sorted(names)) if len(names) <= 5 else '{}..{}'.format(names[0], names[-1])
+            plan.audit_maps.append({'name': name, 'producers': names, 'consumers': v['consumers'], 'channels': v['channels'],
+                                    'layout': v['layout'], 'row': v['row'], 'fmaps': v['fmaps'],
+                                    'extent': (min(a for a, _ in v['spans']), max(b for _, b in v['spans']))})
+
     def _bind_workspaces(self, plan):
         """ split-K partial tiles of the deep-K layers with a tiny per-image grid (res5 branch2b, P5..P7): one workspace per stream lane
         (concurrent launches must not share partial tiles), sized from the descriptors of the whole plan """
@@ -795,6 +961,10 @@ class RetinaNet3D(object):
         # +1.2 %, B = 2 +0.7 %, batch-1 plan 2.67 -> 2.65 ms.  "" for the separate launches (bit-identical either way).  Projection
         # blocks too (GPP_FUSE_BLOCK_PROJ=1) measured -0.6 %: off.
         fuse_block = [int(v) for v in env('GPP_FUSE_BLOCK', '64,128').split(',') if v.strip()] if (x3 and x3_level >= 2) else []
+        if self.audit:
+            # an audit plan reads every operand map in HBM: the separate launches wherever a fused form keeps one in LDS (bit-identical
+            # to them: tests/test_block_gpu.py), so the results do not change
+            fuse_tail, fuse_block = [], []
         head_lanes = env('GPP_HEAD_LANES', '0') != '0'
         fpn_lanes = head_lanes or env('GPP_FPN_LANES', '1') != '0'
         overlap = env('GPP_DECODE_OVERLAP', '1') != '0' and not head_lanes and not self.osf
@@ -821,7 +991,8 @@ class RetinaNet3D(object):
             cls_lane=2 if (overlap and env('GPP_CLS_LANE', '1' if B <= 2 else '0') != '0') else 0,
             autotune=env('GPP_AUTOTUNE', '1') != '0',
             tune_key='x3split={};fuse={}/{};plan={}{}'.format(env('GPP_X3_SPLIT', '2'), env('GPP_FUSE_TAIL', '64,128'), env('GPP_FUSE_BLOCK', '64,128'),
-                                                              self.plan_mode, C.latency_split_config() if self.plan_mode == 'latency' else ''))
+                                                              self.plan_mode, C.latency_split_config() if self.plan_mode == 'latency' else '') +
+                     (';audit' if self.audit else ''))
 
     def _build(self, B, H, Wd, n_planes, planes_batched):
         torch, dev = self.torch, self.device
@@ -855,6 +1026,8 @@ class RetinaNet3D(object):
         self._poll(plan, B, n_planes, planes_batched)
         if self.pose:
             self._pose(plan, B)
+        if self.audit:
+            self._audit(plan)
         self._bind_workspaces(plan)
         plan.finalize()
         plan.tagged = [name for _, tag, _, name, _ in plan.ops if tag]
@@ -1043,6 +1216,7 @@ class RetinaNet3D(object):
         key = (int(B), int(H), int(Wd), int(n_planes), bool(planes_batched))
         if key not in self._plans:
             self._plans[key] = self._build(*key)
+        self._last_plan = self._plans[key]
         return self._plans[key]
 
     # ------------------------------------------------------------------ execution
@@ -1113,7 +1287,43 @@ class RetinaNet3D(object):
             count = int(self.range_snapshot(plan).cpu().view(self.torch.int64).item()) if watch else 0
         if watch and self.note_range(plan, count):
             return self._range_event([plan.images, plan.P_inv, plan.planes], 'predict_on_batch')
+        flagged = self._audit_flags(plan)
+        if flagged:
+            return self._range_event([plan.images, plan.P_inv, plan.planes], 'predict_on_batch', flagged)
         return outs
+
+    # ------------------------------------------------------------------ f16x3: the lower range, audited (range_audit=True)
+    def range_audit(self, plan=None):
+        """ range_audit=True: the report of the plan's last run (default: the plan of the last call), one record per audited map, from ONE
+        copy of the plan's abs-max table (synchronises): see audit_report for the fields and for what `flagged` does and does not say """
+        if not self.audit:
+            raise hip.GppError('this model keeps no range audit: load it with range_audit=True (models.load_model(..., range_audit=True))')
+        plan = plan or self._last_plan
+        if plan is None:
+            raise hip.GppError('range_audit: no plan has run yet')
+        return audit_report(plan.audit_maps, plan.audit_table.cpu().numpy())
+
+    def range_audit_unobserved(self, plan=None):
+        """ the x3 operands of the plan that a pass over HBM cannot see, [{name, consumers, reason}]: listed, not dropped silently """
+        plan = plan or self._last_plan
+        return [{k: u[k] for k in ('name', 'consumers', 'reason')} for u in plan.audit_unobserved]
+
+    def _audit_flags(self, plan):
+        """ an audit model's synchronous calls: read the table of the run just fetched (the one extra copy this mode accepts), keep the
+        report, count the flagged maps; returns those the call has to react to ([] for on_range_event='ignore' and for other models) """
+        if not self.audit:
+            return []
+        self.last_range_audit = self.range_audit(plan)
+        plan.audit_flagged = [r for r in self.last_range_audit if r['flagged']]
+        self.small_magnitude_events += len(plan.audit_flagged)
+        return plan.audit_flagged if self.on_range_event != 'ignore' else []
+
+    @staticmethod
+    def _small_magnitude_message(what, flagged):
+        return ('{}: the largest value of {} lies below 2^-9, where the IEEE-half pair of dtype=\'f16x3\' is a fixed-point number (quantum '
+                '2^-24) that keeps fewer than 16 bits of it: the result would not be the reference\'s -- load the model with dtype=\'f32\' '
+                'or on_range_event=\'f32\''.format(what, ', '.join('the map behind {} (read by {}; max {:.3g})'.format(
+                    r['name'], ', '.join(r['consumers']), r['absmax']) for r in flagged)))
 
     # ------------------------------------------------------------------ f16x3: the half range, watched
     def watches_range(self):
@@ -1152,10 +1362,12 @@ class RetinaNet3D(object):
         n = flat.size - 2
         return D.unpack_outputs(flat[:n].reshape(B, n // (B * D.PACK_WIDTH), D.PACK_WIDTH)), int(flat[n:].view(np.uint64)[0])
 
-    def _range_event(self, device_inputs, what):
-        """ an activation of the call just fetched left the half range: its result is not the reference's.  device_inputs = the call's
-        [images, P_inv, planes] still in HBM. """
+    def _range_event(self, device_inputs, what, flagged=None):
+        """ an activation of the call just fetched left the half range (or, flagged: a whole map of an audit model sits below it): its
+        result is not the reference's.  device_inputs = the call's [images, P_inv, planes] still in HBM. """
         self.range_fallbacks += 1
+        if self.on_range_event == 'raise' and flagged:
+            raise hip.GppError(self._small_magnitude_message(what, flagged))
         if self.on_range_event == 'raise':
             raise hip.GppError('{}: an activation left the IEEE-half range of dtype=\'f16x3\' (finite beyond +-65504, inf or NaN; '
                                'gpp_x3_range_events): the result would not be the reference\'s -- load the model with dtype=\'f32\' '
@@ -1295,6 +1507,9 @@ class RetinaNet3D(object):
             self.range_snapshot(plan, plan.pose_out[n:n + 2])
         flat = plan.pose_out.cpu().numpy()
         if watch and self.note_range(plan, int(flat[n:n + 2].view(np.uint64)[0])):
+            plan.audit_flagged = []
+            return None
+        if self._audit_flags(plan):
             return None
         return flat[:n].reshape(tuple(plan.pose_rows.shape)).copy(), flat[n + 2:].view(np.int32).copy()
 
@@ -1310,7 +1525,7 @@ class RetinaNet3D(object):
         self.run_plan(plan)
         out = self.fetch_poses(plan)
         if out is None:          # an activation left the half range: this call's answer comes from the float32 twin
-            self._range_event_raise_or_prepare('predict_poses_on_batch')
+            self._range_event_raise_or_prepare('predict_poses_on_batch', getattr(plan, 'audit_flagged', None))
             return self._twin.predict_poses_on_batch([plan.images, plan.P_inv, plan.planes], scales, image_shapes)
         return out
 
@@ -1322,13 +1537,15 @@ class RetinaNet3D(object):
         self.run_plan(plan)
         out = self.fetch_poses(plan)
         if out is None:
-            self._range_event_raise_or_prepare('predict_poses_on_frames')        # (the preprocessed frames are still in the plan)
+            self._range_event_raise_or_prepare('predict_poses_on_frames', getattr(plan, 'audit_flagged', None))        # (the preprocessed frames are still in the plan)
             out = self._twin.predict_poses_on_batch([plan.images, plan.P_inv, plan.planes], scale, tuple(frames_u8.shape[1:3]))
         return out, scale
 
-    def _range_event_raise_or_prepare(self, what):
+    def _range_event_raise_or_prepare(self, what, flagged=None):
         """ the bookkeeping of _range_event for the pose calls: count the event, raise (on_range_event='raise') or build the twin """
         self.range_fallbacks += 1
+        if self.on_range_event == 'raise' and flagged:
+            raise hip.GppError(self._small_magnitude_message(what, flagged))
         if self.on_range_event == 'raise':
             raise hip.GppError('{}: an activation left the IEEE-half range of dtype=\'f16x3\' (gpp_x3_range_events): load the model '
                                'with dtype=\'f32\' or on_range_event=\'f32\''.format(what))

@@ -84,6 +84,9 @@ class ShardedModel(object):
     """ Wraps a model: predict_on_batch on a GLOBAL batch, each rank computing its contiguous shard. """
 
     def __init__(self, model, group=None):
+        if getattr(model, 'audit', False):
+            raise ValueError('ShardedModel does not read the range audit of a model loaded with range_audit=True: it would run unwatched '
+                             '-- audit one rank\'s model with predict_on_batch, or load the model without range_audit')
         self.model = model
         self.group = group
 

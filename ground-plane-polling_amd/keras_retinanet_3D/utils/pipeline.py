@@ -26,6 +26,9 @@ class FramePipeline(object):
 
     def __init__(self, model, depth=4, graph=False, pinned=False, inline=False):
         import torch
+        if getattr(model, 'audit', False):
+            raise ValueError('FramePipeline does not read the range audit of a model loaded with range_audit=True: it would run unwatched '
+                             '-- use predict_on_frames, or load the model without range_audit')
         self.model = model
         self.torch = torch
         self.depth = max(3, int(depth))

@@ -477,6 +477,35 @@ int gpp_pose_f32(const float* boxes, const float* dims, const float* scores, con
                  float* rows, int32_t* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Range audit of dtype='f16x3' (csrc/audit.hip; opt-in: RetinaNet3D(range_audit=True)): the largest |x| of
+ * every channel of one NHWC map, read in one of the three forms an x3 convolution reads its activation operand in.
+ *
+ *   in      the map's buffer; pixel m starts at element m * pitch of it, the audited channels are [c_off, c_off + C) of every pixel
+ *           (pitch >= c_off + C: a channel prefix or slice of a wider buffer).  Elements are float32-sized in every layout.
+ *   layout  GPP_ABSMAX_F32         plain float32 rows; any C >= 1 (16-byte loads when C, pitch and the first channel allow them)
+ *           GPP_ABSMAX_SPLIT_F16   pre-split rows (gpp_conv_desc.x3_split): every 32 channels are 128 bytes [32 IEEE halves hi | 32 lo],
+ *           GPP_ABSMAX_SPLIT_BF16  or bf16 halves; the value of a channel is float(hi) + float(lo).  C, pitch and c_off multiples of 32
+ *                                  and `in` 128-byte aligned, else GPP_ERR_BAD_ARG / GPP_ERR_ALIGN.
+ *   out     uint32 [C], device: out[c] = max(out[c], bits(|x[m, c_off + c]|)) over the M pixels.  Non-negative floats order like their
+ *           bit patterns, so this is an integer maximum (one relaxed atomic per channel per workgroup): independent of the order of
+ *           arrival, a NaN wins over every number and stays visible, and a launch ADDS to what earlier launches left (two half batches,
+ *           five pyramid levels).  The caller clears the table: gpp_absmax_clear (a memset on the stream).
+ *   Null pointer, C <= 0, M < 0, pitch < c_off + C, unknown layout, reserved != 0: GPP_ERR_BAD_ARG, nothing launched (checked on the
+ *   host, no device needed).  M == 0: GPP_OK, nothing launched.
+ * ---------------------------------------------------------------------------------------- */
+#define GPP_ABSMAX_F32 1
+#define GPP_ABSMAX_SPLIT_F16 2
+#define GPP_ABSMAX_SPLIT_BF16 3
+typedef struct gpp_absmax_desc {
+    const void* in; uint32_t* out;
+    int64_t M, pitch;
+    int32_t C, c_off, layout, reserved;
+} gpp_absmax_desc;
+typedef struct gpp_absmax_clear_desc { uint32_t* table; int64_t n; } gpp_absmax_clear_desc;
+int gpp_channel_absmax(const gpp_absmax_desc* desc, void* stream);
+int gpp_absmax_clear(uint32_t* table, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Plan execution: one call enqueues a whole predict_on_batch (every kernel of the graph that
  * models/retinanet.py:359-422 `retinanet_bbox` builds) from a host array of descriptors.
  * The runner holds no state: the caller (Python) keeps the descriptors and buffers alive.
@@ -504,6 +533,8 @@ int gpp_pose_f32(const float* boxes, const float* dims, const float* scores, con
 #define GPP_OP_CONV_PREACT 32            /* gpp_preact_desc -> gpp_conv2d_preact (DenseNet); kinds 0..255 exist */
 #define GPP_OP_MOBILENET_STEM 33         /* gpp_mobilenet_stem_desc -> gpp_mobilenet_stem */
 #define GPP_OP_MOBILENET_BLOCK 34        /* gpp_mobilenet_block_desc -> gpp_mobilenet_block */
+#define GPP_OP_ABSMAX 35                 /* gpp_absmax_desc -> gpp_channel_absmax (opt-in: RetinaNet3D(range_audit=True)) */
+#define GPP_OP_ABSMAX_CLEAR 36           /* gpp_absmax_clear_desc -> gpp_absmax_clear: the first op of an audit plan */
 /* (14, 15: the Winograd F(2, 3) form of the tower layers of round 5 -- built, measured at -2 % of the step, shelved in round 6:
    tools/experiments/winograd/) */
 /* Optional concurrency inside a plan: `kind | GPP_OP_LANE(l)` (l = 1, 2) enqueues the op on a library-owned side stream
@@ -530,6 +561,7 @@ int gpp_pose_f32(const float* boxes, const float* dims, const float* scores, con
 #define GPP_STAGE_DECODE 5
 #define GPP_STAGE_POLLING 6
 #define GPP_STAGE_POSE 8
+#define GPP_STAGE_AUDIT 9                /* "gpp:audit": the GPP_OP_ABSMAX launches of an audit plan */
 
 typedef struct gpp_stem_desc { const float* in; const void* weight; const float* bias; void* out;
                                int32_t dtype, B, H, W; uint64_t* range_counter; /* GPP_F16X3: see gpp_stem_conv7x7_bn_relu_x3_rc; NULL otherwise */
