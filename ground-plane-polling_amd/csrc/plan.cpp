@@ -180,6 +180,32 @@ extern "C" int gpp_plan_run(const gpp_plan_op* ops, int n_ops, void* stream, voi
             rc = gpp_maxpool3x3s2_same(d->in, d->out, d->dtype, d->B, d->H, d->W, d->C, stream);
             break;
         }
+        case GPP_OP_STEM_RAGGED: {      // the three launches above for a batch of one height class (gpp_ragged_stem_desc)
+            const gpp_ragged_stem_desc* r = (const gpp_ragged_stem_desc*)op.desc;
+            const gpp_stem_desc* d = &r->stem;
+            if (d->dtype == GPP_F32)
+                rc = gpp_stem_conv7x7_bn_relu_ragged(d->in, (const float*)d->weight, d->bias, d->out, d->dtype, d->B, d->H, d->W, r->Hp, r->heights, stream);
+            else if (d->dtype == GPP_F16X3 || d->dtype == GPP_BF16X3)
+                rc = gpp_stem_conv7x7_bn_relu_x3_rc_ragged(d->in, d->weight, d->bias, (float*)d->out, d->B, d->H, d->W, r->Hp, r->heights, d->range_counter, stream);
+            else
+                rc = gpp_stem_conv7x7_bn_relu_mfma_ragged(d->in, d->weight, d->bias, d->out, d->dtype, d->B, d->H, d->W, r->Hp, r->heights, stream);
+            break;
+        }
+        case GPP_OP_STEM_POOL_RAGGED: {
+            const gpp_ragged_stem_desc* r = (const gpp_ragged_stem_desc*)op.desc;
+            const gpp_stem_desc* d = &r->stem;
+            if (d->dtype == GPP_F16X3 || d->dtype == GPP_BF16X3)
+                rc = gpp_stem_pool_fused_x3_ragged(d->in, d->weight, d->bias, (float*)d->out, d->B, d->H, d->W, r->Hp, r->heights, d->range_counter, stream);
+            else
+                rc = gpp_stem_pool_fused_mfma_ragged(d->in, d->weight, d->bias, d->out, d->dtype, d->B, d->H, d->W, r->Hp, r->heights, stream);
+            break;
+        }
+        case GPP_OP_MAXPOOL_RAGGED: {
+            const gpp_ragged_pool_desc* r = (const gpp_ragged_pool_desc*)op.desc;
+            const gpp_pool_desc* d = &r->pool;
+            rc = gpp_maxpool3x3s2_same_ragged(d->in, d->out, d->dtype, d->B, d->H, d->W, d->C, r->Hp, r->heights, stream);
+            break;
+        }
         case GPP_OP_CONV:
             rc = gpp_conv2d_igemm((const gpp_conv_desc*)op.desc, stream);
             break;

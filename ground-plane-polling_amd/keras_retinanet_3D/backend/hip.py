@@ -153,6 +153,19 @@ def _declare(lib):
         lib.gpp_channel_absmax.argtypes = [ctypes.POINTER(AbsmaxDesc), c_void_p]
         lib.gpp_absmax_clear.restype = c_int
         lib.gpp_absmax_clear.argtypes = [c_void_p, c_int64, c_void_p]
+    # ragged batches (include/gpp.h): the stem, pool1 and the preprocessing with per-image heights read from a device table
+    # (absent from an older build named by GPP_LIB: it runs every plan but a ragged one, whose ops it refuses)
+    if hasattr(lib, 'gpp_stem_pool_fused_x3_ragged'):
+        for name in ('gpp_stem_conv7x7_bn_relu_ragged', 'gpp_stem_conv7x7_bn_relu_mfma_ragged', 'gpp_stem_pool_fused_mfma_ragged'):
+            getattr(lib, name).restype = c_int
+            getattr(lib, name).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+        for name in ('gpp_stem_conv7x7_bn_relu_x3_rc_ragged', 'gpp_stem_pool_fused_x3_ragged'):
+            getattr(lib, name).restype = c_int
+            getattr(lib, name).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+        lib.gpp_maxpool3x3s2_same_ragged.restype = c_int
+        lib.gpp_maxpool3x3s2_same_ragged.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+        lib.gpp_preprocess_u8_bgr_ragged.restype = c_int
+        lib.gpp_preprocess_u8_bgr_ragged.argtypes = [c_void_p] * 10 + [c_int] * 6 + [c_float] * 3 + [c_void_p]
     lib.gpp_relu.restype = c_int
     lib.gpp_relu.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_void_p]
     lib.gpp_preprocess_u8_bgr.restype = c_int

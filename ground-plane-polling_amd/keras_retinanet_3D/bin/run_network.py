@@ -127,6 +127,20 @@ def write_results_from_rows(args, output_dir, item, rows_b, count):
             print('--save-images needs OpenCV (cv2), which is not installed: skipping the composite image')
 
 
+def group_items(model, items):
+    """ the items of one batch in groups that run as one call each.  A model with a ragged form (RetinaNet3D.supports_ragged: the ResNets)
+    takes every frame of one height class (utils/image.height_class: the four KITTI frame sizes are one class) in one call; any other
+    model takes frames of one raw shape per call, as the reference's batches must be.  Returns [(items, ragged)]: ragged = the
+    group mixes raw shapes and goes to the model as a list. """
+    from ..utils.image import height_class
+    ragged_ok = getattr(model, 'supports_ragged', False)
+    groups = {}
+    for it in items:
+        shape = tuple(it['raw_image'].shape)
+        groups.setdefault(height_class(shape) if ragged_ok else shape, []).append(it)
+    return [(group, len(set(tuple(it['raw_image'].shape) for it in group)) > 1) for group in groups.values()]
+
+
 def main(args=None):
     if args is None:
         args = sys.argv[1:]
@@ -142,16 +156,14 @@ def main(args=None):
     for start in range(0, len(files), max(args.batch_size, 1)):
         on_device = hasattr(model, 'predict_on_frames')
         items = [load_item(args, fn, on_device) for fn in files[start:start + max(args.batch_size, 1)]]
-        # images of one batch must share a shape (KITTI frames of one drive do); split otherwise
-        groups = {}
-        for it in items:
-            groups.setdefault(it['raw_image'].shape, []).append(it)
-        for group in groups.values():
+        # images of one call share a shape, or (a model with a ragged form) a height class; split otherwise
+        for group, ragged in group_items(model, items):
+            stack = list if ragged else np.stack          # a ragged group goes to the model as a list of differently sized frames
             P_inv = np.stack([it['P_inv'] for it in group])
             planes = np.tile(plane_params[None], (len(group), 1, 1))
             t0 = time.time()
             if args.device_pose:
-                frames = np.stack([it['raw_image'] for it in group])
+                frames = stack([it['raw_image'] for it in group])
                 (rows, counts), _ = model.predict_poses_on_frames(frames, P_inv, planes)
                 dt = time.time() - t0
                 keep_smallest(audit, model)
@@ -161,9 +173,9 @@ def main(args=None):
                     write_results_from_rows(args, output_dir, it, rows[k], counts[k])
                 continue
             if on_device:
-                outputs = model.predict_on_frames(np.stack([it['raw_image'] for it in group]), P_inv, planes)[0][:8]
+                outputs = model.predict_on_frames(stack([it['raw_image'] for it in group]), P_inv, planes)[0][:8]
             else:
-                outputs = model.predict_on_batch([np.stack([it['image'] for it in group]), P_inv, planes])[:8]
+                outputs = model.predict_on_batch([stack([it['image'] for it in group]), P_inv, planes])[:8]
             dt = time.time() - t0
             keep_smallest(audit, model)
             for k, it in enumerate(group):

@@ -54,6 +54,16 @@ class PoolDesc(ctypes.Structure):
                 ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('C', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
+class RaggedStemDesc(ctypes.Structure):
+    """ gpp_ragged_stem_desc (include/gpp.h): the stem of a batch of one height class; H of `stem` = the 4 Hp rows of the canvas """
+    _fields_ = [('stem', StemDesc), ('heights', ctypes.c_void_p), ('Hp', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
+class RaggedPoolDesc(ctypes.Structure):
+    """ gpp_ragged_pool_desc (include/gpp.h): pool1 behind a ragged stem; H of `pool` = the 2 Hp rows of the stored conv map """
+    _fields_ = [('pool', PoolDesc), ('heights', ctypes.c_void_p), ('Hp', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
 class ReluDesc(ctypes.Structure):
     _fields_ = [('inp', ctypes.c_void_p), ('out', ctypes.c_void_p), ('in_bstride', ctypes.c_int64),
                 ('out_bstride', ctypes.c_int64), ('count', ctypes.c_int64), ('dtype', ctypes.c_int32), ('B', ctypes.c_int32)]
@@ -110,6 +120,7 @@ OP_MAXPOOL_PAD, OP_AVGPOOL, OP_CONV_PREACT = 17, 18, 32         # DenseNet (incl
 OP_MOBILENET_STEM, OP_MOBILENET_BLOCK = 33, 34                  # MobileNet (include/gpp.h)
 OP_POSE = 19                                                    # RetinaNet3D(pose=True): gpp_pose_f32 behind the polling
 OP_ABSMAX, OP_ABSMAX_CLEAR = 35, 36                             # RetinaNet3D(range_audit=True): gpp_channel_absmax behind every audited map
+OP_STEM_RAGGED, OP_STEM_POOL_RAGGED, OP_MAXPOOL_RAGGED = 37, 38, 39    # ragged plans (plan_for(..., ragged=True)): per-image heights from a device table
 DETECT_OPS = (OP_DETECT, OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT, 12)
 OP_JOIN, OP_SYNC = 0x10000, 0x20000
 
@@ -202,6 +213,8 @@ class Plan(object):
         self.ws_need = {}       # stream lane -> the largest split-K workspace one of its conv descriptors needs
         self.array = None
         self.flops = 0.0
+        self.ragged = False     # plan_for(..., ragged=True): the plan of a height class; heights = its int32 device table, heights_host = what it holds
+        self.heights = None
 
     def emit(self, kind, desc, name, reads=(), writes=(), tag=0, flops=0.0, lane=0, join=False, sync=False, io=None, inner=(), atomic=()):
         """ record one launch.  reads / writes: the FMaps and tensors it reads and writes (check_stream_ordering); io: its
@@ -304,7 +317,7 @@ class Plan(object):
     @staticmethod
     def stage_of(kind, name):
         """ include/gpp.h GPP_OP_STAGE: 1 stem, 2 backbone, 3 FPN, 4 heads, 5 decode, 6 polling, 8 pose, 9 audit (roctx ranges under GPP_ROCTX=1) """
-        if kind in (OP_STEM, OP_MAXPOOL, OP_STEM_POOL, OP_MAXPOOL_PAD, OP_MOBILENET_STEM):
+        if kind in (OP_STEM, OP_MAXPOOL, OP_STEM_POOL, OP_MAXPOOL_PAD, OP_MOBILENET_STEM, OP_STEM_RAGGED, OP_STEM_POOL_RAGGED, OP_MAXPOOL_RAGGED):
             return 1
         if kind in DETECT_OPS:
             return 5
@@ -558,6 +571,18 @@ class RetinaNet3D(object):
                      plan.range_slot.data_ptr() if self.dtype == 'f16x3' else None)
         flops = 2.0 * B * H1 * W1 * 147 * 64
         plan.stem_out, plan.pool_out = (None if opts.fuse_stem_pool else conv), x
+        if plan.ragged:
+            # a batch of one height class: H = the 4 Hp rows of the canvas, H1 = 2 Hp the rows of the class's largest conv map; every image's own
+            # height comes from plan.heights on the device (the same launches, per-image H / Ho / pad_top: csrc/stem_kernels.h)
+            rd = RaggedStemDesc(d, plan.heights.data_ptr(), x.H, 0)
+            if opts.fuse_stem_pool:
+                plan.emit(OP_STEM_POOL_RAGGED, rd, 'conv1+pool1', [plan.images, plan.heights], [x], flops=flops)
+                return
+            plan.emit(OP_STEM_RAGGED, rd, 'conv1', [plan.images, plan.heights], [conv], flops=flops)
+            pd = RaggedPoolDesc(PoolDesc(conv.buf.data_ptr(), x.buf.data_ptr(), C.gpp_storage_dtype(self.dtype), B, H1, W1, 64, 0),
+                                plan.heights.data_ptr(), x.H, 0)
+            plan.emit(OP_MAXPOOL_RAGGED, pd, 'pool1', [conv, plan.heights], [C.FMap(x.buf, B, x.H, x.W, 64, pitch=x.pitch)])
+            return
         if opts.fuse_stem_pool:
             plan.emit(OP_STEM_POOL, d, 'conv1+pool1', [plan.images], [x], flops=flops)
             return
@@ -994,11 +1019,27 @@ class RetinaNet3D(object):
                                                               self.plan_mode, C.latency_split_config() if self.plan_mode == 'latency' else '') +
                      (';audit' if self.audit else ''))
 
-    def _build(self, B, H, Wd, n_planes, planes_batched):
+    def _build(self, B, H, Wd, n_planes, planes_batched, ragged=False):
+        """ ragged: the plan of a height class (utils/image.py) -- H = 4 Hp is the row count of the canvas, and the stem and pool1 take
+        every image's own height from plan.heights (int32, on the device: data of the plan, so one plan and one captured graph serve
+        every mix of heights); everything behind pool1 is the uniform plan's """
         torch, dev = self.torch, self.device
+        if ragged:
+            if self.mobilenet or self.densenet:
+                raise ValueError('{} has no ragged form: {}; run its images grouped by shape'.format(
+                    self.backbone_name, 'its first block runs at conv1\'s resolution, which differs inside a height class' if self.mobilenet
+                    else 'its zero-padded pool1 (gpp_maxpool3x3s2_pad_f32) has no per-image form'))
+            if self.audit:
+                raise ValueError('range_audit=True has no ragged form: the audit of the conv1 map reads rows that a shorter image does not have')
+            if H % 4:
+                raise ValueError('the canvas of a ragged plan has 4 Hp rows, got {}'.format(H))
         opts = self._plan_options(B)
         plan = Plan()
         plan.shape = (B, H, Wd, n_planes, planes_batched)
+        plan.ragged = bool(ragged)
+        if ragged:
+            plan.heights = torch.full((B,), H, dtype=torch.int32, device=dev)
+            plan.heights_host = [H] * B
         plan.side_lanes = {'fpn': opts.fpn_lanes, 'branch1': opts.br1_lane, 'p4': bool(opts.p4_lane),
                            'half_batch_stages': sorted(opts.half_stages), 'cls_tower': bool(opts.cls_lane)}
         plan.decode_overlap = opts.decode_overlap
@@ -1212,12 +1253,29 @@ class RetinaNet3D(object):
         plan.range_seen = count
         return True
 
-    def plan_for(self, B, H, Wd, n_planes, planes_batched):
+    def plan_for(self, B, H, Wd, n_planes, planes_batched, ragged=False):
+        """ ragged=True: the plan of the height class whose canvas has H = 4 Hp rows (key: the class in place of H) """
         key = (int(B), int(H), int(Wd), int(n_planes), bool(planes_batched))
+        if ragged:
+            key = (key[0], ('class', key[1] // 4), key[2], key[3], key[4])
         if key not in self._plans:
-            self._plans[key] = self._build(*key)
+            self._plans[key] = self._build(int(B), int(H), *key[2:], **({'ragged': True} if ragged else {}))
         self._last_plan = self._plans[key]
         return self._plans[key]
+
+    def put_heights(self, plan, heights):
+        """ the image heights of the next run of a ragged plan into its device table (asynchronous).  The library cannot read the table,
+        so the range is checked here: every height must lie in the plan's class, [4 Hp - 3, 4 Hp]. """
+        from ..utils import image as image_utils
+        if not getattr(plan, 'ragged', False):
+            raise ValueError('put_heights: not a ragged plan')
+        B, rows = plan.shape[0], plan.shape[1]
+        lo, hi = image_utils.class_height_range(rows // 4)
+        h = [int(v) for v in np.asarray(heights).reshape(-1)]
+        if len(h) != B or any(v < lo or v > hi for v in h):
+            raise ValueError('heights {} do not fit the plan: {} images of height {}..{} (class Hp = {})'.format(h, B, lo, hi, rows // 4))
+        plan.heights_host = h
+        plan.heights.copy_(self.torch.as_tensor(np.asarray(h, dtype=np.int32)), non_blocking=True)
 
     # ------------------------------------------------------------------ execution
     def _require_hip(self):          # a model built on another device (the CPU plan tests): its plans can be inspected, never run
@@ -1286,7 +1344,7 @@ class RetinaNet3D(object):
             outs = [t.cpu().numpy() for t in self.outputs(plan)]
             count = int(self.range_snapshot(plan).cpu().view(self.torch.int64).item()) if watch else 0
         if watch and self.note_range(plan, count):
-            return self._range_event([plan.images, plan.P_inv, plan.planes], 'predict_on_batch')
+            return self._range_event([plan.images, plan.P_inv, plan.planes], 'predict_on_batch', heights=self._heights_of(plan))
         flagged = self._audit_flags(plan)
         if flagged:
             return self._range_event([plan.images, plan.P_inv, plan.planes], 'predict_on_batch', flagged)
@@ -1362,9 +1420,14 @@ class RetinaNet3D(object):
         n = flat.size - 2
         return D.unpack_outputs(flat[:n].reshape(B, n // (B * D.PACK_WIDTH), D.PACK_WIDTH)), int(flat[n:].view(np.uint64)[0])
 
-    def _range_event(self, device_inputs, what, flagged=None):
+    @staticmethod
+    def _heights_of(plan):
+        return plan.heights_host if getattr(plan, 'ragged', False) else None
+
+    def _range_event(self, device_inputs, what, flagged=None, heights=None):
         """ an activation of the call just fetched left the half range (or, flagged: a whole map of an audit model sits below it): its
-        result is not the reference's.  device_inputs = the call's [images, P_inv, planes] still in HBM. """
+        result is not the reference's.  device_inputs = the call's [images, P_inv, planes] still in HBM; heights: the call ran a ragged
+        plan, images is its canvas (the twin gets the same canvas and heights). """
         self.range_fallbacks += 1
         if self.on_range_event == 'raise' and flagged:
             raise hip.GppError(self._small_magnitude_message(what, flagged))
@@ -1375,11 +1438,11 @@ class RetinaNet3D(object):
         self.prepare_fallback()
         if what == 'predict_on_frames':          # device_inputs = [frames uint8, P_inv, planes]: preprocessing included
             return self._twin.predict_on_frames(*device_inputs)[0]
-        plan = self._twin.stage_inputs(device_inputs)
+        plan = self._twin.stage_inputs(device_inputs) if heights is None else self._twin.stage_canvas(device_inputs, heights)
         self._twin.run_plan(plan)
         return self._twin.fetch(plan)
 
-    def prepare_fallback(self, B=None, H=None, Wd=None, n_planes=None, planes_batched=True):
+    def prepare_fallback(self, B=None, H=None, Wd=None, n_planes=None, planes_batched=True, ragged=False):
         """ on_range_event='f32': build the float32 twin NOW -- its weights upload (a second copy of the weights in HBM) and, when a shape is
         given, its plan for that shape (buffers + tile tuning: seconds) -- instead of inside the first call whose activations leave the half
         range, where it would stall a latency-critical predict_on_batch / FramePipeline iteration (and every other rank of a sharded call).
@@ -1392,7 +1455,7 @@ class RetinaNet3D(object):
                                      name=self.name + '-f32-twin', plan=self.plan_mode, pose=self.pose)
             self._weights = None
         if B is not None:
-            self._twin.plan_for(B, H, Wd, n_planes, planes_batched)
+            self._twin.plan_for(B, H, Wd, n_planes, planes_batched, ragged=ragged)
         return self._twin
 
     def stage_inputs(self, inputs):
@@ -1401,6 +1464,8 @@ class RetinaNet3D(object):
         if not isinstance(inputs, (list, tuple)) or len(inputs) != 3:
             raise ValueError('predict_on_batch expects [images, P_inv, planes]')
         images, P_inv, planes = inputs
+        if isinstance(images, (list, tuple)):
+            return self._stage_ragged_images(images, P_inv, planes)
         shp = tuple(images.shape)
         if len(shp) != 4 or shp[3] != 3:
             raise ValueError('images must be (B, H, W, 3), got {}'.format(shp))
@@ -1437,6 +1502,100 @@ class RetinaNet3D(object):
         put(plan.planes, planes)
         return plan
 
+    # ------------------------------------------------------------------ ragged batches: images of one height class, different heights
+    @property
+    def supports_ragged(self):
+        """ predict_on_batch / predict_on_frames / predict_poses_on_frames take a LIST of images of one height class (the ResNets; not
+        with range_audit=True) """
+        return not (self.mobilenet or self.densenet or self.audit)
+
+    @staticmethod
+    def _check_calibration(B, P_inv, planes):
+        if tuple(P_inv.shape) != (B, 4, 3):
+            raise ValueError('P_inv must be (B, 4, 3), got {}'.format(tuple(P_inv.shape)))
+        pshape = tuple(planes.shape)
+        batched = len(pshape) == 3
+        if not ((batched and pshape[0] == B and pshape[2] == 4) or (len(pshape) == 2 and pshape[1] == 4)) or pshape[-2] < 1:
+            raise ValueError('planes must be (B, N, 4) or (N, 4), got {}'.format(pshape))
+        return pshape[-2], batched
+
+    def _put(self, dst, src):
+        torch = self.torch
+        src_t = src if isinstance(src, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(src, dtype=np.float32))
+        dst.copy_(src_t.to(dtype=dst.dtype), non_blocking=True)
+
+    def stage_canvas(self, inputs, heights):
+        """ stage_inputs for a ragged batch that is already a canvas: inputs = [canvas (B, 4 Hp, W, 3) float32 with image b in rows
+        [0, heights[b]) of slot b, P_inv, planes]; returns the ragged plan of the class """
+        canvas, P_inv, planes = inputs
+        shp = tuple(canvas.shape)
+        if len(shp) != 4 or shp[3] != 3 or shp[1] % 4:
+            raise ValueError('the canvas must be (B, 4 Hp, W, 3), got {}'.format(shp))
+        n_planes, batched = self._check_calibration(shp[0], P_inv, planes)
+        plan = self.plan_for(shp[0], shp[1], shp[2], n_planes, batched, ragged=True)
+        self.put_heights(plan, heights)
+        self._put(plan.images, canvas)
+        self._put(plan.P_inv, P_inv)
+        self._put(plan.planes, planes)
+        return plan
+
+    def _stage_ragged_images(self, images, P_inv, planes):
+        """ images: a list of (H_i, W, 3) float32 arrays (NumPy or torch) of ONE height class -> the canvas and the heights of its plan """
+        from ..utils import image as image_utils
+        torch = self.torch
+        shapes = [tuple(im.shape) for im in images]
+        if not shapes or any(len(s) != 3 or s[2] != 3 for s in shapes):
+            raise ValueError('a ragged batch is a non-empty list of (H, W, 3) images, got shapes {}'.format(shapes))
+        classes = sorted(set(image_utils.class_of_resized(s[0], s[1]) for s in shapes))
+        if len(classes) != 1:
+            raise ValueError('the images span {} height classes (Hp, W): {}: a ragged batch holds one class '
+                             '(utils.image.split_by_height_class groups a list)'.format(len(classes), ' and '.join(str(c) for c in classes)))
+        (Hp, Wd), B = classes[0], len(shapes)
+        if all(isinstance(im, torch.Tensor) for im in images):
+            canvas = torch.zeros((B, 4 * Hp, Wd, 3), dtype=torch.float32, device=images[0].device)
+            for b, im in enumerate(images):
+                canvas[b, :shapes[b][0]] = im
+        else:
+            canvas = np.zeros((B, 4 * Hp, Wd, 3), np.float32)
+            for b, im in enumerate(images):
+                canvas[b, :shapes[b][0]] = im.cpu().numpy() if isinstance(im, torch.Tensor) else im
+        return self.stage_canvas([canvas, P_inv, planes], [s[0] for s in shapes])
+
+    def _stage_ragged_frames(self, frames, P_inv, planes, min_side, max_side):
+        """ frames: a list of (h_i, w_i, 3) uint8 frames that resize into ONE height class: uploads the raw bytes (frame b densely at the
+        start of slot b of a uint8 canvas of the largest raw size) and preprocesses them into the plan's canvas on the device
+        (gpp_preprocess_u8_bgr_ragged, per-image taps).  Returns (plan, scales (B,)). """
+        from ..utils import image as image_utils
+        torch, dev = self.torch, self.device
+        frames = [f.cpu().numpy() if isinstance(f, torch.Tensor) else np.asarray(f) for f in frames]
+        if not frames or any(f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 for f in frames):
+            raise ValueError('a ragged batch of frames is a non-empty list of (h, w, 3) uint8 frames')
+        shapes = tuple((int(f.shape[0]), int(f.shape[1])) for f in frames)
+        (Hp, Wo), heights, scales, taps = image_utils.ragged_taps(shapes, min_side, max_side)      # (ValueError: more than one class)
+        B, Hr, Wr = len(frames), max(s[0] for s in shapes), max(s[1] for s in shapes)
+        n_planes, batched = self._check_calibration(B, P_inv, planes)
+        if not hasattr(self, '_ragged_taps'):
+            self._ragged_taps = {}
+        key = (shapes, min_side, max_side)
+        if key not in self._ragged_taps:
+            self._ragged_taps[key] = [torch.as_tensor(a).to(dev) for a in taps] + [torch.as_tensor(np.asarray(shapes, dtype=np.int32)).to(dev)]
+        y0, y1, wy, x0, x1, wx, raw_hw = self._ragged_taps[key]
+        plan = self.plan_for(B, 4 * Hp, Wo, n_planes, batched, ragged=True)
+        self.put_heights(plan, heights)
+        raw = np.zeros((B, Hr * Wr * 3), np.uint8)
+        for b, f in enumerate(frames):
+            raw[b, :f.size] = f.reshape(-1)
+        frames_d = torch.as_tensor(raw).to(dev, non_blocking=True)
+        m = image_utils.IMAGENET_MEAN_BGR
+        hip.check(hip.lib().gpp_preprocess_u8_bgr_ragged(hip.ptr(frames_d), hip.ptr(plan.images), hip.ptr(raw_hw), hip.ptr(plan.heights),
+                                                         hip.ptr(y0), hip.ptr(y1), hip.ptr(wy), hip.ptr(x0), hip.ptr(x1), hip.ptr(wx),
+                                                         B, Hr, Wr, Hp, 4 * Hp, Wo, float(m[0]), float(m[1]), float(m[2]), hip.stream_ptr()),
+                  'gpp_preprocess_u8_bgr_ragged')
+        self._put(plan.P_inv, P_inv)
+        self._put(plan.planes, planes)
+        plan.keep_frames = frames_d
+        return plan, np.asarray(scales, dtype=np.float64)
+
     # ------------------------------------------------------------------ raw frames (GPU preprocessing)
     def stage_frames(self, frames_u8, P_inv, planes, min_side=800, max_side=1333):
         """ frames_u8 (B, H, W, 3) uint8 BGR as utils.image.read_image_bgr returns them.  Uploads the raw
@@ -1444,6 +1603,8 @@ class RetinaNet3D(object):
         bin/run_network.py:95-99 does on the host.  Returns (plan, scale). """
         from ..utils import image as image_utils
         torch = self.torch
+        if isinstance(frames_u8, (list, tuple)):          # frames of one height class, different sizes: (plan, scales (B,))
+            return self._stage_ragged_frames(frames_u8, P_inv, planes, min_side, max_side)
         frames = frames_u8 if isinstance(frames_u8, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(frames_u8))
         if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
             raise ValueError('frames must be (B, H, W, 3) uint8, got {} {}'.format(tuple(frames.shape), frames.dtype))
@@ -1513,32 +1674,33 @@ class RetinaNet3D(object):
             return None
         return flat[:n].reshape(tuple(plan.pose_rows.shape)).copy(), flat[n + 2:].view(np.int32).copy()
 
-    def predict_poses_on_batch(self, inputs, scales, image_shapes):
+    def predict_poses_on_batch(self, inputs, scales, image_shapes, heights=None):
         """ predict_on_batch + what bin/run_network.py does with its result on the host, on the device: inputs as predict_on_batch;
         scales: the image scale of every image (or one for all); image_shapes: the raw images' (height, width[, 3]) (or one for all).
         Returns (rows (B, 100, 36) float32 -- include/gpp.h, gpp_pose_f32 --, counts (B,) int32: the detections above the score
         threshold, which are the first counts[b] rows of image b).  utils.gpp_utils.detections_from_rows / kitti_lines_from_rows
         turn one image's rows into the dict of recover_pose / the KITTI text. """
         self._require_pose()
-        plan = self.stage_inputs(inputs)
+        plan = self.stage_inputs(inputs) if heights is None else self.stage_canvas(inputs, heights)      # (heights: inputs[0] is a ragged canvas)
         self.put_frame_info(plan, scales, image_shapes)
         self.run_plan(plan)
         out = self.fetch_poses(plan)
         if out is None:          # an activation left the half range: this call's answer comes from the float32 twin
             self._range_event_raise_or_prepare('predict_poses_on_batch', getattr(plan, 'audit_flagged', None))
-            return self._twin.predict_poses_on_batch([plan.images, plan.P_inv, plan.planes], scales, image_shapes)
+            return self._twin.predict_poses_on_batch([plan.images, plan.P_inv, plan.planes], scales, image_shapes, heights=self._heights_of(plan))
         return out
 
     def predict_poses_on_frames(self, frames_u8, P_inv, planes):
         """ predict_poses_on_batch for raw uint8 BGR frames (predict_on_frames): returns ((rows, counts), scale) """
         self._require_pose()
         plan, scale = self.stage_frames(frames_u8, P_inv, planes)
-        self.put_frame_info(plan, scale, tuple(frames_u8.shape[1:3]))
+        shapes = [tuple(f.shape[:2]) for f in frames_u8] if isinstance(frames_u8, (list, tuple)) else tuple(frames_u8.shape[1:3])
+        self.put_frame_info(plan, scale, shapes)
         self.run_plan(plan)
         out = self.fetch_poses(plan)
         if out is None:
             self._range_event_raise_or_prepare('predict_poses_on_frames', getattr(plan, 'audit_flagged', None))        # (the preprocessed frames are still in the plan)
-            out = self._twin.predict_poses_on_batch([plan.images, plan.P_inv, plan.planes], scale, tuple(frames_u8.shape[1:3]))
+            out = self._twin.predict_poses_on_batch([plan.images, plan.P_inv, plan.planes], scale, shapes, heights=self._heights_of(plan))
         return out, scale
 
     def _range_event_raise_or_prepare(self, what, flagged=None):

@@ -93,6 +93,9 @@ class ShardedModel(object):
     def predict_on_batch(self, inputs):
         import torch.distributed as dist
         images, P_inv, planes = inputs
+        if isinstance(images, (list, tuple)):
+            raise ValueError('ShardedModel takes images of one shape as an array: a ragged list (images of one height class) runs through '
+                             'the model\'s own predict_on_batch')
         world = dist.get_world_size(self.group) if dist.is_initialized() else 1
         rank = dist.get_rank(self.group) if dist.is_initialized() else 0
         B = images.shape[0]

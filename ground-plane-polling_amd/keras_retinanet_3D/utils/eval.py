@@ -24,6 +24,7 @@ from __future__ import print_function
 import numpy as np
 
 from .anchors import compute_overlap
+from .image import class_of_resized
 
 
 def _compute_ap(recall, precision):
@@ -60,7 +61,9 @@ def _get_detections(generator, model, score_threshold=0.05, max_detections=300, 
     def flush(batch):
         if not batch:
             return
-        inputs = [np.stack([b[1] for b in batch]), np.stack([b[3] for b in batch]),
+        # (images of one shape: an array, as ever; of one height class and different heights: a list, which a model with a ragged form takes)
+        images = [b[1] for b in batch]
+        inputs = [np.stack(images) if len(set(im.shape for im in images)) == 1 else images, np.stack([b[3] for b in batch]),
                   np.tile(np.asarray(generator.plane_params)[None], (len(batch), 1, 1))]
         outputs = [np.asarray(o) for o in model.predict_on_batch(inputs)[:8]]
         for k, (i, _, scale, _) in enumerate(batch):
@@ -71,13 +74,20 @@ def _get_detections(generator, model, score_threshold=0.05, max_detections=300, 
                     all_detections[i][4 * label + orientation] = rows[pick, :-2]
             print('{}/{}'.format(i + 1, generator.size()), end='\r')
 
+    # a batch is cut short where the next image cannot join its call: at a change of shape, or -- a model with a ragged form
+    # (RetinaNet3D.supports_ragged) -- only at a change of height class (utils/image.class_of_resized)
+    ragged_ok = getattr(model, 'supports_ragged', False)
+
+    def same_call(a, b):
+        return a == b or (ragged_ok and class_of_resized(a[0], a[1]) == class_of_resized(b[0], b[1]))
+
     batch = []
     for i in range(generator.size()):
         image = generator.preprocess_image(generator.load_image(i).copy())
         image, scale = generator.resize_image(image)
         P = np.dot(np.diag([scale, scale, 1.0]), generator.load_calibration(i))
         item = (i, image, scale, np.linalg.pinv(P))
-        if batch and (len(batch) >= max(batch_size, 1) or batch[0][1].shape != image.shape):
+        if batch and (len(batch) >= max(batch_size, 1) or not same_call(batch[0][1].shape, image.shape)):
             flush(batch)
             batch = []
         batch.append(item)

@@ -70,3 +70,60 @@ def resize_image(img, min_side=800, max_side=1333):
     """ (resized image, scale), utils/image.py:174-200 """
     scale = compute_resize_scale(img.shape, min_side, max_side)
     return resize_bilinear(img, scale), scale
+
+
+# ---------------------------------------------------------------------------------------------------- height classes (ragged batches)
+# Images whose resized width is the same and whose resized heights give the same pool1 map run as ONE batch (DESIGN.md 4.13): a height
+# class is (Hp, W) = (rows of the pool1 map, resized width); the resized heights 4 Hp - 3 .. 4 Hp belong to it.
+
+def resized_shape(image_shape, min_side=800, max_side=1333):
+    """ (resized height, resized width, scale) of a raw image, as resize_image produces them """
+    scale = compute_resize_scale(image_shape, min_side, max_side)
+    return int(np.rint(image_shape[0] * scale)), int(np.rint(image_shape[1] * scale)), scale
+
+
+def class_of_resized(height, width):
+    """ the height class (Hp, W) of a network input of height x width: Hp = rows of pool1 behind conv1 (7x7 / 2, pad 3) and pool1 (3x3 / 2, 'same') """
+    conv_rows = (int(height) - 1) // 2 + 1
+    return (conv_rows + 1) // 2, int(width)
+
+
+def class_height_range(Hp):
+    """ (lowest, highest) network-input height of a class; the highest is the row count of the class's canvas """
+    return 4 * int(Hp) - 3, 4 * int(Hp)
+
+
+def height_class(image_shape, min_side=800, max_side=1333):
+    """ the height class (Hp, W) of a raw image of image_shape = (rows, cols[, 3]) after resize_image(min_side, max_side) """
+    H, W, _ = resized_shape(image_shape, min_side, max_side)
+    return class_of_resized(H, W)
+
+
+def split_by_height_class(image_shapes, min_side=800, max_side=1333):
+    """ [(class, [indices into image_shapes])] in the order in which the classes first appear; indices ascending inside a class """
+    groups = {}
+    for i, shape in enumerate(image_shapes):
+        groups.setdefault(height_class(shape, min_side, max_side), []).append(i)
+    return list(groups.items())
+
+
+def ragged_taps(image_shapes, min_side=800, max_side=1333):
+    """ the per-image tap tables of gpp_preprocess_u8_bgr_ragged for raw images of ONE height class:
+    (cls, heights int32 [B], scales [B], (y0, y1 int32 [B][4 Hp], wy float32 [B][4 Hp], x0, x1 int32 [B][W], wx float32 [B][W])).
+    Row b of a table = _axis_taps of image b alone; entries of rows >= heights[b] are zero (never read). """
+    classes = split_by_height_class(image_shapes, min_side, max_side)
+    if len(classes) != 1:
+        raise ValueError('the images span {} height classes ({}): a ragged batch holds one class'.format(
+            len(classes), ' and '.join(str(c) for c, _ in classes)))
+    (Hp, W), _ = classes[0]
+    B, rows = len(image_shapes), 4 * Hp
+    y0, y1, x0, x1 = (np.zeros((B, n), np.int32) for n in (rows, rows, W, W))
+    wy, wx = np.zeros((B, rows), np.float32), np.zeros((B, W), np.float32)
+    heights, scales = np.zeros((B,), np.int32), []
+    for b, shape in enumerate(image_shapes):
+        H, _, scale = resized_shape(shape, min_side, max_side)
+        heights[b] = H
+        scales.append(scale)
+        y0[b, :H], y1[b, :H], wy[b, :H] = _axis_taps(H, shape[0], scale)
+        x0[b], x1[b], wx[b] = _axis_taps(W, shape[1], scale)
+    return (Hp, W), heights, scales, (y0, y1, wy, x0, x1, wx)

@@ -118,6 +118,9 @@ class FramePipeline(object):
 
         def start_upload(k, item):
             frames, P_inv, planes = item
+            if isinstance(frames, (list, tuple)):
+                raise ValueError('FramePipeline takes frames of one shape as an array: a ragged list (frames of one height class) runs '
+                                 'through the model\'s own predict_on_frames')
             if self.slots is None:
                 self._make_slots(np.asarray(frames), np.asarray(P_inv), np.asarray(planes))
                 for s in self.slots:

@@ -358,6 +358,29 @@ int gpp_stem_conv7x7_bn_relu_x3_rc(const float* in, const void* packed_weight_x3
  * gpp_maxpool3x3s2_same(GPP_F32), and the range events of the conv map are counted as there (same count). */
 int gpp_stem_pool_fused_x3(const float* in, const void* packed_weight_x3, const float* bias, float* out,
                            int B, int H, int W, uint64_t* range_counter, void* stream);
+/* Ragged batches: the forms of the six functions above for a batch whose images share a HEIGHT CLASS (Hp, W) -- the same pool1 map of Hp rows --
+ * and differ in their own height H_b in [4 Hp - 3, 4 Hp].  `in` is a canvas (B, H, W, 3) with H = 4 Hp rows: image b occupies rows [0, H_b) of slot b,
+ * and rows >= H_b are never read as data (they count as the zero padding below the image, whatever they hold).  heights = int32 [B] in DEVICE
+ * memory, H_b per image: data, not a launch argument, so one plan and one captured graph serve every mix of heights.  Ho_b = (H_b - 1)/2 + 1 and
+ * the pool's pad_top follow from H_b per image.  The unfused conv map is (B, 2 Hp, Wo, 64): image b's rows [0, Ho_b) are written, the rest is not
+ * touched; gpp_maxpool3x3s2_same_ragged reads such a map (H = 2 Hp its rows; heights = the IMAGE heights, as for the stem) and writes (B, Hp, Wp, C).
+ * For every image the result is bit-identical to the uniform function on that image alone (same taps, same accumulation order), and the x3 range
+ * counter counts only conv values that exist (y < Ho_b).
+ * Checked on the host before any launch: null pointers, sizes, alignment (heights: 4 bytes), and H == 4 Hp (the pool: H == 2 Hp), else
+ * GPP_ERR_BAD_ARG / GPP_ERR_ALIGN.  The table itself cannot be read by the host: the caller checks 4 Hp - 3 <= H_b <= 4 Hp before upload (the
+ * Python layer does), and the kernels clamp H_b into [1, H], so a bad table gives a wrong picture and never an access outside the canvas. */
+int gpp_stem_conv7x7_bn_relu_ragged(const float* in, const float* weight, const float* bias, void* out, int dtype,
+                                    int B, int H, int W, int Hp, const int32_t* heights, void* stream);
+int gpp_stem_conv7x7_bn_relu_mfma_ragged(const float* in, const void* packed_weight_f16, const float* bias, void* out,
+                                         int dtype, int B, int H, int W, int Hp, const int32_t* heights, void* stream);
+int gpp_stem_conv7x7_bn_relu_x3_rc_ragged(const float* in, const void* packed_weight_x3, const float* bias, float* out,
+                                          int B, int H, int W, int Hp, const int32_t* heights, uint64_t* range_counter, void* stream);
+int gpp_maxpool3x3s2_same_ragged(const void* in, void* out, int dtype, int B, int H, int W, int C, int Hp,
+                                 const int32_t* heights, void* stream);
+int gpp_stem_pool_fused_mfma_ragged(const float* in, const void* packed_weight_f16, const float* bias, void* out,
+                                    int dtype, int B, int H, int W, int Hp, const int32_t* heights, void* stream);
+int gpp_stem_pool_fused_x3_ragged(const float* in, const void* packed_weight_x3, const float* bias, float* out,
+                                  int B, int H, int W, int Hp, const int32_t* heights, uint64_t* range_counter, void* stream);
 /* dtype GPP_BF16X3 = a pre-split map (gpp_conv_desc.x3_split): ReLU on the [hi | lo] pairs (count in float32-sized elements, a
    multiple of 32) */
 int gpp_relu(const void* in, void* out, int dtype, int64_t count, void* stream);
@@ -376,6 +399,15 @@ int gpp_relu_strided(const void* in, int64_t in_bstride, void* out, int64_t out_
 int gpp_preprocess_u8_bgr(const uint8_t* frames, float* out, const int32_t* y0, const int32_t* y1, const float* wy,
                           const int32_t* x0, const int32_t* x1, const float* wx, int B, int H, int W, int Ho, int Wo,
                           float mean_b, float mean_g, float mean_r, void* stream);
+/* The ragged form (see the ragged stem above): frames of different raw sizes that resize into one height class.  frames = a uint8 canvas of
+ * B slots of H x W x 3 bytes (H, W = the largest raw height and width); frame b is stored DENSELY, h_b x w_b x 3 bytes from the start of its
+ * slot; raw_hw = int32 [B][2] = (h_b, w_b); heights = int32 [B] = the resized heights H_b; y0/y1/wy are [B][Ho] and x0/x1/wx [B][Wo], image b's
+ * row being the taps of that image alone (entries of rows >= H_b are not read).  out = the float32 canvas (B, Ho, Wo, 3) with Ho = 4 Hp: rows
+ * [0, H_b) of image b are bit-identical to gpp_preprocess_u8_bgr on that frame alone, rows >= H_b are written as zero.  All tables are device
+ * arrays; sizes and taps are clamped into the slot.  Null pointer, bad size, Ho != 4 Hp: GPP_ERR_BAD_ARG; a table not 4-byte aligned: GPP_ERR_ALIGN. */
+int gpp_preprocess_u8_bgr_ragged(const uint8_t* frames, float* out, const int32_t* raw_hw, const int32_t* heights,
+                                 const int32_t* y0, const int32_t* y1, const float* wy, const int32_t* x0, const int32_t* x1, const float* wx,
+                                 int B, int H, int W, int Hp, int Ho, int Wo, float mean_b, float mean_g, float mean_r, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Detection decode: sigmoid, orientation fold, score threshold, NMS, top-k, box / dimension
@@ -535,6 +567,9 @@ int gpp_absmax_clear(uint32_t* table, int64_t n, void* stream);
 #define GPP_OP_MOBILENET_BLOCK 34        /* gpp_mobilenet_block_desc -> gpp_mobilenet_block */
 #define GPP_OP_ABSMAX 35                 /* gpp_absmax_desc -> gpp_channel_absmax (opt-in: RetinaNet3D(range_audit=True)) */
 #define GPP_OP_ABSMAX_CLEAR 36           /* gpp_absmax_clear_desc -> gpp_absmax_clear: the first op of an audit plan */
+#define GPP_OP_STEM_RAGGED 37             /* gpp_ragged_stem_desc -> gpp_stem_conv7x7_bn_relu_ragged / _mfma_ragged / _x3_rc_ragged (by dtype, as GPP_OP_STEM) */
+#define GPP_OP_STEM_POOL_RAGGED 38        /* gpp_ragged_stem_desc with out = the pooled map -> gpp_stem_pool_fused_mfma_ragged / gpp_stem_pool_fused_x3_ragged */
+#define GPP_OP_MAXPOOL_RAGGED 39          /* gpp_ragged_pool_desc -> gpp_maxpool3x3s2_same_ragged */
 /* (14, 15: the Winograd F(2, 3) form of the tower layers of round 5 -- built, measured at -2 % of the step, shelved in round 6:
    tools/experiments/winograd/) */
 /* Optional concurrency inside a plan: `kind | GPP_OP_LANE(l)` (l = 1, 2) enqueues the op on a library-owned side stream
@@ -567,6 +602,9 @@ typedef struct gpp_stem_desc { const float* in; const void* weight; const float*
                                int32_t dtype, B, H, W; uint64_t* range_counter; /* GPP_F16X3: see gpp_stem_conv7x7_bn_relu_x3_rc; NULL otherwise */
                              } gpp_stem_desc;   /* weight: packed f16 image (MFMA stem); GPP_F32: float32 [147][64]; GPP_F16X3: gpp_stem_pack_weights_f16x3 */
 typedef struct gpp_pool_desc { const void* in; void* out; int32_t dtype, B, H, W, C, reserved; } gpp_pool_desc;
+/* a batch of one height class: stem.H = 4 Hp canvas rows (pool.H = 2 Hp map rows); heights = int32 [B] in device memory, the IMAGE heights */
+typedef struct gpp_ragged_stem_desc { gpp_stem_desc stem; const int32_t* heights; int32_t Hp, reserved; } gpp_ragged_stem_desc;
+typedef struct gpp_ragged_pool_desc { gpp_pool_desc pool; const int32_t* heights; int32_t Hp, reserved; } gpp_ragged_pool_desc;
 typedef struct gpp_relu_desc { const void* in; void* out; int64_t in_bstride, out_bstride, count;
                                int32_t dtype, B; } gpp_relu_desc;
 typedef struct gpp_detect_desc {
