@@ -2,7 +2,7 @@
 //
 // Every C-ABI entry point validates its descriptors on the host before anything reaches the device; the device-free ones -- gpp_conv2d_flops,
 // gpp_conv2d_split_rule, gpp_conv2d_workspace_bytes, gpp_conv2d_tile_candidates, gpp_stem_pack_weights_f16 / _f16x3 -- and the argument checks of
-// the launching ones (gpp_conv2d_igemm, gpp_bottleneck_tail, gpp_bottleneck_block, gpp_plan_run, gpp_poll_f32, ...: without a device they end
+// the launching ones (gpp_conv2d_igemm, gpp_bottleneck_tail, gpp_bottleneck_block, gpp_plan_run, gpp_poll_f32, gpp_draw_build, gpp_draw_raster, ...: without a device they end
 // in an error code before any launch) are run here over a file of descriptors the test generated, in a build of the library's host code
 // with -fsanitize=address,undefined.  A bad descriptor must come back as GPP_ERR_* (or a hipError_t from the absent device); nothing may
 // trip a sanitizer.  Device pointers inside the descriptors are never dereferenced by host code: they are fuzzed like every other field.
@@ -104,6 +104,17 @@ int main(int argc, char** argv)
             note(gpp_detect_workspace_bytes((int)r.a, (int64_t)(((uint64_t)r.b * (uint64_t)r.c) >> ((r.a >> 8) & 31)), &wb));
             note(gpp_detect_osf_workspace_bytes((int)r.a, (int64_t)(((uint64_t)r.b * (uint64_t)r.c) >> ((r.a >> 8) & 31)), &wb));
             note(gpp_poll_f32(nullptr, nullptr, nullptr, nullptr, nullptr, (int)r.a, (int)r.b, (int)r.c, 0, 0.7f, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr));
+            // the composite's host halves: sizes, then argument checks that end before any launch (fuzzed, misaligned and null pointers)
+            size_t pb = 0;
+            note(gpp_draw_workspace_bytes((int)r.a, (int)r.b, &pb, &wb));
+            note(gpp_draw_workspace_bytes((int)(r.a % 64), (int)(r.b % 2000), &pb, nullptr));
+            note(gpp_draw_build(nullptr, nullptr, (int)r.a, (int)r.b, 0.4f, nullptr, nullptr, nullptr));
+            note(gpp_draw_build((const float*)r.d[0].in, (const double*)((uintptr_t)r.d[0].weight | 4), (int)(r.a % 64) + 1, (int)(r.b % 200) + 1, 0.4f,
+                                r.d[0].out, (int32_t*)(uintptr_t)r.d[0].bias, nullptr));
+            note(gpp_draw_raster(nullptr, nullptr, (int)r.a, (int)r.b, nullptr, nullptr, (int)r.c, nullptr, nullptr, nullptr));
+            note(gpp_draw_raster((const uint8_t*)r.d[0].in, (const int32_t*)(uintptr_t)r.d[0].bias, (int)(r.a % 3000) + 1, (int)(r.b % 3000) + 1,
+                                 (const void*)((uintptr_t)r.d[0].weight | 8), (const int32_t*)(uintptr_t)r.d[0].bias, (int)(r.c % 64) + 1, (uint8_t*)r.d[0].out,
+                                 r.d[0].out, nullptr));
             break;
         }
         }

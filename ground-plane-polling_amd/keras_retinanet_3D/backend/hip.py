@@ -39,6 +39,9 @@ GPP_F32 = 3
 GPP_BF16X3 = 4
 GPP_F16X3 = 5
 GPP_MAX_GROUPS = 5
+GPP_DRAW_PRIM_WORDS = 16   # int32 words per primitive record of gpp_draw_build (include/gpp.h)
+GPP_DRAW_PRIMS_PER_DET = 26
+GPP_DRAW_COUNT_WORDS = 4
 GPP_POSE_COLS = 36         # float32 values per row of gpp_pose_f32 (include/gpp.h)
 GPP_ABSMAX_F32, GPP_ABSMAX_SPLIT_F16, GPP_ABSMAX_SPLIT_BF16 = 1, 2, 3      # gpp_absmax_desc.layout (include/gpp.h)
 
@@ -108,6 +111,14 @@ def _declare(lib):
         [c_void_p, c_size_t, c_void_p]
     lib.gpp_pose_f32.restype = c_int
     lib.gpp_pose_f32.argtypes = [c_void_p] * 8 + [c_int, c_int, c_float] + [c_void_p] * 3
+    # the --save-images composite (include/gpp.h, csrc/draw.hip; absent from an older build named by GPP_LIB: it runs everything but the pictures)
+    if hasattr(lib, 'gpp_draw_build'):
+        lib.gpp_draw_workspace_bytes.restype = c_int
+        lib.gpp_draw_workspace_bytes.argtypes = [c_int, c_int, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]
+        lib.gpp_draw_build.restype = c_int
+        lib.gpp_draw_build.argtypes = [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]
+        lib.gpp_draw_raster.restype = c_int
+        lib.gpp_draw_raster.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
     lib.gpp_conv2d_igemm.restype = c_int
     lib.gpp_conv2d_igemm.argtypes = [ctypes.POINTER(ConvDesc), c_void_p]
     lib.gpp_stem_conv7x7_bn_relu.restype = c_int
@@ -271,6 +282,38 @@ def ptr(t):
         return None
     assert t.is_contiguous(), 'gpp kernels need dense tensors'
     return ctypes.c_void_p(t.data_ptr())
+
+
+def draw_workspace_bytes(B, D):
+    """ (bytes of the primitive table, bytes of the raster's workspace) for B images of D rows each """
+    prims, work = c_size_t(0), c_size_t(0)
+    check(lib().gpp_draw_workspace_bytes(int(B), int(D), ctypes.byref(prims), ctypes.byref(work)), 'gpp_draw_workspace_bytes')
+    return prims.value, work.value
+
+
+def draw_build(rows, P, score_threshold):
+    """ gpp_draw_build: rows (B, D, 36) float32 and P (B, 3, 4) float64 on the device -> (prims (B, 26 D, 16) int32, counts (B, 4) int32) """
+    import torch
+    B, D = int(rows.shape[0]), int(rows.shape[1])
+    if rows.dtype != torch.float32 or rows.dim() != 3 or rows.shape[2] != GPP_POSE_COLS or P.dtype != torch.float64 or tuple(P.shape) != (B, 3, 4):
+        raise ValueError('rows must be (B, D, {}) float32 and P (B, 3, 4) float64, got {} {} and {} {}'.format(
+            GPP_POSE_COLS, tuple(rows.shape), rows.dtype, tuple(P.shape), P.dtype))
+    prims_bytes, _ = draw_workspace_bytes(B, D)
+    prims = torch.empty((B, GPP_DRAW_PRIMS_PER_DET * D, GPP_DRAW_PRIM_WORDS), dtype=torch.int32, device=rows.device)
+    assert prims.numel() * 4 == prims_bytes
+    counts = torch.zeros((B, GPP_DRAW_COUNT_WORDS), dtype=torch.int32, device=rows.device)
+    check(lib().gpp_draw_build(ptr(rows), ptr(P), B, D, float(score_threshold), ptr(prims), ptr(counts), stream_ptr()), 'gpp_draw_build')
+    return prims, counts
+
+
+def draw_raster(frames_u8, raw_hw, Hr, Wr, prims, counts, out_u8, status):
+    """ gpp_draw_raster: frames_u8 B slots of Hr Wr 3 bytes, raw_hw (B, 2) int32 -> out_u8 B slots of 2 Hr Wr 3 bytes (only each image's own
+    2 h x w x 3 bytes are written), status (B, 4) int32 = the raster's workspace """
+    B = int(raw_hw.shape[0])
+    if frames_u8.numel() < B * Hr * Wr * 3 or out_u8.numel() < 2 * B * Hr * Wr * 3 or status.numel() < 4 * B or counts.numel() < GPP_DRAW_COUNT_WORDS * B:
+        raise ValueError('gpp_draw_raster: a buffer is smaller than B = {} slots of Hr = {}, Wr = {}'.format(B, Hr, Wr))
+    check(lib().gpp_draw_raster(ptr(frames_u8), ptr(raw_hw), int(Hr), int(Wr), ptr(prims), ptr(counts), B, ptr(out_u8), ptr(status),
+                                stream_ptr()), 'gpp_draw_raster')
 
 
 def channel_absmax(buf, M, C, pitch, c_off, layout, out, stream=None):

@@ -10,13 +10,16 @@ tree and file formats):
     <output_dir>/<model name>/outputs/full/<image>.mat     boxes keypoints labels scores locations
                                                            angles dimensions residuals  (:291-292)
     <output_dir>/<model name>/outputs/kitti/<image>.txt    KITTI result lines           (:295-330)
-    <output_dir>/<model name>/images/composite/<image>.png only with --save-images and cv2 present
+    <output_dir>/<model name>/images/composite/<image>.png only with --save-images: the 2-D picture over the 3-D picture
+                                                           (utils/visualization.py; with --device-pose rendered on the GPU, csrc/draw.hip)
 
 Differences, all on the host side: images are processed in batches (--batch-size, default 1 =
 the reference's behaviour), the per-detection Python loop of :137-287 is vectorised
 (utils.gpp_utils.recover_pose), and `model_path` may be 'synthetic:<seed>' because no trained
 weights ship with the reference.  With --device-pose the selection, the pose recovery and the KITTI fields are computed
-on the GPU as the last stage of the plan (csrc/pose.hip) and the files are written from its rows.
+on the GPU as the last stage of the plan (csrc/pose.hip) and the files are written from its rows.  The pictures of --save-images follow
+this package's own integer drawing rules, not cv2's pixels; --image-score-threshold (default 0.4, the
+reference's constant) selects what is drawn.
 """
 
 import argparse
@@ -35,7 +38,7 @@ import numpy as np
 import scipy.io
 
 from .. import models
-from ..utils import gpp_utils
+from ..utils import gpp_utils, visualization
 from ..utils.image import compute_resize_scale, preprocess_image, read_image_bgr, resize_image
 
 
@@ -58,7 +61,10 @@ def parse_args(args):
                              'bf16x3 / f16 / bf16 are faster and leave that tolerance.')
     parser.add_argument('--device-pose', action='store_true',
                         help='Pose recovery and KITTI fields on the GPU (not in the reference CLI): the model is loaded with pose=True and '
-                             'the .mat and KITTI files are written from the rows of its pose stage; --save-images is unaffected.')
+                             'the .mat and KITTI files are written from the rows of its pose stage, and the pictures of --save-images are rendered '
+                             'on the GPU from those rows and the raw frames.')
+    parser.add_argument('--image-score-threshold', type=float, default=0.4,
+                        help='Detections with a score above it are drawn by --save-images (not in the reference CLI, which fixes 0.4).')
     parser.add_argument('--range-audit', action='store_true',
                         help='Audit the lower range of --dtype f16x3 (not in the reference CLI): the model is loaded with range_audit=True, a '
                              'call whose run left a whole conv-operand map below 2^-9 is answered by the float32 twin, and at the end the five '
@@ -104,14 +110,23 @@ def write_results(args, output_dir, item, det):
         with open(os.path.join(output_dir, 'outputs', 'kitti', stem + 'txt'), 'w') as f:
             f.writelines(gpp_utils.kitti_lines(det, item['raw_image'].shape))
     if args.save_images:
-        try:
-            import cv2  # noqa: F401
-        except ImportError:
-            print('--save-images needs OpenCV (cv2), which is not installed: skipping the composite image')
+        save_composite(output_dir, item, visualization.composite(item['raw_image'], det, raw_calibration(item), args.image_score_threshold))
 
 
-def write_results_from_rows(args, output_dir, item, rows_b, count):
-    """ write_results for one image's rows of the device pose stage (model.predict_poses_on_batch) """
+def raw_calibration(item):
+    """ the calibration in raw-image pixels (reference run_network.py:115): item['P'] carries the image scale """
+    s = 1.0 / item['scale']
+    return np.dot(np.array([[s, 0.0, 0.0], [0.0, s, 0.0], [0.0, 0.0, 1.0]]), item['P'])
+
+
+def save_composite(output_dir, item, picture):
+    """ images/composite/<image>.png: the 2-D picture over the 3-D picture (reference :334-338) """
+    visualization.write_png(os.path.join(output_dir, 'images', 'composite', os.path.basename(item['image_fp'])), picture)
+
+
+def write_results_from_rows(args, output_dir, item, rows_b, count, picture=None):
+    """ write_results for one image's rows of the device pose stage (model.predict_poses_on_batch); picture: its composite, rendered on the
+    device (model.predict_composites_on_frames) """
     stem = os.path.basename(item['image_fp'])[:-3]
     det = gpp_utils.detections_from_rows(rows_b, count)
     outputs = {'boxes': det['boxes'][:, :4], 'keypoints': det['boxes'][:, 4:], 'labels': det['labels'], 'scores': det['scores'],
@@ -121,10 +136,9 @@ def write_results_from_rows(args, output_dir, item, rows_b, count):
         with open(os.path.join(output_dir, 'outputs', 'kitti', stem + 'txt'), 'w') as f:
             f.write(gpp_utils.kitti_lines_from_rows(rows_b, count))
     if args.save_images:
-        try:
-            import cv2  # noqa: F401
-        except ImportError:
-            print('--save-images needs OpenCV (cv2), which is not installed: skipping the composite image')
+        if picture is None:
+            picture = visualization.composite_from_rows(item['raw_image'], rows_b, count, raw_calibration(item), args.image_score_threshold)
+        save_composite(output_dir, item, picture)
 
 
 def group_items(model, items):
@@ -164,13 +178,18 @@ def main(args=None):
             t0 = time.time()
             if args.device_pose:
                 frames = stack([it['raw_image'] for it in group])
-                (rows, counts), _ = model.predict_poses_on_frames(frames, P_inv, planes)
+                pictures = [None] * len(group)
+                if args.save_images:
+                    P_raw = np.stack([raw_calibration(it) for it in group])
+                    (rows, counts), _, pictures = model.predict_composites_on_frames(frames, P_inv, planes, P_raw, args.image_score_threshold)
+                else:
+                    (rows, counts), _ = model.predict_poses_on_frames(frames, P_inv, planes)
                 dt = time.time() - t0
                 keep_smallest(audit, model)
                 for k, it in enumerate(group):
                     print("Image {}: frame rate: {:.2f}".format(j, len(group) / dt))
                     j += 1
-                    write_results_from_rows(args, output_dir, it, rows[k], counts[k])
+                    write_results_from_rows(args, output_dir, it, rows[k], counts[k], pictures[k])
                 continue
             if on_device:
                 outputs = model.predict_on_frames(stack([it['raw_image'] for it in group]), P_inv, planes)[0][:8]

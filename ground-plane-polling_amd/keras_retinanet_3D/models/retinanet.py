@@ -1703,6 +1703,50 @@ class RetinaNet3D(object):
             out = self._twin.predict_poses_on_batch([plan.images, plan.P_inv, plan.planes], scale, shapes, heights=self._heights_of(plan))
         return out, scale
 
+    def predict_composites_on_frames(self, frames_u8, P_inv, planes, P_raw, score_threshold=0.4):
+        """ predict_poses_on_frames + the pictures of bin/run_network.py --save-images, rendered on the device (csrc/draw.hip, DESIGN.md
+        section 4.14): frames_u8 a (B, H, W, 3) uint8 array or a list of frames of one height class; P_raw (B, 3, 4) (or one (3, 4) for
+        all): the calibration in raw-image pixels (reference run_network.py:115); detections with a score above score_threshold are drawn.
+        Returns ((rows, counts), scale, [composite_b (2 h_b, w_b, 3) uint8]): the 2-D picture over the 3-D picture of every image, equal
+        byte for byte to utils.visualization.composite_from_rows(frame_b, rows[b], counts[b], P_raw[b], score_threshold).
+        The two draw launches follow the plan on its stream and are not plan ops; one more device -> host copy brings the pictures.  When
+        the float32 twin answers the call (a range event), the rows and the pictures are the twin's, drawn over this call's frames. """
+        self._require_pose()
+        torch = self.torch
+        ragged = isinstance(frames_u8, (list, tuple))
+        plan, scale = self.stage_frames(frames_u8, P_inv, planes)
+        shapes = [tuple(int(v) for v in f.shape[:2]) for f in frames_u8] if ragged else [tuple(int(v) for v in frames_u8.shape[1:3])] * plan.shape[0]
+        B = len(shapes)
+        P_raw = np.array(np.broadcast_to(np.asarray(P_raw, dtype=np.float64), (B, 3, 4)))          # (a writable copy)
+        self.put_frame_info(plan, scale, shapes if ragged else shapes[0])
+        self.run_plan(plan)
+        frames_d = plan.keep_frames                      # the raw bytes: image b densely at the start of slot b
+        Hr, Wr = max(s[0] for s in shapes), max(s[1] for s in shapes)
+        raw_hw = torch.as_tensor(np.asarray(shapes, dtype=np.int32)).to(self.device, non_blocking=True)
+        P_d = torch.as_tensor(P_raw).to(self.device, non_blocking=True)
+        slot = 2 * Hr * Wr * 3
+        status_at = (B * slot + 15) // 16 * 16
+        picture = torch.empty((status_at + 16 * B,), dtype=torch.uint8, device=self.device)
+        status = picture[status_at:].view(torch.int32)
+
+        def draw(rows_d):
+            prims, prim_counts = hip.draw_build(rows_d, P_d, score_threshold)
+            hip.draw_raster(frames_d, raw_hw, Hr, Wr, prims, prim_counts, picture, status)
+
+        draw(plan.pose_rows)
+        out = self.fetch_poses(plan)
+        if out is None:
+            self._range_event_raise_or_prepare('predict_composites_on_frames', getattr(plan, 'audit_flagged', None))
+            out = self._twin.predict_poses_on_batch([plan.images, plan.P_inv, plan.planes], scale, shapes if ragged else shapes[0],
+                                                    heights=self._heights_of(plan))
+            draw(torch.as_tensor(out[0]).to(self.device))
+        host = picture.cpu().numpy()
+        report = host[status_at:].view(np.int32).reshape(B, 4)
+        if (report[:, 1] != 0).any():
+            raise hip.GppError('gpp_draw_raster met {} records of an unknown kind'.format(int(report[:, 1].sum())))
+        composites = [host[b * slot:b * slot + 2 * h * w * 3].reshape(2 * h, w, 3).copy() for b, (h, w) in enumerate(shapes)]
+        return out, scale, composites
+
     def _range_event_raise_or_prepare(self, what, flagged=None):
         """ the bookkeeping of _range_event for the pose calls: count the event, raise (on_range_event='raise') or build the twin """
         self.range_fallbacks += 1

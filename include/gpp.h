@@ -509,6 +509,57 @@ int gpp_pose_f32(const float* boxes, const float* dims, const float* scores, con
                  float* rows, int32_t* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The --save-images composite on the device (csrc/draw.hip; DESIGN.md section 4.14 is the specification, utils/visualization.py its host
+ * form): per image the 2-D picture (boxes, keypoint markers, score captions) over the 3-D picture (projected cuboids, residual captions),
+ * from the rows of gpp_pose_f32 and the raw uint8 BGR frames.  Two launches on one stream: gpp_draw_build, then gpp_draw_raster.
+ *
+ * gpp_draw_build: one thread per detection, one workgroup per image, float64.
+ *   rows (B, D, GPP_POSE_COLS) float32: the rows of gpp_pose_f32 (columns 0-24 are read).
+ *   P (B, 3, 4) float64, device: per image the calibration in raw-image pixels.
+ *   score_thr: the rows with score > score_thr are drawn (a NaN score is not), in row order, numbered k = 0 .. n-1.
+ *   prims: gpp_draw_workspace_bytes' prims_bytes, 16-byte aligned.  Image b owns the records [b D 26, (b + 1) D 26) and fills the first
+ *   26 n of them, in painter's order: top picture [0, 3n) = box, circle, caption of every detection, [3n, 13n) = the ten marker lines of
+ *   every detection (3 up-triangle at m, 4 square at r, 3 down-triangle at t); bottom picture [13n, 26n) = caption and twelve edges of
+ *   every detection.  A primitive that is not drawn (a coordinate not finite or |c| >= 2^20, an orientation class outside 0..3, a
+ *   cuboid behind the camera ...) keeps its slot as GPP_DRAW_NONE.
+ *   counts (B, GPP_DRAW_COUNT_WORDS) int32: n, the number of records (26 n), the index of the image's first record, 0.
+ *
+ *   a record = GPP_DRAW_PRIM_WORDS int32 words
+ *    0        kind: GPP_DRAW_NONE / LINE / DASHED / RECT / CIRCLE / CAPTION
+ *    1        picture: 0 = top (output rows [0, h)), 1 = bottom (rows [h, 2h)); coordinates are the picture's own
+ *    2 -  5   x0 y0 x1 y1: the endpoints (LINE, DASHED); the sorted corners x0 <= x1, y0 <= y1 (RECT); the centre and 0 0 (CIRCLE);
+ *             the bottom-left corner of the first glyph, the number of characters and 0 (CAPTION).  |coordinate| < 2^20
+ *    6        colour: channel 0 | channel 1 << 8 | channel 2 << 16 (unused by a CAPTION: black under white)
+ *    7 - 10   bounding box xmin ymin xmax ymax (inclusive) of every pixel the record can paint
+ *   11 - 15   CAPTION: up to GPP_DRAW_CAPTION_MAX characters, one byte each, as indices into "0123456789.:- "
+ *
+ * gpp_draw_raster: one workgroup per 64 x 4 tile of output pixels, one pixel per thread; a later record overwrites an earlier one.
+ *   frames_u8 (B slots of Hr Wr 3 bytes), out_u8 (B slots of 2 Hr Wr 3 bytes): the slot convention of the ragged uint8 canvas -- image b
+ *   sits densely (row pitch 3 w_b) at the start of slot b; raw_hw (B, 2) int32, device: its height and width (clamped to Hr, Wr).  A
+ *   uniform batch (B, Hr, Wr, 3) is the same call.  Bytes of a slot beyond the image's own 2 h_b x w_b x 3 are not written.
+ *   prims, counts: as gpp_draw_build leaves them (or any table of valid records with bounding boxes that hold what they paint).
+ *   workspace: gpp_draw_workspace_bytes' workspace_bytes, 4-byte aligned; afterwards (B, 4) int32: the records examined, the records
+ *   of an unknown kind or picture (ignored; 0 for a table of gpp_draw_build), 2 h_b, w_b.
+ *
+ *   Null pointer, negative size, misaligned pointer: GPP_ERR_BAD_ARG, nothing launched.  B == 0 (or, for the raster, an empty frame):
+ *   GPP_OK, nothing launched.  D == 0: gpp_draw_build writes counts of 0 (rows and prims may be null) and the raster copies the frames.
+ * ---------------------------------------------------------------------------------------- */
+#define GPP_DRAW_PRIM_WORDS 16
+#define GPP_DRAW_PRIMS_PER_DET 26
+#define GPP_DRAW_COUNT_WORDS 4
+#define GPP_DRAW_CAPTION_MAX 20
+#define GPP_DRAW_NONE 0
+#define GPP_DRAW_LINE 1
+#define GPP_DRAW_DASHED 2
+#define GPP_DRAW_RECT 3
+#define GPP_DRAW_CIRCLE 4
+#define GPP_DRAW_CAPTION 5
+int gpp_draw_workspace_bytes(int B, int D, size_t* prims_bytes, size_t* workspace_bytes);
+int gpp_draw_build(const float* rows, const double* P, int B, int D, float score_thr, void* prims, int32_t* counts, void* stream);
+int gpp_draw_raster(const uint8_t* frames_u8, const int32_t* raw_hw, int Hr, int Wr, const void* prims, const int32_t* counts,
+                    int B, uint8_t* out_u8, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Range audit of dtype='f16x3' (csrc/audit.hip; opt-in: RetinaNet3D(range_audit=True)): the largest |x| of
  * every channel of one NHWC map, read in one of the three forms an x3 convolution reads its activation operand in.
  *
