@@ -43,6 +43,8 @@ GPP_DRAW_PRIM_WORDS = 16   # int32 words per primitive record of gpp_draw_build 
 GPP_DRAW_PRIMS_PER_DET = 26
 GPP_DRAW_COUNT_WORDS = 4
 GPP_POSE_COLS = 36         # float32 values per row of gpp_pose_f32 (include/gpp.h)
+GPP_EVAL_MAX_DETECTIONS, GPP_EVAL_MAX_ANNOTATIONS = 1024, 1024      # what gpp_eval_match_f32 takes per image (include/gpp.h)
+GPP_EVAL_ANN_COLS, GPP_EVAL_ERR_COLS = 17, 11
 GPP_ABSMAX_F32, GPP_ABSMAX_SPLIT_F16, GPP_ABSMAX_SPLIT_BF16 = 1, 2, 3      # gpp_absmax_desc.layout (include/gpp.h)
 
 
@@ -119,6 +121,10 @@ def _declare(lib):
         lib.gpp_draw_build.argtypes = [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]
         lib.gpp_draw_raster.restype = c_int
         lib.gpp_draw_raster.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+    # the evaluation's matching (include/gpp.h, csrc/eval.hip; absent from an older build named by GPP_LIB: it runs everything but evaluate(device=True))
+    if hasattr(lib, 'gpp_eval_match_f32'):
+        lib.gpp_eval_match_f32.restype = c_int
+        lib.gpp_eval_match_f32.argtypes = [c_void_p] * 8 + [c_int] * 4 + [c_float, c_int, ctypes.c_double] + [c_void_p] * 4
     lib.gpp_conv2d_igemm.restype = c_int
     lib.gpp_conv2d_igemm.argtypes = [ctypes.POINTER(ConvDesc), c_void_p]
     lib.gpp_stem_conv7x7_bn_relu.restype = c_int
@@ -314,6 +320,29 @@ def draw_raster(frames_u8, raw_hw, Hr, Wr, prims, counts, out_u8, status):
         raise ValueError('gpp_draw_raster: a buffer is smaller than B = {} slots of Hr = {}, Wr = {}'.format(B, Hr, Wr))
     check(lib().gpp_draw_raster(ptr(frames_u8), ptr(raw_hw), int(Hr), int(Wr), ptr(prims), ptr(counts), B, ptr(out_u8), ptr(status),
                                 stream_ptr()), 'gpp_draw_raster')
+
+
+def eval_match(boxes, dims, scores, labels, orientations, scales, annotations, ann_counts, num_classes, score_threshold, max_detections,
+               iou_threshold):
+    """ gpp_eval_match_f32 on the current stream: the decode outputs (B, D, ...) as a plan leaves them, scales (B,) float32, annotations
+    (B, A, 17) float64 and ann_counts (B,) int32, all on the device -> (table (B, D, 3) int32, errors (B, D, 11) float64, counts (B,) int32)
+    on the device; no synchronisation """
+    import torch
+    B, D = int(scores.shape[0]), int(scores.shape[1])
+    A = int(annotations.shape[1])
+    want = ((boxes, torch.float32, (B, D, 12)), (dims, torch.float32, (B, D, 3)), (scores, torch.float32, (B, D)), (labels, torch.int32, (B, D)),
+            (orientations, torch.int32, (B, D)), (scales, torch.float32, (B,)), (annotations, torch.float64, (B, A, GPP_EVAL_ANN_COLS)),
+            (ann_counts, torch.int32, (B,)))
+    for t, dtype, shape in want:
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != scores.device:
+            raise ValueError('gpp_eval_match_f32: expected {} {} on {}, got {} {} on {}'.format(shape, dtype, scores.device, tuple(t.shape), t.dtype, t.device))
+    table = torch.empty((B, D, 3), dtype=torch.int32, device=scores.device)
+    errors = torch.empty((B, D, GPP_EVAL_ERR_COLS), dtype=torch.float64, device=scores.device)
+    counts = torch.empty((B,), dtype=torch.int32, device=scores.device)
+    check(lib().gpp_eval_match_f32(ptr(boxes), ptr(dims), ptr(scores), ptr(labels), ptr(orientations), ptr(scales), ptr(annotations), ptr(ann_counts),
+                                   B, D, A, int(num_classes), float(score_threshold), int(max_detections), float(iou_threshold),
+                                   ptr(table), ptr(errors), ptr(counts), stream_ptr()), 'gpp_eval_match_f32')
+    return table, errors, counts
 
 
 def channel_absmax(buf, M, C, pitch, c_off, layout, out, stream=None):

@@ -4,7 +4,7 @@ Evaluate a model on a KITTI-style directory: mAP over the (class, orientation) b
 L1 errors of keypoints / height / width / length.
 
     evaluate.py model_path kitti_dir [--subset val] [--backbone resnet50] [--batch-size N]
-                [--iou-threshold 0.5] [--score-threshold 0.05] [--max-detections 100]
+                [--iou-threshold 0.5] [--score-threshold 0.05] [--max-detections 100] [--device-eval]
 
 The reference has no evaluation script: it evaluates only from the training callback
 (callbacks/eval.py:50-114 -> utils/eval.py:168-262, created in bin/train.py).  This CLI runs the
@@ -41,6 +41,9 @@ def parse_args(args):
     parser.add_argument('--iou-threshold', type=float, default=0.5)
     parser.add_argument('--score-threshold', type=float, default=0.05)
     parser.add_argument('--max-detections', type=int, default=100)
+    parser.add_argument('--device-eval', action='store_true',
+                        help='Preprocess, resize and match detections to labels on the device (evaluate(device=True), DESIGN.md section 4.15): '
+                             'the same numbers; images go in as raw uint8 frames, --batch-size of them per call (the four KITTI sizes share a call).')
     parser.add_argument('--plane-params-path', help='Plane database (.mat); default <kitti_dir>/road_planes_database.mat.', default=None)
     return parser.parse_args(args)
 
@@ -50,7 +53,7 @@ def main(args=None):
     model = models.load_model(args.model_path, backbone_name=args.backbone, dtype=args.dtype)
     generator = KittiGenerator(args.kitti_dir, subset=args.subset, plane_params_path=args.plane_params_path)
     results = evaluate(generator, model, iou_threshold=args.iou_threshold, score_threshold=args.score_threshold,
-                       max_detections=args.max_detections, batch_size=args.batch_size)
+                       max_detections=args.max_detections, batch_size=args.batch_size, device=args.device_eval)
     return summarize(results, generator)
 
 

@@ -1645,6 +1645,56 @@ class RetinaNet3D(object):
         self.run_plan(plan)
         return self.fetch(plan), scale
 
+    # ------------------------------------------------------------------ evaluation: detections matched to labels on the device
+    def match_outputs(self, outputs, scales, annotations, iou_threshold=0.5, score_threshold=0.05, max_detections=100, num_classes=1):
+        """ The matching of utils.eval.evaluate for one batch, on the device (csrc/eval.hip; one launch on the
+        current stream).  outputs: the decode outputs on the device (boxes, dimensions, scores, labels, orientations[, ...]: the first five
+        of `outputs(plan)`, or tensors made from stored results); scales: one per image (or one for all); annotations: per image the
+        (n, 17) rows of KittiGenerator.load_annotations.  Returns four NumPy arrays (synchronises): table (B, D, 3) int32 -- bin, hit,
+        annotation row of every detection, -1 where it is not selected --, scores (B, D) float32, errors (B, D, 11) float64, counts (B,)
+        int32 (include/gpp.h, gpp_eval_match_f32); utils.eval.assemble_matches turns them into evaluate's result. """
+        torch = self.torch
+        boxes, dims, scores, labels, orientations = outputs[:5]
+        B = int(scores.shape[0])
+        if len(annotations) != B:
+            raise ValueError('match_outputs: {} annotation arrays for {} images'.format(len(annotations), B))
+        rows = [np.asarray(a, dtype=np.float64).reshape(-1, hip.GPP_EVAL_ANN_COLS) for a in annotations]
+        padded = np.zeros((B, max(r.shape[0] for r in rows), hip.GPP_EVAL_ANN_COLS), np.float64)
+        for b, r in enumerate(rows):
+            padded[b, :r.shape[0]] = r
+        dev = scores.device
+        ann_d = torch.as_tensor(padded).to(dev, non_blocking=True)
+        cnt_d = torch.as_tensor(np.asarray([r.shape[0] for r in rows], dtype=np.int32)).to(dev, non_blocking=True)
+        scales_d = torch.as_tensor(np.array(np.broadcast_to(np.asarray(scales, dtype=np.float64).reshape(-1), (B,)), dtype=np.float32)).to(dev, non_blocking=True)
+        table, errors, counts = hip.eval_match(boxes, dims, scores, labels, orientations, scales_d, ann_d, cnt_d, num_classes,
+                                               score_threshold, max_detections, iou_threshold)
+        return table.cpu().numpy(), scores.cpu().numpy(), errors.cpu().numpy(), counts.cpu().numpy()
+
+    def match_on_frames(self, frames_u8, P_inv, planes, annotations, iou_threshold=0.5, score_threshold=0.05, max_detections=100, num_classes=1,
+                        min_side=800, max_side=1333):
+        """ predict_on_frames + match_outputs without the detour over the host: frames_u8 a (B, H, W, 3) uint8 BGR array or a list of
+        frames of one height class, staged as predict_on_frames stages them (stage_frames: P_inv must have been computed for the scale
+        that min_side / max_side give); the match launch follows the plan on its stream, and only
+        table, scores, errors and counts come back.  Returns ((table, scores, errors, counts), scale).  When an activation leaves the
+        half range of dtype='f16x3' the float32 twin answers the call, as it does for predict_on_frames. """
+        self._require_hip()
+        plan, scale = self.stage_frames(frames_u8, P_inv, planes, min_side, max_side)
+        self.run_plan(plan)
+        args = (scale, annotations, iou_threshold, score_threshold, max_detections, num_classes)
+        watch = self.watches_range()
+        snapshot = self.range_snapshot(plan) if watch else None
+        out = self.match_outputs(self.outputs(plan), *args)
+        event = watch and self.note_range(plan, int(snapshot.cpu().view(self.torch.int64).item()))
+        flagged = None if event else self._audit_flags(plan)
+        if event or flagged:
+            self._range_event_raise_or_prepare('match_on_frames', flagged)          # (the preprocessed frames are still in the plan)
+            heights = self._heights_of(plan)
+            inputs = [plan.images, plan.P_inv, plan.planes]
+            twin_plan = self._twin.stage_inputs(inputs) if heights is None else self._twin.stage_canvas(inputs, heights)
+            self._twin.run_plan(twin_plan)
+            out = self._twin.match_outputs(self._twin.outputs(twin_plan), *args)
+        return out, scale
+
     # ------------------------------------------------------------------ pose rows (pose=True)
     def _require_pose(self):
         if not self.pose:

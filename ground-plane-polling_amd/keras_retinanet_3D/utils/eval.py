@@ -17,6 +17,10 @@ is the reference's (bins outermost, then images, then detections in descending s
 unstable `np.argsort(-scores)` that ranks them sees the same array and ties fall the same way.
 
 Drawing (`save_path`, utils/eval.py:120-129) needs OpenCV and is out of scope.
+
+`evaluate(..., device=True)` leaves preprocessing, resize, selection and matching to the device: raw uint8 frames go
+to `model.match_on_frames`, which returns per detection its bin, whether it is a hit, and its errors (csrc/eval.hip);
+`assemble_matches` lays them out in the collection order above and the same ranking code finishes.  The results are the host path's.
 """
 
 from __future__ import print_function
@@ -24,7 +28,7 @@ from __future__ import print_function
 import numpy as np
 
 from .anchors import compute_overlap
-from .image import class_of_resized
+from .image import class_of_resized, compute_resize_scale, height_class
 
 
 def _compute_ap(recall, precision):
@@ -131,26 +135,11 @@ def _match_bin(detections, annotations, iou_threshold):
     return hits, errors
 
 
-def evaluate(generator, model, iou_threshold=0.5, score_threshold=0.05, max_detections=100, save_path=None, batch_size=1):
-    """ Evaluate a dataset (utils/eval.py:168-262).  Returns
-    (average_precisions {bin: (AP, number of annotations)}, keypoint_error, height_error,
-    width_error, length_error); a bin without annotations reports (0, 0). """
-    all_detections = _get_detections(generator, model, score_threshold=score_threshold, max_detections=max_detections,
-                                     save_path=save_path, batch_size=batch_size)
-    all_annotations = _get_annotations(generator)
+def _finish(per_bin, regression_errors):
+    """ The last step of `evaluate`: per_bin[label] = (hit flags per image, scores per image, number of annotations), in collection
+    order; regression_errors = the (11,) error rows of the hits in that order. """
     average_precisions = {}
-    regression_errors = []
-
-    for label in range(4 * generator.num_classes()):
-        flags, scores = [], []
-        num_annotations = 0.0
-        for i in range(generator.size()):
-            detections, annotations = all_detections[i][label], all_annotations[i][label]
-            num_annotations += annotations.shape[0]
-            hits, errors = _match_bin(detections, annotations, iou_threshold)
-            flags.append(hits)
-            scores.append(detections[:, 15])
-            regression_errors.extend(errors)
+    for label, (flags, scores, num_annotations) in enumerate(per_bin):
         if num_annotations == 0:
             average_precisions[label] = 0, 0
             continue
@@ -168,6 +157,107 @@ def evaluate(generator, model, iou_threshold=0.5, score_threshold=0.05, max_dete
     regression_errors = np.vstack(regression_errors)
     return (average_precisions, np.average(regression_errors[:, :8]), np.average(regression_errors[:, 8]),
             np.average(regression_errors[:, 9]), np.average(regression_errors[:, 10]))
+
+
+def assemble_matches(tables, scores, errors, all_annotations, num_classes):
+    """ `evaluate`'s result from what the device matching returns (RetinaNet3D.match_on_frames / match_outputs; include/gpp.h,
+    gpp_eval_match_f32): per image i, tables[i] (D, 3) int32 = bin, hit, annotation row of detection d (-1: not selected), scores[i]
+    (D,) float32, errors[i] (D, 11) float64; all_annotations = `_get_annotations(generator)`.  The collection order is the host
+    path's -- bins outermost, then images, then the detections of the image best score first (equal scores: lower index first) -- so
+    the ranking in `_finish` sees the arrays it sees there. """
+    num_bins = 4 * num_classes
+    orders = []
+    for table, score in zip(tables, scores):
+        selected = np.flatnonzero(np.asarray(table)[:, 1] >= 0)
+        orders.append(selected[np.argsort(-np.asarray(score)[selected], kind='stable')])
+    per_bin, regression_errors = [], []
+    for label in range(num_bins):
+        flags, ranked_scores = [], []
+        num_annotations = 0.0
+        for i, order in enumerate(orders):
+            num_annotations += all_annotations[i][label].shape[0]
+            table = np.asarray(tables[i])
+            pick = order[table[order, 0] == label]
+            hits = table[pick, 1] == 1
+            flags.append(hits)
+            ranked_scores.append(np.asarray(scores[i])[pick].astype(np.float64))
+            regression_errors.extend(np.asarray(errors[i])[pick[hits]])
+        per_bin.append((flags, ranked_scores, num_annotations))
+    return _finish(per_bin, regression_errors)
+
+
+def _match_on_device(generator, model, iou_threshold, score_threshold, max_detections, batch_size):
+    """ (tables, scores, errors) per image from `model.match_on_frames`: the frames are `generator.load_image`'s uint8 BGR arrays;
+    mean subtraction and the resize to the generator's image_min_side / image_max_side (800 / 1333 without these attributes) happen
+    on the device (RetinaNet3D.stage_frames) -- the generator's own preprocess_image / resize_image are NOT called in this mode. """
+    if not hasattr(model, 'match_on_frames'):
+        raise ValueError('evaluate(device=True) needs a model with match_on_frames (models.load_model returns one); {} has none: '
+                         'evaluate it with device=False'.format(type(model).__name__))
+    min_side, max_side = getattr(generator, 'image_min_side', 800), getattr(generator, 'image_max_side', 1333)
+    size = generator.size()
+    tables, scores, errors = [None] * size, [None] * size, [None] * size
+
+    def flush(batch):
+        if not batch:
+            return
+        frames = [b[1] for b in batch]
+        uniform = len(set(f.shape for f in frames)) == 1
+        (table, score, error, _), _ = model.match_on_frames(
+            np.stack(frames) if uniform else frames, np.stack([b[2] for b in batch]),
+            np.tile(np.asarray(generator.plane_params)[None], (len(batch), 1, 1)), [b[3] for b in batch],
+            iou_threshold=iou_threshold, score_threshold=score_threshold, max_detections=max_detections, num_classes=generator.num_classes(),
+            min_side=min_side, max_side=max_side)
+        for k, (i, _, _, _) in enumerate(batch):
+            tables[i], scores[i], errors[i] = table[k], score[k], error[k]
+            print('{}/{}'.format(i + 1, size), end='\r')
+
+    # as in _get_detections: a batch is cut short at a change of shape, or -- a model with a ragged form -- of height class
+    ragged_ok = getattr(model, 'supports_ragged', False)
+
+    def same_call(a, b):
+        return a[:2] == b[:2] or (ragged_ok and height_class(a, min_side, max_side) == height_class(b, min_side, max_side))
+
+    batch = []
+    for i in range(size):
+        frame = np.asarray(generator.load_image(i))
+        scale = compute_resize_scale(frame.shape, min_side, max_side)
+        P = np.dot(np.diag([scale, scale, 1.0]), generator.load_calibration(i))
+        item = (i, frame, np.linalg.pinv(P), generator.load_annotations(i)[0])
+        if batch and (len(batch) >= max(batch_size, 1) or not same_call(batch[0][1].shape, frame.shape)):
+            flush(batch)
+            batch = []
+        batch.append(item)
+    flush(batch)
+    return tables, scores, errors
+
+
+def evaluate(generator, model, iou_threshold=0.5, score_threshold=0.05, max_detections=100, save_path=None, batch_size=1, device=False):
+    """ Evaluate a dataset (utils/eval.py:168-262).  Returns
+    (average_precisions {bin: (AP, number of annotations)}, keypoint_error, height_error,
+    width_error, length_error); a bin without annotations reports (0, 0).
+    device=True: the same results with preprocessing, resize, selection and matching on the device (`_match_on_device`). """
+    if device:
+        if save_path is not None:
+            raise NotImplementedError('drawing detections needs OpenCV, which this build does not use (DESIGN.md §8)')
+        tables, scores, errors = _match_on_device(generator, model, iou_threshold, score_threshold, max_detections, batch_size)
+        return assemble_matches(tables, scores, errors, _get_annotations(generator), generator.num_classes())
+    all_detections = _get_detections(generator, model, score_threshold=score_threshold, max_detections=max_detections,
+                                     save_path=save_path, batch_size=batch_size)
+    all_annotations = _get_annotations(generator)
+    per_bin, regression_errors = [], []
+
+    for label in range(4 * generator.num_classes()):
+        flags, scores = [], []
+        num_annotations = 0.0
+        for i in range(generator.size()):
+            detections, annotations = all_detections[i][label], all_annotations[i][label]
+            num_annotations += annotations.shape[0]
+            hits, errors = _match_bin(detections, annotations, iou_threshold)
+            flags.append(hits)
+            scores.append(detections[:, 15])
+            regression_errors.extend(errors)
+        per_bin.append((flags, scores, num_annotations))
+    return _finish(per_bin, regression_errors)
 
 
 def summarize(results, generator=None, verbose=1):

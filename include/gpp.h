@@ -509,6 +509,46 @@ int gpp_pose_f32(const float* boxes, const float* dims, const float* scores, con
                  float* rows, int32_t* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Matching of detections to labels for the evaluation on the device (csrc/eval.hip): what utils/eval.py does
+ * on the host with the outputs of one image -- selection and order (_image_rows; reference utils/eval.py:93-118) and the greedy
+ * assignment inside every (class, orientation) bin (_match_bin; :207-226) -- restated per detection.  One launch, one workgroup per
+ * image, one thread per detection.
+ *
+ *   boxes (B, D, 12), dims (B, D, 3), scores (B, D) float32, labels (B, D), orientations (B, D) int32: the outputs of gpp_detect_f32
+ *   as a plan leaves them (padding rows are -1), in any order.
+ *   scales (B) float32, device: the image scale of every image.
+ *   annotations (B, A, GPP_EVAL_ANN_COLS) float64, device: the rows of KittiGenerator.load_annotations, padded to A rows per image --
+ *   0-3 box, 4-11 keypoint pixels, 12-14 h w l, 15 class, 16 orientation; ann_counts (B) int32: the rows of image b that count
+ *   (clamped to [0, A]).  A == 0: annotations may be null.
+ *   table (B, D, 3) int32, row d of image b belongs to detection d: bin, hit, annotation row.
+ *   errors (B, D, GPP_EVAL_ERR_COLS) float64; counts (B) int32: the selected detections of the image.
+ *
+ *   selected    score > score_thr (strict) and rank < max_detections; rank = the entries of the image with a higher score, or an equal
+ *               score and a lower index (the stable descending order; computed here, the input need not be sorted).
+ *               A detection that is not selected has -1 in all three table columns and zeros in its errors.
+ *   bin         4 * label + orientation if 0 <= label < num_classes and 0 <= orientation < 4, else -1 (such a detection is selected
+ *               and counted, claims nothing and is no hit).  An annotation's bin likewise, from columns 15 and 16.
+ *   geometry    box columns 0-11 divided by the scale in float32, then widened to float64; dims widened.
+ *   IoU         float64, the operation sequence of utils/anchors.compute_overlap with the union clamped to DBL_EPSILON, no contraction.
+ *   claim       the FIRST annotation of the detection's bin with the largest IoU (column 2; -1 without one: a miss).
+ *   hit         the claimed IoU is >= iou_thr and the detection has the lowest rank among the selected detections that claim the same
+ *               annotation with IoU >= iou_thr (column 1: 1 or 0).
+ *   errors      of a hit: |detection - annotation| over the 8 keypoint pixels (divided by the scale), then h w l; zeros otherwise.
+ *
+ *   D <= GPP_EVAL_MAX_DETECTIONS and A <= GPP_EVAL_MAX_ANNOTATIONS, beyond: GPP_ERR_UNSUPPORTED.  Null pointer or negative size or
+ *   count: GPP_ERR_BAD_ARG, nothing launched.  B * D == 0: GPP_OK, nothing launched.  A == 0 or a count of 0: every selected
+ *   detection is a miss.  Finite inputs are the contract.
+ * ---------------------------------------------------------------------------------------- */
+#define GPP_EVAL_MAX_DETECTIONS 1024
+#define GPP_EVAL_MAX_ANNOTATIONS 1024
+#define GPP_EVAL_ANN_COLS 17
+#define GPP_EVAL_ERR_COLS 11
+int gpp_eval_match_f32(const float* boxes, const float* dims, const float* scores, const int32_t* labels,
+                       const int32_t* orientations, const float* scales, const double* annotations,
+                       const int32_t* ann_counts, int B, int D, int A, int num_classes, float score_thr,
+                       int max_detections, double iou_thr, int32_t* table, double* errors, int32_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The --save-images composite on the device (csrc/draw.hip; DESIGN.md section 4.14 is the specification, utils/visualization.py its host
  * form): per image the 2-D picture (boxes, keypoint markers, score captions) over the 3-D picture (projected cuboids, residual captions),
  * from the rows of gpp_pose_f32 and the raw uint8 BGR frames.  Two launches on one stream: gpp_draw_build, then gpp_draw_raster.
