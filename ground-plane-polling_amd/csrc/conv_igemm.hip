@@ -38,6 +38,10 @@ int validate(const gpp_conv_desc& d)
     if (d.reserved != 0) return GPP_ERR_BAD_ARG;                    // diagnostic switches exist in -DGPP_STAMPS builds only
 #endif
     if (d.reserved2 != 0 || (d.x3_split & ~(GPP_X3_IN | GPP_X3_OUT | GPP_X3_RES))) return GPP_ERR_BAD_ARG;
+    if (d.reserved3 != 0 || (d.gather_rows != nullptr) != (d.gather_counts != nullptr)) return GPP_ERR_BAD_ARG;
+    if (((uintptr_t)d.gather_rows | (uintptr_t)d.gather_counts | (uintptr_t)d.guard) & 3) return GPP_ERR_ALIGN;
+    // the gathered-row form: stride 1, no shortcut, float32 output, never split (split-K would change the summation order of a row)
+    if (d.gather_rows && (d.stride != 1 || d.residual || !d.out_f32 || d.split_k > 1)) return GPP_ERR_UNSUPPORTED;
     if (d.x3_split && !is_x3(d.dtype)) return GPP_ERR_BAD_ARG;
     if (d.out_scale && d.dtype != GPP_F16X3) return GPP_ERR_BAD_ARG;
     if ((d.x3_split & GPP_X3_OUT) && (d.out_f32 || d.C_out % 32 != 0 || d.out_pitch % 32 != 0)) return GPP_ERR_UNSUPPORTED;
@@ -99,6 +103,11 @@ int dispatch_any(gpp_conv_desc& d, hipStream_t st)
     const int rc = fill_range_counter(d);
     if (rc != GPP_OK) return rc;
     if (d.split_k == 0) d.split_k = split_rule(d);
+    if (d.gather_rows) {
+        // a layer the rule splits has another summation order than one gathered launch can give: refused, never computed differently
+        if (d.split_k > 1) return GPP_ERR_UNSUPPORTED;
+        return gpp_conv_gather_dispatch(d, st);
+    }
     switch (d.dtype) {
         case GPP_BF16: return gpp_conv_dispatch_bf16(d, st);
         case GPP_F16: return gpp_conv_dispatch_f16(d, st);
@@ -115,6 +124,7 @@ int tail_entry(const gpp_conv_desc* conv3x3, const gpp_conv_desc* conv1x1, int t
     int rc = validate(d1);
     if (rc == GPP_OK) rc = validate(d2);
     if (rc != GPP_OK) return rc;
+    if (d1.gather_rows || d2.gather_rows || d1.guard || d2.guard) return GPP_ERR_UNSUPPORTED;      // gpp_conv2d_igemm only
     const gpp_conv_group &G1 = d1.groups[0], &G2 = d2.groups[0];
     // the pair this kernel fuses: 3x3 / stride 1 / pad 1 / C -> C (C = 64 or 128) feeding 1x1 / stride 1 / C -> multiple of 128
     if (d1.dtype == GPP_F32) return GPP_ERR_UNSUPPORTED;           // 16-bit storage types, and the x3 types on pre-split maps
@@ -147,6 +157,7 @@ int block_entry(const gpp_conv_desc* conv_a, const gpp_conv_desc* conv_b, const 
     if (rc == GPP_OK) rc = validate(d2);
     if (rc == GPP_OK) rc = validate(d3);
     if (rc != GPP_OK) return rc;
+    if (d1.gather_rows || d2.gather_rows || d3.gather_rows || d1.guard || d2.guard || d3.guard) return GPP_ERR_UNSUPPORTED;
     const gpp_conv_group &G1 = d1.groups[0], &G2 = d2.groups[0], &G3 = d3.groups[0];
     // the triple this kernel fuses, on pre-split maps of one x3 type: 1x1 / stride 1 or 2 / C_in -> C; 3x3 / stride 1 / pad 1 / C -> C (C = 64 or 128);
     // 1x1 / stride 1 / C -> a multiple of 128, + shortcut map of the output's size
@@ -262,7 +273,8 @@ static const int kTiles[] = {0, 64064, 96064, 128064, 160064, 192064, 64128, 961
                              1128128, 1192128, 1128256, 1160256, 1192256, 1224256, 256256, 1256256,
                              128160, 192160, 1192160, 1128160, 2256256, 1192096, 3256224, 3192160, 4128064, 4064064, 4128128, 4064128,
                              5064064, 5096064, 5064128, 5096128, 5128128,      // x3 types, pre-split inputs: the plain loop on a four-deep ring
-                             128256, 192256};            // GPP_BF16X3 only: 8-wavefront tiles with the plain loop
+                             128256, 192256,             // GPP_BF16X3 only: 8-wavefront tiles with the plain loop
+                             6064064, 6032064, 6064160, 7064064, 7032064, 7064160};      // the gathered-row form (gpp_conv_desc.gather_rows) and nothing else
 // (the loader-wavefront form of round 2, tile codes 3064128 ..., measured 1.5 - 2x slower on every layer it was built for
 // (profiles/r2/ring_kernel.txt), is no longer part of the library)
 static bool tile_is_candidate(const gpp_conv_desc* desc, int tile)
@@ -272,6 +284,10 @@ static bool tile_is_candidate(const gpp_conv_desc* desc, int tile)
     int64_t rows = 0;
     for (int g = 0; g < desc->n_groups; ++g) rows += (int64_t)desc->batch * desc->groups[g].H_out * desc->groups[g].W_out;
     const int bn = tile % 1000 ? tile % 1000 : 128;
+    if (desc->gather_rows || tile >= 6000000) {           // gathered rows: their own three tiles; 160 columns only where that cuts the N padding
+        if (!desc->gather_rows || (tile != 0 && tile < 6000000)) return false;
+        return bn != 160 || (desc->C_out + 159) / 160 * 160 < (desc->C_out + 63) / 64 * 64;
+    }
     if (tile >= 5000000) {           // four-deep ring (x3 types, pre-split inputs): deep K, and a grid of at most ~one workgroup per CU
         static const bool no_deep = [] { const char* e = getenv("GPP_NO_DEEP_TILES"); return e && e[0] == '1'; }();      // (A/B)
         const bool x3_in = is_x3(desc->dtype) && (desc->x3_split & GPP_X3_IN);
@@ -425,6 +441,7 @@ int preact_validate(gpp_conv_desc& d, const float* in_scale, const float* in_shi
     if (((uintptr_t)in_scale | (uintptr_t)in_shift) & 15) return GPP_ERR_ALIGN;
     if (d.KH != 1 || d.KW != 1 || d.stride != 1 || d.pad_top != 0 || d.pad_left != 0) return GPP_ERR_UNSUPPORTED;
     if (d.x3_split & GPP_X3_IN) return GPP_ERR_UNSUPPORTED;
+    if (d.gather_rows || d.guard) return GPP_ERR_UNSUPPORTED;          // gpp_conv2d_igemm only
     if (d.C_in > 4096) return GPP_ERR_UNSUPPORTED;               // the scale / shift table lives in LDS beside the ring
     return GPP_OK;
 }

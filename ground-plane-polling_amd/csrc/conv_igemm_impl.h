@@ -468,12 +468,20 @@ constexpr int stage_rows(int BM, int NW) { return (BM + 8 * NW - 1) / (8 * NW) *
 // max(x * pre_s[c] + pre_t[c], 0) where its fragment leaves LDS -- the BatchNormalization + ReLU of a DenseNet layer that belongs to the
 // CONSUMER of a concatenation (it cannot be folded into any producer).  The two per-channel tables are copied to LDS behind the ring
 // (2 * C_in float32) before the first tile load; the K order, and so every bit of the result, is that of the plain loop.
-template <int DT, int BM, int BN, int WM, int WN, int STAGES, bool PIPE, bool XIN = false, bool PRE = false>
+// GATHER (gpp_conv_desc.gather_rows: the head output layers on the pixels the decode reads): GEMM row m of a group is pixel list[m] of that
+// group's ascending device list, and the group has gather_counts[g] rows instead of batch * H_out * W_out.  Exactly two places map a row to a
+// pixel -- the staging setup below (a_base / a_mask) and the epilogue's output address -- so the K order per output element, the epilogue
+// arithmetic and the stores of a listed pixel are those of the dense launch: the same bytes.  A workgroup whose first row lies at or past the
+// count returns before its first barrier.  Plain loop, stride 1, no residual, no split-K (validated on the host).
+template <int DT, int BM, int BN, int WM, int WN, int STAGES, bool PIPE, bool XIN = false, bool PRE = false, bool GATHER = false>
 __device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const int block_x, const int grid_x, const float* pre_s = nullptr,
                                                 const float* pre_t = nullptr)
 {
     static_assert(!XIN || kX3<DT>, "pre-split input maps: GPP_BF16X3 / GPP_F16X3");
     static_assert(!PRE || (!PIPE && !XIN && kF32Storage<DT>), "pre-activation: float32-sized input maps, plain loop");
+    static_assert(!GATHER || (!PIPE && !PRE), "gathered rows: plain loop");
+    // gpp_conv_desc.guard: a launch switched off by a value computed earlier on the device -- every workgroup leaves here (one uniform load)
+    if (d.guard != nullptr && *(const volatile int32_t*)d.guard != d.guard_value) return;
     using E = Elem<DT>;
     using vec8 = typename E::vec8;
     using frag = typename E::frag;
@@ -500,13 +508,20 @@ __device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const in
     GPP_STAMP(0);
 
     // ---- which tile
-    const int bid = xcd_remap(block_x, grid_x);
+    // (GATHER: the live tiles are the first few of every group -- the remap would hand them all to one XCD's 32 CUs (measured: 120 workgroups
+    // took the time of four rounds); left in launch order they go round the eight XCDs)
+    const int bid = GATHER ? block_x : xcd_remap(block_x, grid_x);
     const int n_tiles = (d.C_out + BN - 1) / BN;
     const int nt = bid % n_tiles, mt = bid / n_tiles;
     int tile_start = 0, row_begin = 0, H_in = 0, W_in = 0, H_out = 0, W_out = 0, H_res = 0, W_res = 0;
     int64_t in_off = 0, in_bs = 0, out_off = 0, out_bs = 0, res_off = 0, res_bs = 0;
+    int list_begin = 0, list_next = 0, group = 0;      // GATHER: where this group's pixel list starts (the lists lie back to back, each sized for every pixel)
 #pragma unroll
     for (int q = 0; q < GPP_MAX_GROUPS; ++q) {
+        if constexpr (GATHER) {
+            if (q < d.n_groups && mt >= d.groups[q].tile_start) { list_begin = list_next; group = q; }
+            if (q < d.n_groups) list_next += d.batch * d.groups[q].H_out * d.groups[q].W_out;
+        }
         if (q < d.n_groups && mt >= d.groups[q].tile_start) {
             tile_start = d.groups[q].tile_start;
             row_begin = d.groups[q].row_begin;
@@ -519,8 +534,15 @@ __device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const in
         }
     }
     const int HoWo = H_out * W_out;
-    const int Mg = d.batch * HoWo;
+    const int Mpix = d.batch * HoWo;
+    const int32_t* const glist = GATHER ? d.gather_rows + list_begin : nullptr;
+    const int Mg = GATHER ? min(max(d.gather_counts[group], 0), Mpix) : Mpix;
     const int m0 = row_begin + (mt - tile_start) * BM, n0 = nt * BN;       // (row_begin: 0 except in the second part of a mixed grid)
+    if constexpr (GATHER) {
+        if (m0 >= Mg) return;                           // the grid covers every pixel; the list is usually a small part of them
+    }
+    // GATHER: the pixel of GEMM row m (clamped into the group: a bad list gives a wrong picture, never an access outside the maps)
+    auto pixel_of = [&](int m) { return min(max(glist[m], 0), Mpix - 1); };
     const int Ktot = d.KH * d.KW * d.C_in;
     const int cpt = d.C_in / CK;                        // channel chunks per tap
     const int nk_total = d.KH * d.KW * cpt;
@@ -555,13 +577,14 @@ __device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const in
     const int pitch2 = d.in_pitch * ESZ;                // bytes per input pixel
     {
         PixWalk pw;                                     // rows m, m + 8, m + 16, ...: one pair of divisions, then a walk
-        pw.init(m0 + wave * A_IT * 8 + srow, HoWo, W_out);
+        if constexpr (!GATHER) pw.init(m0 + wave * A_IT * 8 + srow, HoWo, W_out);
 #pragma unroll
         for (int i = 0; i < A_IT; ++i) {
             const int m = m0 + (wave * A_IT + i) * 8 + srow;
             a_mask[i] = 0;
             a_base[i] = 0;
             if (m < Mg) {
+                if constexpr (GATHER) pw.init(pixel_of(m), HoWo, W_out);      // (row -> pixel, first of the two places)
                 const int iy0 = pw.oy * d.stride - d.pad_top, ix0 = pw.ox * d.stride - d.pad_left;
                 // bit k: input row iy0 + k inside the image = k in [max(0, -iy0), min(KH, H_in - iy0)); columns likewise (no loops)
                 const int rlo = max(0, -iy0), rhi = min(d.KH, max(0, H_in - iy0));
@@ -571,7 +594,7 @@ __device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const in
                 a_mask[i] = rmask | (cmask << 8);
                 a_base[i] = (int)((in_off + (int64_t)pw.b * in_bs) * ESZ) + gchunk * 16 + (iy0 * W_in + ix0) * pitch2;
             }
-            if (i + 1 < A_IT) pw.advance(8, H_out, W_out);
+            if (!GATHER && i + 1 < A_IT) pw.advance(8, H_out, W_out);
         }
     }
     int w_voff[B_IT];
@@ -632,7 +655,7 @@ __device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const in
     constexpr bool RESPRE = !PIPE && (MF * NF / 2 <= (ESZ == 4 ? 8 : 10));
     vec8 rpre[RESPRE ? MF : 1][RESPRE ? NF / 2 : 1];
     RowAddr ra_pre[RESPRE ? MF : 1];
-    const bool use_pre = RESPRE && d.residual != nullptr && gridDim.y == 1 && (d.C_out & 7) == 0;
+    const bool use_pre = !GATHER && RESPRE && d.residual != nullptr && gridDim.y == 1 && (d.C_out & 7) == 0;
     if constexpr (RESPRE) {
         if (use_pre) {
             PixWalk pw;
@@ -1167,7 +1190,7 @@ __device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const in
     // An INTERIOR tile -- every row a pixel, every column a channel: all but the last tile of a group / of the channel range --
     // runs the epilogue without per-lane conditions (the general form costs ~280 exec-mask branches per wavefront: 6 us of a
     // 256 x 256 tile's life, a quarter of a 18-K-step tile's) and walks the output rows instead of dividing per row.
-    const bool interior = (m0 + BM <= Mg) && (n0 + BN <= d.C_out) && ((d.C_out & 7) == 0);
+    const bool interior = !GATHER && (m0 + BM <= Mg) && (n0 + BN <= d.C_out) && ((d.C_out & 7) == 0);
     if constexpr (!BIASPRE) load_bias();
     if constexpr (RESPRE) {
         if (use_pre && interior) {
@@ -1233,13 +1256,14 @@ __device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const in
         return;
     }
     PixWalk pwe;
-    pwe.init(m0 + wm * (BM / WM) + frow, HoWo, W_out);
+    if constexpr (!GATHER) pwe.init(m0 + wm * (BM / WM) + frow, HoWo, W_out);
 #pragma unroll
     for (int i = 0; i < MF; ++i) {
         const int m = m0 + wm * (BM / WM) + i * 16 + frow;
         if (m >= Mg) break;                                            // rows ascend with i
+        if constexpr (GATHER) pwe.init(pixel_of(m), HoWo, W_out);      // (row -> pixel, second of the two places)
         const RowAddr ra = row_addr_at(d, pwe, W_out, H_out, H_res, W_res, out_off, out_bs, res_off, res_bs);
-        pwe.advance(16, H_out, W_out);
+        if constexpr (!GATHER) pwe.advance(16, H_out, W_out);
         const scalar* rrow = res ? res + ra.rbase : nullptr;
 #pragma unroll
         for (int jj = 0; jj < NF / 2; ++jj) {
@@ -1261,6 +1285,13 @@ template <int DT, int BM, int BN, int WM, int WN, int STAGES, bool PIPE, bool XI
 __global__ __launch_bounds__(64 * WM * WN, 2) void conv_igemm_kernel(const gpp_conv_desc d)
 {
     conv_igemm_body<DT, BM, BN, WM, WN, STAGES, PIPE, XIN>(d, blockIdx.x, gridDim.x);
+}
+
+// the gathered-row form (GATHER above): kernels of their own, conv_igemm_gather.hip instantiates them
+template <int DT, int BM, int BN, int WM, int WN, int STAGES, bool XIN>
+__global__ __launch_bounds__(64 * WM * WN, 2) void conv_gather_kernel(const gpp_conv_desc d)
+{
+    conv_igemm_body<DT, BM, BN, WM, WN, STAGES, false, XIN, false, true>(d, blockIdx.x, gridDim.x);
 }
 
 // gpp_conv2d_preact: the plain loop with the pre-activation prologue (PRE above); kernels of their own, so that conv_igemm_kernel and its
@@ -1310,6 +1341,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_mix_kernel(const gpp_conv_d
 template <int DT>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const gpp_conv_desc d, int BM, int npad, int nsplit)
 {
+    if (d.guard != nullptr && *(const volatile int32_t*)d.guard != d.guard_value) return;      // (as the launch it finishes)
     using scalar = typename Elem<DT>::scalar;
     const int n8 = (d.C_out + 7) / 8;
     const int64_t total = (int64_t)d.partial_rows * n8;
@@ -2426,9 +2458,51 @@ int launch_ws(gpp_conv_desc& d, hipStream_t st)
     return e == hipSuccess ? GPP_OK : (int)e;
 }
 
+// One tile of the gathered-row form: the grid of the dense launch with this tile (every pixel could be listed), the plain loop on a
+// two- or four-deep ring.
+template <int DT, int BM, int BN, int WM, int WN, int STAGES, bool XIN = false>
+int launch_gather(gpp_conv_desc& d, hipStream_t st)
+{
+    if constexpr (kX3<DT> && !XIN) {
+        if (d.x3_split & GPP_X3_IN) return launch_gather<DT, BM, BN, WM, WN, STAGES, true>(d, st);
+    }
+    constexpr int BMS = stage_rows(BM, WM * WN);
+    constexpr int lds = STAGES * (BMS + BN) * kRowBytes;
+    static DeviceOnce once;
+    auto kernel = conv_gather_kernel<DT, BM, BN, WM, WN, STAGES, XIN>;
+    int rc = once.configure(kernel, lds);
+    if (rc != GPP_OK) return rc;
+    const int tiles = prepare<BM, BN>(d);
+    if (tiles < 0) return tiles;
+    const int n_tiles = (d.C_out + BN - 1) / BN;
+    kernel<<<dim3((unsigned)(tiles * n_tiles)), dim3(64 * WM * WN), lds, st>>>(d);
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? GPP_OK : (int)e;
+}
+
+// the tiles of the gathered-row form (gpp_conv2d_tile_candidates lists the same codes): short and narrow, so that a few thousand rows
+// still field a few hundred workgroups; 64 x 160 on a 4 x 1 layout for the 144 regression channels.  6000000 + BM * 1000 + BN: the
+// two-deep ring; 7000000 + ...: the four-deep ring (three K-steps of tile loads in flight) -- a gathered launch fields at most about one
+// workgroup per CU, and a workgroup alone on its CU is bound by the latency of its own loads, K-step after K-step
+template <int DT>
+int dispatch_gather(gpp_conv_desc& d, hipStream_t st)
+{
+    switch (d.tile_hint) {
+        case 0:
+        case 6064064: return launch_gather<DT, 64, 64, 2, 2, 2>(d, st);
+        case 6032064: return launch_gather<DT, 32, 64, 2, 2, 2>(d, st);
+        case 6064160: return launch_gather<DT, 64, 160, 4, 1, 2>(d, st);
+        case 7064064: return launch_gather<DT, 64, 64, 2, 2, 4>(d, st);
+        case 7032064: return launch_gather<DT, 32, 64, 2, 2, 4>(d, st);
+        case 7064160: return launch_gather<DT, 64, 160, 4, 1, 4>(d, st);
+        default: return GPP_ERR_BAD_ARG;
+    }
+}
+
 template <int DT>
 int dispatch(gpp_conv_desc& d, hipStream_t st)
 {
+    if (d.guard && d.tile_hint >= 4000000 && d.tile_hint < 5000000) return GPP_ERR_UNSUPPORTED;      // (conv1x1_ws_kernel reads no guard)
     switch (d.tile_hint) {               // explicit choices (BM*1000 + BN, or the legacy codes): what the host-side autotuner hands in
         case 64:
         case 128064: return launch<DT, 128, 64, 2, 2, 2, false>(d, st);

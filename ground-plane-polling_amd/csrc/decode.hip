@@ -747,6 +747,133 @@ extern "C" int gpp_pack_detections(const float* boxes, const float* dims, const 
     return e == hipSuccess ? GPP_OK : (int)e;
 }
 
+// ---- gpp_detect_pixel_lists: the pixels that carry a candidate, per pyramid level, ascending (include/gpp.h).  The head output layers
+// run on these pixels only (gpp_conv_desc.gather_rows): nms_kernel and emit_kernel read the regression maps at candidate anchors and nowhere else.
+namespace {
+
+struct LevelTable {
+    int n_levels;
+    int pix[GPP_MAX_GROUPS];          // pixels of a level per image
+    int pix_begin[GPP_MAX_GROUPS];    // first pixel of a level inside an image's pyramid
+    int word_begin[GPP_MAX_GROUPS];   // first bitmap word of a level (every level starts a word)
+    int list_begin[GPP_MAX_GROUPS];   // first entry of a level's list
+};
+
+// one bit per (level, image, pixel): bit b * pix[l] + p of the level's words -- the value its list will hold.  The keys of a list are in
+// the order their atomics arrived; the bitmap forgets it (and folds the up to num_base_anchors candidates of a pixel into one bit).
+__global__ __launch_bounds__(256) void mark_pixels_kernel(const unsigned long long* __restrict__ keys, const int32_t* __restrict__ cnt,
+                                                          int64_t key_stride, int64_t n_anchors, int nba, int lists_per_image,
+                                                          const LevelTable T, uint32_t* __restrict__ bitmap)
+{
+    const int list = blockIdx.y, b = list / lists_per_image;
+    const int64_t n = min((int64_t)max(cnt[list * (kCounterStride / 4)], 0), n_anchors);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const uint32_t a = 0xFFFFFFFFu - (uint32_t)keys[(int64_t)list * key_stride + i];
+        if ((int64_t)a >= n_anchors) continue;
+        const int pixel = (int)(a / (uint32_t)nba);
+        int l = 0;
+        for (int q = 1; q < T.n_levels; ++q) l = pixel >= T.pix_begin[q] ? q : l;
+        const int bit = b * T.pix[l] + (pixel - T.pix_begin[l]);
+        atomicOr(&bitmap[T.word_begin[l] + (bit >> 5)], 1u << (bit & 31));
+    }
+}
+
+// one workgroup walks the levels' words in order: a popcount scan places every set bit, so each list comes out ascending; the words are
+// cleared on the way (the next call finds the map empty).  counts[l], then their sum at counts[GPP_MAX_GROUPS]; flag = the sum exceeds max_rows.
+constexpr int kCompactThreads = 1024;
+__global__ __launch_bounds__(kCompactThreads) void compact_pixels_kernel(uint32_t* __restrict__ bitmap, const LevelTable T, int B, int max_rows,
+                                                                         int32_t* __restrict__ rows, int32_t* __restrict__ counts,
+                                                                         int32_t* __restrict__ flag)
+{
+    __shared__ int wave_sum[kCompactThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int total = 0;
+    for (int l = 0; l < GPP_MAX_GROUPS; ++l) {
+        int running = 0;
+        if (l < T.n_levels) {
+            const int n_words = (B * T.pix[l] + 31) >> 5;
+            for (int w0 = 0; w0 < n_words; w0 += kCompactThreads) {
+                const int w = w0 + tid;
+                uint32_t word = 0;
+                if (w < n_words) {
+                    word = bitmap[T.word_begin[l] + w];
+                    if (word) bitmap[T.word_begin[l] + w] = 0;
+                }
+                const int c = __popc(word);
+                int incl = c;                                      // inclusive scan inside the wavefront
+#pragma unroll
+                for (int s = 1; s < 64; s <<= 1) {
+                    const int up = __shfl_up(incl, s, 64);
+                    if (lane >= s) incl += up;
+                }
+                if (lane == 63) wave_sum[wave] = incl;
+                __syncthreads();
+                int before = 0, all = 0;
+#pragma unroll
+                for (int q = 0; q < kCompactThreads / 64; ++q) {
+                    const int v = wave_sum[q];
+                    before += q < wave ? v : 0;
+                    all += v;
+                }
+                __syncthreads();
+                int pos = running + before + incl - c;
+                while (word) {
+                    const int bit = __ffs((int)word) - 1;
+                    word &= word - 1;
+                    rows[T.list_begin[l] + pos++] = w * 32 + bit;      // (pos < the level's B * pix[l] entries: one per set bit)
+                }
+                running += all;
+            }
+        }
+        if (tid == 0) counts[l] = running;
+        total += running;
+    }
+    if (tid == 0) {
+        counts[GPP_MAX_GROUPS] = total;
+        flag[0] = total > max_rows ? 1 : 0;
+    }
+}
+
+}  // namespace
+
+extern "C" int gpp_detect_pixel_lists(const gpp_pixel_list_desc* host_desc, void* stream)
+{
+    if (!host_desc) return GPP_ERR_BAD_ARG;
+    const gpp_pixel_list_desc& d = *host_desc;
+    if (d.B < 0 || d.B > kMaxBatch || d.n_anchors <= 0 || d.n_anchors > kMaxAnchors || d.num_base_anchors <= 0 || d.max_rows < 0 ||
+        d.n_levels < 1 || d.n_levels > GPP_MAX_GROUPS || (d.lists_per_image != 1 && d.lists_per_image != 4) || d.reserved != 0 || d.reserved2 != 0)
+        return GPP_ERR_BAD_ARG;
+    if (d.B == 0) return GPP_OK;
+    if (!d.workspace || !d.bitmap || !d.rows || !d.counts || !d.flag) return GPP_ERR_BAD_ARG;
+    if (((uintptr_t)d.workspace & 15) || (((uintptr_t)d.bitmap | (uintptr_t)d.rows | (uintptr_t)d.counts | (uintptr_t)d.flag) & 3)) return GPP_ERR_ALIGN;
+    const int lists = d.B * d.lists_per_image;
+    if (lists > 64) return GPP_ERR_UNSUPPORTED;            // header slots of the detect workspace
+    LevelTable T;
+    T.n_levels = d.n_levels;
+    int64_t pixels = 0, words = 0;
+    for (int l = 0; l < GPP_MAX_GROUPS; ++l) {
+        const int pix = l < d.n_levels ? d.level_pixels[l] : 0;
+        if (l < d.n_levels && pix <= 0) return GPP_ERR_BAD_ARG;
+        if ((int64_t)d.B * (pixels + pix) >= (1LL << 31)) return GPP_ERR_UNSUPPORTED;
+        T.pix[l] = pix;
+        T.pix_begin[l] = (int)pixels;
+        T.word_begin[l] = (int)words;
+        T.list_begin[l] = (int)((int64_t)d.B * pixels);
+        pixels += pix;
+        words += ((int64_t)d.B * pix + 31) / 32;
+    }
+    if (pixels * d.num_base_anchors != d.n_anchors) return GPP_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned char* ws = (const unsigned char*)d.workspace;
+    const int32_t* cnt = (const int32_t*)ws;
+    const unsigned long long* keys = (const unsigned long long*)(ws + kHeaderBytes);
+    mark_pixels_kernel<<<dim3(16, (unsigned)lists), 256, 0, st>>>(keys, cnt, pow2_ceil(d.n_anchors), d.n_anchors, d.num_base_anchors,
+                                                                   d.lists_per_image, T, d.bitmap);
+    compact_pixels_kernel<<<1, kCompactThreads, 0, st>>>(d.bitmap, T, d.B, d.max_rows, d.rows, d.counts, d.flag);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? GPP_OK : (int)e;
+}
+
 extern "C" int gpp_detect_workspace_bytes(int B, int64_t n_anchors, size_t* bytes)
 {
     if (!bytes || B < 0 || B > kMaxBatch || n_anchors <= 0 || n_anchors > kMaxAnchors) return GPP_ERR_BAD_ARG;

@@ -275,6 +275,17 @@ extern "C" int gpp_plan_run(const gpp_plan_op* ops, int n_ops, void* stream, voi
                                        d->workspace_bytes, stream);
             break;
         }
+        case GPP_OP_DETECT_CANDIDATE_PIXELS: {      // the candidate pass, then the pixel lists the gathered head output layers run on
+            const gpp_candidate_pixels_desc* c = (const gpp_candidate_pixels_desc*)op.desc;
+            const gpp_detect_desc* d = c->detect;
+            if (!d) return fail(GPP_ERR_BAD_ARG);
+            rc = gpp_detect_stages_f32(GPP_DETECT_CANDIDATES, d->cls_logits, d->regression, d->regression_dim, d->anchors, d->B, d->n_anchors,
+                                       d->num_base_anchors, d->fused_layout, d->score_thr, d->iou_thr, d->max_det, d->boxes,
+                                       d->dims, d->scores, d->labels, d->orientations, d->anchor_index, d->counts, d->workspace,
+                                       d->workspace_bytes, stream);
+            if (rc == GPP_OK) rc = gpp_detect_pixel_lists(&c->lists, stream);
+            break;
+        }
         case GPP_OP_POLL: {
             const gpp_poll_desc* d = (const gpp_poll_desc*)op.desc;
             rc = gpp_poll_f32(d->boxes, d->dims, d->orient, d->P_inv, d->planes, d->B, d->D, d->N, d->planes_batched, d->thr,

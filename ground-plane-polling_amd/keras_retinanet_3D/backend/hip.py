@@ -75,7 +75,17 @@ class ConvDesc(ctypes.Structure):
                 ('in_bytes', ctypes.c_int32), ('weight_bytes', ctypes.c_int32),
                 ('partial', c_void_p), ('partial_bytes', c_int64), ('split_k', ctypes.c_int32), ('partial_rows', ctypes.c_int32),
                 ('groups', ConvGroup * GPP_MAX_GROUPS),
-                ('x3_split', ctypes.c_int32), ('reserved2', ctypes.c_int32), ('out_scale', c_void_p), ('range_counter', c_void_p)]
+                ('x3_split', ctypes.c_int32), ('reserved2', ctypes.c_int32), ('out_scale', c_void_p), ('range_counter', c_void_p),
+                ('gather_rows', c_void_p), ('gather_counts', c_void_p), ('guard', c_void_p),
+                ('guard_value', ctypes.c_int32), ('reserved3', ctypes.c_int32)]
+
+
+class PixelListDesc(ctypes.Structure):
+    """ gpp_pixel_list_desc (include/gpp.h) """
+    _fields_ = [('workspace', c_void_p), ('bitmap', c_void_p), ('rows', c_void_p), ('counts', c_void_p), ('flag', c_void_p),
+                ('n_anchors', c_int64)] + \
+               [(n, ctypes.c_int32) for n in ('B', 'num_base_anchors', 'lists_per_image', 'n_levels', 'max_rows', 'reserved')] + \
+               [('level_pixels', ctypes.c_int32 * GPP_MAX_GROUPS), ('reserved2', ctypes.c_int32)]
 
 
 class MobileNetBlockDesc(ctypes.Structure):
@@ -125,6 +135,9 @@ def _declare(lib):
     if hasattr(lib, 'gpp_eval_match_f32'):
         lib.gpp_eval_match_f32.restype = c_int
         lib.gpp_eval_match_f32.argtypes = [c_void_p] * 8 + [c_int] * 4 + [c_float, c_int, ctypes.c_double] + [c_void_p] * 4
+    if hasattr(lib, 'gpp_detect_pixel_lists'):
+        lib.gpp_detect_pixel_lists.restype = c_int
+        lib.gpp_detect_pixel_lists.argtypes = [ctypes.POINTER(PixelListDesc), c_void_p]
     lib.gpp_conv2d_igemm.restype = c_int
     lib.gpp_conv2d_igemm.argtypes = [ctypes.POINTER(ConvDesc), c_void_p]
     lib.gpp_stem_conv7x7_bn_relu.restype = c_int

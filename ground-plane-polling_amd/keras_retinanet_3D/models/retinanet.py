@@ -77,6 +77,11 @@ class DetectDesc(ctypes.Structure):
                 ('max_det', ctypes.c_int32), ('score_thr', ctypes.c_float), ('iou_thr', ctypes.c_float)]
 
 
+class CandidatePixelsDesc(ctypes.Structure):
+    """ gpp_candidate_pixels_desc (include/gpp.h): the candidate pass of a DetectDesc, then the pixel lists of the gathered head output layers """
+    _fields_ = [('detect', ctypes.c_void_p), ('lists', hip.PixelListDesc)]
+
+
 class PollDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ('boxes', 'dims', 'orient', 'P_inv', 'planes', 'keypoints', 'keyplanes',
                                                'residuals', 'best_idx', 'workspace')] + \
@@ -121,13 +126,14 @@ OP_MOBILENET_STEM, OP_MOBILENET_BLOCK = 33, 34                  # MobileNet (inc
 OP_POSE = 19                                                    # RetinaNet3D(pose=True): gpp_pose_f32 behind the polling
 OP_ABSMAX, OP_ABSMAX_CLEAR = 35, 36                             # RetinaNet3D(range_audit=True): gpp_channel_absmax behind every audited map
 OP_STEM_RAGGED, OP_STEM_POOL_RAGGED, OP_MAXPOOL_RAGGED = 37, 38, 39    # ragged plans (plan_for(..., ragged=True)): per-image heights from a device table
-DETECT_OPS = (OP_DETECT, OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT, 12)
+OP_DETECT_CANDIDATE_PIXELS = 40                                 # OP_DETECT_CANDIDATES + gpp_detect_pixel_lists (sparse head outputs)
+DETECT_OPS = (OP_DETECT, OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT, 12, OP_DETECT_CANDIDATE_PIXELS)
 OP_JOIN, OP_SYNC = 0x10000, 0x20000
 
 
 # the effective plan switches of one (model, batch), read from the GPP_* variables by RetinaNet3D._plan_options
 PlanOptions = collections.namedtuple('PlanOptions', 'x3_level fuse_stem_pool stage_chunks half_stages fuse_tail fuse_block fuse_block_proj '
-                                                    'br1_lane fpn_lanes p4_lane head_lanes decode_overlap cls_lane autotune tune_key')
+                                                    'br1_lane fpn_lanes p4_lane head_lanes decode_overlap cls_lane autotune tune_key sparse_heads')
 
 
 def block_form(opts, width, projection, split_input, halves, join):
@@ -158,6 +164,8 @@ TOWER_SLICES = {('pyramid_towers_0', 0): 'pyramid_regression_0', ('pyramid_tower
 # 2^-9 keeps fewer than 16 significant bits of it, i.e. the whole map is stored at bf16x3 grade or worse
 RANGE_AUDIT_THRESHOLD = 2.0 ** -9
 X3_QUANTUM = 2.0 ** -24
+# sparse head outputs: the share of listed rows up to which the gathered launches run (where their time crosses the dense launches')
+SPARSE_HEADS_MAX_SHARE = '0.5'
 
 
 def audit_report(maps, table, threshold=RANGE_AUDIT_THRESHOLD):
@@ -189,6 +197,44 @@ def audit_report(maps, table, threshold=RANGE_AUDIT_THRESHOLD):
     return out
 
 
+class SparseHeads(object):
+    """ what the gathered head output layers of a plan share: the device lists gpp_detect_pixel_lists writes behind the candidate pass
+    (bitmap, rows, counts, flag), the guarded dense descriptors (Plan.complete_heads) and the gathered ones (the tuner) """
+
+    def __init__(self, torch, device, B, level_pixels, max_share):
+        i32 = torch.int32
+        self.B, self.level_pixels = B, [int(p) for p in level_pixels]
+        total = B * sum(self.level_pixels)
+        self.max_rows = max(0, min(total, int(max_share * total)))
+        self.bitmap = torch.zeros((sum((B * p + 31) // 32 for p in self.level_pixels),), dtype=i32, device=device)
+        self.rows = torch.zeros((total,), dtype=i32, device=device)
+        self.counts = torch.zeros((hip.GPP_MAX_GROUPS + 1,), dtype=i32, device=device)
+        # 1: more rows than max_rows are listed -- the dense launches run and the gathered ones return at once; 0: the other way round.
+        # 1 until a run's lists say otherwise, so that a single op run on its own (the per-layer tests) writes its whole map
+        self.flag = torch.ones((1,), dtype=i32, device=device)
+        self.dense, self.gathered = [], []
+        self.lists_joined = False
+
+    def tensors(self):
+        return [self.bitmap, self.rows, self.counts, self.flag]
+
+    def put_every_nth(self, torch, n=8):
+        """ a synthetic list for the tuner: every n-th pixel of every level """
+        begin, counts = 0, []
+        for p in self.level_pixels:
+            idx = torch.arange(0, self.B * p, n, dtype=torch.int32, device=self.rows.device)
+            self.rows[begin:begin + idx.numel()] = idx
+            counts.append(int(idx.numel()))
+            begin += self.B * p
+        counts += [0] * (hip.GPP_MAX_GROUPS - len(counts)) + [sum(counts)]
+        self.counts.copy_(torch.as_tensor(counts, dtype=torch.int32))
+
+    def reset(self, torch):
+        """ nothing listed, the dense launches run: the state before the first run """
+        self.counts.zero_()
+        self.flag.fill_(1)
+
+
 class Plan(object):
     """ Everything one (batch, H, W, N planes) configuration needs: buffers, descriptors, op array. """
 
@@ -215,6 +261,39 @@ class Plan(object):
         self.flops = 0.0
         self.ragged = False     # plan_for(..., ragged=True): the plan of a height class; heights = its int32 device table, heights_host = what it holds
         self.heights = None
+        self.sparse = None      # SparseHeads: the head output layers run on the candidates' pixels only (RetinaNet3D._heads)
+        self.heads_stale = False    # a run has left rows of regression / regression_dim unwritten: the next read of either completes them
+
+    # The two regression head tensors.  With sparse head outputs a run writes them at the pixels the decode reads and nowhere else; whoever
+    # reads a whole tensor (tests, bench.py --full, the CPU replay of the decode) gets it whole: the first read after such a run enqueues the
+    # two dense launches -- the descriptors a dense plan runs, on the current stream -- and the listed rows keep their bytes (a gathered row
+    # IS the dense row).  predict_on_batch, run_plan and fetch never come here.
+    @property
+    def regression(self):
+        self.complete_heads()
+        return self._regression
+
+    @regression.setter
+    def regression(self, tensor):
+        self._regression = tensor
+
+    @property
+    def regression_dim(self):
+        self.complete_heads()
+        return self._regression_dim
+
+    @regression_dim.setter
+    def regression_dim(self, tensor):
+        self._regression_dim = tensor
+
+    def complete_heads(self):
+        if self.sparse is None or not self.heads_stale:
+            return
+        self.heads_stale = False
+        for guarded in self.sparse.dense:
+            d = type(guarded).from_buffer_copy(guarded)       # the dense launch as it stands in the plan, without its guard
+            d.guard, d.guard_value = None, 0
+            hip.check(hip.lib().gpp_conv2d_igemm(ctypes.byref(d), hip.stream_ptr()), 'gpp_conv2d_igemm (head tensors completed)')
 
     def emit(self, kind, desc, name, reads=(), writes=(), tag=0, flops=0.0, lane=0, join=False, sync=False, io=None, inner=(), atomic=()):
         """ record one launch.  reads / writes: the FMaps and tensors it reads and writes (check_stream_ordering); io: its
@@ -786,6 +865,14 @@ class RetinaNet3D(object):
 
         def decode(kind, name='filtered_detections', **flags):
             reads, writes = access.get(kind, (heads, dets + [ws, plan.counts]))          # (OP_DETECT / OP_DETECT_OSF: the whole decode)
+            if kind == OP_DETECT_CANDIDATE_PIXELS:      # the candidate pass + the pixel lists of the gathered head output layers, one op
+                sp = plan.sparse
+                lists = hip.PixelListDesc(ws.data_ptr(), sp.bitmap.data_ptr(), sp.rows.data_ptr(), sp.counts.data_ptr(), sp.flag.data_ptr(),
+                                          plan.n_anchors, B, anchor_utils.NUM_BASE_ANCHORS, 4 if self.osf else 1, len(sp.level_pixels),
+                                          sp.max_rows, 0, (ctypes.c_int32 * hip.GPP_MAX_GROUPS)(*sp.level_pixels), 0)
+                reads, writes = access[OP_DETECT_CANDIDATES]
+                plan.emit(kind, CandidatePixelsDesc(ctypes.addressof(dd), lists), name, reads, writes + sp.tensors(), inner=(dd,), **flags)
+                return
             plan.emit(kind, dd, name, reads, writes, **flags)
         return (cls_o, reg_o, dim_o), decode
 
@@ -810,15 +897,49 @@ class RetinaNet3D(object):
                 _, dst = pyramid(width)
                 self._conv(plan, '{}_{}'.format(prefix, i), src, dst, 3, pad=(1, 1), relu=True, tag=tag, lane=lane)
                 src = dst
-            self._conv(plan, out_name, src, out, 3, pad=(1, 1), out_f32=True, lane=lane, join=join)
+            out_layer(out_name, src, out, lane, join)
+
+        def out_layer(name, src, out, lane, join):
+            """ the output layer of a tower.  opts.sparse_heads, regression and dimension tower: the decode reads these maps at candidate
+            anchors only (nms_kernel, emit_kernel), and the candidate lists exist before the regression tower starts -- so the layer runs
+            in gathered-row form on the pixels gpp_detect_pixel_lists listed (gpp_conv_desc.gather_rows: byte-identical rows, nothing else
+            written).  The dense launch stays in the plan in front of it, guarded by the lists' flag: when more than max_rows rows are
+            listed it runs and the gathered one returns at once, otherwise all its workgroups return on the flag -- no host round trip
+            either way.  The first of the pair joins the candidates' lane unless a join has followed the lists already.  A layer the
+            split-K rule splits (small maps) keeps its dense launch alone: one gathered launch cannot reproduce that summation order. """
+            sp = plan.sparse
+            kh, kw, cin, cout = self.conv_w[name][2]
+            pixels = sum(f.H * f.W for f in out)
+            split = (C.latency_split if self.plan_mode == 'latency' else C.default_split)(kh, kw, cin, cout, pixels)
+            if sp is None or name == 'pyramid_classification' or lane or split > 1:
+                self._conv(plan, name, src, out, 3, pad=(1, 1), out_f32=True, lane=lane, join=join)
+                if sp is not None and join and not lane:
+                    sp.lists_joined = True
+                return
+            dense = self._desc(plan, name, src, out, 3, pad=(1, 1), out_f32=True, lane=lane)
+            dense.guard, dense.guard_value = sp.flag.data_ptr(), 1
+            plan.emit(OP_CONV, dense, name, list(src) + [sp.flag], out, flops=C.conv_flops(dense), lane=lane, join=join or not sp.lists_joined,
+                      io=(src, out, None))
+            sp.lists_joined = True
+            rows = self._desc(plan, name, src, out, 3, pad=(1, 1), out_f32=True, lane=lane)
+            rows.gather_rows, rows.gather_counts, rows.split_k = sp.rows.data_ptr(), sp.counts.data_ptr(), 1
+            rows.guard, rows.guard_value = sp.flag.data_ptr(), 0
+            # (flops 0: Plan.flops stays the reference graph's algorithmic count, which the dense launch above carries)
+            plan.emit(OP_CONV, rows, name, list(src) + [sp.rows, sp.counts, sp.flag], out, lane=lane, io=(src, out, None))
+            sp.dense.append(dense)
+            sp.gathered.append(rows)
 
         l_dim, l_cls = (1, 2) if opts.head_lanes else (0, 0)
         towers = {'cls': ('pyramid_classification', 256, 512, 'pyramid_classification', cls_o, 0, l_cls or opts.cls_lane),
                   'reg': ('pyramid_regression', 512, 0, 'pyramid_regression_ops', reg_o, 1, 0, bool(opts.cls_lane)),
                   'dim': ('pyramid_regression_dim', 128, 768, 'pyramid_regression_dim', dim_o, 0, l_dim)}
+        if opts.sparse_heads:
+            plan.sparse = SparseHeads(self.torch, self.device, P[0].B, [m.H * m.W for m in P], opts.sparse_heads)
+            plan.keep += plan.sparse.tensors()
         if opts.decode_overlap:
             tower(*towers['cls'])
-            decode(OP_DETECT_CANDIDATES, 'filtered_detections/candidates', lane=opts.cls_lane or 1)     # on the tower's lane when it has one
+            decode(OP_DETECT_CANDIDATE_PIXELS if plan.sparse else OP_DETECT_CANDIDATES, 'filtered_detections/candidates',
+                   lane=opts.cls_lane or 1)     # on the tower's lane when it has one
             tower(*towers['reg'])
             decode(OP_DETECT_SELECT, 'filtered_detections/select', lane=1, sync=True)
             tower(*towers['dim'])
@@ -1015,6 +1136,12 @@ class RetinaNet3D(object):
             # `plan_variants`); at batch 8 every launch fills the chip on its own (off)
             cls_lane=2 if (overlap and env('GPP_CLS_LANE', '1' if B <= 2 else '0') != '0') else 0,
             autotune=env('GPP_AUTOTUNE', '1') != '0',
+            # GPP_SPARSE_HEADS (default 1; needs the decode overlap, whose candidate lists exist before the regression tower): the output
+            # layers of the regression and dimension towers on the candidates' pixels only.  The value of the field is the largest share of
+            # all pyramid pixels the gathered launches take (GPP_SPARSE_HEADS_MAX_SHARE; beyond it the dense launches run: the device
+            # decides, per step); 0.0 = off.  An audit plan keeps the dense launches.
+            sparse_heads=(max(1e-9, float(env('GPP_SPARSE_HEADS_MAX_SHARE', SPARSE_HEADS_MAX_SHARE)))
+                          if (overlap and not self.audit and env('GPP_SPARSE_HEADS', '1') != '0') else 0.0),
             tune_key='x3split={};fuse={}/{};plan={}{}'.format(env('GPP_X3_SPLIT', '2'), env('GPP_FUSE_TAIL', '64,128'), env('GPP_FUSE_BLOCK', '64,128'),
                                                               self.plan_mode, C.latency_split_config() if self.plan_mode == 'latency' else '') +
                      (';audit' if self.audit else ''))
@@ -1143,6 +1270,14 @@ class RetinaNet3D(object):
         for index, (kind, _, desc, name, flops) in enumerate(plan.ops):
             if kind in DETECT_OPS or kind == OP_POLL:
                 continue
+            gathered = kind == OP_CONV and bool(desc.gather_rows)
+            if kind == OP_CONV and desc.guard:
+                # a guarded pair of the sparse head outputs: the dense launch is timed with the flag set, the gathered one with the flag
+                # clear on a synthetic list of every 8th pixel (a run's own lists do not exist yet: the decode ops are not run here)
+                plan.sparse.flag.fill_(0 if gathered else 1)
+                if gathered:
+                    plan.sparse.put_every_nth(self.torch)
+                    name = name + '@rows'
             self.run_op(plan, index)
             if kind not in (OP_CONV, OP_TAIL, OP_CONV_PREACT, OP_MOBILENET_BLOCK):
                 continue
@@ -1163,6 +1298,8 @@ class RetinaNet3D(object):
             setattr(target, field, self._tuned[key][0])
             plan.tuning[name] = self._tuned[key]
             plan.tuning_parts.setdefault(name, []).append(self._tuned[key])
+        if plan.sparse is not None:
+            plan.sparse.reset(self.torch)
         self.torch.cuda.synchronize()
         if fresh:
             self._save_tune_cache()
@@ -1290,6 +1427,7 @@ class RetinaNet3D(object):
     def run_plan(self, plan, events=None):
         """ Enqueue the whole forward on the current stream (asynchronous). """
         self._require_hip()
+        plan.heads_stale = plan.sparse is not None
         if events is None and getattr(plan, 'graph', None) is not None:
             plan.graph.replay()
             return
@@ -1309,6 +1447,7 @@ class RetinaNet3D(object):
         self.run_plan(plan)                      # warm-up outside the capture (one-time kernel attribute calls)
         torch.cuda.synchronize()
         graph = torch.cuda.CUDAGraph()
+        plan.heads_stale = plan.sparse is not None
         with torch.cuda.graph(graph):
             rc = hip.lib().gpp_plan_run(plan.array, len(plan.ops), hip.stream_ptr(), None, 0)
         hip.check(rc, 'gpp_plan_run (capture)')

@@ -191,6 +191,22 @@ typedef struct gpp_conv_desc {
     uint64_t* range_counter;        /* GPP_F16X3 only: device address of the 8-byte counter this launch adds its range events to (see
                                        gpp_x3_range_events below) -- a caller that runs several models or streams gives each plan a slot of
                                        its own and reads THAT (gpp_x3_range_snapshot_of); NULL = the library's per-device counter */
+    const int32_t* gather_rows;     /* NULL = the dense launch.  Otherwise the GATHERED-ROW form: GEMM row m of group g is not pixel m but pixel
+                                       list_g[m], and only gather_counts[g] rows exist.  list_g = gather_rows + batch * (pixels of the groups before g):
+                                       device int32, the pixel indices b * H_out * W_out + p of that group in ascending order, each at most once.
+                                       Every listed pixel receives exactly the bytes the dense launch stores there (same K order, same epilogue);
+                                       no other byte of the output map is written.  The grid is sized for every pixel; a workgroup whose first row
+                                       lies at or past the count returns at once.  Scope: stride 1, no residual, no split-K (split_k 0 or 1 and a
+                                       layer the split rule does not split: GPP_ERR_UNSUPPORTED otherwise), out_f32 output; every dtype.
+                                       tile_hint: 0, 6064064, 6032064, 6064160 (6000000 + BM * 1000 + BN: two-deep ring) or 7064064, 7032064,
+                                       7064160 (four-deep ring), all with the same bytes */
+    const int32_t* gather_counts;   /* device int32 [n_groups] (values outside [0, batch * H_out * W_out] are clamped into it) */
+    const int32_t* guard;           /* NULL = none.  Otherwise a device int32 every workgroup reads first: the launch does its work only while
+                                       *guard == guard_value and returns at once otherwise -- a launch that a value computed earlier on the
+                                       device switches off, without a host round trip.  gpp_conv2d_igemm only (dense or gathered; not the
+                                       weight-stationary tiles 4xxxxxx) */
+    int32_t guard_value;
+    int32_t reserved3;              /* must be 0 */
 } gpp_conv_desc;
 #define GPP_X3_IN 1
 #define GPP_X3_OUT 2
@@ -455,6 +471,26 @@ int gpp_detect_stages_f32(int stages, const float* cls_logits, const float* regr
                           int32_t* anchor_index, int32_t* counts,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* The pixels the decode will read: from the candidate keys of GPP_DETECT_CANDIDATES (still unsorted in `workspace`), per pyramid level the
+ * ascending list of the pixels b * level_pixels[l] + p that carry at least one candidate anchor (anchor a of an image lies on pixel
+ * a / num_base_anchors of the image's levels laid back to back).  The lists are what gpp_conv_desc.gather_rows / gather_counts take: the head
+ * output layers then run on those pixels only.  Built through one bit per pixel, so a list is a function of the candidate SET, not of the order
+ * the candidates' atomics arrived in.  Two small launches on `stream`.
+ *   workspace        the workspace of gpp_detect_stages_f32 / gpp_detect_osf_f32 after its candidate stage; lists_per_image 1 or 4 (osf)
+ *   level_pixels     H_l * W_l of every level, n_levels <= GPP_MAX_GROUPS, their sum * num_base_anchors == n_anchors
+ *   bitmap           uint32, sum over the levels of ceil(B * level_pixels[l] / 32) words; zero before the first call, left zero by every call
+ *   rows             int32 [B * sum(level_pixels)]: level l's list starts at B * (pixels of the levels before l)
+ *   counts           int32 [GPP_MAX_GROUPS + 1]: the length of every level's list, then their sum
+ *   flag             int32 [1]: 1 when the sum exceeds max_rows, else 0 (gpp_conv_desc.guard of the gathered and of the dense launch)
+ * Null pointer, bad size: GPP_ERR_BAD_ARG; nothing launched.  B == 0: GPP_OK. */
+typedef struct gpp_pixel_list_desc {
+    const void* workspace; uint32_t* bitmap; int32_t* rows; int32_t* counts; int32_t* flag;
+    int64_t n_anchors;
+    int32_t B, num_base_anchors, lists_per_image, n_levels, max_rows, reserved;
+    int32_t level_pixels[GPP_MAX_GROUPS]; int32_t reserved2;
+} gpp_pixel_list_desc;
+int gpp_detect_pixel_lists(const gpp_pixel_list_desc* host_desc, void* stream);
+
 /* orientation_specific_filter=True (layers/filter_detections.py:84-98, a non-default argument of models.load_model): threshold
  * and NMS once per orientation on that orientation's folded score, the four survivor lists concatenated in orientation
  * order, then the common top-k; an anchor may be reported once per orientation.  Same arguments as gpp_detect_f32; its own
@@ -661,6 +697,7 @@ int gpp_absmax_clear(uint32_t* table, int64_t n, void* stream);
 #define GPP_OP_STEM_RAGGED 37             /* gpp_ragged_stem_desc -> gpp_stem_conv7x7_bn_relu_ragged / _mfma_ragged / _x3_rc_ragged (by dtype, as GPP_OP_STEM) */
 #define GPP_OP_STEM_POOL_RAGGED 38        /* gpp_ragged_stem_desc with out = the pooled map -> gpp_stem_pool_fused_mfma_ragged / gpp_stem_pool_fused_x3_ragged */
 #define GPP_OP_MAXPOOL_RAGGED 39          /* gpp_ragged_pool_desc -> gpp_maxpool3x3s2_same_ragged */
+#define GPP_OP_DETECT_CANDIDATE_PIXELS 40  /* gpp_candidate_pixels_desc: GPP_OP_DETECT_CANDIDATES, then gpp_detect_pixel_lists on the same stream */
 /* (14, 15: the Winograd F(2, 3) form of the tower layers of round 5 -- built, measured at -2 % of the step, shelved in round 6:
    tools/experiments/winograd/) */
 /* Optional concurrency inside a plan: `kind | GPP_OP_LANE(l)` (l = 1, 2) enqueues the op on a library-owned side stream
@@ -706,6 +743,7 @@ typedef struct gpp_detect_desc {
     int32_t B, num_base_anchors, fused_layout, max_det;
     float score_thr, iou_thr;
 } gpp_detect_desc;
+typedef struct gpp_candidate_pixels_desc { const gpp_detect_desc* detect; gpp_pixel_list_desc lists; } gpp_candidate_pixels_desc;
 typedef struct gpp_poll_desc {
     const float* boxes; const float* dims; const int32_t* orient; const float* P_inv; const float* planes;
     float* keypoints; float* keyplanes; float* residuals; int32_t* best_idx; void* workspace;
