@@ -45,6 +45,8 @@ GPP_DRAW_COUNT_WORDS = 4
 GPP_POSE_COLS = 36         # float32 values per row of gpp_pose_f32 (include/gpp.h)
 GPP_EVAL_MAX_DETECTIONS, GPP_EVAL_MAX_ANNOTATIONS = 1024, 1024      # what gpp_eval_match_f32 takes per image (include/gpp.h)
 GPP_EVAL_ANN_COLS, GPP_EVAL_ERR_COLS = 17, 11
+GPP_KITTI_MAX_DETECTIONS, GPP_KITTI_MAX_LABELS = 128, 128           # what gpp_kitti_stats_f64 takes per image (include/gpp.h)
+GPP_KITTI_MAX_THRESHOLDS, GPP_KITTI_LABEL_COLS = 41, 16
 GPP_ABSMAX_F32, GPP_ABSMAX_SPLIT_F16, GPP_ABSMAX_SPLIT_BF16 = 1, 2, 3      # gpp_absmax_desc.layout (include/gpp.h)
 
 
@@ -135,6 +137,13 @@ def _declare(lib):
     if hasattr(lib, 'gpp_eval_match_f32'):
         lib.gpp_eval_match_f32.restype = c_int
         lib.gpp_eval_match_f32.argtypes = [c_void_p] * 8 + [c_int] * 4 + [c_float, c_int, ctypes.c_double] + [c_void_p] * 4
+    # KITTI's object benchmark (include/gpp.h, csrc/kitti_eval.hip; absent from an older build named by GPP_LIB: it runs everything but
+    # evaluate_kitti(device=True) and score_poses_on_frames)
+    if hasattr(lib, 'gpp_kitti_overlaps_f64'):
+        lib.gpp_kitti_overlaps_f64.restype = c_int
+        lib.gpp_kitti_overlaps_f64.argtypes = [c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 2
+        lib.gpp_kitti_stats_f64.restype = c_int
+        lib.gpp_kitti_stats_f64.argtypes = [c_void_p] * 4 + [ctypes.POINTER(ctypes.c_double)] + [c_void_p] * 2 + [c_int] * 4 + [c_void_p] * 5
     if hasattr(lib, 'gpp_detect_pixel_lists'):
         lib.gpp_detect_pixel_lists.restype = c_int
         lib.gpp_detect_pixel_lists.argtypes = [ctypes.POINTER(PixelListDesc), c_void_p]
@@ -356,6 +365,57 @@ def eval_match(boxes, dims, scores, labels, orientations, scales, annotations, a
                                    B, D, A, int(num_classes), float(score_threshold), int(max_detections), float(iou_threshold),
                                    ptr(table), ptr(errors), ptr(counts), stream_ptr()), 'gpp_eval_match_f32')
     return table, errors, counts
+
+
+def _kitti_check(rows, labels, label_counts, what):
+    import torch
+    if rows.dim() != 3 or labels.dim() != 3:
+        raise ValueError('{}: rows must be (B, D, {}) and labels (B, A, {}), got {} and {}'.format(
+            what, GPP_POSE_COLS, GPP_KITTI_LABEL_COLS, tuple(rows.shape), tuple(labels.shape)))
+    B, D, A = int(rows.shape[0]), int(rows.shape[1]), int(labels.shape[1])
+    want = ((rows, torch.float32, (B, D, GPP_POSE_COLS)), (labels, torch.float64, (B, A, GPP_KITTI_LABEL_COLS)), (label_counts, torch.int32, (B,)))
+    for t, dtype, shape in want:
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != rows.device:
+            raise ValueError('{}: expected {} {} on {}, got {} {} on {}'.format(what, shape, dtype, rows.device, tuple(t.shape), t.dtype, t.device))
+    return B, D, A
+
+
+def kitti_overlaps(rows, labels, label_counts):
+    """ gpp_kitti_overlaps_f64 on the current stream: rows (B, D, 36) float32 -- the rows of gpp_pose_f32 --, labels (B, A, 16) float64 and
+    label_counts (B,) int32 on the device -> overlaps (B, 4, D, A) float64 on the device (image IoU, BEV IoU, 3-D IoU, image intersection
+    over the detection's area); no synchronisation """
+    import torch
+    B, D, A = _kitti_check(rows, labels, label_counts, 'gpp_kitti_overlaps_f64')
+    overlaps = torch.empty((B, 4, D, A), dtype=torch.float64, device=rows.device)
+    check(lib().gpp_kitti_overlaps_f64(ptr(rows), ptr(labels), ptr(label_counts), B, D, A, ptr(overlaps), stream_ptr()), 'gpp_kitti_overlaps_f64')
+    return overlaps
+
+
+def kitti_stats(rows, labels, label_counts, overlaps, min_overlap, thresholds=None, n_thresholds=None):
+    """ gpp_kitti_stats_f64 on the current stream.  Without thresholds (pass 1): -> (tp_scores (B, 3, 3, A) float32, n_gt (B, 3, 3) int32).
+    With thresholds (3, 3, T) float32 and n_thresholds (3, 3) int32 on the device (pass 2): -> (stats (B, 3, 3, T, 3) int32,
+    similarity (B, 3, 3, T) float64).  Everything stays on the device; no synchronisation """
+    import torch
+    B, D, A = _kitti_check(rows, labels, label_counts, 'gpp_kitti_stats_f64')
+    if overlaps.dtype != torch.float64 or tuple(overlaps.shape) != (B, 4, D, A) or overlaps.device != rows.device:
+        raise ValueError('gpp_kitti_stats_f64: overlaps must be {} float64, got {} {}'.format((B, 4, D, A), tuple(overlaps.shape), overlaps.dtype))
+    mo = (ctypes.c_double * 3)(*[float(v) for v in min_overlap])
+    dev = rows.device
+    if thresholds is None:
+        tp_scores = torch.full((B, 3, 3, A), float('nan'), dtype=torch.float32, device=dev)
+        n_gt = torch.zeros((B, 3, 3), dtype=torch.int32, device=dev)
+        check(lib().gpp_kitti_stats_f64(ptr(rows), ptr(labels), ptr(label_counts), ptr(overlaps), mo, None, None, B, D, A, 0,
+                                        ptr(tp_scores), ptr(n_gt), None, None, stream_ptr()), 'gpp_kitti_stats_f64')
+        return tp_scores, n_gt
+    T = int(thresholds.shape[2])
+    if thresholds.dtype != torch.float32 or tuple(thresholds.shape) != (3, 3, T) or n_thresholds.dtype != torch.int32 or \
+            tuple(n_thresholds.shape) != (3, 3) or thresholds.device != dev or n_thresholds.device != dev:
+        raise ValueError('gpp_kitti_stats_f64: thresholds must be (3, 3, T) float32 and n_thresholds (3, 3) int32 on {}'.format(dev))
+    stats = torch.zeros((B, 3, 3, T, 3), dtype=torch.int32, device=dev)
+    similarity = torch.zeros((B, 3, 3, T), dtype=torch.float64, device=dev)
+    check(lib().gpp_kitti_stats_f64(ptr(rows), ptr(labels), ptr(label_counts), ptr(overlaps), mo, ptr(thresholds), ptr(n_thresholds),
+                                    B, D, A, T, None, None, ptr(stats), ptr(similarity), stream_ptr()), 'gpp_kitti_stats_f64')
+    return stats, similarity
 
 
 def channel_absmax(buf, M, C, pitch, c_off, layout, out, stream=None):

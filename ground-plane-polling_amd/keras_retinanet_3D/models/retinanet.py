@@ -1892,6 +1892,37 @@ class RetinaNet3D(object):
             out = self._twin.predict_poses_on_batch([plan.images, plan.P_inv, plan.planes], scale, shapes, heights=self._heights_of(plan))
         return out, scale
 
+    def score_poses_on_frames(self, frames_u8, P_inv, planes, labels):
+        """ predict_poses_on_frames + the overlaps of KITTI's object benchmark (csrc/kitti_eval.hip) without the
+        detour over the host: frames_u8 a (B, H, W, 3) uint8 BGR array or a list of frames of one height class, staged as
+        predict_poses_on_frames stages them; labels: per image the (n, 16) float64 rows of utils.kitti_eval.read_label_file (ORIGINAL
+        label_2 lines).  The overlap launch follows the plan on its stream and reads the rows where the plan left them; nothing but the
+        range watch's 8 bytes comes back.  Returns (chunk, scale): chunk a utils.kitti_eval.DeviceChunk -- this batch's rows (a copy: the
+        plan's buffer is overwritten by its next run), labels, counts and overlaps on the device -- for utils.kitti_eval.evaluate_chunks,
+        which runs the dataset-level passes over the chunks of all batches.  When an activation leaves the half range of dtype='f16x3'
+        the float32 twin answers the call, as it does for match_on_frames: the chunk then holds the twin's rows and their overlaps. """
+        self._require_pose()
+        from ..utils import kitti_eval
+        B = len(frames_u8)
+        if len(labels) != B:
+            raise ValueError('score_poses_on_frames: {} label arrays for {} frames'.format(len(labels), B))
+        if max([np.asarray(g).reshape(-1, kitti_eval.LABEL_COLS).shape[0] for g in labels] + [0]) > hip.GPP_KITTI_MAX_LABELS:
+            raise ValueError('score_poses_on_frames: an image has more than {} labels'.format(hip.GPP_KITTI_MAX_LABELS))
+        plan, scale = self.stage_frames(frames_u8, P_inv, planes)
+        shapes = [tuple(f.shape[:2]) for f in frames_u8] if isinstance(frames_u8, (list, tuple)) else tuple(frames_u8.shape[1:3])
+        self.put_frame_info(plan, scale, shapes)
+        self.run_plan(plan)
+        watch = self.watches_range()
+        snapshot = self.range_snapshot(plan) if watch else None
+        chunk = kitti_eval.upload_chunk(plan.pose_rows.clone(), labels, self.device)
+        event = watch and self.note_range(plan, int(snapshot.cpu().view(self.torch.int64).item()))
+        flagged = None if event else self._audit_flags(plan)
+        if event or flagged:
+            self._range_event_raise_or_prepare('score_poses_on_frames', flagged)        # (the preprocessed frames are still in the plan)
+            rows, _ = self._twin.predict_poses_on_batch([plan.images, plan.P_inv, plan.planes], scale, shapes, heights=self._heights_of(plan))
+            chunk = kitti_eval.upload_chunk(rows, labels, self.device)
+        return chunk, scale
+
     def predict_composites_on_frames(self, frames_u8, P_inv, planes, P_raw, score_threshold=0.4):
         """ predict_poses_on_frames + the pictures of bin/run_network.py --save-images, rendered on the device (csrc/draw.hip, DESIGN.md
         section 4.14): frames_u8 a (B, H, W, 3) uint8 array or a list of frames of one height class; P_raw (B, 3, 4) (or one (3, 4) for

@@ -107,6 +107,10 @@ class ShardedModel(object):
         sizes = [shard_range(B, r, world)[1] - shard_range(B, r, world)[0] for r in range(world)]
         return unpack_outputs(gather_detections(packed, sizes, self.group))
 
+    def score_poses_on_frames(self, *args, **kwargs):
+        raise ValueError('ShardedModel gathers the eight output arrays, not pose rows: KITTI scoring on the device runs through one '
+                         'rank\'s own model.score_poses_on_frames (utils/kitti_eval.py)')
+
     def _packed_shard(self, plan, n_local):
         """ this rank's (n_local, 100, 35) packed detections.  A dtype='f16x3' model watches the half range here as every synchronous call does
         (models/retinanet.py `on_range_event`): the counter rides behind the packed shard, is read BEFORE the shard goes on the wire, and a

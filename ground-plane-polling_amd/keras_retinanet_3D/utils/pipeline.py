@@ -52,6 +52,10 @@ class FramePipeline(object):
         from concurrent.futures import ThreadPoolExecutor
         self.pool = ThreadPoolExecutor(max_workers=1)
 
+    def score_poses_on_frames(self, *args, **kwargs):
+        raise ValueError('FramePipeline streams the eight output arrays, not pose rows: KITTI scoring on the device runs through the '
+                         'model\'s own score_poses_on_frames (utils/kitti_eval.py)')
+
     def _make_slots(self, frames, P_inv, planes):
         torch = self.torch
         dev = self.model.device

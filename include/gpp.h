@@ -585,6 +585,54 @@ int gpp_eval_match_f32(const float* boxes, const float* dims, const float* score
                        int max_detections, double iou_thr, int32_t* table, double* errors, int32_t* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * KITTI's object benchmark on the device (csrc/kitti_eval.hip; DESIGN.md section 4.17 is the specification, a restatement of the
+ * devkit's evaluate_object.cpp -- parity with the devkit itself is UNPINNED; utils/kitti_eval.py is the host form): AP of the image box,
+ * the bird's-eye-view (BEV) box and the 3-D box at Easy / Moderate / Hard, and AOS, of the rows of gpp_pose_f32 against label_2 rows.
+ * Two entry points: the overlaps of every (detection, label) pair once, then the matching of every image, called once without
+ * thresholds (pass 1: the true positives' scores, from which the host takes the 41 recall thresholds) and once with them (pass 2).
+ *
+ *   rows (B, D, GPP_POSE_COLS) float32, device: the rows of gpp_pose_f32.  A row is a detection iff its column 14 is >= 0; the columns of
+ *   the KITTI line are read: 12 score, 25 alpha, 26-29 box, 30 h, 17 w, 18 l, 19 x, 31 y, 21 z, 32 r_y.  Every detection is a Car.
+ *   labels (B, A, GPP_KITTI_LABEL_COLS) float64, device: column 0 the type code (0 Car, 1 Van, 2 DontCare, 3 anything else), columns
+ *   1-14 the numeric fields of a label_2 line (truncation, occlusion, alpha, box x1 y1 x2 y2, h w l, x y z, r_y), column 15 zero.
+ *   label_counts (B) int32, device: the rows of image b that count (clamped to [0, A]).  A == 0: labels and overlaps may be null.
+ *
+ * gpp_kitti_overlaps_f64: one thread per (detection, label) pair.
+ *   overlaps (B, 4, D, A) float64: plane 0 the image IoU (no "+1"; a non-positive width or height of the intersection: 0), plane 1 the
+ *   BEV IoU (the rectangle with corners (+-l/2, +-w/2) placed by X = cos(ry) x + sin(ry) z + tx, Z = -sin(ry) x + cos(ry) z + tz; the
+ *   intersection of the two quadrilaterals by Sutherland-Hodgman clipping, up to 8 vertices in LDS), plane 2 the 3-D IoU (BEV
+ *   intersection times max(0, min(y_d, y_g) - max(y_d - h_d, y_g - h_g)) over the union of the volumes), plane 3 the image intersection
+ *   over the detection's area (the DontCare form).  An overlap with a NaN operand is NaN (a pose row has NaN 3-D fields when its
+ *   keypoints are singular).  Entries of padding rows and of labels beyond the count are 0.  Positive sides are the contract.
+ *
+ * gpp_kitti_stats_f64: one workgroup per image, one thread per (metric, difficulty, threshold); metric 0 image, 1 BEV, 2 3-D;
+ * difficulty 0 Easy (box height >= 40, occlusion <= 0, truncation <= 0.15), 1 Moderate (25, 1, 0.30), 2 Hard (25, 2, 0.50).
+ *   min_overlap: 3 doubles on the HOST, one per metric (KITTI's Car: 0.7 each); a match needs overlap > min_overlap (strict).
+ *   thresholds (3, 3, T) float32 and n_thresholds (3, 3) int32, device -- or thresholds == null for pass 1 (T is then ignored but checked).
+ *   pass 1 writes tp_scores (B, 3, 3, A) float32 -- the score of the detection that label a takes as a true positive, NaN where it takes
+ *   none -- and n_gt (B, 3, 3) int32, the labels that count.  Each label takes the free detection of the highest score (the first of equals).
+ *   pass 2 writes stats (B, 3, 3, T, 3) int32 -- tp, fp, fn at threshold k; zeros for k >= n_thresholds -- and similarity (B, 3, 3, T)
+ *   float64, the sum of (1 + cos(alpha_gt - alpha_det)) / 2 over the true positives in label order (metric 0; 0 for the others).
+ *   Detections with score < threshold (float32 against float32) are out; each label takes the free detection of the largest overlap,
+ *   a detection too low for the difficulty only when nothing else offers; a label that does not count (a Van, a Car too hard for the
+ *   difficulty) or a too-low detection makes the pair neither tp nor fp; for metric 0 a left-over detection in a DontCare box is no fp.
+ *   The per-image outputs are summed by the host in image order: no floating-point atomics, the result is a function of the inputs.
+ *
+ *   D <= GPP_KITTI_MAX_DETECTIONS and A <= GPP_KITTI_MAX_LABELS (the assigned set is a 128-bit mask), beyond: GPP_ERR_UNSUPPORTED.
+ *   Null pointer, negative size, T > GPP_KITTI_MAX_THRESHOLDS: GPP_ERR_BAD_ARG, nothing launched.  B * D == 0: GPP_OK, nothing launched.
+ *   A == 0 or a count of 0: every detection above the threshold and high enough is an fp.
+ * ---------------------------------------------------------------------------------------- */
+#define GPP_KITTI_MAX_DETECTIONS 128
+#define GPP_KITTI_MAX_LABELS 128
+#define GPP_KITTI_MAX_THRESHOLDS 41
+#define GPP_KITTI_LABEL_COLS 16
+int gpp_kitti_overlaps_f64(const float* rows, const double* labels, const int32_t* label_counts, int B, int D, int A,
+                           double* overlaps, void* stream);
+int gpp_kitti_stats_f64(const float* rows, const double* labels, const int32_t* label_counts, const double* overlaps,
+                        const double* min_overlap, const float* thresholds, const int32_t* n_thresholds, int B, int D, int A, int T,
+                        float* tp_scores, int32_t* n_gt, int32_t* stats, double* similarity, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The --save-images composite on the device (csrc/draw.hip; DESIGN.md section 4.14 is the specification, utils/visualization.py its host
  * form): per image the 2-D picture (boxes, keypoint markers, score captions) over the 3-D picture (projected cuboids, residual captions),
  * from the rows of gpp_pose_f32 and the raw uint8 BGR frames.  Two launches on one stream: gpp_draw_build, then gpp_draw_raster.
