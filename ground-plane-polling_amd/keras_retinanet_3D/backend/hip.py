@@ -47,6 +47,7 @@ GPP_EVAL_MAX_DETECTIONS, GPP_EVAL_MAX_ANNOTATIONS = 1024, 1024      # what gpp_e
 GPP_EVAL_ANN_COLS, GPP_EVAL_ERR_COLS = 17, 11
 GPP_KITTI_MAX_DETECTIONS, GPP_KITTI_MAX_LABELS = 128, 128           # what gpp_kitti_stats_f64 takes per image (include/gpp.h)
 GPP_KITTI_MAX_THRESHOLDS, GPP_KITTI_LABEL_COLS = 41, 16
+GPP_LABEL_MOD_COLS = 20    # float64 values per row of gpp_label_prep_f64 (include/gpp.h)
 GPP_ABSMAX_F32, GPP_ABSMAX_SPLIT_F16, GPP_ABSMAX_SPLIT_BF16 = 1, 2, 3      # gpp_absmax_desc.layout (include/gpp.h)
 
 
@@ -144,6 +145,11 @@ def _declare(lib):
         lib.gpp_kitti_overlaps_f64.argtypes = [c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 2
         lib.gpp_kitti_stats_f64.restype = c_int
         lib.gpp_kitti_stats_f64.argtypes = [c_void_p] * 4 + [ctypes.POINTER(ctypes.c_double)] + [c_void_p] * 2 + [c_int] * 4 + [c_void_p] * 5
+    # the keypoint labels (include/gpp.h, csrc/label_prep.hip; absent from an older build named by GPP_LIB: it runs everything but
+    # prepare_device and polling_ceiling)
+    if hasattr(lib, 'gpp_label_prep_f64'):
+        lib.gpp_label_prep_f64.restype = c_int
+        lib.gpp_label_prep_f64.argtypes = [c_void_p] * 4 + [c_int, c_int, ctypes.c_uint, c_int] + [c_void_p] * 7
     if hasattr(lib, 'gpp_detect_pixel_lists'):
         lib.gpp_detect_pixel_lists.restype = c_int
         lib.gpp_detect_pixel_lists.argtypes = [ctypes.POINTER(PixelListDesc), c_void_p]
@@ -416,6 +422,33 @@ def kitti_stats(rows, labels, label_counts, overlaps, min_overlap, thresholds=No
     check(lib().gpp_kitti_stats_f64(ptr(rows), ptr(labels), ptr(label_counts), ptr(overlaps), mo, ptr(thresholds), ptr(n_thresholds),
                                     B, D, A, T, None, None, ptr(stats), ptr(similarity), stream_ptr()), 'gpp_kitti_stats_f64')
     return stats, similarity
+
+
+def label_prep(labels, label_counts, P, trig, det_types=0, own_box=True, detections=True):
+    """ gpp_label_prep_f64 on the current stream: labels (B, A, 16) float64, label_counts (B,) int32, P (B, 3, 4) float64 and trig (B, A, 2)
+    float64 (cos, sin of r_y, computed on the host) on the device -> (mod (B, A, 20) float64, and with `detections` the five arrays of the
+    decode's layout: boxes (B, A, 12), dims (B, A, 3), scores (B, A) float32, labels (B, A), orientations (B, A) int32 -- else None);
+    everything stays on the device, no synchronisation """
+    import torch
+    if labels.dim() != 3:
+        raise ValueError('gpp_label_prep_f64: labels must be (B, A, {}), got {}'.format(GPP_KITTI_LABEL_COLS, tuple(labels.shape)))
+    B, A = int(labels.shape[0]), int(labels.shape[1])
+    want = ((labels, torch.float64, (B, A, GPP_KITTI_LABEL_COLS)), (label_counts, torch.int32, (B,)), (P, torch.float64, (B, 3, 4)),
+            (trig, torch.float64, (B, A, 2)))
+    for t, dtype, shape in want:
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != labels.device:
+            raise ValueError('gpp_label_prep_f64: expected {} {} on {}, got {} {} on {}'.format(shape, dtype, labels.device, tuple(t.shape), t.dtype, t.device))
+    dev = labels.device
+    mod = torch.empty((B, A, GPP_LABEL_MOD_COLS), dtype=torch.float64, device=dev)
+    det = None
+    if detections:
+        det = (torch.empty((B, A, 12), dtype=torch.float32, device=dev), torch.empty((B, A, 3), dtype=torch.float32, device=dev),
+               torch.empty((B, A), dtype=torch.float32, device=dev), torch.empty((B, A), dtype=torch.int32, device=dev),
+               torch.empty((B, A), dtype=torch.int32, device=dev))
+    outs = [ptr(t) for t in det] if detections else [None] * 5
+    check(lib().gpp_label_prep_f64(ptr(labels), ptr(label_counts), ptr(P), ptr(trig), B, A, int(det_types), int(bool(own_box)), ptr(mod),
+                                   *(outs + [stream_ptr()])), 'gpp_label_prep_f64')
+    return mod, det
 
 
 def channel_absmax(buf, M, C, pitch, c_off, layout, out, stream=None):

@@ -34,7 +34,8 @@ _ROW_OF_FIELD = {3: 25, 4: 26, 5: 27, 6: 28, 7: 29, 8: 30, 9: 17, 10: 18, 11: 19
 
 
 # ---------------------------------------------------------------------------------------------------- files
-def _read_lines(path, what):
+def _read_lines(path, what, names=None):
+    """ the lines of a label or result file as (n, 16) rows; `names`: a list that receives the type name of every row (utils/label_prep.py) """
     out = []
     with open(path, 'r') as f:
         for n, line in enumerate(f):
@@ -45,6 +46,8 @@ def _read_lines(path, what):
                 raise ValueError('{}:{}: a {} line has 15 or 16 fields, got {}'.format(path, n + 1, what, len(fields)))
             row = np.zeros(LABEL_COLS, np.float64)
             row[0] = TYPE_CODES.get(fields[0], 3)
+            if names is not None:
+                names.append(fields[0])
             row[1:15] = [float(v) for v in fields[1:15]]
             row[15] = float(fields[15]) if len(fields) == 16 else np.nan
             out.append(row)

@@ -633,6 +633,48 @@ int gpp_kitti_stats_f64(const float* rows, const double* labels, const int32_t* 
                         float* tp_scores, int32_t* n_gt, int32_t* stats, double* similarity, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * KITTI keypoint ("mod") labels on the device (csrc/label_prep.hip; DESIGN.md section 4.18 is the specification, utils/label_prep.py the
+ * host form): what the reference's label_prep/create_mod_labels.m, computeBox3D.m and projectToImage.m make of a label_2 row and the
+ * camera-2 matrix -- the 20 fields that bin/evaluate.py and KittiGenerator read.  Parity with MATLAB itself is UNPINNED.  One launch,
+ * one thread per (image, label row), float64 with every operation separate.
+ *
+ *   labels (B, A, GPP_KITTI_LABEL_COLS) float64, label_counts (B) int32 (clamped to [0, A]), device: as gpp_kitti_overlaps_f64 takes
+ *   them -- one upload serves both.
+ *   P (B, 3, 4) float64, device: per image the camera-2 matrix at scale 1.
+ *   trig (B, A, 2) float64, device: cos(r_y) and sin(r_y) of every row, computed on the HOST for the host form and the device form alike
+ *   (device libm, glibc and MATLAB each round the last bit their own way).  The kernel is left with + - * /, minimum, maximum and
+ *   compares: its result equals the NumPy form bit for bit.
+ *
+ *   per row     the corners 1..8 of computeBox3D.m:22-24, X = c x + s z + t_x, Y = y + t_y, Z = -s x + c z + t_z.  Any Z < 0.1: the row is
+ *               DEMOTED.  Otherwise each corner is projected -- ((P_r0 X + P_r1 Y) + P_r2 Z) + P_r3 per row r, then u / w and v / w --,
+ *               deg = (180 / pi) alpha, the orientation class is 0 for deg in [0, 90), 1 for [90, 180), 2 for [-90, 0), 3 for [-180, -90),
+ *               the keypoints l m r t are the corners 3 2 1 6 | 2 1 4 5 | 4 3 2 7 | 1 4 3 8 of class 0 | 1 | 2 | 3 and the box is the
+ *               minimum / maximum over the eight projected corners, unclipped.
+ *               deg outside [-180, 180) (or NaN) is out of contract (the MATLAB script would reuse the previous object's variables): the
+ *               row is demoted here; the host reader raises ValueError.
+ *   mod (B, A, GPP_LABEL_MOD_COLS) float64:
+ *     column    a valid row                                   a demoted row
+ *      0        type code of the label                        2 (DontCare)
+ *      1 -  3   truncation, occlusion, alpha                  -1, -1, -10
+ *      4 -  7   the prepared box x1 y1 x2 y2                  the label's own box
+ *      8 - 15   xl yl xm ym xr yr xt yt                       -10000
+ *     16 - 18   h w l                                         h w l
+ *     19        orientation class                             -1
+ *     rows at or beyond the count: -1 in every column.
+ *   boxes (B, A, 12) dims (B, A, 3) scores (B, A) float32, det_labels / orientations (B, A) int32: ALL five or NONE (null).  The layout
+ *   gpp_detect_f32 leaves its outputs in, so that gpp_poll_f32 and gpp_pose_f32 read them in place (D = A).  Row a is a detection iff it
+ *   is valid and bit `type code` of det_types is set: then the box (own_box != 0: the label's own 2-D box, own_box == 0: the prepared
+ *   box), the keypoints and h w l, each double rounded to float32 once, score 1, label 0, its orientation class.  Every other row is
+ *   the -1 padding of gpp_detect_f32.
+ *
+ *   Null pointer (or some but not all of the five), negative size: GPP_ERR_BAD_ARG, nothing launched.  B * A == 0: GPP_OK, nothing launched.
+ * ---------------------------------------------------------------------------------------- */
+#define GPP_LABEL_MOD_COLS 20
+int gpp_label_prep_f64(const double* labels, const int32_t* label_counts, const double* P, const double* trig, int B, int A,
+                       unsigned det_types, int own_box, double* mod,
+                       float* boxes, float* dims, float* scores, int32_t* det_labels, int32_t* orientations, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The --save-images composite on the device (csrc/draw.hip; DESIGN.md section 4.14 is the specification, utils/visualization.py its host
  * form): per image the 2-D picture (boxes, keypoint markers, score captions) over the 3-D picture (projected cuboids, residual captions),
  * from the rows of gpp_pose_f32 and the raw uint8 BGR frames.  Two launches on one stream: gpp_draw_build, then gpp_draw_raster.
