@@ -1,0 +1,389 @@
+"""
+What a plan is: the ctypes mirrors of the descriptors of include/gpp.h (gpp_stem_desc ... gpp_plan_op), the op codes and flag bits of
+gpp_plan_op.kind, the plan switches, and the Plan a model records for one (batch, H, W, N planes) -- its buffers, descriptors and op
+array, who reads and writes what, and the race check over them -- with the host side of the range audit's table.  models/retinanet.py
+builds plans out of these and runs them; nothing here launches a network.
+"""
+
+import collections
+import ctypes
+
+import numpy as np
+
+from ..backend import hip
+from ..layers import conv as C
+
+
+class StemDesc(ctypes.Structure):
+    _fields_ = [('inp', ctypes.c_void_p), ('weight', ctypes.c_void_p), ('bias', ctypes.c_void_p), ('out', ctypes.c_void_p),
+                ('dtype', ctypes.c_int32), ('B', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('range_counter', ctypes.c_void_p)]
+
+
+class PoolDesc(ctypes.Structure):
+    _fields_ = [('inp', ctypes.c_void_p), ('out', ctypes.c_void_p), ('dtype', ctypes.c_int32), ('B', ctypes.c_int32),
+                ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('C', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
+class RaggedStemDesc(ctypes.Structure):
+    """ gpp_ragged_stem_desc (include/gpp.h): the stem of a batch of one height class; H of `stem` = the 4 Hp rows of the canvas """
+    _fields_ = [('stem', StemDesc), ('heights', ctypes.c_void_p), ('Hp', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
+class RaggedPoolDesc(ctypes.Structure):
+    """ gpp_ragged_pool_desc (include/gpp.h): pool1 behind a ragged stem; H of `pool` = the 2 Hp rows of the stored conv map """
+    _fields_ = [('pool', PoolDesc), ('heights', ctypes.c_void_p), ('Hp', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
+class ReluDesc(ctypes.Structure):
+    _fields_ = [('inp', ctypes.c_void_p), ('out', ctypes.c_void_p), ('in_bstride', ctypes.c_int64),
+                ('out_bstride', ctypes.c_int64), ('count', ctypes.c_int64), ('dtype', ctypes.c_int32), ('B', ctypes.c_int32)]
+
+
+class DetectDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ('cls_logits', 'regression', 'regression_dim', 'anchors', 'boxes', 'dims',
+                                               'scores', 'labels', 'orientations', 'anchor_index', 'counts', 'workspace')] + \
+               [('workspace_bytes', ctypes.c_size_t), ('n_anchors', ctypes.c_int64),
+                ('B', ctypes.c_int32), ('num_base_anchors', ctypes.c_int32), ('fused_layout', ctypes.c_int32),
+                ('max_det', ctypes.c_int32), ('score_thr', ctypes.c_float), ('iou_thr', ctypes.c_float)]
+
+
+class CandidatePixelsDesc(ctypes.Structure):
+    """ gpp_candidate_pixels_desc (include/gpp.h): the candidate pass of a DetectDesc, then the pixel lists of the gathered head output layers """
+    _fields_ = [('detect', ctypes.c_void_p), ('lists', hip.PixelListDesc)]
+
+
+class PollDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ('boxes', 'dims', 'orient', 'P_inv', 'planes', 'keypoints', 'keyplanes',
+                                               'residuals', 'best_idx', 'workspace')] + \
+               [('workspace_bytes', ctypes.c_size_t), ('B', ctypes.c_int32), ('D', ctypes.c_int32), ('N', ctypes.c_int32),
+                ('planes_batched', ctypes.c_int32), ('thr', ctypes.c_float), ('reserved', ctypes.c_int32)]
+
+
+class PoseDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ('boxes', 'dims', 'scores', 'labels', 'orientations', 'keypoints', 'residuals',
+                                               'frame_info', 'rows', 'counts')] + \
+               [('B', ctypes.c_int32), ('D', ctypes.c_int32), ('score_thr', ctypes.c_float), ('reserved', ctypes.c_int32)]
+
+
+class PreactDesc(ctypes.Structure):
+    _fields_ = [('conv', ctypes.c_void_p), ('in_scale', ctypes.c_void_p), ('in_shift', ctypes.c_void_p)]
+
+
+class DensePoolDesc(ctypes.Structure):
+    _fields_ = [('inp', ctypes.c_void_p), ('out', ctypes.c_void_p), ('B', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32),
+                ('C', ctypes.c_int32), ('pad', ctypes.c_int32), ('out_pitch', ctypes.c_int32)]
+
+
+class PlanOp(ctypes.Structure):
+    _fields_ = [('kind', ctypes.c_int32), ('tag', ctypes.c_int32), ('desc', ctypes.c_void_p)]
+
+
+class TailDesc(ctypes.Structure):
+    _fields_ = [('conv3x3', ctypes.c_void_p), ('conv1x1', ctypes.c_void_p), ('tile_rows', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
+class BlockDesc(ctypes.Structure):
+    _fields_ = [('conv1x1_a', ctypes.c_void_p), ('conv3x3_b', ctypes.c_void_p), ('conv1x1_c', ctypes.c_void_p), ('tile', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
+OP_STEM, OP_MAXPOOL, OP_CONV, OP_RELU, OP_DETECT, OP_POLL, OP_TAIL = 1, 2, 3, 4, 5, 6, 7
+OP_BLOCK = 16
+OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT = 8, 9, 10
+OP_DETECT_OSF = 12
+OP_STEM_POOL = 13
+OP_MAXPOOL_PAD, OP_AVGPOOL, OP_CONV_PREACT = 17, 18, 32         # DenseNet (include/gpp.h)
+OP_MOBILENET_STEM, OP_MOBILENET_BLOCK = 33, 34                  # MobileNet (include/gpp.h)
+OP_POSE = 19                                                    # RetinaNet3D(pose=True): gpp_pose_f32 behind the polling
+OP_ABSMAX, OP_ABSMAX_CLEAR = 35, 36                             # RetinaNet3D(range_audit=True): gpp_channel_absmax behind every audited map
+OP_STEM_RAGGED, OP_STEM_POOL_RAGGED, OP_MAXPOOL_RAGGED = 37, 38, 39    # ragged plans (plan_for(..., ragged=True)): per-image heights from a device table
+OP_DETECT_CANDIDATE_PIXELS = 40                                 # OP_DETECT_CANDIDATES + gpp_detect_pixel_lists (sparse head outputs)
+DETECT_OPS = (OP_DETECT, OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT, 12, OP_DETECT_CANDIDATE_PIXELS)
+OP_JOIN, OP_SYNC = 0x10000, 0x20000
+
+
+# the effective plan switches of one (model, batch), read from the GPP_* variables by RetinaNet3D._plan_options
+PlanOptions = collections.namedtuple('PlanOptions', 'x3_level fuse_stem_pool stage_chunks half_stages fuse_tail fuse_block fuse_block_proj '
+                                                    'br1_lane fpn_lanes p4_lane head_lanes decode_overlap cls_lane autotune tune_key sparse_heads')
+
+
+def block_form(opts, width, projection, split_input, halves, join):
+    """ how one bottleneck runs: (launch, shortcut).
+    launch: 'block' (branch2a + 2b + 2c + shortcut as one launch, gpp_bottleneck_block: pre-split input maps only), 'tail' (branch2a, then
+    2b + 2c as one launch, gpp_bottleneck_tail) or 'convs' (three launches).
+    shortcut: 'identity' (the block's input), 'side' (the projection on side lane 1, beside branch2a / 2b, joined by the launch that adds
+    it) or 'inline' (the projection on the block's own lane: GPP_BR1_LANE=0, half-batch stages, and the first block behind a split stage,
+    whose first launch joins the half-batch lanes). """
+    if width in opts.fuse_block and (not projection or opts.fuse_block_proj) and split_input:    # (res2a reads the pooled map: float32)
+        launch = 'block'
+    else:
+        launch = 'tail' if width in opts.fuse_tail else 'convs'
+    if not projection:
+        return launch, 'identity'
+    return launch, 'side' if opts.br1_lane and not halves and not join else 'inline'
+
+
+def part_of(fm, c0, nb):
+    """ images [c0, c0 + nb) of a map """
+    return C.FMap(fm.buf, nb, fm.H, fm.W, fm.C, off=fm.off + c0 * fm.bstride, bstride=fm.bstride, pitch=fm.pitch, split=fm.split, half=fm.half)
+
+
+# RetinaNet3D(range_audit=True): the fused first layer of the three towers writes one 896-channel map whose slices the towers read
+TOWER_SLICES = {('pyramid_towers_0', 0): 'pyramid_regression_0', ('pyramid_towers_0', 512): 'pyramid_classification_0',
+                ('pyramid_towers_0', 768): 'pyramid_regression_dim_0'}
+# the (hi, lo) IEEE-half pair is a fixed-point number with a quantum of 2^-24: a map whose LARGEST value is below
+# 2^-9 keeps fewer than 16 significant bits of it, i.e. the whole map is stored at bf16x3 grade or worse
+RANGE_AUDIT_THRESHOLD = 2.0 ** -9
+X3_QUANTUM = 2.0 ** -24
+# sparse head outputs: the share of listed rows up to which the gathered launches run (where their time crosses the dense launches')
+SPARSE_HEADS_MAX_SHARE = '0.5'
+
+
+def audit_report(maps, table, threshold=RANGE_AUDIT_THRESHOLD):
+    """ the host side of the range audit: maps = Plan.audit_maps (name, consumers, channels, row = (first word, words)), table = the
+    uint32 abs-max table of one run.  One record per map:
+      name, consumers, channels; live = channels whose maximum is not zero; absmax = the map's largest |x| (NaN when a channel holds one);
+      absmax_min_live / absmax_median_live over the live channels; small_channels = live channels whose maximum is below the threshold
+      (INFORMATION only: every sane model has some); bits = floor(log2(absmax / 2^-24)) capped at 22: how many bits the map's largest
+      value keeps in an IEEE-half pair; flagged = 0 < absmax < threshold -- the whole MAP sits in the fixed-point regime.  That is a
+      sufficient condition for damage, not a necessary one: a few tiny channels with huge weights inside a map of ordinary size are
+      reported (small_channels) and do not trigger.  A NaN maximum is the upper-range counter's business, not flagged here. """
+    table = np.ascontiguousarray(table).view(np.uint32).reshape(-1)
+    out = []
+    for m in maps:
+        first, n = m['row']
+        bits = table[first:first + n]
+        vals = bits.view(np.float32).astype(np.float64)
+        live = vals[bits != 0]
+        finite = live[~np.isnan(live)]
+        absmax = float('nan') if len(finite) < len(live) else float(finite.max()) if len(finite) else 0.0
+        rec = {k: m[k] for k in ('name', 'consumers', 'channels') if k in m}
+        rec.update({'live': int(len(live)), 'absmax': absmax,
+                    'absmax_min_live': float(finite.min()) if len(finite) else None,
+                    'absmax_median_live': float(np.median(finite)) if len(finite) else None,
+                    'small_channels': int((finite < threshold).sum()),
+                    'bits': None if not absmax > 0 else int(min(22, max(0, np.floor(np.log2(absmax / X3_QUANTUM))))) if np.isfinite(absmax) else 22,
+                    'flagged': bool(0 < absmax < threshold)})
+        out.append(rec)
+    return out
+
+
+class SparseHeads(object):
+    """ what the gathered head output layers of a plan share: the device lists gpp_detect_pixel_lists writes behind the candidate pass
+    (bitmap, rows, counts, flag), the guarded dense descriptors (Plan.complete_heads) and the gathered ones (the tuner) """
+
+    def __init__(self, torch, device, B, level_pixels, max_share):
+        i32 = torch.int32
+        self.B, self.level_pixels = B, [int(p) for p in level_pixels]
+        total = B * sum(self.level_pixels)
+        self.max_rows = max(0, min(total, int(max_share * total)))
+        self.bitmap = torch.zeros((sum((B * p + 31) // 32 for p in self.level_pixels),), dtype=i32, device=device)
+        self.rows = torch.zeros((total,), dtype=i32, device=device)
+        self.counts = torch.zeros((hip.GPP_MAX_GROUPS + 1,), dtype=i32, device=device)
+        # 1: more rows than max_rows are listed -- the dense launches run and the gathered ones return at once; 0: the other way round.
+        # 1 until a run's lists say otherwise, so that a single op run on its own (the per-layer tests) writes its whole map
+        self.flag = torch.ones((1,), dtype=i32, device=device)
+        self.dense, self.gathered = [], []
+        self.lists_joined = False
+
+    def tensors(self):
+        return [self.bitmap, self.rows, self.counts, self.flag]
+
+    def put_every_nth(self, torch, n=8):
+        """ a synthetic list for the tuner: every n-th pixel of every level """
+        begin, counts = 0, []
+        for p in self.level_pixels:
+            idx = torch.arange(0, self.B * p, n, dtype=torch.int32, device=self.rows.device)
+            self.rows[begin:begin + idx.numel()] = idx
+            counts.append(int(idx.numel()))
+            begin += self.B * p
+        counts += [0] * (hip.GPP_MAX_GROUPS - len(counts)) + [sum(counts)]
+        self.counts.copy_(torch.as_tensor(counts, dtype=torch.int32))
+
+    def reset(self, torch):
+        """ nothing listed, the dense launches run: the state before the first run """
+        self.counts.zero_()
+        self.flag.fill_(1)
+
+
+class Plan(object):
+    """ Everything one (batch, H, W, N planes) configuration needs: buffers, descriptors, op array. """
+
+    def __init__(self):
+        self.keep = []          # ctypes descriptors and torch buffers kept alive
+        self.io = {}            # conv op name -> (input FMaps, output FMaps, residual FMaps or None); half-batch plans: the LAST part
+        self.io_parts = {}      # conv op name -> [(inputs, outputs, residuals) of every launch under that name] (half-batch plans: two)
+        self.tuning_parts = {}  # conv op name -> [(tile, us) of every launch under that name]
+        self.ops = []           # (kind, tag, desc, name, flops)
+        self.oracle_names = {}  # fused ops: reference layer name of each output map (per-layer parity tests)
+        self.lanes = []         # per op: side-stream lane << 8 | join flag (include/gpp.h GPP_OP_LANE / GPP_OP_JOIN)
+        self.access = []        # per op: (byte intervals read, byte intervals written): check_stream_ordering
+        self.atomic = []        # per op: byte intervals it only updates with order-free atomics (the abs-max rows of an audit plan)
+        self.wrote = []         # per op: the FMaps among its writes; per op: its io record (audit plans: who produces, who reads a map)
+        self.op_io = []
+        self.audit_table = None     # RetinaNet3D(range_audit=True): see RetinaNet3D._audit
+        self.audit_maps = []
+        self.audit_unobserved = []
+        self.inner = {}         # id(descriptor) -> the gpp_conv_desc records a fused or pre-activation launch points to
+        self.open_lanes = set()  # side lanes forked and not joined by the ops recorded so far
+        self.conv_descs = []    # (gpp_conv_desc, stream lane): the split-K workspace of each lane is bound once every op is known
+        self.ws_need = {}       # stream lane -> the largest split-K workspace one of its conv descriptors needs
+        self.array = None
+        self.flops = 0.0
+        self.ragged = False     # plan_for(..., ragged=True): the plan of a height class; heights = its int32 device table, heights_host = what it holds
+        self.heights = None
+        self.sparse = None      # SparseHeads: the head output layers run on the candidates' pixels only (RetinaNet3D._heads)
+        self.heads_stale = False    # a run has left rows of regression / regression_dim unwritten: the next read of either completes them
+
+    # The two regression head tensors.  With sparse head outputs a run writes them at the pixels the decode reads and nowhere else; whoever
+    # reads a whole tensor (tests, bench.py --full, the CPU replay of the decode) gets it whole: the first read after such a run enqueues the
+    # two dense launches -- the descriptors a dense plan runs, on the current stream -- and the listed rows keep their bytes (a gathered row
+    # IS the dense row).  predict_on_batch, run_plan and fetch never come here.
+    @property
+    def regression(self):
+        self.complete_heads()
+        return self._regression
+
+    @regression.setter
+    def regression(self, tensor):
+        self._regression = tensor
+
+    @property
+    def regression_dim(self):
+        self.complete_heads()
+        return self._regression_dim
+
+    @regression_dim.setter
+    def regression_dim(self, tensor):
+        self._regression_dim = tensor
+
+    def complete_heads(self):
+        if self.sparse is None or not self.heads_stale:
+            return
+        self.heads_stale = False
+        for guarded in self.sparse.dense:
+            d = type(guarded).from_buffer_copy(guarded)       # the dense launch as it stands in the plan, without its guard
+            d.guard, d.guard_value = None, 0
+            hip.check(hip.lib().gpp_conv2d_igemm(ctypes.byref(d), hip.stream_ptr()), 'gpp_conv2d_igemm (head tensors completed)')
+
+    def emit(self, kind, desc, name, reads=(), writes=(), tag=0, flops=0.0, lane=0, join=False, sync=False, io=None, inner=(), atomic=()):
+        """ record one launch.  reads / writes: the FMaps and tensors it reads and writes (check_stream_ordering); io: its
+        (inputs, outputs, residuals) FMaps for the per-layer tests; inner: the conv descriptors its descriptor points to; atomic: what
+        it only updates with atomics whose result does not depend on their order (two such launches may run side by side) """
+        self.keep += list(inner) + [desc]
+        if inner:
+            self.inner[id(desc)] = tuple(inner)
+        self.ops.append((kind, tag, desc, name, flops))
+        self.lanes.append((int(lane) << 8) | (OP_JOIN if join else 0) | (OP_SYNC if sync else 0))
+        self.access.append((self.spans(reads), self.spans(writes)))
+        self.atomic.append(self.spans(atomic))
+        self.wrote.append([x for x in writes if isinstance(x, C.FMap)])
+        self.op_io.append(io)
+        self.flops += flops
+        if lane:
+            self.open_lanes.add(lane)
+        elif join:
+            self.open_lanes.clear()
+        if io is not None:
+            self.io[name] = io
+            self.io_parts.setdefault(name, []).append(io)
+
+    # ---- who reads and writes what: the byte intervals (one per image) every launch touches.  check_stream_ordering() replays
+    # gpp_plan_run's fork / join rules over them: the plan builder places launches on side streams by hand, and a missing join is
+    # a race that shows up once in a while, at full size only (round 4 found one between a split and an unsplit stage)
+    @staticmethod
+    def span(fm):
+        """ byte intervals of an FMap, one per image """
+        e = fm.buf.element_size()
+        base = fm.buf.data_ptr() + fm.off * e
+        size = ((fm.H * fm.W - 1) * fm.pitch + fm.C) * e
+        return [(base + b * fm.bstride * e, base + b * fm.bstride * e + size) for b in range(fm.B)]
+
+    @staticmethod
+    def span_of(tensor):
+        return [(tensor.data_ptr(), tensor.data_ptr() + tensor.numel() * tensor.element_size())]
+
+    @staticmethod
+    def spans(items):
+        """ byte intervals of a list of FMaps and tensors """
+        return [iv for x in items for iv in (Plan.span(x) if isinstance(x, C.FMap) else Plan.span_of(x))]
+
+    def insert_behind(self, extra):
+        """ extra: {position: [(kind, desc, name, FMaps read, tensors updated atomically)]}: records these launches directly behind the
+        op at that position, on its lane (no join, no fork of their own) -- the audit launches, placed once every reader of every map is known """
+        old = (self.ops, self.lanes, self.access, self.atomic, self.wrote, self.op_io)
+        self.ops, self.lanes, self.access, self.atomic, self.wrote, self.op_io = [], [], [], [], [], []
+        for pos, row in enumerate(zip(*old)):
+            for dst, item in zip((self.ops, self.lanes, self.access, self.atomic, self.wrote, self.op_io), row):
+                dst.append(item)
+            for kind, desc, name, reads, atomic in extra.get(pos, ()):
+                self.keep.append(desc)
+                self.ops.append((kind, 0, desc, name, 0.0))
+                self.lanes.append(row[1] & 0xff00)
+                self.access.append((self.spans(reads), []))
+                self.atomic.append(self.spans(atomic))
+                self.wrote.append([])
+                self.op_io.append(None)
+
+    def check_stream_ordering(self):
+        """ every pair of launches on DIFFERENT streams that touch overlapping bytes (at least one of them writing) must be ordered by a
+        fork or a join, as gpp_plan_run (csrc/plan.cpp) places them: a side-lane launch forks from the caller's stream when its lane is
+        not open (or carries SYNC); a JOIN launch on the caller's stream (and the end of the plan) closes every open lane.
+        Returns the list of violations [(earlier op, later op)], empty when the plan is race-free by construction. """
+        def overlap(a, b):
+            return any(x0 < y1 and y0 < x1 for x0, x1 in a for y0, y1 in b)
+        bad, seen = [], []                    # seen: (position, lane, name, reads, writes, atomic updates)
+        active = {}
+        forks, joins = {}, []                 # lane -> positions of its forks; positions of joins
+        for pos, (kind, _, desc, name, _) in enumerate(self.ops):
+            flags = self.lanes[pos]
+            lane, join, sync = (flags >> 8) & 0xff, bool(flags & OP_JOIN), bool(flags & OP_SYNC)
+            if lane > 0:
+                if not active.get(lane) or sync:
+                    forks.setdefault(lane, []).append(pos)
+                    active[lane] = True
+            elif join:
+                joins.append(pos)
+                active = {}
+            reads, writes = self.access[pos]
+            atomic = self.atomic[pos]
+            for p0, l0, n0, r0, w0, a0 in seen:
+                # (two order-free atomic updates of the same bytes do not conflict; an atomic update and a plain access do)
+                if l0 == lane or not (overlap(w0, reads) or overlap(w0, writes) or overlap(r0, writes) or overlap(a0, reads) or
+                                      overlap(a0, writes) or overlap(w0, atomic) or overlap(r0, atomic)):
+                    continue
+                j = [q for q in joins if p0 < q <= pos]                      # a join after the earlier launch, not after this one
+                if l0 == 0:
+                    ok = any(p0 < f <= pos for f in forks.get(lane, []))     # this lane forked after the main-stream launch
+                elif lane == 0:
+                    ok = bool(j)
+                else:
+                    ok = bool(j) and any(min(j) <= f <= pos for f in forks.get(lane, []))
+                if not ok:
+                    bad.append((n0, name))
+            seen.append((pos, lane, name, reads, writes, atomic))
+        return bad
+
+    @staticmethod
+    def stage_of(kind, name):
+        """ include/gpp.h GPP_OP_STAGE: 1 stem, 2 backbone, 3 FPN, 4 heads, 5 decode, 6 polling, 8 pose, 9 audit (roctx ranges under GPP_ROCTX=1) """
+        if kind in (OP_STEM, OP_MAXPOOL, OP_STEM_POOL, OP_MAXPOOL_PAD, OP_MOBILENET_STEM, OP_STEM_RAGGED, OP_STEM_POOL_RAGGED, OP_MAXPOOL_RAGGED):
+            return 1
+        if kind in DETECT_OPS:
+            return 5
+        if kind == OP_POLL:
+            return 6
+        if kind == OP_POSE:
+            return 8
+        if kind in (OP_ABSMAX, OP_ABSMAX_CLEAR):
+            return 9
+        if name.startswith('res') or kind in (OP_CONV_PREACT, OP_AVGPOOL, OP_MOBILENET_BLOCK) or name.startswith(('conv2_', 'conv3_', 'conv4_', 'conv5_')):
+            return 2
+        if name.startswith('pyramid_'):
+            return 4
+        return 3                                  # C5_reduced ... P3, P6, C6_relu, P7
+
+    def finalize(self):
+        arr = (PlanOp * len(self.ops))()
+        for i, (kind, tag, desc, name, _) in enumerate(self.ops):
+            arr[i].kind, arr[i].tag, arr[i].desc = kind | self.lanes[i] | (self.stage_of(kind, name) << 20), tag, ctypes.addressof(desc)
+        self.array = arr

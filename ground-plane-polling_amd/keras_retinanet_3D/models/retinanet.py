@@ -28,7 +28,6 @@ Every bit of a result is a function of (image, weights, dtype) alone: block tile
 a result, and split-K follows a rule of the layer alone (gpp_conv2d_split_rule) -- not of the batch size or the rank.
 """
 
-import collections
 import ctypes
 import json
 import os
@@ -42,381 +41,16 @@ from ..layers.filter_detections import MAX_DETECTIONS, NMS_THRESHOLD, SCORE_THRE
 from ..utils import anchors as anchor_utils
 from ..utils.gpp_utils import POLL_THRESHOLD, POSE_SCORE_THRESHOLD
 from . import weights as W
-
-
-class StemDesc(ctypes.Structure):
-    _fields_ = [('inp', ctypes.c_void_p), ('weight', ctypes.c_void_p), ('bias', ctypes.c_void_p), ('out', ctypes.c_void_p),
-                ('dtype', ctypes.c_int32), ('B', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('range_counter', ctypes.c_void_p)]
-
-
-class PoolDesc(ctypes.Structure):
-    _fields_ = [('inp', ctypes.c_void_p), ('out', ctypes.c_void_p), ('dtype', ctypes.c_int32), ('B', ctypes.c_int32),
-                ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('C', ctypes.c_int32), ('reserved', ctypes.c_int32)]
-
-
-class RaggedStemDesc(ctypes.Structure):
-    """ gpp_ragged_stem_desc (include/gpp.h): the stem of a batch of one height class; H of `stem` = the 4 Hp rows of the canvas """
-    _fields_ = [('stem', StemDesc), ('heights', ctypes.c_void_p), ('Hp', ctypes.c_int32), ('reserved', ctypes.c_int32)]
-
-
-class RaggedPoolDesc(ctypes.Structure):
-    """ gpp_ragged_pool_desc (include/gpp.h): pool1 behind a ragged stem; H of `pool` = the 2 Hp rows of the stored conv map """
-    _fields_ = [('pool', PoolDesc), ('heights', ctypes.c_void_p), ('Hp', ctypes.c_int32), ('reserved', ctypes.c_int32)]
-
-
-class ReluDesc(ctypes.Structure):
-    _fields_ = [('inp', ctypes.c_void_p), ('out', ctypes.c_void_p), ('in_bstride', ctypes.c_int64),
-                ('out_bstride', ctypes.c_int64), ('count', ctypes.c_int64), ('dtype', ctypes.c_int32), ('B', ctypes.c_int32)]
-
-
-class DetectDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in ('cls_logits', 'regression', 'regression_dim', 'anchors', 'boxes', 'dims',
-                                               'scores', 'labels', 'orientations', 'anchor_index', 'counts', 'workspace')] + \
-               [('workspace_bytes', ctypes.c_size_t), ('n_anchors', ctypes.c_int64),
-                ('B', ctypes.c_int32), ('num_base_anchors', ctypes.c_int32), ('fused_layout', ctypes.c_int32),
-                ('max_det', ctypes.c_int32), ('score_thr', ctypes.c_float), ('iou_thr', ctypes.c_float)]
-
-
-class CandidatePixelsDesc(ctypes.Structure):
-    """ gpp_candidate_pixels_desc (include/gpp.h): the candidate pass of a DetectDesc, then the pixel lists of the gathered head output layers """
-    _fields_ = [('detect', ctypes.c_void_p), ('lists', hip.PixelListDesc)]
-
-
-class PollDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in ('boxes', 'dims', 'orient', 'P_inv', 'planes', 'keypoints', 'keyplanes',
-                                               'residuals', 'best_idx', 'workspace')] + \
-               [('workspace_bytes', ctypes.c_size_t), ('B', ctypes.c_int32), ('D', ctypes.c_int32), ('N', ctypes.c_int32),
-                ('planes_batched', ctypes.c_int32), ('thr', ctypes.c_float), ('reserved', ctypes.c_int32)]
-
-
-class PoseDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_void_p) for n in ('boxes', 'dims', 'scores', 'labels', 'orientations', 'keypoints', 'residuals',
-                                               'frame_info', 'rows', 'counts')] + \
-               [('B', ctypes.c_int32), ('D', ctypes.c_int32), ('score_thr', ctypes.c_float), ('reserved', ctypes.c_int32)]
-
-
-class PreactDesc(ctypes.Structure):
-    _fields_ = [('conv', ctypes.c_void_p), ('in_scale', ctypes.c_void_p), ('in_shift', ctypes.c_void_p)]
-
-
-class DensePoolDesc(ctypes.Structure):
-    _fields_ = [('inp', ctypes.c_void_p), ('out', ctypes.c_void_p), ('B', ctypes.c_int32), ('H', ctypes.c_int32), ('W', ctypes.c_int32),
-                ('C', ctypes.c_int32), ('pad', ctypes.c_int32), ('out_pitch', ctypes.c_int32)]
-
-
-class PlanOp(ctypes.Structure):
-    _fields_ = [('kind', ctypes.c_int32), ('tag', ctypes.c_int32), ('desc', ctypes.c_void_p)]
-
-
-class TailDesc(ctypes.Structure):
-    _fields_ = [('conv3x3', ctypes.c_void_p), ('conv1x1', ctypes.c_void_p), ('tile_rows', ctypes.c_int32), ('reserved', ctypes.c_int32)]
-
-
-class BlockDesc(ctypes.Structure):
-    _fields_ = [('conv1x1_a', ctypes.c_void_p), ('conv3x3_b', ctypes.c_void_p), ('conv1x1_c', ctypes.c_void_p), ('tile', ctypes.c_int32), ('reserved', ctypes.c_int32)]
-
-
-OP_STEM, OP_MAXPOOL, OP_CONV, OP_RELU, OP_DETECT, OP_POLL, OP_TAIL = 1, 2, 3, 4, 5, 6, 7
-OP_BLOCK = 16
-OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT = 8, 9, 10
-OP_DETECT_OSF = 12
-OP_STEM_POOL = 13
-OP_MAXPOOL_PAD, OP_AVGPOOL, OP_CONV_PREACT = 17, 18, 32         # DenseNet (include/gpp.h)
-OP_MOBILENET_STEM, OP_MOBILENET_BLOCK = 33, 34                  # MobileNet (include/gpp.h)
-OP_POSE = 19                                                    # RetinaNet3D(pose=True): gpp_pose_f32 behind the polling
-OP_ABSMAX, OP_ABSMAX_CLEAR = 35, 36                             # RetinaNet3D(range_audit=True): gpp_channel_absmax behind every audited map
-OP_STEM_RAGGED, OP_STEM_POOL_RAGGED, OP_MAXPOOL_RAGGED = 37, 38, 39    # ragged plans (plan_for(..., ragged=True)): per-image heights from a device table
-OP_DETECT_CANDIDATE_PIXELS = 40                                 # OP_DETECT_CANDIDATES + gpp_detect_pixel_lists (sparse head outputs)
-DETECT_OPS = (OP_DETECT, OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT, 12, OP_DETECT_CANDIDATE_PIXELS)
-OP_JOIN, OP_SYNC = 0x10000, 0x20000
-
-
-# the effective plan switches of one (model, batch), read from the GPP_* variables by RetinaNet3D._plan_options
-PlanOptions = collections.namedtuple('PlanOptions', 'x3_level fuse_stem_pool stage_chunks half_stages fuse_tail fuse_block fuse_block_proj '
-                                                    'br1_lane fpn_lanes p4_lane head_lanes decode_overlap cls_lane autotune tune_key sparse_heads')
-
-
-def block_form(opts, width, projection, split_input, halves, join):
-    """ how one bottleneck runs: (launch, shortcut).
-    launch: 'block' (branch2a + 2b + 2c + shortcut as one launch, gpp_bottleneck_block: pre-split input maps only), 'tail' (branch2a, then
-    2b + 2c as one launch, gpp_bottleneck_tail) or 'convs' (three launches).
-    shortcut: 'identity' (the block's input), 'side' (the projection on side lane 1, beside branch2a / 2b, joined by the launch that adds
-    it) or 'inline' (the projection on the block's own lane: GPP_BR1_LANE=0, half-batch stages, and the first block behind a split stage,
-    whose first launch joins the half-batch lanes). """
-    if width in opts.fuse_block and (not projection or opts.fuse_block_proj) and split_input:    # (res2a reads the pooled map: float32)
-        launch = 'block'
-    else:
-        launch = 'tail' if width in opts.fuse_tail else 'convs'
-    if not projection:
-        return launch, 'identity'
-    return launch, 'side' if opts.br1_lane and not halves and not join else 'inline'
-
-
-def part_of(fm, c0, nb):
-    """ images [c0, c0 + nb) of a map """
-    return C.FMap(fm.buf, nb, fm.H, fm.W, fm.C, off=fm.off + c0 * fm.bstride, bstride=fm.bstride, pitch=fm.pitch, split=fm.split, half=fm.half)
-
-
-# RetinaNet3D(range_audit=True): the fused first layer of the three towers writes one 896-channel map whose slices the towers read
-TOWER_SLICES = {('pyramid_towers_0', 0): 'pyramid_regression_0', ('pyramid_towers_0', 512): 'pyramid_classification_0',
-                ('pyramid_towers_0', 768): 'pyramid_regression_dim_0'}
-# the (hi, lo) IEEE-half pair is a fixed-point number with a quantum of 2^-24 (DESIGN.md section 3): a map whose LARGEST value is below
-# 2^-9 keeps fewer than 16 significant bits of it, i.e. the whole map is stored at bf16x3 grade or worse (DESIGN.md section 4.12)
-RANGE_AUDIT_THRESHOLD = 2.0 ** -9
-X3_QUANTUM = 2.0 ** -24
-# sparse head outputs: the share of listed rows up to which the gathered launches run (DESIGN.md section 4.16: where their time crosses the dense launches')
-SPARSE_HEADS_MAX_SHARE = '0.5'
-
-
-def audit_report(maps, table, threshold=RANGE_AUDIT_THRESHOLD):
-    """ the host side of the range audit: maps = Plan.audit_maps (name, consumers, channels, row = (first word, words)), table = the
-    uint32 abs-max table of one run.  One record per map:
-      name, consumers, channels; live = channels whose maximum is not zero; absmax = the map's largest |x| (NaN when a channel holds one);
-      absmax_min_live / absmax_median_live over the live channels; small_channels = live channels whose maximum is below the threshold
-      (INFORMATION only: every sane model has some); bits = floor(log2(absmax / 2^-24)) capped at 22: how many bits the map's largest
-      value keeps in an IEEE-half pair; flagged = 0 < absmax < threshold -- the whole MAP sits in the fixed-point regime.  That is a
-      sufficient condition for damage, not a necessary one: a few tiny channels with huge weights inside a map of ordinary size are
-      reported (small_channels) and do not trigger.  A NaN maximum is the upper-range counter's business, not flagged here. """
-    table = np.ascontiguousarray(table).view(np.uint32).reshape(-1)
-    out = []
-    for m in maps:
-        first, n = m['row']
-        bits = table[first:first + n]
-        vals = bits.view(np.float32).astype(np.float64)
-        live = vals[bits != 0]
-        finite = live[~np.isnan(live)]
-        absmax = float('nan') if len(finite) < len(live) else float(finite.max()) if len(finite) else 0.0
-        rec = {k: m[k] for k in ('name', 'consumers', 'channels') if k in m}
-        rec.update({'live': int(len(live)), 'absmax': absmax,
-                    'absmax_min_live': float(finite.min()) if len(finite) else None,
-                    'absmax_median_live': float(np.median(finite)) if len(finite) else None,
-                    'small_channels': int((finite < threshold).sum()),
-                    'bits': None if not absmax > 0 else int(min(22, max(0, np.floor(np.log2(absmax / X3_QUANTUM))))) if np.isfinite(absmax) else 22,
-                    'flagged': bool(0 < absmax < threshold)})
-        out.append(rec)
-    return out
-
-
-class SparseHeads(object):
-    """ what the gathered head output layers of a plan share: the device lists gpp_detect_pixel_lists writes behind the candidate pass
-    (bitmap, rows, counts, flag), the guarded dense descriptors (Plan.complete_heads) and the gathered ones (the tuner) """
-
-    def __init__(self, torch, device, B, level_pixels, max_share):
-        i32 = torch.int32
-        self.B, self.level_pixels = B, [int(p) for p in level_pixels]
-        total = B * sum(self.level_pixels)
-        self.max_rows = max(0, min(total, int(max_share * total)))
-        self.bitmap = torch.zeros((sum((B * p + 31) // 32 for p in self.level_pixels),), dtype=i32, device=device)
-        self.rows = torch.zeros((total,), dtype=i32, device=device)
-        self.counts = torch.zeros((hip.GPP_MAX_GROUPS + 1,), dtype=i32, device=device)
-        # 1: more rows than max_rows are listed -- the dense launches run and the gathered ones return at once; 0: the other way round.
-        # 1 until a run's lists say otherwise, so that a single op run on its own (the per-layer tests) writes its whole map
-        self.flag = torch.ones((1,), dtype=i32, device=device)
-        self.dense, self.gathered = [], []
-        self.lists_joined = False
-
-    def tensors(self):
-        return [self.bitmap, self.rows, self.counts, self.flag]
-
-    def put_every_nth(self, torch, n=8):
-        """ a synthetic list for the tuner: every n-th pixel of every level """
-        begin, counts = 0, []
-        for p in self.level_pixels:
-            idx = torch.arange(0, self.B * p, n, dtype=torch.int32, device=self.rows.device)
-            self.rows[begin:begin + idx.numel()] = idx
-            counts.append(int(idx.numel()))
-            begin += self.B * p
-        counts += [0] * (hip.GPP_MAX_GROUPS - len(counts)) + [sum(counts)]
-        self.counts.copy_(torch.as_tensor(counts, dtype=torch.int32))
-
-    def reset(self, torch):
-        """ nothing listed, the dense launches run: the state before the first run """
-        self.counts.zero_()
-        self.flag.fill_(1)
-
-
-class Plan(object):
-    """ Everything one (batch, H, W, N planes) configuration needs: buffers, descriptors, op array. """
-
-    def __init__(self):
-        self.keep = []          # ctypes descriptors and torch buffers kept alive
-        self.io = {}            # conv op name -> (input FMaps, output FMaps, residual FMaps or None); half-batch plans: the LAST part
-        self.io_parts = {}      # conv op name -> [(inputs, outputs, residuals) of every launch under that name] (half-batch plans: two)
-        self.tuning_parts = {}  # conv op name -> [(tile, us) of every launch under that name]
-        self.ops = []           # (kind, tag, desc, name, flops)
-        self.oracle_names = {}  # fused ops: reference layer name of each output map (per-layer parity tests)
-        self.lanes = []         # per op: side-stream lane << 8 | join flag (include/gpp.h GPP_OP_LANE / GPP_OP_JOIN)
-        self.access = []        # per op: (byte intervals read, byte intervals written): check_stream_ordering
-        self.atomic = []        # per op: byte intervals it only updates with order-free atomics (the abs-max rows of an audit plan)
-        self.wrote = []         # per op: the FMaps among its writes; per op: its io record (audit plans: who produces, who reads a map)
-        self.op_io = []
-        self.audit_table = None     # RetinaNet3D(range_audit=True): see RetinaNet3D._audit
-        self.audit_maps = []
-        self.audit_unobserved = []
-        self.inner = {}         # id(descriptor) -> the gpp_conv_desc records a fused or pre-activation launch points to
-        self.open_lanes = set()  # side lanes forked and not joined by the ops recorded so far
-        self.conv_descs = []    # (gpp_conv_desc, stream lane): the split-K workspace of each lane is bound once every op is known
-        self.ws_need = {}       # stream lane -> the largest split-K workspace one of its conv descriptors needs
-        self.array = None
-        self.flops = 0.0
-        self.ragged = False     # plan_for(..., ragged=True): the plan of a height class; heights = its int32 device table, heights_host = what it holds
-        self.heights = None
-        self.sparse = None      # SparseHeads: the head output layers run on the candidates' pixels only (RetinaNet3D._heads)
-        self.heads_stale = False    # a run has left rows of regression / regression_dim unwritten: the next read of either completes them
-
-    # The two regression head tensors.  With sparse head outputs a run writes them at the pixels the decode reads and nowhere else; whoever
-    # reads a whole tensor (tests, bench.py --full, the CPU replay of the decode) gets it whole: the first read after such a run enqueues the
-    # two dense launches -- the descriptors a dense plan runs, on the current stream -- and the listed rows keep their bytes (a gathered row
-    # IS the dense row).  predict_on_batch, run_plan and fetch never come here.
-    @property
-    def regression(self):
-        self.complete_heads()
-        return self._regression
-
-    @regression.setter
-    def regression(self, tensor):
-        self._regression = tensor
-
-    @property
-    def regression_dim(self):
-        self.complete_heads()
-        return self._regression_dim
-
-    @regression_dim.setter
-    def regression_dim(self, tensor):
-        self._regression_dim = tensor
-
-    def complete_heads(self):
-        if self.sparse is None or not self.heads_stale:
-            return
-        self.heads_stale = False
-        for guarded in self.sparse.dense:
-            d = type(guarded).from_buffer_copy(guarded)       # the dense launch as it stands in the plan, without its guard
-            d.guard, d.guard_value = None, 0
-            hip.check(hip.lib().gpp_conv2d_igemm(ctypes.byref(d), hip.stream_ptr()), 'gpp_conv2d_igemm (head tensors completed)')
-
-    def emit(self, kind, desc, name, reads=(), writes=(), tag=0, flops=0.0, lane=0, join=False, sync=False, io=None, inner=(), atomic=()):
-        """ record one launch.  reads / writes: the FMaps and tensors it reads and writes (check_stream_ordering); io: its
-        (inputs, outputs, residuals) FMaps for the per-layer tests; inner: the conv descriptors its descriptor points to; atomic: what
-        it only updates with atomics whose result does not depend on their order (two such launches may run side by side) """
-        self.keep += list(inner) + [desc]
-        if inner:
-            self.inner[id(desc)] = tuple(inner)
-        self.ops.append((kind, tag, desc, name, flops))
-        self.lanes.append((int(lane) << 8) | (OP_JOIN if join else 0) | (OP_SYNC if sync else 0))
-        self.access.append((self.spans(reads), self.spans(writes)))
-        self.atomic.append(self.spans(atomic))
-        self.wrote.append([x for x in writes if isinstance(x, C.FMap)])
-        self.op_io.append(io)
-        self.flops += flops
-        if lane:
-            self.open_lanes.add(lane)
-        elif join:
-            self.open_lanes.clear()
-        if io is not None:
-            self.io[name] = io
-            self.io_parts.setdefault(name, []).append(io)
-
-    # ---- who reads and writes what: the byte intervals (one per image) every launch touches.  check_stream_ordering() replays
-    # gpp_plan_run's fork / join rules over them: the plan builder places launches on side streams by hand, and a missing join is
-    # a race that shows up once in a while, at full size only (round 4 found one between a split and an unsplit stage)
-    @staticmethod
-    def span(fm):
-        """ byte intervals of an FMap, one per image """
-        e = fm.buf.element_size()
-        base = fm.buf.data_ptr() + fm.off * e
-        size = ((fm.H * fm.W - 1) * fm.pitch + fm.C) * e
-        return [(base + b * fm.bstride * e, base + b * fm.bstride * e + size) for b in range(fm.B)]
-
-    @staticmethod
-    def span_of(tensor):
-        return [(tensor.data_ptr(), tensor.data_ptr() + tensor.numel() * tensor.element_size())]
-
-    @staticmethod
-    def spans(items):
-        """ byte intervals of a list of FMaps and tensors """
-        return [iv for x in items for iv in (Plan.span(x) if isinstance(x, C.FMap) else Plan.span_of(x))]
-
-    def insert_behind(self, extra):
-        """ extra: {position: [(kind, desc, name, FMaps read, tensors updated atomically)]}: records these launches directly behind the
-        op at that position, on its lane (no join, no fork of their own) -- the audit launches, placed once every reader of every map is known """
-        old = (self.ops, self.lanes, self.access, self.atomic, self.wrote, self.op_io)
-        self.ops, self.lanes, self.access, self.atomic, self.wrote, self.op_io = [], [], [], [], [], []
-        for pos, row in enumerate(zip(*old)):
-            for dst, item in zip((self.ops, self.lanes, self.access, self.atomic, self.wrote, self.op_io), row):
-                dst.append(item)
-            for kind, desc, name, reads, atomic in extra.get(pos, ()):
-                self.keep.append(desc)
-                self.ops.append((kind, 0, desc, name, 0.0))
-                self.lanes.append(row[1] & 0xff00)
-                self.access.append((self.spans(reads), []))
-                self.atomic.append(self.spans(atomic))
-                self.wrote.append([])
-                self.op_io.append(None)
-
-    def check_stream_ordering(self):
-        """ every pair of launches on DIFFERENT streams that touch overlapping bytes (at least one of them writing) must be ordered by a
-        fork or a join, as gpp_plan_run (csrc/plan.cpp) places them: a side-lane launch forks from the caller's stream when its lane is
-        not open (or carries SYNC); a JOIN launch on the caller's stream (and the end of the plan) closes every open lane.
-        Returns the list of violations [(earlier op, later op)], empty when the plan is race-free by construction. """
-        def overlap(a, b):
-            return any(x0 < y1 and y0 < x1 for x0, x1 in a for y0, y1 in b)
-        bad, seen = [], []                    # seen: (position, lane, name, reads, writes, atomic updates)
-        active = {}
-        forks, joins = {}, []                 # lane -> positions of its forks; positions of joins
-        for pos, (kind, _, desc, name, _) in enumerate(self.ops):
-            flags = self.lanes[pos]
-            lane, join, sync = (flags >> 8) & 0xff, bool(flags & OP_JOIN), bool(flags & OP_SYNC)
-            if lane > 0:
-                if not active.get(lane) or sync:
-                    forks.setdefault(lane, []).append(pos)
-                    active[lane] = True
-            elif join:
-                joins.append(pos)
-                active = {}
-            reads, writes = self.access[pos]
-            atomic = self.atomic[pos]
-            for p0, l0, n0, r0, w0, a0 in seen:
-                # (two order-free atomic updates of the same bytes do not conflict; an atomic update and a plain access do)
-                if l0 == lane or not (overlap(w0, reads) or overlap(w0, writes) or overlap(r0, writes) or overlap(a0, reads) or
-                                      overlap(a0, writes) or overlap(w0, atomic) or overlap(r0, atomic)):
-                    continue
-                j = [q for q in joins if p0 < q <= pos]                      # a join after the earlier launch, not after this one
-                if l0 == 0:
-                    ok = any(p0 < f <= pos for f in forks.get(lane, []))     # this lane forked after the main-stream launch
-                elif lane == 0:
-                    ok = bool(j)
-                else:
-                    ok = bool(j) and any(min(j) <= f <= pos for f in forks.get(lane, []))
-                if not ok:
-                    bad.append((n0, name))
-            seen.append((pos, lane, name, reads, writes, atomic))
-        return bad
-
-    @staticmethod
-    def stage_of(kind, name):
-        """ include/gpp.h GPP_OP_STAGE: 1 stem, 2 backbone, 3 FPN, 4 heads, 5 decode, 6 polling, 8 pose, 9 audit (roctx ranges under GPP_ROCTX=1) """
-        if kind in (OP_STEM, OP_MAXPOOL, OP_STEM_POOL, OP_MAXPOOL_PAD, OP_MOBILENET_STEM, OP_STEM_RAGGED, OP_STEM_POOL_RAGGED, OP_MAXPOOL_RAGGED):
-            return 1
-        if kind in DETECT_OPS:
-            return 5
-        if kind == OP_POLL:
-            return 6
-        if kind == OP_POSE:
-            return 8
-        if kind in (OP_ABSMAX, OP_ABSMAX_CLEAR):
-            return 9
-        if name.startswith('res') or kind in (OP_CONV_PREACT, OP_AVGPOOL, OP_MOBILENET_BLOCK) or name.startswith(('conv2_', 'conv3_', 'conv4_', 'conv5_')):
-            return 2
-        if name.startswith('pyramid_'):
-            return 4
-        return 3                                  # C5_reduced ... P3, P6, C6_relu, P7
-
-    def finalize(self):
-        arr = (PlanOp * len(self.ops))()
-        for i, (kind, tag, desc, name, _) in enumerate(self.ops):
-            arr[i].kind, arr[i].tag, arr[i].desc = kind | self.lanes[i] | (self.stage_of(kind, name) << 20), tag, ctypes.addressof(desc)
-        self.array = arr
+# what a plan is (models/plan.py), under the names this module has always had: tests and tools spell them retinanet.StemDesc, retinanet.OP_CONV ...
+from .plan import (BlockDesc, CandidatePixelsDesc, DensePoolDesc, DetectDesc, PlanOp, PollDesc, PoolDesc, PoseDesc,  # noqa: F401
+                   PreactDesc, RaggedPoolDesc, RaggedStemDesc, ReluDesc, StemDesc, TailDesc,
+                   OP_STEM, OP_MAXPOOL, OP_CONV, OP_RELU, OP_DETECT, OP_POLL, OP_TAIL, OP_BLOCK,
+                   OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT, OP_DETECT_OSF, OP_STEM_POOL,
+                   OP_MAXPOOL_PAD, OP_AVGPOOL, OP_CONV_PREACT, OP_MOBILENET_STEM, OP_MOBILENET_BLOCK, OP_POSE,
+                   OP_ABSMAX, OP_ABSMAX_CLEAR, OP_STEM_RAGGED, OP_STEM_POOL_RAGGED, OP_MAXPOOL_RAGGED,
+                   OP_DETECT_CANDIDATE_PIXELS, DETECT_OPS, OP_JOIN, OP_SYNC,
+                   PlanOptions, block_form, part_of, TOWER_SLICES, RANGE_AUDIT_THRESHOLD, X3_QUANTUM,
+                   SPARSE_HEADS_MAX_SHARE, audit_report, SparseHeads, Plan)
 
 
 class RetinaNet3D(object):
@@ -483,6 +117,7 @@ class RetinaNet3D(object):
         self.torch = torch
         self._plans = {}
         self._anchors = {}
+        self._taps, self._ragged_taps = {}, {}      # resize tap tables on the device, per frame size (stage_frames / _stage_ragged_frames)
         self._tuned = {}             # (layer, B, H, W) -> (tile_hint, split_k, us): see _autotune
         self.stem_x3 = False         # conv1 on the matrix pipe, input and weights split into two IEEE halves (_upload)
         self._load_tune_cache()
@@ -1474,20 +1109,17 @@ class RetinaNet3D(object):
         the other form): ONE launch packs them into a (B, 100, 35) float32 tensor (gpp_pack_detections; labels / orientations are small
         integers: exact) and ONE copy brings it to the host, instead of eight blocking copies of 0.4 - 4.8 KB per image -- the same bytes
         (tests/test_network_gpu.py), 8 -> 1 host round trips inside the bracket the reference times (bin/run_network.py:108-111). """
+        return self._answer(plan, 'predict_on_batch', self.outputs_reader(packed))
+
+    @staticmethod
+    def outputs_reader(packed=None):
+        """ how fetch reads the 8 arrays (a reader of _answer): packed, the counter rides behind the detections (pack_with_range); the
+        other form makes eight copies and reads an 8-byte snapshot behind them """
         if packed is None:
             packed = os.environ.get('GPP_FETCH', 'packed') != 'separate'
-        watch = self.watches_range()
         if packed:
-            outs, count = self.unpack_with_range(self.pack_with_range(plan).cpu().numpy(), plan.shape[0])
-        else:
-            outs = [t.cpu().numpy() for t in self.outputs(plan)]
-            count = int(self.range_snapshot(plan).cpu().view(self.torch.int64).item()) if watch else 0
-        if watch and self.note_range(plan, count):
-            return self._range_event([plan.images, plan.P_inv, plan.planes], 'predict_on_batch', heights=self._heights_of(plan))
-        flagged = self._audit_flags(plan)
-        if flagged:
-            return self._range_event([plan.images, plan.P_inv, plan.planes], 'predict_on_batch', flagged)
-        return outs
+            return lambda model, plan: model.unpack_with_range(model.pack_with_range(plan).cpu().numpy(), plan.shape[0])
+        return RetinaNet3D.behind_snapshot(lambda model, plan: [t.cpu().numpy() for t in model.outputs(plan)])
 
     # ------------------------------------------------------------------ f16x3: the lower range, audited (range_audit=True)
     def range_audit(self, plan=None):
@@ -1507,7 +1139,8 @@ class RetinaNet3D(object):
 
     def _audit_flags(self, plan):
         """ an audit model's synchronous calls: read the table of the run just fetched (the one extra copy this mode accepts), keep the
-        report, count the flagged maps; returns those the call has to react to ([] for on_range_event='ignore' and for other models) """
+        report (last_range_audit; plan.audit_flagged = its flagged maps), count them; returns those the call has to react to ([] for
+        on_range_event='ignore' and for other models).  A run that left the half range is not audited: both keep the previous call's """
         if not self.audit:
             return []
         self.last_range_audit = self.range_audit(plan)
@@ -1559,14 +1192,36 @@ class RetinaNet3D(object):
         n = flat.size - 2
         return D.unpack_outputs(flat[:n].reshape(B, n // (B * D.PACK_WIDTH), D.PACK_WIDTH)), int(flat[n:].view(np.uint64)[0])
 
+    # One path from a plan that has just been enqueued to an answered call.  A *reader* is what a call supplies: reader(model, plan) ->
+    # (the call's result read from that plan, the plan's range counter as the stream saw it behind the result) -- the counter comes with
+    # the copy the call makes anyway (pack_with_range, fetch_poses) or as 8 bytes of its own (behind_snapshot), never with a further
+    # synchronisation; a model that does not watch the range returns any number there.  Everything else happens here, once.
     @staticmethod
-    def _heights_of(plan):
-        return plan.heights_host if getattr(plan, 'ragged', False) else None
+    def behind_snapshot(result_of):
+        """ a reader for a result that does not carry the counter itself: the 8-byte snapshot (range_snapshot) is enqueued in front of
+        result_of(model, plan) and read behind it """
+        def reader(model, plan):
+            snapshot = model.range_snapshot(plan) if model.watches_range() else None
+            result = result_of(model, plan)
+            return result, 0 if snapshot is None else int(snapshot.cpu().view(model.torch.int64).item())
+        return reader
 
-    def _range_event(self, device_inputs, what, flagged=None, heights=None):
-        """ an activation of the call just fetched left the half range (or, flagged: a whole map of an audit model sits below it): its
-        result is not the reference's.  device_inputs = the call's [images, P_inv, planes] still in HBM; heights: the call ran a ragged
-        plan, images is its canvas (the twin gets the same canvas and heights). """
+    def _answer(self, plan, what, reader, restage=None):
+        """ the result of the plan's run for the call `what`: the reader's, unless an activation of the run left the half range or (an
+        audit model; looked at only when the range held) a whole map sits below it -- then what _range_event returns """
+        result, count = reader(self, plan)
+        event = self.watches_range() and self.note_range(plan, count)
+        flagged = [] if event else self._audit_flags(plan)
+        if event or flagged:
+            return self._range_event(plan, what, reader, flagged, restage)
+        return result
+
+    def _range_event(self, plan, what, reader, flagged=(), restage=None):
+        """ the run of `plan` just read is not the reference's (note_range said so, or `flagged` names the maps of an audit model): count
+        it, then raise, or run the call again on the float32 twin and read the same thing there.  The twin gets the call's inputs where
+        they still are: the plan's images (a ragged plan: its canvas and heights), P_inv, planes and frame_info in HBM -- or what
+        restage(twin) -> its plan stages (FramePipeline: the slot's raw frames).  Everything is enqueued on the current stream.
+        utils/pipeline.py and utils/distributed.py come here behind their own note_range. """
         self.range_fallbacks += 1
         if self.on_range_event == 'raise' and flagged:
             raise hip.GppError(self._small_magnitude_message(what, flagged))
@@ -1574,12 +1229,16 @@ class RetinaNet3D(object):
             raise hip.GppError('{}: an activation left the IEEE-half range of dtype=\'f16x3\' (finite beyond +-65504, inf or NaN; '
                                'gpp_x3_range_events): the result would not be the reference\'s -- load the model with dtype=\'f32\' '
                                'or on_range_event=\'f32\''.format(what))
-        self.prepare_fallback()
-        if what == 'predict_on_frames':          # device_inputs = [frames uint8, P_inv, planes]: preprocessing included
-            return self._twin.predict_on_frames(*device_inputs)[0]
-        plan = self._twin.stage_inputs(device_inputs) if heights is None else self._twin.stage_canvas(device_inputs, heights)
-        self._twin.run_plan(plan)
-        return self._twin.fetch(plan)
+        twin = self.prepare_fallback()
+        if restage is not None:
+            twin_plan = restage(twin)
+        else:
+            inputs = [plan.images, plan.P_inv, plan.planes]
+            twin_plan = twin.stage_canvas(inputs, plan.heights_host) if plan.ragged else twin.stage_inputs(inputs)
+        if self.pose:
+            twin_plan.frame_info.copy_(plan.frame_info)          # (what put_frame_info gave the call, or the plan's default)
+        twin.run_plan(twin_plan)
+        return reader(twin, twin_plan)[0]
 
     def prepare_fallback(self, B=None, H=None, Wd=None, n_planes=None, planes_batched=True, ragged=False):
         """ on_range_event='f32': build the float32 twin NOW -- its weights upload (a second copy of the weights in HBM) and, when a shape is
@@ -1608,20 +1267,8 @@ class RetinaNet3D(object):
         shp = tuple(images.shape)
         if len(shp) != 4 or shp[3] != 3:
             raise ValueError('images must be (B, H, W, 3), got {}'.format(shp))
-        if tuple(P_inv.shape) != (shp[0], 4, 3):
-            raise ValueError('P_inv must be (B, 4, 3), got {}'.format(tuple(P_inv.shape)))
-        pshape = tuple(planes.shape)
-        batched = len(pshape) == 3
-        if not ((batched and pshape[0] == shp[0] and pshape[2] == 4) or (len(pshape) == 2 and pshape[1] == 4)) or pshape[-2] < 1:
-            raise ValueError('planes must be (B, N, 4) or (N, 4), got {}'.format(pshape))
-        plan = self.plan_for(shp[0], shp[1], shp[2], pshape[-2], batched)
-
-        def put(dst, src):
-            if isinstance(src, torch.Tensor):
-                dst.copy_(src.to(dtype=dst.dtype), non_blocking=True)
-            else:
-                dst.copy_(torch.as_tensor(np.ascontiguousarray(src, dtype=np.float32)), non_blocking=True)
-
+        n_planes, batched = self._check_calibration(shp[0], P_inv, planes)
+        plan = self.plan_for(shp[0], shp[1], shp[2], n_planes, batched)
         if not isinstance(images, torch.Tensor) and os.environ.get('GPP_UPLOAD', 'pageable') == 'pinned':
             # GPP_UPLOAD=pinned: host frames go through a page-locked staging buffer of the plan (one memcpy on the host, then a DMA).
             # Measured at batch 1 (tools/b1_latency.py --host-variants, profiles/r5/b1_latency.json): 0.37 ms for the 6.4 MB float32 frame
@@ -1636,9 +1283,9 @@ class RetinaNet3D(object):
             plan.images.copy_(plan.host_images, non_blocking=True)
             plan.host_images_free.record()
         else:
-            put(plan.images, images)
-        put(plan.P_inv, P_inv)
-        put(plan.planes, planes)
+            self._put(plan.images, images)
+        self._put(plan.P_inv, P_inv)
+        self._put(plan.planes, planes)
         return plan
 
     # ------------------------------------------------------------------ ragged batches: images of one height class, different heights
@@ -1659,6 +1306,7 @@ class RetinaNet3D(object):
         return pshape[-2], batched
 
     def _put(self, dst, src):
+        """ the one copy into a plan's buffer: a device tensor or a host array (asynchronous) """
         torch = self.torch
         src_t = src if isinstance(src, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(src, dtype=np.float32))
         dst.copy_(src_t.to(dtype=dst.dtype), non_blocking=True)
@@ -1709,12 +1357,10 @@ class RetinaNet3D(object):
         frames = [f.cpu().numpy() if isinstance(f, torch.Tensor) else np.asarray(f) for f in frames]
         if not frames or any(f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 3 for f in frames):
             raise ValueError('a ragged batch of frames is a non-empty list of (h, w, 3) uint8 frames')
-        shapes = tuple((int(f.shape[0]), int(f.shape[1])) for f in frames)
+        shapes = tuple(self._frame_shapes(frames))
         (Hp, Wo), heights, scales, taps = image_utils.ragged_taps(shapes, min_side, max_side)      # (ValueError: more than one class)
         B, Hr, Wr = len(frames), max(s[0] for s in shapes), max(s[1] for s in shapes)
         n_planes, batched = self._check_calibration(B, P_inv, planes)
-        if not hasattr(self, '_ragged_taps'):
-            self._ragged_taps = {}
         key = (shapes, min_side, max_side)
         if key not in self._ragged_taps:
             self._ragged_taps[key] = [torch.as_tensor(a).to(dev) for a in taps] + [torch.as_tensor(np.asarray(shapes, dtype=np.int32)).to(dev)]
@@ -1751,8 +1397,6 @@ class RetinaNet3D(object):
         scale = image_utils.compute_resize_scale((H, Wd, 3), min_side, max_side)
         Ho, Wo = int(np.rint(H * scale)), int(np.rint(Wd * scale))
         key = (H, Wd, Ho, Wo)
-        if not hasattr(self, '_taps'):
-            self._taps = {}
         if key not in self._taps:
             y0, y1, wy = image_utils._axis_taps(Ho, H, scale)
             x0, x1, wx = image_utils._axis_taps(Wo, Wd, scale)
@@ -1760,20 +1404,15 @@ class RetinaNet3D(object):
             self._taps[key] = [torch.as_tensor(a.astype(np.int32)).to(dev) for a in (y0, y1)] + [torch.as_tensor(wy).to(dev)] + \
                               [torch.as_tensor(a.astype(np.int32)).to(dev) for a in (x0, x1)] + [torch.as_tensor(wx).to(dev)]
         y0, y1, wy, x0, x1, wx = self._taps[key]
-        pshape = tuple(planes.shape)
-        plan = self.plan_for(B, Ho, Wo, pshape[-2], len(pshape) == 3)
+        n_planes, batched = self._check_calibration(B, P_inv, planes)
+        plan = self.plan_for(B, Ho, Wo, n_planes, batched)
         frames_d = frames.to(self.device, non_blocking=True).contiguous()
         m = image_utils.IMAGENET_MEAN_BGR
         hip.check(hip.lib().gpp_preprocess_u8_bgr(hip.ptr(frames_d), hip.ptr(plan.images), hip.ptr(y0), hip.ptr(y1), hip.ptr(wy),
                                                   hip.ptr(x0), hip.ptr(x1), hip.ptr(wx), B, H, Wd, Ho, Wo,
                                                   float(m[0]), float(m[1]), float(m[2]), hip.stream_ptr()), 'gpp_preprocess_u8_bgr')
-
-        def put(dst, src):
-            src_t = src if isinstance(src, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(src, dtype=np.float32))
-            dst.copy_(src_t.to(dtype=dst.dtype), non_blocking=True)
-
-        put(plan.P_inv, P_inv)
-        put(plan.planes, planes)
+        self._put(plan.P_inv, P_inv)
+        self._put(plan.planes, planes)
         plan.keep_frames = frames_d
         return plan, scale
 
@@ -1820,19 +1459,8 @@ class RetinaNet3D(object):
         plan, scale = self.stage_frames(frames_u8, P_inv, planes, min_side, max_side)
         self.run_plan(plan)
         args = (scale, annotations, iou_threshold, score_threshold, max_detections, num_classes)
-        watch = self.watches_range()
-        snapshot = self.range_snapshot(plan) if watch else None
-        out = self.match_outputs(self.outputs(plan), *args)
-        event = watch and self.note_range(plan, int(snapshot.cpu().view(self.torch.int64).item()))
-        flagged = None if event else self._audit_flags(plan)
-        if event or flagged:
-            self._range_event_raise_or_prepare('match_on_frames', flagged)          # (the preprocessed frames are still in the plan)
-            heights = self._heights_of(plan)
-            inputs = [plan.images, plan.P_inv, plan.planes]
-            twin_plan = self._twin.stage_inputs(inputs) if heights is None else self._twin.stage_canvas(inputs, heights)
-            self._twin.run_plan(twin_plan)
-            out = self._twin.match_outputs(self._twin.outputs(twin_plan), *args)
-        return out, scale
+        reader = self.behind_snapshot(lambda model, p: model.match_outputs(model.outputs(p), *args))
+        return self._answer(plan, 'match_on_frames', reader), scale
 
     # ------------------------------------------------------------------ pose rows (pose=True)
     def _require_pose(self):
@@ -1847,21 +1475,27 @@ class RetinaNet3D(object):
         info[:, 1:] = np.asarray(image_shapes, dtype=np.float64).reshape(-1, len(np.atleast_2d(image_shapes)[0]))[:, :2]
         plan.frame_info.copy_(self.torch.as_tensor(info), non_blocking=True)
 
-    def fetch_poses(self, plan):
-        """ (rows (B, 100, 36) float32, counts (B,) int32) of the plan's last run: one copy (synchronises); None in place of the result
-        when the half-range watch of dtype='f16x3' saw an event in that run (the caller re-runs on the float32 twin) """
-        B = plan.shape[0]
+    @staticmethod
+    def _frame_shapes(frames_u8):
+        """ the raw (h, w) of every frame of either form of frames_u8: a list of frames, or one (B, h, w, 3) array """
+        if isinstance(frames_u8, (list, tuple)):
+            return [tuple(int(v) for v in f.shape[:2]) for f in frames_u8]
+        return [tuple(int(v) for v in frames_u8.shape[1:3])] * int(frames_u8.shape[0])
+
+    def fetch_poses(self, plan, what='predict_poses_on_batch'):
+        """ (rows (B, 100, 36) float32, counts (B,) int32) of the plan's last run, as fetch returns the 8 arrays: one copy (synchronises);
+        the float32 twin's after a range event """
+        return self._answer(plan, what, self.read_poses)
+
+    @staticmethod
+    def read_poses(model, plan):
+        """ the reader of fetch_poses: ONE copy of pose_out brings the rows, the range counter behind them and the counts """
         n = plan.pose_rows.numel()
-        watch = self.watches_range()
-        if watch:
-            self.range_snapshot(plan, plan.pose_out[n:n + 2])
+        if model.watches_range():
+            model.range_snapshot(plan, plan.pose_out[n:n + 2])
         flat = plan.pose_out.cpu().numpy()
-        if watch and self.note_range(plan, int(flat[n:n + 2].view(np.uint64)[0])):
-            plan.audit_flagged = []
-            return None
-        if self._audit_flags(plan):
-            return None
-        return flat[:n].reshape(tuple(plan.pose_rows.shape)).copy(), flat[n + 2:].view(np.int32).copy()
+        rows, counts = flat[:n].reshape(tuple(plan.pose_rows.shape)).copy(), flat[n + 2:].view(np.int32).copy()
+        return (rows, counts), int(flat[n:n + 2].view(np.uint64)[0])
 
     def predict_poses_on_batch(self, inputs, scales, image_shapes, heights=None):
         """ predict_on_batch + what bin/run_network.py does with its result on the host, on the device: inputs as predict_on_batch;
@@ -1873,24 +1507,15 @@ class RetinaNet3D(object):
         plan = self.stage_inputs(inputs) if heights is None else self.stage_canvas(inputs, heights)      # (heights: inputs[0] is a ragged canvas)
         self.put_frame_info(plan, scales, image_shapes)
         self.run_plan(plan)
-        out = self.fetch_poses(plan)
-        if out is None:          # an activation left the half range: this call's answer comes from the float32 twin
-            self._range_event_raise_or_prepare('predict_poses_on_batch', getattr(plan, 'audit_flagged', None))
-            return self._twin.predict_poses_on_batch([plan.images, plan.P_inv, plan.planes], scales, image_shapes, heights=self._heights_of(plan))
-        return out
+        return self.fetch_poses(plan)
 
     def predict_poses_on_frames(self, frames_u8, P_inv, planes):
         """ predict_poses_on_batch for raw uint8 BGR frames (predict_on_frames): returns ((rows, counts), scale) """
         self._require_pose()
         plan, scale = self.stage_frames(frames_u8, P_inv, planes)
-        shapes = [tuple(f.shape[:2]) for f in frames_u8] if isinstance(frames_u8, (list, tuple)) else tuple(frames_u8.shape[1:3])
-        self.put_frame_info(plan, scale, shapes)
+        self.put_frame_info(plan, scale, self._frame_shapes(frames_u8))
         self.run_plan(plan)
-        out = self.fetch_poses(plan)
-        if out is None:
-            self._range_event_raise_or_prepare('predict_poses_on_frames', getattr(plan, 'audit_flagged', None))        # (the preprocessed frames are still in the plan)
-            out = self._twin.predict_poses_on_batch([plan.images, plan.P_inv, plan.planes], scale, shapes, heights=self._heights_of(plan))
-        return out, scale
+        return self.fetch_poses(plan, 'predict_poses_on_frames'), scale
 
     def score_poses_on_frames(self, frames_u8, P_inv, planes, labels):
         """ predict_poses_on_frames + the overlaps of KITTI's object benchmark (csrc/kitti_eval.hip) without the
@@ -1909,19 +1534,10 @@ class RetinaNet3D(object):
         if max([np.asarray(g).reshape(-1, kitti_eval.LABEL_COLS).shape[0] for g in labels] + [0]) > hip.GPP_KITTI_MAX_LABELS:
             raise ValueError('score_poses_on_frames: an image has more than {} labels'.format(hip.GPP_KITTI_MAX_LABELS))
         plan, scale = self.stage_frames(frames_u8, P_inv, planes)
-        shapes = [tuple(f.shape[:2]) for f in frames_u8] if isinstance(frames_u8, (list, tuple)) else tuple(frames_u8.shape[1:3])
-        self.put_frame_info(plan, scale, shapes)
+        self.put_frame_info(plan, scale, self._frame_shapes(frames_u8))
         self.run_plan(plan)
-        watch = self.watches_range()
-        snapshot = self.range_snapshot(plan) if watch else None
-        chunk = kitti_eval.upload_chunk(plan.pose_rows.clone(), labels, self.device)
-        event = watch and self.note_range(plan, int(snapshot.cpu().view(self.torch.int64).item()))
-        flagged = None if event else self._audit_flags(plan)
-        if event or flagged:
-            self._range_event_raise_or_prepare('score_poses_on_frames', flagged)        # (the preprocessed frames are still in the plan)
-            rows, _ = self._twin.predict_poses_on_batch([plan.images, plan.P_inv, plan.planes], scale, shapes, heights=self._heights_of(plan))
-            chunk = kitti_eval.upload_chunk(rows, labels, self.device)
-        return chunk, scale
+        reader = self.behind_snapshot(lambda model, p: kitti_eval.upload_chunk(p.pose_rows.clone(), labels, self.device))
+        return self._answer(plan, 'score_poses_on_frames', reader), scale
 
     def predict_composites_on_frames(self, frames_u8, P_inv, planes, P_raw, score_threshold=0.4):
         """ predict_poses_on_frames + the pictures of bin/run_network.py --save-images, rendered on the device (csrc/draw.hip, DESIGN.md
@@ -1933,12 +1549,11 @@ class RetinaNet3D(object):
         the float32 twin answers the call (a range event), the rows and the pictures are the twin's, drawn over this call's frames. """
         self._require_pose()
         torch = self.torch
-        ragged = isinstance(frames_u8, (list, tuple))
         plan, scale = self.stage_frames(frames_u8, P_inv, planes)
-        shapes = [tuple(int(v) for v in f.shape[:2]) for f in frames_u8] if ragged else [tuple(int(v) for v in frames_u8.shape[1:3])] * plan.shape[0]
+        shapes = self._frame_shapes(frames_u8)
         B = len(shapes)
         P_raw = np.array(np.broadcast_to(np.asarray(P_raw, dtype=np.float64), (B, 3, 4)))          # (a writable copy)
-        self.put_frame_info(plan, scale, shapes if ragged else shapes[0])
+        self.put_frame_info(plan, scale, shapes)
         self.run_plan(plan)
         frames_d = plan.keep_frames                      # the raw bytes: image b densely at the start of slot b
         Hr, Wr = max(s[0] for s in shapes), max(s[1] for s in shapes)
@@ -1949,33 +1564,20 @@ class RetinaNet3D(object):
         picture = torch.empty((status_at + 16 * B,), dtype=torch.uint8, device=self.device)
         status = picture[status_at:].view(torch.int32)
 
-        def draw(rows_d):
-            prims, prim_counts = hip.draw_build(rows_d, P_d, score_threshold)
+        def rows_and_pictures(model, p):
+            """ the reader: the two draw launches go in front of the fetch of the rows they read, the pictures' copy behind it; after a
+            range event the same again from the twin's rows, into the same buffer, over this call's frames """
+            prims, prim_counts = hip.draw_build(p.pose_rows, P_d, score_threshold)
             hip.draw_raster(frames_d, raw_hw, Hr, Wr, prims, prim_counts, picture, status)
+            poses, count = self.read_poses(model, p)
+            return (poses, picture.cpu().numpy()), count
 
-        draw(plan.pose_rows)
-        out = self.fetch_poses(plan)
-        if out is None:
-            self._range_event_raise_or_prepare('predict_composites_on_frames', getattr(plan, 'audit_flagged', None))
-            out = self._twin.predict_poses_on_batch([plan.images, plan.P_inv, plan.planes], scale, shapes if ragged else shapes[0],
-                                                    heights=self._heights_of(plan))
-            draw(torch.as_tensor(out[0]).to(self.device))
-        host = picture.cpu().numpy()
+        poses, host = self._answer(plan, 'predict_composites_on_frames', rows_and_pictures)
         report = host[status_at:].view(np.int32).reshape(B, 4)
         if (report[:, 1] != 0).any():
             raise hip.GppError('gpp_draw_raster met {} records of an unknown kind'.format(int(report[:, 1].sum())))
         composites = [host[b * slot:b * slot + 2 * h * w * 3].reshape(2 * h, w, 3).copy() for b, (h, w) in enumerate(shapes)]
-        return out, scale, composites
-
-    def _range_event_raise_or_prepare(self, what, flagged=None):
-        """ the bookkeeping of _range_event for the pose calls: count the event, raise (on_range_event='raise') or build the twin """
-        self.range_fallbacks += 1
-        if self.on_range_event == 'raise' and flagged:
-            raise hip.GppError(self._small_magnitude_message(what, flagged))
-        if self.on_range_event == 'raise':
-            raise hip.GppError('{}: an activation left the IEEE-half range of dtype=\'f16x3\' (gpp_x3_range_events): load the model '
-                               'with dtype=\'f32\' or on_range_event=\'f32\''.format(what))
-        self.prepare_fallback()
+        return poses, scale, composites
 
     # Keras-style conveniences used by the reference's scripts
     def predict(self, inputs, batch_size=None, verbose=0):

@@ -125,6 +125,6 @@ class ShardedModel(object):
         count = int(flat[n:].cpu().numpy().view(np.uint64)[0])                       # 8 bytes; the stream has reached the end of this rank's plan
         if not model.note_range(plan, count):
             return flat[:n].view(n_local, det, PACK_WIDTH)
-        outs = model._range_event([plan.images, plan.P_inv, plan.planes], 'predict_on_batch')
+        outs = model._range_event(plan, 'predict_on_batch', model.outputs_reader())
         host = np.concatenate([np.asarray(o, np.float32).reshape(n_local, det, -1) for o in outs], axis=2)
         return torch.as_tensor(np.ascontiguousarray(host)).to(flat.device)

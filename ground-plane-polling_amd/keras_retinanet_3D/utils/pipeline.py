@@ -168,5 +168,6 @@ class FramePipeline(object):
                 self.fallback_stream = torch.cuda.Stream(priority=-1)
             self.fallback_stream.wait_event(slot['uploaded'])
             with torch.cuda.stream(self.fallback_stream):
-                outs = m._range_event([slot['d_frames'], slot['d_pinv'], slot['d_planes']], 'predict_on_frames')
+                outs = m._range_event(slot['plan'], 'predict_on_frames', m.outputs_reader(),
+                                      restage=lambda twin: twin.stage_frames(slot['d_frames'], slot['d_pinv'], slot['d_planes'])[0])
         return outs, slot['scale']

@@ -75,3 +75,23 @@ def test_a_cpu_built_plan_never_reaches_a_kernel(cpu_model):
     for run in (lambda: model.run_op(plan, 0), lambda: model.run_plan(plan), lambda: model.capture(plan), lambda: model._autotune(plan)):
         with pytest.raises(hip.GppError):
             run()
+
+
+PLAN_NAMES = ('StemDesc PoolDesc RaggedStemDesc RaggedPoolDesc ReluDesc DetectDesc CandidatePixelsDesc PollDesc PoseDesc PreactDesc '
+              'DensePoolDesc PlanOp TailDesc BlockDesc '
+              'OP_STEM OP_MAXPOOL OP_CONV OP_RELU OP_DETECT OP_POLL OP_TAIL OP_BLOCK OP_DETECT_CANDIDATES OP_DETECT_SELECT OP_DETECT_EMIT '
+              'OP_DETECT_OSF OP_STEM_POOL OP_MAXPOOL_PAD OP_AVGPOOL OP_CONV_PREACT OP_MOBILENET_STEM OP_MOBILENET_BLOCK OP_POSE OP_ABSMAX '
+              'OP_ABSMAX_CLEAR OP_STEM_RAGGED OP_STEM_POOL_RAGGED OP_MAXPOOL_RAGGED OP_DETECT_CANDIDATE_PIXELS DETECT_OPS OP_JOIN OP_SYNC '
+              'PlanOptions block_form part_of TOWER_SLICES RANGE_AUDIT_THRESHOLD SPARSE_HEADS_MAX_SHARE audit_report SparseHeads Plan').split()
+
+
+def test_the_plan_abi_lives_in_models_plan_under_the_names_retinanet_has_always_had():
+    """ models/plan.py holds what a plan is (the mirrors of include/gpp.h, the op codes, PlanOptions, Plan ...); models/retinanet.py imports
+    every name, so retinanet.StemDesc, retinanet.OP_CONV, retinanet.Plan ... are the same objects """
+    from keras_retinanet_3D.models import plan as P
+    assert len(PLAN_NAMES) == len(set(PLAN_NAMES)) == 14 + 28 + 9          # mirrors, op codes and flags, the rest
+    for name in PLAN_NAMES:
+        assert getattr(P, name) is getattr(R, name), name
+    mirrors = [n for n in PLAN_NAMES if n.endswith('Desc') or n == 'PlanOp']
+    assert len(mirrors) == 14 and all(issubclass(getattr(P, n), ctypes.Structure) and getattr(P, n).__module__ == P.__name__ for n in mirrors)
+    assert P.Plan.__module__ == P.SparseHeads.__module__ == P.block_form.__module__ == P.__name__
