@@ -617,29 +617,21 @@ template <int DT, int CMID, int TH, int TW, bool IDENT, int NWAVES, int RING1>
 int launch_block_x3(gpp_conv_desc& d1, gpp_conv_desc& d2, gpp_conv_desc& d3, int stagger_us, hipStream_t st)
 {
     using S = BlockShape<CMID, TH, TW, NWAVES, RING1>;
-    static DeviceOnce once;
-    auto kernel = bottleneck_block_x3_kernel<DT, CMID, TH, TW, IDENT, NWAVES, RING1>;
-    int rc = once.configure(kernel, S::LDS);
+    constexpr auto kernel = bottleneck_block_x3_kernel<DT, CMID, TH, TW, IDENT, NWAVES, RING1>;
+    int rc = allow_lds<kernel>(S::LDS);
+    if (rc == GPP_OK) rc = set_input_extent(d1, 4);
+    if (rc == GPP_OK) rc = set_weight_extent(d1, d1.C_in, 4);
+    if (rc == GPP_OK) rc = set_weight_extent(d2, 9 * CMID, 4);
+    if (rc == GPP_OK) rc = set_weight_extent(d3, CMID, 4);
     if (rc != GPP_OK) return rc;
-    const gpp_conv_group& G = d1.groups[0];
-    const int64_t in_elems = G.in_off + (int64_t)(d1.batch - 1) * G.in_bstride + ((int64_t)G.H_in * G.W_in - 1) * d1.in_pitch + d1.C_in;
-    const int64_t w1_bytes = (int64_t)d1.weight_rows * d1.C_in * 4, w2_bytes = (int64_t)d2.weight_rows * 9 * CMID * 4,
-                  w3_bytes = (int64_t)d3.weight_rows * CMID * 4;
-    if (G.in_off < 0 || G.in_bstride < 0 || in_elems * 4 >= (1LL << 31) || w1_bytes >= (1LL << 31) || w2_bytes >= (1LL << 31) || w3_bytes >= (1LL << 31))
-        return GPP_ERR_UNSUPPORTED;
-    const gpp_conv_group& G3 = d3.groups[0];
+    const gpp_conv_group &G = d1.groups[0], &G3 = d3.groups[0];
     const int64_t px = (int64_t)G3.H_out * G3.W_out;
     if (px * d3.out_pitch * 4 >= (1LL << 31) || px * d3.res_pitch * 4 >= (1LL << 31)) return GPP_ERR_UNSUPPORTED;     // 32-bit byte offsets inside one image
-    d1.in_bytes = (int32_t)(in_elems * 4);
-    d1.weight_bytes = (int32_t)w1_bytes;
-    d2.weight_bytes = (int32_t)w2_bytes;
-    d3.weight_bytes = (int32_t)w3_bytes;
     const int tiles_x = (G.W_out + TW - 1) / TW, tiles_y = (G.H_out + TH - 1) / TH;
     const int64_t grid = (int64_t)d1.batch * tiles_x * tiles_y;
     if (grid >= (1LL << 31)) return GPP_ERR_UNSUPPORTED;
     kernel<<<dim3((unsigned)grid), dim3(64 * NWAVES), S::LDS, st>>>(d1, d2, d3, tiles_x, tiles_y, stagger_us * 100);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GPP_OK : (int)e;
+    return last_launch_rc();
 }
 
 // tile = TH * 100 + TW (0 = the default of the width)

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 
 #include "conv_igemm_types.h"
+#include "conv_tiles.h"
 #include "gpp.h"
 
 namespace {
@@ -267,67 +268,52 @@ extern "C" int gpp_conv2d_igemm(const gpp_conv_desc* host_desc, void* stream)
     return dispatch_any(d, (hipStream_t)stream);
 }
 
-// The block tiles a layer may run with (same K order per output element in every one of them: the choice never changes a result).
-// One list for the autotuner below and for gpp_conv2d_tile_candidates (tests draw tiles at random from it).
-static const int kTiles[] = {0, 64064, 96064, 128064, 160064, 192064, 64128, 96128, 128128, 160128, 192128, 224128,
-                             1128128, 1192128, 1128256, 1160256, 1192256, 1224256, 256256, 1256256,
-                             128160, 192160, 1192160, 1128160, 2256256, 1192096, 3256224, 3192160, 4128064, 4064064, 4128128, 4064128,
-                             5064064, 5096064, 5064128, 5096128, 5128128,      // x3 types, pre-split inputs: the plain loop on a four-deep ring
-                             128256, 192256,             // GPP_BF16X3 only: 8-wavefront tiles with the plain loop
-                             6064064, 6032064, 6064160, 7064064, 7032064, 7064160};      // the gathered-row form (gpp_conv_desc.gather_rows) and nothing else
-// (the loader-wavefront form of round 2, tile codes 3064128 ..., measured 1.5 - 2x slower on every layer it was built for
-// (profiles/r2/ring_kernel.txt), is no longer part of the library)
-static bool tile_is_candidate(const gpp_conv_desc* desc, int tile)
+// The block tiles a layer may run with (same K order per output element in every one of them: the choice never changes a result): the
+// catalogue's candidates (conv_tiles.h) behind 0 = the library's heuristic.  One list for the autotuner below and for
+// gpp_conv2d_tile_candidates (tests draw tiles at random from it).
+static const gpp_tiles::Entry kTiles[] = {{0, gpp_tiles::PLAIN, gpp_tiles::ALL, 0, 128, 0, 0, 0}, GPP_CONV_TILES(GPP_TILE_ENTRY, GPP_TILE_NONE, GPP_TILE_NONE)};
+
+static bool env_is_1(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }
+
+static bool tile_is_candidate(const gpp_conv_desc* desc, const gpp_tiles::Entry& t)
 {
-    const int ck = 128 / elem_size(desc->dtype);
-    const int nk = desc->KH * desc->KW * (desc->C_in / ck);
+    using namespace gpp_tiles;
+    const gpp_conv_desc& d = *desc;
+    if ((d.gather_rows != nullptr) != (t.form == GATHER)) return t.code == 0;      // gathered rows: their own tiles, and nobody else's
+    // ---- cannot run: nobody's instantiation, or the form's hard conditions (the dispatcher and the launchers refuse on the same functions)
+    const bool x3_in = is_x3(d.dtype) && (d.x3_split & GPP_X3_IN);
+    if (!owner_has(t.owner, f32_storage(d.dtype), is_x3(d.dtype))) return false;
+    // (pinned, tests/test_tile_table_cpu.py: 192160 stays listed for an x3 layer on a float32 input map, where dispatch refuses it)
+    if (is_x3(d.dtype) && x3_wants_split_input(t.form, t.owner) && !x3_in && t.owner != ALL_X3IN) return false;
+    const int nk = d.KH * d.KW * (d.C_in / (128 / elem_size(d.dtype)));
+    if (t.form == DUAL && !dual_can_run(d, nk)) return false;
+    if (t.form == MIX && !mix_can_run(d, nk)) return false;
+    if (t.form == WS && !ws_can_run(d, t.bm, t.bn)) return false;
+    // ---- not worth timing: tuning heuristics, and the A/B switches GPP_NO_{DEEP,WS,MIX}_TILES=1
+    static const bool no_deep = env_is_1("GPP_NO_DEEP_TILES"), no_ws = env_is_1("GPP_NO_WS_TILES"), no_mix = env_is_1("GPP_NO_MIX_TILES");
     int64_t rows = 0;
-    for (int g = 0; g < desc->n_groups; ++g) rows += (int64_t)desc->batch * desc->groups[g].H_out * desc->groups[g].W_out;
-    const int bn = tile % 1000 ? tile % 1000 : 128;
-    if (desc->gather_rows || tile >= 6000000) {           // gathered rows: their own three tiles; 160 columns only where that cuts the N padding
-        if (!desc->gather_rows || (tile != 0 && tile < 6000000)) return false;
-        return bn != 160 || (desc->C_out + 159) / 160 * 160 < (desc->C_out + 63) / 64 * 64;
+    for (int g = 0; g < d.n_groups; ++g) rows += (int64_t)d.batch * d.groups[g].H_out * d.groups[g].W_out;
+    const int bn = t.bn;
+    const auto pads_less_than = [&](int other) { return (d.C_out + bn - 1) / bn * bn < (d.C_out + other - 1) / other * other; };
+    switch (t.form) {
+        case GATHER: return bn != 160 || pads_less_than(64);                // 160 columns only where that cuts the N padding
+        case DEEP: {                                                         // deep K, and a grid of at most ~one workgroup per CU
+            int64_t tiles_m = 0;
+            for (int g = 0; g < d.n_groups; ++g) tiles_m += ((int64_t)d.batch * d.groups[g].H_out * d.groups[g].W_out + t.bm - 1) / t.bm;
+            const int64_t wgs = tiles_m * ((d.C_out + bn - 1) / bn) * (d.split_k > 1 ? d.split_k : 1);
+            return !(bn == 64 && d.C_out > 256) && !no_deep && nk >= 12 && wgs <= 320;
+        }
+        case WS: return !no_ws && rows >= 256 * 16;
+        case MIX: return !no_mix && nk >= 4 && rows * (d.C_out / 256) >= 256 * 256;      // enough rows for two rounds
+        default: break;
     }
-    if (tile >= 5000000) {           // four-deep ring (x3 types, pre-split inputs): deep K, and a grid of at most ~one workgroup per CU
-        static const bool no_deep = [] { const char* e = getenv("GPP_NO_DEEP_TILES"); return e && e[0] == '1'; }();      // (A/B)
-        const bool x3_in = is_x3(desc->dtype) && (desc->x3_split & GPP_X3_IN);
-        const int bm = (tile / 1000) % 1000;
-        int64_t tiles_m = 0;
-        for (int g = 0; g < desc->n_groups; ++g) tiles_m += ((int64_t)desc->batch * desc->groups[g].H_out * desc->groups[g].W_out + bm - 1) / bm;
-        const int64_t wgs = tiles_m * ((desc->C_out + bn - 1) / bn) * (desc->split_k > 1 ? desc->split_k : 1);
-        if (bn == 64 && desc->C_out > 256) return false;
-        return !no_deep && x3_in && nk >= 12 && wgs <= 320;
-    }
-    if (tile >= 4000000) {           // weight-stationary persistent 1 x 1 (x3 types, pre-split maps): the W n-tile and the ring have to fit 160 KB of LDS
-        static const bool no_ws = [] { const char* e = getenv("GPP_NO_WS_TILES"); return e && e[0] == '1'; }();
-        const bool x3_in = is_x3(desc->dtype) && (desc->x3_split & GPP_X3_IN);
-        const int bm = (tile / 1000) % 1000;
-        const gpp_conv_group& G = desc->groups[0];
-        return !no_ws && x3_in && desc->KH == 1 && desc->KW == 1 && desc->stride == 1 && desc->pad_top == 0 && desc->pad_left == 0 && desc->n_groups == 1 &&
-               desc->split_k <= 1 && desc->C_out % bn == 0 && 32 % (desc->C_out / bn) == 0 && G.H_in == G.H_out && G.W_in == G.W_out &&
-               (!desc->residual || ((desc->x3_split & GPP_X3_RES) && G.H_res == G.H_out && G.W_res == G.W_out)) &&
-               (desc->C_in / 32) * bn * 128 + 4 * bm * 128 <= 160 * 1024 && rows >= 256 * 16;
-    }
-    static const bool no_mix = [] { const char* e = getenv("GPP_NO_MIX_TILES"); return e && e[0] == '1'; }();      // (A/B of the mixed grids)
-    if (tile >= 3000000 && no_mix) return false;
-    if (tile >= 3000000) {           // mixed-height grids: x3 types on pre-split inputs, whole 256-column tiles, enough rows for two rounds
-        const bool x3_in = is_x3(desc->dtype) && (desc->x3_split & GPP_X3_IN);
-        return x3_in && desc->C_out % 256 == 0 && nk >= 4 && desc->split_k <= 1 && rows * (desc->C_out / 256) >= 256 * 256;
-    }
+    if (t.code == 0) return true;
     // narrow tiles on wide layers: never competitive -- except on the shallow 1 x 1 layers (K <= 256: a handful of K-steps, bound by the
     // latency of their few dependent tile loads, where more and smaller workgroups per CU win 3 - 6 %: profiles/r4/hbm_layers_f16x3.txt)
-    if (tile && bn == 64 && desc->C_out > 256 && !(desc->KH == 1 && desc->KW == 1 && desc->C_in <= 256)) return false;
-    if (bn == 256 && (desc->C_out < 192 || rows < 256 * 16)) return false;
-    // the pipelined loops need a few K-steps to pay; 16-bit types, and GPP_BF16X3 on a pre-split input map
-    const bool x3_pipe = is_x3(desc->dtype) && (desc->x3_split & GPP_X3_IN);
-    if (tile > 1000000 && tile < 3000000 && (nk < 4 || (f32_storage(desc->dtype) && !x3_pipe))) return false;
-    if ((tile == 1256256 || tile == 1160256 || tile == 1224256) && !x3_pipe) return false;
-    if (x3_pipe && tile == 1192160) return false;
-    if (bn == 256 && desc->dtype == GPP_F32) return false;
-    if ((tile == 128256 || tile == 192256) && !is_x3(desc->dtype)) return false;
-    if (bn == 160 && (desc->C_out + 159) / 160 * 160 >= (desc->C_out + 127) / 128 * 128) return false;   // only where it cuts the N padding
-    if (bn == 96 && (desc->C_out + 95) / 96 * 96 >= (desc->C_out + 127) / 128 * 128) return false;       // likewise (the 96 logits)
-    if (tile == 2256256 && (desc->C_out < 384 || desc->C_out % 256 != 128 || rows < 256 * 16)) return false;   // dual-shape grid: C_out = 256 k + 128
+    if (bn == 64 && d.C_out > 256 && !(d.KH == 1 && d.KW == 1 && d.C_in <= 256)) return false;
+    if (bn == 256 && (d.C_out < 192 || rows < 256 * 16)) return false;
+    if ((t.form == PIPE || t.form == DUAL) && nk < 4) return false;          // the pipelined loops need a few K-steps to pay
+    if ((bn == 160 || bn == 96) && !pads_less_than(128)) return false;      // only where it cuts the N padding (144 regression channels, 96 logits)
     return true;
 }
 
@@ -341,9 +327,9 @@ extern "C" int gpp_conv2d_tile_candidates(const gpp_conv_desc* desc, int* tiles,
         if (rc != GPP_OK) return rc;
     }
     int n = 0;
-    for (int tile : kTiles) {
-        if (!tile_is_candidate(desc, tile)) continue;
-        if (n < capacity) tiles[n] = tile;
+    for (const gpp_tiles::Entry& t : kTiles) {
+        if (!tile_is_candidate(desc, t)) continue;
+        if (n < capacity) tiles[n] = t.code;
         ++n;
     }
     *count = n;
@@ -393,8 +379,9 @@ extern "C" int gpp_conv2d_autotune(gpp_conv_desc* desc, int iters, void* stream,
     };
     float second = 1e30f;
     int second_tile = -1;
-    for (int tile : kTiles) {
-        if (!tile_is_candidate(desc, tile)) continue;
+    for (const gpp_tiles::Entry& t : kTiles) {
+        if (!tile_is_candidate(desc, t)) continue;
+        const int tile = t.code;
         float us = 0.0f;
         int r = time_one(tile, &us);
         if (r != GPP_OK) { if (tile == 0) { rc = r; break; } continue; }
@@ -429,7 +416,9 @@ extern "C" int gpp_conv2d_autotune(gpp_conv_desc* desc, int iters, void* stream,
 // not pre-split, GPP_F32 / GPP_F16X3 / GPP_BF16X3.
 namespace {
 
-static const int kPreactTiles[] = {0, 64064, 128064, 64128, 128128, 192128};
+#define GPP_TILE_CODE(code, ...) code,
+static const int kPreactTiles[] = {0, GPP_CONV_TILES(GPP_TILE_NONE, GPP_TILE_NONE, GPP_TILE_CODE)};
+#undef GPP_TILE_CODE
 
 int preact_validate(gpp_conv_desc& d, const float* in_scale, const float* in_shift)
 {

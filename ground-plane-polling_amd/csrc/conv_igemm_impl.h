@@ -43,7 +43,9 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <type_traits>
 
+#include "conv_tiles.h"
 #include "gpp.h"
 
 namespace {
@@ -135,15 +137,6 @@ constexpr int kOutOfRange = (int)0x80000000;
 #endif
 #ifndef GPP_X3_PRIO
 #define GPP_X3_PRIO 1
-#endif
-#ifndef GPP_X3_WB
-#define GPP_X3_WB 0
-#endif
-#ifndef GPP_X3_BEARLY
-#define GPP_X3_BEARLY 0
-#endif
-#ifndef GPP_X3_TAP_EARLY
-#define GPP_X3_TAP_EARLY 0
 #endif
 constexpr bool kSpreadDma = GPP_DMA_SPREAD != 0;
 
@@ -716,16 +709,6 @@ __device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const in
     constexpr bool BIASPRE = !PIPE && NF <= 4 && MF * NF <= (DT == GPP_F16X3 ? (XIN ? 16 : 0) : 24);
     if constexpr (BIASPRE) load_bias();
 
-#ifdef GPP_VALU_PAD
-    // experiment (make variant EXTRA=-DGPP_VALU_PAD=n): n extra vector-ALU instructions per wavefront ahead of the main loop -- is a layer
-    // bound by instruction issue?  (profiles/r4/valu_pad_experiment.txt)
-    {
-        int pad = lane;
-#pragma unroll
-        for (int i = 0; i < GPP_VALU_PAD; ++i) asm volatile("v_add_u32 %0, %0, 1" : "+v"(pad));
-        if (pad == -12345) acc[0][0][0] = 1.0f;
-    }
-#endif
     // PRE: scale at [0, C_in), shift at [C_in, 2 C_in) of the table behind the ring (visible after the first K-step's barrier)
     const float* pre_tab = (const float*)(smem + STAGES * STAGE);
     if constexpr (PRE) {
@@ -842,14 +825,8 @@ __device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const in
             // it, so the four sets take 96 registers (as in the 16-bit loop) and the body needs no second copy.  One barrier per
             // 3 MF NF MFMAs; the DMA of stage k+2 has two phases to land.
             static_assert(XIN, "the pipelined bf16x3 loop reads pre-split activation rows");
-            // which weight fragments group g of a phase fetches: spread over all MF groups, or (GPP_X3_BEARLY) one per group from the first
-            // group on, so that the last of them has more than a group's time to arrive before the next phase's first MFMA needs all NF
-#if GPP_X3_BEARLY
-            constexpr int BPG = (NF + MF - 1) / MF;
-            auto BJ0 = [](int g) { return g * BPG < NF ? g * BPG : NF; };
-#else
+            // which weight fragments group g of a phase fetches: spread over all MF groups
             auto BJ0 = [](int g) { return g * NF / MF; };
-#endif
             xh8 ah[MF], al[MF], bh[NF], bl[NF];
 #pragma unroll
             for (int idx = 0; idx < PER_STAGE; ++idx) issue_one(idx, 0, in_rsrc, w_rsrc, cc * kRowBytes, ks0 * kRowBytes);
@@ -901,7 +878,7 @@ __device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const in
                 for (int g = 0; g < MF; ++g) {
                     if constexpr (SPREAD) {
 #pragma unroll
-                        for (int idx = A_IT + g * (B_IT - GPP_X3_WB) / MF; idx < A_IT + (g + 1) * (B_IT - GPP_X3_WB) / MF; ++idx) GPP_ABL(abl_dma) issue_one(idx, cur ^ 1, rw_late, rw_late, 0, so_w_late);
+                        for (int idx = A_IT + g * B_IT / MF; idx < A_IT + (g + 1) * B_IT / MF; ++idx) GPP_ABL(abl_dma) issue_one(idx, cur ^ 1, rw_late, rw_late, 0, so_w_late);
                     }
 #pragma unroll
                     for (int j = BJ0(g); j < BJ0(g + 1); ++j) GPP_ABL(abl_rdab) bh[j] = *(const xh8*)(scur + b_rd[0] + j * 16 * kRowBytes);
@@ -916,9 +893,6 @@ __device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const in
                 // ---- phase B: hi * whi, fetch lo
 #pragma unroll
                 for (int g = 0; g < MF; ++g) {
-                    if constexpr (SPREAD && GPP_X3_WB > 0) {
-                        if (g < GPP_X3_WB) GPP_ABL(abl_dma) issue_one(A_IT + B_IT - GPP_X3_WB + g, cur ^ 1, rw_late, rw_late, 0, so_w_late);
-                    }
                     GPP_ABL(abl_rdab) al[g] = *(const xh8*)(scur + a_rd[1] + g * 16 * kRowBytes);
 #pragma unroll
                     for (int j = 0; j < NF; ++j) { const int js = GPP_SERP(g, j, NF); acc[g][js] = X3Half<DT>::mfma(bh[js], ah[g], acc[g][js]); }
@@ -953,30 +927,13 @@ __device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const in
                     GPP_ABL(abl_rdc) ah[g] = *(const xh8*)(snxt + a_rd[0] + g * 16 * kRowBytes);
 #pragma unroll
                     for (int j = BJ0(g); j < BJ0(g + 1); ++j) GPP_ABL(abl_rdc) bl[j] = *(const xh8*)(snxt + b_rd[1] + j * 16 * kRowBytes);
-#if GPP_X3_TAP_EARLY
-                    if (g == MF - 1) {              // the next tap's offsets, computed beside the last group's MFMAs (branch-free: past the last stage the
-                        rw_late = rw;               // descriptors are zero-length, whatever the offsets)
-                        so_w_late = so_w;
-                        ++kw;
-                        const bool ww = kw == d.KW;
-                        kw = ww ? 0 : kw;
-                        kh += ww ? 1 : 0;
-                        const bool wh = kh == d.KH;
-                        kh = wh ? 0 : kh;
-                        cc += wh ? 1 : 0;
-                        set_tap(kh, kw);
-                        ++issued;
-                    }
-#endif
 #pragma unroll
                     for (int j = 0; j < NF; ++j) { const int js = GPP_SERP(g, j, NF); acc[g][js] = X3Half<DT>::mfma(bh[js], al[g], acc[g][js]); }
                     __builtin_amdgcn_sched_barrier(0);
                 }
-#if !GPP_X3_TAP_EARLY
                 rw_late = rw;
                 so_w_late = so_w;
                 if (live) advance_tap();
-#endif
             }
             if (NW == 8) __builtin_amdgcn_s_setprio(0);
 #ifdef GPP_STAMPS
@@ -1413,7 +1370,7 @@ __global__ __launch_bounds__(256, 2) void bottleneck_tail_kernel(const gpp_conv_
     static_assert(BM % (16 * P2M) == 0, "phase-2 wave tile");
     constexpr int KC = CMID / 64;                                          // 64-channel chunks of the intermediate
     constexpr int A_BYTES = BM * kRowBytes, B_BYTES = CMID * kRowBytes, STAGE = A_BYTES + B_BYTES;
-    constexpr int A_IT = BM / 8 / NW, B_IT = CMID / 8 / NW, PER_STAGE = A_IT + B_IT;
+    constexpr int A_IT = BM / 8 / NW, B_IT = CMID / 8 / NW;
     constexpr int T_BYTES = KC * A_BYTES;                                  // intermediate tile, A-operand layout
     constexpr int W2_IT = 128 / 8 / NW;                                    // LDS-DMA per wave per chunk of a W2 tile
     static_assert(BM % 32 == 0 && (CMID == 64 || CMID == 128), "tile shape");
@@ -2241,6 +2198,62 @@ struct DeviceOnce {
     }
 };
 
+inline int last_launch_rc()
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? GPP_OK : (int)e;
+}
+
+// KERNEL may use `lds` bytes of dynamic LDS on this device (asked once per device).  Every launcher asks BEFORE it looks at the layer, so
+// that without a device the answer is the runtime's error, whatever the layer
+template <auto KERNEL>
+int allow_lds(int lds)
+{
+    static DeviceOnce once;
+    return once.configure(KERNEL, lds);
+}
+
+// split-K admission: d.split_k partitions of the nk K-steps (the caller's explicit choice, or the library's batch-independent rule,
+// gpp_conv2d_split_rule, applied by the entry point before it gets here); every split keeps >= 1 K-step and the partial slabs
+// [split][tiles * bm][n_tiles * bn] float32 must fit the workspace -- otherwise GPP_ERR_WORKSPACE, never a silently different summation
+// order.  Returns the number of splits (>= 1) or the error.
+inline int splitk_admit(const gpp_conv_desc& d, int nk, int tiles, int n_tiles, int bm, int bn)
+{
+    if (d.split_k <= 1) return 1;
+    if (nk / d.split_k < 1) return GPP_ERR_BAD_ARG;
+    const int64_t slab = (int64_t)tiles * bm * n_tiles * bn * 4;
+    if (!d.partial || slab * d.split_k > (int64_t)d.partial_bytes) return GPP_ERR_WORKSPACE;
+    return d.split_k;
+}
+
+// ... and the sum of the slabs + epilogue, behind the launch that wrote them; the answer of both launches
+template <int DT>
+int splitk_reduce(const gpp_conv_desc& d, int bm, int n_cols, int nsplit, hipStream_t st)
+{
+    if (nsplit <= 1) return last_launch_rc();
+    const int64_t total = (int64_t)d.partial_rows * ((d.C_out + 7) / 8);
+    splitk_reduce_kernel<DT><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(d, bm, n_cols, nsplit);
+    return last_launch_rc();
+}
+
+// Extents for the range-checked loads of the fused launches (below, conv_block_impl.h): 32-bit byte offsets, esz bytes per element
+inline int set_input_extent(gpp_conv_desc& d, int esz)
+{
+    const gpp_conv_group& G = d.groups[0];
+    const int64_t in_elems = G.in_off + (int64_t)(d.batch - 1) * G.in_bstride + ((int64_t)G.H_in * G.W_in - 1) * d.in_pitch + d.C_in;
+    if (G.in_off < 0 || G.in_bstride < 0 || in_elems * esz >= (1LL << 31)) return GPP_ERR_UNSUPPORTED;
+    d.in_bytes = (int32_t)(in_elems * esz);
+    return GPP_OK;
+}
+
+inline int set_weight_extent(gpp_conv_desc& d, int64_t row_elems, int esz)
+{
+    const int64_t bytes = (int64_t)d.weight_rows * row_elems * esz;
+    if (bytes >= (1LL << 31)) return GPP_ERR_UNSUPPORTED;
+    d.weight_bytes = (int32_t)bytes;
+    return GPP_OK;
+}
+
 // One tile configuration: block tile BM x BN, WM x WN wavefronts, STAGES-deep LDS ring.
 template <int DT, int BM, int BN, int WM, int WN, int STAGES, bool PIPE, bool XIN = false>
 int launch(gpp_conv_desc& d, hipStream_t st)
@@ -2251,25 +2264,15 @@ int launch(gpp_conv_desc& d, hipStream_t st)
     constexpr int BMS = stage_rows(BM, WM * WN);
     constexpr int lds = STAGES * (BMS + BN) * kRowBytes;
     constexpr int CK = kRowBytes / Elem<DT>::ESZ;
-    static DeviceOnce once;
-    auto kernel = conv_igemm_kernel<DT, BM, BN, WM, WN, STAGES, PIPE, XIN>;
-    int rc = once.configure(kernel, lds);
+    constexpr auto kernel = conv_igemm_kernel<DT, BM, BN, WM, WN, STAGES, PIPE, XIN>;
+    const int rc = allow_lds<kernel>(lds);
     if (rc != GPP_OK) return rc;
     const int tiles = prepare<BM, BN>(d);
     if (tiles < 0) return tiles;
     const int n_tiles = (d.C_out + BN - 1) / BN;
-    // split-K: d.split_k partitions of the K-steps (the caller's explicit choice, or the library's batch-independent rule,
-    // gpp_conv2d_split_rule, applied by the entry point before it gets here); every split keeps >= 1 K-step and the
-    // partial slabs [split][tiles*BM][n_tiles*BN] float32 must fit the workspace -- otherwise GPP_ERR_WORKSPACE, never
-    // a silently different summation order
     const int nk = d.KH * d.KW * (d.C_in / CK);
-    int nsplit = 1;
-    if (d.split_k > 1) {
-        nsplit = d.split_k;
-        if (nk / nsplit < 1) return GPP_ERR_BAD_ARG;
-        const int64_t slab = (int64_t)tiles * BM * n_tiles * BN * 4;
-        if (!d.partial || slab * nsplit > (int64_t)d.partial_bytes) return GPP_ERR_WORKSPACE;
-    }
+    const int nsplit = splitk_admit(d, nk, tiles, n_tiles, BM, BN);
+    if (nsplit < 0) return nsplit;
     // a layer with fewer K-steps than ring slots (1x1 convs with C_in = 64) only touches the first slots:
     // declaring just those lets more workgroups share a CU, which is what the HBM-bound layers need
     const int steps = (nk + nsplit - 1) / nsplit;
@@ -2277,12 +2280,7 @@ int launch(gpp_conv_desc& d, hipStream_t st)
     // uses: they get the whole ring whatever the step count, never less LDS than they address)
     const int lds_used = PIPE ? lds : (steps < STAGES ? steps : STAGES) * (BMS + BN) * kRowBytes;
     kernel<<<dim3((unsigned)(tiles * n_tiles), (unsigned)nsplit), dim3(64 * WM * WN), lds_used, st>>>(d);
-    if (nsplit > 1) {
-        const int64_t total = (int64_t)d.partial_rows * ((d.C_out + 7) / 8);
-        splitk_reduce_kernel<DT><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(d, BM, n_tiles * BN, nsplit);
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GPP_OK : (int)e;
+    return splitk_reduce<DT>(d, BM, n_tiles * BN, nsplit, st);
 }
 
 // gpp_conv2d_preact: one tile configuration of the pre-activation form (two-buffer ring + the 2 * C_in float32 scale / shift table)
@@ -2295,60 +2293,29 @@ int launch_preact(gpp_conv_desc& d, const float* in_scale, const float* in_shift
     constexpr int kMaxLds = 160 * 1024;
     const int lds = ring + 2 * d.C_in * 4;
     if (lds > kMaxLds) return GPP_ERR_UNSUPPORTED;
-    static DeviceOnce once;
-    auto kernel = conv_preact_kernel<DT, BM, BN, WM, WN>;
-    int rc = once.configure(kernel, kMaxLds);
+    constexpr auto kernel = conv_preact_kernel<DT, BM, BN, WM, WN>;
+    const int rc = allow_lds<kernel>(kMaxLds);
     if (rc != GPP_OK) return rc;
     const int tiles = prepare<BM, BN>(d);
     if (tiles < 0) return tiles;
     const int n_tiles = (d.C_out + BN - 1) / BN;
-    const int nk = d.C_in / CK;
-    int nsplit = 1;
-    if (d.split_k > 1) {
-        nsplit = d.split_k;
-        if (nk / nsplit < 1) return GPP_ERR_BAD_ARG;
-        const int64_t slab = (int64_t)tiles * BM * n_tiles * BN * 4;
-        if (!d.partial || slab * nsplit > (int64_t)d.partial_bytes) return GPP_ERR_WORKSPACE;
-    }
+    const int nsplit = splitk_admit(d, d.C_in / CK, tiles, n_tiles, BM, BN);
+    if (nsplit < 0) return nsplit;
     kernel<<<dim3((unsigned)(tiles * n_tiles), (unsigned)nsplit), dim3(64 * WM * WN), lds, st>>>(d, in_scale, in_shift);
-    if (nsplit > 1) {
-        const int64_t total = (int64_t)d.partial_rows * ((d.C_out + 7) / 8);
-        splitk_reduce_kernel<DT><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(d, BM, n_tiles * BN, nsplit);
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GPP_OK : (int)e;
-}
-
-// the tiles of the pre-activation form (gpp_conv2d_preact_tile_candidates lists the same codes); 0 = 128 x 128, or 128 x 64 for
-// C_out <= 64
-template <int DT>
-int dispatch_preact(gpp_conv_desc& d, const float* in_scale, const float* in_shift, hipStream_t st)
-{
-    switch (d.tile_hint) {
-        case 0: return d.C_out <= 64 ? launch_preact<DT, 128, 64, 2, 2>(d, in_scale, in_shift, st)
-                                     : launch_preact<DT, 128, 128, 2, 2>(d, in_scale, in_shift, st);
-        case 64064: return launch_preact<DT, 64, 64, 2, 2>(d, in_scale, in_shift, st);
-        case 128064: return launch_preact<DT, 128, 64, 2, 2>(d, in_scale, in_shift, st);
-        case 64128: return launch_preact<DT, 64, 128, 2, 2>(d, in_scale, in_shift, st);
-        case 128128: return launch_preact<DT, 128, 128, 2, 2>(d, in_scale, in_shift, st);
-        case 192128: return launch_preact<DT, 192, 128, 2, 2>(d, in_scale, in_shift, st);
-        default: return GPP_ERR_BAD_ARG;
-    }
+    return splitk_reduce<DT>(d, BM, n_tiles * BN, nsplit, st);
 }
 
 // conv_igemm_dual_kernel: C_out = 256 k + 128.  The caller's descriptor is split into the two column blocks here.
 template <int DT>
 int launch_dual(const gpp_conv_desc& d, hipStream_t st)
 {
-    // 16-bit types, and GPP_BF16X3 on a pre-split input map (its pipelined three-phase loop)
+    // 16-bit types, and the x3 types on a pre-split input map (their pipelined three-phase loop: run_tile has checked the input form)
     constexpr bool X3 = kX3<DT>;
     constexpr int ESZ = Elem<DT>::ESZ, CK = kRowBytes / ESZ;
-    if (X3 && !(d.x3_split & GPP_X3_IN)) return GPP_ERR_UNSUPPORTED;
-    if (d.C_out < 384 || d.C_out % 256 != 128 || d.KH * d.KW * (d.C_in / CK) < 2 || d.split_k > 1) return GPP_ERR_UNSUPPORTED;
+    if (!gpp_tiles::dual_can_run(d, d.KH * d.KW * (d.C_in / CK))) return GPP_ERR_UNSUPPORTED;
     constexpr int lds = 2 * (512 + 128) * kRowBytes;          // 160 KB: the larger of the two bodies
-    static DeviceOnce once;
-    auto kernel = conv_igemm_dual_kernel<DT, X3>;
-    int rc = once.configure(kernel, lds);
+    constexpr auto kernel = conv_igemm_dual_kernel<DT, X3>;
+    const int rc = allow_lds<kernel>(lds);
     if (rc != GPP_OK) return rc;
     const int head = d.C_out - 128;                           // columns of the 256-wide part: a multiple of 256
     gpp_conv_desc d0 = d, d1 = d;
@@ -2368,8 +2335,7 @@ int launch_dual(const gpp_conv_desc& d, hipStream_t st)
     const int n0 = t0 * (head / 256), n1 = t1;
     const int split0 = (n0 + 7) / 8 * 8;                      // keeps workgroup index % 8 = XCD for the second range's remap
     kernel<<<dim3((unsigned)(split0 + n1)), dim3(512), lds, st>>>(d0, d1, n0, split0, n1);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GPP_OK : (int)e;
+    return last_launch_rc();
 }
 
 // conv_igemm_mix_kernel: 256-column tiles of two heights in one grid (x3 types on pre-split input maps: the three-phase loop).
@@ -2381,9 +2347,8 @@ int launch_mix(const gpp_conv_desc& d, hipStream_t st)
 {
     constexpr int BN = 256, CUS = 256;
     constexpr int ESZ = Elem<DT>::ESZ, CK = kRowBytes / ESZ;
-    static_assert(kX3<DT>, "mixed grids exist for the x3 types");
-    if (!(d.x3_split & GPP_X3_IN)) return GPP_ERR_UNSUPPORTED;
-    if (d.C_out % BN != 0 || d.KH * d.KW * (d.C_in / CK) < 2 || d.split_k > 1) return GPP_ERR_UNSUPPORTED;
+    static_assert(kX3<DT>, "mixed grids exist for the x3 types");         // (on pre-split input maps: run_tile has checked)
+    if (!gpp_tiles::mix_can_run(d, d.KH * d.KW * (d.C_in / CK))) return GPP_ERR_UNSUPPORTED;
     const int n_tiles = d.C_out / BN;
     const int64_t rows0 = (int64_t)d.batch * d.groups[0].H_out * d.groups[0].W_out;
     auto tiles_b = [&](int64_t begin, int bm) {
@@ -2402,9 +2367,8 @@ int launch_mix(const gpp_conv_desc& d, hipStream_t st)
     }
     if (best_ra == 0) return GPP_ERR_UNSUPPORTED;
     constexpr int lds = 2 * (stage_rows(BMA > BMB ? BMA : BMB, 8) + BN) * kRowBytes;
-    static DeviceOnce once;
-    auto kernel = conv_igemm_mix_kernel<DT, BMA, BMB, BN, true>;
-    int rc = once.configure(kernel, lds);
+    constexpr auto kernel = conv_igemm_mix_kernel<DT, BMA, BMB, BN, true>;
+    const int rc = allow_lds<kernel>(lds);
     if (rc != GPP_OK) return rc;
     const int ma = best_ra * CUS / n_tiles;
     gpp_conv_desc da = d, db = d;
@@ -2418,44 +2382,29 @@ int launch_mix(const gpp_conv_desc& d, hipStream_t st)
     const int na = ma * n_tiles, nb = tb * n_tiles;
     const int splita = (na + 7) / 8 * 8;                       // keeps workgroup index % 8 = XCD for the second range's remap
     kernel<<<dim3((unsigned)(splita + nb)), dim3(512), lds, st>>>(da, db, na, splita, nb);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GPP_OK : (int)e;
+    return last_launch_rc();
 }
 
-// conv1x1_ws_kernel: which layers it takes, and how it is launched (256 workgroups, W n-tile + ring in LDS).
+// conv1x1_ws_kernel: 256 workgroups, W n-tile + ring in LDS; which layers it takes: gpp_tiles::ws_can_run
 template <int DT, int BM, int BN>
 int launch_ws(gpp_conv_desc& d, hipStream_t st)
 {
     constexpr int R = 4;
     static_assert(kX3<DT>, "weight-stationary 1 x 1: x3 types");
+    if (!gpp_tiles::ws_can_run(d, BM, BN)) return GPP_ERR_UNSUPPORTED;
     const gpp_conv_group& G = d.groups[0];
-    if (!(d.x3_split & GPP_X3_IN) || d.KH != 1 || d.KW != 1 || d.stride != 1 || d.pad_top != 0 || d.pad_left != 0 || d.n_groups != 1 || d.split_k > 1)
-        return GPP_ERR_UNSUPPORTED;
-    if (d.C_out % BN != 0 || 32 % (d.C_out / BN) != 0 || d.C_in % 32 != 0) return GPP_ERR_UNSUPPORTED;
-    if (G.H_in != G.H_out || G.W_in != G.W_out) return GPP_ERR_UNSUPPORTED;
-    if (d.residual && (!(d.x3_split & GPP_X3_RES) || G.H_res != G.H_out || G.W_res != G.W_out)) return GPP_ERR_UNSUPPORTED;   // shortcut: pre-split, same size
-    const int nk = d.C_in / 32;
-    const int lds = nk * BN * kRowBytes + R * BM * kRowBytes;
-    if (lds > 160 * 1024) return GPP_ERR_UNSUPPORTED;
+    const int lds = (d.C_in / 32) * BN * kRowBytes + R * BM * kRowBytes;
     const int tiles = prepare<BM, BN>(d);                       // buffer extents (+ the weight-row check)
     if (tiles < 0) return tiles;
     const int n_mtiles = (int)(((int64_t)d.batch * G.H_out * G.W_out + BM - 1) / BM);
-    int rc;
-    if (d.residual) {
-        static DeviceOnce once;
-        auto kernel = conv1x1_ws_kernel<DT, BM, BN, true>;
-        rc = once.configure(kernel, 160 * 1024);
+    const auto go = [&](auto has_res) {              // the kernel with and without the shortcut read
+        constexpr auto kernel = conv1x1_ws_kernel<DT, BM, BN, decltype(has_res)::value>;
+        const int rc = allow_lds<kernel>(160 * 1024);
         if (rc != GPP_OK) return rc;
         kernel<<<dim3(256), dim3(512), lds, st>>>(d, n_mtiles);
-    } else {
-        static DeviceOnce once;
-        auto kernel = conv1x1_ws_kernel<DT, BM, BN, false>;
-        rc = once.configure(kernel, 160 * 1024);
-        if (rc != GPP_OK) return rc;
-        kernel<<<dim3(256), dim3(512), lds, st>>>(d, n_mtiles);
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GPP_OK : (int)e;
+        return last_launch_rc();
+    };
+    return d.residual ? go(std::true_type()) : go(std::false_type());
 }
 
 // One tile of the gathered-row form: the grid of the dense launch with this tile (every pixel could be listed), the plain loop on a
@@ -2468,141 +2417,81 @@ int launch_gather(gpp_conv_desc& d, hipStream_t st)
     }
     constexpr int BMS = stage_rows(BM, WM * WN);
     constexpr int lds = STAGES * (BMS + BN) * kRowBytes;
-    static DeviceOnce once;
-    auto kernel = conv_gather_kernel<DT, BM, BN, WM, WN, STAGES, XIN>;
-    int rc = once.configure(kernel, lds);
+    constexpr auto kernel = conv_gather_kernel<DT, BM, BN, WM, WN, STAGES, XIN>;
+    const int rc = allow_lds<kernel>(lds);
     if (rc != GPP_OK) return rc;
     const int tiles = prepare<BM, BN>(d);
     if (tiles < 0) return tiles;
     const int n_tiles = (d.C_out + BN - 1) / BN;
     kernel<<<dim3((unsigned)(tiles * n_tiles)), dim3(64 * WM * WN), lds, st>>>(d);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GPP_OK : (int)e;
+    return last_launch_rc();
 }
 
-// the tiles of the gathered-row form (gpp_conv2d_tile_candidates lists the same codes): short and narrow, so that a few thousand rows
-// still field a few hundred workgroups; 64 x 160 on a 4 x 1 layout for the 144 regression channels.  6000000 + BM * 1000 + BN: the
-// two-deep ring; 7000000 + ...: the four-deep ring (three K-steps of tile loads in flight) -- a gathered launch fields at most about one
-// workgroup per CU, and a workgroup alone on its CU is bound by the latency of its own loads, K-step after K-step
+// One entry of the catalogue (conv_tiles.h) for element type DT, dense form: GPP_ERR_UNSUPPORTED where this type or input form has no
+// instantiation of it.  (x3 types: launch<..., XIN = false> carries both input forms of a plain tile, XIN = true the pre-split one alone.)
+template <int DT, int FORM, int OWNER, int BM, int BN, int WM, int WN, int STAGES>
+int run_tile(gpp_conv_desc& d, hipStream_t st)
+{
+    if constexpr (FORM == gpp_tiles::GATHER) {
+        return GPP_ERR_BAD_ARG;                                   // (dispatch_gather's codes mean nothing to a dense launch)
+    } else if constexpr (!gpp_tiles::owner_has(OWNER, kF32Storage<DT>, kX3<DT>)) {
+        // (pinned by tests/golden/tile_table.json: the 16-bit types have always answered the x3 types' codes like unknown ones)
+        return kF32Storage<DT> ? GPP_ERR_UNSUPPORTED : GPP_ERR_BAD_ARG;
+    } else {
+        constexpr bool XIN = kX3<DT> && gpp_tiles::x3_wants_split_input(FORM, OWNER);
+        if (XIN && !(d.x3_split & GPP_X3_IN)) return GPP_ERR_UNSUPPORTED;
+        if constexpr (FORM == gpp_tiles::DUAL) return launch_dual<DT>(d, st);
+        else if constexpr (FORM == gpp_tiles::MIX) return launch_mix<DT, BM, BN>(d, st);
+        else if constexpr (FORM == gpp_tiles::WS) return d.guard ? GPP_ERR_UNSUPPORTED : launch_ws<DT, BM, BN>(d, st);      // (conv1x1_ws_kernel reads no guard)
+        else return launch<DT, BM, BN, WM, WN, STAGES, gpp_tiles::tile_pipelined(FORM, BM, BN, kF32Storage<DT>), XIN>(d, st);
+    }
+}
+
+#define GPP_RUN_TILE(code, form, owner, bm, bn, wm, wn, stages) \
+    case code: return run_tile<DT, gpp_tiles::form, gpp_tiles::owner, bm, bn, wm, wn, stages>(d, st);
+#define GPP_RUN_GATHER(code, form, owner, bm, bn, wm, wn, stages) \
+    case code: if constexpr (gpp_tiles::form == gpp_tiles::GATHER) return launch_gather<DT, bm, bn, wm, wn, stages>(d, st); else break;
+#define GPP_RUN_PREACT(code, form, owner, bm, bn, wm, wn, stages) \
+    case code: return launch_preact<DT, bm, bn, wm, wn>(d, in_scale, in_shift, st);
+
+// 0 = 128 x 128, or 128 x 64 for C_out <= 64
+template <int DT>
+int dispatch_preact(gpp_conv_desc& d, const float* in_scale, const float* in_shift, hipStream_t st)
+{
+    switch (d.tile_hint) {
+        case 0: return d.C_out <= 64 ? launch_preact<DT, 128, 64, 2, 2>(d, in_scale, in_shift, st)
+                                     : launch_preact<DT, 128, 128, 2, 2>(d, in_scale, in_shift, st);
+        GPP_CONV_TILES(GPP_TILE_NONE, GPP_TILE_NONE, GPP_RUN_PREACT)
+        default: return GPP_ERR_BAD_ARG;
+    }
+}
+
+// 0 = 64 x 64 on the two-deep ring; the dense forms' codes mean nothing here
 template <int DT>
 int dispatch_gather(gpp_conv_desc& d, hipStream_t st)
 {
     switch (d.tile_hint) {
-        case 0:
-        case 6064064: return launch_gather<DT, 64, 64, 2, 2, 2>(d, st);
-        case 6032064: return launch_gather<DT, 32, 64, 2, 2, 2>(d, st);
-        case 6064160: return launch_gather<DT, 64, 160, 4, 1, 2>(d, st);
-        case 7064064: return launch_gather<DT, 64, 64, 2, 2, 4>(d, st);
-        case 7032064: return launch_gather<DT, 32, 64, 2, 2, 4>(d, st);
-        case 7064160: return launch_gather<DT, 64, 160, 4, 1, 4>(d, st);
-        default: return GPP_ERR_BAD_ARG;
+        case 0: return launch_gather<DT, 64, 64, 2, 2, 2>(d, st);
+        GPP_CONV_TILES(GPP_RUN_GATHER, GPP_RUN_GATHER, GPP_TILE_NONE)
+        default: break;
     }
+    return GPP_ERR_BAD_ARG;
 }
 
 template <int DT>
 int dispatch(gpp_conv_desc& d, hipStream_t st)
 {
-    if (d.guard && d.tile_hint >= 4000000 && d.tile_hint < 5000000) return GPP_ERR_UNSUPPORTED;      // (conv1x1_ws_kernel reads no guard)
-    switch (d.tile_hint) {               // explicit choices (BM*1000 + BN, or the legacy codes): what the host-side autotuner hands in
-        case 64:
-        case 128064: return launch<DT, 128, 64, 2, 2, 2, false>(d, st);
-        case 64064: return launch<DT, 64, 64, 2, 2, 2, false>(d, st);
-        case 96064: return launch<DT, 96, 64, 2, 2, 2, false>(d, st);
-        case 160064: return launch<DT, 160, 64, 2, 2, 2, false>(d, st);
-        case 192064: return launch<DT, 192, 64, 2, 2, 2, false>(d, st);
-        case 64128: return launch<DT, 64, 128, 2, 2, 2, false>(d, st);
-        case 96128: return launch<DT, 96, 128, 2, 2, 2, false>(d, st);
-        case 128:
-        case 128128:
 #ifdef GPP_STAMPS
-            if constexpr (!kF32Storage<DT>) if (d.reserved & 4) return launch<DT, 128, 128, 2, 2, 2, true>(d, st);
+    // diagnostic flips: the 128 x 128 tile with the pipelined loop, the 256 x 256 tile with the plain one (16-bit types)
+    if constexpr (!kF32Storage<DT>) {
+        if ((d.reserved & 4) && (d.tile_hint == 128 || d.tile_hint == 128128)) return launch<DT, 128, 128, 2, 2, 2, true>(d, st);
+        if ((d.reserved & 8) && (d.tile_hint == 512 || d.tile_hint == 256256)) return launch<DT, 256, 256, 2, 4, 2, false>(d, st);
+    }
 #endif
-            return launch<DT, 128, 128, 2, 2, 2, false>(d, st);
-        case 160128: return launch<DT, 160, 128, 2, 2, 2, false>(d, st);
-        case 192128: return launch<DT, 192, 128, 2, 2, 2, false>(d, st);
-        case 224128: return launch<DT, 224, 128, 2, 2, 2, false>(d, st);
-        // N-remainder tiles (4 x 1 wavefronts, wave tile BM/4 x 160): layers whose C_out is far from a multiple of 128
-        // (regression outputs: 144 -> 160 instead of 256 columns; measured 200 -> 162 us).  96-wide tiles and 3/4-deep
-        // LDS rings on the small tiles were measured too and lost everywhere (fewer workgroups per CU).
-        case 128160: return launch<DT, 128, 160, 4, 1, 2, false>(d, st);
-        case 192160:
-            if constexpr (kX3<DT>) {
-                // float32-input form of this tile: 3 registers over the budget (scratch); only the pre-split form exists
-                if (!(d.x3_split & GPP_X3_IN)) return GPP_ERR_UNSUPPORTED;
-                return launch<DT, 192, 160, 4, 1, 2, false, true>(d, st);
-            } else {
-                return launch<DT, 192, 160, 4, 1, 2, false>(d, st);
-            }
+    switch (d.tile_hint) {               // explicit choices: what the host-side autotuner hands in
+        GPP_CONV_TILES(GPP_RUN_TILE, GPP_RUN_TILE, GPP_TILE_NONE)
         case 0: break;
-        default:
-            // the software-pipelined / 8-wavefront forms exist for the 16-bit types only: the float32 path is bound by the
-            // matrix pipe (8x the MFMA time per staged byte) and gains nothing from them
-            if constexpr (!kF32Storage<DT>) {
-                switch (d.tile_hint) {
-                    case 256: return launch<DT, 256, 128, 4, 2, 3, false>(d, st);          // 3-deep ring, experiments only
-                    case 1128128: return launch<DT, 128, 128, 2, 2, 2, true>(d, st);        // 1000000 + ...: the pipelined main loop
-                    case 1192128: return launch<DT, 192, 128, 2, 2, 2, true>(d, st);
-                    case 1128256: return launch<DT, 128, 256, 2, 4, 2, true>(d, st);
-                    case 1192256: return launch<DT, 192, 256, 2, 4, 2, true>(d, st);
-                    case 1192160: return launch<DT, 192, 160, 4, 1, 2, true>(d, st);
-                    case 1128160: return launch<DT, 128, 160, 4, 1, 2, true>(d, st);
-                    case 1192096: return launch<DT, 192, 96, 4, 1, 2, true>(d, st);          // 96-channel outputs (the classification logits)
-                    case 2256256: return launch_dual<DT>(d, st);            // 256 x 256 tiles + 512 x 128 tiles for the last 128 columns, one grid
-                    case 512:
-                    case 256256:
-#ifdef GPP_STAMPS
-                        if (d.reserved & 8) return launch<DT, 256, 256, 2, 4, 2, false>(d, st);
-#endif
-                        return launch<DT, 256, 256, 2, 4, 2, true>(d, st);
-                    default: return GPP_ERR_BAD_ARG;
-                }
-            } else {
-                // GPP_BF16X3 spends 3 MFMAs per fragment pair: with 4-wavefront tiles its LDS traffic equals its matrix time;
-                // the 8-wavefront 256-column tiles (plain two-buffer loop) halve the LDS bytes per MFMA
-                if constexpr (kX3<DT>) {
-                    if (d.x3_split & GPP_X3_IN) {
-                        // the software-pipelined three-phase loop: pre-split input maps only (1000000 + tile, as for the 16-bit types)
-                        switch (d.tile_hint) {
-                            case 1256256: return launch<DT, 256, 256, 2, 4, 2, true, true>(d, st);
-                            case 1224256: return launch<DT, 224, 256, 2, 4, 2, true, true>(d, st);      // (224 / 160 rows: staged as 256 / 192, see BMS)
-                            case 1192256: return launch<DT, 192, 256, 2, 4, 2, true, true>(d, st);
-                            case 1160256: return launch<DT, 160, 256, 2, 4, 2, true, true>(d, st);
-                            case 1128256: return launch<DT, 128, 256, 2, 4, 2, true, true>(d, st);
-                            case 1192128: return launch<DT, 192, 128, 2, 2, 2, true, true>(d, st);
-                            case 1128128: return launch<DT, 128, 128, 2, 2, 2, true, true>(d, st);
-                            case 1128160: return launch<DT, 128, 160, 4, 1, 2, true, true>(d, st);      // 144-channel outputs: three-phase loop on a 4 x 1 layout
-                            case 1192096: return launch<DT, 192, 96, 4, 1, 2, true, true>(d, st);       // 96-channel outputs, same layout
-                            case 2256256: return launch_dual<DT>(d, st);      // C_out = 256 k + 128: the dual-shape grid
-                            case 3256224: return launch_mix<DT, 256, 224>(d, st);       // 3000000 + BMA * 1000 + BMB: two tile heights, one grid
-                            case 3192160: return launch_mix<DT, 192, 160>(d, st);
-                            case 4128064: return launch_ws<DT, 128, 64>(d, st);        // 4000000 + BM * 1000 + BN: weight-stationary persistent 1 x 1
-                            case 4064064: return launch_ws<DT, 64, 64>(d, st);
-                            case 4128128: return launch_ws<DT, 128, 128>(d, st);
-                            case 4064128: return launch_ws<DT, 64, 128>(d, st);
-                            // 5000000 + BM * 1000 + BN: the plain loop on a FOUR-deep LDS ring (three K-steps of LDS-DMA in flight ahead of the one
-                            // computed).  For the launches that field at most one workgroup per CU anyway -- deep-K, small-M layers, every layer
-                            // at batch 1 -- whose K-steps are bound by the latency of their own tile loads; where more workgroups would share a CU
-                            // the larger footprint loses (round 2: 1.6 x slower at B = 8) and the tuner keeps the two-deep tiles.
-                            case 5064064: return launch<DT, 64, 64, 2, 2, 4, false, true>(d, st);
-                            case 5096064: return launch<DT, 96, 64, 2, 2, 4, false, true>(d, st);
-                            case 5064128: return launch<DT, 64, 128, 2, 2, 4, false, true>(d, st);
-                            case 5096128: return launch<DT, 96, 128, 2, 2, 4, false, true>(d, st);
-                            case 5128128: return launch<DT, 128, 128, 2, 2, 4, false, true>(d, st);
-                            default: break;
-                        }
-                    }
-                    if (d.tile_hint == 256256) return launch<DT, 256, 256, 2, 4, 2, false>(d, st);
-                    if (d.tile_hint == 192256) return launch<DT, 192, 256, 2, 4, 2, false>(d, st);
-                    if (d.tile_hint == 128256) return launch<DT, 128, 256, 2, 4, 2, false>(d, st);
-                }
-                switch (d.tile_hint) {
-                    case 256: case 1128128: case 1192128: case 1128256: case 1192256: case 1192160: case 1128160: case 2256256: case 512: case 256256: case 1256256:
-                    case 192256: case 128256: case 1192096: case 3256224: case 3192160: case 1224256: case 1160256: case 4128064: case 4064064: case 4128128: case 4064128:
-                    case 5064064: case 5096064: case 5064128: case 5096128: case 5128128:
-                        return GPP_ERR_UNSUPPORTED;
-                    default: return GPP_ERR_BAD_ARG;
-                }
-            }
+        default: return GPP_ERR_BAD_ARG;
     }
     // ---- default heuristic (tile_hint == 0)
     if (d.C_out <= 64 || (d.C_out % 128 != 0 && d.C_out % 128 <= 64)) return launch<DT, 128, 64, 2, 2, 2, false>(d, st);
@@ -2621,26 +2510,25 @@ int dispatch(gpp_conv_desc& d, hipStream_t st)
     return launch<DT, 128, 128, 2, 2, 2, false>(d, st);
 }
 
+// The fused 3 x 3 + 1 x 1 pair: one launcher for the 16-bit kernel and the x3 one (ESZ bytes per stored element, LDS bytes of dynamic LDS)
+template <auto KERNEL, int BM, int CMID, int ESZ, int LDS>
+int launch_tail_as(gpp_conv_desc& d1, gpp_conv_desc& d2, hipStream_t st)
+{
+    int rc = allow_lds<KERNEL>(LDS);
+    if (rc == GPP_OK) rc = set_input_extent(d1, ESZ);
+    if (rc == GPP_OK) rc = set_weight_extent(d1, 9 * CMID, ESZ);
+    if (rc == GPP_OK) rc = set_weight_extent(d2, CMID, ESZ);
+    if (rc != GPP_OK) return rc;
+    const gpp_conv_group& G = d1.groups[0];
+    const int64_t rows = (int64_t)d1.batch * G.H_out * G.W_out;
+    KERNEL<<<dim3((unsigned)((rows + BM - 1) / BM)), dim3(256), LDS, st>>>(d1, d2);
+    return last_launch_rc();
+}
+
 template <int DT, int BM, int CMID>
 int launch_tail(gpp_conv_desc& d1, gpp_conv_desc& d2, hipStream_t st)
 {
-    constexpr int lds = 2 * (BM + CMID) * kRowBytes;
-    static DeviceOnce once;
-    auto kernel = bottleneck_tail_kernel<DT, BM, CMID>;
-    int rc = once.configure(kernel, lds);
-    if (rc != GPP_OK) return rc;
-    const gpp_conv_group& G = d1.groups[0];
-    const int64_t in_elems = G.in_off + (int64_t)(d1.batch - 1) * G.in_bstride + ((int64_t)G.H_in * G.W_in - 1) * d1.in_pitch + d1.C_in;
-    const int64_t w1_bytes = (int64_t)d1.weight_rows * 9 * CMID * 2, w2_bytes = (int64_t)d2.weight_rows * CMID * 2;
-    if (G.in_off < 0 || G.in_bstride < 0 || in_elems * 2 >= (1LL << 31) || w1_bytes >= (1LL << 31) || w2_bytes >= (1LL << 31))
-        return GPP_ERR_UNSUPPORTED;
-    d1.in_bytes = (int32_t)(in_elems * 2);
-    d1.weight_bytes = (int32_t)w1_bytes;
-    d2.weight_bytes = (int32_t)w2_bytes;
-    const int64_t rows = (int64_t)d1.batch * G.H_out * G.W_out;
-    kernel<<<dim3((unsigned)((rows + BM - 1) / BM)), dim3(256), lds, st>>>(d1, d2);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GPP_OK : (int)e;
+    return launch_tail_as<bottleneck_tail_kernel<DT, BM, CMID>, BM, CMID, 2, 2 * (BM + CMID) * kRowBytes>(d1, d2, st);
 }
 
 template <int DT, int BM, int CMID>
@@ -2648,23 +2536,7 @@ int launch_tail_x3(gpp_conv_desc& d1, gpp_conv_desc& d2, hipStream_t st)
 {
     constexpr int KC = CMID / 32;
     constexpr int ring = 2 * (BM + CMID) * kRowBytes, phase2 = KC * BM * kRowBytes + KC * 128 * kRowBytes;
-    constexpr int lds = ring > phase2 ? ring : phase2;
-    static DeviceOnce once;
-    auto kernel = bottleneck_tail_x3_kernel<DT, BM, CMID>;
-    int rc = once.configure(kernel, lds);
-    if (rc != GPP_OK) return rc;
-    const gpp_conv_group& G = d1.groups[0];
-    const int64_t in_elems = G.in_off + (int64_t)(d1.batch - 1) * G.in_bstride + ((int64_t)G.H_in * G.W_in - 1) * d1.in_pitch + d1.C_in;
-    const int64_t w1_bytes = (int64_t)d1.weight_rows * 9 * CMID * 4, w2_bytes = (int64_t)d2.weight_rows * CMID * 4;
-    if (G.in_off < 0 || G.in_bstride < 0 || in_elems * 4 >= (1LL << 31) || w1_bytes >= (1LL << 31) || w2_bytes >= (1LL << 31))
-        return GPP_ERR_UNSUPPORTED;
-    d1.in_bytes = (int32_t)(in_elems * 4);
-    d1.weight_bytes = (int32_t)w1_bytes;
-    d2.weight_bytes = (int32_t)w2_bytes;
-    const int64_t rows = (int64_t)d1.batch * G.H_out * G.W_out;
-    kernel<<<dim3((unsigned)((rows + BM - 1) / BM)), dim3(256), lds, st>>>(d1, d2);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GPP_OK : (int)e;
+    return launch_tail_as<bottleneck_tail_x3_kernel<DT, BM, CMID>, BM, CMID, 4, (ring > phase2 ? ring : phase2)>(d1, d2, st);
 }
 
 // x3 types: C = 64 only (at C = 128 the intermediate tile and a W2 tile take 128 KB of LDS: one workgroup per CU)

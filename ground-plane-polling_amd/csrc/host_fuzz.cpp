@@ -15,6 +15,8 @@
 
 #include <vector>
 
+#include <hip/hip_runtime_api.h>
+
 #include "gpp.h"
 
 static long g_rc_hist[3] = {0, 0, 0};      // GPP_OK, GPP_ERR_*, hipError_t
@@ -33,6 +35,12 @@ int main(int argc, char** argv)
 {
     if (argc < 2) { fprintf(stderr, "usage: %s records.bin  (record = %zu bytes, gpp_conv_desc = %zu)\n", argv[0], sizeof(Rec), sizeof(gpp_conv_desc)); return 2; }
     if (!strcmp(argv[1], "--sizes")) { printf("%zu %zu\n", sizeof(Rec), sizeof(gpp_conv_desc)); return 0; }
+    // a descriptor that passes every check is LAUNCHED where a device is visible -- on fuzzed pointers: this driver is for machines without one
+    int devices = 0;
+    if (hipGetDeviceCount(&devices) == hipSuccess && devices > 0) {
+        fprintf(stderr, "%d HIP device(s) visible: run with HIP_VISIBLE_DEVICES=-1 ROCR_VISIBLE_DEVICES= (tests/test_host_fuzz.py does)\n", devices);
+        return 2;
+    }
     FILE* f = fopen(argv[1], "rb");
     if (!f) { perror("open"); return 2; }
     Rec r;

@@ -235,7 +235,9 @@ def conv_desc(inputs, outputs, weight, bias, KH, KW, C_in, C_out, stride=1, pad=
 
 
 def default_split(KH, KW, C_in, C_out, pixels_per_image):
-    """ the library's own split-K rule (csrc/conv_igemm.hip split_rule), restated: deep-K layers whose per-image grid is tiny at any batch """
+    """ the library's own split-K rule (csrc/conv_igemm.hip split_rule), restated: deep-K layers whose per-image grid is tiny at any batch.
+    The plan builder needs the factor before a descriptor exists (the sparse heads' choice of form, latency_split's floor), so the
+    restatement stays; tests/test_plan_cpu.py holds it to gpp_conv2d_split_rule on every descriptor of every plan, both plan modes """
     tiles = -(-pixels_per_image // 128) * -(-C_out // 128)
     kdepth = KH * KW * C_in
     if tiles > 24 or kdepth < 3072:

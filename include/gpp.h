@@ -151,23 +151,17 @@ typedef struct gpp_conv_desc {
     int32_t weight_rows;
     int32_t relu;
     int32_t n_groups;
-    int32_t tile_hint;              /* 0 = library heuristic; BM*1000 + BN forces a block tile (64..224 x 64/128, 128/192 x 160,
-                                       256256), + 1000000 = the software-pipelined main loop (128128, 192128, 128256, 192256,
-                                       192160, 128160, 192096), 2256256 = 256256 plus 512 x 128 tiles for the last 128 columns in one grid
-                                       (C_out = 256 k + 128 only); legacy codes 64 / 128 / 256 / 512; anything else: GPP_ERR_BAD_ARG.
-                                       GPP_BF16X3 / GPP_F16X3 (the same tile set, the same loops): the plain tiles, 128256 / 192256 / 256256
-                                       (8 wavefronts), and on a pre-split input map (x3_split & GPP_X3_IN) the pipelined 1128128, 1192128,
-                                       1128256, 1160256, 1192256, 1224256, 1256256, 1128160, 1192096 and 2256256; 192160 exists on pre-split inputs only;
-                                       3256224 / 3192160 (3000000 + BMA * 1000 + BMB, C_out % 256 == 0, pre-split inputs): 256-column tiles
-                                       of two heights in ONE grid -- whole rounds of BMA-row tiles, the rest in BMB-row tiles -- against the
-                                       round quantisation of one-workgroup-per-CU tiles (GPP_ERR_UNSUPPORTED where it gains nothing);
-                                       4128064 / 4064064 / 4128128 / 4064128 (4000000 + BM * 1000 + BN; 1 x 1, stride 1, one map, pre-split input / shortcut,
-                                       C_out a multiple of BN with 32 % (C_out / BN) == 0, K small enough for BN x K weights + the activation ring in 160 KB of LDS): the
-                                       weight-stationary persistent form of the shallow 1 x 1 layers;
-                                       5064064 / 5096064 / 5064128 / 5096128 / 5128128 (5000000 + BM * 1000 + BN; x3 types, pre-split inputs): the plain loop on a
-                                       four-deep LDS ring -- for launches of at most about one workgroup per CU (deep-K small-M layers, batch 1), whose
-                                       K-steps are bound by the latency of their own tile loads.
-                                       gpp_conv2d_tile_candidates lists what a given layer accepts; see gpp_conv2d_autotune */
+    int32_t tile_hint;              /* 0 = library heuristic; otherwise a block tile, by family:
+                                         BM * 1000 + BN          the plain loop (legacy aliases 64 / 128 / 256 / 512)
+                                         1000000 + BM * 1000 + BN   the software-pipelined loop
+                                         2256256                 256 x 256 tiles + 512 x 128 tiles for the last 128 columns, one grid
+                                         3000000 + BMA * 1000 + BMB  256-column tiles of two heights in one grid
+                                         4000000 + BM * 1000 + BN   the weight-stationary persistent 1 x 1
+                                         5000000 + BM * 1000 + BN   the plain loop on a four-deep LDS ring
+                                         6000000 / 7000000 + BM * 1000 + BN   gathered rows (gather_rows), two- / four-deep ring
+                                       A code nobody has: GPP_ERR_BAD_ARG; one this element type, input form or layer cannot run:
+                                       GPP_ERR_UNSUPPORTED.  The catalogue is csrc/conv_tiles.h; gpp_conv2d_tile_candidates lists
+                                       what a layer accepts; see gpp_conv2d_autotune */
     int32_t reserved;               /* must be 0 (anything else: GPP_ERR_BAD_ARG).  Only the diagnostic -DGPP_STAMPS build of the
                                        library (make stamps; tools/bench_conv.py) reads it: bit 0 skip the tile loads, bit 1 skip
                                        the LDS reads + MFMA, bit 2 / 3 flip the pipelined form of the 128128 / 256256 tile,

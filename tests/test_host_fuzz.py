@@ -22,6 +22,9 @@ from hypothesis import strategies as st
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'ground-plane-polling_amd', 'csrc')
 DRIVER = os.path.join(ROOT, 'ground-plane-polling_amd', 'lib', 'asan', 'gpp_host_fuzz')
+# the driver runs where it sees no device (and refuses to start where it sees one): a descriptor that passes every check would otherwise
+# be launched, on fuzzed pointers
+NO_DEVICE = {'HIP_VISIBLE_DEVICES': '-1', 'ROCR_VISIBLE_DEVICES': ''}
 
 from keras_retinanet_3D.backend import hip  # noqa: E402
 
@@ -32,7 +35,7 @@ def driver():
         pytest.skip('no hipcc: the sanitizer build of the host code cannot be made here')
     rc = subprocess.run(['make', '-C', CSRC, '-j8', 'asan'], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True)
     assert rc.returncode == 0, rc.stdout[-3000:]
-    sizes = subprocess.run([DRIVER, '--sizes'], stdout=subprocess.PIPE, universal_newlines=True, env=dict(os.environ, ASAN_OPTIONS='detect_leaks=0'))
+    sizes = subprocess.run([DRIVER, '--sizes'], stdout=subprocess.PIPE, universal_newlines=True, env=dict(os.environ, ASAN_OPTIONS='detect_leaks=0', **NO_DEVICE))
     rec, desc = (int(v) for v in sizes.stdout.split())
     assert desc == ctypes.sizeof(hip.ConvDesc) and rec == 16 + 3 * desc        # the ctypes mirror and the C struct agree
     return DRIVER
@@ -115,7 +118,7 @@ def run_driver(driver, blob, tmp_path, name):
     path = os.path.join(str(tmp_path), name)
     with open(path, 'wb') as f:
         f.write(blob)
-    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0:halt_on_error=1:abort_on_error=0', UBSAN_OPTIONS='halt_on_error=1:print_stacktrace=1')
+    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=0:halt_on_error=1:abort_on_error=0', UBSAN_OPTIONS='halt_on_error=1:print_stacktrace=1', **NO_DEVICE)
     return subprocess.run([driver, path], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, env=env, timeout=300)
 
 
