@@ -39,10 +39,18 @@ int validate(const gpp_conv_desc& d)
     if (d.reserved != 0) return GPP_ERR_BAD_ARG;                    // diagnostic switches exist in -DGPP_STAMPS builds only
 #endif
     if (d.reserved2 != 0 || (d.x3_split & ~(GPP_X3_IN | GPP_X3_OUT | GPP_X3_RES))) return GPP_ERR_BAD_ARG;
-    if (d.reserved3 != 0 || (d.gather_rows != nullptr) != (d.gather_counts != nullptr)) return GPP_ERR_BAD_ARG;
-    if (((uintptr_t)d.gather_rows | (uintptr_t)d.gather_counts | (uintptr_t)d.guard) & 3) return GPP_ERR_ALIGN;
-    // the gathered-row form: stride 1, no shortcut, float32 output, never split (split-K would change the summation order of a row)
-    if (d.gather_rows && (d.stride != 1 || d.residual || !d.out_f32 || d.split_k > 1)) return GPP_ERR_UNSUPPORTED;
+    if (d.reserved3 != 0 || d.reserved4 != 0 || (d.gather_rows != nullptr) != (d.gather_counts != nullptr)) return GPP_ERR_BAD_ARG;
+    // both forms behind one call (tower_rows / tower_counts / tower_flag): all three or none, and neither a list nor a guard of the caller's
+    const bool tower = d.tower_rows || d.tower_counts || d.tower_flag;
+    if (tower && (!d.tower_rows || !d.tower_counts || !d.tower_flag || d.gather_rows || d.guard)) return GPP_ERR_BAD_ARG;
+    if (!tower && d.tower_tile != 0) return GPP_ERR_BAD_ARG;
+    if (((uintptr_t)d.gather_rows | (uintptr_t)d.gather_counts | (uintptr_t)d.guard | (uintptr_t)d.tower_rows | (uintptr_t)d.tower_counts |
+         (uintptr_t)d.tower_flag) & 3)
+        return GPP_ERR_ALIGN;
+    // the gathered-row form: stride 1, no shortcut, never split (split-K would change the summation order of a row); float32 output, or -- a
+    // layer between two convolutions -- the pre-split maps of an x3 type with whole 256-column tiles (gpp_tiles::gather_pipe_can_run)
+    if (d.gather_rows && (d.stride != 1 || d.residual || d.split_k > 1)) return GPP_ERR_UNSUPPORTED;
+    if (((d.gather_rows && !d.out_f32) || tower) && !gpp_tiles::gather_pipe_can_run(d)) return GPP_ERR_UNSUPPORTED;
     if (d.x3_split && !is_x3(d.dtype)) return GPP_ERR_BAD_ARG;
     if (d.out_scale && d.dtype != GPP_F16X3) return GPP_ERR_BAD_ARG;
     if ((d.x3_split & GPP_X3_OUT) && (d.out_f32 || d.C_out % 32 != 0 || d.out_pitch % 32 != 0)) return GPP_ERR_UNSUPPORTED;
@@ -109,6 +117,20 @@ int dispatch_any(gpp_conv_desc& d, hipStream_t st)
         if (d.split_k > 1) return GPP_ERR_UNSUPPORTED;
         return gpp_conv_gather_dispatch(d, st);
     }
+    if (d.tower_rows) {
+        // both forms on the stream, the device word chooses: the gathered launch works while it is 0, the dense one while it is 1 (the guard
+        // mechanism of the head output layers, here behind one call: the plan keeps ONE op for the layer)
+        if (d.split_k > 1) return GPP_ERR_UNSUPPORTED;
+        gpp_conv_desc rows = d, dense = d;
+        rows.gather_rows = d.tower_rows; rows.gather_counts = d.tower_counts; rows.tile_hint = d.tower_tile;
+        rows.guard = d.tower_flag; rows.guard_value = 0;
+        dense.guard = d.tower_flag; dense.guard_value = 1;
+        rows.tower_rows = rows.tower_counts = rows.tower_flag = dense.tower_rows = dense.tower_counts = dense.tower_flag = nullptr;
+        rows.tower_tile = dense.tower_tile = 0;
+        const int rc_rows = gpp_conv_gather_dispatch(rows, st);
+        if (rc_rows != GPP_OK) return rc_rows;
+        return dispatch_any(dense, st);
+    }
     switch (d.dtype) {
         case GPP_BF16: return gpp_conv_dispatch_bf16(d, st);
         case GPP_F16: return gpp_conv_dispatch_f16(d, st);
@@ -125,7 +147,7 @@ int tail_entry(const gpp_conv_desc* conv3x3, const gpp_conv_desc* conv1x1, int t
     int rc = validate(d1);
     if (rc == GPP_OK) rc = validate(d2);
     if (rc != GPP_OK) return rc;
-    if (d1.gather_rows || d2.gather_rows || d1.guard || d2.guard) return GPP_ERR_UNSUPPORTED;      // gpp_conv2d_igemm only
+    if (d1.gather_rows || d2.gather_rows || d1.guard || d2.guard || d1.tower_rows || d2.tower_rows) return GPP_ERR_UNSUPPORTED;      // gpp_conv2d_igemm only
     const gpp_conv_group &G1 = d1.groups[0], &G2 = d2.groups[0];
     // the pair this kernel fuses: 3x3 / stride 1 / pad 1 / C -> C (C = 64 or 128) feeding 1x1 / stride 1 / C -> multiple of 128
     if (d1.dtype == GPP_F32) return GPP_ERR_UNSUPPORTED;           // 16-bit storage types, and the x3 types on pre-split maps
@@ -158,7 +180,7 @@ int block_entry(const gpp_conv_desc* conv_a, const gpp_conv_desc* conv_b, const 
     if (rc == GPP_OK) rc = validate(d2);
     if (rc == GPP_OK) rc = validate(d3);
     if (rc != GPP_OK) return rc;
-    if (d1.gather_rows || d2.gather_rows || d3.gather_rows || d1.guard || d2.guard || d3.guard) return GPP_ERR_UNSUPPORTED;
+    if (d1.gather_rows || d2.gather_rows || d3.gather_rows || d1.guard || d2.guard || d3.guard || d1.tower_rows || d2.tower_rows || d3.tower_rows) return GPP_ERR_UNSUPPORTED;
     const gpp_conv_group &G1 = d1.groups[0], &G2 = d2.groups[0], &G3 = d3.groups[0];
     // the triple this kernel fuses, on pre-split maps of one x3 type: 1x1 / stride 1 or 2 / C_in -> C; 3x3 / stride 1 / pad 1 / C -> C (C = 64 or 128);
     // 1x1 / stride 1 / C -> a multiple of 128, + shortcut map of the output's size
@@ -279,7 +301,9 @@ static bool tile_is_candidate(const gpp_conv_desc* desc, const gpp_tiles::Entry&
 {
     using namespace gpp_tiles;
     const gpp_conv_desc& d = *desc;
-    if ((d.gather_rows != nullptr) != (t.form == GATHER)) return t.code == 0;      // gathered rows: their own tiles, and nobody else's
+    // gathered rows: their own tiles (the plain ones for a float32 output, the pipelined ones for a pre-split one), and nobody else's
+    const int gform = !d.gather_rows ? -1 : (d.out_f32 ? (int)GATHER : (int)GATHER_PIPE);
+    if ((gform >= 0 || t.form == GATHER || t.form == GATHER_PIPE) && t.form != gform) return t.code == 0 && gform >= 0;
     // ---- cannot run: nobody's instantiation, or the form's hard conditions (the dispatcher and the launchers refuse on the same functions)
     const bool x3_in = is_x3(d.dtype) && (d.x3_split & GPP_X3_IN);
     if (!owner_has(t.owner, f32_storage(d.dtype), is_x3(d.dtype))) return false;
@@ -297,6 +321,7 @@ static bool tile_is_candidate(const gpp_conv_desc* desc, const gpp_tiles::Entry&
     const auto pads_less_than = [&](int other) { return (d.C_out + bn - 1) / bn * bn < (d.C_out + other - 1) / other * other; };
     switch (t.form) {
         case GATHER: return bn != 160 || pads_less_than(64);                // 160 columns only where that cuts the N padding
+        case GATHER_PIPE: return gather_pipe_can_run(d);
         case DEEP: {                                                         // deep K, and a grid of at most ~one workgroup per CU
             int64_t tiles_m = 0;
             for (int g = 0; g < d.n_groups; ++g) tiles_m += ((int64_t)d.batch * d.groups[g].H_out * d.groups[g].W_out + t.bm - 1) / t.bm;
@@ -430,7 +455,7 @@ int preact_validate(gpp_conv_desc& d, const float* in_scale, const float* in_shi
     if (((uintptr_t)in_scale | (uintptr_t)in_shift) & 15) return GPP_ERR_ALIGN;
     if (d.KH != 1 || d.KW != 1 || d.stride != 1 || d.pad_top != 0 || d.pad_left != 0) return GPP_ERR_UNSUPPORTED;
     if (d.x3_split & GPP_X3_IN) return GPP_ERR_UNSUPPORTED;
-    if (d.gather_rows || d.guard) return GPP_ERR_UNSUPPORTED;          // gpp_conv2d_igemm only
+    if (d.gather_rows || d.guard || d.tower_rows) return GPP_ERR_UNSUPPORTED;          // gpp_conv2d_igemm only
     if (d.C_in > 4096) return GPP_ERR_UNSUPPORTED;               // the scale / shift table lives in LDS beside the ring
     return GPP_OK;
 }

@@ -466,13 +466,18 @@ constexpr int stage_rows(int BM, int NW) { return (BM + 8 * NW - 1) / (8 * NW) *
 // pixel -- the staging setup below (a_base / a_mask) and the epilogue's output address -- so the K order per output element, the epilogue
 // arithmetic and the stores of a listed pixel are those of the dense launch: the same bytes.  A workgroup whose first row lies at or past the
 // count returns before its first barrier.  Plain loop, stride 1, no residual, no split-K (validated on the host).
-template <int DT, int BM, int BN, int WM, int WN, int STAGES, bool PIPE, bool XIN = false, bool PRE = false, bool GATHER = false>
+// GLIVE (with GATHER; conv_gather_pipe_kernel: a tower layer on the dilated lists, pre-split maps, the three-phase loop): the row tiles are
+// numbered over the LISTED rows of the groups -- the kernel may run with a height the host did not choose, and the live workgroups are the
+// first of the grid -- instead of over every pixel (gpp_conv_group.tile_start is not read).  The same two places map a row to a pixel.
+template <int DT, int BM, int BN, int WM, int WN, int STAGES, bool PIPE, bool XIN = false, bool PRE = false, bool GATHER = false, bool GLIVE = false>
 __device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const int block_x, const int grid_x, const float* pre_s = nullptr,
                                                 const float* pre_t = nullptr)
 {
     static_assert(!XIN || kX3<DT>, "pre-split input maps: GPP_BF16X3 / GPP_F16X3");
     static_assert(!PRE || (!PIPE && !XIN && kF32Storage<DT>), "pre-activation: float32-sized input maps, plain loop");
-    static_assert(!GATHER || (!PIPE && !PRE), "gathered rows: plain loop");
+    static_assert(!GATHER || !PRE, "gathered rows: no pre-activation");
+    static_assert(!(GATHER && PIPE) || (kX3<DT> && XIN && GLIVE), "gathered rows on the pipelined loop: x3 types, pre-split maps, tiles over the listed rows");
+    static_assert(!GLIVE || GATHER, "tiles over the listed rows: the gathered form");
     // gpp_conv_desc.guard: a launch switched off by a value computed earlier on the device -- every workgroup leaves here (one uniform load)
     if (d.guard != nullptr && *(const volatile int32_t*)d.guard != d.guard_value) return;
     using E = Elem<DT>;
@@ -509,14 +514,19 @@ __device__ __forceinline__ void conv_igemm_body(const gpp_conv_desc& d, const in
     int tile_start = 0, row_begin = 0, H_in = 0, W_in = 0, H_out = 0, W_out = 0, H_res = 0, W_res = 0;
     int64_t in_off = 0, in_bs = 0, out_off = 0, out_bs = 0, res_off = 0, res_bs = 0;
     int list_begin = 0, list_next = 0, group = 0;      // GATHER: where this group's pixel list starts (the lists lie back to back, each sized for every pixel)
+    int live_start = 0;                                // GLIVE: first tile of group q = the tiles the listed rows of the groups before it take
 #pragma unroll
     for (int q = 0; q < GPP_MAX_GROUPS; ++q) {
+        const int first_tile = GLIVE ? live_start : d.groups[q].tile_start;
         if constexpr (GATHER) {
-            if (q < d.n_groups && mt >= d.groups[q].tile_start) { list_begin = list_next; group = q; }
+            if (q < d.n_groups && mt >= first_tile) { list_begin = list_next; group = q; }
             if (q < d.n_groups) list_next += d.batch * d.groups[q].H_out * d.groups[q].W_out;
         }
-        if (q < d.n_groups && mt >= d.groups[q].tile_start) {
-            tile_start = d.groups[q].tile_start;
+        if constexpr (GLIVE) {
+            if (q < d.n_groups) live_start += (min(max(d.gather_counts[q], 0), d.batch * d.groups[q].H_out * d.groups[q].W_out) + BM - 1) / BM;
+        }
+        if (q < d.n_groups && mt >= first_tile) {
+            tile_start = first_tile;
             row_begin = d.groups[q].row_begin;
             H_in = d.groups[q].H_in; W_in = d.groups[q].W_in;
             H_out = d.groups[q].H_out; W_out = d.groups[q].W_out;
@@ -1249,6 +1259,41 @@ template <int DT, int BM, int BN, int WM, int WN, int STAGES, bool XIN>
 __global__ __launch_bounds__(64 * WM * WN, 2) void conv_gather_kernel(const gpp_conv_desc d)
 {
     conv_igemm_body<DT, BM, BN, WM, WN, STAGES, false, XIN, false, true>(d, blockIdx.x, gridDim.x);
+}
+
+// The gathered-row form of a layer between two convolutions (GATHER + GLIVE above: pre-split input and output maps, 256-column tiles, the
+// three-phase loop).  rows = the tile height, 0 = chosen here: the host cannot know how many rows the device listed, and a fixed height pays
+// a whole round of the chip for a few rows past a multiple of it (gpp_tiles::gather_pipe_rows).  Every height computes a row's output with
+// the same K order: the choice never changes a byte.  A PERSISTENT grid: the launch has one workgroup per compute unit, and workgroup w
+// takes tiles w, w + grid, ... of the listed rows -- the order the hardware would hand them out in, without the thousand workgroups a grid
+// sized for every pixel launches only to return (each claims a whole CU's LDS first: 30 - 40 us of a 390 us launch, measured).
+template <int DT, int BM>
+__device__ __forceinline__ void conv_gather_pipe_tiles(const gpp_conv_desc& d, const int live)
+{
+    for (int t = blockIdx.x; t < live; t += gridDim.x) {
+        conv_igemm_body<DT, BM, 256, 2, 4, 2, true, true, false, true, true>(d, t, live);
+        __syncthreads();                                  // the next tile's first loads overwrite the ring
+    }
+}
+
+template <int DT>
+__global__ __launch_bounds__(512, 2) void conv_gather_pipe_kernel(const gpp_conv_desc d, const int rows)
+{
+    if (d.guard != nullptr && *(const volatile int32_t*)d.guard != d.guard_value) return;
+    int counts[GPP_MAX_GROUPS];
+#pragma unroll
+    for (int q = 0; q < GPP_MAX_GROUPS; ++q)
+        counts[q] = q < d.n_groups ? min(max(d.gather_counts[q], 0), d.batch * d.groups[q].H_out * d.groups[q].W_out) : 0;
+    const int bm = __builtin_amdgcn_readfirstlane(rows ? rows : gpp_tiles::gather_pipe_rows(counts, d.n_groups, d.C_out / 256));
+    const int live = __builtin_amdgcn_readfirstlane((int)gpp_tiles::gather_pipe_tiles(counts, d.n_groups, d.C_out / 256, bm));
+    switch (bm) {
+        case 128: conv_gather_pipe_tiles<DT, 128>(d, live); break;
+        case 160: conv_gather_pipe_tiles<DT, 160>(d, live); break;
+        case 192: conv_gather_pipe_tiles<DT, 192>(d, live); break;
+        case 224: conv_gather_pipe_tiles<DT, 224>(d, live); break;
+        case 256: conv_gather_pipe_tiles<DT, 256>(d, live); break;
+        default: break;
+    }
 }
 
 // gpp_conv2d_preact: the plain loop with the pre-activation prologue (PRE above); kernels of their own, so that conv_igemm_kernel and its
@@ -2427,12 +2472,37 @@ int launch_gather(gpp_conv_desc& d, hipStream_t st)
     return last_launch_rc();
 }
 
+// conv_gather_pipe_kernel: rows = 0 (the device's choice) or one of its heights; one workgroup per compute unit, or fewer where every pixel
+// listed would not give each a tile
+template <int DT>
+int launch_gather_pipe(gpp_conv_desc& d, int rows, hipStream_t st)
+{
+    if constexpr (!kX3<DT>) {
+        return kF32Storage<DT> ? GPP_ERR_UNSUPPORTED : GPP_ERR_BAD_ARG;
+    } else {
+        constexpr int BN = 256;
+        if (!gpp_tiles::gather_pipe_can_run(d)) return GPP_ERR_UNSUPPORTED;
+        constexpr int lds = 2 * (gpp_tiles::kGatherPipeMaxRows + BN) * kRowBytes;
+        constexpr auto kernel = conv_gather_pipe_kernel<DT>;
+        const int rc = allow_lds<kernel>(lds);
+        if (rc != GPP_OK) return rc;
+        const int ok = prepare<gpp_tiles::kGatherPipeMinRows, BN>(d);      // buffer extents, the weight-row check
+        if (ok < 0) return ok;
+        const int bm = rows ? rows : gpp_tiles::kGatherPipeMinRows;
+        int64_t tiles = 0;
+        for (int g = 0; g < d.n_groups; ++g) tiles += ((int64_t)d.batch * d.groups[g].H_out * d.groups[g].W_out + bm - 1) / bm;
+        tiles *= d.C_out / BN;
+        kernel<<<dim3((unsigned)(tiles < gpp_tiles::kGatherPipeCus ? tiles : gpp_tiles::kGatherPipeCus)), dim3(512), lds, st>>>(d, rows);
+        return last_launch_rc();
+    }
+}
+
 // One entry of the catalogue (conv_tiles.h) for element type DT, dense form: GPP_ERR_UNSUPPORTED where this type or input form has no
 // instantiation of it.  (x3 types: launch<..., XIN = false> carries both input forms of a plain tile, XIN = true the pre-split one alone.)
 template <int DT, int FORM, int OWNER, int BM, int BN, int WM, int WN, int STAGES>
 int run_tile(gpp_conv_desc& d, hipStream_t st)
 {
-    if constexpr (FORM == gpp_tiles::GATHER) {
+    if constexpr (FORM == gpp_tiles::GATHER || FORM == gpp_tiles::GATHER_PIPE) {
         return GPP_ERR_BAD_ARG;                                   // (dispatch_gather's codes mean nothing to a dense launch)
     } else if constexpr (!gpp_tiles::owner_has(OWNER, kF32Storage<DT>, kX3<DT>)) {
         // (pinned by tests/golden/tile_table.json: the 16-bit types have always answered the x3 types' codes like unknown ones)
@@ -2450,7 +2520,8 @@ int run_tile(gpp_conv_desc& d, hipStream_t st)
 #define GPP_RUN_TILE(code, form, owner, bm, bn, wm, wn, stages) \
     case code: return run_tile<DT, gpp_tiles::form, gpp_tiles::owner, bm, bn, wm, wn, stages>(d, st);
 #define GPP_RUN_GATHER(code, form, owner, bm, bn, wm, wn, stages) \
-    case code: if constexpr (gpp_tiles::form == gpp_tiles::GATHER) return launch_gather<DT, bm, bn, wm, wn, stages>(d, st); else break;
+    case code: if constexpr (gpp_tiles::form == gpp_tiles::GATHER) return d.out_f32 ? launch_gather<DT, bm, bn, wm, wn, stages>(d, st) : GPP_ERR_UNSUPPORTED; \
+               else if constexpr (gpp_tiles::form == gpp_tiles::GATHER_PIPE) return launch_gather_pipe<DT>(d, bm, st); else break;
 #define GPP_RUN_PREACT(code, form, owner, bm, bn, wm, wn, stages) \
     case code: return launch_preact<DT, bm, bn, wm, wn>(d, in_scale, in_shift, st);
 
@@ -2466,12 +2537,13 @@ int dispatch_preact(gpp_conv_desc& d, const float* in_scale, const float* in_shi
     }
 }
 
-// 0 = 64 x 64 on the two-deep ring; the dense forms' codes mean nothing here
+// 0 = 64 x 64 on the two-deep ring (float32 output) or the pipelined 256-column tiles at the device's height (pre-split output); the dense
+// forms' codes mean nothing here
 template <int DT>
 int dispatch_gather(gpp_conv_desc& d, hipStream_t st)
 {
     switch (d.tile_hint) {
-        case 0: return launch_gather<DT, 64, 64, 2, 2, 2>(d, st);
+        case 0: return d.out_f32 ? launch_gather<DT, 64, 64, 2, 2, 2>(d, st) : launch_gather_pipe<DT>(d, 0, st);
         GPP_CONV_TILES(GPP_RUN_GATHER, GPP_RUN_GATHER, GPP_TILE_NONE)
         default: break;
     }

@@ -23,6 +23,7 @@ enum Form {
     DEEP,        // 5000000 + ...: the plain loop on a four-deep ring
     GATHER,      // 6000000 / 7000000 + ...: the gathered-row form (gpp_conv_desc.gather_rows), two- / four-deep ring
     PREACT,      // gpp_conv2d_preact
+    GATHER_PIPE, // 8000000 + ...: the gathered-row form into a pre-split map (a layer between two convolutions): the three-phase pipelined loop
 };
 
 // who has an instantiation of it
@@ -100,6 +101,16 @@ struct Entry {
     T(7064064, GATHER, ALL, 64, 64, 2, 2, 4)                                                                                             \
     T(7032064, GATHER, ALL, 32, 64, 2, 2, 4)                                                                                             \
     T(7064160, GATHER, ALL, 64, 160, 4, 1, 4)                                                                                            \
+    /* gathered rows of a 256 k-column tower layer (pre-split maps, the three-phase loop; a persistent grid of one workgroup per CU that    \
+       takes the listed rows' tiles in order).  The host cannot know the count, and a fixed height pays up to a whole round for a few rows  \
+       past a multiple of the chip: 8000256 takes the height on the device (gather_pipe_rows below), and is the one the tuner and the      \
+       plans use; the fixed heights are reachable (tests, tools/bench_sparse_tower.py) */                                                   \
+    T(8000256, GATHER_PIPE, X3IN, 0, 256, 2, 4, 2)                                                                                       \
+    X(8128256, GATHER_PIPE, X3IN, 128, 256, 2, 4, 2)                                                                                     \
+    X(8160256, GATHER_PIPE, X3IN, 160, 256, 2, 4, 2)                                                                                     \
+    X(8192256, GATHER_PIPE, X3IN, 192, 256, 2, 4, 2)                                                                                     \
+    X(8224256, GATHER_PIPE, X3IN, 224, 256, 2, 4, 2)                                                                                     \
+    X(8256256, GATHER_PIPE, X3IN, 256, 256, 2, 4, 2)                                                                                     \
     X(64, PLAIN, ALL, 128, 64, 2, 2, 2)                                                                                                  \
     X(128, PLAIN, ALL, 128, 128, 2, 2, 2)                                                                                                \
     X(256, PLAIN, B16, 256, 128, 4, 2, 3)                /* 3-deep ring, experiments only */                                             \
@@ -123,6 +134,43 @@ constexpr bool owner_has(int owner, bool f32_storage, bool x3)
 constexpr bool x3_wants_split_input(int form, int owner)
 {
     return owner == X3IN || owner == ALL_X3IN || (form != PLAIN && form != GATHER && form != PREACT);
+}
+
+// the gathered-row form into a pre-split map: x3 types, pre-split input and output, stride 1, no shortcut, never split, whole 256-column tiles
+inline bool gather_pipe_can_run(const gpp_conv_desc& d)
+{
+    return (d.dtype == GPP_BF16X3 || d.dtype == GPP_F16X3) && (d.x3_split & (GPP_X3_IN | GPP_X3_OUT)) == (GPP_X3_IN | GPP_X3_OUT) && !d.out_f32 &&
+           d.stride == 1 && !d.residual && d.split_k <= 1 && d.C_out > 0 && d.C_out % 256 == 0;
+}
+
+// ... and the height its 8000256 code runs with, from the listed rows of every group (host and device: the kernel evaluates it on the counts it
+// finds).  One workgroup of any of these heights fills a compute unit, so a grid costs rounds x rows x (time per row of a tile of that
+// height): measured on the 512 -> 512 tower layer, a round takes 1.25 us per row with 128-row tiles and 0.98 with 256-row ones (the weight
+// tile's traffic is shared by more rows; profiles/sparse_tower/crossover.txt) -- a straight line between the two, in 1/128ths.  Ties go to
+// the SHORTER tile.  Heights: 128 .. 256 in steps of 32.  gather_pipe_tiles: the row tiles x column tiles the listed rows take at a height.
+constexpr int kGatherPipeMinRows = 128, kGatherPipeMaxRows = 256, kGatherPipeCus = 256;
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline long long gather_pipe_tiles(const int (&counts)[GPP_MAX_GROUPS], int n_groups, int n_tiles, int bm)
+{
+    long long tiles = 0;
+    for (int g = 0; g < GPP_MAX_GROUPS; ++g) tiles += g < n_groups ? (counts[g] + bm - 1) / bm : 0;
+    return tiles * n_tiles;
+}
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline int gather_pipe_rows(const int (&counts)[GPP_MAX_GROUPS], int n_groups, int n_tiles)
+{
+    int best = 0;
+    long long best_cost = 0;
+    for (int bm = kGatherPipeMinRows; bm <= kGatherPipeMaxRows; bm += 32) {
+        const long long rounds = (gather_pipe_tiles(counts, n_groups, n_tiles, bm) + kGatherPipeCus - 1) / kGatherPipeCus;
+        const long long cost = rounds * bm * (12416 - 17 * bm);          // (128 rows: 80 / 64 us per row, 256 rows: 63 / 64)
+        if (best == 0 || cost < best_cost) { best = bm; best_cost = cost; }
+    }
+    return best;
 }
 
 constexpr bool tile_pipelined(int form, int bm, int bn, bool f32_storage) { return form == PIPE || (!f32_storage && form == PLAIN && bm == 256 && bn == 256); }

@@ -757,6 +757,7 @@ struct LevelTable {
     int pix_begin[GPP_MAX_GROUPS];    // first pixel of a level inside an image's pyramid
     int word_begin[GPP_MAX_GROUPS];   // first bitmap word of a level (every level starts a word)
     int list_begin[GPP_MAX_GROUPS];   // first entry of a level's list
+    int width[GPP_MAX_GROUPS];        // W of a level (the dilated lists; 0 without them)
 };
 
 // one bit per (level, image, pixel): bit b * pix[l] + p of the level's words -- the value its list will hold.  The keys of a list are in
@@ -778,12 +779,48 @@ __global__ __launch_bounds__(256) void mark_pixels_kernel(const unsigned long lo
     }
 }
 
+// The dilated bitmap: bit (level, image, pixel) = some marked pixel among the 3 x 3 neighbourhood of that pixel INSIDE its image and level
+// (no bleed across an image's border, into the next image or the next level) -- the rows a 3 x 3, pad 1 layer on the marked pixels reads.
+// One thread per bit, a wavefront per two words: every word of the map is written whole (ballot), no atomics, whatever it held before.
+__global__ __launch_bounds__(256) void dilate_pixels_kernel(const uint32_t* __restrict__ bitmap, const LevelTable T, int B, int total_words,
+                                                            uint32_t* __restrict__ dilated)
+{
+    const int64_t gbit = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int word = (int)(gbit >> 5);
+    if (word >= total_words) return;                       // (whole wavefronts: a wavefront covers two words, words are handed out in pairs)
+    int l = 0;
+    for (int q = 1; q < T.n_levels; ++q) l = word >= T.word_begin[q] ? q : l;
+    const int bit = (int)(gbit - ((int64_t)T.word_begin[l] << 5));
+    const int pix = T.pix[l], W = T.width[l], H = pix / W;
+    bool on = false;
+    if (bit < B * pix) {
+        const int b = bit / pix, p = bit - b * pix;
+        const int y = p / W, x = p - y * W;
+        const uint32_t* words = bitmap + T.word_begin[l];
+        for (int dy = -1; dy <= 1; ++dy) {
+            const int yy = y + dy;
+            if (yy < 0 || yy >= H) continue;
+            for (int dx = -1; dx <= 1; ++dx) {
+                const int xx = x + dx;
+                if (xx < 0 || xx >= W) continue;
+                const int nb = b * pix + yy * W + xx;
+                on |= (words[nb >> 5] >> (nb & 31)) & 1u;
+            }
+        }
+    }
+    const unsigned long long mask = __ballot(on);
+    const int lane = threadIdx.x & 63;
+    if (lane == 0) dilated[word] = (uint32_t)mask;
+    if (lane == 32) dilated[word] = (uint32_t)(mask >> 32);
+}
+
 // one workgroup walks the levels' words in order: a popcount scan places every set bit, so each list comes out ascending; the words are
-// cleared on the way (the next call finds the map empty).  counts[l], then their sum at counts[GPP_MAX_GROUPS]; flag = the sum exceeds max_rows.
+// cleared on the way (the next call finds the map empty).  counts[l], then their sum at counts[GPP_MAX_GROUPS]; flag = the sum exceeds max_rows
+// (the dilated lists: or the flag of the lists they were dilated from is set, or_flag).
 constexpr int kCompactThreads = 1024;
 __global__ __launch_bounds__(kCompactThreads) void compact_pixels_kernel(uint32_t* __restrict__ bitmap, const LevelTable T, int B, int max_rows,
                                                                          int32_t* __restrict__ rows, int32_t* __restrict__ counts,
-                                                                         int32_t* __restrict__ flag)
+                                                                         int32_t* __restrict__ flag, const int32_t* __restrict__ or_flag)
 {
     __shared__ int wave_sum[kCompactThreads / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -830,7 +867,7 @@ __global__ __launch_bounds__(kCompactThreads) void compact_pixels_kernel(uint32_
     }
     if (tid == 0) {
         counts[GPP_MAX_GROUPS] = total;
-        flag[0] = total > max_rows ? 1 : 0;
+        flag[0] = (total > max_rows || (or_flag != nullptr && or_flag[0] != 0)) ? 1 : 0;
     }
 }
 
@@ -846,6 +883,9 @@ extern "C" int gpp_detect_pixel_lists(const gpp_pixel_list_desc* host_desc, void
     if (d.B == 0) return GPP_OK;
     if (!d.workspace || !d.bitmap || !d.rows || !d.counts || !d.flag) return GPP_ERR_BAD_ARG;
     if (((uintptr_t)d.workspace & 15) || (((uintptr_t)d.bitmap | (uintptr_t)d.rows | (uintptr_t)d.counts | (uintptr_t)d.flag) & 3)) return GPP_ERR_ALIGN;
+    const bool dilate = d.dilated_bitmap || d.dilated_rows || d.dilated_counts || d.dilated_flag;
+    if (dilate && (!d.dilated_bitmap || !d.dilated_rows || !d.dilated_counts || !d.dilated_flag || d.dilated_max_rows < 0)) return GPP_ERR_BAD_ARG;
+    if (((uintptr_t)d.dilated_bitmap | (uintptr_t)d.dilated_rows | (uintptr_t)d.dilated_counts | (uintptr_t)d.dilated_flag) & 3) return GPP_ERR_ALIGN;
     const int lists = d.B * d.lists_per_image;
     if (lists > 64) return GPP_ERR_UNSUPPORTED;            // header slots of the detect workspace
     LevelTable T;
@@ -859,6 +899,8 @@ extern "C" int gpp_detect_pixel_lists(const gpp_pixel_list_desc* host_desc, void
         T.pix_begin[l] = (int)pixels;
         T.word_begin[l] = (int)words;
         T.list_begin[l] = (int)((int64_t)d.B * pixels);
+        T.width[l] = (dilate && l < d.n_levels) ? d.level_width[l] : 0;
+        if (dilate && l < d.n_levels && (T.width[l] <= 0 || pix % T.width[l] != 0)) return GPP_ERR_BAD_ARG;
         pixels += pix;
         words += ((int64_t)d.B * pix + 31) / 32;
     }
@@ -869,7 +911,15 @@ extern "C" int gpp_detect_pixel_lists(const gpp_pixel_list_desc* host_desc, void
     const unsigned long long* keys = (const unsigned long long*)(ws + kHeaderBytes);
     mark_pixels_kernel<<<dim3(16, (unsigned)lists), 256, 0, st>>>(keys, cnt, pow2_ceil(d.n_anchors), d.n_anchors, d.num_base_anchors,
                                                                    d.lists_per_image, T, d.bitmap);
-    compact_pixels_kernel<<<1, kCompactThreads, 0, st>>>(d.bitmap, T, d.B, d.max_rows, d.rows, d.counts, d.flag);
+    if (dilate) {
+        // before the compaction clears the map it reads; the dilated map's own compaction clears that one
+        const int64_t pairs = (words + 1) / 2;
+        dilate_pixels_kernel<<<dim3((unsigned)((pairs * 64 + 255) / 256)), 256, 0, st>>>(d.bitmap, T, d.B, (int)words, d.dilated_bitmap);
+    }
+    compact_pixels_kernel<<<1, kCompactThreads, 0, st>>>(d.bitmap, T, d.B, d.max_rows, d.rows, d.counts, d.flag, nullptr);
+    if (dilate)
+        compact_pixels_kernel<<<1, kCompactThreads, 0, st>>>(d.dilated_bitmap, T, d.B, d.dilated_max_rows, d.dilated_rows, d.dilated_counts,
+                                                             d.dilated_flag, d.flag);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? GPP_OK : (int)e;
 }

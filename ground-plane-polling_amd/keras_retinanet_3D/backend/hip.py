@@ -80,7 +80,9 @@ class ConvDesc(ctypes.Structure):
                 ('groups', ConvGroup * GPP_MAX_GROUPS),
                 ('x3_split', ctypes.c_int32), ('reserved2', ctypes.c_int32), ('out_scale', c_void_p), ('range_counter', c_void_p),
                 ('gather_rows', c_void_p), ('gather_counts', c_void_p), ('guard', c_void_p),
-                ('guard_value', ctypes.c_int32), ('reserved3', ctypes.c_int32)]
+                ('guard_value', ctypes.c_int32), ('reserved3', ctypes.c_int32),
+                ('tower_rows', c_void_p), ('tower_counts', c_void_p), ('tower_flag', c_void_p),
+                ('tower_tile', ctypes.c_int32), ('reserved4', ctypes.c_int32)]
 
 
 class PixelListDesc(ctypes.Structure):
@@ -88,7 +90,9 @@ class PixelListDesc(ctypes.Structure):
     _fields_ = [('workspace', c_void_p), ('bitmap', c_void_p), ('rows', c_void_p), ('counts', c_void_p), ('flag', c_void_p),
                 ('n_anchors', c_int64)] + \
                [(n, ctypes.c_int32) for n in ('B', 'num_base_anchors', 'lists_per_image', 'n_levels', 'max_rows', 'reserved')] + \
-               [('level_pixels', ctypes.c_int32 * GPP_MAX_GROUPS), ('reserved2', ctypes.c_int32)]
+               [('level_pixels', ctypes.c_int32 * GPP_MAX_GROUPS), ('reserved2', ctypes.c_int32)] + \
+               [('dilated_bitmap', c_void_p), ('dilated_rows', c_void_p), ('dilated_counts', c_void_p), ('dilated_flag', c_void_p),
+                ('level_width', ctypes.c_int32 * GPP_MAX_GROUPS), ('dilated_max_rows', ctypes.c_int32)]
 
 
 class MobileNetBlockDesc(ctypes.Structure):

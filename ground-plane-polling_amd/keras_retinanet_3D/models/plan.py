@@ -103,7 +103,8 @@ OP_JOIN, OP_SYNC = 0x10000, 0x20000
 
 # the effective plan switches of one (model, batch), read from the GPP_* variables by RetinaNet3D._plan_options
 PlanOptions = collections.namedtuple('PlanOptions', 'x3_level fuse_stem_pool stage_chunks half_stages fuse_tail fuse_block fuse_block_proj '
-                                                    'br1_lane fpn_lanes p4_lane head_lanes decode_overlap cls_lane autotune tune_key sparse_heads')
+                                                    'br1_lane fpn_lanes p4_lane head_lanes decode_overlap cls_lane autotune tune_key sparse_heads '
+                                                    'sparse_tower sparse_tower_rounds')
 
 
 def block_form(opts, width, projection, split_input, halves, join):
@@ -136,6 +137,12 @@ RANGE_AUDIT_THRESHOLD = 2.0 ** -9
 X3_QUANTUM = 2.0 ** -24
 # sparse head outputs: the share of listed rows up to which the gathered launches run (where their time crosses the dense launches')
 SPARSE_HEADS_MAX_SHARE = '0.5'
+# sparse regression tower: the share of rows in the DILATED lists up to which the gathered launch of the tower's last layer runs (DESIGN.md
+# section 4.19: where its time crosses the dense launch's), and how many rounds of 256 x 256 workgroups on the chip's 256 compute units the
+# dense launch must exceed for the layer to take the form at all (below one round either launch costs one workgroup life)
+SPARSE_TOWER_MAX_SHARE = '0.75'
+SPARSE_TOWER_MIN_ROUNDS = '1'
+COMPUTE_UNITS = 256
 
 
 def audit_report(maps, table, threshold=RANGE_AUDIT_THRESHOLD):
@@ -171,9 +178,10 @@ class SparseHeads(object):
     """ what the gathered head output layers of a plan share: the device lists gpp_detect_pixel_lists writes behind the candidate pass
     (bitmap, rows, counts, flag), the guarded dense descriptors (Plan.complete_heads) and the gathered ones (the tuner) """
 
-    def __init__(self, torch, device, B, level_pixels, max_share):
+    def __init__(self, torch, device, B, level_pixels, max_share, level_widths=None, tower_share=0.0):
         i32 = torch.int32
         self.B, self.level_pixels = B, [int(p) for p in level_pixels]
+        self.level_widths = [int(w) for w in level_widths] if level_widths else []
         total = B * sum(self.level_pixels)
         self.max_rows = max(0, min(total, int(max_share * total)))
         self.bitmap = torch.zeros((sum((B * p + 31) // 32 for p in self.level_pixels),), dtype=i32, device=device)
@@ -184,25 +192,43 @@ class SparseHeads(object):
         self.flag = torch.ones((1,), dtype=i32, device=device)
         self.dense, self.gathered = [], []
         self.lists_joined = False
+        # the DILATED lists (tower_share > 0: the plan runs the regression tower's last layer on them, RetinaNet3D._heads): the listed pixels
+        # and their eight neighbours, what the gathered 3 x 3 output layer reads.  Same layout; tower_flag = flag | (more than tower_max_rows
+        # rows).  tower = the descriptors of the layers that take both forms (Plan.complete_heads); range_scratch: where a completion's
+        # dense re-run counts its range events (the run itself has counted the listed rows already)
+        self.tower, self.tower_max_rows = [], 0
+        self.tower_bitmap = self.tower_rows = self.tower_counts = self.tower_flag = self.range_scratch = None
+        if tower_share > 0.0:
+            self.tower_max_rows = max(0, min(total, int(tower_share * total)))
+            self.tower_bitmap = torch.zeros_like(self.bitmap)
+            self.tower_rows = torch.zeros_like(self.rows)
+            self.tower_counts = torch.zeros_like(self.counts)
+            self.tower_flag = torch.ones_like(self.flag)
+            self.range_scratch = torch.zeros((1,), dtype=torch.int64, device=device)
 
     def tensors(self):
-        return [self.bitmap, self.rows, self.counts, self.flag]
+        own = [self.bitmap, self.rows, self.counts, self.flag]
+        return own + ([self.tower_bitmap, self.tower_rows, self.tower_counts, self.tower_flag] if self.tower_rows is not None else [])
 
-    def put_every_nth(self, torch, n=8):
-        """ a synthetic list for the tuner: every n-th pixel of every level """
+    def put_every_nth(self, torch, n=8, tower=False):
+        """ a synthetic list for the tuner: every n-th pixel of every level (tower: into the dilated lists) """
+        rows, cnt = (self.tower_rows, self.tower_counts) if tower else (self.rows, self.counts)
         begin, counts = 0, []
         for p in self.level_pixels:
-            idx = torch.arange(0, self.B * p, n, dtype=torch.int32, device=self.rows.device)
-            self.rows[begin:begin + idx.numel()] = idx
+            idx = torch.arange(0, self.B * p, n, dtype=torch.int32, device=rows.device)
+            rows[begin:begin + idx.numel()] = idx
             counts.append(int(idx.numel()))
             begin += self.B * p
         counts += [0] * (hip.GPP_MAX_GROUPS - len(counts)) + [sum(counts)]
-        self.counts.copy_(torch.as_tensor(counts, dtype=torch.int32))
+        cnt.copy_(torch.as_tensor(counts, dtype=torch.int32))
 
     def reset(self, torch):
         """ nothing listed, the dense launches run: the state before the first run """
         self.counts.zero_()
         self.flag.fill_(1)
+        if self.tower_rows is not None:
+            self.tower_counts.zero_()
+            self.tower_flag.fill_(1)
 
 
 class Plan(object):
@@ -237,7 +263,8 @@ class Plan(object):
     # The two regression head tensors.  With sparse head outputs a run writes them at the pixels the decode reads and nowhere else; whoever
     # reads a whole tensor (tests, bench.py --full, the CPU replay of the decode) gets it whole: the first read after such a run enqueues the
     # two dense launches -- the descriptors a dense plan runs, on the current stream -- and the listed rows keep their bytes (a gathered row
-    # IS the dense row).  predict_on_batch, run_plan and fetch never come here.
+    # IS the dense row).  In a plan whose regression tower ends in a layer of both forms (SparseHeads.tower) that layer is run dense first:
+    # the output layer's dense launch reads every row of it.  predict_on_batch, run_plan and fetch never come here.
     @property
     def regression(self):
         self.complete_heads()
@@ -260,6 +287,13 @@ class Plan(object):
         if self.sparse is None or not self.heads_stale:
             return
         self.heads_stale = False
+        for both in self.sparse.tower:
+            d = type(both).from_buffer_copy(both)             # the layer's dense launch alone; its range events go to a scratch slot:
+            d.tower_rows = d.tower_counts = d.tower_flag = None      # the run has counted those of the rows it wrote
+            d.tower_tile = 0
+            if d.range_counter:
+                d.range_counter = self.sparse.range_scratch.data_ptr()
+            hip.check(hip.lib().gpp_conv2d_igemm(ctypes.byref(d), hip.stream_ptr()), 'gpp_conv2d_igemm (tower layer completed)')
         for guarded in self.sparse.dense:
             d = type(guarded).from_buffer_copy(guarded)       # the dense launch as it stands in the plan, without its guard
             d.guard, d.guard_value = None, 0

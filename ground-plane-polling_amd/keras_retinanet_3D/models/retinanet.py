@@ -50,7 +50,7 @@ from .plan import (BlockDesc, CandidatePixelsDesc, DensePoolDesc, DetectDesc, Pl
                    OP_ABSMAX, OP_ABSMAX_CLEAR, OP_STEM_RAGGED, OP_STEM_POOL_RAGGED, OP_MAXPOOL_RAGGED,
                    OP_DETECT_CANDIDATE_PIXELS, DETECT_OPS, OP_JOIN, OP_SYNC,
                    PlanOptions, block_form, part_of, TOWER_SLICES, RANGE_AUDIT_THRESHOLD, X3_QUANTUM,
-                   SPARSE_HEADS_MAX_SHARE, audit_report, SparseHeads, Plan)
+                   SPARSE_HEADS_MAX_SHARE, SPARSE_TOWER_MAX_SHARE, SPARSE_TOWER_MIN_ROUNDS, COMPUTE_UNITS, audit_report, SparseHeads, Plan)
 
 
 class RetinaNet3D(object):
@@ -505,6 +505,11 @@ class RetinaNet3D(object):
                 lists = hip.PixelListDesc(ws.data_ptr(), sp.bitmap.data_ptr(), sp.rows.data_ptr(), sp.counts.data_ptr(), sp.flag.data_ptr(),
                                           plan.n_anchors, B, anchor_utils.NUM_BASE_ANCHORS, 4 if self.osf else 1, len(sp.level_pixels),
                                           sp.max_rows, 0, (ctypes.c_int32 * hip.GPP_MAX_GROUPS)(*sp.level_pixels), 0)
+                if sp.tower_rows is not None:       # ... and their 3 x 3 dilation: what the regression tower's last layer has to write
+                    lists.dilated_bitmap, lists.dilated_rows = sp.tower_bitmap.data_ptr(), sp.tower_rows.data_ptr()
+                    lists.dilated_counts, lists.dilated_flag = sp.tower_counts.data_ptr(), sp.tower_flag.data_ptr()
+                    lists.level_width = (ctypes.c_int32 * hip.GPP_MAX_GROUPS)(*sp.level_widths)
+                    lists.dilated_max_rows = sp.tower_max_rows
                 reads, writes = access[OP_DETECT_CANDIDATES]
                 plan.emit(kind, CandidatePixelsDesc(ctypes.addressof(dd), lists), name, reads, writes + sp.tensors(), inner=(dd,), **flags)
                 return
@@ -530,9 +535,42 @@ class RetinaNet3D(object):
                    for m in wide]
             for i in range(1, 4):
                 _, dst = pyramid(width)
-                self._conv(plan, '{}_{}'.format(prefix, i), src, dst, 3, pad=(1, 1), relu=True, tag=tag, lane=lane)
+                if i == 3 and out_name == 'pyramid_regression_ops' and plan.sparse is not None and plan.sparse.tower_rows is not None:
+                    tower_last('{}_{}'.format(prefix, i), src, dst, tag, lane)
+                else:
+                    self._conv(plan, '{}_{}'.format(prefix, i), src, dst, 3, pad=(1, 1), relu=True, tag=tag, lane=lane)
                 src = dst
             out_layer(out_name, src, out, lane, join)
+
+        def tower_last(name, src, dst, tag, lane):
+            """ the regression tower's last layer where its only reader is the gathered output layer (sparse_tower_form below): that launch
+            reads the map at the listed pixels and their eight neighbours, so this layer has to write the 3 x 3 dilation of the lists and
+            nothing else.  ONE op (its flops the algorithmic count, its tag the tower's): gpp_conv2d_igemm enqueues the dense launch and the
+            gathered one on the dilated lists (gpp_conv_desc.tower_rows), and the lists' flag lets exactly one of them work -- the dense one
+            whenever the output layer runs dense, which reads every row.  The op joins the candidates' lane: it is the first reader of the
+            lists.  The rows nobody reads keep whatever the buffer held; Plan.complete_heads runs the layer dense before anyone reads more. """
+            sp = plan.sparse
+            d = self._desc(plan, name, src, dst, 3, pad=(1, 1), relu=True, lane=lane)
+            d.tower_rows, d.tower_counts, d.tower_flag = sp.tower_rows.data_ptr(), sp.tower_counts.data_ptr(), sp.tower_flag.data_ptr()
+            plan.emit(OP_CONV, d, name, list(src) + [sp.tower_rows, sp.tower_counts, sp.tower_flag], dst, tag=tag, flops=C.conv_flops(d), lane=lane,
+                      join=not sp.lists_joined, io=(src, dst, None))
+            sp.lists_joined = True
+            sp.tower.append(d)
+
+        def sparse_tower_form():
+            """ whether pyramid_regression_3 takes both forms: its reader pyramid_regression_ops is gathered in this plan (out_layer's own
+            conditions), and the dense launch fields more than opts.sparse_tower_rounds rounds of 256 x 256 workgroups on the chip -- a rule
+            of (layer, map sizes, batch) like the split rule: below one round a gathered launch costs one workgroup life either way """
+            if not opts.sparse_heads or not opts.sparse_tower or not opts.decode_overlap or opts.x3_level < 1 or self.dtype not in C.X3_TYPES:
+                return False
+            kh, kw, cin, cout = self.conv_w['pyramid_regression_ops'][2]
+            split = (C.latency_split if self.plan_mode == 'latency' else C.default_split)(kh, kw, cin, cout, sum(f.H * f.W for f in reg_o))
+            kh, kw, cin, cout = self.conv_w['pyramid_regression_3'][2]
+            split3 = (C.latency_split if self.plan_mode == 'latency' else C.default_split)(kh, kw, cin, cout, sum(f.H * f.W for f in reg_o))
+            if split > 1 or split3 > 1 or cout % 256:
+                return False
+            workgroups = sum((P[0].B * m.H * m.W + 255) // 256 for m in P) * (cout // 256)
+            return workgroups > opts.sparse_tower_rounds * COMPUTE_UNITS
 
         def out_layer(name, src, out, lane, join):
             """ the output layer of a tower.  opts.sparse_heads, regression and dimension tower: the decode reads these maps at candidate
@@ -569,7 +607,8 @@ class RetinaNet3D(object):
                   'reg': ('pyramid_regression', 512, 0, 'pyramid_regression_ops', reg_o, 1, 0, bool(opts.cls_lane)),
                   'dim': ('pyramid_regression_dim', 128, 768, 'pyramid_regression_dim', dim_o, 0, l_dim)}
         if opts.sparse_heads:
-            plan.sparse = SparseHeads(self.torch, self.device, P[0].B, [m.H * m.W for m in P], opts.sparse_heads)
+            plan.sparse = SparseHeads(self.torch, self.device, P[0].B, [m.H * m.W for m in P], opts.sparse_heads, [m.W for m in P],
+                                      opts.sparse_tower if sparse_tower_form() else 0.0)
             plan.keep += plan.sparse.tensors()
         if opts.decode_overlap:
             tower(*towers['cls'])
@@ -777,6 +816,13 @@ class RetinaNet3D(object):
             # decides, per step); 0.0 = off.  An audit plan keeps the dense launches.
             sparse_heads=(max(1e-9, float(env('GPP_SPARSE_HEADS_MAX_SHARE', SPARSE_HEADS_MAX_SHARE)))
                           if (overlap and not self.audit and env('GPP_SPARSE_HEADS', '1') != '0') else 0.0),
+            # GPP_SPARSE_TOWER (default 1; with sparse head outputs only): the regression tower's LAST layer on the 3 x 3 dilation of the
+            # candidates' pixels -- the only rows its reader, the gathered output layer, takes.  The value is the largest share of all
+            # pyramid pixels the gathered launch takes (GPP_SPARSE_TOWER_MAX_SHARE); GPP_SPARSE_TOWER_MIN_ROUNDS: the rounds of workgroups
+            # the dense launch must exceed (0 in tests: small plans take the form too)
+            sparse_tower=(max(1e-9, float(env('GPP_SPARSE_TOWER_MAX_SHARE', SPARSE_TOWER_MAX_SHARE)))
+                          if (overlap and not self.audit and env('GPP_SPARSE_HEADS', '1') != '0' and env('GPP_SPARSE_TOWER', '1') != '0') else 0.0),
+            sparse_tower_rounds=float(env('GPP_SPARSE_TOWER_MIN_ROUNDS', SPARSE_TOWER_MIN_ROUNDS)),
             tune_key='x3split={};fuse={}/{};plan={}{}'.format(env('GPP_X3_SPLIT', '2'), env('GPP_FUSE_TAIL', '64,128'), env('GPP_FUSE_BLOCK', '64,128'),
                                                               self.plan_mode, C.latency_split_config() if self.plan_mode == 'latency' else '') +
                      (';audit' if self.audit else ''))
@@ -933,6 +979,17 @@ class RetinaNet3D(object):
             setattr(target, field, self._tuned[key][0])
             plan.tuning[name] = self._tuned[key]
             plan.tuning_parts.setdefault(name, []).append(self._tuned[key])
+            if kind == OP_CONV and desc.tower_rows:
+                # a layer of both forms: the dense tile was timed above (the lists' flag is 1 outside a run); the gathered tiles on a synthetic
+                # list of every THIRD pixel -- between what real frames list and the crossover -- with the flag clear
+                rows_key = (name + '@rows',) + key[1:]
+                if rows_key in self._tuned and self._tuned[rows_key][0] not in self._tower_tiles(desc):
+                    del self._tuned[rows_key]
+                if rows_key not in self._tuned:
+                    self._tuned[rows_key] = self._time_tower_tiles(plan, index, desc)
+                    fresh = True
+                desc.tower_tile = self._tuned[rows_key][0]
+                plan.tuning[name + '@rows'] = self._tuned[rows_key]
         if plan.sparse is not None:
             plan.sparse.reset(self.torch)
         self.torch.cuda.synchronize()
@@ -993,6 +1050,38 @@ class RetinaNet3D(object):
         else:
             hip.check(hip.lib().gpp_conv2d_autotune(ctypes.byref(target), iters, hip.stream_ptr(), ctypes.byref(best)), 'gpp_conv2d_autotune')
         return int(target.tile_hint), round(float(best.value), 2)
+
+    @staticmethod
+    def _tower_tiles(desc):
+        """ the tiles the gathered launch of a layer of both forms may take: the library's candidates for the layer as a gathered one """
+        rows = type(desc).from_buffer_copy(desc)
+        rows.gather_rows, rows.gather_counts = desc.tower_rows, desc.tower_counts
+        rows.tower_rows = rows.tower_counts = rows.tower_flag = None
+        rows.tower_tile, rows.split_k = 0, 1
+        tiles, count = (ctypes.c_int * 32)(), ctypes.c_int(0)
+        hip.check(hip.lib().gpp_conv2d_tile_candidates(ctypes.byref(rows), tiles, 32, ctypes.byref(count)), 'gpp_conv2d_tile_candidates')
+        return [t for t in tiles[:min(count.value, 32)] if t]
+
+    def _time_tower_tiles(self, plan, index, desc, iters=8):
+        """ (tile, us) of the fastest gathered tile of a layer of both forms, on every third pixel; the flag is 1 again afterwards """
+        sp, torch = plan.sparse, self.torch
+        sp.put_every_nth(torch, 3, tower=True)
+        sp.tower_flag.fill_(0)
+        times = {}
+        for tile in self._tower_tiles(desc):
+            desc.tower_tile = tile
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            self.run_op(plan, index)
+            e0.record()
+            for _ in range(iters):
+                self.run_op(plan, index)
+            e1.record()
+            e1.synchronize()
+            times[tile] = e0.elapsed_time(e1) * 1000.0 / iters
+        sp.tower_flag.fill_(1)
+        sp.tower_counts.zero_()
+        tile = min(times, key=times.get)
+        return tile, round(times[tile], 2)
 
     @staticmethod
     def _tile_is_listed(desc, tile):

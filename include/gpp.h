@@ -159,6 +159,7 @@ typedef struct gpp_conv_desc {
                                          4000000 + BM * 1000 + BN   the weight-stationary persistent 1 x 1
                                          5000000 + BM * 1000 + BN   the plain loop on a four-deep LDS ring
                                          6000000 / 7000000 + BM * 1000 + BN   gathered rows (gather_rows), two- / four-deep ring
+                                         8000000 + BM * 1000 + 256  gathered rows into a pre-split map, the pipelined loop (BM 0: chosen on the device)
                                        A code nobody has: GPP_ERR_BAD_ARG; one this element type, input form or layer cannot run:
                                        GPP_ERR_UNSUPPORTED.  The catalogue is csrc/conv_tiles.h; gpp_conv2d_tile_candidates lists
                                        what a layer accepts; see gpp_conv2d_autotune */
@@ -201,7 +202,26 @@ typedef struct gpp_conv_desc {
                                        weight-stationary tiles 4xxxxxx) */
     int32_t guard_value;
     int32_t reserved3;              /* must be 0 */
+    const int32_t* tower_rows;      /* NULL = none (then tower_counts and tower_flag are NULL too).  Otherwise ONE call runs BOTH forms of the layer
+                                       on the stream, and a device word selects which of them does the work: the dense launch (tile_hint) while
+                                       *tower_flag == 1, the gathered-row launch on tower_rows / tower_counts (laid out as gather_rows /
+                                       gather_counts; tile tower_tile) while *tower_flag == 0; the workgroups of the other one return on their
+                                       first load.  For a layer whose only reader takes it at listed pixels (the last layer of the regression
+                                       tower, read by the gathered output layer at the candidates' 3 x 3 neighbourhoods).  gather_rows and
+                                       guard stay NULL.  Scope: the gathered form with a pre-split output map, below */
+    const int32_t* tower_counts;
+    const int32_t* tower_flag;
+    int32_t tower_tile;             /* tile of the gathered launch of such a pair: 0 or an 8xxxxxx code */
+    int32_t reserved4;              /* must be 0 */
 } gpp_conv_desc;
+/* The gathered-row form of a layer between two convolutions (gather_rows set, out_f32 == 0): GPP_BF16X3 / GPP_F16X3 with pre-split input AND
+ * output maps (x3_split & (GPP_X3_IN | GPP_X3_OUT) both set), stride 1, no shortcut, never split-K, C_out a multiple of 256; anything else
+ * with out_f32 == 0 answers GPP_ERR_UNSUPPORTED, as it always has.  It runs the three-phase pipelined loop on 256-column tiles:
+ *   tile_hint 8128256, 8160256, 8192256, 8224256, 8256256   tiles of that many rows
+ *             0 or 8000256                                    the height is chosen ON THE DEVICE from the counts: the one whose grid costs the
+ *                                                             fewest rounds x rows on the chip's 256 compute units (the host cannot know the count)
+ * Row tiles are numbered over the LISTED rows (the live workgroups are the first of the grid); every listed row receives the bytes of the
+ * dense launch in both halves of the split map, no other byte is written, and GPP_F16X3 range events are counted on the listed rows only. */
 #define GPP_X3_IN 1
 #define GPP_X3_OUT 2
 #define GPP_X3_RES 4
@@ -482,6 +502,12 @@ typedef struct gpp_pixel_list_desc {
     int64_t n_anchors;
     int32_t B, num_base_anchors, lists_per_image, n_levels, max_rows, reserved;
     int32_t level_pixels[GPP_MAX_GROUPS]; int32_t reserved2;
+    /* the DILATED lists (NULL / 0 = none): every listed pixel and its eight neighbours inside its own image and level -- what a 3 x 3, pad 1
+       layer on the lists above reads, and so what the layer in front of it has to write.  Same layout as bitmap / rows / counts; level_width[l] =
+       W_l (a divisor of level_pixels[l]).  dilated_flag = flag | (sum of the dilated counts > dilated_max_rows): when the reader runs dense it
+       reads every row, so its producer runs dense too.  All four pointers or none */
+    uint32_t* dilated_bitmap; int32_t* dilated_rows; int32_t* dilated_counts; int32_t* dilated_flag;
+    int32_t level_width[GPP_MAX_GROUPS]; int32_t dilated_max_rows;
 } gpp_pixel_list_desc;
 int gpp_detect_pixel_lists(const gpp_pixel_list_desc* host_desc, void* stream);
 
