@@ -20,6 +20,19 @@ def load_polling_golden(name):
     return g
 
 
+def resize_golden_names():
+    return sorted(os.path.basename(p)[len('resize_'):-len('.npz')] for p in glob.glob(os.path.join(GOLDEN, 'resize_*.npz')))
+
+
+def load_resize_golden(name):
+    """ tests/golden/resize_<name>.npz (oracle/gen_resize_goldens.py): the reference's resize_image(preprocess_image(frame), min_side,
+    max_side) with oracle/image_np as its cv2.resize; the scalars as Python floats """
+    g = dict(np.load(os.path.join(GOLDEN, 'resize_{}.npz'.format(name))))
+    for k in ('min_side', 'max_side', 'fx', 'fy', 'scale'):
+        g[k] = float(g[k])
+    return g
+
+
 def c_oracle_poll(lib, boxes, dims, orient, P_inv, planes, thr=0.7):
     """ oracle/polling.c through ctypes; planes (N,4) shared or (B,N,4). """
     boxes = np.ascontiguousarray(boxes, np.float32)
