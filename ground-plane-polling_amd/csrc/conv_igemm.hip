@@ -44,13 +44,18 @@ int validate(const gpp_conv_desc& d)
     const bool tower = d.tower_rows || d.tower_counts || d.tower_flag;
     if (tower && (!d.tower_rows || !d.tower_counts || !d.tower_flag || d.gather_rows || d.guard)) return GPP_ERR_BAD_ARG;
     if (!tower && d.tower_tile != 0) return GPP_ERR_BAD_ARG;
+    // the same pair for a layer further up the tower (deep_rows / deep_counts / deep_flag): the same rules, and never both sets
+    const bool deep = d.deep_rows || d.deep_counts || d.deep_flag;
+    if (deep && (!d.deep_rows || !d.deep_counts || !d.deep_flag || d.gather_rows || d.guard || tower)) return GPP_ERR_BAD_ARG;
+    if (!deep && d.deep_tile != 0) return GPP_ERR_BAD_ARG;
+    if (d.lists_after < 0) return GPP_ERR_BAD_ARG;
     if (((uintptr_t)d.gather_rows | (uintptr_t)d.gather_counts | (uintptr_t)d.guard | (uintptr_t)d.tower_rows | (uintptr_t)d.tower_counts |
-         (uintptr_t)d.tower_flag) & 3)
+         (uintptr_t)d.tower_flag | (uintptr_t)d.deep_rows | (uintptr_t)d.deep_counts | (uintptr_t)d.deep_flag) & 3)
         return GPP_ERR_ALIGN;
     // the gathered-row form: stride 1, no shortcut, never split (split-K would change the summation order of a row); float32 output, or -- a
     // layer between two convolutions -- the pre-split maps of an x3 type with whole 256-column tiles (gpp_tiles::gather_pipe_can_run)
     if (d.gather_rows && (d.stride != 1 || d.residual || d.split_k > 1)) return GPP_ERR_UNSUPPORTED;
-    if (((d.gather_rows && !d.out_f32) || tower) && !gpp_tiles::gather_pipe_can_run(d)) return GPP_ERR_UNSUPPORTED;
+    if (((d.gather_rows && !d.out_f32) || tower || deep) && !gpp_tiles::gather_pipe_can_run(d)) return GPP_ERR_UNSUPPORTED;
     if (d.x3_split && !is_x3(d.dtype)) return GPP_ERR_BAD_ARG;
     if (d.out_scale && d.dtype != GPP_F16X3) return GPP_ERR_BAD_ARG;
     if ((d.x3_split & GPP_X3_OUT) && (d.out_f32 || d.C_out % 32 != 0 || d.out_pitch % 32 != 0)) return GPP_ERR_UNSUPPORTED;
@@ -117,16 +122,21 @@ int dispatch_any(gpp_conv_desc& d, hipStream_t st)
         if (d.split_k > 1) return GPP_ERR_UNSUPPORTED;
         return gpp_conv_gather_dispatch(d, st);
     }
-    if (d.tower_rows) {
+    if (d.tower_rows || d.deep_rows) {
         // both forms on the stream, the device word chooses: the gathered launch works while it is 0, the dense one while it is 1 (the guard
-        // mechanism of the head output layers, here behind one call: the plan keeps ONE op for the layer)
+        // mechanism of the head output layers, here behind one call: the plan keeps ONE op for the layer).  tower_* and deep_* name the
+        // lists of two different writers (validate: never both); what is launched is the same
         if (d.split_k > 1) return GPP_ERR_UNSUPPORTED;
+        const int32_t* flag = d.tower_rows ? d.tower_flag : d.deep_flag;
         gpp_conv_desc rows = d, dense = d;
-        rows.gather_rows = d.tower_rows; rows.gather_counts = d.tower_counts; rows.tile_hint = d.tower_tile;
-        rows.guard = d.tower_flag; rows.guard_value = 0;
-        dense.guard = d.tower_flag; dense.guard_value = 1;
+        rows.gather_rows = d.tower_rows ? d.tower_rows : d.deep_rows;
+        rows.gather_counts = d.tower_rows ? d.tower_counts : d.deep_counts;
+        rows.tile_hint = d.tower_rows ? d.tower_tile : d.deep_tile;
+        rows.guard = flag; rows.guard_value = 0;
+        dense.guard = flag; dense.guard_value = 1;
         rows.tower_rows = rows.tower_counts = rows.tower_flag = dense.tower_rows = dense.tower_counts = dense.tower_flag = nullptr;
-        rows.tower_tile = dense.tower_tile = 0;
+        rows.deep_rows = rows.deep_counts = rows.deep_flag = dense.deep_rows = dense.deep_counts = dense.deep_flag = nullptr;
+        rows.tower_tile = dense.tower_tile = rows.deep_tile = dense.deep_tile = 0;
         const int rc_rows = gpp_conv_gather_dispatch(rows, st);
         if (rc_rows != GPP_OK) return rc_rows;
         return dispatch_any(dense, st);
@@ -147,7 +157,9 @@ int tail_entry(const gpp_conv_desc* conv3x3, const gpp_conv_desc* conv1x1, int t
     int rc = validate(d1);
     if (rc == GPP_OK) rc = validate(d2);
     if (rc != GPP_OK) return rc;
-    if (d1.gather_rows || d2.gather_rows || d1.guard || d2.guard || d1.tower_rows || d2.tower_rows) return GPP_ERR_UNSUPPORTED;      // gpp_conv2d_igemm only
+    if (d1.gather_rows || d2.gather_rows || d1.guard || d2.guard || d1.tower_rows || d2.tower_rows || d1.deep_rows || d2.deep_rows ||
+        d1.lists_after || d2.lists_after)
+        return GPP_ERR_UNSUPPORTED;      // gpp_conv2d_igemm only
     const gpp_conv_group &G1 = d1.groups[0], &G2 = d2.groups[0];
     // the pair this kernel fuses: 3x3 / stride 1 / pad 1 / C -> C (C = 64 or 128) feeding 1x1 / stride 1 / C -> multiple of 128
     if (d1.dtype == GPP_F32) return GPP_ERR_UNSUPPORTED;           // 16-bit storage types, and the x3 types on pre-split maps
@@ -180,7 +192,9 @@ int block_entry(const gpp_conv_desc* conv_a, const gpp_conv_desc* conv_b, const 
     if (rc == GPP_OK) rc = validate(d2);
     if (rc == GPP_OK) rc = validate(d3);
     if (rc != GPP_OK) return rc;
-    if (d1.gather_rows || d2.gather_rows || d3.gather_rows || d1.guard || d2.guard || d3.guard || d1.tower_rows || d2.tower_rows || d3.tower_rows) return GPP_ERR_UNSUPPORTED;
+    if (d1.gather_rows || d2.gather_rows || d3.gather_rows || d1.guard || d2.guard || d3.guard || d1.tower_rows || d2.tower_rows || d3.tower_rows ||
+        d1.deep_rows || d2.deep_rows || d3.deep_rows || d1.lists_after || d2.lists_after || d3.lists_after)
+        return GPP_ERR_UNSUPPORTED;
     const gpp_conv_group &G1 = d1.groups[0], &G2 = d2.groups[0], &G3 = d3.groups[0];
     // the triple this kernel fuses, on pre-split maps of one x3 type: 1x1 / stride 1 or 2 / C_in -> C; 3x3 / stride 1 / pad 1 / C -> C (C = 64 or 128);
     // 1x1 / stride 1 / C -> a multiple of 128, + shortcut map of the output's size
@@ -287,7 +301,14 @@ extern "C" int gpp_conv2d_igemm(const gpp_conv_desc* host_desc, void* stream)
     for (int g = 0; g < GPP_MAX_GROUPS; ++g) d.groups[g].row_begin = 0;       // the library's own field (mixed grids)
     int rc = validate(d);
     if (rc != GPP_OK) return rc;
-    return dispatch_any(d, (hipStream_t)stream);
+    // lists_after: the deep lists behind this layer's launch on the same stream (the layer writes the logits they are made from); a handle
+    // nobody holds is refused before anything is launched
+    const int32_t lists = d.lists_after;
+    d.lists_after = 0;
+    if (lists && (rc = gpp_detect_deep_lists_run(lists, 1, stream)) != GPP_OK) return rc;
+    rc = dispatch_any(d, (hipStream_t)stream);
+    if (rc != GPP_OK || !lists) return rc;
+    return gpp_detect_deep_lists_run(lists, 0, stream);
 }
 
 // The block tiles a layer may run with (same K order per output element in every one of them: the choice never changes a result): the
@@ -382,6 +403,8 @@ extern "C" int gpp_conv2d_autotune(gpp_conv_desc* desc, int iters, void* stream,
     e = hipEventCreate(&e1);
     if (e != hipSuccess) { (void)hipEventDestroy(e0); return (int)e; }
     const int tile_in = desc->tile_hint;
+    const int32_t lists_in = desc->lists_after;
+    desc->lists_after = 0;                                           // the layer's own launch is what is timed, not the lists behind it
     float best = 1e30f;
     int best_tile = tile_in, rc = GPP_OK;
     auto time_one = [&](int tile, float* us, int reps = 2) -> int {
@@ -432,6 +455,7 @@ extern "C" int gpp_conv2d_autotune(gpp_conv_desc* desc, int iters, void* stream,
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     desc->tile_hint = rc == GPP_OK ? best_tile : tile_in;
+    desc->lists_after = lists_in;
     if (best_us) *best_us = best;
     return rc;
 }
@@ -455,7 +479,7 @@ int preact_validate(gpp_conv_desc& d, const float* in_scale, const float* in_shi
     if (((uintptr_t)in_scale | (uintptr_t)in_shift) & 15) return GPP_ERR_ALIGN;
     if (d.KH != 1 || d.KW != 1 || d.stride != 1 || d.pad_top != 0 || d.pad_left != 0) return GPP_ERR_UNSUPPORTED;
     if (d.x3_split & GPP_X3_IN) return GPP_ERR_UNSUPPORTED;
-    if (d.gather_rows || d.guard || d.tower_rows) return GPP_ERR_UNSUPPORTED;          // gpp_conv2d_igemm only
+    if (d.gather_rows || d.guard || d.tower_rows || d.deep_rows || d.lists_after) return GPP_ERR_UNSUPPORTED;          // gpp_conv2d_igemm only
     if (d.C_in > 4096) return GPP_ERR_UNSUPPORTED;               // the scale / shift table lives in LDS beside the ring
     return GPP_OK;
 }

@@ -21,6 +21,8 @@
 #include <limits.h>
 
 #include <atomic>
+#include <mutex>
+#include <vector>
 
 #include "gpp.h"
 
@@ -77,6 +79,21 @@ __device__ __forceinline__ Folded fold8(const float* l)
     return f;
 }
 
+// whether the anchor with these 8 logits is a candidate at thr, and its fold if it is: THE decision of the candidate pass (candidates_kernel,
+// and the marks of gpp_detect_deep_lists, which must name the same pixels).
+// Cheap exact rejects first (the folded score is the largest of the 8 sigmoids, and the sigmoid used here is
+// accurate to ~1e-7 and monotone to within that): (1) sigmoid(-3.0) = 0.0474 decides every threshold
+// >= 0.048 without any exp; (2) one sigmoid of the largest logit with a 1e-5 guard band decides the rest.
+// Only anchors inside the guard band or above the threshold pay for the exact 8-sigmoid fold.
+__device__ __forceinline__ bool is_candidate(const float* l, float thr, Folded& f)
+{
+    const float lmax = fmaxf(fmaxf(fmaxf(l[0], l[1]), fmaxf(l[2], l[3])), fmaxf(fmaxf(l[4], l[5]), fmaxf(l[6], l[7])));
+    if (thr >= 0.048f && lmax < -3.0f) return false;
+    if (sigmoidf(lmax) < thr - 1e-5f) return false;
+    f = fold8(l);
+    return f.score > thr;
+}
+
 __global__ __launch_bounds__(256) void candidates_kernel(const float* __restrict__ cls, int64_t n_anchors, int64_t key_stride,
                                                          float thr, unsigned long long* __restrict__ keys,
                                                          int32_t* __restrict__ counts)
@@ -87,15 +104,8 @@ __global__ __launch_bounds__(256) void candidates_kernel(const float* __restrict
     const float4* src = (const float4*)(cls + ((int64_t)b * n_anchors + a) * 8);
     const float4 v0 = src[0], v1 = src[1];
     const float l[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-    // cheap exact rejects (the folded score is the largest of the 8 sigmoids, and the sigmoid used here is
-    // accurate to ~1e-7 and monotone to within that): (1) sigmoid(-3.0) = 0.0474 decides every threshold
-    // >= 0.048 without any exp; (2) one sigmoid of the largest logit with a 1e-5 guard band decides the rest.
-    // Only anchors inside the guard band or above the threshold pay for the exact 8-sigmoid fold.
-    const float lmax = fmaxf(fmaxf(fmaxf(l[0], l[1]), fmaxf(l[2], l[3])), fmaxf(fmaxf(l[4], l[5]), fmaxf(l[6], l[7])));
-    if (thr >= 0.048f && lmax < -3.0f) return;
-    if (sigmoidf(lmax) < thr - 1e-5f) return;
-    const Folded f = fold8(l);
-    if (f.score > thr) {
+    Folded f;
+    if (is_candidate(l, thr, f)) {
         const int slot = atomicAdd(&counts[b * (kCounterStride / 4)], 1);
         keys[(int64_t)b * key_stride + slot] =
             ((unsigned long long)__float_as_uint(f.score) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)a);
@@ -818,9 +828,9 @@ __global__ __launch_bounds__(256) void dilate_pixels_kernel(const uint32_t* __re
 // cleared on the way (the next call finds the map empty).  counts[l], then their sum at counts[GPP_MAX_GROUPS]; flag = the sum exceeds max_rows
 // (the dilated lists: or the flag of the lists they were dilated from is set, or_flag).
 constexpr int kCompactThreads = 1024;
-__global__ __launch_bounds__(kCompactThreads) void compact_pixels_kernel(uint32_t* __restrict__ bitmap, const LevelTable T, int B, int max_rows,
-                                                                         int32_t* __restrict__ rows, int32_t* __restrict__ counts,
-                                                                         int32_t* __restrict__ flag, const int32_t* __restrict__ or_flag)
+__device__ __forceinline__ void compact_pixels(uint32_t* __restrict__ bitmap, const LevelTable& T, int B, int max_rows,
+                                               int32_t* __restrict__ rows, int32_t* __restrict__ counts,
+                                               int32_t* __restrict__ flag, const int32_t* __restrict__ or_flag)
 {
     __shared__ int wave_sum[kCompactThreads / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -870,6 +880,136 @@ __global__ __launch_bounds__(kCompactThreads) void compact_pixels_kernel(uint32_
         flag[0] = (total > max_rows || (or_flag != nullptr && or_flag[0] != 0)) ? 1 : 0;
     }
 }
+
+__global__ __launch_bounds__(kCompactThreads) void compact_pixels_kernel(uint32_t* __restrict__ bitmap, const LevelTable T, int B, int max_rows,
+                                                                         int32_t* __restrict__ rows, int32_t* __restrict__ counts,
+                                                                         int32_t* __restrict__ flag, const int32_t* __restrict__ or_flag)
+{
+    compact_pixels(bitmap, T, B, max_rows, rows, counts, flag, or_flag);
+}
+
+// two maps in one launch, a workgroup each (the deep lists: the second map's or_flag is a word an EARLIER launch wrote, not the first's flag)
+struct CompactJob { uint32_t* bitmap; int32_t* rows; int32_t* counts; int32_t* flag; const int32_t* or_flag; };
+__global__ __launch_bounds__(kCompactThreads) void compact_pixels_pair_kernel(const CompactJob a, const CompactJob b, const LevelTable T, int B, int max_rows)
+{
+    const CompactJob& j = blockIdx.x == 0 ? a : b;
+    compact_pixels(j.bitmap, T, B, max_rows, j.rows, j.counts, j.flag, j.or_flag);
+}
+
+// ---- gpp_detect_deep_lists: the marks straight from the logits, their dilations of radius 1, 2, 3, and the lists of radius 2 and 3.
+// Four launches.  The marks: a wavefront per 64 pixels (two words), its lanes over the pixels' 64 * nba anchors in memory order, nba rounds -- every load a
+// coalesced 32 bytes per lane as in candidates_kernel, whose decision it calls (is_candidate).  The hits meet in one LDS word per wavefront
+// and leave as two whole words: no global atomics, nothing read of what the map held.
+__global__ __launch_bounds__(256) void mark_candidate_pixels_kernel(const float* __restrict__ cls, int64_t n_anchors, int nba, float thr,
+                                                                    const LevelTable T, int B, int total_words, uint32_t* __restrict__ marks)
+{
+    __shared__ unsigned long long hit[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t gbit0 = (int64_t)blockIdx.x * 256 + wave * 64;       // the wavefront's first bit; its words: word0, word0 + 1
+    const int word0 = (int)(gbit0 >> 5);
+    if (lane == 0) hit[wave] = 0;
+    __syncthreads();
+    for (int i = 0; i < nba; ++i) {
+        const int j = i * 64 + lane, q = j / nba, k = j - q * nba;      // anchor k of the wavefront's pixel q
+        const int word = word0 + (q >> 5);
+        if (word >= total_words) continue;
+        int l = 0;
+        for (int t = 1; t < T.n_levels; ++t) l = word >= T.word_begin[t] ? t : l;      // (a level starts a word: the two words may lie in two levels)
+        const int64_t bit = gbit0 + q - ((int64_t)T.word_begin[l] << 5);
+        const int pix = T.pix[l];
+        if (bit >= (int64_t)B * pix) continue;                           // the padding of the level's last word
+        const int b = (int)(bit / pix), p = (int)(bit - (int64_t)b * pix);
+        const float4* src = (const float4*)(cls + ((int64_t)b * n_anchors + (int64_t)(T.pix_begin[l] + p) * nba + k) * 8);
+        const float4 v0 = src[0], v1 = src[1];
+        const float lg[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+        Folded f;
+        if (is_candidate(lg, thr, f)) atomicOr(&hit[wave], 1ull << q);
+    }
+    __syncthreads();
+    const unsigned long long mask = hit[wave];
+    if (lane == 0 && word0 < total_words) marks[word0] = (uint32_t)mask;
+    if (lane == 32 && word0 + 1 < total_words) marks[word0 + 1] = (uint32_t)(mask >> 32);
+}
+
+// the three dilations in one pass over the marks: bit (level, image, pixel) of radius r = some mark within Chebyshev distance r of the pixel
+// INSIDE its image and level (what r passes of dilate_pixels_kernel give: an image is a rectangle).  One thread per bit, three ballots.
+__global__ __launch_bounds__(256) void dilate_radii_kernel(const uint32_t* __restrict__ marks, const LevelTable T, int B, int total_words,
+                                                           uint32_t* __restrict__ radius1, uint32_t* __restrict__ radius2,
+                                                           uint32_t* __restrict__ radius3)
+{
+    const int64_t gbit = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int word = (int)(gbit >> 5);
+    if (word >= total_words) return;                       // (whole half-wavefronts: the ballots below are of the lanes that remain)
+    int l = 0;
+    for (int q = 1; q < T.n_levels; ++q) l = word >= T.word_begin[q] ? q : l;
+    const int64_t bit = gbit - ((int64_t)T.word_begin[l] << 5);
+    const int pix = T.pix[l], W = T.width[l], H = pix / W;
+    bool on1 = false, on2 = false, on3 = false;
+    if (bit < (int64_t)B * pix) {
+        const int b = (int)(bit / pix), p = (int)(bit - (int64_t)b * pix);
+        const int y = p / W, x = p - y * W;
+        const uint32_t* words = marks + T.word_begin[l];
+        for (int dy = -3; dy <= 3; ++dy) {
+            const int yy = y + dy;
+            if (yy < 0 || yy >= H) continue;
+            for (int dx = -3; dx <= 3; ++dx) {
+                const int xx = x + dx;
+                if (xx < 0 || xx >= W) continue;
+                const int64_t nb = (int64_t)b * pix + yy * W + xx;
+                const bool v = (words[nb >> 5] >> (nb & 31)) & 1u;
+                const int r = max(abs(dy), abs(dx));
+                on3 |= v;
+                on2 |= v && r <= 2;
+                on1 |= v && r <= 1;
+            }
+        }
+    }
+    const unsigned long long m1 = __ballot(on1), m2 = __ballot(on2), m3 = __ballot(on3);
+    const int lane = threadIdx.x & 63;
+    if (lane == 0 || lane == 32) {
+        const int sh = lane;                               // lane 32 holds the wavefront's second word
+        radius1[word] = (uint32_t)(m1 >> sh);
+        radius2[word] = (uint32_t)(m2 >> sh);
+        radius3[word] = (uint32_t)(m3 >> sh);
+    }
+}
+
+// |marks|, |radius 1| and what the candidate pass's lists will decide for the tower's last layer (compact_pixels_kernel's two flags)
+// ... and flag2, so that the two compactions can share a launch: the radius-3 one takes it from here
+__global__ __launch_bounds__(kCompactThreads) void deep_stats_kernel(const uint32_t* __restrict__ marks, const uint32_t* __restrict__ radius1,
+                                                                     const uint32_t* __restrict__ radius2, int total_words, int max_rows,
+                                                                     int tower_max_rows, int deep_max_rows, int32_t* __restrict__ stats)
+{
+    __shared__ int sums[3][kCompactThreads / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int n[3] = {0, 0, 0};
+    for (int w = tid; w < total_words; w += kCompactThreads) {
+        n[0] += __popc(marks[w]);
+        n[1] += __popc(radius1[w]);
+        n[2] += __popc(radius2[w]);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) n[k] += __shfl_down(n[k], s, 64);
+        if (lane == 0) sums[k][wave] = n[k];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int t[3] = {0, 0, 0};
+        for (int q = 0; q < kCompactThreads / 64; ++q) { t[0] += sums[0][q]; t[1] += sums[1][q]; t[2] += sums[2][q]; }
+        const int f3 = (t[0] > max_rows || t[1] > tower_max_rows) ? 1 : 0;
+        stats[0] = t[0];
+        stats[1] = t[1];
+        stats[2] = f3;
+        stats[3] = (f3 || t[2] > deep_max_rows) ? 1 : 0;
+    }
+}
+
+// the descriptors gpp_conv_desc.lists_after names by number (gpp_detect_deep_lists_register)
+std::mutex g_deep_mutex;
+std::vector<gpp_deep_list_desc> g_deep_descs;
+std::vector<char> g_deep_held;
 
 }  // namespace
 
@@ -922,6 +1062,103 @@ extern "C" int gpp_detect_pixel_lists(const gpp_pixel_list_desc* host_desc, void
                                                              d.dilated_flag, d.flag);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? GPP_OK : (int)e;
+}
+
+namespace {
+
+int deep_lists_table(const gpp_deep_list_desc& d, LevelTable& T, int64_t& words)
+{
+    if (d.B < 0 || d.B > kMaxBatch || d.n_anchors <= 0 || d.n_anchors > kMaxAnchors || d.num_base_anchors <= 0 || d.num_base_anchors > 64 ||
+        d.max_rows < 0 || d.tower_max_rows < 0 || d.deep_max_rows < 0 || d.n_levels < 1 || d.n_levels > GPP_MAX_GROUPS || d.reserved != 0 ||
+        !(d.score_thr == d.score_thr))
+        return GPP_ERR_BAD_ARG;
+    const bool layer1 = d.rows1 || d.counts1 || d.flag1;
+    if (d.B > 0 && (!d.cls_logits || !d.marks || !d.radius1 || !d.radius2 || !d.radius3 || !d.rows2 || !d.counts2 || !d.flag2 || !d.stats ||
+                    (layer1 && (!d.rows1 || !d.counts1 || !d.flag1))))
+        return GPP_ERR_BAD_ARG;
+    if (((uintptr_t)d.cls_logits & 15) || (((uintptr_t)d.marks | (uintptr_t)d.radius1 | (uintptr_t)d.radius2 | (uintptr_t)d.radius3 | (uintptr_t)d.rows2 |
+          (uintptr_t)d.counts2 | (uintptr_t)d.flag2 | (uintptr_t)d.rows1 | (uintptr_t)d.counts1 | (uintptr_t)d.flag1 | (uintptr_t)d.stats) & 3))
+        return GPP_ERR_ALIGN;
+    T.n_levels = d.n_levels;
+    int64_t pixels = 0;
+    words = 0;
+    for (int l = 0; l < GPP_MAX_GROUPS; ++l) {
+        const int pix = l < d.n_levels ? d.level_pixels[l] : 0;
+        if (l < d.n_levels && pix <= 0) return GPP_ERR_BAD_ARG;
+        if ((int64_t)d.B * (pixels + pix) >= (1LL << 31)) return GPP_ERR_UNSUPPORTED;
+        T.pix[l] = pix;
+        T.pix_begin[l] = (int)pixels;
+        T.word_begin[l] = (int)words;
+        T.list_begin[l] = (int)((int64_t)d.B * pixels);
+        T.width[l] = l < d.n_levels ? d.level_width[l] : 0;
+        if (l < d.n_levels && (T.width[l] <= 0 || pix % T.width[l] != 0)) return GPP_ERR_BAD_ARG;
+        pixels += pix;
+        words += ((int64_t)d.B * pix + 31) / 32;
+    }
+    if (pixels * d.num_base_anchors != d.n_anchors) return GPP_ERR_BAD_ARG;
+    return GPP_OK;
+}
+
+}  // namespace
+
+extern "C" int gpp_detect_deep_lists(const gpp_deep_list_desc* host_desc, void* stream)
+{
+    if (!host_desc) return GPP_ERR_BAD_ARG;
+    const gpp_deep_list_desc& d = *host_desc;
+    LevelTable T;
+    int64_t words = 0;
+    const int rc = deep_lists_table(d, T, words);
+    if (rc != GPP_OK) return rc;
+    if (d.B == 0) return GPP_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned blocks = (unsigned)(((words + 1) / 2 * 64 + 255) / 256);       // words are handed out in pairs, a wavefront each
+    mark_candidate_pixels_kernel<<<dim3(blocks), 256, 0, st>>>(d.cls_logits, d.n_anchors, d.num_base_anchors, d.score_thr, T, d.B, (int)words, d.marks);
+    dilate_radii_kernel<<<dim3(blocks), 256, 0, st>>>(d.marks, T, d.B, (int)words, d.radius1, d.radius2, d.radius3);
+    deep_stats_kernel<<<1, kCompactThreads, 0, st>>>(d.marks, d.radius1, d.radius2, (int)words, d.max_rows, d.tower_max_rows, d.deep_max_rows, d.stats);
+    // flag2 = f3 | (|radius 2| > deep_max_rows); flag1 = flag2 | (|radius 3| > deep_max_rows): the or_flag chain of the dilated lists, with
+    // flag2 as the statistics launch has it (stats[3]) so that the two compactions, 25 - 30 us of one workgroup each, run side by side
+    const CompactJob layer2 = {d.radius2, d.rows2, d.counts2, d.flag2, d.stats + 2}, layer1 = {d.radius3, d.rows1, d.counts1, d.flag1, d.stats + 3};
+    if (d.rows1) compact_pixels_pair_kernel<<<2, kCompactThreads, 0, st>>>(layer2, layer1, T, d.B, d.deep_max_rows);
+    else compact_pixels_kernel<<<1, kCompactThreads, 0, st>>>(d.radius2, T, d.B, d.deep_max_rows, d.rows2, d.counts2, d.flag2, d.stats + 2);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? GPP_OK : (int)e;
+}
+
+extern "C" int gpp_detect_deep_lists_register(const gpp_deep_list_desc* host_desc, int32_t* handle)
+{
+    if (!host_desc || !handle) return GPP_ERR_BAD_ARG;
+    LevelTable T;
+    int64_t words = 0;
+    const int rc = deep_lists_table(*host_desc, T, words);
+    if (rc != GPP_OK) return rc;
+    std::lock_guard<std::mutex> lock(g_deep_mutex);
+    size_t slot = 0;
+    while (slot < g_deep_held.size() && g_deep_held[slot]) ++slot;
+    if (slot >= (size_t)INT_MAX - 1) return GPP_ERR_UNSUPPORTED;
+    if (slot == g_deep_held.size()) { g_deep_held.push_back(0); g_deep_descs.push_back(*host_desc); }
+    g_deep_descs[slot] = *host_desc;
+    g_deep_held[slot] = 1;
+    *handle = (int32_t)slot + 1;
+    return GPP_OK;
+}
+
+extern "C" int gpp_detect_deep_lists_release(int32_t handle)
+{
+    std::lock_guard<std::mutex> lock(g_deep_mutex);
+    if (handle < 1 || (size_t)handle > g_deep_held.size() || !g_deep_held[(size_t)handle - 1]) return GPP_ERR_BAD_ARG;
+    g_deep_held[(size_t)handle - 1] = 0;
+    return GPP_OK;
+}
+
+extern "C" int gpp_detect_deep_lists_run(int32_t handle, int check_only, void* stream)
+{
+    gpp_deep_list_desc d;
+    {
+        std::lock_guard<std::mutex> lock(g_deep_mutex);
+        if (handle < 1 || (size_t)handle > g_deep_held.size() || !g_deep_held[(size_t)handle - 1]) return GPP_ERR_BAD_ARG;
+        d = g_deep_descs[(size_t)handle - 1];
+    }
+    return check_only ? GPP_OK : gpp_detect_deep_lists(&d, stream);
 }
 
 extern "C" int gpp_detect_workspace_bytes(int B, int64_t n_anchors, size_t* bytes)

@@ -63,7 +63,25 @@ int main(int argc, char** argv)
         note(gpp_conv2d_flops(nullptr, &flops));
         note(gpp_conv2d_tile_candidates(&r.d[0], nullptr, 0, &count));
         switch (r.kind % 6) {
-        case 0: note(gpp_conv2d_igemm(&r.d[0], nullptr)); break;
+        case 0: {
+            note(gpp_conv2d_igemm(&r.d[0], nullptr));
+            // the same layer as one of both forms on the deep lists (fields of the neighbouring records stand in for the lists), and with
+            // a lists_after handle: nobody has registered one here, so every value but 0 must come back as an error before any launch
+            gpp_conv_desc v = r.d[0];
+            v.deep_rows = r.d[1].tower_rows ? r.d[1].tower_rows : (const int32_t*)r.d[1].out;
+            v.deep_counts = (r.b & 1) ? (const int32_t*)r.d[1].bias : r.d[1].tower_counts;
+            v.deep_flag = (r.b & 2) ? (const int32_t*)r.d[2].out : r.d[2].tower_flag;
+            v.deep_tile = (r.b & 4) ? 0 : (r.b & 8) ? 8000256 : (int32_t)r.c;
+            if (r.b & 16) v.tower_rows = v.tower_counts = v.tower_flag = nullptr;
+            if (r.b & 32) { v.gather_rows = nullptr; v.gather_counts = nullptr; v.guard = nullptr; }
+            note(gpp_conv2d_igemm(&v, nullptr));
+            v = r.d[0];
+            v.lists_after = (int32_t)(r.c % 5) - 1;
+            const int rc = gpp_conv2d_igemm(&v, nullptr);
+            if (v.lists_after != 0 && rc == 0) { fprintf(stderr, "a lists_after handle nobody holds was accepted\n"); return 3; }
+            note(rc);
+            break;
+        }
         case 1: note(gpp_bottleneck_tail(&r.d[0], &r.d[1], (int)(r.b % 200), nullptr)); break;
         case 2: note(gpp_bottleneck_block(&r.d[0], &r.d[1], &r.d[2], (int)(r.b % 2000), nullptr)); break;
         case 3: {
@@ -111,6 +129,35 @@ int main(int argc, char** argv)
             note(gpp_poll_workspace_bytes((int)r.a, (int)r.b, (int)(r.c & 1), &wb));
             note(gpp_detect_workspace_bytes((int)r.a, (int64_t)(((uint64_t)r.b * (uint64_t)r.c) >> ((r.a >> 8) & 31)), &wb));
             note(gpp_detect_osf_workspace_bytes((int)r.a, (int64_t)(((uint64_t)r.b * (uint64_t)r.c) >> ((r.a >> 8) & 31)), &wb));
+            {
+                // gpp_detect_deep_lists and its registry: a descriptor out of the record's bytes (checked on the host, launched nowhere here)
+                static_assert(sizeof(gpp_conv_desc) >= sizeof(gpp_deep_list_desc), "the record's bytes cover a deep-list descriptor");
+                gpp_deep_list_desc dl;
+                memcpy(&dl, &r.d[1], sizeof dl);
+                note(gpp_detect_deep_lists(&dl, nullptr));
+                dl.reserved = 0; dl.B = (int32_t)(r.a % 9); dl.n_levels = (int32_t)(r.b % 7); dl.num_base_anchors = (int32_t)(r.c % 14);
+                dl.max_rows = (int32_t)(r.a >> 8); dl.tower_max_rows = (int32_t)(r.b >> 8); dl.deep_max_rows = (int32_t)(r.c >> 8);
+                int64_t pixels = 0;
+                for (int l = 0; l < GPP_MAX_GROUPS; ++l) {
+                    dl.level_width[l] = (int32_t)((r.a >> (3 * l)) % 40) + ((r.b >> l) & 1);
+                    dl.level_pixels[l] = dl.level_width[l] * (int32_t)((r.c >> (3 * l)) % 30);
+                    if (l < dl.n_levels) pixels += dl.level_pixels[l];
+                }
+                dl.n_anchors = (r.a & 64) ? (int64_t)r.b : pixels * dl.num_base_anchors;
+                note(gpp_detect_deep_lists(&dl, nullptr));
+                note(gpp_detect_deep_lists(nullptr, nullptr));
+                int32_t handle = 0;
+                const int rc = gpp_detect_deep_lists_register(&dl, &handle);
+                note(rc);
+                note(gpp_detect_deep_lists_register(&dl, nullptr));
+                note(gpp_detect_deep_lists_run((int32_t)r.c, 1, nullptr));
+                if (rc == 0) {
+                    note(gpp_detect_deep_lists_run(handle, 1, nullptr));
+                    note(gpp_detect_deep_lists_release(handle));
+                }
+                note(gpp_detect_deep_lists_release(handle));
+                note(gpp_detect_deep_lists_release((int32_t)r.b));
+            }
             note(gpp_poll_f32(nullptr, nullptr, nullptr, nullptr, nullptr, (int)r.a, (int)r.b, (int)r.c, 0, 0.7f, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr));
             // the composite's host halves: sizes, then argument checks that end before any launch (fuzzed, misaligned and null pointers)
             size_t pb = 0;

@@ -29,6 +29,7 @@ typedef __attribute__((ext_vector_type(8))) float f32x8_natural;
 typedef f32x8_natural f32x8 __attribute__((aligned(16)));     // 8 floats, accessed as two 16-byte halves (GPP_F32 maps)
 
 constexpr int TW = 64, TH = 4;                 // output tile
+constexpr int kMaxStemDim = 1 << 20;           // batch, height, width of a launch: far beyond any image, far below overflow of the tile counts
 constexpr int PW = TW * 2 + 5, PH = TH * 2 + 5;  // input patch
 constexpr int PPITCH = PW * 3 + 1;             // floats per patch row (odd: spreads LDS banks)
 
@@ -134,7 +135,9 @@ int stem_f32_run(const float* in, const float* weight, const float* bias, void* 
 {
     if (!in || !weight || !bias || !out || B <= 0 || H <= 0 || W <= 0) return GPP_ERR_BAD_ARG;
     if (((uintptr_t)out) & 15) return GPP_ERR_ALIGN;
+    if (B > kMaxStemDim || H > kMaxStemDim || W > kMaxStemDim) return GPP_ERR_UNSUPPORTED;      // (the tile arithmetic below stays inside an int)
     const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
+    if ((int64_t)((Wo + TW - 1) / TW) * ((Ho + TH - 1) / TH) >= (1LL << 30)) return GPP_ERR_UNSUPPORTED;
     dim3 grid((unsigned)(((Wo + TW - 1) / TW) * ((Ho + TH - 1) / TH)), (unsigned)B);
     hipStream_t st = (hipStream_t)stream;
     if (dtype != GPP_BF16 && dtype != GPP_F16 && dtype != GPP_F32) return GPP_ERR_UNSUPPORTED;
@@ -239,7 +242,9 @@ static int stem_x3_run(const float* in, const void* packed_weight_x3, const floa
     if ((uintptr_t)range_counter & 7) return GPP_ERR_ALIGN;
     if (((uintptr_t)out | (uintptr_t)packed_weight_x3) & 15) return GPP_ERR_ALIGN;
     constexpr int ROWS = 8;
+    if (B > kMaxStemDim || H > kMaxStemDim || W > kMaxStemDim) return GPP_ERR_UNSUPPORTED;      // (the tile arithmetic below stays inside an int)
     const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
+    if ((int64_t)((Wo + TW - 1) / TW) * ((Ho + ROWS - 1) / ROWS) * B >= (1LL << 30)) return GPP_ERR_UNSUPPORTED;
     const int tiles = ((Wo + TW - 1) / TW) * ((Ho + ROWS - 1) / ROWS) * B;
     const int lds = 2 * 64 * MW_PITCH * 2 + 2 * (ROWS * 2 + 5) * MP_PITCH * 2;
     static std::atomic<unsigned long long> configured[2];
@@ -280,7 +285,9 @@ static int stem_mfma_run(const float* in, const void* packed_weight_f16, const f
 {
     if (!in || !packed_weight_f16 || !bias || !out || B <= 0 || H <= 0 || W <= 0) return GPP_ERR_BAD_ARG;
     if (((uintptr_t)out | (uintptr_t)packed_weight_f16) & 15) return GPP_ERR_ALIGN;
+    if (B > kMaxStemDim || H > kMaxStemDim || W > kMaxStemDim) return GPP_ERR_UNSUPPORTED;      // (the tile arithmetic below stays inside an int)
     const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
+    if ((int64_t)((Wo + TW - 1) / TW) * ((Ho + TH - 1) / TH) * B >= (1LL << 30)) return GPP_ERR_UNSUPPORTED;
     const int tiles = ((Wo + TW - 1) / TW) * ((Ho + TH - 1) / TH) * B;
     static const int per_cu = [] { const char* e = getenv("GPP_STEM_WGS_PER_CU"); const int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 4 ? 4 : v); }();
     const unsigned grid = (unsigned)(tiles < 256 * per_cu ? tiles : 256 * per_cu);      // persistent workgroups

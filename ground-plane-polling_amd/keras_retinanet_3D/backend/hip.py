@@ -82,7 +82,9 @@ class ConvDesc(ctypes.Structure):
                 ('gather_rows', c_void_p), ('gather_counts', c_void_p), ('guard', c_void_p),
                 ('guard_value', ctypes.c_int32), ('reserved3', ctypes.c_int32),
                 ('tower_rows', c_void_p), ('tower_counts', c_void_p), ('tower_flag', c_void_p),
-                ('tower_tile', ctypes.c_int32), ('reserved4', ctypes.c_int32)]
+                ('tower_tile', ctypes.c_int32), ('reserved4', ctypes.c_int32),
+                ('deep_rows', c_void_p), ('deep_counts', c_void_p), ('deep_flag', c_void_p),
+                ('deep_tile', ctypes.c_int32), ('lists_after', ctypes.c_int32)]
 
 
 class PixelListDesc(ctypes.Structure):
@@ -93,6 +95,15 @@ class PixelListDesc(ctypes.Structure):
                [('level_pixels', ctypes.c_int32 * GPP_MAX_GROUPS), ('reserved2', ctypes.c_int32)] + \
                [('dilated_bitmap', c_void_p), ('dilated_rows', c_void_p), ('dilated_counts', c_void_p), ('dilated_flag', c_void_p),
                 ('level_width', ctypes.c_int32 * GPP_MAX_GROUPS), ('dilated_max_rows', ctypes.c_int32)]
+
+
+class DeepListDesc(ctypes.Structure):
+    """ gpp_deep_list_desc (include/gpp.h) """
+    _fields_ = [(n, c_void_p) for n in ('cls_logits', 'marks', 'radius1', 'radius2', 'radius3', 'rows2', 'counts2', 'flag2',
+                                        'rows1', 'counts1', 'flag1', 'stats')] + [('n_anchors', c_int64)] + \
+               [(n, ctypes.c_int32) for n in ('B', 'num_base_anchors', 'n_levels', 'max_rows', 'tower_max_rows', 'deep_max_rows')] + \
+               [('score_thr', c_float), ('reserved', ctypes.c_int32),
+                ('level_pixels', ctypes.c_int32 * GPP_MAX_GROUPS), ('level_width', ctypes.c_int32 * GPP_MAX_GROUPS)]
 
 
 class MobileNetBlockDesc(ctypes.Structure):
@@ -157,6 +168,17 @@ def _declare(lib):
     if hasattr(lib, 'gpp_detect_pixel_lists'):
         lib.gpp_detect_pixel_lists.restype = c_int
         lib.gpp_detect_pixel_lists.argtypes = [ctypes.POINTER(PixelListDesc), c_void_p]
+    # the deep lists of the sparse regression tower (include/gpp.h, csrc/decode.hip; absent from an older build named by GPP_LIB: it runs
+    # every plan but one of GPP_SPARSE_TOWER_DEPTH >= 2, which does not build on it)
+    if hasattr(lib, 'gpp_detect_deep_lists'):
+        lib.gpp_detect_deep_lists.restype = c_int
+        lib.gpp_detect_deep_lists.argtypes = [ctypes.POINTER(DeepListDesc), c_void_p]
+        lib.gpp_detect_deep_lists_register.restype = c_int
+        lib.gpp_detect_deep_lists_register.argtypes = [ctypes.POINTER(DeepListDesc), ctypes.POINTER(ctypes.c_int32)]
+        lib.gpp_detect_deep_lists_release.restype = c_int
+        lib.gpp_detect_deep_lists_release.argtypes = [ctypes.c_int32]
+        lib.gpp_detect_deep_lists_run.restype = c_int
+        lib.gpp_detect_deep_lists_run.argtypes = [ctypes.c_int32, c_int, c_void_p]
     lib.gpp_conv2d_igemm.restype = c_int
     lib.gpp_conv2d_igemm.argtypes = [ctypes.POINTER(ConvDesc), c_void_p]
     lib.gpp_stem_conv7x7_bn_relu.restype = c_int

@@ -104,7 +104,7 @@ OP_JOIN, OP_SYNC = 0x10000, 0x20000
 # the effective plan switches of one (model, batch), read from the GPP_* variables by RetinaNet3D._plan_options
 PlanOptions = collections.namedtuple('PlanOptions', 'x3_level fuse_stem_pool stage_chunks half_stages fuse_tail fuse_block fuse_block_proj '
                                                     'br1_lane fpn_lanes p4_lane head_lanes decode_overlap cls_lane autotune tune_key sparse_heads '
-                                                    'sparse_tower sparse_tower_rounds')
+                                                    'sparse_tower sparse_tower_rounds sparse_deep sparse_deep_rounds sparse_depth')
 
 
 def block_form(opts, width, projection, split_input, halves, join):
@@ -142,6 +142,13 @@ SPARSE_HEADS_MAX_SHARE = '0.5'
 # dense launch must exceed for the layer to take the form at all (below one round either launch costs one workgroup life)
 SPARSE_TOWER_MAX_SHARE = '0.75'
 SPARSE_TOWER_MIN_ROUNDS = '1'
+# ... and layers 2 and 1 of that tower on the 5 x 5 and 7 x 7 dilations: how many tower layers take both forms
+# (1: the last one only), the share of rows up to which their gathered launches run (the last share measured below the dense launch for this
+# kernel and shape, section 4.19's table), and the rounds their dense launch must exceed -- a variable of its own: tests pin what small
+# plans do under GPP_SPARSE_TOWER_MIN_ROUNDS=0
+SPARSE_TOWER_DEPTH = '3'
+SPARSE_TOWER_DEEP_MAX_SHARE = '0.75'
+SPARSE_TOWER_DEEP_MIN_ROUNDS = '1'
 COMPUTE_UNITS = 256
 
 
@@ -206,6 +213,59 @@ class SparseHeads(object):
             self.tower_flag = torch.ones_like(self.flag)
             self.range_scratch = torch.zeros((1,), dtype=torch.int64, device=device)
 
+        # the DEEP lists (add_deep): the rows of tower layers 2 and 1, written on the caller's stream behind the layer that writes the logits
+        self.deep, self.deep_layers, self.deep_max_rows, self.deep_handle = [], 0, 0, 0
+        self.deep_bitmaps = self.deep_rows = self.deep_counts = self.deep_flags = self.deep_stats = None
+
+    def add_deep(self, torch, layers, deep_share):
+        """ the buffers of gpp_detect_deep_lists for `layers` (1: layer 2 only, 2: layers 2 and 1) tower layers in front of the last one: the
+        marks and the three dilation bitmaps, a row list, a count vector and a flag per layer (index 0: layer 2 on the radius-2 map, index 1:
+        layer 1 on the radius-3 map), and the call's statistics.  The flags start at 1, like every flag here.  deep = [descriptor of layer 1,
+        descriptor of layer 2], in layer order (Plan.complete_heads) """
+        total = self.B * sum(self.level_pixels)
+        self.deep_layers = int(layers)
+        self.deep_max_rows = max(0, min(total, int(deep_share * total)))
+        self.deep_bitmaps = [torch.zeros_like(self.bitmap) for _ in range(4)]
+        self.deep_rows = [torch.zeros_like(self.rows) for _ in range(self.deep_layers)]
+        self.deep_counts = [torch.zeros_like(self.counts) for _ in range(self.deep_layers)]
+        self.deep_flags = [torch.ones_like(self.flag) for _ in range(self.deep_layers)]
+        self.deep_stats = torch.zeros((4,), dtype=torch.int32, device=self.rows.device)
+
+    def deep_tensors(self):
+        if self.deep_rows is None:
+            return []
+        return self.deep_bitmaps + self.deep_rows + self.deep_counts + self.deep_flags + [self.deep_stats]
+
+    def deep_desc(self, cls_logits, n_anchors, num_base_anchors, score_thr):
+        """ the gpp_deep_list_desc of these buffers """
+        d = hip.DeepListDesc()
+        d.cls_logits = cls_logits.data_ptr()
+        d.marks, d.radius1, d.radius2, d.radius3 = [t.data_ptr() for t in self.deep_bitmaps]
+        d.rows2, d.counts2, d.flag2 = self.deep_rows[0].data_ptr(), self.deep_counts[0].data_ptr(), self.deep_flags[0].data_ptr()
+        if self.deep_layers > 1:
+            d.rows1, d.counts1, d.flag1 = self.deep_rows[1].data_ptr(), self.deep_counts[1].data_ptr(), self.deep_flags[1].data_ptr()
+        d.stats = self.deep_stats.data_ptr()
+        d.n_anchors, d.B, d.num_base_anchors, d.n_levels = n_anchors, self.B, num_base_anchors, len(self.level_pixels)
+        d.max_rows, d.tower_max_rows, d.deep_max_rows, d.score_thr = self.max_rows, self.tower_max_rows, self.deep_max_rows, score_thr
+        d.level_pixels = (ctypes.c_int32 * hip.GPP_MAX_GROUPS)(*self.level_pixels)
+        d.level_width = (ctypes.c_int32 * hip.GPP_MAX_GROUPS)(*self.level_widths)
+        return d
+
+    def register_deep(self, desc):
+        """ the library keeps a copy of the descriptor; gpp_conv_desc.lists_after names it by the handle returned here """
+        handle = ctypes.c_int32(0)
+        hip.check(hip.lib().gpp_detect_deep_lists_register(ctypes.byref(desc), ctypes.byref(handle)), 'gpp_detect_deep_lists_register')
+        self.deep_handle = int(handle.value)
+        return self.deep_handle
+
+    def __del__(self):
+        if getattr(self, 'deep_handle', 0):
+            try:
+                hip.lib().gpp_detect_deep_lists_release(self.deep_handle)
+            except Exception:          # (interpreter shutdown)
+                pass
+            self.deep_handle = 0
+
     def tensors(self):
         own = [self.bitmap, self.rows, self.counts, self.flag]
         return own + ([self.tower_bitmap, self.tower_rows, self.tower_counts, self.tower_flag] if self.tower_rows is not None else [])
@@ -229,6 +289,12 @@ class SparseHeads(object):
         if self.tower_rows is not None:
             self.tower_counts.zero_()
             self.tower_flag.fill_(1)
+        self.reset_deep()
+
+    def reset_deep(self):
+        """ the deep flags at 1, ordered on the current stream: what an op run on its own leaves behind it (it writes its whole map) """
+        for flag in self.deep_flags or ():
+            flag.fill_(1)
 
 
 class Plan(object):
@@ -287,6 +353,13 @@ class Plan(object):
         if self.sparse is None or not self.heads_stale:
             return
         self.heads_stale = False
+        for both in self.sparse.deep:                         # layers 1, 2 in layer order: each dense reader reads every row of the layer in front
+            d = type(both).from_buffer_copy(both)
+            d.deep_rows = d.deep_counts = d.deep_flag = None
+            d.deep_tile = 0
+            if d.range_counter:
+                d.range_counter = self.sparse.range_scratch.data_ptr()
+            hip.check(hip.lib().gpp_conv2d_igemm(ctypes.byref(d), hip.stream_ptr()), 'gpp_conv2d_igemm (deep tower layer completed)')
         for both in self.sparse.tower:
             d = type(both).from_buffer_copy(both)             # the layer's dense launch alone; its range events go to a scratch slot:
             d.tower_rows = d.tower_counts = d.tower_flag = None      # the run has counted those of the rows it wrote

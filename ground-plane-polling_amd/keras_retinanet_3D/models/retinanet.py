@@ -50,7 +50,8 @@ from .plan import (BlockDesc, CandidatePixelsDesc, DensePoolDesc, DetectDesc, Pl
                    OP_ABSMAX, OP_ABSMAX_CLEAR, OP_STEM_RAGGED, OP_STEM_POOL_RAGGED, OP_MAXPOOL_RAGGED,
                    OP_DETECT_CANDIDATE_PIXELS, DETECT_OPS, OP_JOIN, OP_SYNC,
                    PlanOptions, block_form, part_of, TOWER_SLICES, RANGE_AUDIT_THRESHOLD, X3_QUANTUM,
-                   SPARSE_HEADS_MAX_SHARE, SPARSE_TOWER_MAX_SHARE, SPARSE_TOWER_MIN_ROUNDS, COMPUTE_UNITS, audit_report, SparseHeads, Plan)
+                   SPARSE_HEADS_MAX_SHARE, SPARSE_TOWER_MAX_SHARE, SPARSE_TOWER_MIN_ROUNDS, SPARSE_TOWER_DEPTH,
+                   SPARSE_TOWER_DEEP_MAX_SHARE, SPARSE_TOWER_DEEP_MIN_ROUNDS, COMPUTE_UNITS, audit_report, SparseHeads, Plan)
 
 
 class RetinaNet3D(object):
@@ -537,6 +538,8 @@ class RetinaNet3D(object):
                 _, dst = pyramid(width)
                 if i == 3 and out_name == 'pyramid_regression_ops' and plan.sparse is not None and plan.sparse.tower_rows is not None:
                     tower_last('{}_{}'.format(prefix, i), src, dst, tag, lane)
+                elif out_name == 'pyramid_regression_ops' and plan.sparse is not None and 3 - plan.sparse.deep_layers <= i < 3:
+                    tower_deep('{}_{}'.format(prefix, i), src, dst, tag, lane, 2 - i)
                 else:
                     self._conv(plan, '{}_{}'.format(prefix, i), src, dst, 3, pad=(1, 1), relu=True, tag=tag, lane=lane)
                 src = dst
@@ -556,6 +559,39 @@ class RetinaNet3D(object):
                       join=not sp.lists_joined, io=(src, dst, None))
             sp.lists_joined = True
             sp.tower.append(d)
+
+        def tower_deep(name, src, dst, tag, lane, which):
+            """ layers 2 (which = 0) and 1 (which = 1) of the regression tower in a plan of the deep form (sparse_deep_layers below): the
+            only reader of layer 2 is the gathered layer 3, which reads it on the 5 x 5 neighbourhoods of the candidates' pixels, and layer 1
+            is read by the gathered layer 2 on the 7 x 7 ones.  ONE op each, as tower_last; the lists (gpp_conv_desc.deep_rows) come from
+            gpp_detect_deep_lists behind pyramid_classification on this same stream, so there is no lane to join """
+            sp = plan.sparse
+            d = self._desc(plan, name, src, dst, 3, pad=(1, 1), relu=True, lane=lane)
+            lists = [sp.deep_rows[which], sp.deep_counts[which], sp.deep_flags[which]]
+            d.deep_rows, d.deep_counts, d.deep_flag = [t.data_ptr() for t in lists]
+            plan.emit(OP_CONV, d, name, list(src) + lists, dst, tag=tag, flops=C.conv_flops(d), lane=lane, io=(src, dst, None))
+            sp.deep.append(d)
+
+        def sparse_deep_layers():
+            """ how many tower layers in front of the last one take both forms (0, 1: layer 2, 2: layers 2 and 1) -- a rule of layer, map
+            sizes, batch and plan options, like sparse_tower_form, which must hold: the lists are made on the caller's stream right behind
+            pyramid_classification, so that layer runs there, unsplit, with the candidate pass on its side lane (decode_overlap without
+            cls_lane: no head_lanes), in a plan that is neither orientation-specific nor an audit; and the dense launch of a layer fields more
+            than opts.sparse_deep_rounds rounds of workgroups """
+            if not opts.sparse_deep or opts.sparse_depth < 2 or not sparse_tower_form():
+                return 0
+            if opts.cls_lane or opts.head_lanes or self.osf or self.audit or not hasattr(hip.lib(), 'gpp_detect_deep_lists'):
+                return 0
+            rule = C.latency_split if self.plan_mode == 'latency' else C.default_split
+            pixels = sum(f.H * f.W for f in reg_o)
+            for name in ('pyramid_classification', 'pyramid_regression_1', 'pyramid_regression_2'):
+                kh, kw, cin, cout = self.conv_w[name][2]
+                if rule(kh, kw, cin, cout, pixels) > 1 or (name != 'pyramid_classification' and cout % 256):
+                    return 0
+            workgroups = sum((P[0].B * m.H * m.W + 255) // 256 for m in P) * (cout // 256)
+            if not workgroups > opts.sparse_deep_rounds * COMPUTE_UNITS:
+                return 0
+            return min(2, opts.sparse_depth - 1)
 
         def sparse_tower_form():
             """ whether pyramid_regression_3 takes both forms: its reader pyramid_regression_ops is gathered in this plan (out_layer's own
@@ -584,6 +620,14 @@ class RetinaNet3D(object):
             kh, kw, cin, cout = self.conv_w[name][2]
             pixels = sum(f.H * f.W for f in out)
             split = (C.latency_split if self.plan_mode == 'latency' else C.default_split)(kh, kw, cin, cout, pixels)
+            if sp is not None and sp.deep_layers and name == 'pyramid_classification':
+                # the layer that writes the logits: gpp_conv2d_igemm enqueues the deep lists behind its launch (gpp_conv_desc.lists_after) --
+                # part of this op, on this stream, in front of the tower layers that read them
+                d = self._desc(plan, name, src, out, 3, pad=(1, 1), out_f32=True, lane=lane)
+                d.lists_after = sp.register_deep(sp.deep_desc(plan.cls_logits, plan.n_anchors, anchor_utils.NUM_BASE_ANCHORS, SCORE_THRESHOLD))
+                plan.emit(OP_CONV, d, name, list(src), list(out) + sp.deep_tensors(), flops=C.conv_flops(d), lane=lane, join=join,
+                          io=(src, out, None))
+                return
             if sp is None or name == 'pyramid_classification' or lane or split > 1:
                 self._conv(plan, name, src, out, 3, pad=(1, 1), out_f32=True, lane=lane, join=join)
                 if sp is not None and join and not lane:
@@ -610,6 +654,10 @@ class RetinaNet3D(object):
             plan.sparse = SparseHeads(self.torch, self.device, P[0].B, [m.H * m.W for m in P], opts.sparse_heads, [m.W for m in P],
                                       opts.sparse_tower if sparse_tower_form() else 0.0)
             plan.keep += plan.sparse.tensors()
+            layers = sparse_deep_layers()
+            if layers:
+                plan.sparse.add_deep(self.torch, layers, opts.sparse_deep)
+                plan.keep += plan.sparse.deep_tensors()
         if opts.decode_overlap:
             tower(*towers['cls'])
             decode(OP_DETECT_CANDIDATE_PIXELS if plan.sparse else OP_DETECT_CANDIDATES, 'filtered_detections/candidates',
@@ -823,6 +871,14 @@ class RetinaNet3D(object):
             sparse_tower=(max(1e-9, float(env('GPP_SPARSE_TOWER_MAX_SHARE', SPARSE_TOWER_MAX_SHARE)))
                           if (overlap and not self.audit and env('GPP_SPARSE_HEADS', '1') != '0' and env('GPP_SPARSE_TOWER', '1') != '0') else 0.0),
             sparse_tower_rounds=float(env('GPP_SPARSE_TOWER_MIN_ROUNDS', SPARSE_TOWER_MIN_ROUNDS)),
+            # GPP_SPARSE_TOWER_DEPTH (default 3; with the sparse tower only): how many layers of the regression tower run on the rows their
+            # reader takes -- 1 the last layer alone, 2 layer 2 as well (the 5 x 5 dilation of the candidates' pixels), 3 layer 1 too (7 x 7).
+            # The lists of layers 2 and 1 are made from the logits on the caller's stream (gpp_detect_deep_lists);
+            # GPP_SPARSE_TOWER_DEEP_MAX_SHARE: the largest share of rows their gathered launches take; GPP_SPARSE_TOWER_DEEP_MIN_ROUNDS: the
+            # rounds of workgroups their dense launch must exceed (its own variable: tests force the tower's to 0 at small shapes)
+            sparse_deep=max(1e-9, float(env('GPP_SPARSE_TOWER_DEEP_MAX_SHARE', SPARSE_TOWER_DEEP_MAX_SHARE))),
+            sparse_deep_rounds=float(env('GPP_SPARSE_TOWER_DEEP_MIN_ROUNDS', SPARSE_TOWER_DEEP_MIN_ROUNDS)),
+            sparse_depth=int(env('GPP_SPARSE_TOWER_DEPTH', SPARSE_TOWER_DEPTH)),
             tune_key='x3split={};fuse={}/{};plan={}{}'.format(env('GPP_X3_SPLIT', '2'), env('GPP_FUSE_TAIL', '64,128'), env('GPP_FUSE_BLOCK', '64,128'),
                                                               self.plan_mode, C.latency_split_config() if self.plan_mode == 'latency' else '') +
                      (';audit' if self.audit else ''))
@@ -991,6 +1047,8 @@ class RetinaNet3D(object):
                 desc.tower_tile = self._tuned[rows_key][0]
                 plan.tuning[name + '@rows'] = self._tuned[rows_key]
         if plan.sparse is not None:
+            for d in plan.sparse.deep:           # the same layer shape as the last layer: the tile its gathered launches were timed to
+                d.deep_tile = plan.sparse.tower[0].tower_tile
             plan.sparse.reset(self.torch)
         self.torch.cuda.synchronize()
         if fresh:
@@ -1147,6 +1205,11 @@ class RetinaNet3D(object):
         """ Enqueue ONE op of the plan (per-layer tests). """
         self._require_hip()
         hip.check(hip.lib().gpp_plan_run(ctypes.byref(plan.array, index * ctypes.sizeof(PlanOp)), 1, hip.stream_ptr(), None, 0), 'gpp_plan_run')
+        kind, _, desc, _, _ = plan.ops[index]
+        if kind == OP_CONV and desc.lists_after:
+            # the op has made the deep lists and set their flags; an op run on its own writes its whole map (DESIGN.md section 4.19), so the
+            # flags are 1 again behind it, ordered on the stream
+            plan.sparse.reset_deep()
 
     def run_plan(self, plan, events=None):
         """ Enqueue the whole forward on the current stream (asynchronous). """

@@ -213,6 +213,17 @@ typedef struct gpp_conv_desc {
     const int32_t* tower_flag;
     int32_t tower_tile;             /* tile of the gathered launch of such a pair: 0 or an 8xxxxxx code */
     int32_t reserved4;              /* must be 0 */
+    const int32_t* deep_rows;       /* NULL = none.  Otherwise what tower_rows / tower_counts / tower_flag / tower_tile are, for a tower layer further up
+                                       (layers 1 and 2 of the regression tower, on the 7 x 7 and the 5 x 5 neighbourhoods of the candidates' pixels):
+                                       both forms behind one call, *deep_flag == 1 the dense launch works, == 0 the gathered one on deep_rows /
+                                       deep_counts with tile deep_tile.  Same scope, same checks; the lists are those of gpp_detect_deep_lists, written
+                                       on the caller's stream.  All three or none; not together with tower_rows, gather_rows or guard */
+    const int32_t* deep_counts;
+    const int32_t* deep_flag;
+    int32_t deep_tile;              /* 0 or an 8xxxxxx code */
+    int32_t lists_after;            /* 0 = none.  Otherwise a handle of gpp_detect_deep_lists_register: gpp_conv2d_igemm enqueues gpp_detect_deep_lists
+                                       of that descriptor behind the layer's own launch, on the same stream (the layer that writes the logits).  A
+                                       handle nobody holds: GPP_ERR_BAD_ARG, nothing launched.  gpp_conv2d_igemm only */
 } gpp_conv_desc;
 /* The gathered-row form of a layer between two convolutions (gather_rows set, out_f32 == 0): GPP_BF16X3 / GPP_F16X3 with pre-split input AND
  * output maps (x3_split & (GPP_X3_IN | GPP_X3_OUT) both set), stride 1, no shortcut, never split-K, C_out a multiple of 256; anything else
@@ -510,6 +521,41 @@ typedef struct gpp_pixel_list_desc {
     int32_t level_width[GPP_MAX_GROUPS]; int32_t dilated_max_rows;
 } gpp_pixel_list_desc;
 int gpp_detect_pixel_lists(const gpp_pixel_list_desc* host_desc, void* stream);
+
+/* The rows the regression tower's layers 2 and 1 have to write, straight from the logits: no keys, no workspace of the candidate pass, four small
+ * launches on ONE stream (the caller's, behind the layer that writes the logits: gpp_conv_desc.lists_after).
+ *   marks            one bit per (level, image, pixel), the layout of gpp_pixel_list_desc.bitmap: set iff one of the pixel's num_base_anchors anchors
+ *                    is a candidate by the decision GPP_DETECT_CANDIDATES makes at score_thr (the same device functions) -- the pixel set of
+ *                    gpp_detect_pixel_lists' undilated lists
+ *   radius1/2/3      the 3 x 3, 5 x 5 and 7 x 7 dilations of the marks inside the pixel's own image and level (level_width[l] = W_l): what the
+ *                    output layer, layer 3 and layer 2 read.  Every word of the four maps is written whole, whatever it held; a map that
+ *                    is compacted (radius2; radius3 with layer 1's lists) is zero again when the call has run
+ *   rows2 / counts2  the radius-2 map as ascending per-level lists with their lengths and the sum, the layout of gpp_conv_desc.gather_rows /
+ *                    gather_counts: the rows of layer 2.  rows1 / counts1: the radius-3 map, the rows of layer 1 (all three of rows1, counts1,
+ *                    flag1 NULL: layer 2 only)
+ *   stats            int32 [4]: |marks|, |radius 1|, f3, flag2.  f3 = (|marks| > max_rows) | (|radius 1| > tower_max_rows) is what the candidate
+ *                    pass's lists will decide for layer 3 (gpp_pixel_list_desc.dilated_flag)
+ *   flag2, flag1     int32 [1] each, 1 = dense: flag2 = f3 | (|radius 2| > deep_max_rows), flag1 = flag2 | (|radius 3| > deep_max_rows) -- a layer
+ *                    whose reader runs dense runs dense, by construction
+ * Null pointer, bad size, num_base_anchors > 64, reserved != 0: GPP_ERR_BAD_ARG; nothing launched.  B == 0: GPP_OK.
+ * gpp_detect_deep_lists_register keeps a copy of a descriptor in the library and hands out a handle > 0 for gpp_conv_desc.lists_after (a number,
+ * not an address: a conv descriptor holds no host pointer); gpp_detect_deep_lists_release gives it back. */
+typedef struct gpp_deep_list_desc {
+    const float* cls_logits;
+    uint32_t* marks; uint32_t* radius1; uint32_t* radius2; uint32_t* radius3;
+    int32_t* rows2; int32_t* counts2; int32_t* flag2;
+    int32_t* rows1; int32_t* counts1; int32_t* flag1;
+    int32_t* stats;
+    int64_t n_anchors;
+    int32_t B, num_base_anchors, n_levels, max_rows, tower_max_rows, deep_max_rows;
+    float score_thr; int32_t reserved;
+    int32_t level_pixels[GPP_MAX_GROUPS]; int32_t level_width[GPP_MAX_GROUPS];
+} gpp_deep_list_desc;
+int gpp_detect_deep_lists(const gpp_deep_list_desc* host_desc, void* stream);
+int gpp_detect_deep_lists_register(const gpp_deep_list_desc* host_desc, int32_t* handle);
+int gpp_detect_deep_lists_release(int32_t handle);
+/* gpp_detect_deep_lists of the descriptor a handle names (check_only != 0: whether somebody holds the handle, nothing launched) */
+int gpp_detect_deep_lists_run(int32_t handle, int check_only, void* stream);
 
 /* orientation_specific_filter=True (layers/filter_detections.py:84-98, a non-default argument of models.load_model): threshold
  * and NMS once per orientation on that orientation's folded score, the four survivor lists concatenated in orientation

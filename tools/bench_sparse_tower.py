@@ -45,6 +45,7 @@ def main():
     args = ap.parse_args()
     os.environ['GPP_SPARSE_HEADS'] = '1'
     os.environ['GPP_SPARSE_TOWER'] = '1'
+    os.environ['GPP_SPARSE_TOWER_DEPTH'] = '1'        # the layers in front stay dense here (tools/bench_deep_tower.py measures them gathered)
     import torch
     from keras_retinanet_3D import models
     from keras_retinanet_3D.backend import hip
