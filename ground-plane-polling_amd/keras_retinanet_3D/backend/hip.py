@@ -165,6 +165,18 @@ def _declare(lib):
     if hasattr(lib, 'gpp_label_prep_f64'):
         lib.gpp_label_prep_f64.restype = c_int
         lib.gpp_label_prep_f64.argtypes = [c_void_p] * 4 + [c_int, c_int, ctypes.c_uint, c_int] + [c_void_p] * 7
+    # the plane-database distillation (include/gpp.h, csrc/plane_db.hip; absent from an older build named by GPP_LIB: it runs everything but
+    # utils/plane_db's device entry points)
+    if hasattr(lib, 'gpp_poll_costs_u16'):
+        lib.gpp_poll_costs_workspace_bytes.restype = c_int
+        lib.gpp_poll_costs_workspace_bytes.argtypes = [c_int, ctypes.POINTER(c_size_t)]
+        lib.gpp_poll_costs_u16.restype = c_int
+        lib.gpp_poll_costs_u16.argtypes = [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_int64, c_int64,
+                                           c_void_p, c_size_t, c_void_p]
+        lib.gpp_plane_select_workspace_bytes.restype = c_int
+        lib.gpp_plane_select_workspace_bytes.argtypes = [c_int, ctypes.POINTER(c_size_t)]
+        lib.gpp_plane_select.restype = c_int
+        lib.gpp_plane_select.argtypes = [c_void_p, c_int, c_int, c_int64, c_int] + [c_void_p] * 4 + [c_void_p, c_size_t, c_void_p]
     if hasattr(lib, 'gpp_detect_pixel_lists'):
         lib.gpp_detect_pixel_lists.restype = c_int
         lib.gpp_detect_pixel_lists.argtypes = [ctypes.POINTER(PixelListDesc), c_void_p]
@@ -475,6 +487,64 @@ def label_prep(labels, label_counts, P, trig, det_types=0, own_box=True, detecti
     check(lib().gpp_label_prep_f64(ptr(labels), ptr(label_counts), ptr(P), ptr(trig), B, A, int(det_types), int(bool(own_box)), ptr(mod),
                                    *(outs + [stream_ptr()])), 'gpp_label_prep_f64')
     return mod, det
+
+
+def table_pitch(M):
+    """ the smallest row pitch gpp_poll_costs_u16 and gpp_plane_select take for M planes: M rounded up to 8 (16 bytes) """
+    return max(8, (int(M) + 7) // 8 * 8)
+
+
+def poll_costs(boxes, dims, orient, P_inv, planes, table, row_index=None, row_offset=0, thr=0.7):
+    """ gpp_poll_costs_u16 on the current stream: boxes (B, D, 12), dims (B, D, 3) float32, orient (B, D) int32, P_inv (B, 4, 3) float32 and
+    planes (M, 4) float32 on the device; row_index (O,) int32 flat rows b * D + d, None = all B * D.  Fills the columns [0, M) of the rows
+    [row_offset, row_offset + O) of `table`, a (rows, pitch) int16 tensor that holds the uint16 keys (view it as uint16 on the host).
+    No synchronisation; returns O """
+    import torch
+    if boxes.dim() != 3 or planes.dim() != 2 or table.dim() != 2:
+        raise ValueError('gpp_poll_costs_u16: boxes must be (B, D, 12), planes (M, 4) and table (rows, pitch), got {} {} {}'.format(
+            tuple(boxes.shape), tuple(planes.shape), tuple(table.shape)))
+    B, D, M = int(boxes.shape[0]), int(boxes.shape[1]), int(planes.shape[0])
+    want = [(boxes, torch.float32, (B, D, 12)), (dims, torch.float32, (B, D, 3)), (orient, torch.int32, (B, D)), (P_inv, torch.float32, (B, 4, 3)),
+            (planes, torch.float32, (M, 4)), (table, torch.int16, tuple(table.shape))]
+    O = B * D
+    if row_index is not None:
+        O = int(row_index.numel())
+        want.append((row_index, torch.int32, (O,)))
+    for t, dtype, shape in want:
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != boxes.device:
+            raise ValueError('gpp_poll_costs_u16: expected {} {} on {}, got {} {} on {}'.format(shape, dtype, boxes.device, tuple(t.shape), t.dtype, t.device))
+    rows, pitch = int(table.shape[0]), int(table.shape[1])
+    if int(row_offset) < 0 or int(row_offset) + O > rows or pitch < M or pitch % 8:
+        raise ValueError('gpp_poll_costs_u16: rows [{}, {}) of {} planes do not fit a table of {} rows, pitch {} (pitch >= M, a multiple of 8)'.format(
+            int(row_offset), int(row_offset) + O, M, rows, pitch))
+    need = c_size_t(0)
+    check(lib().gpp_poll_costs_workspace_bytes(M, ctypes.byref(need)), 'gpp_poll_costs_workspace_bytes')
+    workspace = torch.empty((max(int(need.value), 16),), dtype=torch.uint8, device=boxes.device)
+    check(lib().gpp_poll_costs_u16(ptr(boxes), ptr(dims), ptr(orient), ptr(P_inv), ptr(planes), B, D, M, float(thr), ptr(row_index), O,
+                                   ptr(table), pitch, int(row_offset), ptr(workspace), workspace.numel(), stream_ptr()), 'gpp_poll_costs_u16')
+    return O
+
+
+def plane_select(table, M, K):
+    """ gpp_plane_select on the current stream: table (O, pitch) int16 on the device (uint16 keys), its first M columns the planes, K picks ->
+    (chosen (K,) int32, trace (K + 1,) int64, best (O,) int16 holding uint16 keys, count (1,) int32) on the device; no synchronisation """
+    import torch
+    if table.dim() != 2 or table.dtype != torch.int16:
+        raise ValueError('gpp_plane_select: table must be (O, pitch) int16, got {} {}'.format(tuple(table.shape), table.dtype))
+    O, pitch, M, K = int(table.shape[0]), int(table.shape[1]), int(M), int(K)
+    if O < 1 or M < 1 or pitch < M or pitch % 8 or K < 1 or K > M:
+        raise ValueError('gpp_plane_select: O = {}, M = {}, pitch = {}, K = {}: needs O >= 1, 1 <= K <= M <= pitch, pitch a multiple of 8'.format(O, M, pitch, K))
+    dev = table.device
+    chosen = torch.empty((K,), dtype=torch.int32, device=dev)
+    trace = torch.empty((K + 1,), dtype=torch.int64, device=dev)
+    best = torch.empty((O,), dtype=torch.int16, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    need = c_size_t(0)
+    check(lib().gpp_plane_select_workspace_bytes(M, ctypes.byref(need)), 'gpp_plane_select_workspace_bytes')
+    workspace = torch.empty((int(need.value),), dtype=torch.uint8, device=dev)
+    check(lib().gpp_plane_select(ptr(table), O, M, pitch, K, ptr(chosen), ptr(trace), ptr(best), ptr(count), ptr(workspace), workspace.numel(),
+                                 stream_ptr()), 'gpp_plane_select')
+    return chosen, trace, best, count
 
 
 def channel_absmax(buf, M, C, pitch, c_off, layout, out, stream=None):

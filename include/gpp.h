@@ -741,6 +741,54 @@ int gpp_label_prep_f64(const double* labels, const int32_t* label_counts, const 
                        float* boxes, float* dims, float* scores, int32_t* det_labels, int32_t* orientations, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Plane-database distillation (csrc/plane_db.hip; DESIGN.md section 4.21 is the specification, utils/plane_db.py the host side): from a
+ * pool of M candidate planes and the objects of a labelled dataset, the K planes that polling on that dataset loses least with.
+ *
+ * gpp_poll_costs_u16: the cost of serving object o with plane p alone, for every pair.  One workgroup per listed row, the pair arithmetic
+ * of gpp_poll_f32 (csrc/poll_eval.h: the same float32 operations in the same order).
+ *   boxes (B, D, 12), dims (B, D, 3), orient (B, D), P_inv (B, 4, 3), thr: exactly as gpp_poll_f32 takes them.
+ *   planes (M, 4) float32, 16-byte aligned, shared by the batch; canonicalised into the workspace as gpp_poll_f32 does.
+ *   row_index (O) int32: the flat rows b * D + d to evaluate, in table order; NULL: all B * D rows in order, and O must be B * D.
+ *   table: uint16, 16-byte aligned, `pitch` values per row with pitch >= M and pitch % 8 == 0.  Listed row i fills the columns [0, M) of
+ *   table row row_offset + i (row_offset >= 0: a dataset is filled chunk by chunk); the columns [M, pitch) are left untouched.
+ *   per pair, with zc, votes and res as polling computes them (votes of the six segments, res their residual SUM in metres):
+ *       invalid, if zc < 0.0f is true or res < FLT_MAX is false (a NaN residual):       key = GPP_PLANE_COST_INVALID
+ *       otherwise   s = res * 1024.0f,  q = (s < 8191.0f) ? (int)s : 8191,              key = (6 - (int)votes) * 8192 + q   (<= 57343)
+ *   the order in which polling itself ranks the planes of one object -- votes first, then the residual -- quantised to 1/1024 m.
+ *   A row whose orient is negative (the -1 padding of gpp_label_prep_f64), or a list entry outside [0, B * D), is
+ *   GPP_PLANE_COST_INVALID throughout.
+ *   workspace: gpp_poll_costs_workspace_bytes() bytes, 16-byte aligned (the canonical planes).
+ *   Null pointer, negative size, pitch < M or pitch % 8 != 0, O != B * D without a list: GPP_ERR_BAD_ARG; planes, table or workspace not
+ *   16-byte aligned: GPP_ERR_ALIGN; a short workspace: GPP_ERR_WORKSPACE; nothing is launched in any of these cases.
+ *   O * M == 0: GPP_OK, nothing launched.
+ *
+ * gpp_plane_select: greedy facility location on the table, in exact integers.
+ *   table, pitch: as above (16-byte aligned, pitch >= M, pitch % 8 == 0), O >= 1 rows, M >= 1 planes, 1 <= K <= M picks.
+ *   state       best[o] = 65535 for every row, trace[0] = 65535 * O.
+ *   pick k      gain[p] = sum over o of max(0, best[o] - table[o][p]);  p* = the FIRST index of the largest gain.
+ *               gain[p*] == 0: the run stops -- count stays k, chosen[k..K) = -1, trace[k+1..K] repeat trace[k].
+ *               otherwise chosen[k] = p*, best[o] = min(best[o], table[o][p*]), trace[k + 1] = trace[k] - gain[p*], count = k + 1.
+ *   The pick order is the result: the first K' entries of a run with K >= K' are the run with K'.  A plane is never picked twice (its
+ *   gain is 0 once it is in), and of two equal columns only the first can be picked.
+ *   chosen (K) int32, trace (K + 1) uint64 (8-byte aligned), best (O) uint16, count (1) int32: device, all written.
+ *   workspace: gpp_plane_select_workspace_bytes() bytes, 16-byte aligned (gain (M) uint64, then the done flag).
+ *   2 K + 1 plain launches in stream order: per pick one launch of ceil(O / 256) x ceil(M / 512) workgroups that adds the gains (16-byte
+ *   loads of 8 planes of a row, 32-bit partial sums over a slab of 256 rows, 64-bit atomic adds: integer sums do not depend on the order)
+ *   and one single-workgroup launch that picks, lowers `best` and clears the gains.  Once the run has stopped the remaining launches
+ *   return at once.  Nothing is read back: the caller fetches `count` when the stream has finished.
+ *   K > M, K < 1, O < 1, M < 1, a bad pitch or a null pointer: GPP_ERR_BAD_ARG; alignment: GPP_ERR_ALIGN; a short workspace:
+ *   GPP_ERR_WORKSPACE; nothing is launched in any of these cases.
+ * ---------------------------------------------------------------------------------------- */
+#define GPP_PLANE_COST_INVALID 65535
+int gpp_poll_costs_workspace_bytes(int M, size_t* bytes);
+int gpp_poll_costs_u16(const float* boxes, const float* dims, const int32_t* orient, const float* P_inv, const float* planes,
+                       int B, int D, int M, float thr, const int32_t* row_index, int O, uint16_t* table, int64_t pitch,
+                       int64_t row_offset, void* workspace, size_t workspace_bytes, void* stream);
+int gpp_plane_select_workspace_bytes(int M, size_t* bytes);
+int gpp_plane_select(const uint16_t* table, int O, int M, int64_t pitch, int K, int32_t* chosen, uint64_t* trace,
+                     uint16_t* best, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The --save-images composite on the device (csrc/draw.hip; DESIGN.md section 4.14 is the specification, utils/visualization.py its host
  * form): per image the 2-D picture (boxes, keypoint markers, score captions) over the 3-D picture (projected cuboids, residual captions),
  * from the rows of gpp_pose_f32 and the raw uint8 BGR frames.  Two launches on one stream: gpp_draw_build, then gpp_draw_raster.
