@@ -2,7 +2,7 @@
 //
 // Every C-ABI entry point validates its descriptors on the host before anything reaches the device; the device-free ones -- gpp_conv2d_flops,
 // gpp_conv2d_split_rule, gpp_conv2d_workspace_bytes, gpp_conv2d_tile_candidates, gpp_stem_pack_weights_f16 / _f16x3 -- and the argument checks of
-// the launching ones (gpp_conv2d_igemm, gpp_bottleneck_tail, gpp_bottleneck_block, gpp_plan_run, gpp_poll_f32, gpp_draw_build, gpp_draw_raster, gpp_poll_costs_u16, gpp_plane_select, ...: without a device they end
+// the launching ones (gpp_conv2d_igemm, gpp_bottleneck_tail, gpp_bottleneck_block, gpp_plan_run, gpp_poll_f32, gpp_draw_build, gpp_draw_raster, gpp_poll_costs_u16, gpp_plane_select, gpp_road_*, ...: without a device they end
 // in an error code before any launch) are run here over a file of descriptors the test generated, in a build of the library's host code
 // with -fsanitize=address,undefined.  A bad descriptor must come back as GPP_ERR_* (or a hipError_t from the absent device); nothing may
 // trip a sanitizer.  Device pointers inside the descriptors are never dereferenced by host code: they are fuzzed like every other field.
@@ -183,6 +183,32 @@ int main(int argc, char** argv)
             note(gpp_plane_select((const uint16_t*)((uintptr_t)r.d[0].in | 2), (int)(r.a % 5000) + 1, (int)(r.b % 3000) + 1, (int64_t)((r.b % 3000) + 8) / 8 * 8,
                                   (int)(r.c % 16) + 1, (int32_t*)(uintptr_t)r.d[0].bias, (uint64_t*)r.d[0].out, (uint16_t*)r.d[0].out,
                                   (int32_t*)(uintptr_t)r.d[0].bias, r.d[0].out, (size_t)r.d[0].partial_bytes, nullptr));
+            // the road fit's host halves: null pointers, F = 0, H = 0, region bounds over the caps, a frame bound above the total, NaN gates,
+            // misaligned points and sums.  (The offsets are device memory: a descending pair is the kernels' to refuse, gpp.h.)
+            {
+                const int32_t* i32 = (const int32_t*)(uintptr_t)r.d[0].bias;
+                const uint32_t* u32 = (const uint32_t*)(uintptr_t)r.d[0].bias;
+                const int F = (int)(r.a % 70000), total = (int)(r.b >> 1), mp = (int)(r.c % ((1u << 20) + 3));
+                const double nan = __builtin_nan(""), g = (r.a & 1) ? nan : (double)(int32_t)r.b;
+                note(gpp_road_points_i32(nullptr, nullptr, nullptr, (int)r.a, (int)r.b, (int)r.c, 1, 1, 1, nullptr, nullptr, nullptr));
+                note(gpp_road_points_i32(nullptr, nullptr, nullptr, 0, 0, 0, 5120, 2048, 12800, nullptr, nullptr, nullptr));
+                note(gpp_road_points_i32((const float*)((uintptr_t)r.d[0].in | ((r.a & 2) ? 4 : 0)), i32, (const double*)r.d[0].weight, F, total, mp,
+                                         (int)(r.a % 10243), (int)(r.b % 2051), (int)(r.c % 20483), (int32_t*)r.d[0].out, (int32_t*)r.d[0].out, nullptr));
+                if (gpp_road_points_i32((const float*)r.d[0].in, i32, (const double*)r.d[0].weight, 1, 8, 8, 10240 + (r.a % 3 == 0), 2048 + (r.a % 3 == 1),
+                                        20480 + (r.a % 3 == 2), (int32_t*)r.d[0].out, (int32_t*)r.d[0].out, nullptr) == 0) {
+                    fprintf(stderr, "a road region over the caps was accepted\n"); return 3;
+                }
+                note(gpp_road_score(nullptr, nullptr, nullptr, nullptr, r.a, (int)r.b, (int)r.c, (int)r.a, (int)r.b, 0.9, 1.0, 2.0, 3.0, nullptr, nullptr));
+                note(gpp_road_score(i32, i32, i32, u32, r.c, F, total, mp, 0, 0.9, 1.0, 2.0, 3.0, (int32_t*)r.d[0].out, nullptr));
+                note(gpp_road_score(i32, i32, i32, u32, r.c, 0, total, 0, (int)(r.b % 5000), 0.9, 1.0, 2.0, 3.0, (int32_t*)r.d[0].out, nullptr));
+                note(gpp_road_score(i32, i32, i32, u32, r.c, F, total, mp, (int)(r.b % 5000), g, g, (r.a & 4) ? nan : 2.0 * g, (double)(int32_t)r.c,
+                                    (r.a & 8) ? nullptr : (int32_t*)r.d[0].out, nullptr));
+                note(gpp_road_winner(nullptr, (int)r.a, (int)r.b, (int)r.c, nullptr, nullptr, nullptr));
+                note(gpp_road_winner(i32, F, (int)(r.b % 5000), (int)(r.c % 300) - 1, (int32_t*)r.d[0].out, (r.a & 8) ? nullptr : (int32_t*)r.d[0].out, nullptr));
+                note(gpp_road_moments(nullptr, nullptr, nullptr, nullptr, r.a, nullptr, (int)r.b, (int)r.c, (int)r.a, (int)r.b, 1.0, nullptr, nullptr));
+                note(gpp_road_moments(i32, i32, i32, u32, r.c, i32, F, total, mp, (int)(r.b % 5000), (r.a & 4) ? nan : 655.36,
+                                      (int64_t*)((uintptr_t)r.d[0].out | ((r.a & 16) ? 4 : 0)), nullptr));
+            }
             break;
         }
         }

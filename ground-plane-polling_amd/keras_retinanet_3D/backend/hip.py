@@ -177,6 +177,18 @@ def _declare(lib):
         lib.gpp_plane_select_workspace_bytes.argtypes = [c_int, ctypes.POINTER(c_size_t)]
         lib.gpp_plane_select.restype = c_int
         lib.gpp_plane_select.argtypes = [c_void_p, c_int, c_int, c_int64, c_int] + [c_void_p] * 4 + [c_void_p, c_size_t, c_void_p]
+    # the per-frame road-plane fit (include/gpp.h, csrc/road_fit.hip; absent from an older build named by GPP_LIB: it runs everything but
+    # utils/road_fit's device entry points)
+    if hasattr(lib, 'gpp_road_score'):
+        c_double, c_uint32 = ctypes.c_double, ctypes.c_uint32
+        lib.gpp_road_points_i32.restype = c_int
+        lib.gpp_road_points_i32.argtypes = [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 3
+        lib.gpp_road_score.restype = c_int
+        lib.gpp_road_score.argtypes = [c_void_p] * 4 + [c_uint32] + [c_int] * 4 + [c_double] * 4 + [c_void_p] * 2
+        lib.gpp_road_winner.restype = c_int
+        lib.gpp_road_winner.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+        lib.gpp_road_moments.restype = c_int
+        lib.gpp_road_moments.argtypes = [c_void_p] * 4 + [c_uint32, c_void_p] + [c_int] * 4 + [c_double, c_void_p, c_void_p]
     if hasattr(lib, 'gpp_detect_pixel_lists'):
         lib.gpp_detect_pixel_lists.restype = c_int
         lib.gpp_detect_pixel_lists.argtypes = [ctypes.POINTER(PixelListDesc), c_void_p]
@@ -545,6 +557,67 @@ def plane_select(table, M, K):
     check(lib().gpp_plane_select(ptr(table), O, M, pitch, K, ptr(chosen), ptr(trace), ptr(best), ptr(count), ptr(workspace), workspace.numel(),
                                  stream_ptr()), 'gpp_plane_select')
     return chosen, trace, best, count
+
+
+def _road_check(what, want, dev):
+    for t, dtype, shape in want:
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev:
+            raise ValueError('{}: expected {} {} on {}, got {} {} on {}'.format(what, shape, dtype, dev, tuple(t.shape), t.dtype, t.device))
+
+
+def road_points(points, offsets, T, max_points, region_q):
+    """ gpp_road_points_i32 on the current stream: points (total, 4) float32, offsets (F + 1) int32 and T (F, 12) float64 on the device,
+    max_points >= every frame's size, region_q = (xq, yq, zq) in quanta -> (q (total, 3) int32, kept (F,) int32) on the device; the rows of
+    q past a frame's kept count are zero.  No synchronisation """
+    import torch
+    if points.dim() != 2 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError('gpp_road_points_i32: points must be (total, 4) and offsets (F + 1,), got {} {}'.format(tuple(points.shape), tuple(offsets.shape)))
+    total, F = int(points.shape[0]), int(offsets.numel()) - 1
+    _road_check('gpp_road_points_i32', ((points, torch.float32, (total, 4)), (offsets, torch.int32, (F + 1,)), (T, torch.float64, (F, 12))), points.device)
+    q = torch.zeros((total, 3), dtype=torch.int32, device=points.device)
+    kept = torch.zeros((F,), dtype=torch.int32, device=points.device)
+    xq, yq, zq = [int(v) for v in region_q]
+    check(lib().gpp_road_points_i32(ptr(points), ptr(offsets), ptr(T), F, total, int(max_points), xq, yq, zq, ptr(q), ptr(kept), stream_ptr()),
+          'gpp_road_points_i32')
+    return q, kept
+
+
+def road_score(q, offsets, kept, frame_id, seed, max_points, H, c2, hlo2, hhi2, tq2):
+    """ gpp_road_score on the current stream: q (total, 3) int32, offsets (F + 1,), kept (F,) int32 and frame_id (F,) int32 holding the uint32
+    ids, on the device -> count (F, H) int32 on the device (-1 = an invalid hypothesis); no synchronisation """
+    import torch
+    total, F, H = int(q.shape[0]), int(kept.numel()), int(H)
+    _road_check('gpp_road_score', ((q, torch.int32, (total, 3)), (offsets, torch.int32, (F + 1,)), (kept, torch.int32, (F,)),
+                                   (frame_id, torch.int32, (F,))), q.device)
+    count = torch.empty((F, max(H, 0)), dtype=torch.int32, device=q.device)
+    check(lib().gpp_road_score(ptr(q), ptr(offsets), ptr(kept), ptr(frame_id), int(seed) & 0xffffffff, F, total, int(max_points), H,
+                               float(c2), float(hlo2), float(hhi2), float(tq2), ptr(count), stream_ptr()), 'gpp_road_score')
+    return count
+
+
+def road_winner(count, min_inliers):
+    """ gpp_road_winner on the current stream: count (F, H) int32 on the device -> (winner (F,) int32, -1 = no plane; inliers (F,) int32) """
+    import torch
+    if count.dim() != 2 or count.dtype != torch.int32:
+        raise ValueError('gpp_road_winner: count must be (F, H) int32, got {} {}'.format(tuple(count.shape), count.dtype))
+    F, H = int(count.shape[0]), int(count.shape[1])
+    winner = torch.full((F,), -1, dtype=torch.int32, device=count.device)
+    inliers = torch.zeros((F,), dtype=torch.int32, device=count.device)
+    check(lib().gpp_road_winner(ptr(count), F, H, int(min_inliers), ptr(winner), ptr(inliers), stream_ptr()), 'gpp_road_winner')
+    return winner, inliers
+
+
+def road_moments(q, offsets, kept, frame_id, seed, winner, max_points, H, tq2):
+    """ gpp_road_moments on the current stream -> sums (F, 10) int64 on the device: N, Sx, Sy, Sz, Sxx, Sxz, Szz, Sxy, Szy, Syy over the
+    winner's inliers, zero for a frame without a winner; no synchronisation """
+    import torch
+    total, F = int(q.shape[0]), int(kept.numel())
+    _road_check('gpp_road_moments', ((q, torch.int32, (total, 3)), (offsets, torch.int32, (F + 1,)), (kept, torch.int32, (F,)),
+                                     (frame_id, torch.int32, (F,)), (winner, torch.int32, (F,))), q.device)
+    sums = torch.zeros((F, 10), dtype=torch.int64, device=q.device)
+    check(lib().gpp_road_moments(ptr(q), ptr(offsets), ptr(kept), ptr(frame_id), int(seed) & 0xffffffff, ptr(winner), F, total, int(max_points),
+                                 int(H), float(tq2), ptr(sums), stream_ptr()), 'gpp_road_moments')
+    return sums
 
 
 def channel_absmax(buf, M, C, pitch, c_off, layout, out, stream=None):

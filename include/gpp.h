@@ -789,6 +789,65 @@ int gpp_plane_select(const uint16_t* table, int O, int M, int64_t pitch, int K, 
                      uint16_t* best, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Per-frame road-plane fit (csrc/road_fit.hip; DESIGN.md section 4.22 is the specification, utils/road_fit.py the host side and the NumPy
+ * form): from a batch of LiDAR scans one plane per frame, in rectified camera coordinates -- the pool that gpp_poll_costs_u16 /
+ * gpp_plane_select distil.  Exact integers: points are quantised once at GPP_ROAD_Q quanta per metre and every later quantity is an integer
+ * below 2^53 or one rounded float64 operation of such integers, so every output equals the NumPy form and does not depend on the order of
+ * lanes or atomics.  Four plain launches in stream order (points, score, winner, moments); no workspace; the 2 x 2 solve is the host's.
+ *
+ * The ragged batch: frame f owns the points [offsets[f], offsets[f + 1]) of `points` and the same rows of `q`.  offsets (F + 1) int32 is
+ * DEVICE memory; the host passes what it knows of it, total = offsets[F] and max_points >= every frame's size.  A frame whose offsets
+ * descend, leave [0, total] or span more than max_points is an empty frame to every kernel (kept 0, counts -1, winner -1, sums 0): nothing
+ * is read or written outside [0, total).  F <= 65535 (chunk a dataset), max_points <= GPP_ROAD_MAX_POINTS = 2^20, max_points <= total
+ * <= GPP_ROAD_MAX_TOTAL.
+ *
+ * gpp_road_points_i32: gate and quantise.  One workgroup per frame, chunks of 256 points, a stable compaction.
+ *   points (total, 4) float32 x y z reflectance, 16-byte aligned; T (F, 12) float64: per frame R0_rect . Tr_velo_to_cam, rows of 4.
+ *   per point and row r, in float64, every operation rounded:  v_r = ((T[r][0] x + T[r][1] y) + T[r][2] z) + T[r][3],
+ *   q_r = floor(v_r * 256.0 + 0.5);  kept iff |q_0| <= xq, |q_1| <= yq and 1 <= q_2 <= zq on the doubles (NaN and infinity fail).
+ *   xq, yq, zq: the region in quanta, 0 <= xq <= 10240, 0 <= yq <= 2048, 1 <= zq <= 20480 (40 m, 8 m, 80 m).  These caps are what bound
+ *   everything below: a difference of two points < 2^15.4 per axis, a cross-product component < 2^33, n . (p - p0) < 2^51.
+ *   q (total, 3) int32: the kept points of frame f, IN THE SCAN'S ORDER, at rows offsets[f] ... offsets[f] + kept[f]; the rest of the
+ *   frame's rows are left untouched.  kept (F) int32.
+ *
+ * gpp_road_score: count (F, H) int32.  mix(u): u ^= u >> 16, u *= 0x7feb352d, u ^= u >> 15, u *= 0x846ca68b, u ^= u >> 16 (uint32).
+ *   hypothesis h of frame f with m = kept[f]:  r_k = mix(mix(mix(seed + frame_id[f]) + h) + k), i_k = (uint64(r_k) * m) >> 32, k = 0 1 2;
+ *   n = (p_i1 - p_i0) x (p_i2 - p_i0), d0 = n . p_i0 (integers); nn = (nx nx + ny ny) + nz nz in float64, every operation rounded;
+ *   valid iff m >= 3, nn > 0, ny ny >= c2 nn and hlo2 nn <= d0 d0 <= hhi2 nn (float64 products of the integers' exact conversions).
+ *   count = the number of kept points p of the frame with dot dot <= tq2 nn, dot = n . p - d0 (an integer, converted exactly);
+ *   an invalid hypothesis: count = -1.  frame_id (F) uint32 and seed make the draws: chunking a dataset never changes a frame's draws.
+ *   c2 in [0, 1], 0 <= hlo2 <= hhi2, tq2 >= 0 (cos^2 of the largest tilt, the height band and the threshold in quanta, squared).
+ *   Grid: ceil(H / 256) x min(ceil(max_points / GPP_ROAD_SLAB), 64) x F workgroups, one lane per hypothesis; a workgroup walks every
+ *   64th slab of GPP_ROAD_SLAB points, staged in LDS as float64 and read as a broadcast, and adds the lane's count with one atomicAdd.
+ *   `count` is cleared first.
+ *   H <= GPP_ROAD_MAX_HYPOTHESES.  F == 0 or H == 0: GPP_OK, nothing launched.
+ *
+ * gpp_road_winner: per frame the largest count and the FIRST h among equals.  winner (F) int32: that h, or -1 when the count is below
+ *   min_inliers (>= 1) or no hypothesis is valid; inliers (F) int32: the largest count, 0 when no hypothesis is valid.
+ *
+ * gpp_road_moments: sums (F, 10) int64, 8-byte aligned: N, Sx, Sy, Sz, Sxx, Sxz, Szz, Sxy, Szy, Syy over the inliers (the rule of
+ *   gpp_road_score) of the winner's plane, recomputed from its three draws; zero for a frame without a winner.  ceil(max_points / 2048) x F
+ *   workgroups, 64-bit integer atomics.  A frame has at most 2^20 points: every sum < 2^50.
+ *
+ * Null pointer, a size or bound outside the ranges above: GPP_ERR_BAD_ARG; alignment: GPP_ERR_ALIGN; nothing is launched in these cases.
+ * ---------------------------------------------------------------------------------------- */
+#define GPP_ROAD_Q 256
+#define GPP_ROAD_MAX_XQ 10240
+#define GPP_ROAD_MAX_YQ 2048
+#define GPP_ROAD_MAX_ZQ 20480
+#define GPP_ROAD_SLAB 512
+#define GPP_ROAD_MAX_POINTS (1 << 20)
+#define GPP_ROAD_MAX_TOTAL (1 << 30)
+#define GPP_ROAD_MAX_HYPOTHESES (1 << 20)
+int gpp_road_points_i32(const float* points, const int32_t* offsets, const double* T, int F, int total, int max_points,
+                        int xq, int yq, int zq, int32_t* q, int32_t* kept, void* stream);
+int gpp_road_score(const int32_t* q, const int32_t* offsets, const int32_t* kept, const uint32_t* frame_id, uint32_t seed,
+                   int F, int total, int max_points, int H, double c2, double hlo2, double hhi2, double tq2, int32_t* count, void* stream);
+int gpp_road_winner(const int32_t* count, int F, int H, int min_inliers, int32_t* winner, int32_t* inliers, void* stream);
+int gpp_road_moments(const int32_t* q, const int32_t* offsets, const int32_t* kept, const uint32_t* frame_id, uint32_t seed,
+                     const int32_t* winner, int F, int total, int max_points, int H, double tq2, int64_t* sums, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The --save-images composite on the device (csrc/draw.hip; DESIGN.md section 4.14 is the specification, utils/visualization.py its host
  * form): per image the 2-D picture (boxes, keypoint markers, score captions) over the 3-D picture (projected cuboids, residual captions),
  * from the rows of gpp_pose_f32 and the raw uint8 BGR frames.  Two launches on one stream: gpp_draw_build, then gpp_draw_raster.
