@@ -2,7 +2,7 @@
 //
 // Every C-ABI entry point validates its descriptors on the host before anything reaches the device; the device-free ones -- gpp_conv2d_flops,
 // gpp_conv2d_split_rule, gpp_conv2d_workspace_bytes, gpp_conv2d_tile_candidates, gpp_stem_pack_weights_f16 / _f16x3 -- and the argument checks of
-// the launching ones (gpp_conv2d_igemm, gpp_bottleneck_tail, gpp_bottleneck_block, gpp_plan_run, gpp_poll_f32, gpp_draw_build, gpp_draw_raster, gpp_poll_costs_u16, gpp_plane_select, gpp_road_*, ...: without a device they end
+// the launching ones (gpp_conv2d_igemm, gpp_bottleneck_tail, gpp_bottleneck_block, gpp_plan_run, gpp_poll_f32, gpp_draw_build, gpp_draw_raster, gpp_poll_costs_u16, gpp_plane_select, gpp_pose_costs_u16, gpp_plane_select_polled, gpp_road_*, ...: without a device they end
 // in an error code before any launch) are run here over a file of descriptors the test generated, in a build of the library's host code
 // with -fsanitize=address,undefined.  A bad descriptor must come back as GPP_ERR_* (or a hipError_t from the absent device); nothing may
 // trip a sanitizer.  Device pointers inside the descriptors are never dereferenced by host code: they are fuzzed like every other field.
@@ -183,6 +183,28 @@ int main(int argc, char** argv)
             note(gpp_plane_select((const uint16_t*)((uintptr_t)r.d[0].in | 2), (int)(r.a % 5000) + 1, (int)(r.b % 3000) + 1, (int64_t)((r.b % 3000) + 8) / 8 * 8,
                                   (int)(r.c % 16) + 1, (int32_t*)(uintptr_t)r.d[0].bias, (uint64_t*)r.d[0].out, (uint16_t*)r.d[0].out,
                                   (int32_t*)(uintptr_t)r.d[0].bias, r.d[0].out, (size_t)r.d[0].partial_bytes, nullptr));
+            // ... and of the polled-location pair (two tables: either one null or misaligned, a short workspace, K > M, a bad pitch)
+            note(gpp_plane_select_polled_workspace_bytes((int)r.b, nullptr));
+            note(gpp_plane_select_polled_workspace_bytes((int)r.a, &wb));
+            note(gpp_pose_costs_u16(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, (int)r.a, (int)r.b, (int)r.c, 0.7f, nullptr, (int)(r.a * r.b),
+                                    nullptr, nullptr, (int64_t)r.c, (int64_t)(int32_t)r.b, nullptr, 0, nullptr));
+            note(gpp_pose_costs_u16((const float*)r.d[0].in, (const float*)r.d[0].in, (const int32_t*)(uintptr_t)r.d[0].bias, (const float*)r.d[0].in,
+                                    (const float*)r.d[0].in, (const float*)((uintptr_t)r.d[0].weight | ((r.a & 1) ? 4 : 0)), (int)(r.a % 64) + 1,
+                                    (int)(r.b % 64) + 1, (int)(r.c % 3000) + 1, 0.7f, (const int32_t*)(uintptr_t)r.d[0].bias, (int)(r.b % 500),
+                                    (uint16_t*)r.d[0].out, (uint16_t*)((uintptr_t)r.d[0].out | ((r.a & 2) ? 2 : 0)), (int64_t)((r.c % 3000) + 8) / 8 * 8, 0,
+                                    r.d[0].out, (size_t)r.d[0].partial_bytes, nullptr));
+            note(gpp_pose_costs_u16((const float*)r.d[0].in, (const float*)r.d[0].in, (const int32_t*)(uintptr_t)r.d[0].bias, (const float*)r.d[0].in,
+                                    (const float*)r.d[0].in, (const float*)r.d[0].weight, 2, 5, (int)(r.c % 3000) + 1, 0.7f, nullptr, 10,
+                                    (uint16_t*)r.d[0].out, (r.a & 4) ? nullptr : (uint16_t*)r.d[0].out, (int64_t)(r.c % 3000) + 1, 0, r.d[0].out, 0, nullptr));
+            note(gpp_plane_select_polled(nullptr, nullptr, (int)r.a, (int)r.b, (int64_t)(int32_t)r.c, (int)r.c, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                         nullptr, 0, nullptr));
+            note(gpp_plane_select_polled((const uint16_t*)r.d[0].in, (const uint16_t*)((uintptr_t)r.d[0].in | 2), (int)(r.a % 5000) + 1, (int)(r.b % 3000) + 1,
+                                         (int64_t)((r.b % 3000) + 8) / 8 * 8, (int)(r.c % 16) + 1, (int32_t*)(uintptr_t)r.d[0].bias, (uint64_t*)r.d[0].out,
+                                         (uint16_t*)r.d[0].out, (uint16_t*)r.d[0].out, (int32_t*)(uintptr_t)r.d[0].bias, r.d[0].out,
+                                         (size_t)r.d[0].partial_bytes, nullptr));
+            note(gpp_plane_select_polled((const uint16_t*)r.d[0].in, (r.a & 1) ? nullptr : (const uint16_t*)r.d[0].in, 8, (int)(r.b % 64) + 1,
+                                         (int64_t)(r.b % 64) + 1, (int)(r.c % 80), (int32_t*)(uintptr_t)r.d[0].bias, (uint64_t*)r.d[0].out, (uint16_t*)r.d[0].out,
+                                         (uint16_t*)r.d[0].out, (int32_t*)(uintptr_t)r.d[0].bias, r.d[0].out, 0, nullptr));
             // the road fit's host halves: null pointers, F = 0, H = 0, region bounds over the caps, a frame bound above the total, NaN gates,
             // misaligned points and sums.  (The offsets are device memory: a descending pair is the kernels' to refuse, gpp.h.)
             {

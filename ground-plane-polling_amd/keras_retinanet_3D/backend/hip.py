@@ -177,6 +177,15 @@ def _declare(lib):
         lib.gpp_plane_select_workspace_bytes.argtypes = [c_int, ctypes.POINTER(c_size_t)]
         lib.gpp_plane_select.restype = c_int
         lib.gpp_plane_select.argtypes = [c_void_p, c_int, c_int, c_int64, c_int] + [c_void_p] * 4 + [c_void_p, c_size_t, c_void_p]
+    # the distillation for the polled location error (absent from an older build: utils/plane_db's objective='location' needs it)
+    if hasattr(lib, 'gpp_pose_costs_u16'):
+        lib.gpp_pose_costs_u16.restype = c_int
+        lib.gpp_pose_costs_u16.argtypes = [c_void_p] * 6 + [c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int64,
+                                           c_void_p, c_size_t, c_void_p]
+        lib.gpp_plane_select_polled_workspace_bytes.restype = c_int
+        lib.gpp_plane_select_polled_workspace_bytes.argtypes = [c_int, ctypes.POINTER(c_size_t)]
+        lib.gpp_plane_select_polled.restype = c_int
+        lib.gpp_plane_select_polled.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int64, c_int] + [c_void_p] * 5 + [c_void_p, c_size_t, c_void_p]
     # the per-frame road-plane fit (include/gpp.h, csrc/road_fit.hip; absent from an older build named by GPP_LIB: it runs everything but
     # utils/road_fit's device entry points)
     if hasattr(lib, 'gpp_road_score'):
@@ -557,6 +566,63 @@ def plane_select(table, M, K):
     check(lib().gpp_plane_select(ptr(table), O, M, pitch, K, ptr(chosen), ptr(trace), ptr(best), ptr(count), ptr(workspace), workspace.numel(),
                                  stream_ptr()), 'gpp_plane_select')
     return chosen, trace, best, count
+
+
+def pose_costs(boxes, dims, orient, P_inv, want, planes, keys, errs, row_index=None, row_offset=0, thr=0.7):
+    """ gpp_pose_costs_u16 on the current stream: the arguments of poll_costs, with want (B, D, 3) float32 (the labels' locations) and two
+    tables of one shape, (rows, pitch) int16: `keys` gets what poll_costs writes, `errs` the location error of every pair in 1/256 m
+    (65535 where the key is).  No synchronisation; returns O """
+    import torch
+    if boxes.dim() != 3 or planes.dim() != 2 or keys.dim() != 2:
+        raise ValueError('gpp_pose_costs_u16: boxes must be (B, D, 12), planes (M, 4) and keys (rows, pitch), got {} {} {}'.format(
+            tuple(boxes.shape), tuple(planes.shape), tuple(keys.shape)))
+    B, D, M = int(boxes.shape[0]), int(boxes.shape[1]), int(planes.shape[0])
+    expect = [(boxes, torch.float32, (B, D, 12)), (dims, torch.float32, (B, D, 3)), (orient, torch.int32, (B, D)), (P_inv, torch.float32, (B, 4, 3)),
+              (want, torch.float32, (B, D, 3)), (planes, torch.float32, (M, 4)), (keys, torch.int16, tuple(keys.shape)),
+              (errs, torch.int16, tuple(keys.shape))]
+    O = B * D
+    if row_index is not None:
+        O = int(row_index.numel())
+        expect.append((row_index, torch.int32, (O,)))
+    for t, dtype, shape in expect:
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != boxes.device or not t.is_contiguous():
+            raise ValueError('gpp_pose_costs_u16: expected contiguous {} {} on {}, got {} {} on {}'.format(shape, dtype, boxes.device, tuple(t.shape), t.dtype, t.device))
+    rows, pitch = int(keys.shape[0]), int(keys.shape[1])
+    if int(row_offset) < 0 or int(row_offset) + O > rows or pitch < M or pitch % 8:
+        raise ValueError('gpp_pose_costs_u16: rows [{}, {}) of {} planes do not fit tables of {} rows, pitch {} (pitch >= M, a multiple of 8)'.format(
+            int(row_offset), int(row_offset) + O, M, rows, pitch))
+    need = c_size_t(0)
+    check(lib().gpp_poll_costs_workspace_bytes(M, ctypes.byref(need)), 'gpp_poll_costs_workspace_bytes')
+    workspace = torch.empty((max(int(need.value), 16),), dtype=torch.uint8, device=boxes.device)
+    check(lib().gpp_pose_costs_u16(ptr(boxes), ptr(dims), ptr(orient), ptr(P_inv), ptr(want), ptr(planes), B, D, M, float(thr), ptr(row_index), O,
+                                   ptr(keys), ptr(errs), pitch, int(row_offset), ptr(workspace), workspace.numel(), stream_ptr()), 'gpp_pose_costs_u16')
+    return O
+
+
+def plane_select_polled(keys, errs, M, K):
+    """ gpp_plane_select_polled on the current stream: keys and errs (O, pitch) int16 on the device (uint16 values), their first M columns
+    the planes, K picks -> (chosen (K,) int32, trace (K + 1,) int64, best (O,), cur (O,) int16 holding uint16 values, count (1,) int32) on
+    the device; no synchronisation """
+    import torch
+    if keys.dim() != 2 or keys.dtype != torch.int16 or errs.dtype != torch.int16 or tuple(errs.shape) != tuple(keys.shape) or \
+            errs.device != keys.device or not keys.is_contiguous() or not errs.is_contiguous():
+        raise ValueError('gpp_plane_select_polled: keys and errs must be contiguous (O, pitch) int16 of one shape on one device, got {} {} and {} {}'.format(
+            tuple(keys.shape), keys.dtype, tuple(errs.shape), errs.dtype))
+    O, pitch, M, K = int(keys.shape[0]), int(keys.shape[1]), int(M), int(K)
+    if O < 1 or M < 1 or pitch < M or pitch % 8 or K < 1 or K > M:
+        raise ValueError('gpp_plane_select_polled: O = {}, M = {}, pitch = {}, K = {}: needs O >= 1, 1 <= K <= M <= pitch, pitch a multiple of 8'.format(O, M, pitch, K))
+    dev = keys.device
+    chosen = torch.empty((K,), dtype=torch.int32, device=dev)
+    trace = torch.empty((K + 1,), dtype=torch.int64, device=dev)
+    best = torch.empty((O,), dtype=torch.int16, device=dev)
+    cur = torch.empty((O,), dtype=torch.int16, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    need = c_size_t(0)
+    check(lib().gpp_plane_select_polled_workspace_bytes(M, ctypes.byref(need)), 'gpp_plane_select_polled_workspace_bytes')
+    workspace = torch.empty((int(need.value),), dtype=torch.uint8, device=dev)
+    check(lib().gpp_plane_select_polled(ptr(keys), ptr(errs), O, M, pitch, K, ptr(chosen), ptr(trace), ptr(best), ptr(cur), ptr(count), ptr(workspace),
+                                        workspace.numel(), stream_ptr()), 'gpp_plane_select_polled')
+    return chosen, trace, best, cur, count
 
 
 def _road_check(what, want, dev):

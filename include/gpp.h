@@ -789,6 +789,55 @@ int gpp_plane_select(const uint16_t* table, int O, int M, int64_t pitch, int K, 
                      uint16_t* best, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same distillation for the location error that polling leaves (csrc/plane_db.hip, csrc/pose_eval.h; DESIGN.md section 4.23 is the
+ * specification, utils/plane_db.py the host side and the NumPy form).  Opt-in: nothing above changes.
+ *
+ * gpp_pose_costs_u16: two tables from one evaluation of every pair, both uint16, (O, pitch), laid out as the table above.
+ *   keys[o][p]  exactly what gpp_poll_costs_u16 writes for the same call.
+ *   errs[o][p]  the distance between the location that pose recovery gives object o when polling has plane p alone, and the label's.
+ *   want (B, D, 3) float32: the labels' locations (label columns 11:14, rounded to float32 once on the host), indexed like dims.
+ *   With X[0..3] = X_l, X_m, X_r, X_t of the pair, o = orient, w = dims[1], float32, every operation separate, norm3 and cross3 as in
+ *   csrc/poll_eval.h (norm3(a) = sqrt((a.x a.x + a.y a.y) + a.z a.z)):
+ *       X_s = (o == 0 || o == 3) ? X_l : X_r
+ *       h = norm3(X_t - X_m),  e = norm3(X_s - X_m)
+ *       y = (X_m - X_t) / h                        component by component
+ *       x = (sx * (X_m - X_s)) / e                 sx = +1, +1, -1, -1 for o = 0..3
+ *       z = cross3(x, y)
+ *       loc = (X_m + X_s) / 2 + ((sz * z) * w) / 2                sz = +1, -1, +1, -1 for o = 0..3
+ *       dist = norm3(loc - want),  s = dist * 256.0f,  q = (s < 65534.0f) ? (int)s : 65534     (a NaN or infinite s: 65534)
+ *       errs = GPP_PLANE_COST_INVALID exactly where keys is, else q: 1/256 m per quantum, saturating just below 256 m.
+ *   Every other argument, the checks, the alignment (keys and errs both), the workspace (gpp_poll_costs_workspace_bytes), padding rows,
+ *   list entries outside the batch (both tables GPP_PLANE_COST_INVALID) and the untouched pad columns: exactly as gpp_poll_costs_u16.
+ *
+ * gpp_plane_select_polled: a greedy selection on the two tables for the error of the plane that polling itself would pick.
+ *   state       best[o] = cur[o] = 65535 for every row: the smallest key among the picks so far and the error of the plane that holds it;
+ *               trace[0] = 65535 * O.
+ *   pick k      gain[p] = sum over o with keys[o][p] < best[o] of (cur[o] - errs[o][p]): a signed 64-bit sum, its terms may be negative.
+ *               p* = the FIRST index of the largest gain.  gain[p*] <= 0: the run stops -- count stays k, chosen[k..K) = -1,
+ *               trace[k+1..K] repeat trace[k].  Otherwise chosen[k] = p*; for the rows with keys[o][p*] < best[o]: best[o] = keys[o][p*],
+ *               cur[o] = errs[o][p*]; trace[k + 1] = trace[k] - gain[p*], count = k + 1.
+ *   The inequality is strict: the incumbent stands earlier in the written database, and polling gives equal candidates to the lower index.
+ *   trace[j] is the sum of cur after the first j picks and falls strictly up to count; no plane is picked twice (a chosen plane has no
+ *   strictly lower key: its gain is 0); the first K' picks of a longer run are the run with K'; the first pick is the best single plane.
+ *   Beyond the first pick this is a greedy heuristic on an objective that is not monotone: a pick can raise some rows' errors, and a
+ *   plane that would lower the sum only together with another one is never found.
+ *   chosen (K) int32, trace (K + 1) uint64 (8-byte aligned), best (O), cur (O) uint16, count (1) int32: device, all written.
+ *   workspace: gpp_plane_select_polled_workspace_bytes() bytes, 16-byte aligned (gain (M) int64, then the done flag).
+ *   2 K + 1 plain launches in stream order, as gpp_plane_select: the gain launch reads 8 planes of a row from each table with two 16-byte
+ *   loads, keeps signed 32-bit partial sums over a slab of 256 rows (at most 256 x 65535 < 2^24 in magnitude), adds them in LDS and then
+ *   into the 64-bit gains with integer atomics (two's-complement addition does not depend on the order); the single-workgroup launch
+ *   takes the lexicographic (signed gain, -index) maximum, updates best and cur along the column and clears the gains.  Pad columns are
+ *   read and never counted.  Error codes as gpp_plane_select (keys and errs both checked); nothing is launched on a bad argument.
+ * ---------------------------------------------------------------------------------------- */
+int gpp_pose_costs_u16(const float* boxes, const float* dims, const int32_t* orient, const float* P_inv, const float* want,
+                       const float* planes, int B, int D, int M, float thr, const int32_t* row_index, int O, uint16_t* keys,
+                       uint16_t* errs, int64_t pitch, int64_t row_offset, void* workspace, size_t workspace_bytes, void* stream);
+int gpp_plane_select_polled_workspace_bytes(int M, size_t* bytes);
+int gpp_plane_select_polled(const uint16_t* keys, const uint16_t* errs, int O, int M, int64_t pitch, int K, int32_t* chosen,
+                            uint64_t* trace, uint16_t* best, uint16_t* cur, int32_t* count, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Per-frame road-plane fit (csrc/road_fit.hip; DESIGN.md section 4.22 is the specification, utils/road_fit.py the host side and the NumPy
  * form): from a batch of LiDAR scans one plane per frame, in rectified camera coordinates -- the pool that gpp_poll_costs_u16 /
  * gpp_plane_select distil.  Exact integers: points are quantised once at GPP_ROAD_Q quanta per metre and every later quantity is an integer
