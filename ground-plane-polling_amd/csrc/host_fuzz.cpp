@@ -230,6 +230,29 @@ int main(int argc, char** argv)
                 note(gpp_road_moments(nullptr, nullptr, nullptr, nullptr, r.a, nullptr, (int)r.b, (int)r.c, (int)r.a, (int)r.b, 1.0, nullptr, nullptr));
                 note(gpp_road_moments(i32, i32, i32, u32, r.c, i32, F, total, mp, (int)(r.b % 5000), (r.a & 4) ? nan : 655.36,
                                       (int64_t*)((uintptr_t)r.d[0].out | ((r.a & 16) ? 4 : 0)), nullptr));
+                // the peel's host half: the workspace size over the whole range and beyond it, null pointers, F = 0, q_out == q_in and ranges
+                // that overlap by one row, a workspace one byte short, misaligned buffers, a NaN threshold
+                size_t peel = 0;
+                note(gpp_road_peel_workspace_bytes((int)r.a, (int)r.b, (r.c & 1) ? nullptr : &peel));
+                note(gpp_road_peel_workspace_bytes(F, mp, &peel));
+                if (gpp_road_peel_workspace_bytes(F, mp, &peel) == 0 && peel < sizeof(int32_t) * (size_t)F * (size_t)((mp + 2047) / 2048)) {
+                    fprintf(stderr, "a peel workspace smaller than its block counts\n"); return 3;
+                }
+                note(gpp_road_peel_i32(nullptr, nullptr, nullptr, nullptr, r.a, nullptr, (int)r.b, (int)r.c, (int)r.a, (int)r.b, 1.0, nullptr, nullptr,
+                                       nullptr, 0, nullptr));
+                note(gpp_road_peel_i32(i32, i32, i32, u32, r.c, i32, 0, total, 0, (int)(r.b % 5000), 1.0, (int32_t*)r.d[0].out, (int32_t*)r.d[0].out,
+                                       r.d[0].out, 0, nullptr));
+                int32_t* const qo = (int32_t*)((uintptr_t)r.d[0].out | ((r.a & 32) ? 2 : 0));
+                note(gpp_road_peel_i32(i32, i32, i32, u32, r.c, i32, F, total, mp, (int)(r.b % 5000), (r.a & 4) ? nan : 655.36, qo, (int32_t*)r.d[0].out,
+                                       (r.a & 64) ? nullptr : (void*)((uintptr_t)r.d[0].partial | ((r.a & 128) ? 1 : 0)),
+                                       (r.a & 256) ? (peel ? peel - 1 : 0) : (size_t)r.d[0].partial_bytes, nullptr));
+                if (F > 0 && total > 0 && mp <= total && i32 && (uintptr_t)i32 < ((uintptr_t)1 << 62)) {      // (no wrap-around of the fuzzed address)
+                    const int32_t* const over = (r.a & 512) ? i32 : (const int32_t*)((uintptr_t)i32 + 12 * ((size_t)total - 1));
+                    if (gpp_road_peel_i32(i32, i32, i32, u32, r.c, i32, F, total, mp, 8, 1.0, (int32_t*)(uintptr_t)over, (int32_t*)r.d[0].out,
+                                          r.d[0].out, (size_t)-1, nullptr) != GPP_ERR_BAD_ARG) {
+                        fprintf(stderr, "overlapping peel buffers were accepted\n"); return 3;
+                    }
+                }
             }
             break;
         }

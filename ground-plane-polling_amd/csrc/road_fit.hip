@@ -9,6 +9,9 @@
 //                         read as a broadcast, up to 64 workgroups along a frame's points, one atomicAdd of the lane's count per workgroup
 //   gpp_road_winner       the largest count, the first hypothesis among equals: the lexicographic reduction of gpp_plane_select's pick
 //   gpp_road_moments      ten integer sums over the winner's inliers, 64-bit integer atomics
+//   gpp_road_peel_i32     section 4.24, several planes per frame: the kept points that are NOT inliers of the winner, in their order, into a
+//                         second buffer -- a stable compaction over many workgroups in three launches (count per block of 2048 points, an
+//                         exclusive scan of a frame's block counts, scatter); the next round's score / winner / moments run on the result
 //
 // Plain launches in stream order; no cooperative launch, no persistent grid, no spin.  The host side -- the 2 x 2 solve on the ten sums -- is
 // utils/road_fit.py.  Nothing of the reference corresponds to this file: the reference ships its plane databases and no way to make one.
@@ -25,6 +28,7 @@ constexpr int kThreads = 256;                 // every kernel here: four wavefro
 constexpr int kSlab = GPP_ROAD_SLAB;          // points per workgroup of the score launch (12 KiB of LDS as float64)
 constexpr int kMomentSlab = 2048;             // points per workgroup of the moments launch: 8 per thread
 constexpr int kScoreSlabGroups = 64;         // workgroups along a frame's points in the score launch, at most: each walks every 64th slab
+constexpr int kPeelBlock = GPP_ROAD_PEEL_BLOCK; // points per workgroup of the peel's count and scatter launches: 8 chunks of 256
 constexpr int kMaxFrames = 65535;             // frames are the grid's z (score) or y (moments) dimension
 
 __device__ __forceinline__ uint32_t mix(uint32_t u)
@@ -245,6 +249,146 @@ __global__ __launch_bounds__(kThreads) void road_moments_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- peel (section 4.24)
+// What the three peel launches know of a frame: its segment, its kept points and the winner's plane, recomputed from the three draws as
+// gpp_road_moments does (only nn > 0 is asked).  live: the frame has a winner in [0, H); a frame without one is finished (no survivor).
+// A winner whose plane has nn = 0 (hand-set only: such a hypothesis is never scored) has no inliers, as in gpp_road_moments.
+struct PeelFrame { const int32_t* qf; int64_t base; int m; bool live; double nx, ny, nz, nd0, t2; };
+
+__device__ __forceinline__ PeelFrame peel_frame(const int32_t* __restrict__ q, const int32_t* __restrict__ offsets,
+                                                const int32_t* __restrict__ kept, const uint32_t* __restrict__ frame_id, uint32_t seed,
+                                                const int32_t* __restrict__ winner, int f, int H, int total, int max_points, double tq2)
+{
+    PeelFrame R;
+    int n;
+    frame_segment(offsets, f, total, max_points, R.base, n);
+    R.m = frame_kept(kept, f, n);
+    R.qf = q + R.base * 3;
+    const int w = winner[f];
+    R.live = w >= 0 && w < H;
+    R.nx = R.ny = R.nz = R.nd0 = 0.0;
+    R.t2 = -1.0;                                                   // (no inlier: dot dot >= 0 > -1)
+    if (R.live && R.m > 0) {
+        const Plane P = road_plane(R.qf, R.m, mix(seed + frame_id[f]), (uint32_t)w, 0.0, 0.0, __builtin_huge_val());
+        if (P.valid) { R.nx = P.nx; R.ny = P.ny; R.nz = P.nz; R.nd0 = -P.d0; R.t2 = tq2 * P.nn; }
+    }
+    return R;
+}
+
+// point i of the frame survives the round: it is no inlier of the winner (the test of gpp_road_moments, operation for operation)
+__device__ __forceinline__ bool peel_survives(const PeelFrame& R, int i, int& xi, int& yi, int& zi)
+{
+    const int32_t* s = R.qf + (int64_t)i * 3;
+    xi = s[0]; yi = s[1]; zi = s[2];
+    const double dot = fma(R.nx, (double)xi, fma(R.ny, (double)yi, fma(R.nz, (double)zi, R.nd0)));
+    return !(dot * dot <= R.t2);
+}
+
+// (a) block_count[f][b]: the survivors among the frame's kept points [b 2048, b 2048 + 2048); every workgroup writes its word
+__global__ __launch_bounds__(kThreads) void road_peel_count_kernel(
+    const int32_t* __restrict__ q, const int32_t* __restrict__ offsets, const int32_t* __restrict__ kept,
+    const uint32_t* __restrict__ frame_id, uint32_t seed, const int32_t* __restrict__ winner, int H, int total, int max_points,
+    double tq2, int32_t* __restrict__ block_count)
+{
+    __shared__ int s_wave[kThreads / 64];
+    const int f = blockIdx.y, tid = threadIdx.x;
+    int32_t* out = block_count + (int64_t)f * gridDim.x + blockIdx.x;
+    const PeelFrame R = peel_frame(q, offsets, kept, frame_id, seed, winner, f, H, total, max_points, tq2);
+    const int p0 = (int)blockIdx.x * kPeelBlock;
+    if (!R.live || p0 >= R.m) {                                    // (uniform)
+        if (tid == 0) *out = 0;
+        return;
+    }
+    const int p1 = min(R.m, p0 + kPeelBlock);
+    int c = 0;
+    for (int i = p0 + tid; i < p1; i += kThreads) {
+        int xi, yi, zi;
+        c += peel_survives(R, i, xi, yi, zi) ? 1 : 0;
+    }
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) c += __shfl_xor(c, s, 64);
+    if ((tid & 63) == 0) s_wave[tid >> 6] = c;
+    __syncthreads();
+    if (tid == 0) {
+        int v = 0;
+#pragma unroll
+        for (int w = 0; w < kThreads / 64; ++w) v += s_wave[w];
+        *out = v;
+    }
+}
+
+// (b) one workgroup per frame: block_count[f][0 .. blocks) becomes its own exclusive scan, kept_out[f] the total.  Up to 512 blocks: the
+// workgroup walks them in chunks of 256 with a running carry
+__global__ __launch_bounds__(kThreads) void road_peel_scan_kernel(int32_t* __restrict__ block_count, int blocks, int32_t* __restrict__ kept_out)
+{
+    __shared__ int s_wave[kThreads / 64];
+    const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int32_t* row = block_count + (int64_t)f * blocks;
+    int carry = 0;                                                 // (uniform)
+    for (int at = 0; at < blocks; at += kThreads) {
+        const int b = at + tid;
+        const int v = b < blocks ? row[b] : 0;
+        int incl = v;
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) {
+            const int o = __shfl_up(incl, s, 64);
+            if (lane >= s) incl += o;
+        }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        int prefix = carry, sum = 0;
+#pragma unroll
+        for (int w = 0; w < kThreads / 64; ++w) {
+            const int c = s_wave[w];
+            if (w < wave) prefix += c;
+            sum += c;
+        }
+        if (b < blocks) row[b] = prefix + incl - v;
+        carry += sum;
+        __syncthreads();                                           // (s_wave is rewritten by the next chunk)
+    }
+    if (tid == 0) kept_out[f] = carry;
+}
+
+// (c) the grid of (a): the mask again, every survivor to q_out at the block's scanned start + its rank inside the block -- chunks of 256
+// points, a ballot per wavefront and an LDS prefix across the four, as in road_points_kernel: the order is kept
+__global__ __launch_bounds__(kThreads) void road_peel_scatter_kernel(
+    const int32_t* __restrict__ q, const int32_t* __restrict__ offsets, const int32_t* __restrict__ kept,
+    const uint32_t* __restrict__ frame_id, uint32_t seed, const int32_t* __restrict__ winner, int H, int total, int max_points,
+    double tq2, const int32_t* __restrict__ block_start, int32_t* __restrict__ q_out)
+{
+    __shared__ int s_wave[kThreads / 64];
+    const int f = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const PeelFrame R = peel_frame(q, offsets, kept, frame_id, seed, winner, f, H, total, max_points, tq2);
+    const int p0 = (int)blockIdx.x * kPeelBlock;
+    if (!R.live || p0 >= R.m) return;                              // (uniform)
+    const int p1 = min(R.m, p0 + kPeelBlock);
+    int32_t* out = q_out + R.base * 3;
+    int written = block_start[(int64_t)f * gridDim.x + blockIdx.x];      // (uniform) survivors of the frame before this block: <= p0
+    for (int at = p0; at < p1; at += kThreads) {
+        const int i = at + tid;
+        int xi = 0, yi = 0, zi = 0;
+        const bool keep = i < p1 && peel_survives(R, i, xi, yi, zi);
+        const unsigned long long mask = __ballot(keep);
+        const int before = __popcll(mask & ((1ull << lane) - 1ull));
+        if (lane == 0) s_wave[wave] = __popcll(mask);
+        __syncthreads();
+        int prefix = written, sum = 0;
+#pragma unroll
+        for (int w = 0; w < kThreads / 64; ++w) {
+            const int c = s_wave[w];
+            if (w < wave) prefix += c;
+            sum += c;
+        }
+        if (keep) {
+            int32_t* o = out + (int64_t)(prefix + before) * 3;      // prefix + before <= i < m: inside the frame's own segment
+            o[0] = xi; o[1] = yi; o[2] = zi;
+        }
+        written += sum;
+        __syncthreads();                                           // (s_wave is rewritten by the next chunk)
+    }
+}
+
 bool ragged_ok(int F, int total, int max_points)
 {
     return F >= 0 && F <= kMaxFrames && total >= 0 && total <= GPP_ROAD_MAX_TOTAL && max_points >= 0 && max_points <= GPP_ROAD_MAX_POINTS &&
@@ -311,5 +455,42 @@ extern "C" int gpp_road_moments(const int32_t* q, const int32_t* offsets, const 
     road_moments_kernel<<<dim3(slabs, (unsigned)F), dim3(kThreads), 0, st>>>(
         q, offsets, kept, frame_id, seed, winner, H, total, max_points, tq2, (unsigned long long*)sums);
     e = hipGetLastError();
+    return e == hipSuccess ? GPP_OK : (int)e;
+}
+
+extern "C" int gpp_road_peel_workspace_bytes(int F, int max_points, size_t* bytes)
+{
+    if (!bytes || F < 0 || F > kMaxFrames || max_points < 0 || max_points > GPP_ROAD_MAX_POINTS) return GPP_ERR_BAD_ARG;
+    const size_t blocks = ((size_t)max_points + kPeelBlock - 1) / kPeelBlock;
+    *bytes = sizeof(int32_t) * (size_t)F * blocks + 16;            // a frame's block counts, then their scan in place; never zero
+    return GPP_OK;
+}
+
+extern "C" int gpp_road_peel_i32(const int32_t* q_in, const int32_t* offsets, const int32_t* kept_in, const uint32_t* frame_id, uint32_t seed,
+                                 const int32_t* winner, int F, int total, int max_points, int H, double tq2,
+                                 int32_t* q_out, int32_t* kept_out, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (!ragged_ok(F, total, max_points) || H < 0 || H > GPP_ROAD_MAX_HYPOTHESES || !(tq2 >= 0.0)) return GPP_ERR_BAD_ARG;
+    if (F == 0) return GPP_OK;
+    if (!offsets || !kept_in || !frame_id || !winner || !kept_out || !workspace || (total > 0 && (!q_in || !q_out))) return GPP_ERR_BAD_ARG;
+    if (total > 0) {                                               // the two point buffers are distinct: a survivor may land on a row not yet read
+        const uintptr_t a = (uintptr_t)q_in, b = (uintptr_t)q_out, span = sizeof(int32_t) * 3 * (uintptr_t)total;
+        if (a < b ? b - a < span : a - b < span) return GPP_ERR_BAD_ARG;
+    }
+    size_t need = 0;
+    gpp_road_peel_workspace_bytes(F, max_points, &need);
+    if (workspace_bytes < need) return GPP_ERR_WORKSPACE;
+    if (((uintptr_t)q_in & 3) || ((uintptr_t)q_out & 3) || ((uintptr_t)kept_out & 3) || ((uintptr_t)workspace & 3)) return GPP_ERR_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned blocks = (unsigned)((max_points + kPeelBlock - 1) / kPeelBlock);
+    int32_t* block_count = (int32_t*)workspace;
+    if (blocks > 0)
+        road_peel_count_kernel<<<dim3(blocks, (unsigned)F), dim3(kThreads), 0, st>>>(
+            q_in, offsets, kept_in, frame_id, seed, winner, H, total, max_points, tq2, block_count);
+    road_peel_scan_kernel<<<dim3((unsigned)F), dim3(kThreads), 0, st>>>(block_count, (int)blocks, kept_out);
+    if (blocks > 0)
+        road_peel_scatter_kernel<<<dim3(blocks, (unsigned)F), dim3(kThreads), 0, st>>>(
+            q_in, offsets, kept_in, frame_id, seed, winner, H, total, max_points, tq2, block_count, q_out);
+    hipError_t e = hipGetLastError();
     return e == hipSuccess ? GPP_OK : (int)e;
 }

@@ -198,6 +198,12 @@ def _declare(lib):
         lib.gpp_road_winner.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
         lib.gpp_road_moments.restype = c_int
         lib.gpp_road_moments.argtypes = [c_void_p] * 4 + [c_uint32, c_void_p] + [c_int] * 4 + [c_double, c_void_p, c_void_p]
+    # several planes per frame (absent from a build older than that section)
+    if hasattr(lib, 'gpp_road_peel_i32'):
+        lib.gpp_road_peel_workspace_bytes.restype = c_int
+        lib.gpp_road_peel_workspace_bytes.argtypes = [c_int, c_int, ctypes.POINTER(c_size_t)]
+        lib.gpp_road_peel_i32.restype = c_int
+        lib.gpp_road_peel_i32.argtypes = [c_void_p] * 4 + [c_uint32, c_void_p] + [c_int] * 4 + [c_double] + [c_void_p] * 3 + [c_size_t, c_void_p]
     if hasattr(lib, 'gpp_detect_pixel_lists'):
         lib.gpp_detect_pixel_lists.restype = c_int
         lib.gpp_detect_pixel_lists.argtypes = [ctypes.POINTER(PixelListDesc), c_void_p]
@@ -684,6 +690,27 @@ def road_moments(q, offsets, kept, frame_id, seed, winner, max_points, H, tq2):
     check(lib().gpp_road_moments(ptr(q), ptr(offsets), ptr(kept), ptr(frame_id), int(seed) & 0xffffffff, ptr(winner), F, total, int(max_points),
                                  int(H), float(tq2), ptr(sums), stream_ptr()), 'gpp_road_moments')
     return sums
+
+
+def road_peel(q, offsets, kept, frame_id, seed, winner, max_points, H, tq2):
+    """ gpp_road_peel_i32 on the current stream: the kept points of every frame that are no inliers of `winner`'s plane under `seed`, in
+    their order -> (q_out (total, 3) int32, a frame's survivors at the head of its own segment and zeros behind; kept_out (F,) int32) on
+    the device, a frame without a winner: kept_out 0.  q is not changed.  No synchronisation """
+    import torch
+    if not hasattr(lib(), 'gpp_road_peel_i32'):
+        raise GppError('gpp_road_peel_i32: this build of the library has no peel stage (several planes per frame)')
+    total, F = int(q.shape[0]), int(kept.numel())
+    _road_check('gpp_road_peel_i32', ((q, torch.int32, (total, 3)), (offsets, torch.int32, (F + 1,)), (kept, torch.int32, (F,)),
+                                      (frame_id, torch.int32, (F,)), (winner, torch.int32, (F,))), q.device)
+    q_out = torch.zeros((total, 3), dtype=torch.int32, device=q.device)
+    kept_out = torch.zeros((F,), dtype=torch.int32, device=q.device)
+    need = c_size_t(0)
+    check(lib().gpp_road_peel_workspace_bytes(F, int(max_points), ctypes.byref(need)), 'gpp_road_peel_workspace_bytes')
+    workspace = torch.empty((int(need.value),), dtype=torch.uint8, device=q.device)
+    check(lib().gpp_road_peel_i32(ptr(q), ptr(offsets), ptr(kept), ptr(frame_id), int(seed) & 0xffffffff, ptr(winner), F, total, int(max_points),
+                                  int(H), float(tq2), ptr(q_out), ptr(kept_out), ptr(workspace), workspace.numel(), stream_ptr()),
+          'gpp_road_peel_i32')
+    return q_out, kept_out
 
 
 def channel_absmax(buf, M, C, pitch, c_off, layout, out, stream=None):

@@ -8,6 +8,8 @@ another dataset to "replace road_planes_database.mat with relevant files of your
     fit_np         the same in NumPy: equal to fit_device entry for entry, planes bit for bit
     solve_moments  ten integer sums -> the plane (host only; both forms use it)
     fit_pool       velodyne + calib directories -> the valid planes in file order, with the per-frame record
+    fit_rounds_np, fit_rounds_device   several planes per frame: after a round's winner its inliers are taken out
+                   of the frame's point list (peel_np / gpp_road_peel_i32) and the frame is scored again under the round's seed
     read_plane_files   the planes/NNNNNN.txt files that KITTI-derived sets distribute, as a pool
 
 The fit is done in exact integers: a point is quantised once, at Q = 256 quanta per metre, and every later quantity is an integer below
@@ -28,6 +30,8 @@ MAX_FRAMES = 65535                                          # frames of one devi
 SUM_NAMES = ('N', 'Sx', 'Sy', 'Sz', 'Sxx', 'Sxz', 'Szz', 'Sxy', 'Szy', 'Syy')
 DEFAULTS = dict(hypotheses=1024, threshold=0.10, region=(20.0, 8.0, 50.0), height=(1.0, 2.5), max_tilt=15.0, min_inliers=100, seed=0)
 CHUNK_BYTES = 1 << 30                                       # fit_pool: device bytes of one chunk (points, q, counts)
+ROUND_SEED_STEP = 0x9e3779b9                                # section 4.24: round r draws with seed + r * ROUND_SEED_STEP (mod 2^32)
+MIN_SHARE = 0.10                                            # section 4.24: a later round's plane needs this share of the frame's kept points
 
 
 # ---------------------------------------------------------------------------------------------------- options
@@ -260,6 +264,142 @@ def fit_device(points_list, T_list, frame_ids, **options):
     return _assemble(s['kept'], s['winner'], s['inliers'], s['sums'])
 
 
+# ---------------------------------------------------------------------------------------------------- several planes per frame (4.24)
+def round_seed(seed, r):
+    """ the seed of round r: (seed + r * ROUND_SEED_STEP) mod 2^32 """
+    return (int(seed) + int(r) * ROUND_SEED_STEP) & 0xffffffff
+
+
+def peel_np(q, frame_id, winner, o):
+    """ the peel of one frame: the points of q (m, 3) int32 that are NOT inliers of hypothesis `winner` under o['seed'], in their order.
+    No winner (< 0 or >= H): the frame is finished, (0, 3).  The inlier rule is gpp_road_moments': a winner whose plane has nn = 0, or a
+    frame of fewer than three points (hand-set winners only), has no inliers and every point stays. """
+    q = np.asarray(q, np.int32).reshape(-1, 3)
+    if winner < 0 or winner >= o['H']:
+        return q[:0].copy()
+    n, d0, nn, _ = planes_np(q, frame_id, o)
+    if not nn[winner] > 0.0:
+        return q.copy()
+    inl = _inlier_mask(q.astype(np.int64), n[winner:winner + 1], d0[winner:winner + 1], o['tq2'] * nn[winner:winner + 1])[:, 0]
+    return np.ascontiguousarray(q[~inl])
+
+
+def _check_rounds(planes_per_frame, min_share):
+    P = int(planes_per_frame)
+    if P != planes_per_frame or P < 1 or P > 16:
+        raise ValueError('planes_per_frame {}: needs a whole number 1 .. 16'.format(planes_per_frame))
+    share = float(min_share)
+    if not 0.0 <= share <= 1.0:
+        raise ValueError('min_share {}: needs 0 .. 1'.format(min_share))
+    return P, share
+
+
+def _assemble_rounds(kept, winner, inliers, sums, min_share):
+    """ the host's step of section 4.24 on (F, P) stages: round r of a frame is valid iff every earlier round is, it has a winner,
+    solve_moments gives a plane and, for r >= 1, inliers_r >= ceil(min_share * kept_0), exactly (Fraction of the float64 min_share) """
+    kept, winner, inliers = [np.asarray(v, np.int32) for v in (kept, winner, inliers)]
+    F, P = kept.shape
+    sums = np.asarray(sums, np.int64).reshape(F, P, 10)
+    planes = np.full((F, P, 4), np.nan, np.float64)
+    rms = np.full((F, P), np.nan, np.float64)
+    valid = np.zeros((F, P), bool)
+    share = Fraction(float(min_share))
+    for f in range(F):
+        need = math.ceil(share * int(kept[f, 0]))
+        for r in range(P):
+            if winner[f, r] < 0 or (r >= 1 and int(inliers[f, r]) < need):
+                break
+            plane, v = solve_moments(sums[f, r])
+            if plane is None:
+                break
+            planes[f, r], rms[f, r], valid[f, r] = plane, v, True
+    return {'planes': planes, 'valid': valid, 'kept': kept, 'winner': winner, 'inliers': inliers, 'sums': sums, 'rms': rms}
+
+
+def np_round_stages(points_list, T_list, frame_ids, planes_per_frame, **options):
+    """ every stage of every round in NumPy: a list of P dicts q (list of (m, 3) int32 per frame), kept, count (F, H), winner, inliers,
+    sums (F, 10).  What fit_rounds_np is made of """
+    o = resolve_options(**options)
+    P, _ = _check_rounds(planes_per_frame, 0.0)
+    pts, Ts, ids = _check_frames(points_list, T_list, frame_ids)
+    q = [quantise_np(p, T, o['region_q']) for p, T in zip(pts, Ts)]
+    rounds = []
+    for r in range(P):
+        orr = dict(o, seed=round_seed(o['seed'], r))
+        count = [score_np(v, fid, orr) for v, fid in zip(q, ids)]
+        picks = [winner_np(c, o['min_inliers']) for c in count]
+        sums = [moments_np(v, fid, w, orr) for v, fid, (w, _) in zip(q, ids, picks)]
+        rounds.append({'q': q, 'kept': np.asarray([v.shape[0] for v in q], np.int32), 'count': np.asarray(count, np.int32).reshape(len(q), o['H']),
+                       'winner': np.asarray([w for w, _ in picks], np.int32), 'inliers': np.asarray([c for _, c in picks], np.int32),
+                       'sums': np.asarray(sums, np.int64).reshape(len(q), 10)})
+        if r + 1 < P:
+            q = [peel_np(v, fid, w, orr) for v, fid, (w, _) in zip(q, ids, picks)]
+    return rounds
+
+
+def _stack_rounds(rounds, min_share):
+    stack = lambda key: np.stack([r[key] for r in rounds], axis=1)  # noqa: E731
+    return _assemble_rounds(stack('kept'), stack('winner'), stack('inliers'), stack('sums'), min_share)
+
+
+def fit_rounds_np(points_list, T_list, frame_ids, planes_per_frame, min_share=MIN_SHARE, **options):
+    """ up to planes_per_frame planes per frame in NumPy (section 4.24): fit_np's dict with a round axis -- planes (F, P, 4) float64 (NaN
+    where invalid), valid (F, P) bool, kept, winner, inliers (F, P) int32, sums (F, P, 10) int64, rms (F, P) float64.  Round 0 is fit_np.
+    Options: DEFAULTS. """
+    P, share = _check_rounds(planes_per_frame, min_share)
+    return _stack_rounds(np_round_stages(points_list, T_list, frame_ids, P, **options), share)
+
+
+def _device_rounds(points_list, T_list, frame_ids, P, everything, **options):
+    import torch
+    from ..backend import hip
+    dev = hip.require_device()
+    o = resolve_options(**options)
+    pts, Ts, ids = _check_frames(points_list, T_list, frame_ids)
+    F = len(pts)
+    if F > MAX_FRAMES:
+        raise ValueError('{} frames in one call: the device form takes up to {} (fit_pool chunks a dataset)'.format(F, MAX_FRAMES))
+    sizes = [p.shape[0] for p in pts]
+    offsets = np.zeros(F + 1, np.int64)
+    offsets[1:] = np.cumsum(sizes)
+    total, max_points = int(offsets[-1]), max(sizes + [0])
+    if total > (1 << 30):
+        raise ValueError('{} points in one call: the device form takes up to 2^30'.format(total))
+    up = lambda a: torch.as_tensor(a).to(dev)  # noqa: E731
+    points_d = up(np.concatenate(pts + [np.zeros((0, 4), np.float32)]))
+    offsets_d = up(offsets.astype(np.int32))
+    T_d = up(np.asarray(Ts, np.float64).reshape(F, 12))
+    ids_d = up(np.asarray(ids, np.uint32).view(np.int32))
+    q, kept = hip.road_points(points_d, offsets_d, T_d, max_points, o['region_q'])
+    held = []
+    for r in range(P):
+        seed = round_seed(o['seed'], r)
+        count = hip.road_score(q, offsets_d, kept, ids_d, seed, max_points, o['H'], o['c2'], o['hlo2'], o['hhi2'], o['tq2'])
+        winner, inliers = hip.road_winner(count, o['min_inliers'])
+        sums = hip.road_moments(q, offsets_d, kept, ids_d, seed, winner, max_points, o['H'], o['tq2'])
+        held.append({'q': q, 'kept': kept, 'count': count, 'winner': winner, 'inliers': inliers, 'sums': sums} if everything else
+                    {'kept': kept, 'winner': winner, 'inliers': inliers, 'sums': sums})
+        if r + 1 < P:                                         # (without `everything` the buffer of two rounds ago is free again: two in use)
+            q, kept = hip.road_peel(q, offsets_d, kept, ids_d, seed, winner, max_points, o['H'], o['tq2'])
+    torch.cuda.synchronize(dev)
+    return [dict({k: v.cpu().numpy() for k, v in h.items()}, offsets=offsets.astype(np.int32)) for h in held]
+
+
+def device_round_stages(points_list, T_list, frame_ids, planes_per_frame, **options):
+    """ device_stages per round: a list of P dicts q (total, 3) int32 (a frame's points of that round at the head of its own segment,
+    zeros behind), offsets (F + 1,), kept (F,), count (F, H), winner, inliers (F,) int32, sums (F, 10) int64 -- gpp_road_points_i32 once,
+    then per round score, winner and moments under the round's seed, and gpp_road_peel_i32 between two rounds.  What fit_rounds_device is
+    made of; the tests compare every stage.  Raises GppError without a GPU. """
+    P, _ = _check_rounds(planes_per_frame, 0.0)
+    return _device_rounds(points_list, T_list, frame_ids, P, True, **options)
+
+
+def fit_rounds_device(points_list, T_list, frame_ids, planes_per_frame, min_share=MIN_SHARE, **options):
+    """ fit_rounds_np's dict from the device: equal to it entry for entry, planes bit for bit.  Raises GppError without a GPU. """
+    P, share = _check_rounds(planes_per_frame, min_share)
+    return _stack_rounds(_device_rounds(points_list, T_list, frame_ids, P, False, **options), share)
+
+
 # ---------------------------------------------------------------------------------------------------- files
 def read_velodyne(path):
     """ a KITTI velodyne .bin: (n, 4) float32 x y z reflectance """
@@ -309,11 +449,12 @@ def read_plane_files(directory):
     return np.asarray(rows, np.float64).reshape(-1, 4), files
 
 
-def _chunks(sizes, H, chunk_frames, budget):
-    """ consecutive index ranges: at most chunk_frames frames and about `budget` device bytes (28 per point, 4 H per frame) each """
+def _chunks(sizes, H, chunk_frames, budget, point_bytes=28):
+    """ consecutive index ranges: at most chunk_frames frames and about `budget` device bytes (28 per point, 4 H per frame) each; with
+    several planes per frame the peel's second point buffer makes it 40 per point """
     out, at, n, used = [], 0, 0, 0
     for i, s in enumerate(sizes):
-        need = 28 * s + 4 * H + 256
+        need = point_bytes * s + 4 * H + 256
         if n and (n >= chunk_frames or used + need > budget):
             out.append((at, i))
             at, n, used = i, 0, 0
@@ -323,24 +464,36 @@ def _chunks(sizes, H, chunk_frames, budget):
     return out
 
 
-def fit_pool(velodyne_dir, calib_dir, device=True, chunk_frames=64, chunk_bytes=CHUNK_BYTES, **options):
+def fit_pool(velodyne_dir, calib_dir, device=True, chunk_frames=64, chunk_bytes=CHUNK_BYTES, planes_per_frame=1, min_share=MIN_SHARE,
+             **options):
     """ the pool of a dataset: the .bin scans of `velodyne_dir` sorted by name (frame_id = the position in that list), the calibration files
     of the same stems in `calib_dir` -> dict: planes (V, 4) float64, the valid frames' planes in file order; files, their names; frames,
     every scan's name; record, fit_np's dict over all frames.  Frames are read and fitted in chunks of up to chunk_frames frames and about
-    chunk_bytes device bytes; a frame's result does not depend on the chunking.  device=False: fit_np instead of fit_device. """
+    chunk_bytes device bytes; a frame's result does not depend on the chunking.  device=False: fit_np instead of fit_device.
+    planes_per_frame > 1 (section 4.24): fit_rounds_device / fit_rounds_np -- planes (V, 4), the valid planes in frame order and within a
+    frame in round order; files, the scan's name once per plane; rounds (V,) int32, each plane's round; record, the rounds dict. """
     files = sorted(f for f in os.listdir(velodyne_dir) if f.endswith('.bin'))
     if not files:
         raise ValueError('{}: no .bin scans'.format(velodyne_dir))
     resolve_options(**options)
+    P, share = _check_rounds(planes_per_frame, min_share)
     sizes = [os.path.getsize(os.path.join(velodyne_dir, f)) // 16 for f in files]
     H = int(dict(DEFAULTS, **options)['hypotheses'])
-    fit = fit_device if device else fit_np
+    if P == 1:
+        fit = fit_device if device else fit_np
+    else:
+        one = fit_rounds_device if device else fit_rounds_np
+        fit = lambda pts, Ts, ids, **kw: one(pts, Ts, ids, P, share, **kw)  # noqa: E731
     parts = []
-    for a, b in _chunks(sizes, H, max(1, min(int(chunk_frames), MAX_FRAMES)), int(chunk_bytes)):
+    for a, b in _chunks(sizes, H, max(1, min(int(chunk_frames), MAX_FRAMES)), int(chunk_bytes), 28 if P == 1 else 40):
         pts = [read_velodyne(os.path.join(velodyne_dir, f)) for f in files[a:b]]
         Ts = [read_velo_calibration(os.path.join(calib_dir, os.path.splitext(f)[0] + '.txt')) for f in files[a:b]]
         parts.append(fit(pts, Ts, list(range(a, b)), **options))
     record = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
     valid = record['valid']
-    return {'planes': np.ascontiguousarray(record['planes'][valid]), 'files': [f for f, v in zip(files, valid) if v], 'frames': files,
-            'record': record}
+    if P == 1:
+        return {'planes': np.ascontiguousarray(record['planes'][valid]), 'files': [f for f, v in zip(files, valid) if v], 'frames': files,
+                'record': record}
+    at, rounds = np.nonzero(valid)                            # row-major: frame order, within a frame round order
+    return {'planes': np.ascontiguousarray(record['planes'][valid]), 'files': [files[f] for f in at], 'rounds': rounds.astype(np.int32),
+            'frames': files, 'record': record}

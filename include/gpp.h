@@ -843,6 +843,7 @@ int gpp_plane_select_polled(const uint16_t* keys, const uint16_t* errs, int O, i
  * gpp_plane_select distil.  Exact integers: points are quantised once at GPP_ROAD_Q quanta per metre and every later quantity is an integer
  * below 2^53 or one rounded float64 operation of such integers, so every output equals the NumPy form and does not depend on the order of
  * lanes or atomics.  Four plain launches in stream order (points, score, winner, moments); no workspace; the 2 x 2 solve is the host's.
+ * A second, third ... plane per frame: gpp_road_peel_i32 below takes the winner's inliers out and the three launches run again.
  *
  * The ragged batch: frame f owns the points [offsets[f], offsets[f + 1]) of `points` and the same rows of `q`.  offsets (F + 1) int32 is
  * DEVICE memory; the host passes what it knows of it, total = offsets[F] and max_points >= every frame's size.  A frame whose offsets
@@ -878,6 +879,21 @@ int gpp_plane_select_polled(const uint16_t* keys, const uint16_t* errs, int O, i
  *   gpp_road_score) of the winner's plane, recomputed from its three draws; zero for a frame without a winner.  ceil(max_points / 2048) x F
  *   workgroups, 64-bit integer atomics.  A frame has at most 2^20 points: every sum < 2^50.
  *
+ * gpp_road_peel_i32 (several planes per frame): q_out (total, 3) int32, the layout of q_in: the kept points of
+ *   frame f that are NOT inliers of `winner[f]`'s plane, IN THEIR ORDER (a stable compaction), at rows offsets[f] ... offsets[f] +
+ *   kept_out[f]; the rest of the frame's rows are left untouched.  kept_out (F) int32.  The inlier test is gpp_road_moments', operation for
+ *   operation, on the plane recomputed from the winner's three draws under `seed`: kept_in[f] - kept_out[f] equals that launch's N for
+ *   every frame with a winner.  A frame without a winner (winner < 0 or >= H) is finished: kept_out = 0, nothing written.  A winner whose
+ *   plane has nn = 0 or whose frame has fewer than three points (hand-set only: the winner launch never names one) has no inliers, here
+ *   as in gpp_road_moments: every kept point survives.  The next round's score / winner / moments run unchanged on (q_out, kept_out) with
+ *   the round's seed, seed_r = seed + r * 0x9e3779b9 (mod 2^32), made by the host.
+ *   q_out and q_in are distinct buffers whose (total, 3) ranges do not overlap (GPP_ERR_BAD_ARG otherwise): the host ping-pongs two.
+ *   Three plain launches, no atomics: (a) ceil(max_points / GPP_ROAD_PEEL_BLOCK) x F workgroups count their block's survivors into the
+ *   workspace; (b) one workgroup per frame scans its block counts in place (up to 512 of them, in chunks of 256 with a carry) and writes
+ *   kept_out; (c) the grid of (a) recomputes the mask and places every survivor: a ballot per wavefront and an LDS prefix across the four.
+ *   workspace: gpp_road_peel_workspace_bytes(F, max_points) bytes, 4-byte aligned like q_in, q_out and kept_out; too small:
+ *   GPP_ERR_WORKSPACE.  F == 0: GPP_OK, nothing launched.
+ *
  * Null pointer, a size or bound outside the ranges above: GPP_ERR_BAD_ARG; alignment: GPP_ERR_ALIGN; nothing is launched in these cases.
  * ---------------------------------------------------------------------------------------- */
 #define GPP_ROAD_Q 256
@@ -895,6 +911,11 @@ int gpp_road_score(const int32_t* q, const int32_t* offsets, const int32_t* kept
 int gpp_road_winner(const int32_t* count, int F, int H, int min_inliers, int32_t* winner, int32_t* inliers, void* stream);
 int gpp_road_moments(const int32_t* q, const int32_t* offsets, const int32_t* kept, const uint32_t* frame_id, uint32_t seed,
                      const int32_t* winner, int F, int total, int max_points, int H, double tq2, int64_t* sums, void* stream);
+#define GPP_ROAD_PEEL_BLOCK 2048
+int gpp_road_peel_workspace_bytes(int F, int max_points, size_t* bytes);
+int gpp_road_peel_i32(const int32_t* q_in, const int32_t* offsets, const int32_t* kept_in, const uint32_t* frame_id, uint32_t seed,
+                      const int32_t* winner, int F, int total, int max_points, int H, double tq2,
+                      int32_t* q_out, int32_t* kept_out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The --save-images composite on the device (csrc/draw.hip; DESIGN.md section 4.14 is the specification, utils/visualization.py its host
