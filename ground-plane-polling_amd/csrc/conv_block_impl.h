@@ -129,11 +129,23 @@ struct BlockShape {
 // channels 32 k .. 32 k + 31.  The two wavefronts that will finish those channels in phase 3 copy their 16-byte pieces from the ring into
 // registers there and then, and those channels of the shortcut map are never read a second time (C = 64: all 256 channels, 112 registers per
 // lane; C = 128: 384 of 512 -- the fourth output tile's rows are fetched like the general form's: with all of them the compiler spilled).
-template <int DT, int CMID, int TH, int TW, bool IDENT, int NWAVES, int RING1>
-__global__ __launch_bounds__(64 * NWAVES, 2) void bottleneck_block_x3_kernel(const gpp_conv_desc d1, const gpp_conv_desc d2, const gpp_conv_desc d3,
-                                                                      const int tiles_x, const int tiles_y, const int stagger_ticks)
+//
+// PROJ: a projection block whose shortcut is a 1x1 / stride-1 convolution ("branch1": C_in -> 4 C, no ReLU) of the block's own input (res2a).
+// Stage k of the phase-1 ring holds channels 32 k .. 32 k + 31 of every halo pixel, the tile's own pixels among them: the A operand of
+// branch1's K-step k.  Each wavefront multiplies the tile's rows with the branch1 weight rows of the channels it will finish in phase 3 (same
+// wavefront layout, same 128-column tiles; the fragments come straight from L2 into registers: the matrix is 64 KB and two K-steps deep),
+// applies branch1's own epilogue (scale, bias, range check, split) in registers and keeps float32(hi) + float32(lo) -- the value phase 3
+// would have read from the shortcut map, which is never written nor read.  The accumulators take the registers IDENT spends on its copied
+// rows.  XF32 (PROJ only): the block's input is a float32 map (pool1's output) and is split where a fragment is read, as the tile kernels do.
+struct NoDesc {};
+template <int DT, int CMID, int TH, int TW, bool IDENT, int NWAVES, int RING1, bool PROJ, bool XF32>
+__device__ __forceinline__ void bottleneck_block_x3_body(const gpp_conv_desc d1, const gpp_conv_desc d2, const gpp_conv_desc d3,
+                                                         const int tiles_x, const int tiles_y, const int stagger_ticks,
+                                                         const std::conditional_t<PROJ, gpp_conv_desc, NoDesc> dp)
 {
     static_assert(kX3<DT>, "x3 types on pre-split maps");
+    static_assert(!PROJ || (!IDENT && CMID == 64 && NWAVES == 4), "the projection form: C = 64, 4 wavefronts");
+    static_assert(!XF32 || PROJ, "float32 input: the projection form only");
     using S = BlockShape<CMID, TH, TW, NWAVES, RING1>;
     using xh8 = typename X3Half<DT>::vec;
     using half_t = typename X3Half<DT>::half;
@@ -182,7 +194,7 @@ __global__ __launch_bounds__(64 * NWAVES, 2) void bottleneck_block_x3_kernel(con
     char* const out_img = (char*)d3.out + ((G3.out_off + (int64_t)b * G3.out_bstride) << 2);
     const char* const res_img = (const char*)d3.residual + ((G3.res_off + (int64_t)b * G3.res_bstride) << 2);
     auto map_off = [&](int pixel, int pitch, int n) { return (int)((((unsigned)pixel * (unsigned)pitch + (unsigned)(n & ~31)) << 2) + ((unsigned)(n & 31) << 1)); };
-    int ctr_off[IDENT ? S::MF3 : 1];                               // IDENT: where the pixel's own row sits in a ring stage (hi piece; lo: ^ 64)
+    int ctr_off[(IDENT || PROJ) ? S::MF3 : 1];                     // IDENT / PROJ: where the pixel's own row sits in a ring stage (hi piece; lo: ^ 64; XF32: floats 0-3, 4-7: ^ 16)
 #pragma unroll
     for (int i = 0; i < S::MF3; ++i) {
         const int m = (wm3 * S::MF3 + i) * 16 + frow;
@@ -190,17 +202,17 @@ __global__ __launch_bounds__(64 * NWAVES, 2) void bottleneck_block_x3_kernel(con
         const int oy = y0 + ty, ox = x0 + tx;
         const bool ok = i < nrb3 && oy < H && ox < W;
         pix3[i] = ok ? oy * W + ox : -1;
-        if constexpr (IDENT) {
+        if constexpr (IDENT || PROJ) {
             const int r = (ty + 1) * HWD + tx + 1;                 // its halo row
-            ctr_off[i] = (i < nrb3 ? r : 0) * kRowBytes + ((fq ^ (r & 7)) << 4);
+            ctr_off[i] = (i < nrb3 ? r : 0) * kRowBytes + (((XF32 ? 2 * fq : fq) ^ (r & 7)) << 4);
         }
     }
     // IDENT: the shortcut rows of the first RT 128-channel output tiles live in registers from phase 1 on; the last tile's are fetched from the
     // map like the general form's (with all four in registers -- 128 per lane -- the compiler spilled 30 of them: the budget is 256 beside
     // the accumulators and fragments of three matrix phases; three quarters of the re-read is what there is room for)
     constexpr int N3T = CMID / 32;                                 // output tiles of an identity block (C_out = 4 C)
-    constexpr int RT = IDENT ? (CMID == 64 ? N3T : N3T - 1) : 0;
-    f32x8 rres[RT > 0 ? RT : 1][S::MF3];                           // [output tile][row block] raw [8 hi][8 lo] bits
+    constexpr int RT = IDENT ? (CMID == 64 ? N3T : N3T - 1) : (PROJ ? N3T : 0);
+    f32x8 rres[RT > 0 ? RT : 1][S::MF3];                           // [output tile][row block] raw [8 hi][8 lo] bits (PROJ: branch1's accumulators, then its 8 values)
     f32x8 rpre[S::MF3];                                            // the prefetched tile of the general form / the last tile of an identity block
     auto prefetch_res = [&](int t) {
         const int n = t * 128 + wn3 * 32 + fq * 8;
@@ -251,7 +263,7 @@ __global__ __launch_bounds__(64 * NWAVES, 2) void bottleneck_block_x3_kernel(con
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const int sw = ((h * 4 + fq) ^ (frow & 7)) << 4;
-        a_rd1[h] = (wm1 * (R1 / S::WM1) + frow) * kRowBytes + sw;
+        a_rd1[h] = (wm1 * (R1 / S::WM1) + frow) * kRowBytes + (XF32 ? ((2 * fq + h) ^ (frow & 7)) << 4 : sw);
         b_rd1[h] = S::A1_BYTES + (wn1 * 32 + frow) * kRowBytes + sw;
     }
     f32x4 acc1[S::MF1][2];
@@ -268,8 +280,13 @@ __global__ __launch_bounds__(64 * NWAVES, 2) void bottleneck_block_x3_kernel(con
 #pragma unroll
         for (int i = 0; i < S::MF1; ++i) {
             if (i >= nrb1) break;
-            const xh8 ah = *(const xh8*)(sb + a_rd1[0] + i * 16 * kRowBytes);
-            const xh8 al = *(const xh8*)(sb + a_rd1[1] + i * 16 * kRowBytes);
+            xh8 ah, al;
+            if constexpr (XF32) {
+                Elem<DT>::split(*(const f32x4*)(sb + a_rd1[0] + i * 16 * kRowBytes), *(const f32x4*)(sb + a_rd1[1] + i * 16 * kRowBytes), ah, al);
+            } else {
+                ah = *(const xh8*)(sb + a_rd1[0] + i * 16 * kRowBytes);
+                al = *(const xh8*)(sb + a_rd1[1] + i * 16 * kRowBytes);
+            }
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int js = GPP_SERP2(i, j, 2);
@@ -304,6 +321,99 @@ __global__ __launch_bounds__(64 * NWAVES, 2) void bottleneck_block_x3_kernel(con
                 }
             }
             step1(ks);
+        }
+    } else if constexpr (PROJ) {
+        // branch1 beside branch2a: K-step ks of both reads stage ks of the ring.  This wavefront's branch1 weight fragments of a K-step -- packed
+        // rows t * 128 + wn3 * 32 + j * 16 + frow, halves hi / lo, K elements 8 fq .. 8 fq + 7 -- are 8 x 16 bytes per lane, requested (L2-hot)
+        // just before the K-step's wait, which is vmcnt(0) at this ring depth and covers them.  (Requested a K-step ahead they stay live across
+        // branch2a's K-step: 254 registers, and the float32-input form spilled 20.)
+        static_assert(S::S1 == 2, "the weight fragments ride on the two-deep ring's vmcnt(0)");
+        // (plain loads, not a buffer resource: rows t * 128 + wn3 * 32 + j * 16 + frow < 256 = C_out <= weight_rows and K-steps ks < C_in / 32 of
+        // a packed matrix of weight_rows x C_in x 4 bytes -- the entry point checks both before the launch)
+        const int nk1 = d1.C_in / 32;
+        const char* const wp = (const char*)dp.weight + ((wn3 * 32 + frow) * d1.C_in * 4 + fq * 16);
+        xh8 ph[RT][2], pl[RT][2];
+        auto load_wp = [&](int ks) {
+#pragma unroll
+            for (int t = 0; t < RT; ++t)
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const char* p = wp + ((t * 128 + j * 16) * d1.C_in * 4 + ks * kRowBytes);
+                    ph[t][j] = *(const xh8*)p;
+                    pl[t][j] = *(const xh8*)(p + 64);
+                }
+        };
+#pragma unroll
+        for (int t = 0; t < RT; ++t)
+#pragma unroll
+            for (int i = 0; i < S::MF3; ++i) { rres[t][i].lo = (f32x4){0.f, 0.f, 0.f, 0.f}; rres[t][i].hi = (f32x4){0.f, 0.f, 0.f, 0.f}; }
+        issue1(0, 0);
+        int issued = 1;
+        for (int ks = 0; ks < nk1; ++ks) {
+            load_wp(ks);
+            wait_vmcnt<0>();
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            if (issued < nk1) { issue1(issued & (S::S1 - 1), issued); ++issued; }
+            const unsigned char* sb = smem + (ks & (S::S1 - 1)) * S::STAGE1;
+#pragma unroll
+            for (int i = 0; i < S::MF3; ++i) {
+                if (i >= nrb3) break;
+                xh8 ah, al;
+                if constexpr (XF32) {
+                    Elem<DT>::split(*(const f32x4*)(sb + ctr_off[i]), *(const f32x4*)(sb + (ctr_off[i] ^ 16)), ah, al);
+                } else {
+                    ah = *(const xh8*)(sb + ctr_off[i]);
+                    al = *(const xh8*)(sb + (ctr_off[i] ^ 64));
+                }
+#pragma unroll
+                for (int t = 0; t < RT; ++t) {
+                    rres[t][i].lo = X3Half<DT>::mfma(pl[t][0], ah, rres[t][i].lo);
+                    rres[t][i].lo = X3Half<DT>::mfma(ph[t][0], ah, rres[t][i].lo);
+                    rres[t][i].hi = X3Half<DT>::mfma(pl[t][1], ah, rres[t][i].hi);
+                    rres[t][i].hi = X3Half<DT>::mfma(ph[t][1], ah, rres[t][i].hi);
+                }
+#pragma unroll
+                for (int t = 0; t < RT; ++t) {
+                    rres[t][i].lo = X3Half<DT>::mfma(ph[t][0], al, rres[t][i].lo);
+                    rres[t][i].hi = X3Half<DT>::mfma(ph[t][1], al, rres[t][i].hi);
+                }
+            }
+            step1(ks);
+        }
+        // branch1's epilogue, in registers: fma(acc, out_scale, bias), no ReLU, range check (counted for the pixels the tile owns), split -- and
+        // back to float32(hi) + float32(lo), what phase 3 would have unpacked from the shortcut map
+        unsigned long long* const counter_p = (unsigned long long*)dp.range_counter;
+#pragma unroll
+        for (int t = 0; t < RT; ++t) {
+            const int n = t * 128 + wn3 * 32 + fq * 8;
+            float bias_v[8], scale_v[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                bias_v[e] = dp.bias ? dp.bias[n + e] : 0.0f;
+                scale_v[e] = (OSCALE && dp.out_scale) ? dp.out_scale[n + e] : 1.0f;
+            }
+#pragma unroll
+            for (int i = 0; i < S::MF3; ++i) {
+                if (i >= nrb3) break;
+                float v8[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const float a = e < 4 ? rres[t][i].lo[e] : rres[t][i].hi[e - 4];
+                    if constexpr (OSCALE) v8[e] = __builtin_fmaf(a, scale_v[e], bias_v[e]);
+                    else v8[e] = a + bias_v[e];
+                }
+                x3_range_if<DT>(v8, counter_p, pix3[i] >= 0);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const half_t h = (half_t)v8[e];
+                    const half_t l = (half_t)(v8[e] - (float)h);
+                    const float r = (float)h + (float)l;
+                    if (e < 4) rres[t][i].lo[e] = r;
+                    else rres[t][i].hi[e - 4] = r;
+                }
+            }
         }
     } else {
         const int nk1 = d1.C_in / 32;
@@ -463,7 +573,7 @@ __global__ __launch_bounds__(64 * NWAVES, 2) void bottleneck_block_x3_kernel(con
                        smem + S::T1_BYTES + kc * S::W3_SLAB + (wave * S::W3_IT + i) * 8 * kRowBytes);
     };
     stage_w3(0);
-    if constexpr (!IDENT) prefetch_res(0);                         // the shortcut rows of output tile 0: in flight under the b-tile's epilogue
+    if constexpr (!IDENT && !PROJ) prefetch_res(0);                         // the shortcut rows of output tile 0: in flight under the b-tile's epilogue
     {
         const int n = wn2 * 32 + fq * 8;
         float bias_v[8], scale_v[8];
@@ -513,11 +623,11 @@ __global__ __launch_bounds__(64 * NWAVES, 2) void bottleneck_block_x3_kernel(con
         a_rd3[h] = (wm3 * S::MF3 * 16 + frow) * kRowBytes + sw;
         b_rd3[h] = S::T1_BYTES + (wn3 * 32 + frow) * kRowBytes + sw;
     }
-    const int n3_tiles = IDENT ? N3T : d3.C_out / 128;
+    const int n3_tiles = (IDENT || PROJ) ? N3T : d3.C_out / 128;
     auto phase3 = [&]() {
         constexpr int NRB = S::MF3;
 #pragma unroll
-        for (int t = 0; t < (IDENT ? N3T : n3_tiles); ++t) {
+        for (int t = 0; t < ((IDENT || PROJ) ? N3T : n3_tiles); ++t) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();                          // W3 tile t (and, for t = 0, the b-tile) is in LDS
@@ -563,7 +673,7 @@ __global__ __launch_bounds__(64 * NWAVES, 2) void bottleneck_block_x3_kernel(con
             }
             // one row block at a time (registers): accumulator -> scale, bias -> + shortcut -> the next tile's shortcut rows of this row block are
             // requested (general form; before this block's stores go out) -> ReLU, range check, split, store
-            const bool fetch_next = t + 1 < n3_tiles && (!IDENT || t + 1 >= RT);
+            const bool fetch_next = !PROJ && t + 1 < n3_tiles && (!IDENT || t + 1 >= RT);
             const int n_next = (t + 1) * 128 + wn3 * 32 + fq * 8;
 #pragma unroll
             for (int i = 0; i < NRB; ++i) {
@@ -576,7 +686,10 @@ __global__ __launch_bounds__(64 * NWAVES, 2) void bottleneck_block_x3_kernel(con
                     else outv[e] = a + bias_v[e];
                 }
                 float r[8];
-                if (IDENT && t < RT) x3_unpack<DT>(rres[t < RT ? t : 0][i].lo, rres[t < RT ? t : 0][i].hi, r);
+                if constexpr (PROJ) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) r[e] = e < 4 ? rres[t][i].lo[e] : rres[t][i].hi[e - 4];
+                } else if (IDENT && t < RT) x3_unpack<DT>(rres[t < RT ? t : 0][i].lo, rres[t < RT ? t : 0][i].hi, r);
                 else x3_unpack<DT>(rpre[i].lo, rpre[i].hi, r);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) outv[e] += r[e];
@@ -613,6 +726,22 @@ __global__ __launch_bounds__(64 * NWAVES, 2) void bottleneck_block_x3_kernel(con
 #endif
 }
 
+// the two kernels of the body: the three-layer forms (the shortcut a map, or the block's input), and the projection form
+template <int DT, int CMID, int TH, int TW, bool IDENT, int NWAVES, int RING1>
+__global__ __launch_bounds__(64 * NWAVES, 2) void bottleneck_block_x3_kernel(const gpp_conv_desc d1, const gpp_conv_desc d2, const gpp_conv_desc d3,
+                                                                      const int tiles_x, const int tiles_y, const int stagger_ticks)
+{
+    bottleneck_block_x3_body<DT, CMID, TH, TW, IDENT, NWAVES, RING1, false, false>(d1, d2, d3, tiles_x, tiles_y, stagger_ticks, NoDesc());
+}
+
+template <int DT, int TH, int TW, bool XF32>
+__global__ __launch_bounds__(256, 2) void bottleneck_block_proj_x3_kernel(const gpp_conv_desc d1, const gpp_conv_desc d2, const gpp_conv_desc d3,
+                                                                   const gpp_conv_desc dp, const int tiles_x, const int tiles_y,
+                                                                   const int stagger_ticks)
+{
+    bottleneck_block_x3_body<DT, 64, TH, TW, false, 4, 2, true, XF32>(d1, d2, d3, tiles_x, tiles_y, stagger_ticks, dp);
+}
+
 template <int DT, int CMID, int TH, int TW, bool IDENT, int NWAVES, int RING1>
 int launch_block_x3(gpp_conv_desc& d1, gpp_conv_desc& d2, gpp_conv_desc& d3, int stagger_us, hipStream_t st)
 {
@@ -632,6 +761,44 @@ int launch_block_x3(gpp_conv_desc& d1, gpp_conv_desc& d2, gpp_conv_desc& d3, int
     if (grid >= (1LL << 31)) return GPP_ERR_UNSUPPORTED;
     kernel<<<dim3((unsigned)grid), dim3(64 * NWAVES), S::LDS, st>>>(d1, d2, d3, tiles_x, tiles_y, stagger_us * 100);
     return last_launch_rc();
+}
+
+// the projection form (C = 64): branch1 = dp computed inside the launch; d3 carries no shortcut map
+template <int DT, int TH, int TW, bool XF32>
+int launch_block_proj_x3(gpp_conv_desc& d1, gpp_conv_desc& d2, gpp_conv_desc& d3, gpp_conv_desc& dp, int stagger_us, hipStream_t st)
+{
+    using S = BlockShape<64, TH, TW, 4, 2>;
+    constexpr auto kernel = bottleneck_block_proj_x3_kernel<DT, TH, TW, XF32>;
+    int rc = allow_lds<kernel>(S::LDS);
+    if (rc == GPP_OK) rc = set_input_extent(d1, 4);
+    if (rc == GPP_OK) rc = set_weight_extent(d1, d1.C_in, 4);
+    if (rc == GPP_OK) rc = set_weight_extent(d2, 9 * 64, 4);
+    if (rc == GPP_OK) rc = set_weight_extent(d3, 64, 4);
+    if (rc != GPP_OK) return rc;
+    const gpp_conv_group &G = d1.groups[0], &G3 = d3.groups[0];
+    const int64_t px = (int64_t)G3.H_out * G3.W_out;
+    if (px * d3.out_pitch * 4 >= (1LL << 31)) return GPP_ERR_UNSUPPORTED;     // 32-bit byte offsets inside one image
+    const int tiles_x = (G.W_out + TW - 1) / TW, tiles_y = (G.H_out + TH - 1) / TH;
+    const int64_t grid = (int64_t)d1.batch * tiles_x * tiles_y;
+    if (grid >= (1LL << 31)) return GPP_ERR_UNSUPPORTED;
+    kernel<<<dim3((unsigned)grid), dim3(256), S::LDS, st>>>(d1, d2, d3, dp, tiles_x, tiles_y, stagger_us * 100);
+    return last_launch_rc();
+}
+
+// tile = TH * 100 + TW (0 = the default) as dispatch_block_x3 takes it; the input map pre-split or float32 (d1.x3_split & GPP_X3_IN)
+template <int DT>
+int dispatch_block_proj_x3(gpp_conv_desc& d1, gpp_conv_desc& d2, gpp_conv_desc& d3, gpp_conv_desc& dp, int tile, hipStream_t st)
+{
+    const int stagger_us = tile / 10000;
+    tile %= 10000;
+    if (stagger_us < 0 || stagger_us > 200) return GPP_ERR_BAD_ARG;
+    if (d2.C_in != 64) return GPP_ERR_UNSUPPORTED;
+    switch (tile) {
+        case 0:
+        case 814: return (d1.x3_split & GPP_X3_IN) ? launch_block_proj_x3<DT, 8, 14, false>(d1, d2, d3, dp, stagger_us, st)
+                                                   : launch_block_proj_x3<DT, 8, 14, true>(d1, d2, d3, dp, stagger_us, st);
+        default: return GPP_ERR_BAD_ARG;
+    }
 }
 
 // tile = TH * 100 + TW (0 = the default of the width)

@@ -221,7 +221,56 @@ int block_entry(const gpp_conv_desc* conv_a, const gpp_conv_desc* conv_b, const 
     return d1.dtype == GPP_F16X3 ? gpp_block_dispatch_f16x3(d1, d2, d3, tile, st) : gpp_block_dispatch_bf16x3(d1, d2, d3, tile, st);
 }
 
+// the same block with its projection shortcut (conv_p: 1x1 / stride 1 / C_in -> 4 C on the block's own input) computed inside the launch
+int block_proj_entry(const gpp_conv_desc* conv_a, const gpp_conv_desc* conv_b, const gpp_conv_desc* conv_c, const gpp_conv_desc* conv_p, int tile,
+                     void* stream)
+{
+    if (!conv_a || !conv_b || !conv_c || !conv_p) return GPP_ERR_BAD_ARG;
+    gpp_conv_desc d1 = *conv_a, d2 = *conv_b, d3 = *conv_c, dp = *conv_p;
+    int rc = validate(d1);
+    if (rc == GPP_OK) rc = validate(d2);
+    if (rc == GPP_OK) rc = validate(d3);
+    if (rc == GPP_OK) rc = validate(dp);
+    if (rc != GPP_OK) return rc;
+    for (const gpp_conv_desc* d : {&d1, &d2, &d3, &dp})
+        if (d->gather_rows || d->guard || d->tower_rows || d->deep_rows || d->lists_after) return GPP_ERR_UNSUPPORTED;
+    const gpp_conv_group &G1 = d1.groups[0], &G2 = d2.groups[0], &G3 = d3.groups[0], &GP = dp.groups[0];
+    if (!is_x3(d1.dtype) || d1.dtype != d2.dtype || d1.dtype != d3.dtype || d1.dtype != dp.dtype) return GPP_ERR_UNSUPPORTED;
+    if (d1.n_groups != 1 || d2.n_groups != 1 || d3.n_groups != 1 || dp.n_groups != 1 || d1.batch != d2.batch || d1.batch != d3.batch || d1.batch != dp.batch)
+        return GPP_ERR_UNSUPPORTED;
+    // every map between the layers pre-split; the block's input pre-split or float32 (pool1's map), the same for both of its readers
+    if ((d1.x3_split | GPP_X3_IN) != (GPP_X3_IN | GPP_X3_OUT) || d2.x3_split != (GPP_X3_IN | GPP_X3_OUT) || d3.x3_split != (GPP_X3_IN | GPP_X3_OUT) ||
+        dp.x3_split != d1.x3_split)
+        return GPP_ERR_UNSUPPORTED;
+    if (d1.KH != 1 || d1.KW != 1 || d1.stride != 1 || d1.pad_top != 0 || d1.pad_left != 0 || d1.residual || d1.out_f32 || d1.split_k > 1) return GPP_ERR_UNSUPPORTED;
+    if (d2.KH != 3 || d2.KW != 3 || d2.stride != 1 || d2.pad_top != 1 || d2.pad_left != 1 || d2.residual || d2.out_f32 || d2.split_k > 1) return GPP_ERR_UNSUPPORTED;
+    if (d3.KH != 1 || d3.KW != 1 || d3.stride != 1 || d3.pad_top != 0 || d3.pad_left != 0 || d3.residual || d3.out_f32 || d3.split_k > 1) return GPP_ERR_UNSUPPORTED;
+    if (dp.KH != 1 || dp.KW != 1 || dp.stride != 1 || dp.pad_top != 0 || dp.pad_left != 0 || dp.residual || dp.relu || dp.out_f32 || dp.split_k > 1) return GPP_ERR_UNSUPPORTED;
+    // res2a's shape: 64 -> 64 -> 256 (the kernel's branch1 loop is written for any C_in that is a multiple of 32; only this one is built and tested)
+    if (d1.C_in != 64 || d2.C_in != 64 || d2.C_out != 64 || d1.C_out != 64 || d3.C_in != 64 || d3.C_out != 256 || dp.C_out != d3.C_out) return GPP_ERR_UNSUPPORTED;
+    if (dp.in != d1.in || dp.in_pitch != d1.in_pitch || dp.C_in != d1.C_in || GP.in_off != G1.in_off || GP.in_bstride != G1.in_bstride ||
+        GP.H_in != G1.H_in || GP.W_in != G1.W_in || GP.H_out != G1.H_out || GP.W_out != G1.W_out)
+        return GPP_ERR_UNSUPPORTED;
+    // (dp.weight_rows >= dp.C_out with dp.C_in == d1.C_in is also what bounds the kernel's plain loads of the branch1 weight fragments)
+    if (d1.weight_rows < 64 || d2.weight_rows < 64 || d3.weight_rows < d3.C_out || dp.weight_rows < dp.C_out) return GPP_ERR_UNSUPPORTED;
+    if (G1.H_out != G1.H_in || G1.W_out != G1.W_in) return GPP_ERR_BAD_ARG;
+    if (G2.H_in != G1.H_out || G2.W_in != G1.W_out || G2.H_out != G1.H_out || G2.W_out != G1.W_out || G3.H_in != G1.H_out || G3.W_in != G1.W_out ||
+        G3.H_out != G1.H_out || G3.W_out != G1.W_out)
+        return GPP_ERR_BAD_ARG;
+    for (gpp_conv_desc* d : {&d1, &d2, &d3, &dp})
+        if ((rc = fill_range_counter(*d)) != GPP_OK) return rc;
+    if (d1.range_counter != d3.range_counter || d2.range_counter != d3.range_counter || dp.range_counter != d3.range_counter) return GPP_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    return d1.dtype == GPP_F16X3 ? gpp_block_proj_dispatch_f16x3(d1, d2, d3, dp, tile, st) : gpp_block_proj_dispatch_bf16x3(d1, d2, d3, dp, tile, st);
+}
+
 }  // namespace
+
+extern "C" int gpp_bottleneck_block_proj(const gpp_conv_desc* conv1x1_a, const gpp_conv_desc* conv3x3_b, const gpp_conv_desc* conv1x1_c,
+                                         const gpp_conv_desc* conv1x1_proj, int tile, void* stream)
+{
+    return block_proj_entry(conv1x1_a, conv3x3_b, conv1x1_c, conv1x1_proj, tile, stream);
+}
 
 extern "C" int gpp_bottleneck_block(const gpp_conv_desc* conv1x1_a, const gpp_conv_desc* conv3x3_b, const gpp_conv_desc* conv1x1_c, int tile, void* stream)
 {

@@ -19,6 +19,8 @@ int gpp_tail_dispatch_bf16x3(gpp_conv_desc& d1, gpp_conv_desc& d2, int tile_rows
 int gpp_tail_dispatch_f16x3(gpp_conv_desc& d1, gpp_conv_desc& d2, int tile_rows, hipStream_t st);
 int gpp_block_dispatch_f16x3(gpp_conv_desc& d1, gpp_conv_desc& d2, gpp_conv_desc& d3, int tile, hipStream_t st);
 int gpp_block_dispatch_bf16x3(gpp_conv_desc& d1, gpp_conv_desc& d2, gpp_conv_desc& d3, int tile, hipStream_t st);
+int gpp_block_proj_dispatch_f16x3(gpp_conv_desc& d1, gpp_conv_desc& d2, gpp_conv_desc& d3, gpp_conv_desc& dp, int tile, hipStream_t st);
+int gpp_block_proj_dispatch_bf16x3(gpp_conv_desc& d1, gpp_conv_desc& d2, gpp_conv_desc& d3, gpp_conv_desc& dp, int tile, hipStream_t st);
 int gpp_preact_dispatch_f32(gpp_conv_desc& d, const float* in_scale, const float* in_shift, hipStream_t st);
 int gpp_preact_dispatch_bf16x3(gpp_conv_desc& d, const float* in_scale, const float* in_shift, hipStream_t st);
 int gpp_preact_dispatch_f16x3(gpp_conv_desc& d, const float* in_scale, const float* in_shift, hipStream_t st);

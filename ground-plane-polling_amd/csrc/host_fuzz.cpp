@@ -83,11 +83,15 @@ int main(int argc, char** argv)
             break;
         }
         case 1: note(gpp_bottleneck_tail(&r.d[0], &r.d[1], (int)(r.b % 200), nullptr)); break;
-        case 2: note(gpp_bottleneck_block(&r.d[0], &r.d[1], &r.d[2], (int)(r.b % 2000), nullptr)); break;
+        case 2:
+            note(gpp_bottleneck_block(&r.d[0], &r.d[1], &r.d[2], (int)(r.b % 2000), nullptr));
+            note(gpp_bottleneck_block_proj(&r.d[0], &r.d[1], &r.d[2], (r.c & 1) ? &r.d[r.c % 3] : nullptr, (int)(r.b % 2000), nullptr));
+            break;
         case 3: {
             // a plan of a few ops over these descriptors (kinds and lane / join / sync flags fuzzed)
             gpp_tail_desc t = {&r.d[0], &r.d[1], (int32_t)(r.b % 200), 0};
-            gpp_block_desc bl = {&r.d[0], &r.d[1], &r.d[2], (int32_t)(r.c % 2000), 0};
+            // (form 1, now and then 2: the record with the projection layer behind it)
+            gpp_block_proj_desc bl = {{&r.d[0], &r.d[1], &r.d[2], (int32_t)(r.c % 2000), (int32_t)((r.c >> 11) % 3)}, &r.d[(r.c >> 13) % 3]};
             // (a kind whose descriptor type the record does not carry gets a conv descriptor's bytes, or NULL: every entry point checks its own
             // arguments, and none of the other descriptor types is larger than a gpp_conv_desc)
             static_assert(sizeof(gpp_conv_desc) >= sizeof(gpp_detect_desc) && sizeof(gpp_conv_desc) >= sizeof(gpp_poll_desc) &&

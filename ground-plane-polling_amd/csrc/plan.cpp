@@ -216,7 +216,10 @@ extern "C" int gpp_plan_run(const gpp_plan_op* ops, int n_ops, void* stream, voi
         }
         case GPP_OP_BOTTLENECK_BLOCK: {
             const gpp_block_desc* d = (const gpp_block_desc*)op.desc;
-            rc = gpp_bottleneck_block(d->conv1x1_a, d->conv3x3_b, d->conv1x1_c, d->tile, stream);
+            if (d->form == 1)             // a projection block: the shortcut's layer is the fourth pointer, computed inside the launch
+                rc = gpp_bottleneck_block_proj(d->conv1x1_a, d->conv3x3_b, d->conv1x1_c, ((const gpp_block_proj_desc*)op.desc)->conv1x1_proj, d->tile, stream);
+            else
+                rc = d->form != 0 ? GPP_ERR_BAD_ARG : gpp_bottleneck_block(d->conv1x1_a, d->conv3x3_b, d->conv1x1_c, d->tile, stream);
             break;
         }
         case GPP_OP_CONV_PREACT: {

@@ -321,6 +321,9 @@ def _declare(lib):
     lib.gpp_stem_pool_fused_x3.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     lib.gpp_bottleneck_block.restype = c_int
     lib.gpp_bottleneck_block.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), c_int, c_void_p]
+    lib.gpp_bottleneck_block_proj.restype = c_int
+    lib.gpp_bottleneck_block_proj.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc),
+                                              c_int, c_void_p]
     lib.gpp_conv2d_autotune.restype = c_int
     lib.gpp_conv2d_autotune.argtypes = [ctypes.POINTER(ConvDesc), c_int, c_void_p, ctypes.POINTER(c_float)]
 

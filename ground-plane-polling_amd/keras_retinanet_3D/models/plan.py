@@ -86,6 +86,11 @@ class BlockDesc(ctypes.Structure):
     _fields_ = [('conv1x1_a', ctypes.c_void_p), ('conv3x3_b', ctypes.c_void_p), ('conv1x1_c', ctypes.c_void_p), ('tile', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
+class BlockProjDesc(ctypes.Structure):         # gpp_block_proj_desc: a BlockDesc whose `reserved` (the header's `form`) is 1, then the shortcut's layer
+    _fields_ = [('conv1x1_a', ctypes.c_void_p), ('conv3x3_b', ctypes.c_void_p), ('conv1x1_c', ctypes.c_void_p), ('tile', ctypes.c_int32),
+                ('form', ctypes.c_int32), ('conv1x1_proj', ctypes.c_void_p)]
+
+
 OP_STEM, OP_MAXPOOL, OP_CONV, OP_RELU, OP_DETECT, OP_POLL, OP_TAIL = 1, 2, 3, 4, 5, 6, 7
 OP_BLOCK = 16
 OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT = 8, 9, 10
@@ -103,17 +108,35 @@ OP_JOIN, OP_SYNC = 0x10000, 0x20000
 
 # the effective plan switches of one (model, batch), read from the GPP_* variables by RetinaNet3D._plan_options
 PlanOptions = collections.namedtuple('PlanOptions', 'x3_level fuse_stem_pool stage_chunks half_stages fuse_tail fuse_block fuse_block_proj '
+                                                    'fuse_block_inproj fuse_inproj_rounds '
                                                     'br1_lane fpn_lanes p4_lane head_lanes decode_overlap cls_lane autotune tune_key sparse_heads '
                                                     'sparse_tower sparse_tower_rounds sparse_deep sparse_deep_rounds sparse_depth')
 
 
-def block_form(opts, width, projection, split_input, halves, join):
+# the fused projection block: its workgroups compute 8 x 14 output pixels, two share a compute unit
+INPROJ_TILE = (8, 14)
+FUSE_INPROJ_MIN_ROUNDS = '1'
+
+
+def inproj_rounds(images, h, w):
+    """ rounds of 2 x COMPUTE_UNITS workgroups the fused projection block of `images` images of h x w output pixels fields """
+    th, tw = INPROJ_TILE
+    return images * (-(-h // th)) * (-(-w // tw)) / (2.0 * COMPUTE_UNITS)
+
+
+def block_form(opts, width, projection, split_input, halves, join, inproj=None):
     """ how one bottleneck runs: (launch, shortcut).
     launch: 'block' (branch2a + 2b + 2c + shortcut as one launch, gpp_bottleneck_block: pre-split input maps only), 'tail' (branch2a, then
     2b + 2c as one launch, gpp_bottleneck_tail) or 'convs' (three launches).
+    inproj: (stride, images, h, w) of a projection block's batch part -- a rule of layer, map size and batch part, like the split rule: a
+    stride-1 projection block of width 64 (res2a) whose launch fields MORE than opts.fuse_inproj_rounds rounds of workgroups runs as
+    ('block', 'inproj'): one launch, gpp_bottleneck_block_proj, the shortcut computed inside it (float32 or pre-split input).
     shortcut: 'identity' (the block's input), 'side' (the projection on side lane 1, beside branch2a / 2b, joined by the launch that adds
     it) or 'inline' (the projection on the block's own lane: GPP_BR1_LANE=0, half-batch stages, and the first block behind a split stage,
     whose first launch joins the half-batch lanes). """
+    if (projection and inproj is not None and opts.fuse_block_inproj and width == 64 and width in opts.fuse_block and inproj[0] == 1 and
+            inproj_rounds(*inproj[1:]) > opts.fuse_inproj_rounds):
+        return 'block', 'inproj'
     if width in opts.fuse_block and (not projection or opts.fuse_block_proj) and split_input:    # (res2a reads the pooled map: float32)
         launch = 'block'
     else:

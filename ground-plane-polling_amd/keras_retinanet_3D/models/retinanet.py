@@ -42,7 +42,7 @@ from ..utils import anchors as anchor_utils
 from ..utils.gpp_utils import POLL_THRESHOLD, POSE_SCORE_THRESHOLD
 from . import weights as W
 # what a plan is (models/plan.py), under the names this module has always had: tests and tools spell them retinanet.StemDesc, retinanet.OP_CONV ...
-from .plan import (BlockDesc, CandidatePixelsDesc, DensePoolDesc, DetectDesc, PlanOp, PollDesc, PoolDesc, PoseDesc,  # noqa: F401
+from .plan import (BlockDesc, BlockProjDesc, FUSE_INPROJ_MIN_ROUNDS, CandidatePixelsDesc, DensePoolDesc, DetectDesc, PlanOp, PollDesc, PoolDesc, PoseDesc,  # noqa: F401
                    PreactDesc, RaggedPoolDesc, RaggedStemDesc, ReluDesc, StemDesc, TailDesc,
                    OP_STEM, OP_MAXPOOL, OP_CONV, OP_RELU, OP_DETECT, OP_POLL, OP_TAIL, OP_BLOCK,
                    OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT, OP_DETECT_OSF, OP_STEM_POOL,
@@ -267,6 +267,19 @@ class RetinaNet3D(object):
         plan.emit(OP_BLOCK, t, 'res{}_branch2a+2b+2c'.format(nm), [x, shortcut], [y], flops=C.conv_flops(d1) + C.conv_flops(d2) + C.conv_flops(d3),
                   join=join, lane=lane, io=([x], [y], [shortcut]), inner=(d1, d2, d3))
 
+    def _block_proj(self, plan, nm, x, a, bmap, sc, y, join=False, lane=0):
+        """ a whole projection bottleneck -- branch2a, branch1, branch2b, branch2c (+ shortcut, ReLU) -- as ONE launch (gpp_bottleneck_block_proj): the
+        shortcut is computed from the input rows branch2a stages and never becomes a map (`a` / `bmap` / `sc` only lend the descriptors their
+        shapes).  Bit-identical to the four layers. """
+        d1 = self._desc(plan, 'res{}_branch2a'.format(nm), [x], [a], 1, relu=True)
+        d2 = self._desc(plan, 'res{}_branch2b'.format(nm), [a], [bmap], 3, pad=(1, 1), relu=True)
+        d3 = self._desc(plan, 'res{}_branch2c'.format(nm), [bmap], [y], 1, relu=True)
+        dp = self._desc(plan, 'res{}_branch1'.format(nm), [x], [sc], 1)
+        t = BlockProjDesc(ctypes.addressof(d1), ctypes.addressof(d2), ctypes.addressof(d3), 0, 1, ctypes.addressof(dp))
+        plan.emit(OP_BLOCK, t, 'res{}_branch2a+2b+2c'.format(nm), [x], [y],
+                  flops=C.conv_flops(d1) + C.conv_flops(d2) + C.conv_flops(d3) + C.conv_flops(dp), join=join, lane=lane, io=([x], [y], None),
+                  inner=(d1, d2, d3, dp))
+
     def _preact(self, plan, name, inputs, outputs, relu=False):
         """ a 1x1 conv behind its input's BatchNormalization + ReLU (gpp_conv2d_preact): DenseNet's _1_conv and transition convs """
         d = self._desc(plan, name, inputs, outputs, 1, relu=relu)
@@ -336,7 +349,7 @@ class RetinaNet3D(object):
                                                               [(k, p) for p in parts for k in blocks]):
                 xs = xs_of[c0]
                 join = not halves and bool(plan.open_lanes)          # the first launch of a whole-batch stage behind a split one
-                form = block_form(opts, f, sc is not None, xs.split, halves, join)
+                form = block_form(opts, f, sc is not None, xs.split, halves, join, inproj=(stride, nb, y.H, y.W))
                 xs_of[c0] = part_of(y, c0, nb)
                 self._bottleneck(plan, nm, form, stride, xs, part_of(a, c0, nb), b and part_of(b, c0, nb),
                                  part_of(sc, c0, nb) if sc else xs, xs_of[c0], lane, join)
@@ -348,6 +361,9 @@ class RetinaNet3D(object):
         before; a projection shortcut on side lane 1 is joined by the launch that adds it. """
         launch, shortcut = form
         branch1 = 'res{}_branch1'.format(nm)
+        if shortcut == 'inproj':
+            self._block_proj(plan, nm, x, a, b or a, sc, y, join=join, lane=lane)
+            return
         if shortcut == 'side':
             self._conv(plan, branch1, [x], [sc], 1, stride=stride, lane=1)
         if launch == 'block':
@@ -848,6 +864,12 @@ class RetinaNet3D(object):
             fuse_tail=tuple(v for v in fuse_tail if v in (64, 128)),
             fuse_block=tuple(v for v in fuse_block if v in (64, 128)),
             fuse_block_proj=env('GPP_FUSE_BLOCK_PROJ', '0') != '0',
+            # GPP_FUSE_BLOCK_INPROJ (default 1; with 64 in GPP_FUSE_BLOCK): res2a -- the stride-1 projection block -- as ONE launch that computes the
+            # shortcut itself (gpp_bottleneck_block_proj): no res2a_branch1 launch, no shortcut map through HBM (276 MB written and read back at
+            # B = 8).  Only where a batch part's launch fields more than GPP_FUSE_INPROJ_MIN_ROUNDS rounds of 2 x 256 workgroups of 8 x 14 pixels
+            # (a rule of layer, map size and batch part); 0 = res2a as three launches.  Bit-identical either way.
+            fuse_block_inproj=env('GPP_FUSE_BLOCK_INPROJ', '1') != '0',
+            fuse_inproj_rounds=float(env('GPP_FUSE_INPROJ_MIN_ROUNDS', FUSE_INPROJ_MIN_ROUNDS)),
             br1_lane=env('GPP_BR1_LANE', '1') != '0',           # measured +0.4 % on the f16x3 step (same box, alternating)
             fpn_lanes=fpn_lanes,
             p4_lane=1 if (fpn_lanes and env('GPP_P4_LANE', '1') != '0') else 0,
@@ -881,7 +903,7 @@ class RetinaNet3D(object):
             sparse_depth=int(env('GPP_SPARSE_TOWER_DEPTH', SPARSE_TOWER_DEPTH)),
             tune_key='x3split={};fuse={}/{};plan={}{}'.format(env('GPP_X3_SPLIT', '2'), env('GPP_FUSE_TAIL', '64,128'), env('GPP_FUSE_BLOCK', '64,128'),
                                                               self.plan_mode, C.latency_split_config() if self.plan_mode == 'latency' else '') +
-                     (';audit' if self.audit else ''))
+                     (';audit' if self.audit else '') + ('' if env('GPP_FUSE_BLOCK_INPROJ', '1') != '0' else ';inproj=0'))      # (the default keeps its key)
 
     def _build(self, B, H, Wd, n_planes, planes_batched, ragged=False):
         """ ragged: the plan of a height class (utils/image.py) -- H = 4 Hp is the row count of the canvas, and the stem and pool1 take

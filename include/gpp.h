@@ -276,6 +276,16 @@ int gpp_bottleneck_tail(const gpp_conv_desc* conv3x3, const gpp_conv_desc* conv1
    (an experiment).  Every map of the block must stay below 2 GiB per image.  Other shapes / types: GPP_ERR_UNSUPPORTED. */
 int gpp_bottleneck_block(const gpp_conv_desc* conv1x1_a, const gpp_conv_desc* conv3x3_b, const gpp_conv_desc* conv1x1_c, int tile, void* stream);
 
+/* The same launch for a block whose shortcut is a PROJECTION of its own input (res2a): conv1x1_proj ("branch1": 1x1, stride 1, C_in -> 4 C, + bias,
+   no ReLU) is computed inside the launch from the input rows that pass through the LDS ring for branch2a, finished by its own epilogue (scale, bias,
+   range check, split) in registers and added where gpp_bottleneck_block adds the shortcut map's values.  conv1x1_proj->out, conv1x1_a->out and
+   conv3x3_b->out are not written; conv1x1_c->residual must be NULL.  Bit-identical to the four gpp_conv2d_igemm launches (branch2a, branch1,
+   branch2b, branch2c), range events included.  GPP_ERR_UNSUPPORTED unless: one x3 type; C_in = C = 64 and C_out = 256 (res2a); both 1x1 layers on the input have
+   stride 1, the same input pointer, offsets, pitch, C_in and sizes; every map behind the input is pre-split (the input itself pre-split or float32,
+   the same for both of its readers); conv1x1_proj has no residual, ReLU, lists or guard.  tile as gpp_bottleneck_block's (0 or 814). */
+int gpp_bottleneck_block_proj(const gpp_conv_desc* conv1x1_a, const gpp_conv_desc* conv3x3_b, const gpp_conv_desc* conv1x1_c,
+                              const gpp_conv_desc* conv1x1_proj, int tile, void* stream);
+
 /* GPP_F16X3 range ledger.  The half type ends at +-65504: an epilogue that stores an activation outside it (a finite value it has to
    clamp, an inf or a NaN) adds one event per 8-channel group to a device-side counter (one per device).  host_count (host pointer,
    may be NULL) receives the events since the last reset; reset != 0 clears the counter.  Synchronises the device.  Zero after a run
@@ -1018,7 +1028,7 @@ int gpp_absmax_clear(uint32_t* table, int64_t n, void* stream);
 /* (11: the three-layer tail of round 2, removed in round 3 -- measured slower than its separate launches) */
 #define GPP_OP_DETECT_OSF 12             /* gpp_detect_desc -> gpp_detect_osf_f32 */
 #define GPP_OP_STEM_POOL 13              /* gpp_stem_desc with out = the pooled map -> gpp_stem_pool_fused_mfma (GPP_BF16 / GPP_F16) / gpp_stem_pool_fused_x3 (GPP_F16X3 / GPP_BF16X3) */
-#define GPP_OP_BOTTLENECK_BLOCK 16       /* gpp_block_desc -> gpp_bottleneck_block */
+#define GPP_OP_BOTTLENECK_BLOCK 16       /* gpp_block_desc -> gpp_bottleneck_block; with form = 1 a gpp_block_proj_desc -> gpp_bottleneck_block_proj */
 #define GPP_OP_MAXPOOL_PAD 17            /* gpp_dense_pool_desc -> gpp_maxpool3x3s2_pad_f32 (DenseNet pool1) */
 #define GPP_OP_AVGPOOL 18                /* gpp_dense_pool_desc -> gpp_avgpool2x2_f32 (DenseNet transitions) */
 #define GPP_OP_POSE 19                   /* gpp_pose_desc -> gpp_pose_f32 (opt-in: RetinaNet3D(pose=True)) */
@@ -1093,7 +1103,9 @@ typedef struct gpp_pose_desc {
 } gpp_pose_desc;
 
 typedef struct gpp_tail_desc { const gpp_conv_desc* conv3x3; const gpp_conv_desc* conv1x1; int32_t tile_rows, reserved; } gpp_tail_desc;
-typedef struct gpp_block_desc { const gpp_conv_desc* conv1x1_a; const gpp_conv_desc* conv3x3_b; const gpp_conv_desc* conv1x1_c; int32_t tile, reserved; } gpp_block_desc;
+/* form: 0 = the three layers (the shortcut is conv1x1_c->residual); 1 = the record is a gpp_block_proj_desc (the same fields, then the fourth layer) */
+typedef struct gpp_block_desc { const gpp_conv_desc* conv1x1_a; const gpp_conv_desc* conv3x3_b; const gpp_conv_desc* conv1x1_c; int32_t tile, form; } gpp_block_desc;
+typedef struct gpp_block_proj_desc { gpp_block_desc block; const gpp_conv_desc* conv1x1_proj; } gpp_block_proj_desc;
 
 typedef struct gpp_preact_desc { const gpp_conv_desc* conv; const float* in_scale; const float* in_shift; } gpp_preact_desc;
 typedef struct gpp_dense_pool_desc { const float* in; float* out; int32_t B, H, W, C, pad, out_pitch; } gpp_dense_pool_desc;   /* pad: max-pool only */
