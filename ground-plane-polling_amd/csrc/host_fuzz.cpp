@@ -174,6 +174,12 @@ int main(int argc, char** argv)
             note(gpp_draw_raster((const uint8_t*)r.d[0].in, (const int32_t*)(uintptr_t)r.d[0].bias, (int)(r.a % 3000) + 1, (int)(r.b % 3000) + 1,
                                  (const void*)((uintptr_t)r.d[0].weight | 8), (const int32_t*)(uintptr_t)r.d[0].bias, (int)(r.c % 64) + 1, (uint8_t*)r.d[0].out,
                                  r.d[0].out, nullptr));
+            // the cuboid NMS: null pointers, more rows than the kept mask holds, a threshold outside (0, 1) -- all end before any launch
+            note(gpp_cuboid_nms_f64(nullptr, (int)r.a, (int)r.b, (int)(r.c % 4), 0.3, nullptr, nullptr, nullptr, nullptr));
+            note(gpp_cuboid_nms_f64((const float*)r.d[0].in, (int)(r.a % 64) + 1, 129 + (int)(r.b % 2000), (int)(r.c & 1), 0.3, (float*)r.d[0].out,
+                                    (int32_t*)(uintptr_t)r.d[0].bias, (int32_t*)(uintptr_t)r.d[0].bias, nullptr));
+            note(gpp_cuboid_nms_f64((const float*)r.d[0].in, (int)(r.a % 64) + 1, (int)(r.b % 128) + 1, (int)(r.c & 1), (double)(r.c % 3) - 1.0, (float*)r.d[0].out,
+                                    (int32_t*)(uintptr_t)r.d[0].bias, (int32_t*)(uintptr_t)r.d[0].bias, nullptr));
             // the plane distillation's host halves: sizes, then argument checks (bad pitch, K > M, null and misaligned pointers) that end before any launch
             note(gpp_poll_costs_workspace_bytes((int)r.a, &wb));
             note(gpp_plane_select_workspace_bytes((int)r.b, nullptr));

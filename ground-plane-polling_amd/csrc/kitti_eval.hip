@@ -8,6 +8,7 @@
 //                           edge, 4 -> 8, and is indexed at run time: it lives in LDS, two buffers of 8 vertices per thread laid out
 //                           [buffer][vertex][thread] (consecutive lanes, consecutive doubles: no bank conflict), 16 KB per workgroup of
 //                           64 threads.  The label's corners are indexed by an unrolled loop and stay in registers.  No scratch.
+//                           The clipping itself is rot_iou.h, which cuboid_nms.hip shares.
 //   kitti_stats_kernel      one workgroup per image, one thread per (metric, difficulty, threshold) triple, each walking the labels
 //                           serially as the devkit does; the set of assigned detections is a 128-bit mask in two registers.  Scores,
 //                           alphas and the status vectors of the image are staged in LDS, the four overlap planes too when they fit
@@ -23,6 +24,7 @@
 #include <math.h>
 
 #include "gpp.h"
+#include "rot_iou.h"
 
 namespace {
 
@@ -32,7 +34,7 @@ constexpr int kMaxT = GPP_KITTI_MAX_THRESHOLDS;
 constexpr int kRow = GPP_POSE_COLS;
 constexpr int kLab = GPP_KITTI_LABEL_COLS;
 constexpr int kPairThreads = 64;
-constexpr int kMaxVerts = 8;
+constexpr int kMaxVerts = rot_iou::kMaxVerts;
 constexpr int kStagedPairs = 1536;                   // 4 planes * 1536 pairs * 8 bytes = 48 KB of LDS
 
 __device__ inline double dmin(double a, double b) { return a < b ? a : b; }
@@ -89,66 +91,25 @@ __global__ __launch_bounds__(kPairThreads) void kitti_overlaps_kernel(const floa
     if (isnan(dw) || isnan(dl) || isnan(dtx) || isnan(dtz) || isnan(dry) || isnan(gw) || isnan(gl) || isnan(gtx) || isnan(gtz) || isnan(gry)) {
         o_bev = nan; o_3d = nan;
     } else {
-        // corners (+,+) (-,+) (-,-) (+,-) of (l/2, w/2): counter-clockwise in (x, z), and the placement is a rotation
+        // corners (+,+) (-,+) (-,-) (+,-) of (l/2, w/2): counter-clockwise in (x, z), and the placement is a rotation (rot_iou.h)
         double gX[4], gZ[4];
         {
             const double c = cos(gry), s = sin(gry), hl = gl / 2.0, hw = gw / 2.0;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const double x = (k == 0 || k == 3) ? hl : -hl, z = (k < 2) ? hw : -hw;
-                gX[k] = c * x + s * z + gtx;
-                gZ[k] = -s * x + c * z + gtz;
-            }
+            for (int k = 0; k < 4; ++k) rot_iou::corner(k, c, s, hl, hw, gtx, gtz, gX[k], gZ[k]);
         }
         {
             const double c = cos(dry), s = sin(dry), hl = dl / 2.0, hw = dw / 2.0;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const double x = (k == 0 || k == 3) ? hl : -hl, z = (k < 2) ? hw : -hw;
-                s_x[0][k][tid] = c * x + s * z + dtx;
-                s_z[0][k][tid] = -s * x + c * z + dtz;
-            }
+            for (int k = 0; k < 4; ++k) rot_iou::corner(k, c, s, hl, hw, dtx, dtz, s_x[0][k][tid], s_z[0][k][tid]);
         }
-        int n = 4, cur = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const double ax = gX[e], az = gZ[e];
-            const double ex = gX[(e + 1) & 3] - ax, ez = gZ[(e + 1) & 3] - az;
-            int m = 0;
-            for (int i = 0; i < n; ++i) {
-                const int j = i + 1 == n ? 0 : i + 1;
-                const double px = s_x[cur][i][tid], pz = s_z[cur][i][tid];
-                const double qx = s_x[cur][j][tid], qz = s_z[cur][j][tid];
-                const double dp = ex * (pz - az) - ez * (px - ax);
-                const double dq = ex * (qz - az) - ez * (qx - ax);
-                const bool in_p = dp >= 0.0, in_q = dq >= 0.0;
-                if (in_p && m < kMaxVerts) {
-                    s_x[cur ^ 1][m][tid] = px; s_z[cur ^ 1][m][tid] = pz;
-                    ++m;
-                }
-                if (in_p != in_q && m < kMaxVerts) { // (a convex polygon gains one vertex per edge; the bound only guards the store)
-                    const double den = dq - dp;
-                    s_x[cur ^ 1][m][tid] = (px * dq - qx * dp) / den;
-                    s_z[cur ^ 1][m][tid] = (pz * dq - qz * dp) / den;
-                    ++m;
-                }
-            }
-            n = m;
-            cur ^= 1;
-        }
-        double twice = 0.0;
-        for (int i = 0; i < n; ++i) {
-            const int j = i + 1 == n ? 0 : i + 1;
-            twice = twice + (s_x[cur][i][tid] * s_z[cur][j][tid] - s_x[cur][j][tid] * s_z[cur][i][tid]);
-        }
-        const double inter = n < 3 ? 0.0 : fabs(twice) / 2.0;
+        const double inter = rot_iou::intersection<kPairThreads>(s_x, s_z, tid, gX, gZ);
         const double area_d = dl * dw, area_g = gl * gw;
         o_bev = inter / (area_d + area_g - inter);
         if (isnan(dh) || isnan(dty) || isnan(gh) || isnan(gty)) {
             o_3d = nan;
         } else {
-            double hh = dmin(dty, gty) - dmax(dty - dh, gty - gh);
-            hh = hh > 0.0 ? hh : 0.0;
+            const double hh = rot_iou::height_overlap(dty, dh, gty, gh);
             const double iv = inter * hh;
             const double vol_d = area_d * dh, vol_g = area_g * gh;
             o_3d = iv / (vol_d + vol_g - iv);

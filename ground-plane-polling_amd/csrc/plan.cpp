@@ -54,7 +54,7 @@ struct Lanes {
 };
 Lanes g_lanes_of_device[kMaxDevices];
 
-// GPP_ROCTX=1: a roctx range per stage of the plan (GPP_OP_STAGE: stem, backbone, FPN, heads, decode, polling, pose, audit) around the launches that
+// GPP_ROCTX=1: a roctx range per stage of the plan (GPP_OP_STAGE: stem, backbone, FPN, heads, decode, polling, pose, cuboid NMS, audit) around the launches that
 // gpp_plan_run enqueues for it, so that `rocprofv3 --marker-trace --kernel-trace` gives the per-stage split of a step without
 // matching kernel names.  The marker library is looked up at run time (librocprofiler-sdk-roctx.so, the one rocprofv3 listens to; libroctx64.so
 // as a fallback): the library has no link-time dependency on it, and without the variable nothing is loaded and a plan run pays one branch.
@@ -79,7 +79,7 @@ struct Roctx {
     }
 };
 const char* const kStageNames[16] = {nullptr, "gpp:stem", "gpp:backbone", "gpp:fpn", "gpp:heads", "gpp:decode", "gpp:polling", "gpp:gather",
-                                     "gpp:pose", "gpp:audit", "gpp:stage10", "gpp:stage11", "gpp:stage12", "gpp:stage13", "gpp:stage14", "gpp:stage15"};
+                                     "gpp:pose", "gpp:audit", "gpp:cuboid_nms", "gpp:stage11", "gpp:stage12", "gpp:stage13", "gpp:stage14", "gpp:stage15"};
 
 }  // namespace
 
@@ -299,6 +299,12 @@ extern "C" int gpp_plan_run(const gpp_plan_op* ops, int n_ops, void* stream, voi
             const gpp_pose_desc* d = (const gpp_pose_desc*)op.desc;
             rc = gpp_pose_f32(d->boxes, d->dims, d->scores, d->labels, d->orientations, d->keypoints, d->residuals, d->frame_info,
                               d->B, d->D, d->score_thr, d->rows, d->counts, stream);
+            break;
+        }
+        case GPP_OP_CUBOID_NMS: {
+            const gpp_cuboid_nms_desc* d = (const gpp_cuboid_nms_desc*)op.desc;
+            rc = d->reserved != 0 ? GPP_ERR_BAD_ARG
+                                  : gpp_cuboid_nms_f64(d->rows, d->B, d->D, d->metric, d->iou_thr, d->rows, d->counts, d->suppressor, stream);
             break;
         }
         case GPP_OP_ABSMAX:

@@ -153,6 +153,10 @@ def _declare(lib):
     if hasattr(lib, 'gpp_eval_match_f32'):
         lib.gpp_eval_match_f32.restype = c_int
         lib.gpp_eval_match_f32.argtypes = [c_void_p] * 8 + [c_int] * 4 + [c_float, c_int, ctypes.c_double] + [c_void_p] * 4
+    # the cuboid NMS (include/gpp.h, csrc/cuboid_nms.hip; absent from an older build named by GPP_LIB: it runs everything but cuboid_nms models)
+    if hasattr(lib, 'gpp_cuboid_nms_f64'):
+        lib.gpp_cuboid_nms_f64.restype = c_int
+        lib.gpp_cuboid_nms_f64.argtypes = [c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]
     # KITTI's object benchmark (include/gpp.h, csrc/kitti_eval.hip; absent from an older build named by GPP_LIB: it runs everything but
     # evaluate_kitti(device=True) and score_poses_on_frames)
     if hasattr(lib, 'gpp_kitti_overlaps_f64'):
@@ -490,6 +494,27 @@ def kitti_stats(rows, labels, label_counts, overlaps, min_overlap, thresholds=No
     check(lib().gpp_kitti_stats_f64(ptr(rows), ptr(labels), ptr(label_counts), ptr(overlaps), mo, ptr(thresholds), ptr(n_thresholds),
                                     B, D, A, T, None, None, ptr(stats), ptr(similarity), stream_ptr()), 'gpp_kitti_stats_f64')
     return stats, similarity
+
+
+def cuboid_nms(rows, metric, threshold, out=None, counts=None, suppressor=None):
+    """ gpp_cuboid_nms_f64 on the current stream: rows (B, D, 36) float32 on the device -- the rows of gpp_pose_f32 --, metric 0 (bird's-eye
+    view) or 1 (3-D) -> (rows_out (B, D, 36) float32, counts (B,) int32, suppressor (B, D) int32) on the device; no synchronisation.
+    out: where the rows go (default: a new tensor; `rows` itself: in place) """
+    import torch
+    if rows.dim() != 3 or rows.dtype != torch.float32 or rows.shape[2] != GPP_POSE_COLS:
+        raise ValueError('gpp_cuboid_nms_f64: rows must be (B, D, {}) float32, got {} {}'.format(GPP_POSE_COLS, tuple(rows.shape), rows.dtype))
+    B, D = int(rows.shape[0]), int(rows.shape[1])
+    dev = rows.device
+    out = torch.empty_like(rows) if out is None else out
+    counts = torch.zeros((B,), dtype=torch.int32, device=dev) if counts is None else counts
+    suppressor = torch.full((B, D), -1, dtype=torch.int32, device=dev) if suppressor is None else suppressor
+    want = ((out, torch.float32, (B, D, GPP_POSE_COLS)), (counts, torch.int32, (B,)), (suppressor, torch.int32, (B, D)))
+    for t, dtype, shape in want:
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev:
+            raise ValueError('gpp_cuboid_nms_f64: expected {} {} on {}, got {} {} on {}'.format(shape, dtype, dev, tuple(t.shape), t.dtype, t.device))
+    check(lib().gpp_cuboid_nms_f64(ptr(rows), B, D, int(metric), float(threshold), ptr(out), ptr(counts), ptr(suppressor), stream_ptr()),
+          'gpp_cuboid_nms_f64')
+    return out, counts, suppressor
 
 
 def label_prep(labels, label_counts, P, trig, det_types=0, own_box=True, detections=True):

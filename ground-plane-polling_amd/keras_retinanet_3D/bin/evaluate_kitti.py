@@ -5,6 +5,9 @@ image box, the bird's-eye-view box and the 3-D box at Easy / Moderate / Hard, an
 
     evaluate_kitti.py <label_dir> <result_dir> [--device]
         scores the result files that bin/run_network.py --kitti wrote against ORIGINAL label_2 files of the same names
+    evaluate_kitti.py <label_dir> <result_dir> --cuboid-nms {bev,3d} --cuboid-nms-threshold T [--device]
+        the same after a greedy NMS of every file's cuboids (utils/cuboid_nms.py): a threshold can be swept over
+        one result directory without running the network again
     evaluate_kitti.py <label_dir> --model <path | synthetic:seed> --images <dir> --calibs <dir> --planes <file.mat> [--batch-size N]
         runs the model on the images of the label files and scores its rows without writing them: poses, overlaps and matching on the GPU
 
@@ -23,7 +26,7 @@ if __name__ == "__main__" and __package__ is None:
 
 import numpy as np
 
-from ..utils import kitti_eval
+from ..utils import cuboid_nms, kitti_eval
 
 
 def parse_args(args):
@@ -42,7 +45,16 @@ def parse_args(args):
                         help='A match needs an overlap above it (KITTI\'s Car: 0.7 each).')
     parser.add_argument('--json', default=None, help='Where the result is written as JSON (default: <result_dir>/kitti_eval.json; '
                                                      'with --model: ./kitti_eval.json).')
+    parser.add_argument('--cuboid-nms', choices=['bev', '3d'], default=None,
+                        help='Suppress duplicate cuboids before scoring: in score order a detection is dropped when a kept one overlaps its '
+                             'cuboid by more than --cuboid-nms-threshold in the bird\'s-eye view (bev) or in 3-D (3d).  With --device on the '
+                             'GPU (csrc/cuboid_nms.hip); with --model a stage of the model\'s plan.')
+    parser.add_argument('--cuboid-nms-threshold', type=float, default=None, help='Inside (0, 1).  No default: it depends on the checkpoint.')
     parsed = parser.parse_args(args)
+    if (parsed.cuboid_nms is None) != (parsed.cuboid_nms_threshold is None):
+        parser.error('--cuboid-nms and --cuboid-nms-threshold go together: both or neither')
+    if parsed.cuboid_nms is not None and not 0.0 < parsed.cuboid_nms_threshold < 1.0:
+        parser.error('--cuboid-nms-threshold must lie inside (0, 1), got {}'.format(parsed.cuboid_nms_threshold))
     if (parsed.result_dir is None) == (parsed.model is None):
         parser.error('give either a result directory or --model')
     if parsed.model is not None and not (parsed.images and parsed.calibs and parsed.planes):
@@ -57,7 +69,8 @@ def score_model(args):
     from ..utils import gpp_utils
     from ..utils.image import compute_resize_scale, read_image_bgr
     from .run_network import group_items
-    model = models.load_model(args.model, backbone_name=args.backbone, dtype=args.dtype, pose=True)
+    model = models.load_model(args.model, backbone_name=args.backbone, dtype=args.dtype, pose=True,
+                              cuboid_nms=None if args.cuboid_nms is None else (args.cuboid_nms, args.cuboid_nms_threshold))
     plane_params = scipy.io.loadmat(args.planes)['road_planes_database']
     names = sorted(f for f in os.listdir(args.label_dir) if f.endswith('.txt'))
     chunks = []
@@ -77,13 +90,33 @@ def score_model(args):
     return kitti_eval.evaluate_chunks(chunks, args.min_overlap)
 
 
+def suppressed_rows(args):
+    """ --cuboid-nms: the rows of every result file (a missing file: no detections) after the suppression, in the order of the sorted
+    label files -- what utils.kitti_eval.evaluate_kitti takes as `rows` """
+    rows_list = []
+    for f in sorted(f for f in os.listdir(args.label_dir) if f.endswith('.txt')):
+        path = os.path.join(args.result_dir, f)
+        if not os.path.isfile(path):
+            rows_list.append(np.zeros((0, kitti_eval.POSE_COLS), np.float32))
+            continue
+        rows = kitti_eval.rows_from_results(kitti_eval.read_result_file(path))
+        if args.device and rows.shape[0]:
+            rows_list.append(cuboid_nms.suppress_rows_device(rows[None], args.cuboid_nms, args.cuboid_nms_threshold)[0][0])
+        else:
+            rows_list.append(cuboid_nms.suppress_rows_np(rows, args.cuboid_nms, args.cuboid_nms_threshold)[0])
+    return rows_list
+
+
 def main(args=None):
     args = parse_args(sys.argv[1:] if args is None else args)
     if args.model is not None:
         result = score_model(args)
         out = args.json or 'kitti_eval.json'
     else:
-        result = kitti_eval.evaluate_kitti(args.label_dir, args.result_dir, device=args.device, min_overlap=args.min_overlap)
+        if args.cuboid_nms is not None:
+            result = kitti_eval.evaluate_kitti(args.label_dir, rows=suppressed_rows(args), device=args.device, min_overlap=args.min_overlap)
+        else:
+            result = kitti_eval.evaluate_kitti(args.label_dir, args.result_dir, device=args.device, min_overlap=args.min_overlap)
         out = args.json or os.path.join(args.result_dir, 'kitti_eval.json')
     print(kitti_eval.summary_table(result))
     with open(out, 'w') as f:

@@ -38,7 +38,7 @@ import numpy as np
 import scipy.io
 
 from .. import models
-from ..utils import gpp_utils, visualization
+from ..utils import cuboid_nms, gpp_utils, visualization
 from ..utils.image import compute_resize_scale, preprocess_image, read_image_bgr, resize_image
 
 
@@ -69,7 +69,17 @@ def parse_args(args):
                         help='Audit the lower range of --dtype f16x3 (not in the reference CLI): the model is loaded with range_audit=True, a '
                              'call whose run left a whole conv-operand map below 2^-9 is answered by the float32 twin, and at the end the five '
                              'smallest maps are printed and <output_dir>/<model name>/range_audit.json is written (per map, the minimum over all calls).')
+    parser.add_argument('--cuboid-nms', choices=['bev', '3d'], default=None,
+                        help='Suppress duplicate cuboids (not in the reference CLI): in score order a detection is dropped when a kept one overlaps '
+                             'its cuboid by more than --cuboid-nms-threshold in the bird\'s-eye view (bev) or in 3-D (3d).  With --device-pose a '
+                             'stage of the plan on the GPU (cuboid_nms=(metric, threshold)), otherwise applied on the host before the results are written.')
+    parser.add_argument('--cuboid-nms-threshold', type=float, default=None,
+                        help='The overlap above which --cuboid-nms drops a detection, inside (0, 1).  No default: it depends on the checkpoint.')
     parsed = parser.parse_args(args)
+    if (parsed.cuboid_nms is None) != (parsed.cuboid_nms_threshold is None):
+        parser.error('--cuboid-nms and --cuboid-nms-threshold go together: both or neither')
+    if parsed.cuboid_nms is not None and not 0.0 < parsed.cuboid_nms_threshold < 1.0:
+        parser.error('--cuboid-nms-threshold must lie inside (0, 1), got {}'.format(parsed.cuboid_nms_threshold))
     if parsed.range_audit and parsed.dtype != 'f16x3':
         parser.error('--range-audit audits the IEEE-half pairs of --dtype f16x3, not {}'.format(parsed.dtype))
     return parsed
@@ -128,6 +138,8 @@ def write_results_from_rows(args, output_dir, item, rows_b, count, picture=None)
     """ write_results for one image's rows of the device pose stage (model.predict_poses_on_batch); picture: its composite, rendered on the
     device (model.predict_composites_on_frames) """
     stem = os.path.basename(item['image_fp'])[:-3]
+    if args.cuboid_nms is not None:
+        rows_b = cuboid_nms.live_first(rows_b)      # (a suppressed row is padding between the kept ones; count = the kept ones)
     det = gpp_utils.detections_from_rows(rows_b, count)
     outputs = {'boxes': det['boxes'][:, :4], 'keypoints': det['boxes'][:, 4:], 'labels': det['labels'], 'scores': det['scores'],
                'locations': det['locations'], 'angles': det['angles'], 'dimensions': det['dimensions'], 'residuals': det['residuals']}
@@ -160,7 +172,8 @@ def main(args=None):
         args = sys.argv[1:]
     args = parse_args(args)
 
-    model = models.load_model(args.model_path, backbone_name=args.backbone, dtype=args.dtype, pose=args.device_pose, range_audit=args.range_audit)
+    model = models.load_model(args.model_path, backbone_name=args.backbone, dtype=args.dtype, pose=args.device_pose, range_audit=args.range_audit,
+                              cuboid_nms=(args.cuboid_nms, args.cuboid_nms_threshold) if args.device_pose and args.cuboid_nms is not None else None)
     audit = {}               # --range-audit: per map, the report of the call that left it smallest
     plane_params = scipy.io.loadmat(args.plane_params_path)['road_planes_database']
     output_dir = make_output_tree(args)
@@ -201,6 +214,8 @@ def main(args=None):
                 print("Image {}: frame rate: {:.2f}".format(j, len(group) / dt))
                 j += 1
                 det = gpp_utils.recover_pose(gpp_utils.select_detections(outputs, it['scale'], image_index=k))
+                if args.cuboid_nms is not None:
+                    det, _ = cuboid_nms.suppress_detections(det, args.cuboid_nms, args.cuboid_nms_threshold)
                 write_results(args, output_dir, it, det)
 
 

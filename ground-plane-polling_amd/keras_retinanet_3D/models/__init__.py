@@ -52,7 +52,7 @@ def backbone(backbone_name):
 
 
 def load_model(filepath, backbone_name='resnet50', convert=False, nms=True, class_specific_filter=True,
-               orientation_specific_filter=False, dtype=None, on_range_event=None, plan=None, pose=False, range_audit=False):
+               orientation_specific_filter=False, dtype=None, on_range_event=None, plan=None, pose=False, range_audit=False, cuboid_nms=None):
     """ Loads a RetinaNet-3D inference model (reference models/__init__.py:59-88).
 
     `convert` is accepted for signature compatibility: every model this function returns already
@@ -88,6 +88,11 @@ def load_model(filepath, backbone_name='resnet50', convert=False, nms=True, clas
     `pose` (not in the reference; default False): the plan ends with the pose stage (gpp_pose_f32: what bin/run_network.py does on the host
     after predict_on_batch, on the device) and the model has predict_poses_on_batch / predict_poses_on_frames, which return one
     (B, 100, 36) table of rows (include/gpp.h) and the number of detections per image.  predict_on_batch is unchanged either way.
+    `cuboid_nms` (not in the reference; default None; needs pose=True): a pair (metric, threshold), metric 'bev' or '3d' -- the plan ends
+    with one more op, a greedy NMS of the cuboids themselves on the pose rows (gpp_cuboid_nms_f64): in score order
+    a row is dropped when a kept row overlaps it by more than the threshold in the bird's-eye view ('bev') or in 3-D ('3d').  Every reader of
+    the rows (predict_poses_*, score_poses_on_frames, predict_composites_on_frames) sees the suppressed set; model.cuboid_suppressors()
+    says which row removed which.  There is no default threshold: it depends on the checkpoint.  predict_on_batch is unchanged.
     """
     import os
     if dtype is None:
@@ -104,7 +109,8 @@ def load_model(filepath, backbone_name='resnet50', convert=False, nms=True, clas
     else:
         w = W.load_weights(filepath)
     model = RetinaNet3D(w, backbone_name=name, dtype=dtype, nms=nms, class_specific_filter=class_specific_filter,
-                        orientation_specific_filter=orientation_specific_filter, on_range_event=on_range_event, plan=plan, pose=pose, range_audit=range_audit)
+                        orientation_specific_filter=orientation_specific_filter, on_range_event=on_range_event, plan=plan, pose=pose, range_audit=range_audit,
+                        cuboid_nms=cuboid_nms)
     if convert:
         model.summary()
     return model

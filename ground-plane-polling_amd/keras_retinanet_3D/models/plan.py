@@ -65,6 +65,11 @@ class PoseDesc(ctypes.Structure):
                [('B', ctypes.c_int32), ('D', ctypes.c_int32), ('score_thr', ctypes.c_float), ('reserved', ctypes.c_int32)]
 
 
+class CuboidNmsDesc(ctypes.Structure):
+    _fields_ = [('rows', ctypes.c_void_p), ('counts', ctypes.c_void_p), ('suppressor', ctypes.c_void_p), ('iou_thr', ctypes.c_double),
+                ('B', ctypes.c_int32), ('D', ctypes.c_int32), ('metric', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
 class PreactDesc(ctypes.Structure):
     _fields_ = [('conv', ctypes.c_void_p), ('in_scale', ctypes.c_void_p), ('in_shift', ctypes.c_void_p)]
 
@@ -99,6 +104,7 @@ OP_STEM_POOL = 13
 OP_MAXPOOL_PAD, OP_AVGPOOL, OP_CONV_PREACT = 17, 18, 32         # DenseNet (include/gpp.h)
 OP_MOBILENET_STEM, OP_MOBILENET_BLOCK = 33, 34                  # MobileNet (include/gpp.h)
 OP_POSE = 19                                                    # RetinaNet3D(pose=True): gpp_pose_f32 behind the polling
+OP_CUBOID_NMS = 20                                              # RetinaNet3D(pose=True, cuboid_nms=(metric, threshold)): gpp_cuboid_nms_f64 behind the pose stage
 OP_ABSMAX, OP_ABSMAX_CLEAR = 35, 36                             # RetinaNet3D(range_audit=True): gpp_channel_absmax behind every audited map
 OP_STEM_RAGGED, OP_STEM_POOL_RAGGED, OP_MAXPOOL_RAGGED = 37, 38, 39    # ragged plans (plan_for(..., ragged=True)): per-image heights from a device table
 OP_DETECT_CANDIDATE_PIXELS = 40                                 # OP_DETECT_CANDIDATES + gpp_detect_pixel_lists (sparse head outputs)
@@ -495,7 +501,7 @@ class Plan(object):
 
     @staticmethod
     def stage_of(kind, name):
-        """ include/gpp.h GPP_OP_STAGE: 1 stem, 2 backbone, 3 FPN, 4 heads, 5 decode, 6 polling, 8 pose, 9 audit (roctx ranges under GPP_ROCTX=1) """
+        """ include/gpp.h GPP_OP_STAGE: 1 stem, 2 backbone, 3 FPN, 4 heads, 5 decode, 6 polling, 8 pose, 9 audit, 10 cuboid NMS (roctx ranges under GPP_ROCTX=1) """
         if kind in (OP_STEM, OP_MAXPOOL, OP_STEM_POOL, OP_MAXPOOL_PAD, OP_MOBILENET_STEM, OP_STEM_RAGGED, OP_STEM_POOL_RAGGED, OP_MAXPOOL_RAGGED):
             return 1
         if kind in DETECT_OPS:
@@ -504,6 +510,8 @@ class Plan(object):
             return 6
         if kind == OP_POSE:
             return 8
+        if kind == OP_CUBOID_NMS:
+            return 10
         if kind in (OP_ABSMAX, OP_ABSMAX_CLEAR):
             return 9
         if name.startswith('res') or kind in (OP_CONV_PREACT, OP_AVGPOOL, OP_MOBILENET_BLOCK) or name.startswith(('conv2_', 'conv3_', 'conv4_', 'conv5_')):

@@ -39,14 +39,15 @@ from ..layers import conv as C
 from ..layers import mobilenet as M
 from ..layers.filter_detections import MAX_DETECTIONS, NMS_THRESHOLD, SCORE_THRESHOLD
 from ..utils import anchors as anchor_utils
+from ..utils import cuboid_nms as cuboid_nms_utils
 from ..utils.gpp_utils import POLL_THRESHOLD, POSE_SCORE_THRESHOLD
 from . import weights as W
 # what a plan is (models/plan.py), under the names this module has always had: tests and tools spell them retinanet.StemDesc, retinanet.OP_CONV ...
-from .plan import (BlockDesc, BlockProjDesc, FUSE_INPROJ_MIN_ROUNDS, CandidatePixelsDesc, DensePoolDesc, DetectDesc, PlanOp, PollDesc, PoolDesc, PoseDesc,  # noqa: F401
+from .plan import (BlockDesc, BlockProjDesc, FUSE_INPROJ_MIN_ROUNDS, CandidatePixelsDesc, DensePoolDesc, DetectDesc, PlanOp, PollDesc, PoolDesc, PoseDesc, CuboidNmsDesc,  # noqa: F401
                    PreactDesc, RaggedPoolDesc, RaggedStemDesc, ReluDesc, StemDesc, TailDesc,
                    OP_STEM, OP_MAXPOOL, OP_CONV, OP_RELU, OP_DETECT, OP_POLL, OP_TAIL, OP_BLOCK,
                    OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT, OP_DETECT_OSF, OP_STEM_POOL,
-                   OP_MAXPOOL_PAD, OP_AVGPOOL, OP_CONV_PREACT, OP_MOBILENET_STEM, OP_MOBILENET_BLOCK, OP_POSE,
+                   OP_MAXPOOL_PAD, OP_AVGPOOL, OP_CONV_PREACT, OP_MOBILENET_STEM, OP_MOBILENET_BLOCK, OP_POSE, OP_CUBOID_NMS,
                    OP_ABSMAX, OP_ABSMAX_CLEAR, OP_STEM_RAGGED, OP_STEM_POOL_RAGGED, OP_MAXPOOL_RAGGED,
                    OP_DETECT_CANDIDATE_PIXELS, DETECT_OPS, OP_JOIN, OP_SYNC,
                    PlanOptions, block_form, part_of, TOWER_SLICES, RANGE_AUDIT_THRESHOLD, X3_QUANTUM,
@@ -58,7 +59,8 @@ class RetinaNet3D(object):
     """ Inference model: ResNet-50/101/152, DenseNet-121/169/201 or MobileNet (v1) + FPN + heads + decode + ground-plane polling. """
 
     def __init__(self, weights, backbone_name='resnet50', dtype='f16x3', nms=True, class_specific_filter=True,
-                 orientation_specific_filter=False, name='retinanet-bbox', on_range_event=None, plan=None, pose=False, range_audit=False):
+                 orientation_specific_filter=False, name='retinanet-bbox', on_range_event=None, plan=None, pose=False, range_audit=False,
+                 cuboid_nms=None):
         import torch
         # range_audit=True (dtype='f16x3' only): every plan also measures the largest |x| of every channel of every map an x3 convolution
         # reads (gpp_channel_absmax, _audit), and a synchronous call whose run left a whole map below RANGE_AUDIT_THRESHOLD reacts as
@@ -74,6 +76,14 @@ class RetinaNet3D(object):
         # pose=True: every plan ends with the pose stage (gpp_pose_f32 on the polling outputs) and predict_poses_on_batch /
         # predict_poses_on_frames fetch its rows; a model attribute, not a plan switch: without it every plan is what it was
         self.pose = bool(pose)
+        # cuboid_nms=(metric, threshold), metric 'bev' or '3d' (pose=True only): every plan ends with ONE more op behind the pose stage,
+        # gpp_cuboid_nms_f64 in place on the pose rows -- a greedy NMS of the cuboids themselves; every reader
+        # of the rows sees the suppressed set, cuboid_suppressors() says which row removed which.  A model attribute like `pose`; there
+        # is no default threshold
+        self.cuboid_nms = cuboid_nms_utils.check_option(cuboid_nms)
+        if self.cuboid_nms is not None and not self.pose:
+            raise ValueError('cuboid_nms={!r} suppresses pose rows: it needs pose=True'.format(cuboid_nms))
+        self._answered = None                # (model, plan) that answered the last call of the pose family
         # 'throughput' | 'latency' (models.load_model): which layers split their K loop (layers/conv.latency_split)
         self.plan_mode = plan or os.environ.get('GPP_PLAN', 'throughput')
         if self.plan_mode not in ('throughput', 'latency'):
@@ -723,6 +733,16 @@ class RetinaNet3D(object):
         plan.emit(OP_POSE, pd, 'recover_pose', [plan.boxes, plan.dimensions, plan.scores, plan.labels, plan.orientations, plan.keypoints,
                                                 plan.residuals, plan.frame_info], [plan.pose_rows, plan.pose_counts])
 
+    def _cuboid_nms(self, plan, B):
+        """ cuboid_nms=(metric, threshold): the greedy NMS of the cuboids (gpp_cuboid_nms_f64) on lane 0 behind the pose op, in place on
+        its rows and counts; plan.pose_suppressor (B, D) int32 names the kept row that removed each suppressed one """
+        metric, threshold = self.cuboid_nms
+        D = MAX_DETECTIONS
+        plan.pose_suppressor = self.torch.full((B, D), -1, dtype=self.torch.int32, device=self.device)
+        nd = CuboidNmsDesc(plan.pose_rows.data_ptr(), plan.pose_counts.data_ptr(), plan.pose_suppressor.data_ptr(), threshold, B, D,
+                           cuboid_nms_utils.metric_code(metric), 0)
+        plan.emit(OP_CUBOID_NMS, nd, 'suppress_cuboids', [plan.pose_rows], [plan.pose_rows, plan.pose_counts, plan.pose_suppressor])
+
     def _audit(self, plan):
         """ range_audit=True: one gpp_channel_absmax launch behind every launch that writes (a part, a level or a channel slice of) a map
         that some convolution of the plan reads as its activation operand or adds as its residual -- the maps an x3 loop splits into
@@ -953,6 +973,8 @@ class RetinaNet3D(object):
         self._poll(plan, B, n_planes, planes_batched)
         if self.pose:
             self._pose(plan, B)
+        if self.cuboid_nms is not None:
+            self._cuboid_nms(plan, B)
         if self.audit:
             self._audit(plan)
         self._bind_workspaces(plan)
@@ -1384,6 +1406,7 @@ class RetinaNet3D(object):
         """ the result of the plan's run for the call `what`: the reader's, unless an activation of the run left the half range or (an
         audit model; looked at only when the range held) a whole map sits below it -- then what _range_event returns """
         result, count = reader(self, plan)
+        self._answered = (self, plan)
         event = self.watches_range() and self.note_range(plan, count)
         flagged = [] if event else self._audit_flags(plan)
         if event or flagged:
@@ -1412,6 +1435,7 @@ class RetinaNet3D(object):
         if self.pose:
             twin_plan.frame_info.copy_(plan.frame_info)          # (what put_frame_info gave the call, or the plan's default)
         twin.run_plan(twin_plan)
+        self._answered = (twin, twin_plan)
         return reader(twin, twin_plan)[0]
 
     def prepare_fallback(self, B=None, H=None, Wd=None, n_planes=None, planes_batched=True, ragged=False):
@@ -1424,7 +1448,7 @@ class RetinaNet3D(object):
         if self._twin is None:
             self._twin = RetinaNet3D(self._weights, backbone_name=self.backbone_name, dtype='f32', nms=self.nms,
                                      class_specific_filter=self.class_specific_filter, orientation_specific_filter=self.osf,
-                                     name=self.name + '-f32-twin', plan=self.plan_mode, pose=self.pose)
+                                     name=self.name + '-f32-twin', plan=self.plan_mode, pose=self.pose, cuboid_nms=self.cuboid_nms)
             self._weights = None
         if B is not None:
             self._twin.plan_for(B, H, Wd, n_planes, planes_batched, ragged=ragged)
@@ -1656,6 +1680,16 @@ class RetinaNet3D(object):
             return [tuple(int(v) for v in f.shape[:2]) for f in frames_u8]
         return [tuple(int(v) for v in frames_u8.shape[1:3])] * int(frames_u8.shape[0])
 
+    def cuboid_suppressors(self):
+        """ cuboid_nms=(metric, threshold): the (B, 100) int32 suppressor table of the last answered call -- for every row the index of
+        the kept row that removed it, -1 for kept rows and padding (include/gpp.h, gpp_cuboid_nms_f64); the float32 twin's when it
+        answered the call.  One copy (synchronises). """
+        if self.cuboid_nms is None:
+            raise hip.GppError('this model has no cuboid NMS stage: load it with pose=True, cuboid_nms=(metric, threshold)')
+        if self._answered is None:
+            raise hip.GppError('cuboid_suppressors: no call has been answered yet')
+        return self._answered[1].pose_suppressor.cpu().numpy()
+
     def fetch_poses(self, plan, what='predict_poses_on_batch'):
         """ (rows (B, 100, 36) float32, counts (B,) int32) of the plan's last run, as fetch returns the 8 arrays: one copy (synchronises);
         the float32 twin's after a range event """
@@ -1676,7 +1710,10 @@ class RetinaNet3D(object):
         scales: the image scale of every image (or one for all); image_shapes: the raw images' (height, width[, 3]) (or one for all).
         Returns (rows (B, 100, 36) float32 -- include/gpp.h, gpp_pose_f32 --, counts (B,) int32: the detections above the score
         threshold, which are the first counts[b] rows of image b).  utils.gpp_utils.detections_from_rows / kitti_lines_from_rows
-        turn one image's rows into the dict of recover_pose / the KITTI text. """
+        turn one image's rows into the dict of recover_pose / the KITTI text.
+        A cuboid_nms model: the rows a kept row suppressed are -1 throughout WHERE THEY STOOD (no compaction) and counts[b] is the number
+        of kept rows -- the detections are the rows whose column 14 is >= 0; utils.cuboid_nms.live_first moves them to the front for the
+        two readers above. """
         self._require_pose()
         plan = self.stage_inputs(inputs) if heights is None else self.stage_canvas(inputs, heights)      # (heights: inputs[0] is a ragged canvas)
         self.put_frame_info(plan, scales, image_shapes)

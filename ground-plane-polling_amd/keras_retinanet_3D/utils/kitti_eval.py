@@ -120,6 +120,32 @@ def _corners(l, w, tx, tz, ry):
     return c[:, None] * xs + s[:, None] * zs + tx[:, None], -s[:, None] * xs + c[:, None] * zs + tz[:, None]
 
 
+def rect_intersections(dl, dw, dtx, dtz, dry, gl, gw, gtx, gtz, gry):
+    """ the area of the intersection of N pairs of rotated rectangles in the (X, Z) plane, (N,) float64 each: the d rectangle clipped
+    against the four edges of the g rectangle, then the area sum (csrc/rot_iou.h; utils/cuboid_nms.py shares it).  No NaN operand. """
+    N = dl.shape[0]
+    gX, gZ = _corners(gl, gw, gtx, gtz, gry)
+    X, Z = np.zeros((N, 8)), np.zeros((N, 8))
+    X[:, :4], Z[:, :4] = _corners(dl, dw, dtx, dtz, dry)
+    n = np.full(N, 4, np.int64)
+    for e in range(4):
+        ax, az = gX[:, e], gZ[:, e]
+        X, Z, n = _clip(X, Z, n, ax, az, gX[:, (e + 1) & 3] - ax, gZ[:, (e + 1) & 3] - az)
+    twice = np.zeros(N)
+    idx = np.arange(N)
+    for i in range(int(n.max())):
+        j = np.where(i + 1 == n, 0, i + 1) % 8
+        twice = twice + np.where(i < n, X[:, i] * Z[idx, j] - X[idx, j] * Z[:, i], 0.0)
+    return np.where(n < 3, 0.0, np.abs(twice) / 2.0)
+
+
+def height_overlaps(dty, dh, gty, gh):
+    """ the height term of the 3-D overlap: max(0, min(y_d, y_g) - max(y_d - h_d, y_g - h_g)) """
+    lo = np.where(dty - dh > gty - gh, dty - dh, gty - gh)
+    hh = np.where(dty < gty, dty, gty) - lo
+    return np.where(hh > 0.0, hh, 0.0)
+
+
 def image_overlaps(rows, labels):
     """ rows (D, 36) float32, labels (A, 16) float64 -> (4, D, A) float64: image IoU, BEV IoU, 3-D IoU, image intersection over the
     detection's area.  Rows that are no detection (column 14 < 0) give 0. """
@@ -153,26 +179,12 @@ def image_overlaps(rows, labels):
         ok = np.flatnonzero(live & ~bad_bev)
         inter = np.zeros(D * A)
         if ok.size:
-            gX, gZ = _corners(gl[ok], gw[ok], gtx[ok], gtz[ok], gry[ok])
-            X, Z = np.zeros((ok.size, 8)), np.zeros((ok.size, 8))
-            X[:, :4], Z[:, :4] = _corners(dl[ok], dw[ok], dtx[ok], dtz[ok], dry[ok])
-            n = np.full(ok.size, 4, np.int64)
-            for e in range(4):
-                ax, az = gX[:, e], gZ[:, e]
-                X, Z, n = _clip(X, Z, n, ax, az, gX[:, (e + 1) & 3] - ax, gZ[:, (e + 1) & 3] - az)
-            twice = np.zeros(ok.size)
-            idx = np.arange(ok.size)
-            for i in range(int(n.max())):
-                j = np.where(i + 1 == n, 0, i + 1) % 8
-                twice = twice + np.where(i < n, X[:, i] * Z[idx, j] - X[idx, j] * Z[:, i], 0.0)
-            inter[ok] = np.where(n < 3, 0.0, np.abs(twice) / 2.0)
+            inter[ok] = rect_intersections(dl[ok], dw[ok], dtx[ok], dtz[ok], dry[ok], gl[ok], gw[ok], gtx[ok], gtz[ok], gry[ok])
         area_d, area_g = dl * dw, gl * gw
         o_bev = inter / (area_d + area_g - inter)
         o_bev[bad_bev] = np.nan
         bad_3d = bad_bev | np.isnan(np.stack([dh, dty, gh, gty])).any(axis=0)
-        lo = np.where(dty - dh > gty - gh, dty - dh, gty - gh)
-        hh = np.where(dty < gty, dty, gty) - lo
-        hh = np.where(hh > 0.0, hh, 0.0)
+        hh = height_overlaps(dty, dh, gty, gh)
         iv = inter * hh
         o_3d = iv / (area_d * dh + area_g * gh - iv)
         o_3d[bad_3d] = np.nan

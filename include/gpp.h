@@ -709,6 +709,40 @@ int gpp_kitti_stats_f64(const float* rows, const double* labels, const int32_t* 
                         float* tp_scores, int32_t* n_gt, int32_t* stats, double* similarity, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Suppression of duplicate cuboids on the device (csrc/cuboid_nms.hip; DESIGN.md section 4.26 is the specification,
+ * utils/cuboid_nms.py the host form): a greedy non-maximum suppression of the rows of gpp_pose_f32 by the overlap of the cuboids
+ * themselves -- in the bird's-eye view or in 3-D -- where the decode's NMS judges image rectangles.  One launch, one workgroup per image.
+ *
+ *   rows_in, rows_out (B, D, GPP_POSE_COLS) float32, device: the rows of gpp_pose_f32.  rows_out == rows_in is allowed (the form a plan
+ *   uses); otherwise the two do not overlap.  A workgroup reads all it needs of its image before it writes any of it.
+ *   live        a row is live iff its column 14 is >= 0.
+ *   rank        live rows by (column 12 descending, row index ascending), computed here: the rows need not arrive sorted (rows built
+ *               from labels all score 1).  A NaN score ranks as -infinity.
+ *   overlap     of the live rows i < j: row i in the place of gpp_kitti_overlaps_f64's detection, row j in the place of its label --
+ *               the fields w 17, l 18, x 19, z 21, r_y 32 (3-D also h 30, y 31), the same corner order, placement, clipping (row i's
+ *               rectangle against row j's edges), area sum and height term, operation for operation (csrc/rot_iou.h); overlap(j, i) is
+ *               overlap(i, j).  A NaN operand gives a NaN overlap, which suppresses nothing and is suppressed by nothing.
+ *   metric      GPP_CUBOID_NMS_BEV: plane 1 of gpp_kitti_overlaps_f64; GPP_CUBOID_NMS_3D: plane 2.
+ *   greedy      in rank order a row is kept iff no already KEPT row overlaps it by more than iou_thr (strict); a suppressed row
+ *               suppresses nothing.
+ *   rows_out    a suppressed row is -1 in all its columns -- the padding every reader skips; kept rows and padding rows are copied bit
+ *               for bit (in place: left alone).
+ *   counts (B) int32: the kept rows of image b.
+ *   suppressor (B, D) int32: the row index of the kept row that removed row d -- of several, the first in rank order; -1 for kept rows
+ *               and padding rows.
+ *
+ *   A pair whose centres lie further apart than the sum of the two half-diagonals times 1 + 1/32 has an empty intersection and is not
+ *   clipped; the gate changes no overlap (section 4.26 has the argument).
+ *   D <= GPP_KITTI_MAX_DETECTIONS (the kept set is a 128-bit mask, as the assigned set of gpp_kitti_stats_f64), beyond:
+ *   GPP_ERR_UNSUPPORTED.  iou_thr outside (0, 1) or NaN, a metric other than the two: GPP_ERR_BAD_ARG.  Null pointer or negative size:
+ *   GPP_ERR_BAD_ARG, nothing launched.  B * D == 0: GPP_OK, nothing launched.
+ * ---------------------------------------------------------------------------------------- */
+#define GPP_CUBOID_NMS_BEV 0
+#define GPP_CUBOID_NMS_3D 1
+int gpp_cuboid_nms_f64(const float* rows_in, int B, int D, int metric, double iou_thr,
+                       float* rows_out, int32_t* counts, int32_t* suppressor, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * KITTI keypoint ("mod") labels on the device (csrc/label_prep.hip; DESIGN.md section 4.18 is the specification, utils/label_prep.py the
  * host form): what the reference's label_prep/create_mod_labels.m, computeBox3D.m and projectToImage.m make of a label_2 row and the
  * camera-2 matrix -- the 20 fields that bin/evaluate.py and KittiGenerator read.  Parity with MATLAB itself is UNPINNED.  One launch,
@@ -1032,6 +1066,7 @@ int gpp_absmax_clear(uint32_t* table, int64_t n, void* stream);
 #define GPP_OP_MAXPOOL_PAD 17            /* gpp_dense_pool_desc -> gpp_maxpool3x3s2_pad_f32 (DenseNet pool1) */
 #define GPP_OP_AVGPOOL 18                /* gpp_dense_pool_desc -> gpp_avgpool2x2_f32 (DenseNet transitions) */
 #define GPP_OP_POSE 19                   /* gpp_pose_desc -> gpp_pose_f32 (opt-in: RetinaNet3D(pose=True)) */
+#define GPP_OP_CUBOID_NMS 20             /* gpp_cuboid_nms_desc -> gpp_cuboid_nms_f64 behind GPP_OP_POSE (opt-in: RetinaNet3D(pose=True, cuboid_nms=(metric, threshold))) */
 #define GPP_OP_CONV_PREACT 32            /* gpp_preact_desc -> gpp_conv2d_preact (DenseNet); kinds 0..255 exist */
 #define GPP_OP_MOBILENET_STEM 33         /* gpp_mobilenet_stem_desc -> gpp_mobilenet_stem */
 #define GPP_OP_MOBILENET_BLOCK 34        /* gpp_mobilenet_block_desc -> gpp_mobilenet_block */
@@ -1056,7 +1091,7 @@ int gpp_absmax_clear(uint32_t* table, int64_t n, void* stream);
 #define GPP_OP_SYNC 0x20000
 
 /* Optional stage label of an op, bits 20-23 of `kind`: with GPP_ROCTX=1 in the environment gpp_plan_run opens a roctx range ("gpp:stem", "gpp:backbone",
-   "gpp:fpn", "gpp:heads", "gpp:decode", "gpp:polling", "gpp:pose") around each run of consecutive ops with the same label (rocprofv3 --marker-trace); 0 = none.
+   "gpp:fpn", "gpp:heads", "gpp:decode", "gpp:polling", "gpp:pose", "gpp:cuboid_nms") around each run of consecutive ops with the same label (rocprofv3 --marker-trace); 0 = none.
    The marker library is looked up at run time; without the variable nothing is loaded.  GPP_ROCTX=2 additionally synchronises the device where a range opens and
    closes: a range's duration in the marker trace is then its stage's time on the device (tools/roctx_stages.sh); a measuring mode, not a production one. */
 #define GPP_OP_STAGE(s) (((s) & 15) << 20)
@@ -1068,6 +1103,7 @@ int gpp_absmax_clear(uint32_t* table, int64_t n, void* stream);
 #define GPP_STAGE_POLLING 6
 #define GPP_STAGE_POSE 8
 #define GPP_STAGE_AUDIT 9                /* "gpp:audit": the GPP_OP_ABSMAX launches of an audit plan */
+#define GPP_STAGE_CUBOID_NMS 10          /* "gpp:cuboid_nms": the GPP_OP_CUBOID_NMS launch behind the pose stage */
 
 typedef struct gpp_stem_desc { const float* in; const void* weight; const float* bias; void* out;
                                int32_t dtype, B, H, W; uint64_t* range_counter; /* GPP_F16X3: see gpp_stem_conv7x7_bn_relu_x3_rc; NULL otherwise */
@@ -1101,6 +1137,13 @@ typedef struct gpp_pose_desc {
     int32_t B, D;
     float score_thr; int32_t reserved;
 } gpp_pose_desc;
+
+/* in place on the pose op's rows and counts: rows = gpp_pose_desc.rows, counts = gpp_pose_desc.counts */
+typedef struct gpp_cuboid_nms_desc {
+    float* rows; int32_t* counts; int32_t* suppressor;
+    double iou_thr;
+    int32_t B, D, metric, reserved;
+} gpp_cuboid_nms_desc;
 
 typedef struct gpp_tail_desc { const gpp_conv_desc* conv3x3; const gpp_conv_desc* conv1x1; int32_t tile_rows, reserved; } gpp_tail_desc;
 /* form: 0 = the three layers (the shortcut is conv1x1_c->residual); 1 = the record is a gpp_block_proj_desc (the same fields, then the fourth layer) */
