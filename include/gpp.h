@@ -124,6 +124,12 @@ int gpp_poll_f32(const float* boxes, const float* dims, const int32_t* orient, c
  * Padding is explicit (pad_top, pad_left); bottom/right padding is implied by H_out/W_out
  * (this covers Keras 'same' at stride 1, TF's asymmetric 'same' at stride 2, and
  * ZeroPadding2D + 'valid').  Every input map and the weight tensor must be smaller than 2 GiB.
+ * Supported and tested geometry: KH, KW each in 1..8 (square or not, odd or even; 9 and up is GPP_ERR_UNSUPPORTED), any
+ * pad_top / pad_left >= 0 -- beyond K/2 and beyond the map's size included -- stride 1 or 2, any H_out / W_out >= 1: an output
+ * pixel none of whose taps lands on the map is act(bias).  Every tile code an element type owns computes every such layer with the
+ * bits of the default tile or refuses it for its own documented reason (tests/test_conv_geometry_gpu.py, ..._cpu.py: kernels from
+ * 1x7 / 7x1 to 8x8 against a float64 convolution, split-K, the dual / mixed grids and the gathered forms included).  Negative pads
+ * and strides above 2 are not supported.
  * ---------------------------------------------------------------------------------------- */
 #define GPP_MAX_GROUPS 5
 
