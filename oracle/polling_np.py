@@ -73,11 +73,12 @@ def back_project(boxes, P_inv):
     return d * np.sign(d[..., 2:3])                   # (B, D, 4, 3)
 
 
-def poll(P0, P1, target):
-    """ fit_road_planes.py:18-32. """
+def poll(P0, P1, target, threshold=POLL_THRESHOLD):
+    """ fit_road_planes.py:18-32.  (The reference's threshold is the constant 0.7; the kernel and the C restatement take it as
+    an argument, so this one does too.) """
     dist = _norm3(P0 - P1)
     res = np.abs(dist - target)
-    votes = np.where(res > POLL_THRESHOLD, F(0.0), F(1.0)).astype(F)
+    votes = np.where(res > F(threshold), F(0.0), F(1.0)).astype(F)
     return votes, res
 
 
@@ -121,11 +122,9 @@ def poll_targets(dimensions, orientations):
 POLL_SEGMENTS = [(1, 3), (0, 1), (1, 2), (0, 2), (0, 3), (2, 3)]   # fit_road_planes.py:95-109
 
 
-def fit_road_planes(boxes, dimensions, orientations, P_inv, planes, return_index=False):
-    """ Same arguments and outputs as the reference fit_road_planes (fit_road_planes.py:49-139):
-    keypoints (B, D, 4, 3), keyplanes (B, D, 1, 4), residuals (B, D), all float32.
-    With return_index=True also the selected plane index (B, D) int64, which the
-    reference computes (:119) but never returns. """
+def poll_table(boxes, dimensions, orientations, P_inv, planes, threshold=POLL_THRESHOLD):
+    """ Everything the selection reads, before any masking (fit_road_planes.py:75-111): canonical planes (B, N, 4), hypotheses
+    X (B, D, N, 4, 3), zc, votes and residual sums (B, D, N).  planes (B, N, 4). """
     planes_c = canonical_planes(planes)
     rays = back_project(boxes, P_inv)
     X, zc = hypotheses(rays, planes_c)
@@ -133,9 +132,18 @@ def fit_road_planes(boxes, dimensions, orientations, P_inv, planes, return_index
     votes = None
     residuals = None
     for (a, b), t in zip(POLL_SEGMENTS, targets):
-        v, r = poll(X[..., a, :], X[..., b, :], t[..., None])
+        v, r = poll(X[..., a, :], X[..., b, :], t[..., None], threshold)
         votes = v if votes is None else votes + v
         residuals = r if residuals is None else residuals + r
+    return planes_c, X, zc, votes, residuals
+
+
+def fit_road_planes(boxes, dimensions, orientations, P_inv, planes, return_index=False, threshold=POLL_THRESHOLD):
+    """ Same arguments and outputs as the reference fit_road_planes (fit_road_planes.py:49-139):
+    keypoints (B, D, 4, 3), keyplanes (B, D, 1, 4), residuals (B, D), all float32.
+    With return_index=True also the selected plane index (B, D) int64, which the
+    reference computes (:119) but never returns. """
+    planes_c, X, zc, votes, residuals = poll_table(boxes, dimensions, orientations, P_inv, planes, threshold)
     vmax = votes.max(axis=2, keepdims=True)
     residuals = np.where(votes - vmax < 0, MASK_SENTINEL, residuals)
     residuals = np.where(zc < 0, MASK_SENTINEL, residuals).astype(F)

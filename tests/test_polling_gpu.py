@@ -65,7 +65,11 @@ def test_hip_polling_per_image_databases_differ(oracle_lib):
 
 
 def test_hip_polling_adversarial_ties_and_sentinels(oracle_lib):
-    """ duplicated planes (first index must win), planes reversed, tiny databases (N < 64 lanes) """
+    """ duplicated planes (first index must win), planes reversed, tiny databases (N < 64 lanes), all at N <= 350: the 1-plane form only.
+    Of the 66 rows of a database the 10 degenerate ones leave `rmin < 100 -> imin`: the swapped rows have every plane masked
+    (`rmin = inf -> i100`), the tall ones end in `rmin > 100 -> i100` (`-> imin` at N = 1 and 3, where no plane is masked), and the
+    answer is plane 0, 1, 2 or 9: a plane of the lane's first iteration in wavefront 0.  `rmin == 100`, the `-> 0` fallback, a
+    sentinel behind a level rise and the 2- and 4-plane forms are not reached here: tests/test_polling_selection_gpu.py drives those """
     base = synthetic.load_plane_database('100').astype(np.float32)
     for planes in (np.concatenate([base, base, base]), base[::-1].copy(), base[:1], base[:3], base[:65],
                    np.concatenate([base[:50]] * 7)):
