@@ -85,11 +85,18 @@ __device__ __forceinline__ Folded fold8(const float* l)
 // accurate to ~1e-7 and monotone to within that): (1) sigmoid(-3.0) = 0.0474 decides every threshold
 // >= 0.048 without any exp; (2) one sigmoid of the largest logit with a 1e-5 guard band decides the rest.
 // Only anchors inside the guard band or above the threshold pay for the exact 8-sigmoid fold.
+// A NaN logit: the reference's fold propagates it (np.maximum / tf.maximum), the folded score is NaN and `NaN > thr` is false, so an
+// anchor with a NaN among its logits is NO candidate.  fmaxf and the clamp inside cephes_expf drop a NaN instead (sigmoidf(NaN) is 1.0
+// here), so the rejects above stay right -- what they turn away has no finite logit that passes -- but what gets through them is asked.
 __device__ __forceinline__ bool is_candidate(const float* l, float thr, Folded& f)
 {
     const float lmax = fmaxf(fmaxf(fmaxf(l[0], l[1]), fmaxf(l[2], l[3])), fmaxf(fmaxf(l[4], l[5]), fmaxf(l[6], l[7])));
     if (thr >= 0.048f && lmax < -3.0f) return false;
     if (sigmoidf(lmax) < thr - 1e-5f) return false;
+    bool nan = false;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) nan |= (l[k] != l[k]);
+    if (nan) return false;
     f = fold8(l);
     return f.score > thr;
 }
@@ -134,7 +141,8 @@ __global__ __launch_bounds__(256) void candidates_osf_kernel(const float* __rest
 #pragma unroll
     for (int o = 0; o < 4; ++o) {
         const float so = fmaxf(s[o], s[o + 4]);
-        if (so > thr) {
+        // (a NaN among the two logits of an orientation: its folded score is NaN in the reference, and the anchor stays out of THAT list)
+        if (l[o] == l[o] && l[o + 4] == l[o + 4] && so > thr) {
             const int list = 4 * b + o;
             const int slot = atomicAdd(&counts[list * (kCounterStride / 4)], 1);
             keys[(int64_t)list * key_stride + slot] =
