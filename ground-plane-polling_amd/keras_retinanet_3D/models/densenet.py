@@ -1,7 +1,7 @@
 """
 DenseNet backbones (reference models/densenet.py:24-94).  The reference builds keras.applications.densenet.DenseNet and takes the raw
 concatenations at the end of dense blocks 3, 4 and 5 as C3, C4, C5; here the backbone is part of the device plan built by
-models/retinanet.py (RetinaNet3D._densenet_backbone) from the layer inventory in models/weights.py.
+models/builder.py (PlanBuilder.densenet_backbone) from the layer inventory in models/weights.py.
 """
 
 from . import Backbone

@@ -1,7 +1,7 @@
 """
 MobileNet backbones (reference models/mobilenet.py:27-111).  The reference builds keras.applications.mobilenet.MobileNet(alpha,
 include_top=False) and takes conv_pw_5_relu, conv_pw_11_relu and conv_pw_13_relu as C3, C4, C5; here the backbone is part of the device
-plan built by models/retinanet.py (RetinaNet3D._mobilenet_backbone) from the layer inventory in models/weights.py: one fused launch per
+plan built by models/builder.py (PlanBuilder.mobilenet_backbone) from the layer inventory in models/weights.py: one fused launch per
 depthwise-separable block (csrc/mobilenet.hip).
 
 A backbone name is 'mobilenet<rows>_<alpha>', e.g. 'mobilenet224_1.0'.  <rows> (128, 160, 192 or 224) only names the ImageNet weights

@@ -1,12 +1,14 @@
 """
 What a plan is: the ctypes mirrors of the descriptors of include/gpp.h (gpp_stem_desc ... gpp_plan_op), the op codes and flag bits of
 gpp_plan_op.kind, the plan switches, and the Plan a model records for one (batch, H, W, N planes) -- its buffers, descriptors and op
-array, who reads and writes what, and the race check over them -- with the host side of the range audit's table.  models/retinanet.py
-builds plans out of these and runs them; nothing here launches a network.
+array, who reads and writes what, and the race check over them -- with the pure rules that name the form of a bottleneck and of the head
+layers (block_form, head_forms) and the host side of the range audit's table.  models/builder.py builds plans out of these, models/tuning.py
+chooses their tiles, models/retinanet.py runs them; nothing here launches a network.
 """
 
 import collections
 import ctypes
+import os
 
 import numpy as np
 
@@ -112,11 +114,106 @@ DETECT_OPS = (OP_DETECT, OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT,
 OP_JOIN, OP_SYNC = 0x10000, 0x20000
 
 
-# the effective plan switches of one (model, batch), read from the GPP_* variables by RetinaNet3D._plan_options
+# the effective plan switches of one (model, batch), read from the GPP_* variables by plan_options (RetinaNet3D._plan_options)
 PlanOptions = collections.namedtuple('PlanOptions', 'x3_level fuse_stem_pool stage_chunks half_stages fuse_tail fuse_block fuse_block_proj '
                                                     'fuse_block_inproj fuse_inproj_rounds '
                                                     'br1_lane fpn_lanes p4_lane head_lanes decode_overlap cls_lane autotune tune_key sparse_heads '
                                                     'sparse_tower sparse_tower_rounds sparse_deep sparse_deep_rounds sparse_depth')
+
+
+def plan_options(model, B):
+    """ every GPP_* switch of the plan builder, read once per plan (when its PlanBuilder is made), as its effective value for this model
+    and batch (PlanOptions) """
+    env = os.environ.get
+    x3 = model.dtype in C.X3_TYPES
+    # x3 types: maps written and read by convolutions only are stored PRE-SPLIT ([32 hi | 32 lo] halves per 32 channels,
+    # gpp_conv_desc.x3_split): GPP_X3_SPLIT=2 (default) every such map, 1 = only the maps between the FPN / head layers -- 80 % of the
+    # FLOPs, all of them matrix-pipe bound -- 0 = none.  Written that way by the producing layer's epilogue, read by the consumers
+    # without the per-fragment split on the vector ALU.
+    x3_split = env('GPP_X3_SPLIT', '2')
+    x3_level = int(x3_split) if x3 else 0
+    # GPP_STAGE_CHUNKS="2,4,8,8": a stage chunk of images by chunk of images, to keep a chunk's working set inside the 256 MiB Infinity
+    # Cache; measured on MI355X at B = 8 this LOSES 1-6 % (the smaller launches cost more than the on-die re-reads save): off
+    chunks = env('GPP_STAGE_CHUNKS')
+    # GPP_FUSE_TAIL: widths whose branch2b + branch2c run as one launch ("" or 0 for none).  Measured at B = 8, same box, whole step:
+    # none 1553, res3 only 1562, res2 + res3 1571 images/s (in isolation the fused res2 launch is no faster than its two layers --
+    # 122 us vs 36 + 80 -- but the step is: 69 MB less through HBM per block).  The x3 form (bottleneck_tail_x3_kernel) reads
+    # pre-split maps at C = 64 (res2) only -- at C = 128 its LDS footprint leaves one workgroup per CU; float32 operands: none
+    tail_widths = env('GPP_FUSE_TAIL', '64,128')
+    fuse_tail = [int(v) for v in tail_widths.split(',') if v.strip() and int(v) > 0]
+    if x3:
+        fuse_tail = [v for v in fuse_tail if v == 64] if x3_level >= 2 else []
+    elif model.esz == 4:
+        fuse_tail = []
+    # GPP_FUSE_BLOCK: widths whose IDENTITY blocks (branch2a + 2b + 2c + shortcut) run as one launch (gpp_bottleneck_block; x3 types on
+    # pre-split maps): res2 (C = 64: 4-wavefront workgroups, two per CU; x in once, y out once: 245 -> 212 us per block at B = 8) and
+    # res3 (C = 128: 8 wavefronts, one per CU; at parity with its three launches in isolation, half their fabric bytes).  Same-box A/B
+    # of the step (profiles/r6/ab_fuse_block_*.txt): B = 8: 780 -> 793 images/s (+1.7 %) with both, +0.9 % with res2 alone; B = 4
+    # +1.2 %, B = 2 +0.7 %, batch-1 plan 2.67 -> 2.65 ms.  "" for the separate launches (bit-identical either way).  Projection
+    # blocks too (GPP_FUSE_BLOCK_PROJ=1) measured -0.6 %: off.
+    block_widths = env('GPP_FUSE_BLOCK', '64,128')
+    fuse_block = [int(v) for v in block_widths.split(',') if v.strip()] if (x3 and x3_level >= 2) else []
+    if model.audit:
+        # an audit plan reads every operand map in HBM: the separate launches wherever a fused form keeps one in LDS (bit-identical
+        # to them: tests/test_block_gpu.py), so the results do not change
+        fuse_tail, fuse_block = [], []
+    # GPP_FUSE_BLOCK_INPROJ (default 1; with 64 in GPP_FUSE_BLOCK): res2a -- the stride-1 projection block -- as ONE launch that computes the
+    # shortcut itself (gpp_bottleneck_block_proj): no res2a_branch1 launch, no shortcut map through HBM (276 MB written and read back at
+    # B = 8).  Only where a batch part's launch fields more than GPP_FUSE_INPROJ_MIN_ROUNDS rounds of 2 x 256 workgroups of 8 x 14 pixels
+    # (a rule of layer, map size and batch part); 0 = res2a as three launches.  Bit-identical either way.
+    inproj = env('GPP_FUSE_BLOCK_INPROJ', '1') != '0'
+    head_lanes = env('GPP_HEAD_LANES', '0') != '0'
+    fpn_lanes = head_lanes or env('GPP_FPN_LANES', '1') != '0'
+    overlap = env('GPP_DECODE_OVERLAP', '1') != '0' and not head_lanes and not model.osf
+    sparse = overlap and not model.audit and env('GPP_SPARSE_HEADS', '1') != '0'
+    return PlanOptions(
+        x3_level=x3_level,
+        fuse_stem_pool=not model.densenet and not model.mobilenet and (model.esz == 2 or model.stem_x3) and env('GPP_FUSE_STEM_POOL', '1') != '0',
+        stage_chunks=tuple(max(1, min(B, int(v))) for v in chunks.split(',')) if chunks else (B,) * 4,
+        # GPP_HALF_LANES (default "0,1,2,3" = res2 .. res5; "" for whole batches): a launch of these stages fills the 256 CUs 0.7 - 1.4
+        # times and is bound by tile fills and first-touch latency; two half-batch chains in flight overlap one's prologue / epilogue /
+        # barrier waits with the other's main loop (f16x3 step, same box: 775 -> 793 images/s; three parts: 801 against 811).  res2
+        # since round 6, with fused identity blocks: B = 8 +0.7 %, B = 4 +1.1 %, B = 2 +1.1 % (profiles/r6/ab_half_lanes_with_blocks.txt)
+        half_stages=frozenset(int(v) for v in env('GPP_HALF_LANES', '0,1,2,3').split(',') if v.strip()) if B >= 2 else frozenset(),
+        fuse_tail=tuple(v for v in fuse_tail if v in (64, 128)),
+        fuse_block=tuple(v for v in fuse_block if v in (64, 128)),
+        fuse_block_proj=env('GPP_FUSE_BLOCK_PROJ', '0') != '0',
+        fuse_block_inproj=inproj,
+        fuse_inproj_rounds=float(env('GPP_FUSE_INPROJ_MIN_ROUNDS', FUSE_INPROJ_MIN_ROUNDS)),
+        br1_lane=env('GPP_BR1_LANE', '1') != '0',           # measured +0.4 % on the f16x3 step (same box, alternating)
+        fpn_lanes=fpn_lanes,
+        p4_lane=1 if (fpn_lanes and env('GPP_P4_LANE', '1') != '0') else 0,
+        head_lanes=head_lanes,
+        decode_overlap=overlap,
+        # GPP_CLS_LANE (default: on for B <= 2): at batch 1 a tower launch fields 0.9 - 1.9 rounds of workgroups of one wavefront per
+        # SIMD: two independent chains in flight fill the other half of every SIMD (measured: profiles/r5/b1_latency.json, field
+        # `plan_variants`); at batch 8 every launch fills the chip on its own (off)
+        cls_lane=2 if (overlap and env('GPP_CLS_LANE', '1' if B <= 2 else '0') != '0') else 0,
+        autotune=env('GPP_AUTOTUNE', '1') != '0',
+        # GPP_SPARSE_HEADS (default 1; needs the decode overlap, whose candidate lists exist before the regression tower): the output
+        # layers of the regression and dimension towers on the candidates' pixels only.  The value of the field is the largest share of
+        # all pyramid pixels the gathered launches take (GPP_SPARSE_HEADS_MAX_SHARE; beyond it the dense launches run: the device
+        # decides, per step); 0.0 = off.  An audit plan keeps the dense launches.
+        sparse_heads=max(1e-9, float(env('GPP_SPARSE_HEADS_MAX_SHARE', SPARSE_HEADS_MAX_SHARE))) if sparse else 0.0,
+        # GPP_SPARSE_TOWER (default 1; with sparse head outputs only): the regression tower's LAST layer on the 3 x 3 dilation of the
+        # candidates' pixels -- the only rows its reader, the gathered output layer, takes.  The value is the largest share of all
+        # pyramid pixels the gathered launch takes (GPP_SPARSE_TOWER_MAX_SHARE); GPP_SPARSE_TOWER_MIN_ROUNDS: the rounds of workgroups
+        # the dense launch must exceed (0 in tests: small plans take the form too)
+        sparse_tower=(max(1e-9, float(env('GPP_SPARSE_TOWER_MAX_SHARE', SPARSE_TOWER_MAX_SHARE)))
+                      if (sparse and env('GPP_SPARSE_TOWER', '1') != '0') else 0.0),
+        sparse_tower_rounds=float(env('GPP_SPARSE_TOWER_MIN_ROUNDS', SPARSE_TOWER_MIN_ROUNDS)),
+        # GPP_SPARSE_TOWER_DEPTH (default 3; with the sparse tower only): how many layers of the regression tower run on the rows their
+        # reader takes -- 1 the last layer alone, 2 layer 2 as well (the 5 x 5 dilation of the candidates' pixels), 3 layer 1 too (7 x 7).
+        # The lists of layers 2 and 1 are made from the logits on the caller's stream (gpp_detect_deep_lists);
+        # GPP_SPARSE_TOWER_DEEP_MAX_SHARE: the largest share of rows their gathered launches take; GPP_SPARSE_TOWER_DEEP_MIN_ROUNDS: the
+        # rounds of workgroups their dense launch must exceed (its own variable: tests force the tower's to 0 at small shapes)
+        sparse_deep=max(1e-9, float(env('GPP_SPARSE_TOWER_DEEP_MAX_SHARE', SPARSE_TOWER_DEEP_MAX_SHARE))),
+        sparse_deep_rounds=float(env('GPP_SPARSE_TOWER_DEEP_MIN_ROUNDS', SPARSE_TOWER_DEEP_MIN_ROUNDS)),
+        sparse_depth=int(env('GPP_SPARSE_TOWER_DEPTH', SPARSE_TOWER_DEPTH)),
+        # what of all this a cached tile choice depends on (models/tuning.py), the same at every batch: the variables as they are set
+        tune_key='x3split={};fuse={}/{};plan={}{}'.format(x3_split, tail_widths, block_widths, model.plan_mode,
+                                                          C.latency_split_config() if model.plan_mode == 'latency' else '') +
+                 (';audit' if model.audit else '') + ('' if inproj else ';inproj=0'))      # (the default keeps its key)
 
 
 # the fused projection block (DESIGN.md section 4.25): its workgroups compute 8 x 14 output pixels, two share a compute unit
@@ -150,6 +247,62 @@ def block_form(opts, width, projection, split_input, halves, join, inproj=None):
     if not projection:
         return launch, 'identity'
     return launch, 'side' if opts.br1_lane and not halves and not join else 'inline'
+
+
+def layer_split(plan_mode, shape, pixels):
+    """ the split-K factor the rule of this plan mode gives a layer of shape (kh, kw, cin, cout) with `pixels` output pixels per image: the
+    one place that chooses between the two rules (layers/conv.py).  A throughput plan's descriptors leave the factor to the library, whose
+    rule default_split restates; the forms below need it before a descriptor exists """
+    return (C.latency_split if plan_mode == 'latency' else C.default_split)(*shape, pixels)
+
+
+# what head_forms decides: sparse = the plan has sparse head outputs at all (a SparseHeads); outputs = {output layer: 'dense' | 'pair' |
+# 'lists_after'}; tower_both = pyramid_regression_3 takes both forms; deep_layers = how many tower layers in front of it do (0, 1, 2)
+HeadForms = collections.namedtuple('HeadForms', 'sparse outputs tower_both deep_layers')
+HEAD_OUTPUTS = ('pyramid_classification', 'pyramid_regression_ops', 'pyramid_regression_dim')
+
+
+def head_forms(opts, dtype, plan_mode, osf, audit, layers, deep_lists, levels, B):
+    """ the form of every head layer that has more than one, named before anything is emitted (as block_form does for a bottleneck).
+    layers: {name: (kh, kw, cin, cout)} of the three output layers and pyramid_regression_1 .. 3; deep_lists: the library has
+    gpp_detect_deep_lists; levels: the (h, w) of the pyramid levels; B: the batch.  Every rule is one of layer, map sizes, batch and plan
+    options, like the split rule -- never of a timing.
+
+    An output layer is a 'pair' with opts.sparse_heads, regression and dimension tower: the decode reads these maps at candidate anchors
+    only, so the layer runs in gathered-row form behind its guarded dense launch (PlanBuilder.out_layer).  A layer the split-K rule splits
+    (small maps) keeps its dense launch alone: one gathered launch cannot reproduce that summation order.  pyramid_classification writes
+    the logits the lists come from: always dense, 'lists_after' in a plan with deep layers (it makes their lists behind its launch).
+
+    tower_both: pyramid_regression_3's reader pyramid_regression_ops is gathered in this plan, and the dense launch fields more than
+    opts.sparse_tower_rounds rounds of 256 x 256 workgroups on the chip: below one round a gathered launch costs one workgroup life either way.
+
+    deep_layers: the lists are made on the caller's stream right behind pyramid_classification, so that layer runs there, unsplit, with the
+    candidate pass on its side lane (decode_overlap without cls_lane: no head_lanes), in a plan that is neither orientation-specific nor an
+    audit; and the dense launch of a layer fields more than opts.sparse_deep_rounds rounds of workgroups """
+    pixels = sum(h * w for h, w in levels)
+    rows = sum((B * h * w + 255) // 256 for h, w in levels)
+
+    def split(name):
+        return layer_split(plan_mode, layers[name], pixels) > 1
+
+    def fills(name, min_rounds):         # the layer's dense launch is a grid of 256 x 256 workgroups that fields more than min_rounds rounds
+        cout = layers[name][3]
+        return not cout % 256 and rows * (cout // 256) > min_rounds * COMPUTE_UNITS
+
+    sparse = bool(opts.sparse_heads)
+    tower_both = bool(sparse and opts.sparse_tower and opts.decode_overlap and opts.x3_level >= 1 and dtype in C.X3_TYPES and
+                      not split('pyramid_regression_ops') and not split('pyramid_regression_3') and
+                      fills('pyramid_regression_3', opts.sparse_tower_rounds))
+    deep_layers = 0
+    if (tower_both and opts.sparse_deep and opts.sparse_depth >= 2 and deep_lists and
+            not (opts.cls_lane or opts.head_lanes or osf or audit) and
+            not any(split(n) for n in ('pyramid_classification', 'pyramid_regression_1', 'pyramid_regression_2')) and
+            not layers['pyramid_regression_1'][3] % 256 and fills('pyramid_regression_2', opts.sparse_deep_rounds)):
+        deep_layers = min(2, opts.sparse_depth - 1)
+    outputs = {name: 'dense' if not sparse or name == 'pyramid_classification' or split(name) else 'pair' for name in HEAD_OUTPUTS}
+    if sparse and deep_layers:
+        outputs['pyramid_classification'] = 'lists_after'
+    return HeadForms(sparse, outputs, tower_both, deep_layers)
 
 
 def part_of(fm, c0, nb):
@@ -228,7 +381,7 @@ class SparseHeads(object):
         self.flag = torch.ones((1,), dtype=i32, device=device)
         self.dense, self.gathered = [], []
         self.lists_joined = False
-        # the DILATED lists (tower_share > 0: the plan runs the regression tower's last layer on them, RetinaNet3D._heads): the listed pixels
+        # the DILATED lists (tower_share > 0: the plan runs the regression tower's last layer on them, PlanBuilder.heads): the listed pixels
         # and their eight neighbours, what the gathered 3 x 3 output layer reads.  Same layout; tower_flag = flag | (more than tower_max_rows
         # rows).  tower = the descriptors of the layers that take both forms (Plan.complete_heads); range_scratch: where a completion's
         # dense re-run counts its range events (the run itself has counted the listed rows already)
@@ -341,7 +494,7 @@ class Plan(object):
         self.atomic = []        # per op: byte intervals it only updates with order-free atomics (the abs-max rows of an audit plan)
         self.wrote = []         # per op: the FMaps among its writes; per op: its io record (audit plans: who produces, who reads a map)
         self.op_io = []
-        self.audit_table = None     # RetinaNet3D(range_audit=True): see RetinaNet3D._audit
+        self.audit_table = None     # RetinaNet3D(range_audit=True): see PlanBuilder.audit
         self.audit_maps = []
         self.audit_unobserved = []
         self.inner = {}         # id(descriptor) -> the gpp_conv_desc records a fused or pre-activation launch points to
@@ -352,7 +505,7 @@ class Plan(object):
         self.flops = 0.0
         self.ragged = False     # plan_for(..., ragged=True): the plan of a height class; heights = its int32 device table, heights_host = what it holds
         self.heights = None
-        self.sparse = None      # SparseHeads: the head output layers run on the candidates' pixels only (RetinaNet3D._heads)
+        self.sparse = None      # SparseHeads: the head output layers run on the candidates' pixels only (PlanBuilder.heads)
         self.heads_stale = False    # a run has left rows of regression / regression_dim unwritten: the next read of either completes them
 
     # The two regression head tensors.  With sparse head outputs a run writes them at the pixels the decode reads and nowhere else; whoever
@@ -382,24 +535,22 @@ class Plan(object):
         if self.sparse is None or not self.heads_stale:
             return
         self.heads_stale = False
-        for both in self.sparse.deep:                         # layers 1, 2 in layer order: each dense reader reads every row of the layer in front
-            d = type(both).from_buffer_copy(both)
-            d.deep_rows = d.deep_counts = d.deep_flag = None
-            d.deep_tile = 0
-            if d.range_counter:
-                d.range_counter = self.sparse.range_scratch.data_ptr()
-            hip.check(hip.lib().gpp_conv2d_igemm(ctypes.byref(d), hip.stream_ptr()), 'gpp_conv2d_igemm (deep tower layer completed)')
-        for both in self.sparse.tower:
-            d = type(both).from_buffer_copy(both)             # the layer's dense launch alone; its range events go to a scratch slot:
-            d.tower_rows = d.tower_counts = d.tower_flag = None      # the run has counted those of the rows it wrote
-            d.tower_tile = 0
-            if d.range_counter:
-                d.range_counter = self.sparse.range_scratch.data_ptr()
-            hip.check(hip.lib().gpp_conv2d_igemm(ctypes.byref(d), hip.stream_ptr()), 'gpp_conv2d_igemm (tower layer completed)')
-        for guarded in self.sparse.dense:
-            d = type(guarded).from_buffer_copy(guarded)       # the dense launch as it stands in the plan, without its guard
-            d.guard, d.guard_value = None, 0
-            hip.check(hip.lib().gpp_conv2d_igemm(ctypes.byref(d), hip.stream_ptr()), 'gpp_conv2d_igemm (head tensors completed)')
+        sp = self.sparse
+        # deep layers 1, 2 in layer order, then the tower's last layer, then the output layers: each dense reader reads every row of the layer
+        # in front.  Each is the dense launch as it stands in the plan, without its lists or its guard; a layer of both forms counts its range
+        # events into a scratch slot: the run has counted those of the rows it wrote
+        for descs, lists, tile, scratch, what in (
+                (sp.deep, ('deep_rows', 'deep_counts', 'deep_flag'), 'deep_tile', True, 'deep tower layer completed'),
+                (sp.tower, ('tower_rows', 'tower_counts', 'tower_flag'), 'tower_tile', True, 'tower layer completed'),
+                (sp.dense, ('guard',), 'guard_value', False, 'head tensors completed')):
+            for desc in descs:
+                d = type(desc).from_buffer_copy(desc)
+                for field in lists:
+                    setattr(d, field, None)
+                setattr(d, tile, 0)
+                if scratch and d.range_counter:
+                    d.range_counter = sp.range_scratch.data_ptr()
+                hip.check(hip.lib().gpp_conv2d_igemm(ctypes.byref(d), hip.stream_ptr()), 'gpp_conv2d_igemm ({})'.format(what))
 
     def emit(self, kind, desc, name, reads=(), writes=(), tag=0, flops=0.0, lane=0, join=False, sync=False, io=None, inner=(), atomic=()):
         """ record one launch.  reads / writes: the FMaps and tensors it reads and writes (check_stream_ordering); io: its

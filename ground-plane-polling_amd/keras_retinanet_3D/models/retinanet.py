@@ -13,7 +13,8 @@ with the same `predict_on_batch([images, P_inv, planes])` -> 8 arrays contract
 Nothing is traced or compiled at run time: for a given (batch, H, W) the model lays out its
 activations in HBM once and records a *plan* -- a flat array of C-ABI descriptors (include/gpp.h) --
 that one `gpp_plan_run` call enqueues on the current HIP stream.  All arithmetic happens in the
-hand-written kernels of ../csrc; PyTorch only owns the device buffers.
+hand-written kernels of ../csrc; PyTorch only owns the device buffers.  The model here owns the weights and the plans per shape and runs
+them; one PlanBuilder (models/builder.py) records each plan, models/tuning.py chooses its tiles.
 
 HBM layout
   * activations NHWC, 16-bit (bf16 default, f16) or float32 (dtype='f32': the reference's own arithmetic type --
@@ -29,7 +30,6 @@ a result, and split-K follows a rule of the layer alone (gpp_conv2d_split_rule) 
 """
 
 import ctypes
-import json
 import os
 
 import numpy as np
@@ -37,11 +37,10 @@ import numpy as np
 from ..backend import hip
 from ..layers import conv as C
 from ..layers import mobilenet as M
-from ..layers.filter_detections import MAX_DETECTIONS, NMS_THRESHOLD, SCORE_THRESHOLD
-from ..utils import anchors as anchor_utils
 from ..utils import cuboid_nms as cuboid_nms_utils
-from ..utils.gpp_utils import POLL_THRESHOLD, POSE_SCORE_THRESHOLD
+from . import tuning
 from . import weights as W
+from .builder import PlanBuilder
 # what a plan is (models/plan.py), under the names this module has always had: tests and tools spell them retinanet.StemDesc, retinanet.OP_CONV ...
 from .plan import (BlockDesc, BlockProjDesc, FUSE_INPROJ_MIN_ROUNDS, CandidatePixelsDesc, DensePoolDesc, DetectDesc, PlanOp, PollDesc, PoolDesc, PoseDesc, CuboidNmsDesc,  # noqa: F401
                    PreactDesc, RaggedPoolDesc, RaggedStemDesc, ReluDesc, StemDesc, TailDesc,
@@ -50,7 +49,7 @@ from .plan import (BlockDesc, BlockProjDesc, FUSE_INPROJ_MIN_ROUNDS, CandidatePi
                    OP_MAXPOOL_PAD, OP_AVGPOOL, OP_CONV_PREACT, OP_MOBILENET_STEM, OP_MOBILENET_BLOCK, OP_POSE, OP_CUBOID_NMS,
                    OP_ABSMAX, OP_ABSMAX_CLEAR, OP_STEM_RAGGED, OP_STEM_POOL_RAGGED, OP_MAXPOOL_RAGGED,
                    OP_DETECT_CANDIDATE_PIXELS, DETECT_OPS, OP_JOIN, OP_SYNC,
-                   PlanOptions, block_form, part_of, TOWER_SLICES, RANGE_AUDIT_THRESHOLD, X3_QUANTUM,
+                   PlanOptions, block_form, part_of, plan_options, TOWER_SLICES, RANGE_AUDIT_THRESHOLD, X3_QUANTUM,
                    SPARSE_HEADS_MAX_SHARE, SPARSE_TOWER_MAX_SHARE, SPARSE_TOWER_MIN_ROUNDS, SPARSE_TOWER_DEPTH,
                    SPARSE_TOWER_DEEP_MAX_SHARE, SPARSE_TOWER_DEEP_MIN_ROUNDS, COMPUTE_UNITS, audit_report, SparseHeads, Plan)
 
@@ -129,9 +128,9 @@ class RetinaNet3D(object):
         self._plans = {}
         self._anchors = {}
         self._taps, self._ragged_taps = {}, {}      # resize tap tables on the device, per frame size (stage_frames / _stage_ragged_frames)
-        self._tuned = {}             # (layer, B, H, W) -> (tile_hint, split_k, us): see _autotune
         self.stem_x3 = False         # conv1 on the matrix pipe, input and weights split into two IEEE halves (_upload)
-        self._load_tune_cache()
+        self._tune = tuning.TuneCache.for_model(self)        # (layer, B, H, W) -> (tile, us): what _autotune has chosen or found in GPP_TUNE_CACHE
+        self._tune.load(os.environ.get('GPP_TUNE_CACHE'))
         self._upload(weights)
         self.tag_names = []          # filled by the plan builder: names of event-tagged ops
 
@@ -230,706 +229,14 @@ class RetinaNet3D(object):
             self.mbn_w[i] = (up(M.pack_depthwise(np.transpose(kd, (0, 1, 3, 2)))), up(bd), pw, up(bp), scale)
 
     # ------------------------------------------------------------------ plan
-    def _anchor_table(self, hw, shapes=None):
-        key = hw if shapes is None else (hw, tuple(shapes))
-        if key not in self._anchors:
-            a = anchor_utils.anchors_for_image(hw) if shapes is None else anchor_utils.anchors_for_shapes(shapes)
-            self._anchors[key] = self.torch.as_tensor(a).to(self.device).contiguous()
-        return self._anchors[key]
-
-    def _desc(self, plan, name, inputs, outputs, K, stride=1, pad=None, relu=False, residuals=None, out_f32=False, lane=0):
-        wt, bias, shape = self.conv_w[name]
-        kh, kw, cin, cout = shape
-        if pad is None:
-            pad = (0, 0)
-        # plan='latency': an explicit split-K factor per layer (a function of the layer alone); 0 = the library's own rule
-        split = C.latency_split(kh, kw, cin, cout, sum(f.H * f.W for f in outputs)) if self.plan_mode == 'latency' else 0
-        d = C.conv_desc(inputs, outputs, wt, bias, kh, kw, cin, cout, stride=stride, pad=pad, relu=relu,
-                        residuals=residuals, dtype=self.dtype, out_f32=out_f32, out_scale=self.conv_scale.get(name), split_k=split)
-        if self.dtype == 'f16x3':         # this plan's own range-event slot (Plan.range_slot): what its launches count no other plan sees
-            d.range_counter = plan.range_slot.data_ptr()
-        # split-K partial tiles: the workspace of this op's stream lane is allocated once every op is known (_build)
-        plan.conv_descs.append((d, lane))
-        plan.ws_need[lane] = max(plan.ws_need.get(lane, 0), C.workspace_bytes(d))
-        return d
-
-    def _conv(self, plan, name, inputs, outputs, K, stride=1, pad=None, relu=False, residuals=None, out_f32=False, tag=0, lane=0,
-              join=False, sync=False):
-        d = self._desc(plan, name, inputs, outputs, K, stride, pad, relu, residuals, out_f32, lane)
-        plan.emit(OP_CONV, d, name, list(inputs) + list(residuals or []), outputs, tag=tag, flops=C.conv_flops(d), lane=lane, join=join,
-                  sync=sync, io=(inputs, outputs, residuals))
-
-    def _tail(self, plan, nm, a, y, shortcut, join=False, lane=0):
-        """ branch2b (3x3) + branch2c (1x1, + shortcut, ReLU) of one bottleneck as ONE launch
-        (gpp_bottleneck_tail): the intermediate map never reaches HBM.  Bit-identical to the two layers. """
-        d1 = self._desc(plan, 'res{}_branch2b'.format(nm), [a], [a], 3, pad=(1, 1), relu=True)       # its `out` is never written
-        d2 = self._desc(plan, 'res{}_branch2c'.format(nm), [a], [y], 1, relu=True, residuals=[shortcut])
-        plan.emit(OP_TAIL, TailDesc(ctypes.addressof(d1), ctypes.addressof(d2), 0, 0), 'res{}_branch2b+2c'.format(nm), [a, shortcut], [y],
-                  flops=C.conv_flops(d1) + C.conv_flops(d2), join=join, lane=lane, io=([a], [y], [shortcut]), inner=(d1, d2))
-
-    def _block(self, plan, nm, x, a, bmap, y, shortcut, stride=1, join=False, lane=0):
-        """ a whole bottleneck -- branch2a, branch2b, branch2c (+ shortcut, ReLU) -- as ONE launch (gpp_bottleneck_block): neither intermediate map
-        reaches HBM (`a` / `bmap` only lend the descriptors their shapes).  Bit-identical to the three layers. """
-        d1 = self._desc(plan, 'res{}_branch2a'.format(nm), [x], [a], 1, stride=stride, relu=True)
-        d2 = self._desc(plan, 'res{}_branch2b'.format(nm), [a], [bmap], 3, pad=(1, 1), relu=True)
-        d3 = self._desc(plan, 'res{}_branch2c'.format(nm), [bmap], [y], 1, relu=True, residuals=[shortcut])
-        t = BlockDesc(ctypes.addressof(d1), ctypes.addressof(d2), ctypes.addressof(d3), 0, 0)
-        plan.emit(OP_BLOCK, t, 'res{}_branch2a+2b+2c'.format(nm), [x, shortcut], [y], flops=C.conv_flops(d1) + C.conv_flops(d2) + C.conv_flops(d3),
-                  join=join, lane=lane, io=([x], [y], [shortcut]), inner=(d1, d2, d3))
-
-    def _block_proj(self, plan, nm, x, a, bmap, sc, y, join=False, lane=0):
-        """ a whole projection bottleneck -- branch2a, branch1, branch2b, branch2c (+ shortcut, ReLU) -- as ONE launch (gpp_bottleneck_block_proj): the
-        shortcut is computed from the input rows branch2a stages and never becomes a map (`a` / `bmap` / `sc` only lend the descriptors their
-        shapes).  Bit-identical to the four layers. """
-        d1 = self._desc(plan, 'res{}_branch2a'.format(nm), [x], [a], 1, relu=True)
-        d2 = self._desc(plan, 'res{}_branch2b'.format(nm), [a], [bmap], 3, pad=(1, 1), relu=True)
-        d3 = self._desc(plan, 'res{}_branch2c'.format(nm), [bmap], [y], 1, relu=True)
-        dp = self._desc(plan, 'res{}_branch1'.format(nm), [x], [sc], 1)
-        t = BlockProjDesc(ctypes.addressof(d1), ctypes.addressof(d2), ctypes.addressof(d3), 0, 1, ctypes.addressof(dp))
-        plan.emit(OP_BLOCK, t, 'res{}_branch2a+2b+2c'.format(nm), [x], [y],
-                  flops=C.conv_flops(d1) + C.conv_flops(d2) + C.conv_flops(d3) + C.conv_flops(dp), join=join, lane=lane, io=([x], [y], None),
-                  inner=(d1, d2, d3, dp))
-
-    def _preact(self, plan, name, inputs, outputs, relu=False):
-        """ a 1x1 conv behind its input's BatchNormalization + ReLU (gpp_conv2d_preact): DenseNet's _1_conv and transition convs """
-        d = self._desc(plan, name, inputs, outputs, 1, relu=relu)
-        s, t = self.preact[name]
-        plan.emit(OP_CONV_PREACT, PreactDesc(ctypes.addressof(d), s.data_ptr(), t.data_ptr()), name, inputs, outputs, flops=C.conv_flops(d),
-                  io=(inputs, outputs, None), inner=(d,))
-
-    def _stem(self, plan, opts, B, H, Wd, fmap, x):
-        """ conv1 + bn + relu (7x7 / 2) and pool1 (3x3 / 2) into x.  opts.fuse_stem_pool: one launch, the (B, H1, W1, 64) conv map is never
-        stored (bit-identical to the two launches: tests/test_stem_gpu.py; 16-bit types since round 2, the x3 types since round 6 --
-        gpp_stem_pool_fused_x3: the float32 conv map was 274 MB written + read back at B = 8).  Else the conv map is stored and pooled by a
-        second launch: ResNet's max pool, or DenseNet's zero-padded one into the channel prefix of its first concatenation buffer. """
-        H1, W1 = (H + 6 - 7) // 2 + 1, (Wd + 6 - 7) // 2 + 1
-        conv = x if opts.fuse_stem_pool else fmap(H1, W1, 64)
-        d = StemDesc(plan.images.data_ptr(), self.stem_w.data_ptr(), self.stem_b.data_ptr(), conv.buf.data_ptr(),
-                     hip.GPP_F16X3 if self.stem_x3 else C.gpp_storage_dtype(self.dtype), B, H, Wd,
-                     plan.range_slot.data_ptr() if self.dtype == 'f16x3' else None)
-        flops = 2.0 * B * H1 * W1 * 147 * 64
-        plan.stem_out, plan.pool_out = (None if opts.fuse_stem_pool else conv), x
-        if plan.ragged:
-            # a batch of one height class: H = the 4 Hp rows of the canvas, H1 = 2 Hp the rows of the class's largest conv map; every image's own
-            # height comes from plan.heights on the device (the same launches, per-image H / Ho / pad_top: csrc/stem_kernels.h)
-            rd = RaggedStemDesc(d, plan.heights.data_ptr(), x.H, 0)
-            if opts.fuse_stem_pool:
-                plan.emit(OP_STEM_POOL_RAGGED, rd, 'conv1+pool1', [plan.images, plan.heights], [x], flops=flops)
-                return
-            plan.emit(OP_STEM_RAGGED, rd, 'conv1', [plan.images, plan.heights], [conv], flops=flops)
-            pd = RaggedPoolDesc(PoolDesc(conv.buf.data_ptr(), x.buf.data_ptr(), C.gpp_storage_dtype(self.dtype), B, H1, W1, 64, 0),
-                                plan.heights.data_ptr(), x.H, 0)
-            plan.emit(OP_MAXPOOL_RAGGED, pd, 'pool1', [conv, plan.heights], [C.FMap(x.buf, B, x.H, x.W, 64, pitch=x.pitch)])
-            return
-        if opts.fuse_stem_pool:
-            plan.emit(OP_STEM_POOL, d, 'conv1+pool1', [plan.images], [x], flops=flops)
-            return
-        plan.emit(OP_STEM, d, 'conv1', [plan.images], [conv], flops=flops)
-        pooled = C.FMap(x.buf, B, x.H, x.W, 64, pitch=x.pitch)
-        if self.densenet:
-            pd = DensePoolDesc(conv.buf.data_ptr(), x.buf.data_ptr(), B, H1, W1, 64, 1, x.pitch)
-            plan.emit(OP_MAXPOOL_PAD, pd, 'pool1', [conv], [pooled])
-        else:
-            pd = PoolDesc(conv.buf.data_ptr(), x.buf.data_ptr(), C.gpp_storage_dtype(self.dtype), B, H1, W1, 64, 0)
-            plan.emit(OP_MAXPOOL, pd, 'pool1', [conv], [pooled])
-
-    def _resnet_backbone(self, plan, opts, B, H, Wd, fmap, bmap):
-        """ conv1 .. res5 of keras_resnet (bottleneck_2d: stride on the first 1x1) -> [C2, C3, C4, C5].  A stage runs as two half
-        batches (opts.half_stages), the second half on side lane 1 beside the first, or chunk of images by chunk of images
-        (opts.stage_chunks), one chunk after the other; the halves stay apart until the next whole-batch launch joins them. """
-        H1, W1 = (H + 6 - 7) // 2 + 1, (Wd + 6 - 7) // 2 + 1
-        x = fmap((H1 + 1) // 2, (W1 + 1) // 2, 64)
-        self._stem(plan, opts, B, H, Wd, fmap, x)
-        feats = []
-        for stage, n_blocks in enumerate(W.BLOCKS[self.backbone_name]):
-            f, xin, blocks = 64 * 2 ** stage, x, []
-            for block in range(n_blocks):
-                stride = 2 if (block == 0 and stage > 0) else 1
-                ho, wo = (x.H - 1) // stride + 1, (x.W - 1) // stride + 1
-                # (fused tails have no branch2b map: a fused block's descriptors borrow branch2a's -- neither is written)
-                a, b = bmap(ho, wo, f), None if f in opts.fuse_tail else bmap(ho, wo, f)
-                sc = bmap(ho, wo, 4 * f) if block == 0 else None
-                x = bmap(ho, wo, 4 * f)
-                blocks.append((W.block_name(self.backbone_name, stage, block), stride, a, b, sc, x))
-            chunk = opts.stage_chunks[stage]
-            halves = stage in opts.half_stages and chunk >= B       # (a stage that is chunked runs its chunks one after the other)
-            parts = [(B // 2, B - B // 2, 1), (0, B // 2, 0)] if halves else [(c0, min(chunk, B - c0), 0) for c0 in range(0, B, chunk)]
-            xs_of = {c0: part_of(xin, c0, nb) for c0, nb, _ in parts}
-            for (nm, stride, a, b, sc, y), (c0, nb, lane) in ([(k, p) for k in blocks for p in parts] if halves else
-                                                              [(k, p) for p in parts for k in blocks]):
-                xs = xs_of[c0]
-                join = not halves and bool(plan.open_lanes)          # the first launch of a whole-batch stage behind a split one
-                form = block_form(opts, f, sc is not None, xs.split, halves, join, inproj=(stride, nb, y.H, y.W))
-                xs_of[c0] = part_of(y, c0, nb)
-                self._bottleneck(plan, nm, form, stride, xs, part_of(a, c0, nb), b and part_of(b, c0, nb),
-                                 part_of(sc, c0, nb) if sc else xs, xs_of[c0], lane, join)
-            feats.append(x)
-        return feats
-
-    def _bottleneck(self, plan, nm, form, stride, x, a, b, sc, y, lane, join):
-        """ one bottleneck (of one batch part) in the form block_form chose.  join: its first launch closes the side lanes of the stage
-        before; a projection shortcut on side lane 1 is joined by the launch that adds it. """
-        launch, shortcut = form
-        branch1 = 'res{}_branch1'.format(nm)
-        if shortcut == 'inproj':
-            self._block_proj(plan, nm, x, a, b or a, sc, y, join=join, lane=lane)
-            return
-        if shortcut == 'side':
-            self._conv(plan, branch1, [x], [sc], 1, stride=stride, lane=1)
-        if launch == 'block':
-            if shortcut == 'inline':         # a projection block: the shortcut map first, in line, then the whole block
-                self._conv(plan, branch1, [x], [sc], 1, stride=stride, lane=lane, join=join)
-                join = False
-            self._block(plan, nm, x, a, b or a, y, sc, stride=stride, join=join or shortcut == 'side', lane=lane)
-            return
-        self._conv(plan, 'res{}_branch2a'.format(nm), [x], [a], 1, stride=stride, relu=True, lane=lane, join=join)
-        if shortcut == 'inline':
-            self._conv(plan, branch1, [x], [sc], 1, stride=stride, lane=lane)
-        if launch == 'tail':
-            self._tail(plan, nm, a, y, sc, join=shortcut == 'side', lane=lane)
-        else:
-            self._conv(plan, 'res{}_branch2b'.format(nm), [a], [b], 3, pad=(1, 1), relu=True, lane=lane)
-            self._conv(plan, 'res{}_branch2c'.format(nm), [b], [y], 1, relu=True, residuals=[sc], join=shortcut == 'side', lane=lane)
-
-    def _densenet_backbone(self, plan, opts, B, H, Wd, fmap, bmap):
-        """ conv1 .. conv5_block{N}_concat of keras' DenseNet (reference models/densenet.py:62-94) -> the four block concatenations.
-        One float32 buffer per dense block at its final width: the block input (pool1 / the transition's average pool) is written into
-        channels [0, C0), layer I's 32 channels into [C0 + 32 (I - 1), C0 + 32 I), and layer I's _1_conv reads the prefix [0, C0 + 32 (I - 1))
-        through in_pitch.  The 128-channel map between _1_conv and _2_conv is pre-split for the x3 types.  The whole batch on lane 0. """
-        widths = W.densenet_widths(self.backbone_name)
-        H1, W1 = (H + 6 - 7) // 2 + 1, (Wd + 6 - 7) // 2 + 1
-        h, w = (H1 - 1) // 2 + 1, (W1 - 1) // 2 + 1
-        cats = []
-        for stage in range(4):
-            cats.append(fmap(h, w, widths[stage]))
-            h, w = h // 2, w // 2
-        self._stem(plan, opts, B, H, Wd, fmap, cats[0])
-        c0 = 64
-        for stage, n in enumerate(W.DENSENET_BLOCKS[self.backbone_name]):
-            cat = cats[stage]
-            for i in range(1, n + 1):
-                nm = 'conv{}_block{}'.format(stage + 2, i)
-                cin = c0 + W.DENSENET_GROWTH * (i - 1)
-                mid = bmap(cat.H, cat.W, W.DENSENET_BOTTLENECK)
-                self._preact(plan, nm + '_1_conv', [C.FMap(cat.buf, B, cat.H, cat.W, cin, pitch=cat.pitch)], [mid], relu=True)
-                self._conv(plan, nm + '_2_conv', [mid], [C.FMap(cat.buf, B, cat.H, cat.W, W.DENSENET_GROWTH, off=cin, pitch=cat.pitch)], 3,
-                           pad=(1, 1))
-            if stage == 3:
-                break
-            nm = 'pool{}'.format(stage + 2)
-            t = fmap(cat.H, cat.W, widths[stage] // 2)
-            self._preact(plan, nm + '_conv', [cat], [t])
-            nxt = cats[stage + 1]
-            pd = DensePoolDesc(t.buf.data_ptr(), nxt.buf.data_ptr(), B, t.H, t.W, t.C, 0, nxt.pitch)
-            plan.emit(OP_AVGPOOL, pd, nm + '_pool', [t], [C.FMap(nxt.buf, B, nxt.H, nxt.W, t.C, pitch=nxt.pitch)])
-            c0 = t.C
-        return cats
-
-    def _mobilenet_backbone(self, plan, opts, B, H, Wd, fmap, bmap):
-        """ conv1 .. conv_pw_13_relu of keras' MobileNet (reference models/mobilenet.py:94-111) -> conv_pw_3 / 5 / 11 / 13 behind their
-        ReLU6 (C2 .. C5).  conv1 is one launch (gpp_mobilenet_stem), every depthwise-separable block ONE launch (gpp_mobilenet_block: the
-        depthwise map never reaches HBM).  Every map is float32, never pre-split; the whole batch on lane 0. """
-        c0 = W.mobilenet_filters(self.backbone_name)[0]
-        x = fmap(M.out_size(H, 2), M.out_size(Wd, 2), c0)
-        sd = hip.MobileNetStemDesc(plan.images.data_ptr(), self.stem_w.data_ptr(), self.stem_b.data_ptr(), x.buf.data_ptr(), B, H, Wd, c0, x.pitch, 0)
-        plan.stem_out, plan.pool_out = x, None
-        plan.emit(OP_MOBILENET_STEM, sd, 'conv1', [plan.images], [x], flops=2.0 * B * x.H * x.W * 27 * c0)
-        feats = []
-        for i, cin, cout, stride in W.mobilenet_blocks(self.backbone_name):
-            y = fmap(M.out_size(x.H, stride), M.out_size(x.W, stride), cout)
-            dw_w, dw_b, pw_w, pw_b, scale = self.mbn_w[i]
-            d = M.block_desc(x, y, dw_w, dw_b, pw_w, pw_b, scale, stride, self.dtype)
-            plan.emit(OP_MOBILENET_BLOCK, d, 'conv_pw_{}'.format(i), [x], [y], flops=M.block_flops(d), io=([x], [y], None))
-            x = y
-            if i in W.MOBILENET_TAPS:
-                feats.append(x)
-        return feats
-
-    def _pyramid(self, plan, opts, B, H, Wd, C3, C4, C5):
-        """ the layout of every FPN / head tensor: the five levels back to back per image, (B, sum(H_l*W_l), C), so that one grouped
-        launch covers all levels; a DenseNet's pyramid has the sizes of its own C3 .. C5 (floor pools).
-        Returns (level shapes, pyramid(c, dtype=None) -> (buffer, its five level FMaps)). """
-        got = [(C3.H, C3.W), (C4.H, C4.W), (C5.H, C5.W)]
-        shapes = anchor_utils.pyramid_shapes_of_features(got) if self.densenet else anchor_utils.pyramid_shapes((H, Wd))
-        if got != [tuple(s) for s in shapes[:3]]:
-            raise RuntimeError('backbone / pyramid shape mismatch: {} vs {}'.format(got, shapes))
-        pix = [h * w for h, w in shapes]
-        total = sum(pix)
-        plan.n_anchors = total * anchor_utils.NUM_BASE_ANCHORS
-        x3s = opts.x3_level >= 1
-
-        def pyramid(c, dtype=None):
-            buf = self.torch.empty((B, total, c), dtype=dtype or self.tdtype, device=self.device)
-            plan.keep.append(buf)
-            sp = x3s and dtype is None
-            return buf, [C.FMap(buf, B, h, w, c, off=sum(pix[:i]) * c, bstride=total * c, split=sp, half=self.dtype if sp else 'bf16x3')
-                         for i, (h, w) in enumerate(shapes)]
-        return shapes, pyramid
-
-    def _fpn(self, plan, opts, C3, C4, C5, pyramid, smap):
-        """ P3 .. P7 into one pyramid tensor (512 channels); returns its five level maps.  P5 and the P6 -> ReLU -> P7 chain are small
-        launches (a few dozen tiles) independent of the C4 / C3 chain: with opts.fpn_lanes they run on the side streams underneath the
-        C4_reduced / P4 launches (182 workgroups each: 74 CUs idle), joined by the fused first tower layer (measured +0.8 % on the f16x3
-        step).  P4 (182 workgroups of 192 x 256: 71 % of the CUs) only feeds the towers: with opts.p4_lane it runs behind P5 on its side
-        stream (re-forked: it needs T4), beside C3_reduced / P3. """
-        _, P = pyramid(512)
-        l_p5, l_p6 = (1, 2) if opts.fpn_lanes else (0, 0)
-        T5 = smap(C5.H, C5.W, 512)
-        self._conv(plan, 'C5_reduced', [C5], [T5], 1, join=bool(plan.open_lanes))
-        self._conv(plan, 'P5', [T5], [P[2]], 3, pad=(1, 1), lane=l_p5)
-        self._conv(plan, 'P6', [C5], [P[3]], 3, stride=2, pad=(C.same_pad(C5.H, 3, 2)[1], C.same_pad(C5.W, 3, 2)[1]), lane=l_p6)
-        R6 = smap(P[3].H, P[3].W, 512)
-        relu_d = ReluDesc(P[3].buf.data_ptr() + P[3].off * self.esz, R6.buf.data_ptr(), P[3].bstride, R6.bstride, P[3].H * P[3].W * 512,
-                          C.gpp_dtype(self.dtype) if opts.x3_level >= 1 else C.gpp_storage_dtype(self.dtype), P[3].B)
-        plan.emit(OP_RELU, relu_d, 'C6_relu', [P[3]], [R6], lane=l_p6)
-        plan.relu_io = (P[3], R6)
-        self._conv(plan, 'P7', [R6], [P[4]], 3, stride=2, pad=(C.same_pad(P[3].H, 3, 2)[1], C.same_pad(P[3].W, 3, 2)[1]), lane=l_p6)
-        T4 = smap(C4.H, C4.W, 512)
-        self._conv(plan, 'C4_reduced', [C4], [T4], 1, residuals=[T5])          # + UpsampleLike(P5, C4), fused
-        self._conv(plan, 'P4', [T4], [P[1]], 3, pad=(1, 1), lane=opts.p4_lane, sync=bool(opts.p4_lane))
-        T3 = smap(C3.H, C3.W, 512)
-        self._conv(plan, 'C3_reduced', [C3], [T3], 1, residuals=[T4])          # + UpsampleLike(P4, C3), fused
-        self._conv(plan, 'P3', [T3], [P[0]], 3, pad=(1, 1))
-        return P
-
-    def _detect(self, plan, B, anchors, pyramid):
-        """ decode + NMS (RegressBoxes, RegressDims, FilterDetections): the three head outputs (float32 pyramids), the detection outputs,
-        the workspace and the one descriptor the decode launches share, allocated before the towers are emitted.
-        Returns ((classification, regression, dimension) output maps, decode(kind, name, **flags): records one decode launch). """
-        torch, dev, D = self.torch, self.device, MAX_DETECTIONS
-        f32, i32 = torch.float32, torch.int32
-        plan.cls_logits, cls_o = pyramid(96, f32)
-        plan.regression, reg_o = pyramid(144, f32)
-        plan.regression_dim, dim_o = pyramid(36, f32)
-        plan.boxes = torch.empty((B, D, 12), dtype=f32, device=dev)
-        plan.dimensions = torch.empty((B, D, 3), dtype=f32, device=dev)
-        plan.scores = torch.empty((B, D), dtype=f32, device=dev)
-        plan.labels = torch.empty((B, D), dtype=i32, device=dev)
-        plan.orientations = torch.empty((B, D), dtype=i32, device=dev)
-        plan.anchor_index = torch.empty((B, D), dtype=i32, device=dev)
-        plan.counts = torch.zeros((B,), dtype=i32, device=dev)
-        need = hip.c_size_t(0)
-        if self.osf and B > 16:
-            raise ValueError('orientation_specific_filter=True handles at most 16 images per batch')
-        size_fn = hip.lib().gpp_detect_osf_workspace_bytes if self.osf else hip.lib().gpp_detect_workspace_bytes
-        hip.check(size_fn(B, plan.n_anchors, need), 'gpp_detect_workspace_bytes')
-        plan.detect_ws = ws = torch.empty((int(need.value),), dtype=torch.uint8, device=dev)
-        plan.anchors = anchors
-        dd = DetectDesc(plan.cls_logits.data_ptr(), plan.regression.data_ptr(), plan.regression_dim.data_ptr(),
-                        anchors.data_ptr(), plan.boxes.data_ptr(), plan.dimensions.data_ptr(), plan.scores.data_ptr(),
-                        plan.labels.data_ptr(), plan.orientations.data_ptr(), plan.anchor_index.data_ptr(),
-                        plan.counts.data_ptr(), ws.data_ptr(), ws.numel(), plan.n_anchors,
-                        B, anchor_utils.NUM_BASE_ANCHORS, 1, D, SCORE_THRESHOLD, NMS_THRESHOLD if self.nms else 2.0)
-        heads = [plan.cls_logits, plan.regression, plan.regression_dim]
-        dets = [plan.boxes, plan.dimensions, plan.scores, plan.labels, plan.orientations, plan.anchor_index]
-        access = {OP_DETECT_CANDIDATES: ([plan.cls_logits], [ws, plan.counts]), OP_DETECT_SELECT: ([ws, plan.regression], [ws]),
-                  OP_DETECT_EMIT: (heads + [ws], dets)}
-
-        def decode(kind, name='filtered_detections', **flags):
-            reads, writes = access.get(kind, (heads, dets + [ws, plan.counts]))          # (OP_DETECT / OP_DETECT_OSF: the whole decode)
-            if kind == OP_DETECT_CANDIDATE_PIXELS:      # the candidate pass + the pixel lists of the gathered head output layers, one op
-                sp = plan.sparse
-                lists = hip.PixelListDesc(ws.data_ptr(), sp.bitmap.data_ptr(), sp.rows.data_ptr(), sp.counts.data_ptr(), sp.flag.data_ptr(),
-                                          plan.n_anchors, B, anchor_utils.NUM_BASE_ANCHORS, 4 if self.osf else 1, len(sp.level_pixels),
-                                          sp.max_rows, 0, (ctypes.c_int32 * hip.GPP_MAX_GROUPS)(*sp.level_pixels), 0)
-                if sp.tower_rows is not None:       # ... and their 3 x 3 dilation: what the regression tower's last layer has to write
-                    lists.dilated_bitmap, lists.dilated_rows = sp.tower_bitmap.data_ptr(), sp.tower_rows.data_ptr()
-                    lists.dilated_counts, lists.dilated_flag = sp.tower_counts.data_ptr(), sp.tower_flag.data_ptr()
-                    lists.level_width = (ctypes.c_int32 * hip.GPP_MAX_GROUPS)(*sp.level_widths)
-                    lists.dilated_max_rows = sp.tower_max_rows
-                reads, writes = access[OP_DETECT_CANDIDATES]
-                plan.emit(kind, CandidatePixelsDesc(ctypes.addressof(dd), lists), name, reads, writes + sp.tensors(), inner=(dd,), **flags)
-                return
-            plan.emit(kind, dd, name, reads, writes, **flags)
-        return (cls_o, reg_o, dim_o), decode
-
-    def _heads(self, plan, opts, P, pyramid, outs, decode):
-        """ the three towers (every layer one grouped launch over the five levels; layer 0 of the three shares its input: one fused
-        launch, C_out = 896, whose channel slices layers 1..3 read) and the decode launches where their inputs are complete.
-        opts.decode_overlap: classification, regression, dimension tower; the detection selection (one workgroup per image, 8 of the
-        256 CUs) only needs the logits and the corner regressions, so it runs on a side stream underneath the dimension tower, and the
-        decode of the <= 100 survivors joins when every head is done.  opts.head_lanes: the two small towers on side streams, filling
-        the ramp-up / tail phases of the big regression-tower kernels.  opts.cls_lane: the classification tower (+ the candidate pass)
-        on side lane 2 BESIDE the regression tower, whose last layer joins it. """
-        cls_o, reg_o, dim_o = outs
-        _, wide = pyramid(896)
-        # (measured and rejected: the half-empty fourth 256-column tile of this 896-wide layer as its own 128-column launch
-        # on a side stream -- the two launches do not pack into each other's partial rounds, no gain)
-        self._conv(plan, 'pyramid_towers_0', P, wide, 3, pad=(1, 1), relu=True, join=True)
-
-        def tower(prefix, width, c0, out_name, out, tag=0, lane=0, join=False):
-            src = [C.FMap(m.buf, m.B, m.H, m.W, width, off=m.off + c0, bstride=m.bstride, pitch=m.pitch, split=m.split, half=m.half)
-                   for m in wide]
-            for i in range(1, 4):
-                _, dst = pyramid(width)
-                if i == 3 and out_name == 'pyramid_regression_ops' and plan.sparse is not None and plan.sparse.tower_rows is not None:
-                    tower_last('{}_{}'.format(prefix, i), src, dst, tag, lane)
-                elif out_name == 'pyramid_regression_ops' and plan.sparse is not None and 3 - plan.sparse.deep_layers <= i < 3:
-                    tower_deep('{}_{}'.format(prefix, i), src, dst, tag, lane, 2 - i)
-                else:
-                    self._conv(plan, '{}_{}'.format(prefix, i), src, dst, 3, pad=(1, 1), relu=True, tag=tag, lane=lane)
-                src = dst
-            out_layer(out_name, src, out, lane, join)
-
-        def tower_last(name, src, dst, tag, lane):
-            """ the regression tower's last layer where its only reader is the gathered output layer (sparse_tower_form below): that launch
-            reads the map at the listed pixels and their eight neighbours, so this layer has to write the 3 x 3 dilation of the lists and
-            nothing else.  ONE op (its flops the algorithmic count, its tag the tower's): gpp_conv2d_igemm enqueues the dense launch and the
-            gathered one on the dilated lists (gpp_conv_desc.tower_rows), and the lists' flag lets exactly one of them work -- the dense one
-            whenever the output layer runs dense, which reads every row.  The op joins the candidates' lane: it is the first reader of the
-            lists.  The rows nobody reads keep whatever the buffer held; Plan.complete_heads runs the layer dense before anyone reads more. """
-            sp = plan.sparse
-            d = self._desc(plan, name, src, dst, 3, pad=(1, 1), relu=True, lane=lane)
-            d.tower_rows, d.tower_counts, d.tower_flag = sp.tower_rows.data_ptr(), sp.tower_counts.data_ptr(), sp.tower_flag.data_ptr()
-            plan.emit(OP_CONV, d, name, list(src) + [sp.tower_rows, sp.tower_counts, sp.tower_flag], dst, tag=tag, flops=C.conv_flops(d), lane=lane,
-                      join=not sp.lists_joined, io=(src, dst, None))
-            sp.lists_joined = True
-            sp.tower.append(d)
-
-        def tower_deep(name, src, dst, tag, lane, which):
-            """ layers 2 (which = 0) and 1 (which = 1) of the regression tower in a plan of the deep form (sparse_deep_layers below): the
-            only reader of layer 2 is the gathered layer 3, which reads it on the 5 x 5 neighbourhoods of the candidates' pixels, and layer 1
-            is read by the gathered layer 2 on the 7 x 7 ones.  ONE op each, as tower_last; the lists (gpp_conv_desc.deep_rows) come from
-            gpp_detect_deep_lists behind pyramid_classification on this same stream, so there is no lane to join """
-            sp = plan.sparse
-            d = self._desc(plan, name, src, dst, 3, pad=(1, 1), relu=True, lane=lane)
-            lists = [sp.deep_rows[which], sp.deep_counts[which], sp.deep_flags[which]]
-            d.deep_rows, d.deep_counts, d.deep_flag = [t.data_ptr() for t in lists]
-            plan.emit(OP_CONV, d, name, list(src) + lists, dst, tag=tag, flops=C.conv_flops(d), lane=lane, io=(src, dst, None))
-            sp.deep.append(d)
-
-        def sparse_deep_layers():
-            """ how many tower layers in front of the last one take both forms (0, 1: layer 2, 2: layers 2 and 1) -- a rule of layer, map
-            sizes, batch and plan options, like sparse_tower_form, which must hold: the lists are made on the caller's stream right behind
-            pyramid_classification, so that layer runs there, unsplit, with the candidate pass on its side lane (decode_overlap without
-            cls_lane: no head_lanes), in a plan that is neither orientation-specific nor an audit; and the dense launch of a layer fields more
-            than opts.sparse_deep_rounds rounds of workgroups """
-            if not opts.sparse_deep or opts.sparse_depth < 2 or not sparse_tower_form():
-                return 0
-            if opts.cls_lane or opts.head_lanes or self.osf or self.audit or not hasattr(hip.lib(), 'gpp_detect_deep_lists'):
-                return 0
-            rule = C.latency_split if self.plan_mode == 'latency' else C.default_split
-            pixels = sum(f.H * f.W for f in reg_o)
-            for name in ('pyramid_classification', 'pyramid_regression_1', 'pyramid_regression_2'):
-                kh, kw, cin, cout = self.conv_w[name][2]
-                if rule(kh, kw, cin, cout, pixels) > 1 or (name != 'pyramid_classification' and cout % 256):
-                    return 0
-            workgroups = sum((P[0].B * m.H * m.W + 255) // 256 for m in P) * (cout // 256)
-            if not workgroups > opts.sparse_deep_rounds * COMPUTE_UNITS:
-                return 0
-            return min(2, opts.sparse_depth - 1)
-
-        def sparse_tower_form():
-            """ whether pyramid_regression_3 takes both forms: its reader pyramid_regression_ops is gathered in this plan (out_layer's own
-            conditions), and the dense launch fields more than opts.sparse_tower_rounds rounds of 256 x 256 workgroups on the chip -- a rule
-            of (layer, map sizes, batch) like the split rule: below one round a gathered launch costs one workgroup life either way """
-            if not opts.sparse_heads or not opts.sparse_tower or not opts.decode_overlap or opts.x3_level < 1 or self.dtype not in C.X3_TYPES:
-                return False
-            kh, kw, cin, cout = self.conv_w['pyramid_regression_ops'][2]
-            split = (C.latency_split if self.plan_mode == 'latency' else C.default_split)(kh, kw, cin, cout, sum(f.H * f.W for f in reg_o))
-            kh, kw, cin, cout = self.conv_w['pyramid_regression_3'][2]
-            split3 = (C.latency_split if self.plan_mode == 'latency' else C.default_split)(kh, kw, cin, cout, sum(f.H * f.W for f in reg_o))
-            if split > 1 or split3 > 1 or cout % 256:
-                return False
-            workgroups = sum((P[0].B * m.H * m.W + 255) // 256 for m in P) * (cout // 256)
-            return workgroups > opts.sparse_tower_rounds * COMPUTE_UNITS
-
-        def out_layer(name, src, out, lane, join):
-            """ the output layer of a tower.  opts.sparse_heads, regression and dimension tower: the decode reads these maps at candidate
-            anchors only (nms_kernel, emit_kernel), and the candidate lists exist before the regression tower starts -- so the layer runs
-            in gathered-row form on the pixels gpp_detect_pixel_lists listed (gpp_conv_desc.gather_rows: byte-identical rows, nothing else
-            written).  The dense launch stays in the plan in front of it, guarded by the lists' flag: when more than max_rows rows are
-            listed it runs and the gathered one returns at once, otherwise all its workgroups return on the flag -- no host round trip
-            either way.  The first of the pair joins the candidates' lane unless a join has followed the lists already.  A layer the
-            split-K rule splits (small maps) keeps its dense launch alone: one gathered launch cannot reproduce that summation order. """
-            sp = plan.sparse
-            kh, kw, cin, cout = self.conv_w[name][2]
-            pixels = sum(f.H * f.W for f in out)
-            split = (C.latency_split if self.plan_mode == 'latency' else C.default_split)(kh, kw, cin, cout, pixels)
-            if sp is not None and sp.deep_layers and name == 'pyramid_classification':
-                # the layer that writes the logits: gpp_conv2d_igemm enqueues the deep lists behind its launch (gpp_conv_desc.lists_after) --
-                # part of this op, on this stream, in front of the tower layers that read them
-                d = self._desc(plan, name, src, out, 3, pad=(1, 1), out_f32=True, lane=lane)
-                d.lists_after = sp.register_deep(sp.deep_desc(plan.cls_logits, plan.n_anchors, anchor_utils.NUM_BASE_ANCHORS, SCORE_THRESHOLD))
-                plan.emit(OP_CONV, d, name, list(src), list(out) + sp.deep_tensors(), flops=C.conv_flops(d), lane=lane, join=join,
-                          io=(src, out, None))
-                return
-            if sp is None or name == 'pyramid_classification' or lane or split > 1:
-                self._conv(plan, name, src, out, 3, pad=(1, 1), out_f32=True, lane=lane, join=join)
-                if sp is not None and join and not lane:
-                    sp.lists_joined = True
-                return
-            dense = self._desc(plan, name, src, out, 3, pad=(1, 1), out_f32=True, lane=lane)
-            dense.guard, dense.guard_value = sp.flag.data_ptr(), 1
-            plan.emit(OP_CONV, dense, name, list(src) + [sp.flag], out, flops=C.conv_flops(dense), lane=lane, join=join or not sp.lists_joined,
-                      io=(src, out, None))
-            sp.lists_joined = True
-            rows = self._desc(plan, name, src, out, 3, pad=(1, 1), out_f32=True, lane=lane)
-            rows.gather_rows, rows.gather_counts, rows.split_k = sp.rows.data_ptr(), sp.counts.data_ptr(), 1
-            rows.guard, rows.guard_value = sp.flag.data_ptr(), 0
-            # (flops 0: Plan.flops stays the reference graph's algorithmic count, which the dense launch above carries)
-            plan.emit(OP_CONV, rows, name, list(src) + [sp.rows, sp.counts, sp.flag], out, lane=lane, io=(src, out, None))
-            sp.dense.append(dense)
-            sp.gathered.append(rows)
-
-        l_dim, l_cls = (1, 2) if opts.head_lanes else (0, 0)
-        towers = {'cls': ('pyramid_classification', 256, 512, 'pyramid_classification', cls_o, 0, l_cls or opts.cls_lane),
-                  'reg': ('pyramid_regression', 512, 0, 'pyramid_regression_ops', reg_o, 1, 0, bool(opts.cls_lane)),
-                  'dim': ('pyramid_regression_dim', 128, 768, 'pyramid_regression_dim', dim_o, 0, l_dim)}
-        if opts.sparse_heads:
-            plan.sparse = SparseHeads(self.torch, self.device, P[0].B, [m.H * m.W for m in P], opts.sparse_heads, [m.W for m in P],
-                                      opts.sparse_tower if sparse_tower_form() else 0.0)
-            plan.keep += plan.sparse.tensors()
-            layers = sparse_deep_layers()
-            if layers:
-                plan.sparse.add_deep(self.torch, layers, opts.sparse_deep)
-                plan.keep += plan.sparse.deep_tensors()
-        if opts.decode_overlap:
-            tower(*towers['cls'])
-            decode(OP_DETECT_CANDIDATE_PIXELS if plan.sparse else OP_DETECT_CANDIDATES, 'filtered_detections/candidates',
-                   lane=opts.cls_lane or 1)     # on the tower's lane when it has one
-            tower(*towers['reg'])
-            decode(OP_DETECT_SELECT, 'filtered_detections/select', lane=1, sync=True)
-            tower(*towers['dim'])
-            decode(OP_DETECT_EMIT, join=True)
-        else:
-            for t in ('dim', 'cls', 'reg'):
-                tower(*towers[t])
-            decode(OP_DETECT_OSF if self.osf else OP_DETECT, join=True)
-
-    def _poll(self, plan, B, n_planes, planes_batched):
-        """ ground-plane polling (FitRoadPlanes) of the detections """
-        torch, dev, D = self.torch, self.device, MAX_DETECTIONS
-        plan.keypoints = torch.empty((B, D, 4, 3), dtype=torch.float32, device=dev)
-        plan.keyplanes = torch.empty((B, D, 1, 4), dtype=torch.float32, device=dev)
-        plan.residuals = torch.empty((B, D), dtype=torch.float32, device=dev)
-        plan.best_index = torch.empty((B, D), dtype=torch.int32, device=dev)
-        need = hip.c_size_t(0)
-        hip.check(hip.lib().gpp_poll_workspace_bytes(B, n_planes, int(planes_batched), need), 'gpp_poll_workspace_bytes')
-        plan.poll_ws = torch.empty((max(int(need.value), 16),), dtype=torch.uint8, device=dev)
-        pd = PollDesc(plan.boxes.data_ptr(), plan.dimensions.data_ptr(), plan.orientations.data_ptr(), plan.P_inv.data_ptr(),
-                      plan.planes.data_ptr(), plan.keypoints.data_ptr(), plan.keyplanes.data_ptr(), plan.residuals.data_ptr(),
-                      plan.best_index.data_ptr(), plan.poll_ws.data_ptr(), plan.poll_ws.numel(), B, D, n_planes,
-                      int(planes_batched), POLL_THRESHOLD, 0)
-        plan.emit(OP_POLL, pd, 'fit_road_planes', [plan.boxes, plan.dimensions, plan.orientations, plan.P_inv, plan.planes],
-                  [plan.keypoints, plan.keyplanes, plan.residuals, plan.best_index, plan.poll_ws], tag=2,    # tag 2: bench.py times it live too
-                  flops=162.0 * B * D * n_planes)
-
-    def _pose(self, plan, B):
-        """ 6-DoF pose + KITTI fields of the detections (what bin/run_network.py does on the host after predict_on_batch), on lane 0
-        behind the polling.  Rows, range-event snapshot and counts share ONE flat buffer, so that one copy brings a call's result to
-        the host: [B x D x 36 rows | 2 words: the plan's range counter as the stream saw it | B counts (int32 bits)]. """
-        torch, dev, D = self.torch, self.device, MAX_DETECTIONS
-        n = B * D * hip.GPP_POSE_COLS
-        plan.pose_out = torch.zeros((n + 2 + B,), dtype=torch.float32, device=dev)
-        plan.pose_rows = plan.pose_out[:n].view(B, D, hip.GPP_POSE_COLS)
-        plan.pose_counts = plan.pose_out[n + 2:].view(torch.int32)
-        # per image: the image scale, the raw image's height and width (predict_poses_*: uploaded with P_inv; a captured graph reads
-        # the buffer, not the values).  Until a caller says otherwise: the frame as it is, scale 1
-        plan.frame_info = torch.tensor([[1.0, plan.shape[1], plan.shape[2]]] * B, dtype=torch.float32, device=dev)
-        pd = PoseDesc(plan.boxes.data_ptr(), plan.dimensions.data_ptr(), plan.scores.data_ptr(), plan.labels.data_ptr(),
-                      plan.orientations.data_ptr(), plan.keypoints.data_ptr(), plan.residuals.data_ptr(), plan.frame_info.data_ptr(),
-                      plan.pose_rows.data_ptr(), plan.pose_counts.data_ptr(), B, D, POSE_SCORE_THRESHOLD, 0)
-        plan.emit(OP_POSE, pd, 'recover_pose', [plan.boxes, plan.dimensions, plan.scores, plan.labels, plan.orientations, plan.keypoints,
-                                                plan.residuals, plan.frame_info], [plan.pose_rows, plan.pose_counts])
-
-    def _cuboid_nms(self, plan, B):
-        """ cuboid_nms=(metric, threshold): the greedy NMS of the cuboids (gpp_cuboid_nms_f64) on lane 0 behind the pose op, in place on
-        its rows and counts; plan.pose_suppressor (B, D) int32 names the kept row that removed each suppressed one """
-        metric, threshold = self.cuboid_nms
-        D = MAX_DETECTIONS
-        plan.pose_suppressor = self.torch.full((B, D), -1, dtype=self.torch.int32, device=self.device)
-        nd = CuboidNmsDesc(plan.pose_rows.data_ptr(), plan.pose_counts.data_ptr(), plan.pose_suppressor.data_ptr(), threshold, B, D,
-                           cuboid_nms_utils.metric_code(metric), 0)
-        plan.emit(OP_CUBOID_NMS, nd, 'suppress_cuboids', [plan.pose_rows], [plan.pose_rows, plan.pose_counts, plan.pose_suppressor])
-
-    def _audit(self, plan):
-        """ range_audit=True: one gpp_channel_absmax launch behind every launch that writes (a part, a level or a channel slice of) a map
-        that some convolution of the plan reads as its activation operand or adds as its residual -- the maps an x3 loop splits into
-        (hi, lo) halves or reads pre-split -- on that launch's lane, into the map's row of plan.audit_table; the first op of the plan
-        clears the table on the stream.  A map is a channel range of a buffer as its READERS name it (the three towers read three
-        slices of the fused first layer's 896 channels: three maps; the five levels of a pyramid tensor: one map).  Placed once every
-        op is known: who reads what is only known then.  Operands that never exist in HBM go to plan.audit_unobserved. """
-        torch, esz = self.torch, self.esz
-        views, order = {}, []                       # (buffer, pitch, first channel, channels) -> record
-
-        def key_of(f):
-            return (f.buf.data_ptr(), f.pitch, f.off % f.pitch, f.C)
-
-        for pos, (kind, _, desc, name, _) in enumerate(plan.ops):
-            io = plan.op_io[pos]
-            if kind == OP_CONV_PREACT:
-                lo, hi = min(a for a, _ in Plan.spans(io[0])), max(b for _, b in Plan.spans(io[0]))
-                plan.audit_unobserved.append({'name': name + '/operand', 'consumers': [name], 'extent': (lo, hi),
-                                              'reason': 'max(x * scale + shift, 0) is formed after the load (gpp_conv2d_preact)'})
-            elif kind == OP_MOBILENET_BLOCK:
-                plan.audit_unobserved.append({'name': name.replace('conv_pw_', 'conv_dw_'), 'consumers': [name], 'extent': None,
-                                              'reason': 'the depthwise result lives in LDS (gpp_mobilenet_block); bounded by ReLU6'})
-            elif kind == OP_CONV:
-                for f in list(io[0]) + list(io[2] or []):
-                    k = key_of(f)
-                    if k not in views:
-                        views[k] = {'consumers': [], 'producers': [], 'channels': f.C, 'spans': [], 'fmaps': [], 'split': f.split,
-                                    'layout': 'split_f16' if f.split else 'f32'}
-                        order.append(k)
-                    if name not in views[k]['consumers']:
-                        views[k]['consumers'].append(name)
-                    views[k]['spans'] += Plan.span(f)
-                    if not any((g.off, g.B, g.H, g.W) == (f.off, f.B, f.H, f.W) for g in views[k]['fmaps']):
-                        views[k]['fmaps'].append(f)
-        offset = 0
-        for k in order:
-            views[k]['row'] = (offset, k[3])
-            offset += k[3]
-        plan.audit_table = table = torch.zeros((max(offset, 1),), dtype=torch.int32, device=self.device)       # (uint32 bit patterns)
-        extra = {}
-        for pos, (kind, _, desc, name, _) in enumerate(plan.ops):
-            for k in order:
-                ptr, pitch, c0, c = k
-                outs = [o for o in plan.wrote[pos] if o.buf.data_ptr() == ptr and o.pitch == pitch]
-                if not outs:
-                    continue
-                oc0, oc = outs[0].off % pitch, outs[0].C
-                lo, hi = max(c0, oc0), min(c0 + c, oc0 + oc)
-                if lo >= hi:
-                    continue
-                v = views[k]
-                if name not in v['producers']:
-                    v['producers'].append(name)
-                # the pixels this launch wrote, as runs of consecutive pixels of the buffer (a dense batch, the five levels of every
-                # image of a pyramid tensor: one run; one level of a pyramid tensor: one run per image)
-                runs = []
-                for start, n in sorted(((o.off - oc0 + b * o.bstride) // pitch, o.H * o.W) for o in outs for b in range(o.B)):
-                    if runs and runs[-1][0] + runs[-1][1] == start:
-                        runs[-1][1] += n
-                    else:
-                        runs.append([start, n])
-                row = table[v['row'][0] + lo - c0:v['row'][0] + hi - c0]
-                for start, n in runs:
-                    d = hip.AbsmaxDesc(ptr + start * pitch * esz, row.data_ptr(), n, pitch, hi - lo, lo,
-                                       hip.GPP_ABSMAX_SPLIT_F16 if v['split'] else hip.GPP_ABSMAX_F32, 0)
-                    extra.setdefault(pos, []).append((OP_ABSMAX, d, 'absmax:' + name, outs, [row]))
-        plan.insert_behind(extra)
-        plan.keep.append(table)
-        clear = hip.AbsmaxClearDesc(table.data_ptr(), table.numel())
-        plan.emit(OP_ABSMAX_CLEAR, clear, 'absmax:clear', [], [table])
-        for lst in (plan.ops, plan.lanes, plan.access, plan.atomic, plan.wrote, plan.op_io):       # ... as the FIRST op of the plan
-            lst.insert(0, lst.pop())
-        for k in order:
-            v = views[k]
-            names = v['producers']
-            if not names:
-                raise RuntimeError('range audit: no launch of the plan writes the operand of {}'.format(v['consumers']))
-            # a channel slice of a launch's output carries the name of the layer it is in the reference (the fused first tower layer)
-            name = TOWER_SLICES.get((names[0], k[2]), names[0]) if len(names) == 1 else \
-                '+'.join(sorted(names)) if len(names) <= 5 else '{}..{}'.format(names[0], names[-1])
-            plan.audit_maps.append({'name': name, 'producers': names, 'consumers': v['consumers'], 'channels': v['channels'],
-                                    'layout': v['layout'], 'row': v['row'], 'fmaps': v['fmaps'],
-                                    'extent': (min(a for a, _ in v['spans']), max(b for _, b in v['spans']))})
-
-    def _bind_workspaces(self, plan):
-        """ split-K partial tiles of the deep-K layers with a tiny per-image grid (res5 branch2b, P5..P7): one workspace per stream lane
-        (concurrent launches must not share partial tiles), sized from the descriptors of the whole plan """
-        plan.workspaces = {lane: self.torch.empty((max(need, 16),), dtype=self.torch.uint8, device=self.device)
-                           for lane, need in plan.ws_need.items()}
-        for d, lane in plan.conv_descs:
-            d.partial = plan.workspaces[lane].data_ptr()
-            d.partial_bytes = plan.workspaces[lane].numel()
-
     def _plan_options(self, B):
-        """ every GPP_* switch of the plan builder, read once per plan (at the start of _build), as its effective value for this model
-        and batch (PlanOptions) """
-        env = os.environ.get
-        x3 = self.dtype in C.X3_TYPES
-        # x3 types: maps written and read by convolutions only are stored PRE-SPLIT ([32 hi | 32 lo] halves per 32 channels,
-        # gpp_conv_desc.x3_split): GPP_X3_SPLIT=2 (default) every such map, 1 = only the maps between the FPN / head layers -- 80 % of the
-        # FLOPs, all of them matrix-pipe bound -- 0 = none.  Written that way by the producing layer's epilogue, read by the consumers
-        # without the per-fragment split on the vector ALU.
-        x3_level = int(env('GPP_X3_SPLIT', '2')) if x3 else 0
-        # GPP_STAGE_CHUNKS="2,4,8,8": a stage chunk of images by chunk of images, to keep a chunk's working set inside the 256 MiB Infinity
-        # Cache; measured on MI355X at B = 8 this LOSES 1-6 % (the smaller launches cost more than the on-die re-reads save): off
-        chunks = env('GPP_STAGE_CHUNKS')
-        # GPP_FUSE_TAIL: widths whose branch2b + branch2c run as one launch ("" or 0 for none).  Measured at B = 8, same box, whole step:
-        # none 1553, res3 only 1562, res2 + res3 1571 images/s (in isolation the fused res2 launch is no faster than its two layers --
-        # 122 us vs 36 + 80 -- but the step is: 69 MB less through HBM per block).  The x3 form (bottleneck_tail_x3_kernel) reads
-        # pre-split maps at C = 64 (res2) only -- at C = 128 its LDS footprint leaves one workgroup per CU; float32 operands: none
-        fuse_tail = [int(v) for v in env('GPP_FUSE_TAIL', '64,128').split(',') if v.strip() and int(v) > 0]
-        if x3:
-            fuse_tail = [v for v in fuse_tail if v == 64] if x3_level >= 2 else []
-        elif self.esz == 4:
-            fuse_tail = []
-        # GPP_FUSE_BLOCK: widths whose IDENTITY blocks (branch2a + 2b + 2c + shortcut) run as one launch (gpp_bottleneck_block; x3 types on
-        # pre-split maps): res2 (C = 64: 4-wavefront workgroups, two per CU; x in once, y out once: 245 -> 212 us per block at B = 8) and
-        # res3 (C = 128: 8 wavefronts, one per CU; at parity with its three launches in isolation, half their fabric bytes).  Same-box A/B
-        # of the step (profiles/r6/ab_fuse_block_*.txt): B = 8: 780 -> 793 images/s (+1.7 %) with both, +0.9 % with res2 alone; B = 4
-        # +1.2 %, B = 2 +0.7 %, batch-1 plan 2.67 -> 2.65 ms.  "" for the separate launches (bit-identical either way).  Projection
-        # blocks too (GPP_FUSE_BLOCK_PROJ=1) measured -0.6 %: off.
-        fuse_block = [int(v) for v in env('GPP_FUSE_BLOCK', '64,128').split(',') if v.strip()] if (x3 and x3_level >= 2) else []
-        if self.audit:
-            # an audit plan reads every operand map in HBM: the separate launches wherever a fused form keeps one in LDS (bit-identical
-            # to them: tests/test_block_gpu.py), so the results do not change
-            fuse_tail, fuse_block = [], []
-        head_lanes = env('GPP_HEAD_LANES', '0') != '0'
-        fpn_lanes = head_lanes or env('GPP_FPN_LANES', '1') != '0'
-        overlap = env('GPP_DECODE_OVERLAP', '1') != '0' and not head_lanes and not self.osf
-        return PlanOptions(
-            x3_level=x3_level,
-            fuse_stem_pool=not self.densenet and not self.mobilenet and (self.esz == 2 or self.stem_x3) and env('GPP_FUSE_STEM_POOL', '1') != '0',
-            stage_chunks=tuple(max(1, min(B, int(v))) for v in chunks.split(',')) if chunks else (B,) * 4,
-            # GPP_HALF_LANES (default "0,1,2,3" = res2 .. res5; "" for whole batches): a launch of these stages fills the 256 CUs 0.7 - 1.4
-            # times and is bound by tile fills and first-touch latency; two half-batch chains in flight overlap one's prologue / epilogue /
-            # barrier waits with the other's main loop (f16x3 step, same box: 775 -> 793 images/s; three parts: 801 against 811).  res2
-            # since round 6, with fused identity blocks: B = 8 +0.7 %, B = 4 +1.1 %, B = 2 +1.1 % (profiles/r6/ab_half_lanes_with_blocks.txt)
-            half_stages=frozenset(int(v) for v in env('GPP_HALF_LANES', '0,1,2,3').split(',') if v.strip()) if B >= 2 else frozenset(),
-            fuse_tail=tuple(v for v in fuse_tail if v in (64, 128)),
-            fuse_block=tuple(v for v in fuse_block if v in (64, 128)),
-            fuse_block_proj=env('GPP_FUSE_BLOCK_PROJ', '0') != '0',
-            # GPP_FUSE_BLOCK_INPROJ (default 1; with 64 in GPP_FUSE_BLOCK): res2a -- the stride-1 projection block -- as ONE launch that computes the
-            # shortcut itself (gpp_bottleneck_block_proj): no res2a_branch1 launch, no shortcut map through HBM (276 MB written and read back at
-            # B = 8).  Only where a batch part's launch fields more than GPP_FUSE_INPROJ_MIN_ROUNDS rounds of 2 x 256 workgroups of 8 x 14 pixels
-            # (a rule of layer, map size and batch part); 0 = res2a as three launches.  Bit-identical either way.
-            fuse_block_inproj=env('GPP_FUSE_BLOCK_INPROJ', '1') != '0',
-            fuse_inproj_rounds=float(env('GPP_FUSE_INPROJ_MIN_ROUNDS', FUSE_INPROJ_MIN_ROUNDS)),
-            br1_lane=env('GPP_BR1_LANE', '1') != '0',           # measured +0.4 % on the f16x3 step (same box, alternating)
-            fpn_lanes=fpn_lanes,
-            p4_lane=1 if (fpn_lanes and env('GPP_P4_LANE', '1') != '0') else 0,
-            head_lanes=head_lanes,
-            decode_overlap=overlap,
-            # GPP_CLS_LANE (default: on for B <= 2): at batch 1 a tower launch fields 0.9 - 1.9 rounds of workgroups of one wavefront per
-            # SIMD: two independent chains in flight fill the other half of every SIMD (measured: profiles/r5/b1_latency.json, field
-            # `plan_variants`); at batch 8 every launch fills the chip on its own (off)
-            cls_lane=2 if (overlap and env('GPP_CLS_LANE', '1' if B <= 2 else '0') != '0') else 0,
-            autotune=env('GPP_AUTOTUNE', '1') != '0',
-            # GPP_SPARSE_HEADS (default 1; needs the decode overlap, whose candidate lists exist before the regression tower): the output
-            # layers of the regression and dimension towers on the candidates' pixels only.  The value of the field is the largest share of
-            # all pyramid pixels the gathered launches take (GPP_SPARSE_HEADS_MAX_SHARE; beyond it the dense launches run: the device
-            # decides, per step); 0.0 = off.  An audit plan keeps the dense launches.
-            sparse_heads=(max(1e-9, float(env('GPP_SPARSE_HEADS_MAX_SHARE', SPARSE_HEADS_MAX_SHARE)))
-                          if (overlap and not self.audit and env('GPP_SPARSE_HEADS', '1') != '0') else 0.0),
-            # GPP_SPARSE_TOWER (default 1; with sparse head outputs only): the regression tower's LAST layer on the 3 x 3 dilation of the
-            # candidates' pixels -- the only rows its reader, the gathered output layer, takes.  The value is the largest share of all
-            # pyramid pixels the gathered launch takes (GPP_SPARSE_TOWER_MAX_SHARE); GPP_SPARSE_TOWER_MIN_ROUNDS: the rounds of workgroups
-            # the dense launch must exceed (0 in tests: small plans take the form too)
-            sparse_tower=(max(1e-9, float(env('GPP_SPARSE_TOWER_MAX_SHARE', SPARSE_TOWER_MAX_SHARE)))
-                          if (overlap and not self.audit and env('GPP_SPARSE_HEADS', '1') != '0' and env('GPP_SPARSE_TOWER', '1') != '0') else 0.0),
-            sparse_tower_rounds=float(env('GPP_SPARSE_TOWER_MIN_ROUNDS', SPARSE_TOWER_MIN_ROUNDS)),
-            # GPP_SPARSE_TOWER_DEPTH (default 3; with the sparse tower only): how many layers of the regression tower run on the rows their
-            # reader takes -- 1 the last layer alone, 2 layer 2 as well (the 5 x 5 dilation of the candidates' pixels), 3 layer 1 too (7 x 7).
-            # The lists of layers 2 and 1 are made from the logits on the caller's stream (gpp_detect_deep_lists);
-            # GPP_SPARSE_TOWER_DEEP_MAX_SHARE: the largest share of rows their gathered launches take; GPP_SPARSE_TOWER_DEEP_MIN_ROUNDS: the
-            # rounds of workgroups their dense launch must exceed (its own variable: tests force the tower's to 0 at small shapes)
-            sparse_deep=max(1e-9, float(env('GPP_SPARSE_TOWER_DEEP_MAX_SHARE', SPARSE_TOWER_DEEP_MAX_SHARE))),
-            sparse_deep_rounds=float(env('GPP_SPARSE_TOWER_DEEP_MIN_ROUNDS', SPARSE_TOWER_DEEP_MIN_ROUNDS)),
-            sparse_depth=int(env('GPP_SPARSE_TOWER_DEPTH', SPARSE_TOWER_DEPTH)),
-            tune_key='x3split={};fuse={}/{};plan={}{}'.format(env('GPP_X3_SPLIT', '2'), env('GPP_FUSE_TAIL', '64,128'), env('GPP_FUSE_BLOCK', '64,128'),
-                                                              self.plan_mode, C.latency_split_config() if self.plan_mode == 'latency' else '') +
-                     (';audit' if self.audit else '') + ('' if env('GPP_FUSE_BLOCK_INPROJ', '1') != '0' else ';inproj=0'))      # (the default keeps its key)
+        """ every GPP_* switch of the plan builder as its effective value for this model and batch (models/plan.py) """
+        return plan_options(self, B)
 
     def _build(self, B, H, Wd, n_planes, planes_batched, ragged=False):
         """ ragged: the plan of a height class (utils/image.py) -- H = 4 Hp is the row count of the canvas, and the stem and pool1 take
         every image's own height from plan.heights (int32, on the device: data of the plan, so one plan and one captured graph serve
         every mix of heights); everything behind pool1 is the uniform plan's """
-        torch, dev = self.torch, self.device
         if ragged:
             if self.mobilenet or self.densenet:
                 raise ValueError('{} has no ragged form: {}; run its images grouped by shape'.format(
@@ -939,257 +246,15 @@ class RetinaNet3D(object):
                 raise ValueError('range_audit=True has no ragged form: the audit of the conv1 map reads rows that a shorter image does not have')
             if H % 4:
                 raise ValueError('the canvas of a ragged plan has 4 Hp rows, got {}'.format(H))
-        opts = self._plan_options(B)
-        plan = Plan()
-        plan.shape = (B, H, Wd, n_planes, planes_batched)
-        plan.ragged = bool(ragged)
-        if ragged:
-            plan.heights = torch.full((B,), H, dtype=torch.int32, device=dev)
-            plan.heights_host = [H] * B
-        plan.side_lanes = {'fpn': opts.fpn_lanes, 'branch1': opts.br1_lane, 'p4': bool(opts.p4_lane),
-                           'half_batch_stages': sorted(opts.half_stages), 'cls_tower': bool(opts.cls_lane)}
-        plan.decode_overlap = opts.decode_overlap
-        # dtype='f16x3': the 8-byte counter every launch of THIS plan adds its range events to (gpp_conv_desc.range_counter, gpp_stem_desc.range_counter),
-        # never reset by anyone but x3_range_events(reset=True) of this model; range_seen = its value when a result of the plan was last fetched
-        plan.range_slot = torch.zeros((1,), dtype=torch.int64, device=dev)
-        plan.range_seen = 0
-        plan.images = torch.empty((B, H, Wd, 3), dtype=torch.float32, device=dev)
-        plan.P_inv = torch.empty((B, 4, 3), dtype=torch.float32, device=dev)
-        plan.planes = torch.empty((B, n_planes, 4) if planes_batched else (n_planes, 4), dtype=torch.float32, device=dev)
-
-        def fmap(h, w, c, split=False):
-            f = C.FMap.empty(B, h, w, c, self.tdtype, dev, half=self.dtype if self.dtype in C.X3_TYPES else 'bf16x3')
-            plan.keep.append(f.buf)
-            return f.mark_split() if split else f
-
-        backbone = self._densenet_backbone if self.densenet else self._mobilenet_backbone if self.mobilenet else self._resnet_backbone
-        C2, C3, C4, C5 = backbone(plan, opts, B, H, Wd, fmap, lambda h, w, c: fmap(h, w, c, opts.x3_level >= 2))
-        plan.features = {'stem': plan.stem_out, 'C2': C2, 'C3': C3, 'C4': C4, 'C5': C5}
-        shapes, pyramid = self._pyramid(plan, opts, B, H, Wd, C3, C4, C5)
-        P = self._fpn(plan, opts, C3, C4, C5, pyramid, lambda h, w, c: fmap(h, w, c, opts.x3_level >= 1))
-        plan.features.update({'P{}'.format(i + 3): P[i] for i in range(5)})
-        outs, decode = self._detect(plan, B, self._anchor_table((H, Wd), shapes if self.densenet else None), pyramid)
-        self._heads(plan, opts, P, pyramid, outs, decode)
-        self._poll(plan, B, n_planes, planes_batched)
-        if self.pose:
-            self._pose(plan, B)
-        if self.cuboid_nms is not None:
-            self._cuboid_nms(plan, B)
-        if self.audit:
-            self._audit(plan)
-        self._bind_workspaces(plan)
-        plan.finalize()
-        plan.tagged = [name for _, tag, _, name, _ in plan.ops if tag]
-        if opts.autotune:
+        builder = PlanBuilder(self, B, H, Wd, n_planes, planes_batched, ragged)
+        plan = builder.build()
+        if builder.opts.autotune:
             self._autotune(plan)
         return plan
 
-    # ------------------------------------------------------------------ per-layer tile selection
-    def _tune_cache_path(self):
-        return os.environ.get('GPP_TUNE_CACHE')
-
-    def _tune_config(self):
-        """ what a cached tile choice is valid for besides (backbone, type, layer, batch, image size): the build of the library (tile codes
-        come and go with it: gpp_version() carries a hash of the kernel sources) and the plan options that change which maps are
-        pre-split or fused (PlanOptions.tune_key, the same at every batch) -- a tile timed on a float32 map may not even exist for the
-        pre-split form of the same layer """
-        ver = hip.lib().gpp_version().decode().split('src:')[-1]
-        return 'v2;{};{}'.format(ver, self._plan_options(1).tune_key)
-
-    def _load_tune_cache(self):
-        path = self._tune_cache_path()
-        if path and os.path.exists(path):
-            with open(path) as f:
-                for key, val in json.load(f).items():
-                    parts = key.split('|')
-                    if len(parts) != 7:              # (files of rounds 1-3: no library hash in the key -- ignored, the layers are timed again)
-                        continue
-                    cfg, bb, dt, name, b, h, w = parts
-                    if cfg == self._tune_config() and bb == self.backbone_name and dt == self.dtype:
-                        self._tuned[(name, int(b), int(h), int(w))] = (int(val[0]), float(val[-1]))
-
-    def _save_tune_cache(self):
-        """ Rank 0 only, through a temporary file + os.replace: readers never see a torn file, ranks never race. """
-        path = self._tune_cache_path()
-        if not path or int(os.environ.get('RANK', '0')) != 0:
-            return
-        data = {}
-        if os.path.exists(path):
-            try:
-                with open(path) as f:
-                    data = json.load(f)
-            except ValueError:
-                data = {}
-        for (name, b, h, w), val in self._tuned.items():
-            data['|'.join([self._tune_config(), self.backbone_name, self.dtype, name, str(b), str(h), str(w)])] = list(val)
-        tmp = '{}.tmp.{}'.format(path, os.getpid())
-        with open(tmp, 'w') as f:
-            json.dump(data, f, indent=0, sort_keys=True)
-        os.replace(tmp, path)
-
     def _autotune(self, plan):
-        """ Choose the block tile of every conv layer of this plan by timing the candidates on the device
-        (gpp_conv2d_autotune), layer by layer on realistic activations (a noise frame pushed through the layers
-        before).  Whether a layer's tile grid fills the 256 CUs in 1.07 or 0.95 rounds decides its time by up to 1.5x
-        and is cheap to measure.  The tile NEVER changes a result (same K order per output element,
-        test_every_tile_gives_identical_results), so ranks and plans may choose differently without any effect on the
-        outputs; split-K, which would, is not tuned (gpp_conv2d_split_rule).  Choices are remembered per (layer, batch,
-        image size) and can be persisted with GPP_TUNE_CACHE=<file.json>.  GPP_AUTOTUNE=0 keeps the library heuristic.
-        The fused tails choose their row count (tile_rows), DenseNet's pre-activation convs the tile of their inner conv, MobileNet's
-        blocks their own tile_hint. """
-        self._require_hip()
-        H, Wd = plan.shape[1:3]
-        plan.images.uniform_(-120.0, 130.0)
-        fresh = False
-        plan.tuning = {}
-        # GPP_TUNE_RANDOM=<seed> (tests / tools/first_run_stress.py): every layer takes a RANDOM tile among those the library
-        # accepts for it instead of the fastest one -- the outputs may not change by a bit, whatever the draw
-        rnd = None
-        if os.environ.get('GPP_TUNE_RANDOM'):
-            import random
-            rnd = random.Random(int(os.environ['GPP_TUNE_RANDOM']) * 1000003 + int(os.environ.get('RANK', '0')))
-        for index, (kind, _, desc, name, flops) in enumerate(plan.ops):
-            if kind in DETECT_OPS or kind == OP_POLL:
-                continue
-            gathered = kind == OP_CONV and bool(desc.gather_rows)
-            if kind == OP_CONV and desc.guard:
-                # a guarded pair of the sparse head outputs: the dense launch is timed with the flag set, the gathered one with the flag
-                # clear on a synthetic list of every 8th pixel (a run's own lists do not exist yet: the decode ops are not run here)
-                plan.sparse.flag.fill_(0 if gathered else 1)
-                if gathered:
-                    plan.sparse.put_every_nth(self.torch)
-                    name = name + '@rows'
-            self.run_op(plan, index)
-            if kind not in (OP_CONV, OP_TAIL, OP_CONV_PREACT, OP_MOBILENET_BLOCK):
-                continue
-            # where the choice is written: the conv's own descriptor, the pre-activation's inner one, the tail's row count
-            target = plan.inner[id(desc)][0] if kind == OP_CONV_PREACT else desc
-            field = 'tile_rows' if kind == OP_TAIL else 'tile_hint'
-            if rnd is not None:
-                setattr(target, field, rnd.choice(self._tile_choices(plan, index, kind, target)))
-                plan.tuning[name] = (int(getattr(target, field)), 0.0)
-                self.run_op(plan, index)
-                continue
-            key = (name, target.B if kind == OP_MOBILENET_BLOCK else (plan.inner[id(desc)][0] if kind == OP_TAIL else target).batch, H, Wd)     # (a half-batch launch is tuned as what it is)
-            if kind == OP_CONV and key in self._tuned and not self._tile_is_listed(desc, self._tuned[key][0]):
-                del self._tuned[key]                 # a remembered tile this build does not offer for this layer: time the layer again
-            if key not in self._tuned:
-                self._tuned[key] = self._time_tiles(plan, index, kind, desc, target, flops)
-                fresh = True
-            setattr(target, field, self._tuned[key][0])
-            plan.tuning[name] = self._tuned[key]
-            plan.tuning_parts.setdefault(name, []).append(self._tuned[key])
-            if kind == OP_CONV and desc.tower_rows:
-                # a layer of both forms: the dense tile was timed above (the lists' flag is 1 outside a run); the gathered tiles on a synthetic
-                # list of every THIRD pixel -- between what real frames list and the crossover -- with the flag clear
-                rows_key = (name + '@rows',) + key[1:]
-                if rows_key in self._tuned and self._tuned[rows_key][0] not in self._tower_tiles(desc):
-                    del self._tuned[rows_key]
-                if rows_key not in self._tuned:
-                    self._tuned[rows_key] = self._time_tower_tiles(plan, index, desc)
-                    fresh = True
-                desc.tower_tile = self._tuned[rows_key][0]
-                plan.tuning[name + '@rows'] = self._tuned[rows_key]
-        if plan.sparse is not None:
-            for d in plan.sparse.deep:           # the same layer shape as the last layer: the tile its gathered launches were timed to
-                d.deep_tile = plan.sparse.tower[0].tower_tile
-            plan.sparse.reset(self.torch)
-        self.torch.cuda.synchronize()
-        if fresh:
-            self._save_tune_cache()
-
-    def _tile_choices(self, plan, index, kind, target):
-        """ the tiles one op can take: the fused tail's row counts, the pre-activation conv's candidates, or the conv's candidates that its
-        launcher accepts for this shape (a trial launch each: a candidate the launcher refuses is skipped, as the autotuner does) """
-        if kind == OP_TAIL:
-            return (64, 96, 128, 160) if self.dtype in C.X3_TYPES else (96, 128, 160)
-        lib, tiles, count = hip.lib(), (ctypes.c_int * 32)(), ctypes.c_int(0)
-        if kind == OP_MOBILENET_BLOCK:
-            hip.check(lib.gpp_mobilenet_block_tile_candidates(ctypes.byref(target), tiles, 16, ctypes.byref(count)),
-                      'gpp_mobilenet_block_tile_candidates')
-            return list(tiles[:min(count.value, 16)])
-        if kind == OP_CONV_PREACT:
-            hip.check(lib.gpp_conv2d_preact_tile_candidates(ctypes.byref(target), tiles, 16, ctypes.byref(count)),
-                      'gpp_conv2d_preact_tile_candidates')
-            return list(tiles[:min(count.value, 16)])
-        hip.check(lib.gpp_conv2d_tile_candidates(ctypes.byref(target), tiles, 32, ctypes.byref(count)), 'gpp_conv2d_tile_candidates')
-        ok = []
-        for tile in tiles[:count.value]:
-            target.tile_hint = tile
-            if lib.gpp_plan_run(ctypes.byref(plan.array, index * ctypes.sizeof(PlanOp)), 1, hip.stream_ptr(), None, 0) == 0:
-                ok.append(tile)
-        return ok
-
-    def _time_tiles(self, plan, index, kind, desc, target, flops):
-        """ (tile, us) of the fastest choice of one op: the fused tail's row counts timed here (GPP_TAIL64=0: not 64), the conv tiles by
-        the library -- fewer launches per candidate for the float32 path, whose launches are 3 x as long (round 4: the x3 types on those
-        counts rested a big layer's choice on four launches per candidate, and one tuning run in ~60 picked a tile that cost 5 %) """
-        if kind == OP_TAIL:
-            times = {}
-            for rows in self._tile_choices(plan, index, kind, target):
-                if rows == 64 and os.environ.get('GPP_TAIL64', '1') == '0':
-                    continue
-                desc.tile_rows = rows
-                e0, e1 = self.torch.cuda.Event(enable_timing=True), self.torch.cuda.Event(enable_timing=True)
-                self.run_op(plan, index)
-                e0.record()
-                for _ in range(16):
-                    self.run_op(plan, index)
-                e1.record()
-                e1.synchronize()
-                times[rows] = e0.elapsed_time(e1) * 1000.0 / 16
-            rows = min(times, key=times.get)
-            return rows, round(times[rows], 2)
-        slow = self.dtype == 'f32'
-        iters = (2 if slow else 6) if flops > 5e10 else (4 if slow else 16)
-        best = ctypes.c_float(0.0)
-        if kind == OP_MOBILENET_BLOCK:
-            hip.check(hip.lib().gpp_mobilenet_block_autotune(ctypes.byref(target), iters, hip.stream_ptr(), ctypes.byref(best)),
-                      'gpp_mobilenet_block_autotune')
-        elif kind == OP_CONV_PREACT:
-            hip.check(hip.lib().gpp_conv2d_preact_autotune(ctypes.byref(target), desc.in_scale, desc.in_shift, iters, hip.stream_ptr(),
-                                                           ctypes.byref(best)), 'gpp_conv2d_preact_autotune')
-        else:
-            hip.check(hip.lib().gpp_conv2d_autotune(ctypes.byref(target), iters, hip.stream_ptr(), ctypes.byref(best)), 'gpp_conv2d_autotune')
-        return int(target.tile_hint), round(float(best.value), 2)
-
-    @staticmethod
-    def _tower_tiles(desc):
-        """ the tiles the gathered launch of a layer of both forms may take: the library's candidates for the layer as a gathered one """
-        rows = type(desc).from_buffer_copy(desc)
-        rows.gather_rows, rows.gather_counts = desc.tower_rows, desc.tower_counts
-        rows.tower_rows = rows.tower_counts = rows.tower_flag = None
-        rows.tower_tile, rows.split_k = 0, 1
-        tiles, count = (ctypes.c_int * 32)(), ctypes.c_int(0)
-        hip.check(hip.lib().gpp_conv2d_tile_candidates(ctypes.byref(rows), tiles, 32, ctypes.byref(count)), 'gpp_conv2d_tile_candidates')
-        return [t for t in tiles[:min(count.value, 32)] if t]
-
-    def _time_tower_tiles(self, plan, index, desc, iters=8):
-        """ (tile, us) of the fastest gathered tile of a layer of both forms, on every third pixel; the flag is 1 again afterwards """
-        sp, torch = plan.sparse, self.torch
-        sp.put_every_nth(torch, 3, tower=True)
-        sp.tower_flag.fill_(0)
-        times = {}
-        for tile in self._tower_tiles(desc):
-            desc.tower_tile = tile
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            self.run_op(plan, index)
-            e0.record()
-            for _ in range(iters):
-                self.run_op(plan, index)
-            e1.record()
-            e1.synchronize()
-            times[tile] = e0.elapsed_time(e1) * 1000.0 / iters
-        sp.tower_flag.fill_(1)
-        sp.tower_counts.zero_()
-        tile = min(times, key=times.get)
-        return tile, round(times[tile], 2)
-
-    @staticmethod
-    def _tile_is_listed(desc, tile):
-        tiles, count = (ctypes.c_int * 64)(), ctypes.c_int(0)
-        hip.check(hip.lib().gpp_conv2d_tile_candidates(ctypes.byref(desc), tiles, 64, ctypes.byref(count)), 'gpp_conv2d_tile_candidates')
-        return int(tile) in list(tiles[:min(count.value, 64)])
+        """ the tile of every layer of the plan, timed on the device or remembered (models/tuning.py) """
+        tuning.autotune(self, plan)
 
     def x3_range_events(self, reset=False):
         """ dtype='f16x3': how many 8-channel groups the epilogues of THIS model's plans have stored with a value outside the half range (a finite

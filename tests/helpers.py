@@ -62,7 +62,7 @@ def bits_equal(a, b):
     return a.shape == b.shape and bool(np.all((a == b) | (np.isnan(a) & np.isnan(b))))
 
 
-# every switch of the plan builder (GPP_* variables read by RetinaNet3D._build): the GPU test runs each against the one-stream plan
+# every switch of the plan builder (GPP_* variables read by models/plan.plan_options when a plan is built): the GPU test runs each against the one-stream plan
 # (tests/test_network_gpu.py), the CPU test (tests/test_plan_cpu.py) checks the stream ordering and the descriptors of each at several batches
 PLAN_OPTIONS = [{}, {'GPP_HALF_LANES': '1,2'}, {'GPP_HALF_LANES': '1'}, {'GPP_HALF_LANES': '2'}, {'GPP_HALF_LANES': '0,1,2,3'}, {'GPP_HALF_LANES': '0,2'},
                 {'GPP_HALF_LANES': ''}, {'GPP_BR1_LANE': '0'}, {'GPP_FPN_LANES': '0'}, {'GPP_P4_LANE': '0'}, {'GPP_HEAD_LANES': '1'},
@@ -83,6 +83,22 @@ def plan_matrix():
     cfgs += [('resnet50', dt, {}, env, 4) + small for dt in ('f16x3', 'bf16x3', 'bf16')
              for env in ({'GPP_X3_SPLIT': '0'}, {'GPP_X3_SPLIT': '1'}, {'GPP_FUSE_TAIL': ''}, {'GPP_FUSE_STEM_POOL': '0'})]
     cfgs += [('resnet50', 'f16x3', {}, {}, 8, 402, 1333)]
+    # 224 x 352 with both round thresholds at 0: the smallest shape at which the regression tower takes its sparse and deep forms (at
+    # 200 x 333 pyramid_regression_ops is split-K and stays dense), every type, every switch those forms depend on, the other backbones
+    tower, Z = (224, 352), {'GPP_SPARSE_TOWER_MIN_ROUNDS': '0', 'GPP_SPARSE_TOWER_DEEP_MIN_ROUNDS': '0'}
+    cfgs += [('resnet50', 'f16x3', {}, Z, 1) + tower] + [('resnet50', dt, {}, Z, 4) + tower for dt in ('f16x3', 'bf16x3', 'bf16', 'f32')]
+    cfgs += [('resnet50', 'f16x3', {}, dict(Z, **env), 4) + tower
+             for env in ({'GPP_SPARSE_TOWER_DEPTH': '1'}, {'GPP_SPARSE_TOWER_DEPTH': '2'}, {'GPP_SPARSE_TOWER': '0'}, {'GPP_SPARSE_HEADS': '0'},
+                         {'GPP_CLS_LANE': '1'}, {'GPP_HEAD_LANES': '1'}, {'GPP_X3_SPLIT': '0'}, {'GPP_DECODE_OVERLAP': '0'})]
+    cfgs += [('resnet50', 'f16x3', kw, Z, 4) + tower for kw in ({'plan': 'latency'}, {'orientation_specific_filter': True}, {'pose': True})]
+    cfgs += [('densenet121', 'f16x3', {}, Z, 2) + tower, ('mobilenet224_1.0', 'f16x3', {}, Z, 4) + tower]
+    # ... and at the default thresholds: the same shape, MobileNet, the pose stage with and without the cuboid NMS, audit plans, the
+    # latency plan at full size, and ragged plans ('ragged' is no model argument: both consumers of the matrix pop it for plan_for)
+    cfgs += [('resnet50', 'f16x3', {}, {}, 4) + tower, ('mobilenet224_1.0', 'f16x3', {}, {}, 2) + small, ('mobilenet224_1.0', 'f32', {}, {}, 1) + small]
+    cfgs += [('resnet50', 'f16x3', kw, {}, 2) + small for kw in ({'pose': True}, {'pose': True, 'cuboid_nms': ('bev', 0.5)}, {'range_audit': True})]
+    cfgs += [('densenet121', 'f16x3', {'range_audit': True}, {}, 1) + small, ('resnet50', 'f16x3', {'plan': 'latency'}, Z, 8, 402, 1333)]
+    cfgs += [('resnet50', dt, {'ragged': True}, env, b, 192, 333)
+             for dt, env, b in (('f16x3', {}, 3), ('bf16', {}, 3), ('f16x3', {'GPP_FUSE_STEM_POOL': '0'}, 2))]
     return cfgs
 
 

@@ -311,6 +311,51 @@ def test_random_tiles_never_change_a_byte(dtype, monkeypatch):
     assert any(draws[0][k][0] != tuned[k][0] for k in tuned)
 
 
+def test_the_tune_cache_carries_every_choice_from_one_model_to_the_next(tmp_path, monkeypatch):
+    """ GPP_TUNE_CACHE across two models of one process, on the smallest plan whose cache holds every kind of key (resnet50 f16x3, B = 4,
+    224 x 352, both round thresholds at 0): half-batch layers, a fused tail's row count, a guarded pair's and a tower layer's '@rows' key.
+    The first model times its layers and writes the file; the second finds every choice there -- the same plan.tuning, the file's bytes
+    untouched, the same output bytes; an entry edited to a tile its layer does not list is timed again, never launched """
+    import json
+    path = tmp_path / 'tile_choices.json'
+    monkeypatch.setenv('GPP_TUNE_CACHE', str(path))
+    monkeypatch.setenv('GPP_SPARSE_TOWER_MIN_ROUNDS', '0')
+    monkeypatch.setenv('GPP_SPARSE_TOWER_DEEP_MIN_ROUNDS', '0')
+    planes = synthetic.load_plane_database('100').astype(np.float32)
+    _, P_inv = synthetic.synthetic_calibration()
+    inputs = [images(4, 224, 352, seed=5), np.tile(P_inv[None].astype(np.float32), (4, 1, 1)), np.tile(planes[None], (4, 1, 1))]
+
+    def run():
+        model = models.load_model('synthetic:1234', backbone_name='resnet50', dtype='f16x3')
+        out = model.predict_on_batch(inputs)
+        plan = model.plan_for(4, 224, 352, planes.shape[0], True)
+        return out + [plan.cls_logits.cpu().numpy(), plan.regression.cpu().numpy(), plan.regression_dim.cpu().numpy()], plan
+
+    want, first = run()
+    assert (want[2] > 0.05).sum() > 0 and len(first.sparse.gathered) == 2 and len(first.sparse.tower) == 1 and first.sparse.deep_layers == 2
+    written = path.read_bytes()
+    keys = [k.split('|') for k in json.loads(written)]
+    assert all(len(k) == 7 and k[1:3] == ['resnet50', 'f16x3'] and k[5:] == ['224', '352'] for k in keys)
+    layers = {(k[3], int(k[4])) for k in keys}
+    assert {('res4a_branch2a', 2), ('res2a_branch2b+2c', 2), ('P3', 4), ('pyramid_regression_ops', 4), ('pyramid_regression_ops@rows', 4),
+            ('pyramid_regression_dim@rows', 4), ('pyramid_regression_3', 4), ('pyramid_regression_3@rows', 4)} <= layers
+    assert {name for name, _ in layers} == set(first.tuning)
+    got, second = run()
+    assert second is not first and second.tuning == first.tuning and second.tuning_parts == first.tuning_parts
+    assert path.read_bytes() == written                          # nothing was timed again
+    for a, b in zip(got, want):
+        assert helpers.bits_equal(a, b)
+    data = json.loads(written)
+    edited = next(k for k in data if k.split('|')[3:5] == ['P3', '4'])
+    data[edited] = [0x7fffffff, 1.0]
+    path.write_text(json.dumps(data))
+    got, third = run()
+    assert third.tuning['P3'][0] != 0x7fffffff and third.tuning['P3'][0] == json.loads(path.read_text())[edited][0]
+    assert {k: v for k, v in third.tuning.items() if k != 'P3'} == {k: v for k, v in first.tuning.items() if k != 'P3'}
+    for a, b in zip(got, want):
+        assert helpers.bits_equal(a, b)
+
+
 def test_hip_graph_capture_replays_the_plan(monkeypatch):
     """ model.capture(plan): the whole plan, side-stream fork / join of the detection selection included, recorded into a
     HIP graph; replays give the eager results bit for bit on new inputs """

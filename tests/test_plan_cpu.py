@@ -1,6 +1,6 @@
 """ Plans built without a GPU: the model on the CPU device (hip.require_device patched, GPP_AUTOTUNE=0) builds every plan of the matrix
 (helpers.plan_matrix: every plan switch x every type x several batches, the deeper ResNets, DenseNet, the latency plan, per-orientation
-NMS, no NMS, a full-size frame).  What the plan builder asks of the library there is host code (FLOPs, workspace sizes, the split rule).
+NMS, no NMS, a full-size frame, the regression tower's sparse and deep forms at 224 x 352, MobileNet, pose, audit and ragged plans).  What the plan builder asks of the library there is host code (FLOPs, workspace sizes, the split rule).
 Each plan is checked for races between its streams, for descriptors the library would refuse, and for the host restatement of the split
 rule (layers/conv.default_split) against the library's own. """
 import ctypes
@@ -51,11 +51,13 @@ def conv_descs(plan):
 @pytest.mark.parametrize('cfg', helpers.plan_matrix(), ids=helpers.plan_label)
 def test_plan_is_race_free_and_every_descriptor_is_accepted(cfg, cpu_model, monkeypatch):
     bb, dt, kw, env, B, H, Wd = cfg
+    kw = dict(kw)
+    ragged = kw.pop('ragged', False)
     model = cpu_model(bb, dt, kw)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     model._plans.clear()
-    plan = model.plan_for(B, H, Wd, 100, True)
+    plan = model.plan_for(B, H, Wd, 100, True, ragged=ragged)
     model._plans.clear()
     assert plan.check_stream_ordering() == []
     tiles, count = (ctypes.c_int * 64)(), ctypes.c_int(0)
@@ -73,7 +75,8 @@ def test_plan_is_race_free_and_every_descriptor_is_accepted(cfg, cpu_model, monk
             q.split_k = 0
             assert C.default_split(d.KH, d.KW, d.C_in, d.C_out, pixels) == C.split_rule(q) <= C.split_rule(d), name
         n += 1
-    assert n > 50
+    # (a MobileNet backbone is 14 fused launches with no gpp_conv_desc: only the FPN's 8 layers and the heads' 13 carry one)
+    assert n > (20 if model.mobilenet else 50)
 
 
 def test_a_cpu_built_plan_never_reaches_a_kernel(cpu_model):

@@ -31,7 +31,7 @@ def test_the_heights_of_a_class(Hp):
     assert (lo, hi) == (4 * Hp - 3, 4 * Hp)
     assert [I.class_of_resized(h, 160) for h in range(lo, hi + 1)] == [(Hp, 160)] * 4
     assert I.class_of_resized(hi + 1, 160) == (Hp + 1, 160) and I.class_of_resized(lo - 1, 160) == (Hp - 1, 160)
-    for h in range(lo, hi + 1):          # the class is the pool1 shape of the uniform stem (models/retinanet.py _resnet_backbone)
+    for h in range(lo, hi + 1):          # the class is the pool1 shape of the uniform stem (models/builder.py resnet_backbone)
         H1 = (h + 6 - 7) // 2 + 1
         assert (H1 + 1) // 2 == Hp
 

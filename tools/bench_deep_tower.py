@@ -44,7 +44,7 @@ def main():
     plan = model.plan_for(B, inputs[0].shape[1], inputs[0].shape[2], planes.shape[0], True)
     sp = plan.sparse
     if sp is None or sp.deep_layers < 2:
-        raise SystemExit('this plan does not take the deep form (see sparse_deep_layers in models/retinanet.py)')
+        raise SystemExit('this plan does not take the deep form (see head_forms in models/plan.py)')
     torch.cuda.synchronize()
     G = hip.GPP_MAX_GROUPS
     total = B * sum(sp.level_pixels)

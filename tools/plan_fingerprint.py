@@ -121,6 +121,8 @@ def main():
     weights, built = {}, {}
     for cfg in helpers.plan_matrix():
         bb, dt, kw, env, B, H, Wd = cfg
+        kw = dict(kw)
+        ragged = kw.pop('ragged', False)
         key = (bb, dt, tuple(sorted(kw.items())))
         if key not in built:
             if bb not in weights:
@@ -130,7 +132,7 @@ def main():
         model._plans.clear()
         os.environ.update(env)
         try:
-            plan = model.plan_for(B, H, Wd, 100, True)
+            plan = model.plan_for(B, H, Wd, 100, True, ragged=ragged)
         finally:
             for k in env:
                 del os.environ[k]

@@ -10,7 +10,7 @@ from keras_retinanet_3D.models import weights as W  # noqa: E402
 
 
 def conv_names(backbone, fused_stages=(0, 1), block_stages=()):
-    """ launch order of models/retinanet.py:_build (fused 2b+2c launches are bottleneck_tail_kernel, whole identity blocks bottleneck_block_x3_kernel) """
+    """ launch order of models/builder.py:PlanBuilder.build (fused 2b+2c launches are bottleneck_tail_kernel, whole identity blocks bottleneck_block_x3_kernel) """
     names = []
     for stage, n in enumerate(W.BLOCKS[backbone]):
         for b in range(n):
