@@ -7,7 +7,11 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <limits.h>
 #include <stdlib.h>
+
+#include <mutex>
+#include <vector>
 
 #include "conv_igemm_types.h"
 #include "conv_tiles.h"
@@ -49,6 +53,10 @@ int validate(const gpp_conv_desc& d)
     if (deep && (!d.deep_rows || !d.deep_counts || !d.deep_flag || d.gather_rows || d.guard || tower)) return GPP_ERR_BAD_ARG;
     if (!deep && d.deep_tile != 0) return GPP_ERR_BAD_ARG;
     if (d.lists_after < 0) return GPP_ERR_BAD_ARG;
+    // conv_after: a layer enqueued behind this one (and behind its lists) -- this one is then a plain dense launch, as the deep layers' rules go
+    // conv_before: the same kind of handle in front of a plain dense call, which reads every row of the layer the handle names
+    if (d.conv_after < 0 || d.conv_before < 0) return GPP_ERR_BAD_ARG;
+    if ((d.conv_after || d.conv_before) && (d.gather_rows || d.guard || tower || deep)) return GPP_ERR_BAD_ARG;
     if (((uintptr_t)d.gather_rows | (uintptr_t)d.gather_counts | (uintptr_t)d.guard | (uintptr_t)d.tower_rows | (uintptr_t)d.tower_counts |
          (uintptr_t)d.tower_flag | (uintptr_t)d.deep_rows | (uintptr_t)d.deep_counts | (uintptr_t)d.deep_flag) & 3)
         return GPP_ERR_ALIGN;
@@ -158,7 +166,7 @@ int tail_entry(const gpp_conv_desc* conv3x3, const gpp_conv_desc* conv1x1, int t
     if (rc == GPP_OK) rc = validate(d2);
     if (rc != GPP_OK) return rc;
     if (d1.gather_rows || d2.gather_rows || d1.guard || d2.guard || d1.tower_rows || d2.tower_rows || d1.deep_rows || d2.deep_rows ||
-        d1.lists_after || d2.lists_after)
+        d1.lists_after || d2.lists_after || d1.conv_after || d2.conv_after || d1.conv_before || d2.conv_before)
         return GPP_ERR_UNSUPPORTED;      // gpp_conv2d_igemm only
     const gpp_conv_group &G1 = d1.groups[0], &G2 = d2.groups[0];
     // the pair this kernel fuses: 3x3 / stride 1 / pad 1 / C -> C (C = 64 or 128) feeding 1x1 / stride 1 / C -> multiple of 128
@@ -193,7 +201,8 @@ int block_entry(const gpp_conv_desc* conv_a, const gpp_conv_desc* conv_b, const 
     if (rc == GPP_OK) rc = validate(d3);
     if (rc != GPP_OK) return rc;
     if (d1.gather_rows || d2.gather_rows || d3.gather_rows || d1.guard || d2.guard || d3.guard || d1.tower_rows || d2.tower_rows || d3.tower_rows ||
-        d1.deep_rows || d2.deep_rows || d3.deep_rows || d1.lists_after || d2.lists_after || d3.lists_after)
+        d1.deep_rows || d2.deep_rows || d3.deep_rows || d1.lists_after || d2.lists_after || d3.lists_after || d1.conv_after || d2.conv_after ||
+        d3.conv_after || d1.conv_before || d2.conv_before || d3.conv_before)
         return GPP_ERR_UNSUPPORTED;
     const gpp_conv_group &G1 = d1.groups[0], &G2 = d2.groups[0], &G3 = d3.groups[0];
     // the triple this kernel fuses, on pre-split maps of one x3 type: 1x1 / stride 1 or 2 / C_in -> C; 3x3 / stride 1 / pad 1 / C -> C (C = 64 or 128);
@@ -233,7 +242,7 @@ int block_proj_entry(const gpp_conv_desc* conv_a, const gpp_conv_desc* conv_b, c
     if (rc == GPP_OK) rc = validate(dp);
     if (rc != GPP_OK) return rc;
     for (const gpp_conv_desc* d : {&d1, &d2, &d3, &dp})
-        if (d->gather_rows || d->guard || d->tower_rows || d->deep_rows || d->lists_after) return GPP_ERR_UNSUPPORTED;
+        if (d->gather_rows || d->guard || d->tower_rows || d->deep_rows || d->lists_after || d->conv_after || d->conv_before) return GPP_ERR_UNSUPPORTED;
     const gpp_conv_group &G1 = d1.groups[0], &G2 = d2.groups[0], &G3 = d3.groups[0], &GP = dp.groups[0];
     if (!is_x3(d1.dtype) || d1.dtype != d2.dtype || d1.dtype != d3.dtype || d1.dtype != dp.dtype) return GPP_ERR_UNSUPPORTED;
     if (d1.n_groups != 1 || d2.n_groups != 1 || d3.n_groups != 1 || dp.n_groups != 1 || d1.batch != d2.batch || d1.batch != d3.batch || d1.batch != dp.batch)
@@ -263,6 +272,11 @@ int block_proj_entry(const gpp_conv_desc* conv_a, const gpp_conv_desc* conv_b, c
     hipStream_t st = (hipStream_t)stream;
     return d1.dtype == GPP_F16X3 ? gpp_block_proj_dispatch_f16x3(d1, d2, d3, dp, tile, st) : gpp_block_proj_dispatch_bf16x3(d1, d2, d3, dp, tile, st);
 }
+
+// the descriptors gpp_conv_desc.conv_after names by number (gpp_conv2d_deferred_register)
+std::mutex g_deferred_mutex;
+std::vector<gpp_conv_desc> g_deferred_descs;
+std::vector<char> g_deferred_held;
 
 }  // namespace
 
@@ -352,12 +366,67 @@ extern "C" int gpp_conv2d_igemm(const gpp_conv_desc* host_desc, void* stream)
     if (rc != GPP_OK) return rc;
     // lists_after: the deep lists behind this layer's launch on the same stream (the layer writes the logits they are made from); a handle
     // nobody holds is refused before anything is launched
-    const int32_t lists = d.lists_after;
-    d.lists_after = 0;
+    // conv_after: a layer of both forms behind the lists (their rows are its rows), the same kind of handle
+    // conv_before: the registered layer in front, dense -- its lists dropped, its range events into this call's counter -- then this one
+    const int32_t lists = d.lists_after, after = d.conv_after, before = d.conv_before;
+    d.lists_after = d.conv_after = d.conv_before = 0;
     if (lists && (rc = gpp_detect_deep_lists_run(lists, 1, stream)) != GPP_OK) return rc;
+    if (after && (rc = gpp_conv2d_deferred_run(after, 1, stream)) != GPP_OK) return rc;
+    if (before) {
+        gpp_conv_desc front;
+        {
+            std::lock_guard<std::mutex> lock(g_deferred_mutex);
+            if ((size_t)before > g_deferred_held.size() || !g_deferred_held[(size_t)before - 1]) return GPP_ERR_BAD_ARG;
+            front = g_deferred_descs[(size_t)before - 1];
+        }
+        front.deep_rows = front.deep_counts = front.deep_flag = nullptr;
+        front.deep_tile = 0;
+        if (d.range_counter) front.range_counter = d.range_counter;
+        if ((rc = gpp_conv2d_igemm(&front, stream)) != GPP_OK) return rc;
+    }
     rc = dispatch_any(d, (hipStream_t)stream);
-    if (rc != GPP_OK || !lists) return rc;
-    return gpp_detect_deep_lists_run(lists, 0, stream);
+    if (rc == GPP_OK && lists) rc = gpp_detect_deep_lists_run(lists, 0, stream);
+    if (rc == GPP_OK && after) rc = gpp_conv2d_deferred_run(after, 0, stream);
+    return rc;
+}
+
+extern "C" int gpp_conv2d_deferred_register(const gpp_conv_desc* host_desc, int32_t* handle)
+{
+    if (!host_desc || !handle) return GPP_ERR_BAD_ARG;
+    gpp_conv_desc d = *host_desc;
+    for (int g = 0; g < GPP_MAX_GROUPS; ++g) d.groups[g].row_begin = 0;
+    const int rc = validate(d);
+    if (rc != GPP_OK) return rc;
+    // a layer of both forms on the deep lists, and the end of the chain: what it names cannot name another
+    if (!d.deep_rows || d.lists_after || d.conv_after || d.conv_before) return GPP_ERR_BAD_ARG;
+    std::lock_guard<std::mutex> lock(g_deferred_mutex);
+    size_t slot = 0;
+    while (slot < g_deferred_held.size() && g_deferred_held[slot]) ++slot;
+    if (slot >= (size_t)INT_MAX - 1) return GPP_ERR_UNSUPPORTED;
+    if (slot == g_deferred_held.size()) { g_deferred_held.push_back(0); g_deferred_descs.push_back(d); }
+    g_deferred_descs[slot] = d;
+    g_deferred_held[slot] = 1;
+    *handle = (int32_t)slot + 1;
+    return GPP_OK;
+}
+
+extern "C" int gpp_conv2d_deferred_release(int32_t handle)
+{
+    std::lock_guard<std::mutex> lock(g_deferred_mutex);
+    if (handle < 1 || (size_t)handle > g_deferred_held.size() || !g_deferred_held[(size_t)handle - 1]) return GPP_ERR_BAD_ARG;
+    g_deferred_held[(size_t)handle - 1] = 0;
+    return GPP_OK;
+}
+
+extern "C" int gpp_conv2d_deferred_run(int32_t handle, int check_only, void* stream)
+{
+    gpp_conv_desc d;
+    {
+        std::lock_guard<std::mutex> lock(g_deferred_mutex);
+        if (handle < 1 || (size_t)handle > g_deferred_held.size() || !g_deferred_held[(size_t)handle - 1]) return GPP_ERR_BAD_ARG;
+        d = g_deferred_descs[(size_t)handle - 1];
+    }
+    return check_only ? GPP_OK : gpp_conv2d_igemm(&d, stream);
 }
 
 // The block tiles a layer may run with (same K order per output element in every one of them: the choice never changes a result): the
@@ -452,8 +521,8 @@ extern "C" int gpp_conv2d_autotune(gpp_conv_desc* desc, int iters, void* stream,
     e = hipEventCreate(&e1);
     if (e != hipSuccess) { (void)hipEventDestroy(e0); return (int)e; }
     const int tile_in = desc->tile_hint;
-    const int32_t lists_in = desc->lists_after;
-    desc->lists_after = 0;                                           // the layer's own launch is what is timed, not the lists behind it
+    const int32_t lists_in = desc->lists_after, after_in = desc->conv_after, before_in = desc->conv_before;
+    desc->lists_after = desc->conv_after = desc->conv_before = 0;                        // the layer's own launch is what is timed, not the lists or the layer behind it
     float best = 1e30f;
     int best_tile = tile_in, rc = GPP_OK;
     auto time_one = [&](int tile, float* us, int reps = 2) -> int {
@@ -505,6 +574,8 @@ extern "C" int gpp_conv2d_autotune(gpp_conv_desc* desc, int iters, void* stream,
     (void)hipEventDestroy(e1);
     desc->tile_hint = rc == GPP_OK ? best_tile : tile_in;
     desc->lists_after = lists_in;
+    desc->conv_after = after_in;
+    desc->conv_before = before_in;
     if (best_us) *best_us = best;
     return rc;
 }
@@ -528,7 +599,7 @@ int preact_validate(gpp_conv_desc& d, const float* in_scale, const float* in_shi
     if (((uintptr_t)in_scale | (uintptr_t)in_shift) & 15) return GPP_ERR_ALIGN;
     if (d.KH != 1 || d.KW != 1 || d.stride != 1 || d.pad_top != 0 || d.pad_left != 0) return GPP_ERR_UNSUPPORTED;
     if (d.x3_split & GPP_X3_IN) return GPP_ERR_UNSUPPORTED;
-    if (d.gather_rows || d.guard || d.tower_rows || d.deep_rows || d.lists_after) return GPP_ERR_UNSUPPORTED;          // gpp_conv2d_igemm only
+    if (d.gather_rows || d.guard || d.tower_rows || d.deep_rows || d.lists_after || d.conv_after || d.conv_before) return GPP_ERR_UNSUPPORTED;          // gpp_conv2d_igemm only
     if (d.C_in > 4096) return GPP_ERR_UNSUPPORTED;               // the scale / shift table lives in LDS beside the ring
     return GPP_OK;
 }

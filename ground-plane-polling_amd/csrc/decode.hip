@@ -896,16 +896,18 @@ __global__ __launch_bounds__(kCompactThreads) void compact_pixels_kernel(uint32_
     compact_pixels(bitmap, T, B, max_rows, rows, counts, flag, or_flag);
 }
 
-// two maps in one launch, a workgroup each (the deep lists: the second map's or_flag is a word an EARLIER launch wrote, not the first's flag)
+// two or three maps in one launch, a workgroup each (the deep lists: the or_flag of the second and of the third map is a word an EARLIER
+// launch wrote, not the flag of the map in front); the grid says how many
 struct CompactJob { uint32_t* bitmap; int32_t* rows; int32_t* counts; int32_t* flag; const int32_t* or_flag; };
-__global__ __launch_bounds__(kCompactThreads) void compact_pixels_pair_kernel(const CompactJob a, const CompactJob b, const LevelTable T, int B, int max_rows)
+__global__ __launch_bounds__(kCompactThreads) void compact_pixels_pair_kernel(const CompactJob a, const CompactJob b, const CompactJob c, const LevelTable T,
+                                                                              int B, int max_rows)
 {
-    const CompactJob& j = blockIdx.x == 0 ? a : b;
+    const CompactJob& j = blockIdx.x == 0 ? a : blockIdx.x == 1 ? b : c;
     compact_pixels(j.bitmap, T, B, max_rows, j.rows, j.counts, j.flag, j.or_flag);
 }
 
-// ---- gpp_detect_deep_lists: the marks straight from the logits, their dilations of radius 1, 2, 3, and the lists of radius 2 and 3.
-// Four launches.  The marks: a wavefront per 64 pixels (two words), its lanes over the pixels' 64 * nba anchors in memory order, nba rounds -- every load a
+// ---- gpp_detect_deep_lists: the marks straight from the logits, their dilations of radius 1, 2, 3 (and 4), and the lists of radius 2 and 3
+// (and 4: the rows of layer 0's regression slice).  Four launches either way.  The marks: a wavefront per 64 pixels (two words), its lanes over the pixels' 64 * nba anchors in memory order, nba rounds -- every load a
 // coalesced 32 bytes per lane as in candidates_kernel, whose decision it calls (is_candidate).  The hits meet in one LDS word per wavefront
 // and leave as two whole words: no global atomics, nothing read of what the map held.
 __global__ __launch_bounds__(256) void mark_candidate_pixels_kernel(const float* __restrict__ cls, int64_t n_anchors, int nba, float thr,
@@ -941,10 +943,13 @@ __global__ __launch_bounds__(256) void mark_candidate_pixels_kernel(const float*
 
 // the three dilations in one pass over the marks: bit (level, image, pixel) of radius r = some mark within Chebyshev distance r of the pixel
 // INSIDE its image and level (what r passes of dilate_pixels_kernel give: an image is a rectangle).  One thread per bit, three ballots.
+// R4: the radius-4 map too (the rows of layer 0's regression slice) -- up to 81 probes, a fourth ballot; without it the pass of the three
+template <bool R4>
 __global__ __launch_bounds__(256) void dilate_radii_kernel(const uint32_t* __restrict__ marks, const LevelTable T, int B, int total_words,
                                                            uint32_t* __restrict__ radius1, uint32_t* __restrict__ radius2,
-                                                           uint32_t* __restrict__ radius3)
+                                                           uint32_t* __restrict__ radius3, uint32_t* __restrict__ radius4)
 {
+    constexpr int R = R4 ? 4 : 3;
     const int64_t gbit = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int word = (int)(gbit >> 5);
     if (word >= total_words) return;                       // (whole half-wavefronts: the ballots below are of the lanes that remain)
@@ -952,33 +957,35 @@ __global__ __launch_bounds__(256) void dilate_radii_kernel(const uint32_t* __res
     for (int q = 1; q < T.n_levels; ++q) l = word >= T.word_begin[q] ? q : l;
     const int64_t bit = gbit - ((int64_t)T.word_begin[l] << 5);
     const int pix = T.pix[l], W = T.width[l], H = pix / W;
-    bool on1 = false, on2 = false, on3 = false;
+    bool on1 = false, on2 = false, on3 = false, on4 = false;
     if (bit < (int64_t)B * pix) {
         const int b = (int)(bit / pix), p = (int)(bit - (int64_t)b * pix);
         const int y = p / W, x = p - y * W;
         const uint32_t* words = marks + T.word_begin[l];
-        for (int dy = -3; dy <= 3; ++dy) {
+        for (int dy = -R; dy <= R; ++dy) {
             const int yy = y + dy;
             if (yy < 0 || yy >= H) continue;
-            for (int dx = -3; dx <= 3; ++dx) {
+            for (int dx = -R; dx <= R; ++dx) {
                 const int xx = x + dx;
                 if (xx < 0 || xx >= W) continue;
                 const int64_t nb = (int64_t)b * pix + yy * W + xx;
                 const bool v = (words[nb >> 5] >> (nb & 31)) & 1u;
                 const int r = max(abs(dy), abs(dx));
-                on3 |= v;
+                on4 |= v;
+                on3 |= v && r <= 3;
                 on2 |= v && r <= 2;
                 on1 |= v && r <= 1;
             }
         }
     }
-    const unsigned long long m1 = __ballot(on1), m2 = __ballot(on2), m3 = __ballot(on3);
+    const unsigned long long m1 = __ballot(on1), m2 = __ballot(on2), m3 = __ballot(on3), m4 = R4 ? __ballot(on4) : 0ull;
     const int lane = threadIdx.x & 63;
     if (lane == 0 || lane == 32) {
         const int sh = lane;                               // lane 32 holds the wavefront's second word
         radius1[word] = (uint32_t)(m1 >> sh);
         radius2[word] = (uint32_t)(m2 >> sh);
         radius3[word] = (uint32_t)(m3 >> sh);
+        if (R4) radius4[word] = (uint32_t)(m4 >> sh);
     }
 }
 
@@ -986,31 +993,36 @@ __global__ __launch_bounds__(256) void dilate_radii_kernel(const uint32_t* __res
 // ... and flag2, so that the two compactions can share a launch: the radius-3 one takes it from here
 __global__ __launch_bounds__(kCompactThreads) void deep_stats_kernel(const uint32_t* __restrict__ marks, const uint32_t* __restrict__ radius1,
                                                                      const uint32_t* __restrict__ radius2, int total_words, int max_rows,
-                                                                     int tower_max_rows, int deep_max_rows, int32_t* __restrict__ stats)
+                                                                     int tower_max_rows, int deep_max_rows, int32_t* __restrict__ stats,
+                                                                     const uint32_t* __restrict__ radius3, int32_t* __restrict__ stats0)
 {
-    __shared__ int sums[3][kCompactThreads / 64];
+    // (stats0 with layer 0's lists only, and radius3 is read only then: flag1 as the third compaction needs it, one more link of the chain)
+    __shared__ int sums[4][kCompactThreads / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int n[3] = {0, 0, 0};
+    int n[4] = {0, 0, 0, 0};
     for (int w = tid; w < total_words; w += kCompactThreads) {
         n[0] += __popc(marks[w]);
         n[1] += __popc(radius1[w]);
         n[2] += __popc(radius2[w]);
+        if (stats0 != nullptr) n[3] += __popc(radius3[w]);
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < 4; ++k) {
 #pragma unroll
         for (int s = 32; s >= 1; s >>= 1) n[k] += __shfl_down(n[k], s, 64);
         if (lane == 0) sums[k][wave] = n[k];
     }
     __syncthreads();
     if (tid == 0) {
-        int t[3] = {0, 0, 0};
-        for (int q = 0; q < kCompactThreads / 64; ++q) { t[0] += sums[0][q]; t[1] += sums[1][q]; t[2] += sums[2][q]; }
+        int t[4] = {0, 0, 0, 0};
+        for (int q = 0; q < kCompactThreads / 64; ++q) { t[0] += sums[0][q]; t[1] += sums[1][q]; t[2] += sums[2][q]; t[3] += sums[3][q]; }
         const int f3 = (t[0] > max_rows || t[1] > tower_max_rows) ? 1 : 0;
+        const int f2 = (f3 || t[2] > deep_max_rows) ? 1 : 0;
         stats[0] = t[0];
         stats[1] = t[1];
         stats[2] = f3;
-        stats[3] = (f3 || t[2] > deep_max_rows) ? 1 : 0;
+        stats[3] = f2;
+        if (stats0 != nullptr) stats0[0] = (f2 || t[3] > deep_max_rows) ? 1 : 0;
     }
 }
 
@@ -1081,11 +1093,15 @@ int deep_lists_table(const gpp_deep_list_desc& d, LevelTable& T, int64_t& words)
         !(d.score_thr == d.score_thr))
         return GPP_ERR_BAD_ARG;
     const bool layer1 = d.rows1 || d.counts1 || d.flag1;
+    // layer 0's lists: all five fields or none (also at B == 0: the set is a property of the descriptor), and never without layer 1's
+    const bool layer0 = d.radius4 || d.rows0 || d.counts0 || d.flag0 || d.stats0;
+    if (layer0 && (!d.radius4 || !d.rows0 || !d.counts0 || !d.flag0 || !d.stats0 || !d.rows1 || !d.counts1 || !d.flag1)) return GPP_ERR_BAD_ARG;
     if (d.B > 0 && (!d.cls_logits || !d.marks || !d.radius1 || !d.radius2 || !d.radius3 || !d.rows2 || !d.counts2 || !d.flag2 || !d.stats ||
                     (layer1 && (!d.rows1 || !d.counts1 || !d.flag1))))
         return GPP_ERR_BAD_ARG;
     if (((uintptr_t)d.cls_logits & 15) || (((uintptr_t)d.marks | (uintptr_t)d.radius1 | (uintptr_t)d.radius2 | (uintptr_t)d.radius3 | (uintptr_t)d.rows2 |
-          (uintptr_t)d.counts2 | (uintptr_t)d.flag2 | (uintptr_t)d.rows1 | (uintptr_t)d.counts1 | (uintptr_t)d.flag1 | (uintptr_t)d.stats) & 3))
+          (uintptr_t)d.counts2 | (uintptr_t)d.flag2 | (uintptr_t)d.rows1 | (uintptr_t)d.counts1 | (uintptr_t)d.flag1 | (uintptr_t)d.stats |
+          (uintptr_t)d.radius4 | (uintptr_t)d.rows0 | (uintptr_t)d.counts0 | (uintptr_t)d.flag0 | (uintptr_t)d.stats0) & 3))
         return GPP_ERR_ALIGN;
     T.n_levels = d.n_levels;
     int64_t pixels = 0;
@@ -1121,12 +1137,16 @@ extern "C" int gpp_detect_deep_lists(const gpp_deep_list_desc* host_desc, void* 
     hipStream_t st = (hipStream_t)stream;
     const unsigned blocks = (unsigned)(((words + 1) / 2 * 64 + 255) / 256);       // words are handed out in pairs, a wavefront each
     mark_candidate_pixels_kernel<<<dim3(blocks), 256, 0, st>>>(d.cls_logits, d.n_anchors, d.num_base_anchors, d.score_thr, T, d.B, (int)words, d.marks);
-    dilate_radii_kernel<<<dim3(blocks), 256, 0, st>>>(d.marks, T, d.B, (int)words, d.radius1, d.radius2, d.radius3);
-    deep_stats_kernel<<<1, kCompactThreads, 0, st>>>(d.marks, d.radius1, d.radius2, (int)words, d.max_rows, d.tower_max_rows, d.deep_max_rows, d.stats);
-    // flag2 = f3 | (|radius 2| > deep_max_rows); flag1 = flag2 | (|radius 3| > deep_max_rows): the or_flag chain of the dilated lists, with
-    // flag2 as the statistics launch has it (stats[3]) so that the two compactions, 25 - 30 us of one workgroup each, run side by side
+    if (d.radius4) dilate_radii_kernel<true><<<dim3(blocks), 256, 0, st>>>(d.marks, T, d.B, (int)words, d.radius1, d.radius2, d.radius3, d.radius4);
+    else dilate_radii_kernel<false><<<dim3(blocks), 256, 0, st>>>(d.marks, T, d.B, (int)words, d.radius1, d.radius2, d.radius3, nullptr);
+    deep_stats_kernel<<<1, kCompactThreads, 0, st>>>(d.marks, d.radius1, d.radius2, (int)words, d.max_rows, d.tower_max_rows, d.deep_max_rows, d.stats,
+                                                     d.radius3, d.stats0);
+    // flag2 = f3 | (|radius 2| > deep_max_rows); flag1 = flag2 | (|radius 3| > deep_max_rows); flag0 = flag1 | (|radius 4| > deep_max_rows): the
+    // or_flag chain of the dilated lists, with flag2 (stats[3]) and flag1 (stats0[0]) as the statistics launch has them, so that the
+    // compactions, 25 - 30 us of one workgroup each, run side by side
     const CompactJob layer2 = {d.radius2, d.rows2, d.counts2, d.flag2, d.stats + 2}, layer1 = {d.radius3, d.rows1, d.counts1, d.flag1, d.stats + 3};
-    if (d.rows1) compact_pixels_pair_kernel<<<2, kCompactThreads, 0, st>>>(layer2, layer1, T, d.B, d.deep_max_rows);
+    const CompactJob layer0 = {d.radius4, d.rows0, d.counts0, d.flag0, d.stats0};
+    if (d.rows1) compact_pixels_pair_kernel<<<d.rows0 ? 3 : 2, kCompactThreads, 0, st>>>(layer2, layer1, layer0, T, d.B, d.deep_max_rows);
     else compact_pixels_kernel<<<1, kCompactThreads, 0, st>>>(d.radius2, T, d.B, d.deep_max_rows, d.rows2, d.counts2, d.flag2, d.stats + 2);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? GPP_OK : (int)e;

@@ -80,6 +80,42 @@ int main(int argc, char** argv)
             const int rc = gpp_conv2d_igemm(&v, nullptr);
             if (v.lists_after != 0 && rc == 0) { fprintf(stderr, "a lists_after handle nobody holds was accepted\n"); return 3; }
             note(rc);
+            // conv_after and its registry: a handle nobody holds is refused like the other one; a descriptor is kept only when it passes
+            // gpp_conv2d_igemm's checks as a layer of both forms that names nothing behind itself, and its handle then passes those of
+            // the layer that carries it (run with check_only: nothing of it is launched)
+            v = r.d[0];
+            v.conv_after = (int32_t)(r.a % 5) - 1;
+            v.conv_before = (r.b & 64) ? (int32_t)(r.c % 7) - 2 : 0;
+            const int rc_after = gpp_conv2d_igemm(&v, nullptr);
+            if ((v.conv_after != 0 || v.conv_before != 0) && rc_after == 0) { fprintf(stderr, "a conv_after handle nobody holds was accepted\n"); return 3; }
+            note(rc_after);
+            gpp_conv_desc w = r.d[1];
+            if (r.b & 128) { w.deep_rows = (const int32_t*)r.d[2].out; w.deep_counts = (const int32_t*)r.d[2].bias; w.deep_flag = (const int32_t*)r.d[2].zero_page; }
+            if (r.b & 256) { w.lists_after = 0; w.conv_after = 0; w.conv_before = 0; }
+            int32_t held = 0;
+            const int rc_reg = gpp_conv2d_deferred_register(&w, &held);
+            note(rc_reg);
+            note(gpp_conv2d_deferred_register(&w, nullptr));
+            note(gpp_conv2d_deferred_register(nullptr, &held));
+            note(gpp_conv2d_deferred_run((int32_t)r.c, 1, nullptr));
+            if (rc_reg == 0) {
+                if (!w.deep_rows || w.lists_after || w.conv_after || w.conv_before) { fprintf(stderr, "a deferred layer that is no end of a chain was kept\n"); return 3; }
+                note(gpp_conv2d_deferred_run(held, 1, nullptr));
+                v = r.d[0];
+                v.conv_after = held;
+                note(gpp_conv2d_igemm(&v, nullptr));
+                v.conv_after = 0;
+                v.conv_before = held;      // the same layer in front of a plain call: dense, its lists dropped (no device here: an error code either way)
+                note(gpp_conv2d_igemm(&v, nullptr));
+                v.conv_after = held;
+                note(gpp_conv2d_deferred_release(held));
+                v.gather_rows = nullptr; v.gather_counts = nullptr; v.guard = nullptr;
+                const int rc_gone = gpp_conv2d_igemm(&v, nullptr);
+                if (rc_gone == 0) { fprintf(stderr, "a released conv_after handle was accepted\n"); return 3; }
+                note(rc_gone);
+            }
+            note(gpp_conv2d_deferred_release(held));
+            note(gpp_conv2d_deferred_release((int32_t)r.b));
             break;
         }
         case 1: note(gpp_bottleneck_tail(&r.d[0], &r.d[1], (int)(r.b % 200), nullptr)); break;
@@ -148,6 +184,10 @@ int main(int argc, char** argv)
                     if (l < dl.n_levels) pixels += dl.level_pixels[l];
                 }
                 dl.n_anchors = (r.a & 64) ? (int64_t)r.b : pixels * dl.num_base_anchors;
+                // layer 0's lists: none of the five fields, all of them (aligned), or whatever the record holds -- all or none, never without layer 1's
+                if (r.a & 128) dl.radius4 = nullptr, dl.rows0 = dl.counts0 = dl.flag0 = dl.stats0 = nullptr;
+                else if (r.a & 256) dl.radius4 = dl.marks, dl.rows0 = dl.rows2, dl.counts0 = dl.counts2, dl.flag0 = dl.flag2, dl.stats0 = dl.stats;
+                if (r.a & 512) dl.rows1 = nullptr;
                 note(gpp_detect_deep_lists(&dl, nullptr));
                 note(gpp_detect_deep_lists(nullptr, nullptr));
                 int32_t handle = 0;

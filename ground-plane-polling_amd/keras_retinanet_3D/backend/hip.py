@@ -84,7 +84,8 @@ class ConvDesc(ctypes.Structure):
                 ('tower_rows', c_void_p), ('tower_counts', c_void_p), ('tower_flag', c_void_p),
                 ('tower_tile', ctypes.c_int32), ('reserved4', ctypes.c_int32),
                 ('deep_rows', c_void_p), ('deep_counts', c_void_p), ('deep_flag', c_void_p),
-                ('deep_tile', ctypes.c_int32), ('lists_after', ctypes.c_int32)]
+                ('deep_tile', ctypes.c_int32), ('lists_after', ctypes.c_int32),
+                ('conv_after', ctypes.c_int32), ('conv_before', ctypes.c_int32)]
 
 
 class PixelListDesc(ctypes.Structure):
@@ -103,7 +104,8 @@ class DeepListDesc(ctypes.Structure):
                                         'rows1', 'counts1', 'flag1', 'stats')] + [('n_anchors', c_int64)] + \
                [(n, ctypes.c_int32) for n in ('B', 'num_base_anchors', 'n_levels', 'max_rows', 'tower_max_rows', 'deep_max_rows')] + \
                [('score_thr', c_float), ('reserved', ctypes.c_int32),
-                ('level_pixels', ctypes.c_int32 * GPP_MAX_GROUPS), ('level_width', ctypes.c_int32 * GPP_MAX_GROUPS)]
+                ('level_pixels', ctypes.c_int32 * GPP_MAX_GROUPS), ('level_width', ctypes.c_int32 * GPP_MAX_GROUPS)] + \
+               [(n, c_void_p) for n in ('radius4', 'rows0', 'counts0', 'flag0', 'stats0')]
 
 
 class MobileNetBlockDesc(ctypes.Structure):
@@ -222,6 +224,14 @@ def _declare(lib):
         lib.gpp_detect_deep_lists_release.argtypes = [ctypes.c_int32]
         lib.gpp_detect_deep_lists_run.restype = c_int
         lib.gpp_detect_deep_lists_run.argtypes = [ctypes.c_int32, c_int, c_void_p]
+    # ... and the layer gpp_conv_desc.conv_after names (csrc/conv_igemm.hip; a plan of GPP_SPARSE_TOWER_DEPTH >= 4 does not build without it)
+    if hasattr(lib, 'gpp_conv2d_deferred_register'):
+        lib.gpp_conv2d_deferred_register.restype = c_int
+        lib.gpp_conv2d_deferred_register.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_int32)]
+        lib.gpp_conv2d_deferred_release.restype = c_int
+        lib.gpp_conv2d_deferred_release.argtypes = [ctypes.c_int32]
+        lib.gpp_conv2d_deferred_run.restype = c_int
+        lib.gpp_conv2d_deferred_run.argtypes = [ctypes.c_int32, c_int, c_void_p]
     lib.gpp_conv2d_igemm.restype = c_int
     lib.gpp_conv2d_igemm.argtypes = [ctypes.POINTER(ConvDesc), c_void_p]
     lib.gpp_stem_conv7x7_bn_relu.restype = c_int

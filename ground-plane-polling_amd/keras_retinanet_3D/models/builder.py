@@ -22,7 +22,7 @@ from .plan import (BlockDesc, BlockProjDesc, CandidatePixelsDesc, CuboidNmsDesc,
                    OP_DETECT_CANDIDATES, OP_DETECT_SELECT, OP_DETECT_EMIT, OP_DETECT_OSF, OP_STEM_POOL,
                    OP_MAXPOOL_PAD, OP_AVGPOOL, OP_CONV_PREACT, OP_MOBILENET_STEM, OP_MOBILENET_BLOCK, OP_POSE, OP_CUBOID_NMS,
                    OP_ABSMAX, OP_ABSMAX_CLEAR, OP_STEM_RAGGED, OP_STEM_POOL_RAGGED, OP_MAXPOOL_RAGGED, OP_DETECT_CANDIDATE_PIXELS,
-                   block_form, head_forms, layer_split, part_of, TOWER_SLICES, SparseHeads, Plan)
+                   block_form, head_forms, layer_split, part_of, TOWER_SLICES, TOWER0, TOWER0_SLICE, SparseHeads, Plan)
 
 
 class PlanBuilder(object):
@@ -51,6 +51,7 @@ class PlanBuilder(object):
         plan.planes = torch.empty((B, n_planes, 4) if planes_batched else (n_planes, 4), dtype=torch.float32, device=dev)
         # the pyramid layout (layout()) and the decode descriptor with what each decode launch reads and writes (detect())
         self.shapes = self.pix = self.total = None
+        self.tower0 = None         # towers_0_split: (the regression slice's descriptor, the maps it reads, the maps it writes)
         self.detect_desc = self.detect_access = self.detect_all = None
 
     def build(self):
@@ -430,13 +431,10 @@ class PlanBuilder(object):
         m, plan, opts = self.model, self.plan, self.opts
         cls_o, reg_o, dim_o = outs
         _, wide = self.pyramid(896)
-        # (measured and rejected: the half-empty fourth 256-column tile of this 896-wide layer as its own 128-column launch
-        # on a side stream -- the two launches do not pack into each other's partial rounds, no gain)
-        self.conv('pyramid_towers_0', P, wide, 3, pad=(1, 1), relu=True, join=True)
         names = ('pyramid_classification', 'pyramid_regression_ops', 'pyramid_regression_dim', 'pyramid_regression_1', 'pyramid_regression_2',
-                 'pyramid_regression_3')
+                 'pyramid_regression_3', TOWER0)
         forms = head_forms(opts, m.dtype, m.plan_mode, m.osf, m.audit, {n: m.conv_w[n][2] for n in names},
-                           hasattr(hip.lib(), 'gpp_detect_deep_lists'), self.shapes, self.B)
+                           hasattr(hip.lib(), 'gpp_detect_deep_lists'), self.shapes, self.B, hasattr(hip.lib(), 'gpp_conv2d_deferred_register'))
         if forms.sparse:
             plan.sparse = SparseHeads(self.torch, self.device, self.B, [f.H * f.W for f in P], opts.sparse_heads, [f.W for f in P],
                                       opts.sparse_tower if forms.tower_both else 0.0)
@@ -444,6 +442,15 @@ class PlanBuilder(object):
             if forms.deep_layers:
                 plan.sparse.add_deep(self.torch, forms.deep_layers, opts.sparse_deep)
                 plan.keep += plan.sparse.deep_tensors()
+            if forms.tower0:
+                plan.sparse.add_tower0(self.torch)
+                plan.keep += plan.sparse.tower0_tensors()
+        # (measured and rejected: the half-empty fourth 256-column tile of this 896-wide layer as its own 128-column launch
+        # on a side stream -- the two launches do not pack into each other's partial rounds, no gain)
+        if forms.tower0:
+            self.towers_0_split(P, wide)
+        else:
+            self.conv(TOWER0, P, wide, 3, pad=(1, 1), relu=True, join=True)
         l_dim, l_cls = (1, 2) if opts.head_lanes else (0, 0)
         towers = {'cls': ('pyramid_classification', 256, 512, 'pyramid_classification', cls_o, 0, l_cls or opts.cls_lane),
                   'reg': ('pyramid_regression', 512, 0, 'pyramid_regression_ops', reg_o, 1, 0, bool(opts.cls_lane)),
@@ -460,6 +467,42 @@ class PlanBuilder(object):
             for t in ('dim', 'cls', 'reg'):
                 self.tower(forms, wide, *towers[t])
             self.decode(OP_DETECT_OSF if m.osf else OP_DETECT, join=True)
+
+    def towers_0_split(self, P, wide):
+        """ the fused first layer of the three towers in a plan whose regression tower is gathered down to layer 1 (head_forms: tower0).
+        Columns [0, TOWER0_SLICE) of its map are layer 0 of the regression tower, and their only reader, the gathered layer 1, takes them on
+        the 3 x 3 halo of its own rows: the 9 x 9 dilation of the candidates' pixels.  Those rows are known once the logits are, so the
+        slice leaves this launch: the op computes the other columns (the classification and dimension slices, contiguous; the packed
+        weights, the bias and the scale are addressed by a row offset: 512 is a multiple of the 32-row interleave), and the slice becomes a
+        layer of both forms on the radius-4 lists that the library enqueues behind pyramid_classification's lists (out_layer:
+        gpp_conv_desc.conv_after).  Still ONE op under this name with the algorithmic FLOPs of all columns and the whole map as its io:
+        RetinaNet3D.run_op writes every column, as an op run on its own does. """
+        m, plan, sp = self.model, self.plan, self.plan.sparse
+        wt, bias, (kh, kw, cin, cout) = m.conv_w[TOWER0]
+        scale = m.conv_scale.get(TOWER0)
+        n = TOWER0_SLICE
+
+        def cols(c0, c):
+            return [C.FMap(f.buf, f.B, f.H, f.W, c, off=f.off + c0, bstride=f.bstride, pitch=f.pitch, split=f.split, half=f.half) for f in wide]
+
+        def desc(c0, c):
+            parts = [wt[c0:], bias[c0:]] + ([scale[c0:]] if scale is not None else [])
+            plan.keep += parts
+            d = C.conv_desc(P, cols(c0, c), parts[0], parts[1], kh, kw, cin, c, pad=(1, 1), relu=True, dtype=m.dtype,
+                            out_scale=parts[2] if scale is not None else None)
+            if m.dtype == 'f16x3':
+                d.range_counter = plan.range_slot.data_ptr()
+            return d
+        rest = desc(n, cout - n)
+        plan.conv_descs.append((rest, 0))
+        plan.ws_need[0] = max(plan.ws_need.get(0, 0), C.workspace_bytes(rest))
+        # (the slice never splits -- head_forms asked the rule -- and carries no workspace: the library's copy is made before any is bound)
+        first = desc(0, n)
+        first.weight_rows = n
+        first.deep_rows, first.deep_counts, first.deep_flag = sp.tower0_rows.data_ptr(), sp.tower0_counts.data_ptr(), sp.tower0_flag.data_ptr()
+        plan.keep.append(first)
+        plan.emit(OP_CONV, rest, TOWER0, list(P), cols(n, cout - n), flops=C.conv_flops(rest) + C.conv_flops(first), join=True, io=(P, wide, None))
+        self.tower0 = (first, list(P), cols(0, n))
 
     def tower(self, forms, wide, prefix, width, c0, out_name, out, tag=0, lane=0, join=False):
         """ layers 1 .. 3 of one tower on its `width` channels from c0 of the fused first layer's map, then its output layer.  The regression
@@ -519,8 +562,14 @@ class PlanBuilder(object):
             # part of this op, on this stream, in front of the tower layers that read them
             d = self.desc(name, src, out, 3, pad=(1, 1), out_f32=True, lane=lane)
             d.lists_after = sp.register_deep(sp.deep_desc(plan.cls_logits, plan.n_anchors, anchor_utils.NUM_BASE_ANCHORS, SCORE_THRESHOLD))
-            plan.emit(OP_CONV, d, name, list(src), list(out) + sp.deep_tensors(), flops=C.conv_flops(d), lane=lane, join=join,
-                      io=(src, out, None))
+            reads, writes = list(src), list(out) + sp.deep_tensors()
+            if sp.tower0_rows is not None:
+                # ... and, behind the lists, the regression slice of the towers' first layer on the radius-4 rows (towers_0_split): the
+                # library's launches under this op, which so reads the P maps and writes the slice and layer 0's lists
+                first, p_maps, slice_maps = self.tower0
+                sp.register_tower0(first, d)
+                reads, writes = reads + p_maps, writes + slice_maps + sp.tower0_tensors()
+            plan.emit(OP_CONV, d, name, reads, writes, flops=C.conv_flops(d), lane=lane, join=join, io=(src, out, None))
             return
         if form == 'dense':
             self.conv(name, src, out, 3, pad=(1, 1), out_f32=True, lane=lane, join=join)

@@ -202,8 +202,9 @@ def plan_options(model, B):
         sparse_tower=(max(1e-9, float(env('GPP_SPARSE_TOWER_MAX_SHARE', SPARSE_TOWER_MAX_SHARE)))
                       if (sparse and env('GPP_SPARSE_TOWER', '1') != '0') else 0.0),
         sparse_tower_rounds=float(env('GPP_SPARSE_TOWER_MIN_ROUNDS', SPARSE_TOWER_MIN_ROUNDS)),
-        # GPP_SPARSE_TOWER_DEPTH (default 3; with the sparse tower only): how many layers of the regression tower run on the rows their
-        # reader takes -- 1 the last layer alone, 2 layer 2 as well (the 5 x 5 dilation of the candidates' pixels), 3 layer 1 too (7 x 7).
+        # GPP_SPARSE_TOWER_DEPTH (with the sparse tower only): how many layers of the regression tower run on the rows their
+        # reader takes -- 1 the last layer alone, 2 layer 2 as well (the 5 x 5 dilation of the candidates' pixels), 3 layer 1 too (7 x 7),
+        # 4 the regression slice of the fused first layer as well (9 x 9).
         # The lists of layers 2 and 1 are made from the logits on the caller's stream (gpp_detect_deep_lists);
         # GPP_SPARSE_TOWER_DEEP_MAX_SHARE: the largest share of rows their gathered launches take; GPP_SPARSE_TOWER_DEEP_MIN_ROUNDS: the
         # rounds of workgroups their dense launch must exceed (its own variable: tests force the tower's to 0 at small shapes)
@@ -257,12 +258,16 @@ def layer_split(plan_mode, shape, pixels):
 
 
 # what head_forms decides: sparse = the plan has sparse head outputs at all (a SparseHeads); outputs = {output layer: 'dense' | 'pair' |
-# 'lists_after'}; tower_both = pyramid_regression_3 takes both forms; deep_layers = how many tower layers in front of it do (0, 1, 2)
-HeadForms = collections.namedtuple('HeadForms', 'sparse outputs tower_both deep_layers')
+# 'lists_after'}; tower_both = pyramid_regression_3 takes both forms; deep_layers = how many tower layers in front of it do (0, 1, 2);
+# tower0 = the regression slice of pyramid_towers_0 does too, as a launch pair behind pyramid_classification's lists
+HeadForms = collections.namedtuple('HeadForms', 'sparse outputs tower_both deep_layers tower0')
+HeadForms.__new__.__defaults__ = (False,)
+TOWER0 = 'pyramid_towers_0'
+TOWER0_SLICE = 512          # channels [0, 512) of the fused first layer's map are layer 0 of the regression tower (TOWER_SLICES)
 HEAD_OUTPUTS = ('pyramid_classification', 'pyramid_regression_ops', 'pyramid_regression_dim')
 
 
-def head_forms(opts, dtype, plan_mode, osf, audit, layers, deep_lists, levels, B):
+def head_forms(opts, dtype, plan_mode, osf, audit, layers, deep_lists, levels, B, deferred=True):
     """ the form of every head layer that has more than one, named before anything is emitted (as block_form does for a bottleneck).
     layers: {name: (kh, kw, cin, cout)} of the three output layers and pyramid_regression_1 .. 3; deep_lists: the library has
     gpp_detect_deep_lists; levels: the (h, w) of the pyramid levels; B: the batch.  Every rule is one of layer, map sizes, batch and plan
@@ -278,7 +283,11 @@ def head_forms(opts, dtype, plan_mode, osf, audit, layers, deep_lists, levels, B
 
     deep_layers: the lists are made on the caller's stream right behind pyramid_classification, so that layer runs there, unsplit, with the
     candidate pass on its side lane (decode_overlap without cls_lane: no head_lanes), in a plan that is neither orientation-specific nor an
-    audit; and the dense launch of a layer fields more than opts.sparse_deep_rounds rounds of workgroups """
+    audit; and the dense launch of a layer fields more than opts.sparse_deep_rounds rounds of workgroups
+
+    tower0: both deep layers take the form, opts.sparse_depth >= 4, the library has gpp_conv2d_deferred_register
+    (deferred), the plan is a throughput plan, `layers` names pyramid_towers_0, whose first TOWER0_SLICE columns are the regression tower's layer 0 -- a 256-column grid of
+    layer 1's shape that fields more than opts.sparse_deep_rounds rounds -- and neither that slice nor the columns behind it are split """
     pixels = sum(h * w for h, w in levels)
     rows = sum((B * h * w + 255) // 256 for h, w in levels)
 
@@ -299,10 +308,17 @@ def head_forms(opts, dtype, plan_mode, osf, audit, layers, deep_lists, levels, B
             not any(split(n) for n in ('pyramid_classification', 'pyramid_regression_1', 'pyramid_regression_2')) and
             not layers['pyramid_regression_1'][3] % 256 and fills('pyramid_regression_2', opts.sparse_deep_rounds)):
         deep_layers = min(2, opts.sparse_depth - 1)
+    tower0 = False
+    if deep_layers == 2 and opts.sparse_depth >= 4 and deferred and plan_mode != 'latency' and layers.get(TOWER0) is not None:
+        kh, kw, cin, cout = layers[TOWER0]
+        parts = {'slice': (kh, kw, cin, TOWER0_SLICE), 'rest': (kh, kw, cin, cout - TOWER0_SLICE)}
+        tower0 = bool(cout > TOWER0_SLICE and layers['pyramid_regression_1'][2] == TOWER0_SLICE and
+                      not any(layer_split(plan_mode, shape, pixels) > 1 for shape in parts.values()) and
+                      rows * (TOWER0_SLICE // 256) > opts.sparse_deep_rounds * COMPUTE_UNITS)
     outputs = {name: 'dense' if not sparse or name == 'pyramid_classification' or split(name) else 'pair' for name in HEAD_OUTPUTS}
     if sparse and deep_layers:
         outputs['pyramid_classification'] = 'lists_after'
-    return HeadForms(sparse, outputs, tower_both, deep_layers)
+    return HeadForms(sparse, outputs, tower_both, deep_layers, tower0)
 
 
 def part_of(fm, c0, nb):
@@ -328,7 +344,7 @@ SPARSE_TOWER_MIN_ROUNDS = '1'
 # (1: the last one only), the share of rows up to which their gathered launches run (the last share measured below the dense launch for this
 # kernel and shape, section 4.19's table), and the rounds their dense launch must exceed -- a variable of its own: tests pin what small
 # plans do under GPP_SPARSE_TOWER_MIN_ROUNDS=0
-SPARSE_TOWER_DEPTH = '3'
+SPARSE_TOWER_DEPTH = '4'
 SPARSE_TOWER_DEEP_MAX_SHARE = '0.75'
 SPARSE_TOWER_DEEP_MIN_ROUNDS = '1'
 COMPUTE_UNITS = 256
@@ -398,6 +414,37 @@ class SparseHeads(object):
         # the DEEP lists (add_deep): the rows of tower layers 2 and 1, written on the caller's stream behind the layer that writes the logits
         self.deep, self.deep_layers, self.deep_max_rows, self.deep_handle = [], 0, 0, 0
         self.deep_bitmaps = self.deep_rows = self.deep_counts = self.deep_flags = self.deep_stats = None
+        # LAYER 0 (add_tower0): the regression slice of the towers' fused first layer on the radius-4 map of the same call.  Attributes of
+        # their own, not members of the deep_* lists: tower0 = the slice's descriptor (both forms on tower0_rows / tower0_counts /
+        # tower0_flag), which the library keeps a copy of (tower0_handle) and enqueues behind the lists of tower0_carrier, the descriptor
+        # of the layer that writes the logits (gpp_conv_desc.conv_after)
+        self.tower0 = self.tower0_carrier = None
+        self.tower0_handle = 0
+        self.tower0_bitmap = self.tower0_rows = self.tower0_counts = self.tower0_flag = self.tower0_stats = None
+
+    def add_tower0(self, torch):
+        """ the buffers of layer 0's lists (gpp_deep_list_desc.radius4 / rows0 / counts0 / flag0 / stats0); the flag starts at 1 """
+        self.tower0_bitmap = torch.zeros_like(self.bitmap)
+        self.tower0_rows = torch.zeros_like(self.rows)
+        self.tower0_counts = torch.zeros_like(self.counts)
+        self.tower0_flag = torch.ones_like(self.flag)
+        self.tower0_stats = torch.zeros_like(self.flag)
+
+    def tower0_tensors(self):
+        if self.tower0_rows is None:
+            return []
+        return [self.tower0_bitmap, self.tower0_rows, self.tower0_counts, self.tower0_flag, self.tower0_stats]
+
+    def register_tower0(self, desc=None, carrier=None):
+        """ hands the slice's descriptor to the library and its handle to the carrier (gpp_conv_desc.conv_after); without arguments: again,
+        after the tuner has written the tiles into the descriptor -- the library holds a copy """
+        self.tower0, self.tower0_carrier = desc or self.tower0, carrier or self.tower0_carrier
+        lib, handle = hip.lib(), ctypes.c_int32(0)
+        if self.tower0_handle:
+            hip.check(lib.gpp_conv2d_deferred_release(self.tower0_handle), 'gpp_conv2d_deferred_release')
+            self.tower0_handle = 0
+        hip.check(lib.gpp_conv2d_deferred_register(ctypes.byref(self.tower0), ctypes.byref(handle)), 'gpp_conv2d_deferred_register')
+        self.tower0_handle = self.tower0_carrier.conv_after = int(handle.value)
 
     def add_deep(self, torch, layers, deep_share):
         """ the buffers of gpp_detect_deep_lists for `layers` (1: layer 2 only, 2: layers 2 and 1) tower layers in front of the last one: the
@@ -427,6 +474,9 @@ class SparseHeads(object):
         if self.deep_layers > 1:
             d.rows1, d.counts1, d.flag1 = self.deep_rows[1].data_ptr(), self.deep_counts[1].data_ptr(), self.deep_flags[1].data_ptr()
         d.stats = self.deep_stats.data_ptr()
+        if self.tower0_rows is not None:
+            d.radius4, d.rows0, d.counts0 = self.tower0_bitmap.data_ptr(), self.tower0_rows.data_ptr(), self.tower0_counts.data_ptr()
+            d.flag0, d.stats0 = self.tower0_flag.data_ptr(), self.tower0_stats.data_ptr()
         d.n_anchors, d.B, d.num_base_anchors, d.n_levels = n_anchors, self.B, num_base_anchors, len(self.level_pixels)
         d.max_rows, d.tower_max_rows, d.deep_max_rows, d.score_thr = self.max_rows, self.tower_max_rows, self.deep_max_rows, score_thr
         d.level_pixels = (ctypes.c_int32 * hip.GPP_MAX_GROUPS)(*self.level_pixels)
@@ -447,6 +497,12 @@ class SparseHeads(object):
             except Exception:          # (interpreter shutdown)
                 pass
             self.deep_handle = 0
+        if getattr(self, 'tower0_handle', 0):
+            try:
+                hip.lib().gpp_conv2d_deferred_release(self.tower0_handle)
+            except Exception:
+                pass
+            self.tower0_handle = 0
 
     def tensors(self):
         own = [self.bitmap, self.rows, self.counts, self.flag]
@@ -475,7 +531,7 @@ class SparseHeads(object):
 
     def reset_deep(self):
         """ the deep flags at 1, ordered on the current stream: what an op run on its own leaves behind it (it writes its whole map) """
-        for flag in self.deep_flags or ():
+        for flag in list(self.deep_flags or ()) + ([self.tower0_flag] if self.tower0_flag is not None else []):
             flag.fill_(1)
 
 
@@ -536,7 +592,7 @@ class Plan(object):
             return
         self.heads_stale = False
         sp = self.sparse
-        # deep layers 1, 2 in layer order, then the tower's last layer, then the output layers: each dense reader reads every row of the layer
+        # layer 0's regression slice (in front of layer 1, inside its call), deep layers 1, 2 in layer order, then the tower's last layer, then the output layers: each dense reader reads every row of the layer
         # in front.  Each is the dense launch as it stands in the plan, without its lists or its guard; a layer of both forms counts its range
         # events into a scratch slot: the run has counted those of the rows it wrote
         for descs, lists, tile, scratch, what in (
@@ -550,6 +606,10 @@ class Plan(object):
                 setattr(d, tile, 0)
                 if scratch and d.range_counter:
                     d.range_counter = sp.range_scratch.data_ptr()
+                if sp.tower0 is not None and desc is sp.deep[0]:
+                    # layer 1 reads every row of layer 0's regression slice, which the run wrote on the radius-4 rows: the library runs the
+                    # copy it holds dense in front of this launch, into the same counter (gpp_conv_desc.conv_before)
+                    d.conv_before = sp.tower0_handle
                 hip.check(hip.lib().gpp_conv2d_igemm(ctypes.byref(d), hip.stream_ptr()), 'gpp_conv2d_igemm ({})'.format(what))
 
     def emit(self, kind, desc, name, reads=(), writes=(), tag=0, flops=0.0, lane=0, join=False, sync=False, io=None, inner=(), atomic=()):

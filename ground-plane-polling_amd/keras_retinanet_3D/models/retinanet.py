@@ -49,7 +49,7 @@ from .plan import (BlockDesc, BlockProjDesc, FUSE_INPROJ_MIN_ROUNDS, CandidatePi
                    OP_MAXPOOL_PAD, OP_AVGPOOL, OP_CONV_PREACT, OP_MOBILENET_STEM, OP_MOBILENET_BLOCK, OP_POSE, OP_CUBOID_NMS,
                    OP_ABSMAX, OP_ABSMAX_CLEAR, OP_STEM_RAGGED, OP_STEM_POOL_RAGGED, OP_MAXPOOL_RAGGED,
                    OP_DETECT_CANDIDATE_PIXELS, DETECT_OPS, OP_JOIN, OP_SYNC,
-                   PlanOptions, block_form, part_of, plan_options, TOWER_SLICES, RANGE_AUDIT_THRESHOLD, X3_QUANTUM,
+                   PlanOptions, block_form, part_of, plan_options, TOWER_SLICES, TOWER0, RANGE_AUDIT_THRESHOLD, X3_QUANTUM,
                    SPARSE_HEADS_MAX_SHARE, SPARSE_TOWER_MAX_SHARE, SPARSE_TOWER_MIN_ROUNDS, SPARSE_TOWER_DEPTH,
                    SPARSE_TOWER_DEEP_MAX_SHARE, SPARSE_TOWER_DEEP_MIN_ROUNDS, COMPUTE_UNITS, audit_report, SparseHeads, Plan)
 
@@ -314,11 +314,18 @@ class RetinaNet3D(object):
         """ Enqueue ONE op of the plan (per-layer tests). """
         self._require_hip()
         hip.check(hip.lib().gpp_plan_run(ctypes.byref(plan.array, index * ctypes.sizeof(PlanOp)), 1, hip.stream_ptr(), None, 0), 'gpp_plan_run')
-        kind, _, desc, _, _ = plan.ops[index]
+        kind, _, desc, name, _ = plan.ops[index]
         if kind == OP_CONV and desc.lists_after:
             # the op has made the deep lists and set their flags; an op run on its own writes its whole map (DESIGN.md section 4.19), so the
             # flags are 1 again behind it, ordered on the stream
             plan.sparse.reset_deep()
+        if kind == OP_CONV and name == TOWER0 and plan.sparse is not None and plan.sparse.tower0 is not None:
+            # the plan's launch under this name computes the columns behind the regression slice (PlanBuilder.towers_0_split); an op run
+            # on its own writes its whole map: the slice dense, here
+            d = type(plan.sparse.tower0).from_buffer_copy(plan.sparse.tower0)
+            d.deep_rows = d.deep_counts = d.deep_flag = None
+            d.deep_tile = 0
+            hip.check(hip.lib().gpp_conv2d_igemm(ctypes.byref(d), hip.stream_ptr()), 'gpp_conv2d_igemm (regression slice of {})'.format(TOWER0))
 
     def run_plan(self, plan, events=None):
         """ Enqueue the whole forward on the current stream (asynchronous). """

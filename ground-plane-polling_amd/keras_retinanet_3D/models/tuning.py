@@ -11,7 +11,7 @@ import os
 
 from ..backend import hip
 from ..layers import conv as C
-from .plan import DETECT_OPS, OP_CONV, OP_CONV_PREACT, OP_MOBILENET_BLOCK, OP_POLL, OP_TAIL, PlanOp
+from .plan import DETECT_OPS, OP_CONV, OP_CONV_PREACT, OP_MOBILENET_BLOCK, OP_POLL, OP_TAIL, TOWER0, PlanOp
 
 
 class TuneCache(object):
@@ -191,6 +191,10 @@ def autotune(model, plan):
             if gathered:
                 plan.sparse.put_every_nth(model.torch)
                 name = name + '@rows'
+        if kind == OP_CONV and name == TOWER0 and plan.sparse is not None and plan.sparse.tower0 is not None:
+            # the launch under this name computes the columns behind the regression slice only (PlanBuilder.towers_0_split): another layer
+            # than the fused one, timed under a key of its own -- the fused layer's key keeps its meaning
+            name = name + '@cols'
         model.run_op(plan, index)
         if kind not in (OP_CONV, OP_TAIL, OP_CONV_PREACT, OP_MOBILENET_BLOCK):
             continue
@@ -225,6 +229,11 @@ def autotune(model, plan):
     if plan.sparse is not None:
         for d in plan.sparse.deep:           # the same layer shape as the last layer: the tile its gathered launches were timed to
             d.deep_tile = plan.sparse.tower[0].tower_tile
+        if plan.sparse.tower0 is not None:
+            # layer 0's regression slice has layer 1's shape: its dense tile and the gathered one; the library holds a copy of the descriptor
+            plan.sparse.tower0.tile_hint = plan.sparse.deep[0].tile_hint
+            plan.sparse.tower0.deep_tile = plan.sparse.tower[0].tower_tile
+            plan.sparse.register_tower0()
         plan.sparse.reset(model.torch)
     model.torch.cuda.synchronize()
     if fresh:

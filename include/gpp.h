@@ -230,6 +230,18 @@ typedef struct gpp_conv_desc {
     int32_t lists_after;            /* 0 = none.  Otherwise a handle of gpp_detect_deep_lists_register: gpp_conv2d_igemm enqueues gpp_detect_deep_lists
                                        of that descriptor behind the layer's own launch, on the same stream (the layer that writes the logits).  A
                                        handle nobody holds: GPP_ERR_BAD_ARG, nothing launched.  gpp_conv2d_igemm only */
+    int32_t conv_after;             /* 0 = none.  Otherwise a handle of gpp_conv2d_deferred_register: gpp_conv2d_igemm enqueues that descriptor -- a layer
+                                       of both forms on deep_rows / deep_counts / deep_flag -- behind this layer's launch AND behind the lists of
+                                       lists_after, on the same stream: the regression slice of the towers' fused first layer, whose rows
+                                       (gpp_deep_list_desc.rows0) only exist once the logits do.  A handle nobody holds: GPP_ERR_BAD_ARG, nothing
+                                       launched.  Not together with gather_rows, guard, tower_rows or deep_rows of this descriptor.
+                                       gpp_conv2d_igemm only */
+    int32_t conv_before;            /* 0 = none.  Otherwise a handle of gpp_conv2d_deferred_register on a PLAIN dense call of the layer that reads that
+                                       layer's map (no lists or guard of its own: GPP_ERR_BAD_ARG otherwise): gpp_conv2d_igemm first enqueues the
+                                       registered layer DENSE -- without its lists, its range events into THIS call's range_counter -- and then
+                                       this layer.  A dense reader reads every row of the layer in front of it: whoever completes a map that a
+                                       run wrote on listed rows only names the layer in front this way, and the library runs the copy it holds.
+                                       A handle nobody holds: GPP_ERR_BAD_ARG, nothing launched.  gpp_conv2d_igemm only */
 } gpp_conv_desc;
 /* The gathered-row form of a layer between two convolutions (gather_rows set, out_f32 == 0): GPP_BF16X3 / GPP_F16X3 with pre-split input AND
  * output maps (x3_split & (GPP_X3_IN | GPP_X3_OUT) both set), stride 1, no shortcut, never split-K, C_out a multiple of 256; anything else
@@ -244,6 +256,13 @@ typedef struct gpp_conv_desc {
 #define GPP_X3_RES 4
 
 int gpp_conv2d_igemm(const gpp_conv_desc* host_desc, void* stream);
+/* gpp_conv_desc.conv_after: the library keeps a copy of a descriptor -- validated as gpp_conv2d_igemm validates it, a layer of both forms on
+ * deep_rows / deep_counts / deep_flag, itself without lists_after / conv_after: GPP_ERR_BAD_ARG otherwise -- and hands out a handle > 0 (a
+ * number, not an address, as gpp_detect_deep_lists_register does).  gpp_conv2d_deferred_run: gpp_conv2d_igemm of the copy (check_only != 0:
+ * whether somebody holds the handle, nothing launched). */
+int gpp_conv2d_deferred_register(const gpp_conv_desc* host_desc, int32_t* handle);
+int gpp_conv2d_deferred_release(int32_t handle);
+int gpp_conv2d_deferred_run(int32_t handle, int check_only, void* stream);
 
 /* Split-K factor the library uses for this layer when desc->split_k == 0 and a workspace is given.  It is a function of
    the layer alone (kernel size, channels, output pixels PER IMAGE) -- never of the batch size, the block tile or a timing --
@@ -553,6 +572,11 @@ int gpp_detect_pixel_lists(const gpp_pixel_list_desc* host_desc, void* stream);
  *                    pass's lists will decide for layer 3 (gpp_pixel_list_desc.dilated_flag)
  *   flag2, flag1     int32 [1] each, 1 = dense: flag2 = f3 | (|radius 2| > deep_max_rows), flag1 = flag2 | (|radius 3| > deep_max_rows) -- a layer
  *                    whose reader runs dense runs dense, by construction
+ *   radius4 / rows0 / counts0 / flag0 / stats0   (all five NULL: none, and the call is the one above byte for byte.  All five or none; they need
+ *                    rows1 / counts1 / flag1.)  The 9 x 9 dilation, written in the same pass as the other three and compacted by a third workgroup
+ *                    of the compaction launch into the rows of LAYER 0's regression slice (gpp_conv_desc.conv_after), which layer 1 reads on the
+ *                    halo of its own rows; flag0 = flag1 | (|radius 4| > deep_max_rows).  stats0: int32 [1], flag1 as the statistics launch
+ *                    computes it (the third compaction does not wait for the second); stats keeps its four words
  * Null pointer, bad size, num_base_anchors > 64, reserved != 0: GPP_ERR_BAD_ARG; nothing launched.  B == 0: GPP_OK.
  * gpp_detect_deep_lists_register keeps a copy of a descriptor in the library and hands out a handle > 0 for gpp_conv_desc.lists_after (a number,
  * not an address: a conv descriptor holds no host pointer); gpp_detect_deep_lists_release gives it back. */
@@ -566,6 +590,7 @@ typedef struct gpp_deep_list_desc {
     int32_t B, num_base_anchors, n_levels, max_rows, tower_max_rows, deep_max_rows;
     float score_thr; int32_t reserved;
     int32_t level_pixels[GPP_MAX_GROUPS]; int32_t level_width[GPP_MAX_GROUPS];
+    uint32_t* radius4; int32_t* rows0; int32_t* counts0; int32_t* flag0; int32_t* stats0;
 } gpp_deep_list_desc;
 int gpp_detect_deep_lists(const gpp_deep_list_desc* host_desc, void* stream);
 int gpp_detect_deep_lists_register(const gpp_deep_list_desc* host_desc, int32_t* handle);
