@@ -220,6 +220,22 @@ int main(int argc, char** argv)
                                     (int32_t*)(uintptr_t)r.d[0].bias, (int32_t*)(uintptr_t)r.d[0].bias, nullptr));
             note(gpp_cuboid_nms_f64((const float*)r.d[0].in, (int)(r.a % 64) + 1, (int)(r.b % 128) + 1, (int)(r.c & 1), (double)(r.c % 3) - 1.0, (float*)r.d[0].out,
                                     (int32_t*)(uintptr_t)r.d[0].bias, (int32_t*)(uintptr_t)r.d[0].bias, nullptr));
+            // the tracker: sizes, then fuzzed parameters and sequence starts against null pointers, more rows than a workgroup has threads, and a
+            // workspace of no bytes -- all end before any launch or copy (seq_start is the one host array the call reads)
+            {
+                gpp_track_params tp = {(int32_t)(r.c % 5) - 1, (int32_t)(r.a % 7) - 2, (int32_t)(r.b % 3), (int32_t)(r.c % 11 == 0),
+                                       (double)(r.c % 7) * 0.5 - 0.5, (double)(r.a % 4) * 0.5, (double)(r.b % 4) * 0.5 - 0.5, 0.25, 0.0};
+                int32_t seq[3] = {(int32_t)(r.c % 3) - 1, (int32_t)(r.a % 9), (int32_t)(r.b % 9)};
+                size_t tb = 0;
+                note(gpp_track_state_bytes(&tb));
+                note(gpp_track_workspace_bytes((int)r.a, &tb));
+                note(gpp_track_workspace_bytes((int)(r.a % 64), nullptr));
+                note(gpp_track_f64(nullptr, (int)r.a, (int)r.b, seq, 2, nullptr, nullptr, &tp, nullptr, nullptr, nullptr, nullptr, 0, nullptr));
+                note(gpp_track_f64((const float*)r.d[0].in, 8, 129 + (int)(r.b % 2000), seq, 2, r.d[0].in, r.d[0].out, &tp, (float*)r.d[0].out,
+                                   (int32_t*)(uintptr_t)r.d[0].bias, (int32_t*)(uintptr_t)r.d[0].bias, r.d[0].out, (size_t)r.d[0].partial_bytes, nullptr));
+                note(gpp_track_f64((const float*)r.d[0].in, 8, (int)(r.b % 128) + 1, seq, 2, r.d[0].in, r.d[0].out, &tp, (float*)r.d[0].out,
+                                   (int32_t*)(uintptr_t)r.d[0].bias, (int32_t*)(uintptr_t)r.d[0].bias, (void*)((uintptr_t)r.d[0].out | 8), 0, nullptr));
+            }
             // the plane distillation's host halves: sizes, then argument checks (bad pitch, K > M, null and misaligned pointers) that end before any launch
             note(gpp_poll_costs_workspace_bytes((int)r.a, &wb));
             note(gpp_plane_select_workspace_bytes((int)r.b, nullptr));

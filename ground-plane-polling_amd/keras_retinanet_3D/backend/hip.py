@@ -128,6 +128,24 @@ class AbsmaxDesc(ctypes.Structure):
                [(n, ctypes.c_int32) for n in ('C', 'c_off', 'layout', 'reserved')]
 
 
+GPP_TRACK_MAX_TRACKS, GPP_TRACK_FIELDS = 128, 10   # include/gpp.h, gpp_track_state
+
+
+class TrackState(ctypes.Structure):
+    """ gpp_track_state (include/gpp.h) """
+    _fields_ = [('id1', ctypes.c_int32 * GPP_TRACK_MAX_TRACKS), ('hits', ctypes.c_int32 * GPP_TRACK_MAX_TRACKS),
+                ('misses', ctypes.c_int32 * GPP_TRACK_MAX_TRACKS), ('score', c_float * GPP_TRACK_MAX_TRACKS),
+                ('box', (ctypes.c_double * GPP_TRACK_MAX_TRACKS) * GPP_TRACK_FIELDS),
+                ('next_id', ctypes.c_int32), ('frames', ctypes.c_int32), ('dropped', ctypes.c_int32), ('reserved', ctypes.c_int32)]
+
+
+class TrackParams(ctypes.Structure):
+    """ gpp_track_params (include/gpp.h) """
+    _fields_ = [('metric', ctypes.c_int32), ('max_age', ctypes.c_int32), ('smooth', ctypes.c_int32), ('reserved', ctypes.c_int32),
+                ('threshold', ctypes.c_double), ('gain_a', ctypes.c_double), ('gain_b', ctypes.c_double), ('gain_c', ctypes.c_double),
+                ('birth_score', ctypes.c_double)]
+
+
 class AbsmaxClearDesc(ctypes.Structure):
     """ gpp_absmax_clear_desc (include/gpp.h) """
     _fields_ = [('table', c_void_p), ('n', c_int64)]
@@ -159,6 +177,15 @@ def _declare(lib):
     if hasattr(lib, 'gpp_cuboid_nms_f64'):
         lib.gpp_cuboid_nms_f64.restype = c_int
         lib.gpp_cuboid_nms_f64.argtypes = [c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]
+    # the tracker (include/gpp.h, csrc/track.hip; absent from an older build named by GPP_LIB: it runs everything but track models)
+    if hasattr(lib, 'gpp_track_f64'):
+        lib.gpp_track_state_bytes.restype = c_int
+        lib.gpp_track_state_bytes.argtypes = [ctypes.POINTER(c_size_t)]
+        lib.gpp_track_workspace_bytes.restype = c_int
+        lib.gpp_track_workspace_bytes.argtypes = [c_int, ctypes.POINTER(c_size_t)]
+        lib.gpp_track_f64.restype = c_int
+        lib.gpp_track_f64.argtypes = [c_void_p, c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_void_p, c_void_p,
+                                      ctypes.POINTER(TrackParams), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     # KITTI's object benchmark (include/gpp.h, csrc/kitti_eval.hip; absent from an older build named by GPP_LIB: it runs everything but
     # evaluate_kitti(device=True) and score_poses_on_frames)
     if hasattr(lib, 'gpp_kitti_overlaps_f64'):
@@ -525,6 +552,52 @@ def cuboid_nms(rows, metric, threshold, out=None, counts=None, suppressor=None):
     check(lib().gpp_cuboid_nms_f64(ptr(rows), B, D, int(metric), float(threshold), ptr(out), ptr(counts), ptr(suppressor), stream_ptr()),
           'gpp_cuboid_nms_f64')
     return out, counts, suppressor
+
+
+def track_state_bytes():
+    n = c_size_t(0)
+    check(lib().gpp_track_state_bytes(ctypes.byref(n)), 'gpp_track_state_bytes')
+    return n.value
+
+
+def track_workspace_bytes(S):
+    n = c_size_t(0)
+    check(lib().gpp_track_workspace_bytes(int(S), ctypes.byref(n)), 'gpp_track_workspace_bytes')
+    return n.value
+
+
+def track(rows, state_in, params, seq_start=None, state_out=None, out=None, ids=None, hits=None, workspace=None):
+    """ gpp_track_f64 on the current stream: rows (N, D, 36) float32 on the device -- the rows of gpp_pose_f32 of N frames --, state_in
+    (S, gpp_track_state bytes) uint8 on the device, params a TrackParams, seq_start (S + 1) host integers (default: one sequence of all N
+    frames) -> (rows_out (N, D, 36) float32, ids (N, D) int32, hits (N, D) int32, state_out) on the device; no synchronisation.
+    out: where the rows go (default: a new tensor; `rows` itself: in place); state_out: default a new tensor (`state_in` itself: in place) """
+    import torch
+    if rows.dim() != 3 or rows.dtype != torch.float32 or rows.shape[2] != GPP_POSE_COLS:
+        raise ValueError('gpp_track_f64: rows must be (N, D, {}) float32, got {} {}'.format(GPP_POSE_COLS, tuple(rows.shape), rows.dtype))
+    N, D = int(rows.shape[0]), int(rows.shape[1])
+    dev = rows.device
+    nbytes = track_state_bytes()
+    if state_in.dim() != 2 or state_in.dtype != torch.uint8 or state_in.shape[1] != nbytes or state_in.device != dev:
+        raise ValueError('gpp_track_f64: the state must be (S, {}) uint8 on {}, got {} {}'.format(nbytes, dev, tuple(state_in.shape), state_in.dtype))
+    S = int(state_in.shape[0])
+    seq = (ctypes.c_int32 * (S + 1))(*([0, N] if seq_start is None and S == 1 else [int(v) for v in seq_start]))
+    covered = S > 0 and seq[0] == 0 and seq[S] == N
+    out = (torch.empty_like(rows) if covered else rows.clone()) if out is None else out      # (frames outside every sequence are not written)
+    ids = torch.full((N, D), -1, dtype=torch.int32, device=dev) if ids is None else ids
+    hits = torch.zeros((N, D), dtype=torch.int32, device=dev) if hits is None else hits
+    state_out = torch.empty_like(state_in) if state_out is None else state_out
+    need = track_workspace_bytes(S)
+    workspace = torch.empty((need,), dtype=torch.uint8, device=dev) if workspace is None else workspace
+    want = ((out, torch.float32, (N, D, GPP_POSE_COLS)), (ids, torch.int32, (N, D)), (hits, torch.int32, (N, D)),
+            (state_out, torch.uint8, (S, nbytes)))
+    for t, dtype, shape in want:
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev:
+            raise ValueError('gpp_track_f64: expected {} {} on {}, got {} {} on {}'.format(shape, dtype, dev, tuple(t.shape), t.dtype, t.device))
+    if workspace.dtype != torch.uint8 or workspace.device != dev:
+        raise ValueError('gpp_track_f64: the workspace must be uint8 on {}'.format(dev))
+    check(lib().gpp_track_f64(ptr(rows), N, D, seq, S, ptr(state_in), ptr(state_out), ctypes.byref(params), ptr(out), ptr(ids), ptr(hits),
+                              ptr(workspace), int(workspace.numel()), stream_ptr()), 'gpp_track_f64')
+    return out, ids, hits, state_out
 
 
 def label_prep(labels, label_counts, P, trig, det_types=0, own_box=True, detections=True):

@@ -39,6 +39,7 @@ import scipy.io
 
 from .. import models
 from ..utils import cuboid_nms, gpp_utils, visualization
+from ..utils import track as track_utils
 from ..utils.image import compute_resize_scale, preprocess_image, read_image_bgr, resize_image
 
 
@@ -75,7 +76,31 @@ def parse_args(args):
                              'stage of the plan on the GPU (cuboid_nms=(metric, threshold)), otherwise applied on the host before the results are written.')
     parser.add_argument('--cuboid-nms-threshold', type=float, default=None,
                         help='The overlap above which --cuboid-nms drops a detection, inside (0, 1).  No default: it depends on the checkpoint.')
+    parser.add_argument('--track', choices=['bev', '3d', 'dist'], default=None,
+                        help='Track the cuboids across the images (not in the reference CLI; needs --device-pose): the sorted image list is one '
+                             'sequence, every detection gets an identity that persists from frame to frame (csrc/track.hip, on the GPU behind '
+                             'the plan) and <output_dir>/<model name>/outputs/tracking/tracks.txt is written in KITTI\'s tracking format.  A '
+                             'detection continues a track when their cuboids overlap by more than --track-threshold in the bird\'s-eye view '
+                             '(bev) or in 3-D (3d), or when their centres lie closer than --track-threshold metres on the ground (dist).')
+    parser.add_argument('--track-threshold', type=float, default=None,
+                        help='The threshold of --track.  No default: it depends on the checkpoint and the frame rate.')
+    parser.add_argument('--track-max-age', type=int, default=track_utils.DEFAULTS['max_age'],
+                        help='Frames a track survives without a detection.')
+    parser.add_argument('--track-min-hits', type=int, default=1, help='Only tracks seen in at least this many frames are written to tracks.txt.')
+    parser.add_argument('--track-smooth', action='store_true',
+                        help='Write the filtered cuboid (position, size, r_y, alpha) of tracked detections instead of the detector\'s.')
     parsed = parser.parse_args(args)
+    if (parsed.track is None) != (parsed.track_threshold is None):
+        parser.error('--track and --track-threshold go together: both or neither')
+    if parsed.track is not None:
+        if not parsed.device_pose:
+            parser.error('--track follows the pose stage on the GPU: it needs --device-pose')
+        if parsed.save_images:
+            parser.error('--track does not draw: the composites carry no identities; run --save-images without it')
+        try:
+            track_utils.check_option(track_option(parsed))
+        except ValueError as e:
+            parser.error(str(e))
     if (parsed.cuboid_nms is None) != (parsed.cuboid_nms_threshold is None):
         parser.error('--cuboid-nms and --cuboid-nms-threshold go together: both or neither')
     if parsed.cuboid_nms is not None and not 0.0 < parsed.cuboid_nms_threshold < 1.0:
@@ -83,6 +108,13 @@ def parse_args(args):
     if parsed.range_audit and parsed.dtype != 'f16x3':
         parser.error('--range-audit audits the IEEE-half pairs of --dtype f16x3, not {}'.format(parsed.dtype))
     return parsed
+
+
+def track_option(args):
+    """ the model's `track` option of the command line, or None """
+    if args.track is None:
+        return None
+    return {'metric': args.track, 'threshold': args.track_threshold, 'max_age': args.track_max_age, 'smooth': args.track_smooth}
 
 
 def make_output_tree(args):
@@ -95,6 +127,8 @@ def make_output_tree(args):
         os.mkdir(os.path.join(output_dir, 'outputs', 'kitti'))
     if args.save_images:
         os.makedirs(os.path.join(output_dir, 'images', 'composite'))
+    if args.track is not None:
+        os.mkdir(os.path.join(output_dir, 'outputs', 'tracking'))
     return output_dir
 
 
@@ -153,17 +187,22 @@ def write_results_from_rows(args, output_dir, item, rows_b, count, picture=None)
         save_composite(output_dir, item, picture)
 
 
-def group_items(model, items):
-    """ the items of one batch in groups that run as one call each.  A model with a ragged form (RetinaNet3D.supports_ragged: the ResNets)
+def group_items(model, items, in_order=False):
+    """ the items of one batch in groups that run as one call each (in_order: only neighbours share a group, so that the groups keep
+    the items' order -- what a tracker needs).  A model with a ragged form (RetinaNet3D.supports_ragged: the ResNets)
     takes every frame of one height class (utils/image.height_class: the four KITTI frame sizes are one class) in one call; any other
     model takes frames of one raw shape per call, as the reference's batches must be.  Returns [(items, ragged)]: ragged = the
     group mixes raw shapes and goes to the model as a list. """
     from ..utils.image import height_class
     ragged_ok = getattr(model, 'supports_ragged', False)
-    groups = {}
-    for it in items:
+    groups, last = {}, None
+    for n, it in enumerate(items):
         shape = tuple(it['raw_image'].shape)
-        groups.setdefault(height_class(shape) if ragged_ok else shape, []).append(it)
+        key = height_class(shape) if ragged_ok else shape
+        if in_order:
+            last = (n, key) if last is None or last[1] != key else last
+            key = last
+        groups.setdefault(key, []).append(it)
     return [(group, len(set(tuple(it['raw_image'].shape) for it in group)) > 1) for group in groups.values()]
 
 
@@ -173,18 +212,22 @@ def main(args=None):
     args = parse_args(args)
 
     model = models.load_model(args.model_path, backbone_name=args.backbone, dtype=args.dtype, pose=args.device_pose, range_audit=args.range_audit,
-                              cuboid_nms=(args.cuboid_nms, args.cuboid_nms_threshold) if args.device_pose and args.cuboid_nms is not None else None)
+                              cuboid_nms=(args.cuboid_nms, args.cuboid_nms_threshold) if args.device_pose and args.cuboid_nms is not None else None,
+                              track=track_option(args))
     audit = {}               # --range-audit: per map, the report of the call that left it smallest
     plane_params = scipy.io.loadmat(args.plane_params_path)['road_planes_database']
     output_dir = make_output_tree(args)
 
     files = os.listdir(args.calib_dir)
+    if args.track is not None:
+        files = sorted(files)                    # the sorted image list is one sequence
+        tracks = open(os.path.join(output_dir, 'outputs', 'tracking', 'tracks.txt'), 'w')
     j = 0
     for start in range(0, len(files), max(args.batch_size, 1)):
         on_device = hasattr(model, 'predict_on_frames')
         items = [load_item(args, fn, on_device) for fn in files[start:start + max(args.batch_size, 1)]]
         # images of one call share a shape, or (a model with a ragged form) a height class; split otherwise
-        for group, ragged in group_items(model, items):
+        for group, ragged in group_items(model, items, in_order=args.track is not None):
             stack = list if ragged else np.stack          # a ragged group goes to the model as a list of differently sized frames
             P_inv = np.stack([it['P_inv'] for it in group])
             planes = np.tile(plane_params[None], (len(group), 1, 1))
@@ -192,7 +235,11 @@ def main(args=None):
             if args.device_pose:
                 frames = stack([it['raw_image'] for it in group])
                 pictures = [None] * len(group)
-                if args.save_images:
+                if args.track is not None:
+                    (rows, counts, ids, hits), _ = model.predict_tracks_on_frames(frames, P_inv, planes)
+                    for k in range(len(group)):
+                        tracks.write(track_utils.tracking_lines(j + k, rows[k], ids[k], hits[k], args.track_min_hits))
+                elif args.save_images:
                     P_raw = np.stack([raw_calibration(it) for it in group])
                     (rows, counts), _, pictures = model.predict_composites_on_frames(frames, P_inv, planes, P_raw, args.image_score_threshold)
                 else:
@@ -218,7 +265,8 @@ def main(args=None):
                     det, _ = cuboid_nms.suppress_detections(det, args.cuboid_nms, args.cuboid_nms_threshold)
                 write_results(args, output_dir, it, det)
 
-
+    if args.track is not None:
+        tracks.close()
     if args.range_audit:
         write_range_audit(output_dir, model, audit)
 

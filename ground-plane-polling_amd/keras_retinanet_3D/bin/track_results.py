@@ -1,0 +1,79 @@
+#!/usr/bin/env python
+
+"""
+Track the cuboids of a directory of KITTI result files (not in the reference): the sorted file list is one sequence, every detection gets
+an identity that persists from frame to frame and the tracks are written in KITTI's tracking format,
+
+    frame id Car -1 -1 alpha x1 y1 x2 y2 h w l x y z r_y score
+
+The network does not run again: the result files of bin/run_network.py --kitti are read (utils/kitti_eval.read_result_file), so a
+threshold can be swept.  On the GPU by default (csrc/track.hip: one launch for the whole sequence); --host uses the NumPy form
+(utils/track.track_rows_np) and, without --smooth, writes the same bytes.
+
+    track_results.py result_dir/ tracks.txt --metric dist --threshold 2.0 [--max-age 2] [--min-hits 1] [--smooth] [--host]
+"""
+
+import argparse
+import os
+import sys
+
+import numpy as np
+
+# Allow relative imports when being executed as script.
+if __name__ == "__main__" and __package__ is None:
+    sys.path.insert(0, os.path.join(os.path.dirname(__file__), '..', '..'))
+    import keras_retinanet_3D.bin  # noqa: F401
+    __package__ = "keras_retinanet_3D.bin"
+
+from ..utils import kitti_eval
+from ..utils import track as track_utils
+
+
+def parse_args(args):
+    parser = argparse.ArgumentParser(description='Track the cuboids of a directory of KITTI result files.')
+    parser.add_argument('result_dir', help='Directory of KITTI result files, one per frame; their sorted names are the sequence.')
+    parser.add_argument('tracks_path', help='The file to write, in KITTI\'s tracking format.')
+    parser.add_argument('--metric', choices=list(track_utils.METRICS), required=True,
+                        help='bev / 3d: a detection continues a track when their cuboids overlap by more than --threshold in the bird\'s-eye '
+                             'view / in 3-D; dist: when their centres lie closer than --threshold metres on the ground.')
+    parser.add_argument('--threshold', type=float, required=True, help='No default: it depends on the checkpoint and the frame rate.')
+    parser.add_argument('--max-age', type=int, default=track_utils.DEFAULTS['max_age'], help='Frames a track survives without a detection.')
+    parser.add_argument('--min-hits', type=int, default=1, help='Only tracks seen in at least this many frames are written.')
+    parser.add_argument('--birth-score', type=float, default=track_utils.DEFAULTS['birth_score'],
+                        help='Only detections with at least this score start a track.')
+    parser.add_argument('--smooth', action='store_true', help='Write the filtered cuboid of tracked detections instead of the detector\'s.')
+    parser.add_argument('--host', action='store_true', help='The NumPy form instead of the GPU.')
+    parsed = parser.parse_args(args)
+    try:
+        parsed.option = track_utils.check_option({'metric': parsed.metric, 'threshold': parsed.threshold, 'max_age': parsed.max_age,
+                                                  'birth_score': parsed.birth_score, 'smooth': parsed.smooth})
+    except ValueError as e:
+        parser.error(str(e))
+    return parsed
+
+
+def read_sequence(result_dir):
+    """ (names, rows (N, D, 36) float32): the sorted result files of a directory as pose rows, D = the most detections of a frame """
+    names = sorted(fn for fn in os.listdir(result_dir) if fn.endswith('.txt'))
+    results = [kitti_eval.read_result_file(os.path.join(result_dir, fn)) for fn in names]
+    cars = [r[r[:, 0] == 0] for r in results]
+    D = max([len(r) for r in cars] + [1])
+    if D > track_utils.MAX_DETECTIONS:
+        raise ValueError('a frame has {} detections, the tracker takes {}'.format(D, track_utils.MAX_DETECTIONS))
+    rows = [kitti_eval.rows_from_results(r, D) for r in cars]
+    return names, np.stack(rows) if rows else np.zeros((0, D, track_utils.POSE_COLS), np.float32)
+
+
+def main(args=None):
+    args = parse_args(sys.argv[1:] if args is None else args)
+    names, frames = read_sequence(args.result_dir)
+    run = track_utils.track_rows_np if args.host else track_utils.track_rows_device
+    rows, ids, hits, state = run(frames, args.option)
+    with open(args.tracks_path, 'w') as f:
+        for k in range(len(names)):
+            f.write(track_utils.tracking_lines(k, rows[k], ids[k], hits[k], args.min_hits))
+    print('{} frames, {} tracks, {} births dropped -> {}'.format(len(names), int(state['next_id']), int(state['dropped']), args.tracks_path))
+
+
+if __name__ == '__main__':
+    main()

@@ -52,7 +52,8 @@ def backbone(backbone_name):
 
 
 def load_model(filepath, backbone_name='resnet50', convert=False, nms=True, class_specific_filter=True,
-               orientation_specific_filter=False, dtype=None, on_range_event=None, plan=None, pose=False, range_audit=False, cuboid_nms=None):
+               orientation_specific_filter=False, dtype=None, on_range_event=None, plan=None, pose=False, range_audit=False, cuboid_nms=None,
+               track=None):
     """ Loads a RetinaNet-3D inference model (reference models/__init__.py:59-88).
 
     `convert` is accepted for signature compatibility: every model this function returns already
@@ -93,6 +94,15 @@ def load_model(filepath, backbone_name='resnet50', convert=False, nms=True, clas
     a row is dropped when a kept row overlaps it by more than the threshold in the bird's-eye view ('bev') or in 3-D ('3d').  Every reader of
     the rows (predict_poses_*, score_poses_on_frames, predict_composites_on_frames) sees the suppressed set; model.cuboid_suppressors()
     says which row removed which.  There is no default threshold: it depends on the checkpoint.  predict_on_batch is unchanged.
+    `track` (not in the reference; default None; needs pose=True): a pair (metric, threshold) or a dict {'metric': 'bev' | '3d' | 'dist',
+    'threshold': T, 'max_age': 2, 'gains': (a, b, c), 'birth_score': 0.0, 'smooth': False} -- the model gets predict_tracks_on_frames /
+    predict_tracks_on_batch, which follow the plan with one more launch (gpp_track_f64): the rows of every image
+    are associated greedily with the cuboids carried over from the frames before (overlap above T for 'bev' / '3d', centre distance on the
+    ground below T metres for 'dist') and get an identity that persists; a fixed-gain filter carries each cuboid.  The images of a call
+    are consecutive frames of the model's one sequence and a later call continues it; model.reset_tracks() starts a new one,
+    model.track_state() reads the state.  There is no default threshold: it depends on the checkpoint and the frame rate; the default
+    gains and max_age come from synthetic scenes only.  Every other method is unchanged and does not touch the tracker.  FramePipeline and
+    ShardedModel refuse such a model: they reorder or split the frames.
     """
     import os
     if dtype is None:
@@ -110,7 +120,7 @@ def load_model(filepath, backbone_name='resnet50', convert=False, nms=True, clas
         w = W.load_weights(filepath)
     model = RetinaNet3D(w, backbone_name=name, dtype=dtype, nms=nms, class_specific_filter=class_specific_filter,
                         orientation_specific_filter=orientation_specific_filter, on_range_event=on_range_event, plan=plan, pose=pose, range_audit=range_audit,
-                        cuboid_nms=cuboid_nms)
+                        cuboid_nms=cuboid_nms, track=track)
     if convert:
         model.summary()
     return model

@@ -38,6 +38,7 @@ from ..backend import hip
 from ..layers import conv as C
 from ..layers import mobilenet as M
 from ..utils import cuboid_nms as cuboid_nms_utils
+from ..utils import track as track_utils
 from . import tuning
 from . import weights as W
 from .builder import PlanBuilder
@@ -59,7 +60,7 @@ class RetinaNet3D(object):
 
     def __init__(self, weights, backbone_name='resnet50', dtype='f16x3', nms=True, class_specific_filter=True,
                  orientation_specific_filter=False, name='retinanet-bbox', on_range_event=None, plan=None, pose=False, range_audit=False,
-                 cuboid_nms=None):
+                 cuboid_nms=None, track=None):
         import torch
         # range_audit=True (dtype='f16x3' only): every plan also measures the largest |x| of every channel of every map an x3 convolution
         # reads (gpp_channel_absmax, _audit), and a synchronous call whose run left a whole map below RANGE_AUDIT_THRESHOLD reacts as
@@ -82,6 +83,13 @@ class RetinaNet3D(object):
         self.cuboid_nms = cuboid_nms_utils.check_option(cuboid_nms)
         if self.cuboid_nms is not None and not self.pose:
             raise ValueError('cuboid_nms={!r} suppresses pose rows: it needs pose=True'.format(cuboid_nms))
+        # track=(metric, threshold) or a dict (utils/track.check_option; pose=True only): predict_tracks_on_frames / _on_batch follow the plan
+        # with ONE more launch, gpp_track_f64 -- not a plan op: every plan and every other method is what it was.
+        # The images of a call are consecutive frames of the model's one sequence; the state lives in HBM between the calls
+        self.track = track_utils.check_option(track)
+        if self.track is not None and not self.pose:
+            raise ValueError('track={!r} associates pose rows: it needs pose=True'.format(track))
+        self._track_state = None             # (current, next): two (1, gpp_track_state) buffers, swapped after every answered call
         self._answered = None                # (model, plan) that answered the last call of the pose family
         # 'throughput' | 'latency' (models.load_model): which layers split their K loop (layers/conv.latency_split)
         self.plan_mode = plan or os.environ.get('GPP_PLAN', 'throughput')
@@ -799,6 +807,74 @@ class RetinaNet3D(object):
         self.put_frame_info(plan, scale, self._frame_shapes(frames_u8))
         self.run_plan(plan)
         return self.fetch_poses(plan, 'predict_poses_on_frames'), scale
+
+    # ------------------------------------------------------------------ tracks (pose=True, track=...)
+    def _track_buffers(self):
+        if self.track is None:
+            raise hip.GppError('this model has no tracker: load it with pose=True, track=(metric, threshold)')
+        if self._track_state is None:
+            torch = self.torch
+            state = torch.zeros((2, 1, hip.track_state_bytes()), dtype=torch.uint8, device=self.device)
+            self._track_state = [state[0], state[1]]
+            self._track_work = torch.empty((hip.track_workspace_bytes(1),), dtype=torch.uint8, device=self.device)
+            self._track_params = track_utils.params_of(self.track)
+        return self._track_state
+
+    def reset_tracks(self):
+        """ start a new sequence: the empty tracker (the next birth gets id 0) """
+        self._track_buffers()[0].zero_()
+
+    def track_state(self):
+        """ the tracker's state as one utils.track.STATE_DTYPE record (include/gpp.h, gpp_track_state).  One copy (synchronises). """
+        return track_utils.read_state(self._track_buffers()[0])[0]
+
+    def fetch_tracks(self, plan, what='predict_tracks_on_batch'):
+        """ ((rows, counts, ids, hits)) of the plan's last run: fetch_poses + the tracker's frame steps over the images of the batch, in
+        order.  The launch follows the plan (and its cuboid NMS) on the stream and is no plan op; it goes from the current state to a
+        second buffer, because _range_event calls the reader a second time on the float32 twin: the model commits by swapping the two
+        only after _answer has returned -- the state advances once per answered call, by the rows that answered it. """
+        torch = self.torch
+        state, nxt = self._track_buffers()
+        B, D = int(plan.pose_rows.shape[0]), int(plan.pose_rows.shape[1])
+        smooth = self.track['smooth']
+        out = torch.empty((B, D, hip.GPP_POSE_COLS), dtype=torch.float32, device=self.device) if smooth else None
+        tags = torch.empty((2, B, D), dtype=torch.int32, device=self.device)
+
+        def rows_and_tracks(model, p):
+            # (smooth: the plan's rows stay what predict_poses_* reads; otherwise the kernel's bit copy lands where it came from)
+            hip.track(p.pose_rows, state, self._track_params, state_out=nxt, out=out if smooth else p.pose_rows, ids=tags[0], hits=tags[1],
+                      workspace=self._track_work)
+            (rows, counts), count = self.read_poses(model, p)
+            if smooth:
+                rows = out.cpu().numpy()
+            host = tags.cpu().numpy()
+            return (rows, counts, host[0], host[1]), count
+
+        result = self._answer(plan, what, rows_and_tracks)
+        self._track_state = [nxt, state]
+        return result
+
+    def predict_tracks_on_batch(self, inputs, scales, image_shapes, heights=None):
+        """ predict_poses_on_batch + the tracker: the images of the call are consecutive frames of the model's one sequence, a later call
+        continues it (reset_tracks starts a new one).  Returns (rows (B, 100, 36) float32, counts (B,) int32, ids (B, 100) int32, hits
+        (B, 100) int32): ids[b, d] is the identity of row d of image b, -1 for padding rows, rows with a NaN among their cuboid's fields
+        and rows below the option's birth_score that matched nothing; hits the frames that identity has been seen in.  With smooth the
+        cuboid's columns of rows that carry an id are the filter's (include/gpp.h, gpp_track_f64). """
+        self._require_pose()
+        self._track_buffers()
+        plan = self.stage_inputs(inputs) if heights is None else self.stage_canvas(inputs, heights)
+        self.put_frame_info(plan, scales, image_shapes)
+        self.run_plan(plan)
+        return self.fetch_tracks(plan)
+
+    def predict_tracks_on_frames(self, frames_u8, P_inv, planes):
+        """ predict_tracks_on_batch for raw uint8 BGR frames (predict_on_frames): returns ((rows, counts, ids, hits), scale) """
+        self._require_pose()
+        self._track_buffers()
+        plan, scale = self.stage_frames(frames_u8, P_inv, planes)
+        self.put_frame_info(plan, scale, self._frame_shapes(frames_u8))
+        self.run_plan(plan)
+        return self.fetch_tracks(plan, 'predict_tracks_on_frames'), scale
 
     def score_poses_on_frames(self, frames_u8, P_inv, planes, labels):
         """ predict_poses_on_frames + the overlaps of KITTI's object benchmark (csrc/kitti_eval.hip) without the

@@ -87,6 +87,9 @@ class ShardedModel(object):
         if getattr(model, 'audit', False):
             raise ValueError('ShardedModel does not read the range audit of a model loaded with range_audit=True: it would run unwatched '
                              '-- audit one rank\'s model with predict_on_batch, or load the model without range_audit')
+        if getattr(model, 'track', None) is not None:
+            raise ValueError('ShardedModel splits a batch over the ranks: a model loaded with track=... needs the frames of its sequence in '
+                             'one place and in order -- use predict_tracks_on_frames on one rank')
         self.model = model
         self.group = group
 

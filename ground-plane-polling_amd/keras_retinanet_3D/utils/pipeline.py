@@ -29,6 +29,9 @@ class FramePipeline(object):
         if getattr(model, 'audit', False):
             raise ValueError('FramePipeline does not read the range audit of a model loaded with range_audit=True: it would run unwatched '
                              '-- use predict_on_frames, or load the model without range_audit')
+        if getattr(model, 'track', None) is not None:
+            raise ValueError('FramePipeline keeps several batches in flight and answers a range event out of order: a model loaded with '
+                             'track=... needs its frames in order -- use predict_tracks_on_frames')
         self.model = model
         self.torch = torch
         self.depth = max(3, int(depth))

@@ -1,0 +1,305 @@
+"""
+Tracking of cuboids across frames: the pose rows of one frame are associated greedily with the cuboids carried over from the frames
+before, and every carried cuboid is a fixed-gain (alpha-beta) filter -- DESIGN.md section 4.28 is the specification, include/gpp.h
+(gpp_track_f64, gpp_track_state) the contract.  An identity per car that persists from frame to frame, and optionally a pose that does
+not jump by the detector's depth jitter.  There is no default threshold: it depends on the checkpoint and the frame rate.
+
+Two forms of one computation:
+    track_rows_np        NumPy, no GPU and no library: the candidates of a frame at once (the clipping of utils/kitti_eval.py), the
+                         greedy pass serial over the sorted candidates, as the rule demands.
+    track_rows_device    csrc/track.hip: one launch, one workgroup per sequence.
+
+The state is one record of STATE_DTYPE, byte for byte the gpp_track_state of include/gpp.h; all zero bytes is the empty tracker.
+"""
+import numpy as np
+
+from . import gpp_utils, kitti_eval
+
+METRICS = ('bev', '3d', 'dist')             # include/gpp.h: GPP_TRACK_BEV 0, GPP_TRACK_3D 1, GPP_TRACK_DIST 2
+POSE_COLS = kitti_eval.POSE_COLS
+MAX_DETECTIONS = kitti_eval.MAX_DETECTIONS  # what the device form takes per frame
+MAX_TRACKS = 128                            # GPP_TRACK_MAX_TRACKS
+FIELDS = ('x', 'y', 'z', 'r_y', 'h', 'w', 'l', 'vx', 'vy', 'vz')
+ROW_COLS = [19, 31, 21, 32, 30, 17, 18]     # the pose row's column of the first seven fields
+STATE_DTYPE = np.dtype([('id1', '<i4', (MAX_TRACKS,)), ('hits', '<i4', (MAX_TRACKS,)), ('misses', '<i4', (MAX_TRACKS,)),
+                        ('score', '<f4', (MAX_TRACKS,)), ('box', '<f8', (len(FIELDS), MAX_TRACKS)),
+                        ('next_id', '<i4'), ('frames', '<i4'), ('dropped', '<i4'), ('reserved', '<i4')])
+# gains and max_age: chosen on synthetic constant-velocity scenes only (tests/track_oracle.py); no real sequence has been measured
+DEFAULTS = {'max_age': 2, 'gains': (0.5, 0.25, 0.25), 'birth_score': 0.0, 'smooth': False}
+PI = float(np.pi)
+TWO_PI = 2.0 * PI
+TRACKING_FORMAT = '%d %d ' + gpp_utils.KITTI_FORMAT
+
+
+def metric_code(metric):
+    if metric not in METRICS:
+        raise ValueError("track: the metric must be 'bev', '3d' or 'dist', got {!r}".format(metric))
+    return METRICS.index(metric)
+
+
+def check_option(option):
+    """ the `track` option of load_model / RetinaNet3D: None, a pair (metric, threshold), or a dict with 'metric' and 'threshold' and
+    optionally 'max_age', 'gains' (a, b, c), 'birth_score', 'smooth' -> None or the complete dict """
+    if option is None:
+        return None
+    if isinstance(option, dict):
+        unknown = sorted(set(option) - {'metric', 'threshold'} - set(DEFAULTS))
+        if unknown or 'metric' not in option or 'threshold' not in option:
+            raise ValueError("track: a dict needs 'metric' and 'threshold' and may have {}; got {!r}".format(sorted(DEFAULTS), option))
+        opt = dict(DEFAULTS, **option)
+    else:
+        try:
+            metric, threshold = option
+        except (TypeError, ValueError):
+            raise ValueError("track must be None, a pair (metric, threshold) such as ('dist', 2.0) or a dict, got {!r}".format(option))
+        opt = dict(DEFAULTS, metric=metric, threshold=threshold)
+    code = metric_code(opt['metric'])
+    thr = float(opt['threshold'])
+    if code == 2 and not (np.isfinite(thr) and thr > 0.0):
+        raise ValueError('track: a dist threshold must be finite and positive, got {!r}'.format(thr))
+    if code != 2 and not 0.0 <= thr < 1.0:
+        raise ValueError('track: an overlap threshold must lie inside [0, 1), got {!r}'.format(thr))
+    try:
+        a, b, c = [float(g) for g in opt['gains']]
+    except (TypeError, ValueError):
+        raise ValueError('track: gains must be three numbers (a, b, c), got {!r}'.format(opt['gains']))
+    if not (0.0 < a <= 1.0 and 0.0 <= b <= 1.0 and 0.0 <= c <= 1.0):
+        raise ValueError('track: gains must satisfy 0 < a <= 1, 0 <= b <= 1, 0 <= c <= 1, got {!r}'.format((a, b, c)))
+    if int(opt['max_age']) != opt['max_age'] or opt['max_age'] < 0:
+        raise ValueError('track: max_age must be an integer >= 0, got {!r}'.format(opt['max_age']))
+    birth = float(opt['birth_score'])
+    if np.isnan(birth):
+        raise ValueError('track: birth_score must not be NaN')
+    return {'metric': opt['metric'], 'threshold': thr, 'max_age': int(opt['max_age']), 'gains': (a, b, c), 'birth_score': birth,
+            'smooth': bool(opt['smooth'])}
+
+
+def empty_state(S=None):
+    """ the empty tracker: one record (S None) or S of them """
+    return np.zeros(() if S is None else (int(S),), STATE_DTYPE)
+
+
+def read_state(buffer):
+    """ the bytes of gpp_track_state(s) -- a uint8 tensor or array (S, bytes) or (bytes,), or a bytes object -> a STATE_DTYPE array (S,) or
+    one record; a copy """
+    if hasattr(buffer, 'cpu'):
+        buffer = buffer.cpu().numpy()
+    raw = np.frombuffer(buffer, np.uint8) if isinstance(buffer, (bytes, bytearray)) else np.ascontiguousarray(buffer).view(np.uint8)
+    if raw.size % STATE_DTYPE.itemsize:
+        raise ValueError('read_state: {} bytes are no multiple of a state ({})'.format(raw.size, STATE_DTYPE.itemsize))
+    out = raw.reshape(-1).view(STATE_DTYPE).copy()
+    return out[0] if np.ndim(buffer) <= 1 and out.size == 1 else out
+
+
+def tracks_of(state):
+    """ one state -> a list of dicts, one per occupied slot in slot order: slot, id, hits, misses, score and the ten fields """
+    out = []
+    for t in np.flatnonzero(state['id1'] != 0):
+        rec = {'slot': int(t), 'id': int(state['id1'][t]) - 1, 'hits': int(state['hits'][t]), 'misses': int(state['misses'][t]),
+               'score': float(state['score'][t])}
+        rec.update({name: float(state['box'][k][t]) for k, name in enumerate(FIELDS)})
+        out.append(rec)
+    return out
+
+
+def wrap(a):
+    """ into [-pi, pi): the wrap of csrc/pose.hip, operation for operation """
+    a = a - TWO_PI * np.floor(a / TWO_PI)
+    a = np.where(a < 0.0, a + TWO_PI, a)
+    a = np.where(a >= TWO_PI, a - TWO_PI, a)
+    return np.where(a >= PI, a - TWO_PI, a)
+
+
+def candidate_keys(box, occupied, rows, valid, metric, threshold):
+    """ the candidate table of one frame: (MAX_TRACKS, D) float64, +inf where the pair is no candidate, otherwise its key -- the smaller
+    the better: q for 'dist', minus the overlap otherwise.  box (10, MAX_TRACKS): the PREDICTED state; rows (D, 36) float32 """
+    D = rows.shape[0]
+    keys = np.full((MAX_TRACKS, D), np.inf)
+    ts, ds = np.flatnonzero(occupied), np.flatnonzero(valid)
+    if ts.size == 0 or ds.size == 0:
+        return keys
+    t, d = np.repeat(ts, ds.size), np.tile(ds, ts.size)
+    g = rows[d].astype(np.float64)
+    sx, sy, sz, sry, sh, sw, sl = [box[k][t] for k in range(7)]
+    gx, gy, gz, gry, gh, gw, gl = [g[:, c] for c in ROW_COLS]
+    with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
+        if metric == 'dist':
+            dx, dz = gx - sx, gz - sz
+            q = dx * dx + dz * dz
+            hit = q < threshold * threshold
+            keys[t[hit], d[hit]] = q[hit]
+            return keys
+        inter = kitti_eval.rect_intersections(sl, sw, sx, sz, sry, gl, gw, gx, gz, gry)
+        area_d, area_g = sl * sw, gl * gw
+        if metric == 'bev':
+            o = inter / (area_d + area_g - inter)
+        else:
+            iv = inter * kitti_eval.height_overlaps(sy, sh, gy, gh)
+            o = iv / (area_d * sh + area_g * gh - iv)
+        hit = o > threshold
+    keys[t[hit], d[hit]] = -o[hit]
+    return keys
+
+
+def greedy(keys):
+    """ candidates best first (ties: the smaller slot, then the smaller row), each taken iff its slot and its row are both still free
+    -> [(slot, row)] in the order taken """
+    t, d = np.nonzero(np.isfinite(keys))
+    order = np.lexsort((d, t, keys[t, d]))
+    slot_taken, row_taken, out = set(), set(), []
+    for k in order:
+        if t[k] in slot_taken or d[k] in row_taken:
+            continue
+        slot_taken.add(t[k])
+        row_taken.add(d[k])
+        out.append((int(t[k]), int(d[k])))
+    return out
+
+
+def step_np(state, rows, opt, keys_out=None):
+    """ one frame step on `state` (one writable STATE_DTYPE record, changed in place) -> (rows_out (D, 36) float32, ids (D,) int32,
+    hits (D,) int32).  keys_out: a list that receives the frame's candidate table (the tests' margins) """
+    rows = np.asarray(rows, np.float32).reshape(-1, POSE_COLS)
+    D = rows.shape[0]
+    if D > MAX_DETECTIONS:
+        raise ValueError('track: {} rows in a frame, at most {}'.format(D, MAX_DETECTIONS))
+    a, b, c = opt['gains']
+    box, id1, hits, misses, score = state['box'], state['id1'], state['hits'], state['misses'], state['score']
+    occupied = id1 != 0
+    box[0:3, occupied] = box[0:3, occupied] + box[7:10, occupied]                                  # 1 predict
+    live = rows[:, 14] >= 0.0                                                                       # 2 rows
+    valid = live & ~np.isnan(rows[:, ROW_COLS]).any(axis=1)
+    keys = candidate_keys(box, occupied, rows, valid, opt['metric'], opt['threshold'])              # 3 candidates
+    if keys_out is not None:
+        keys_out.append(keys)
+    pairs = greedy(keys)                                                                            # 4 greedy
+    row_slot = np.full(D, -1, np.int64)
+    if pairs:                                                                                       # 5 update
+        t, d = np.array([p[0] for p in pairs]), np.array([p[1] for p in pairs])
+        z = rows[d][:, ROW_COLS].astype(np.float64).T                                               # (7, matched)
+        r = z[0:3] - box[0:3, t]
+        box[7:10, t] = box[7:10, t] + b * r
+        box[0:3, t] = box[0:3, t] + a * r
+        box[4:7, t] = box[4:7, t] + c * (z[4:7] - box[4:7, t])
+        delta = wrap(z[3] - box[3, t])
+        delta = np.where(delta >= PI / 2.0, delta - PI, delta)
+        delta = np.where(delta < -(PI / 2.0), delta + PI, delta)
+        box[3, t] = wrap(box[3, t] + a * delta)
+        hits[t] += 1
+        misses[t] = 0
+        score[t] = rows[d, 12]
+        row_slot[d] = t
+    lost = occupied.copy()                                                                          # 6 deaths
+    lost[[p[0] for p in pairs]] = False
+    misses[lost] += 1
+    dead = lost & (misses > opt['max_age'])
+    for field in (id1, hits, misses, score):
+        field[dead] = 0
+    box[:, dead] = 0.0
+    with np.errstate(invalid='ignore'):                                                             # 7 births
+        born = np.flatnonzero(valid & (row_slot < 0) & (rows[:, 12].astype(np.float64) >= opt['birth_score']))
+    free = np.flatnonzero(id1 == 0)
+    n = min(born.size, free.size)
+    t, d = free[:n], born[:n]
+    id1[t] = state['next_id'] + np.arange(n, dtype=np.int32) + 1
+    hits[t], misses[t], score[t] = 1, 0, rows[d, 12]
+    box[0:7, t] = rows[d][:, ROW_COLS].astype(np.float64).T
+    box[7:10, t] = 0.0
+    row_slot[d] = t
+    state['next_id'] += n
+    state['dropped'] += born.size - n
+    state['frames'] += 1
+    has = row_slot >= 0                                                                             # 8 outputs
+    ids = np.where(has, id1[row_slot] - 1, -1).astype(np.int32)
+    out_hits = np.where(has, hits[row_slot], 0).astype(np.int32)
+    out = rows.copy()
+    if opt['smooth'] and has.any():
+        t = row_slot[has]
+        for k, col in enumerate(ROW_COLS):
+            out[has, col] = box[k, t].astype(np.float32)
+        out[has, 25] = wrap(box[3, t] - np.arctan2(box[0, t], box[2, t])).astype(np.float32)
+    return out, ids, out_hits
+
+
+def track_rows_np(rows_per_frame, options, state=None, keys_out=None):
+    """ the NumPy form: rows_per_frame (N, D, 36) float32 (or a list of (D_f, 36) arrays), the consecutive frames of one sequence; options:
+    what check_option takes; state: one STATE_DTYPE record (None: the empty tracker; it is not changed) -> (rows_out, ids, hits, state):
+    arrays (N, D, 36), (N, D), (N, D) (lists for a list) and the new state.  As the device form, N * D == 0 leaves the state as it is. """
+    opt = check_option(options)
+    state = empty_state() if state is None else np.array(state, STATE_DTYPE).reshape(())
+    state = state.copy()
+    as_list = isinstance(rows_per_frame, (list, tuple))
+    frames = [np.asarray(r, np.float32).reshape(-1, POSE_COLS) for r in rows_per_frame] if as_list else np.asarray(rows_per_frame, np.float32)
+    if not as_list and frames.size == 0:
+        return frames.copy(), np.zeros(frames.shape[:2], np.int32), np.zeros(frames.shape[:2], np.int32), state
+    res = [step_np(state, r, opt, keys_out) for r in frames]
+    if as_list:
+        return [x[0] for x in res], [x[1] for x in res], [x[2] for x in res], state
+    return np.stack([x[0] for x in res]), np.stack([x[1] for x in res]), np.stack([x[2] for x in res]), state
+
+
+def params_of(options):
+    """ options -> backend.hip.TrackParams """
+    from ..backend import hip
+    opt = check_option(options)
+    a, b, c = opt['gains']
+    return hip.TrackParams(metric_code(opt['metric']), opt['max_age'], int(opt['smooth']), 0, opt['threshold'], a, b, c, opt['birth_score'])
+
+
+def state_tensor(state, device, S=1):
+    """ None (S empty trackers), STATE_DTYPE records or a uint8 tensor -> the (S, bytes) uint8 tensor gpp_track_f64 takes """
+    import torch
+    if isinstance(state, torch.Tensor):
+        return state
+    host = empty_state(S) if state is None else np.atleast_1d(np.array(state, STATE_DTYPE))
+    return torch.as_tensor(np.ascontiguousarray(host).view(np.uint8).reshape(host.shape[0], STATE_DTYPE.itemsize).copy()).to(device)
+
+
+def track_rows_device(rows, options, state=None, seq_start=None, out=None, state_out=None):
+    """ csrc/track.hip: rows (N, D, 36), the frames of S sequences (seq_start (S + 1,), default one sequence of all frames): a NumPy array
+    -> NumPy results and STATE_DTYPE state(s), or a float32 device tensor -> device tensors with the state as (S, bytes) uint8 (no
+    synchronisation; read_state reads it).  state: None (empty), STATE_DTYPE record(s) or such a tensor.  out / state_out (tensors only):
+    where the rows and the state go -- `rows` and `state` themselves are allowed.
+    Returns (rows_out, ids (N, D) int32, hits (N, D) int32, state).  D <= 128. """
+    import torch
+    from ..backend import hip
+    params = params_of(options)
+    S = 1 if seq_start is None else len(seq_start) - 1
+    if isinstance(rows, torch.Tensor):
+        if rows.dim() != 3 or not rows.is_contiguous():
+            raise ValueError('track_rows_device: rows must be a dense (N, D, {}) tensor, got {}'.format(POSE_COLS, tuple(rows.shape)))
+        return hip.track(rows, state_tensor(state, rows.device, S), params, seq_start, state_out=state_out, out=out)
+    host = np.ascontiguousarray(rows, np.float32)
+    if host.ndim != 3 or host.shape[2] != POSE_COLS:
+        raise ValueError('track_rows_device: rows must be (N, D, {}), got {}'.format(POSE_COLS, host.shape))
+    dev = hip.require_device()
+    res = hip.track(torch.as_tensor(host).to(dev), state_tensor(state, dev, S), params, seq_start)
+    new = read_state(res[3])
+    return res[0].cpu().numpy(), res[1].cpu().numpy(), res[2].cpu().numpy(), (new[0] if seq_start is None else new)
+
+
+def tracking_lines(frame, rows, ids, hits, min_hits=1):
+    """ the lines of one frame in KITTI's tracking format, `frame id Car -1 -1 alpha x1 y1 x2 y2 h w l x y z r_y score`: the rows that
+    carry an id whose track has at least min_hits hits, in row order """
+    rows = np.asarray(rows, np.float32).reshape(-1, POSE_COLS)
+    ids, hits = np.asarray(ids).reshape(-1), np.asarray(hits).reshape(-1)
+    keep = np.flatnonzero((ids >= 0) & (hits >= min_hits))
+    values = rows[keep][:, gpp_utils.KITTI_COLUMNS].astype(np.float64)
+    out = []
+    for k, v in zip(keep, values):
+        out.append(TRACKING_FORMAT % ((int(frame), int(ids[k])) + tuple(v.tolist())))
+    return ''.join(out)
+
+
+def id_switches(gt_ids_per_frame, ids_per_frame):
+    """ the identity switches of a sequence: gt_ids_per_frame[f][k] is the true object of row k of frame f (< 0: none), ids_per_frame[f][k]
+    the id the tracker gave it (< 0: none).  A switch is counted whenever an object carries another id than the last one it carried. """
+    last, switches = {}, 0
+    for gts, ids in zip(gt_ids_per_frame, ids_per_frame):
+        for g, i in zip(np.asarray(gts).reshape(-1).tolist(), np.asarray(ids).reshape(-1).tolist()):
+            if g < 0 or i < 0:
+                continue
+            if g in last and last[g] != i:
+                switches += 1
+            last[g] = i
+    return switches

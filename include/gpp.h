@@ -774,6 +774,80 @@ int gpp_cuboid_nms_f64(const float* rows_in, int B, int D, int metric, double io
                        float* rows_out, int32_t* counts, int32_t* suppressor, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Tracking of cuboids across frames on the device (csrc/track.hip; DESIGN.md section 4.28 is the specification, utils/track.py the
+ * host form): a greedy association of the rows of gpp_pose_f32 of one frame with the cuboids carried over from the frames before, and a
+ * fixed-gain (alpha-beta) filter on each carried cuboid.  One launch, one workgroup per sequence, which walks its frames in order.
+ *
+ *   rows_in, rows_out (N, D, GPP_POSE_COLS) float32, device: the rows of N frames.  rows_out == rows_in is allowed; otherwise the two do
+ *               not overlap.  A workgroup reads all it needs of a frame before it writes any of that frame.
+ *   seq_start   (S + 1) int32 on the HOST, 0 <= seq_start[0] <= ... <= seq_start[S] <= N: the frames of sequence s are
+ *               [seq_start[s], seq_start[s + 1]) in time order.  Frames outside every sequence are not touched.
+ *   state_in, state_out (S, gpp_track_state) on the device, 8-byte aligned; they may be the same buffer, otherwise they do not overlap.
+ *               A state of all zero bytes is the empty tracker.  The host may read a state back (gpp_track_state below).
+ *   frame step  all float64, every operation separate.  For the rows of one frame:
+ *     1 predict    every occupied slot: x += vx, y += vy, z += vz (velocity is per frame step; there is no time difference).
+ *     2 rows       a row is live iff its column 14 is >= 0; a live row with a NaN among the columns 17 18 19 21 30 31 32 is blind: never
+ *                  matched, never born, id -1.
+ *     3 candidates slot t against live, non-blind row d.  GPP_TRACK_BEV / GPP_TRACK_3D: the overlap of gpp_kitti_overlaps_f64 (plane 1 /
+ *                  plane 2) with the slot's predicted cuboid in the place of the detection and the row in the place of the label
+ *                  (csrc/rot_iou.h, the gate of gpp_cuboid_nms_f64 included); a candidate iff overlap > threshold (strict); the larger
+ *                  overlap is better.  GPP_TRACK_DIST: q = dx dx + dz dz between the centres on the ground plane; a candidate iff
+ *                  q < threshold * threshold; the smaller q is better.
+ *     4 greedy     candidates best first, ties to the smaller slot, then to the smaller row; taken iff slot and row are both free.
+ *     5 update     of a matched pair, per component of x y z: r = row - predicted, position = predicted + a r, velocity += b r;
+ *                  h (30), w (17), l (18): s += c (row - s); r_y: delta = wrap(row - slot) in [-pi, pi), delta -= pi if delta >= pi / 2,
+ *                  delta += pi if delta < -pi / 2 (a detection facing the other way is read as facing the track's), r_y = wrap(r_y +
+ *                  a delta), the wrap of gpp_pose_f32; hits += 1, misses = 0, score = the row's column 12.
+ *     6 deaths     an occupied, unmatched slot: misses += 1; freed (all its fields 0) iff misses > max_age.
+ *     7 births     after the deaths: live, non-blind, unmatched rows with column 12 >= birth_score (a NaN score is not), in ascending row
+ *                  order, each into the lowest free slot: id = next_id++, the row's fields, velocity 0, hits 1, misses 0.  No free slot:
+ *                  id -1 and dropped += 1.
+ *   track_ids   (N, D) int32: the id of the slot the row matched or was born into; -1 for padding, blind and unborn rows.
+ *   track_hits  (N, D) int32: that slot's hits after the step; 0 where the id is -1.
+ *   rows_out    smooth == 0: a bit copy.  smooth == 1: in rows that carry an id the columns 19 31 21 30 17 18 32 are the slot's
+ *               x y z h w l r_y after the step, each rounded to float32 once, and column 25 is wrap(r_y - atan2(x, z)); all else a bit copy.
+ *   workspace   gpp_track_workspace_bytes(S) bytes on the device, 8-byte aligned: seq_start's copy and, per sequence, the
+ *               GPP_TRACK_MAX_TRACKS x GPP_KITTI_MAX_DETECTIONS float64 table of the frame's candidates and its transpose (128 KiB each:
+ *               they do not fit into LDS beside the clipping buffers).  Nothing in it survives the call.
+ *
+ *   GPP_ERR_BAD_ARG, nothing launched: an unknown metric; a BEV / 3-D threshold outside [0, 1); a DIST threshold that is not finite and
+ *   positive; gain_a outside (0, 1]; gain_b or gain_c outside [0, 1]; max_age < 0; smooth other than 0 or 1; reserved != 0; a NaN in any
+ *   of them or in birth_score; a seq_start that is not monotone inside [0, N]; a null pointer; a negative size.  A short workspace:
+ *   GPP_ERR_WORKSPACE.  D > GPP_KITTI_MAX_DETECTIONS: GPP_ERR_UNSUPPORTED.  N * D == 0 or S == 0: GPP_OK, state_in is copied to state_out
+ *   and nothing else is written.
+ * ---------------------------------------------------------------------------------------- */
+#define GPP_TRACK_BEV 0
+#define GPP_TRACK_3D 1
+#define GPP_TRACK_DIST 2
+#define GPP_TRACK_MAX_TRACKS 128
+#define GPP_TRACK_FIELDS 10              /* x y z r_y h w l vx vy vz */
+typedef struct gpp_track_state {
+    int32_t id1[GPP_TRACK_MAX_TRACKS];                        /* id + 1 of the slot's track; 0: the slot is free */
+    int32_t hits[GPP_TRACK_MAX_TRACKS];                       /* frames in which the track was matched, its birth included */
+    int32_t misses[GPP_TRACK_MAX_TRACKS];                     /* frames since it was last matched */
+    float score[GPP_TRACK_MAX_TRACKS];                        /* column 12 of the row it last matched */
+    double box[GPP_TRACK_FIELDS][GPP_TRACK_MAX_TRACKS];       /* field-major: box[f][slot] */
+    int32_t next_id;                                          /* the id the next birth gets */
+    int32_t frames;                                           /* frame steps so far */
+    int32_t dropped;                                          /* births that found no free slot */
+    int32_t reserved;
+} gpp_track_state;
+typedef struct gpp_track_params {
+    int32_t metric;                      /* GPP_TRACK_BEV | GPP_TRACK_3D | GPP_TRACK_DIST */
+    int32_t max_age;
+    int32_t smooth;
+    int32_t reserved;                    /* must be 0 */
+    double threshold;
+    double gain_a, gain_b, gain_c;       /* position, velocity, dimensions */
+    double birth_score;
+} gpp_track_params;
+int gpp_track_state_bytes(size_t* bytes);                     /* sizeof(gpp_track_state) */
+int gpp_track_workspace_bytes(int S, size_t* bytes);
+int gpp_track_f64(const float* rows_in, int N, int D, const int32_t* seq_start, int S, const void* state_in, void* state_out,
+                  const gpp_track_params* params, float* rows_out, int32_t* track_ids, int32_t* track_hits,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * KITTI keypoint ("mod") labels on the device (csrc/label_prep.hip; DESIGN.md section 4.18 is the specification, utils/label_prep.py the
  * host form): what the reference's label_prep/create_mod_labels.m, computeBox3D.m and projectToImage.m make of a label_2 row and the
  * camera-2 matrix -- the 20 fields that bin/evaluate.py and KittiGenerator read.  Parity with MATLAB itself is UNPINNED.  One launch,
