@@ -236,6 +236,27 @@ int main(int argc, char** argv)
                 note(gpp_track_f64((const float*)r.d[0].in, 8, (int)(r.b % 128) + 1, seq, 2, r.d[0].in, r.d[0].out, &tp, (float*)r.d[0].out,
                                    (int32_t*)(uintptr_t)r.d[0].bias, (int32_t*)(uintptr_t)r.d[0].bias, (void*)((uintptr_t)r.d[0].out | 8), 0, nullptr));
             }
+            // the tracking score: fuzzed parameters, sizes and sequence starts against null pointers, more rows or trajectories than the kernels
+            // take, and a workspace of no bytes -- all end before any launch or copy (seq_start is the one host array gpp_mot_clear reads)
+            {
+                gpp_mot_params mp = {(int32_t)(r.c % 5) - 1, (int32_t)(r.c % 11 == 0), (double)(r.a % 5) * 0.5 - 0.5, (double)(r.b % 4), 0.0, 25.0};
+                int32_t seq[3] = {(int32_t)(r.c % 3) - 1, (int32_t)(r.a % 9), (int32_t)(r.b % 9)};
+                size_t wb = 0;
+                note(gpp_mot_clear_workspace_bytes((int)r.a, &wb));
+                note(gpp_mot_clear_workspace_bytes((int)(r.a % 64), nullptr));
+                note(gpp_mot_assign(nullptr, nullptr, nullptr, nullptr, nullptr, (int)r.a, (int)r.b, (int)r.c, &mp, nullptr, nullptr, nullptr, nullptr, nullptr));
+                note(gpp_mot_assign((const double*)r.d[0].in, (const double*)r.d[0].in, (const int32_t*)(uintptr_t)r.d[0].bias, (const float*)r.d[0].in,
+                                    (const int32_t*)(uintptr_t)r.d[0].bias, 8, 129 + (int)(r.b % 2000), (int)(r.c % 128), &mp, (int32_t*)r.d[0].out,
+                                    (int32_t*)r.d[0].out, (int32_t*)r.d[0].out, (int64_t*)r.d[0].out, nullptr));
+                note(gpp_mot_clear(nullptr, nullptr, nullptr, nullptr, nullptr, (int)r.a, (int)r.b, (int)r.c, seq, 2, (int)(r.b % 2048), nullptr, nullptr,
+                                   nullptr, 0, nullptr));
+                note(gpp_mot_clear((const int32_t*)r.d[0].in, (const int32_t*)r.d[0].in, (const int32_t*)r.d[0].in, (const int32_t*)r.d[0].in,
+                                   (const int64_t*)r.d[0].in, 8, (int)(r.b % 128) + 1, (int)(r.c % 128) + 1, seq, 2, 1025 + (int)(r.a % 100),
+                                   (int64_t*)r.d[0].out, (int32_t*)r.d[0].out, r.d[0].out, 0, nullptr));
+                note(gpp_mot_clear((const int32_t*)r.d[0].in, (const int32_t*)r.d[0].in, (const int32_t*)r.d[0].in, (const int32_t*)r.d[0].in,
+                                   (const int64_t*)r.d[0].in, 8, (int)(r.b % 128) + 1, (int)(r.c % 128) + 1, seq, 2, (int)(r.a % 1024),
+                                   (int64_t*)r.d[0].out, (int32_t*)r.d[0].out, (void*)((uintptr_t)r.d[0].out | 2), 0, nullptr));
+            }
             // the plane distillation's host halves: sizes, then argument checks (bad pitch, K > M, null and misaligned pointers) that end before any launch
             note(gpp_poll_costs_workspace_bytes((int)r.a, &wb));
             note(gpp_plane_select_workspace_bytes((int)r.b, nullptr));

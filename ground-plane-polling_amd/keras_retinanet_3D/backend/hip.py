@@ -146,6 +146,16 @@ class TrackParams(ctypes.Structure):
                 ('birth_score', ctypes.c_double)]
 
 
+GPP_MOT_SCALE_BITS, GPP_MOT_BIG, GPP_MOT_MAX_TRAJECTORIES = 20, 1 << 28, 1024      # include/gpp.h, gpp_mot_assign / gpp_mot_clear
+GPP_MOT_FRAME_COUNTS, GPP_MOT_SEQ_COUNTS, GPP_MOT_TRAJ_COLS = 8, 16, 4
+
+
+class MotParams(ctypes.Structure):
+    """ gpp_mot_params (include/gpp.h) """
+    _fields_ = [('metric', ctypes.c_int32), ('reserved', ctypes.c_int32), ('min_overlap', ctypes.c_double), ('max_occlusion', ctypes.c_double),
+                ('max_truncation', ctypes.c_double), ('min_height', ctypes.c_double)]
+
+
 class AbsmaxClearDesc(ctypes.Structure):
     """ gpp_absmax_clear_desc (include/gpp.h) """
     _fields_ = [('table', c_void_p), ('n', c_int64)]
@@ -186,6 +196,16 @@ def _declare(lib):
         lib.gpp_track_f64.restype = c_int
         lib.gpp_track_f64.argtypes = [c_void_p, c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_void_p, c_void_p,
                                       ctypes.POINTER(TrackParams), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    # the tracking score (include/gpp.h, csrc/mot_eval.hip; absent from an older build named by GPP_LIB: it runs everything but
+    # evaluate_tracking(device=True))
+    if hasattr(lib, 'gpp_mot_assign'):
+        lib.gpp_mot_assign.restype = c_int
+        lib.gpp_mot_assign.argtypes = [c_void_p] * 5 + [c_int] * 3 + [ctypes.POINTER(MotParams)] + [c_void_p] * 5
+        lib.gpp_mot_clear_workspace_bytes.restype = c_int
+        lib.gpp_mot_clear_workspace_bytes.argtypes = [c_int, ctypes.POINTER(c_size_t)]
+        lib.gpp_mot_clear.restype = c_int
+        lib.gpp_mot_clear.argtypes = [c_void_p] * 5 + [c_int] * 3 + [ctypes.POINTER(ctypes.c_int32), c_int, c_int] + [c_void_p] * 3 + \
+            [c_size_t, c_void_p]
     # KITTI's object benchmark (include/gpp.h, csrc/kitti_eval.hip; absent from an older build named by GPP_LIB: it runs everything but
     # evaluate_kitti(device=True) and score_poses_on_frames)
     if hasattr(lib, 'gpp_kitti_overlaps_f64'):
@@ -598,6 +618,53 @@ def track(rows, state_in, params, seq_start=None, state_out=None, out=None, ids=
     check(lib().gpp_track_f64(ptr(rows), N, D, seq, S, ptr(state_in), ptr(state_out), ctypes.byref(params), ptr(out), ptr(ids), ptr(hits),
                               ptr(workspace), int(workspace.numel()), stream_ptr()), 'gpp_track_f64')
     return out, ids, hits, state_out
+
+
+def mot_assign(overlaps, labels, label_counts, rows, ids, params):
+    """ gpp_mot_assign on the current stream: overlaps (N, 4, D, A) float64, labels (N, A, 16) float64, label_counts (N,) int32, rows
+    (N, D, 36) float32 and ids (N, D) int32 on the device, params a MotParams -> (match (N, A) int32, label_outcome (N, A) int32,
+    row_outcome (N, D) int32, frame_counts (N, 8) int64) on the device; no synchronisation """
+    import torch
+    N, D, A = _kitti_check(rows, labels, label_counts, 'gpp_mot_assign')
+    dev = rows.device
+    for t, dtype, shape in ((overlaps, torch.float64, (N, 4, D, A)), (ids, torch.int32, (N, D))):
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev:
+            raise ValueError('gpp_mot_assign: expected {} {} on {}, got {} {} on {}'.format(shape, dtype, dev, tuple(t.shape), t.dtype, t.device))
+    match = torch.full((N, A), -1, dtype=torch.int32, device=dev)
+    label_outcome = torch.zeros((N, A), dtype=torch.int32, device=dev)
+    row_outcome = torch.zeros((N, D), dtype=torch.int32, device=dev)
+    frame_counts = torch.zeros((N, GPP_MOT_FRAME_COUNTS), dtype=torch.int64, device=dev)
+    check(lib().gpp_mot_assign(ptr(overlaps), ptr(labels), ptr(label_counts), ptr(rows), ptr(ids), N, D, A, ctypes.byref(params),
+                               ptr(match), ptr(label_outcome), ptr(row_outcome), ptr(frame_counts), stream_ptr()), 'gpp_mot_assign')
+    return match, label_outcome, row_outcome, frame_counts
+
+
+def mot_clear_workspace_bytes(S):
+    n = c_size_t(0)
+    check(lib().gpp_mot_clear_workspace_bytes(int(S), ctypes.byref(n)), 'gpp_mot_clear_workspace_bytes')
+    return n.value
+
+
+def mot_clear(match, label_outcome, traj, ids, frame_counts, seq_start, max_traj):
+    """ gpp_mot_clear on the current stream: match, label_outcome and traj (N, A) int32, ids (N, D) int32 and frame_counts (N, 8) int64 on
+    the device, seq_start (S + 1) host integers -> (seq_counts (S, 16) int64, traj_table (S, max_traj, 4) int32) on the device; no
+    synchronisation """
+    import torch
+    N, A, D = int(match.shape[0]), int(match.shape[1]), int(ids.shape[1])
+    dev = match.device
+    want = ((match, torch.int32, (N, A)), (label_outcome, torch.int32, (N, A)), (traj, torch.int32, (N, A)), (ids, torch.int32, (N, D)),
+            (frame_counts, torch.int64, (N, GPP_MOT_FRAME_COUNTS)))
+    for t, dtype, shape in want:
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev:
+            raise ValueError('gpp_mot_clear: expected {} {} on {}, got {} {} on {}'.format(shape, dtype, dev, tuple(t.shape), t.dtype, t.device))
+    S = len(seq_start) - 1
+    seq = (ctypes.c_int32 * (S + 1))(*[int(v) for v in seq_start])
+    seq_counts = torch.zeros((S, GPP_MOT_SEQ_COUNTS), dtype=torch.int64, device=dev)
+    traj_table = torch.zeros((S, int(max_traj), GPP_MOT_TRAJ_COLS), dtype=torch.int32, device=dev)
+    workspace = torch.empty((mot_clear_workspace_bytes(S),), dtype=torch.uint8, device=dev)
+    check(lib().gpp_mot_clear(ptr(match), ptr(label_outcome), ptr(traj), ptr(ids), ptr(frame_counts), N, D, A, seq, S, int(max_traj),
+                              ptr(seq_counts), ptr(traj_table), ptr(workspace), int(workspace.numel()), stream_ptr()), 'gpp_mot_clear')
+    return seq_counts, traj_table
 
 
 def label_prep(labels, label_counts, P, trig, det_types=0, own_box=True, detections=True):

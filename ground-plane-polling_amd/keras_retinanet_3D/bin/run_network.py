@@ -89,7 +89,13 @@ def parse_args(args):
     parser.add_argument('--track-min-hits', type=int, default=1, help='Only tracks seen in at least this many frames are written to tracks.txt.')
     parser.add_argument('--track-smooth', action='store_true',
                         help='Write the filtered cuboid (position, size, r_y, alpha) of tracked detections instead of the detector\'s.')
+    parser.add_argument('--tracking-labels', default=None,
+                        help='With --track: the sequence\'s KITTI label_02 file.  tracks.txt is scored against it on the GPU (CLEAR-MOT on the '
+                             'optimal assignment of every frame, image overlap >= 0.5, csrc/mot_eval.hip) and the table of '
+                             'bin/evaluate_tracking.py is printed.')
     parsed = parser.parse_args(args)
+    if parsed.tracking_labels is not None and parsed.track is None:
+        parser.error('--tracking-labels scores the tracks of --track: it needs --track')
     if (parsed.track is None) != (parsed.track_threshold is None):
         parser.error('--track and --track-threshold go together: both or neither')
     if parsed.track is not None:
@@ -267,6 +273,10 @@ def main(args=None):
 
     if args.track is not None:
         tracks.close()
+    if args.tracking_labels is not None:
+        from ..utils import mot_eval
+        print(mot_eval.summary_table(mot_eval.evaluate_tracking(args.tracking_labels, os.path.join(output_dir, 'outputs', 'tracking', 'tracks.txt'),
+                                                                device=True)))
     if args.range_audit:
         write_range_audit(output_dir, model, audit)
 

@@ -11,6 +11,10 @@ threshold can be swept.  On the GPU by default (csrc/track.hip: one launch for t
 (utils/track.track_rows_np) and, without --smooth, writes the same bytes.
 
     track_results.py result_dir/ tracks.txt --metric dist --threshold 2.0 [--max-age 2] [--min-hits 1] [--smooth] [--host]
+                     [--labels label_02/0000.txt [--score-metric image] [--score-min-overlap 0.5]]
+
+--labels scores the tracks just written against the sequence's label_02 file (CLEAR-MOT; on the GPU unless
+--host) and prints the table of bin/evaluate_tracking.py: a threshold sweep is one loop of this one command.
 """
 
 import argparse
@@ -25,7 +29,9 @@ if __name__ == "__main__" and __package__ is None:
     import keras_retinanet_3D.bin  # noqa: F401
     __package__ = "keras_retinanet_3D.bin"
 
+from . import evaluate_tracking
 from ..utils import kitti_eval
+from ..utils import mot_eval
 from ..utils import track as track_utils
 
 
@@ -43,10 +49,13 @@ def parse_args(args):
                         help='Only detections with at least this score start a track.')
     parser.add_argument('--smooth', action='store_true', help='Write the filtered cuboid of tracked detections instead of the detector\'s.')
     parser.add_argument('--host', action='store_true', help='The NumPy form instead of the GPU.')
+    parser.add_argument('--labels', help='The sequence\'s label_02 file: score the tracks just written and print the CLEAR-MOT table.')
+    evaluate_tracking.add_scoring_arguments(parser, 'score-')
     parsed = parser.parse_args(args)
     try:
         parsed.option = track_utils.check_option({'metric': parsed.metric, 'threshold': parsed.threshold, 'max_age': parsed.max_age,
                                                   'birth_score': parsed.birth_score, 'smooth': parsed.smooth})
+        mot_eval.check_params(parsed.mot_metric, parsed.mot_min_overlap)
     except ValueError as e:
         parser.error(str(e))
     return parsed
@@ -73,6 +82,11 @@ def main(args=None):
         for k in range(len(names)):
             f.write(track_utils.tracking_lines(k, rows[k], ids[k], hits[k], args.min_hits))
     print('{} frames, {} tracks, {} births dropped -> {}'.format(len(names), int(state['next_id']), int(state['dropped']), args.tracks_path))
+    if args.labels:
+        result = mot_eval.evaluate_tracking(args.labels, args.tracks_path, metric=args.mot_metric, min_overlap=args.mot_min_overlap,
+                                            device=not args.host)
+        print(mot_eval.summary_table(result))
+        return result
 
 
 if __name__ == '__main__':

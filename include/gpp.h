@@ -848,6 +848,81 @@ int gpp_track_f64(const float* rows_in, int N, int D, const int32_t* seq_start, 
                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * CLEAR-MOT scoring of tracks on the device (csrc/mot_eval.hip; DESIGN.md section 4.29 is the specification, a restatement of the KITTI
+ * tracking devkit's CLEAR-MOT -- parity with the devkit itself is UNPINNED; utils/mot_eval.py is the host form): per frame the OPTIMAL
+ * one-to-one assignment of the tracker's rows to the labels (the Hungarian method, shortest augmenting paths, exact integers), then per
+ * sequence the identity switches, fragmentations and mostly-tracked / mostly-lost shares.  Two launches.
+ *
+ *   overlaps (N, 4, D, A) float64, labels (N, A, GPP_KITTI_LABEL_COLS) float64, label_counts (N) int32 (clamped to [0, A]), rows
+ *   (N, D, GPP_POSE_COLS) float32, device: exactly what gpp_kitti_overlaps_f64 took and wrote.  ids (N, D) int32, device: the tracker's id
+ *   of every row, in the layout gpp_track_f64 writes.  A row is a ROW of the assignment iff its column 14 is >= 0 and its id is >= 0.
+ *
+ * gpp_mot_assign: one frame per workgroup of one wavefront; the frame's cost matrix lies in LDS.
+ *   status      of label a < count, from its type code (column 0): a Car (0) COUNTS, unless occlusion (column 2) > max_occlusion or
+ *               truncation (column 1) > max_truncation or |y2 - y1| (columns 7, 5) < min_height: then it is IGNORED; a Van (1) is IGNORED;
+ *               DontCare (2) is a region only; anything else is not in play.  The labels in play are the counting and the ignored ones.
+ *   matrix      square, of side n = max(G, T): G labels in play in ascending label order are its rows, T rows in ascending row order its
+ *               columns.  With o the overlap of plane `metric` (0 image, 1 BEV, 2 3-D): the pair is admissible iff o >= min_overlap (not
+ *               strict; float64; false for NaN); k = floor(min(o * 2^20, 2^20)); the cell is 2^20 - k if admissible, GPP_MOT_BIG otherwise
+ *               and in every padding cell.  n * 2^20 < GPP_MOT_BIG: the minimum total cost is "most admissible pairs, then the largest sum
+ *               of k".
+ *   assignment  the matrix's rows i = 0 .. n - 1 in order, each by one shortest augmenting path over int64 potentials u (rows), v
+ *               (columns), all zero at the start.  Per row: minv = infinity, no column used, i0 = i.  Repeat: for every unused column j,
+ *               cur = cell(i0, j) - u[i0] - v[j]; if cur < minv[j] then minv[j] = cur and way[j] = the column the step came from; delta =
+ *               the smallest minv of the unused columns, j1 = the FIRST column that has it; u += delta on row i and on the row of every
+ *               used column, v -= delta on every used column, minv -= delta on every unused one; j1 becomes used; if j1 holds a row,
+ *               i0 = that row and repeat, otherwise the rows are handed back along way, j1 first, and row i takes the last column.
+ *   match       (N, A) int32: the row index d that label a is paired with, -1 for none.  A pair whose cell is GPP_MOT_BIG is no pair.
+ *   label_outcome (N, A) int32: 0 not in play, 1 counting and paired (a true positive), 2 counting and unpaired (a false negative),
+ *               3 ignored and paired, 4 ignored and unpaired.
+ *   row_outcome (N, D) int32: 0 no row, 1 paired with a counting label, 2 paired with an ignored label (neither true nor false positive),
+ *               3 unpaired: a false positive, 4 unpaired and |y2 - y1| (columns 29, 27) < min_height, 5 unpaired and plane 3 of the overlaps
+ *               (intersection over the row's area) with some DontCare label of the frame is > 0.5.
+ *   frame_counts (N, GPP_MOT_FRAME_COUNTS) int64: true positives, false positives, false negatives, counting labels, the sum of k over
+ *               the true positives, the assignment's total cost (all n cells), G, T.
+ *   GPP_ERR_BAD_ARG, nothing launched: a null pointer that the sizes make necessary (A == 0: labels, label_counts, match, label_outcome and
+ *   overlaps may be null; D == 0: rows, ids, row_outcome and overlaps may be null), a negative size, a metric other than 0 1 2, min_overlap
+ *   outside [0, 1] or NaN, a NaN limit, reserved != 0.  D or A > 128: GPP_ERR_UNSUPPORTED.  N == 0: GPP_OK, nothing launched.  D == 0 is
+ *   legal: every counting label is a false negative.  A == 0 is legal: every row that is high enough is a false positive.
+ *
+ * gpp_mot_clear: one workgroup per sequence, which walks its frames in order.
+ *   seq_start   (S + 1) int32 on the HOST, as gpp_track_f64 takes it.
+ *   traj        (N, A) int32, device: the trajectory of label a -- the index of its track_id among the sequence's track_ids, compacted by
+ *               the host to [0, max_traj); a trajectory appears at most once per frame.  Read only where the label counts.
+ *   per trajectory, over the frames in which it counts: counting += 1; paired: matched += 1, and if it was paired before: a SWITCH when
+ *               the row's id differs from the id at its last paired frame, a FRAGMENTATION when its previous counting frame was unpaired.
+ *   traj_table  (S, max_traj, GPP_MOT_TRAJ_COLS) int32: counting frames, matched frames, switches, fragmentations.
+ *   seq_counts  (S, GPP_MOT_SEQ_COUNTS) int64: the sums of frame_counts' first six columns over the sequence's frames, then switches,
+ *               fragmentations, mostly tracked (5 matched >= 4 counting), partly tracked, mostly lost (5 matched < counting), trajectories
+ *               with a counting frame, frames, and three zeros.  Integer sums: the result does not depend on the order.
+ *   max_traj <= GPP_MOT_MAX_TRAJECTORIES: the state of a sequence's trajectories lies in LDS (21 KiB at the cap); beyond:
+ *   GPP_ERR_UNSUPPORTED, as D or A > 128.  workspace: gpp_mot_clear_workspace_bytes(S) bytes on the device, 4-byte aligned (seq_start's
+ *   copy); short: GPP_ERR_WORKSPACE.  Null pointer, negative size, a seq_start that is not monotone inside [0, N]: GPP_ERR_BAD_ARG,
+ *   nothing launched.  S == 0: GPP_OK, nothing launched.
+ * ---------------------------------------------------------------------------------------- */
+#define GPP_MOT_SCALE_BITS 20
+#define GPP_MOT_BIG (1 << 28)
+#define GPP_MOT_MAX_TRAJECTORIES 1024
+#define GPP_MOT_FRAME_COUNTS 8
+#define GPP_MOT_SEQ_COUNTS 16
+#define GPP_MOT_TRAJ_COLS 4
+typedef struct gpp_mot_params {
+    int32_t metric;                      /* the overlaps' plane: 0 image, 1 BEV, 2 3-D */
+    int32_t reserved;                    /* must be 0 */
+    double min_overlap;                  /* the devkit: 0.5 */
+    double max_occlusion;                /* 2 */
+    double max_truncation;               /* 0 */
+    double min_height;                   /* 25 */
+} gpp_mot_params;
+int gpp_mot_assign(const double* overlaps, const double* labels, const int32_t* label_counts, const float* rows, const int32_t* ids,
+                   int N, int D, int A, const gpp_mot_params* params, int32_t* match, int32_t* label_outcome, int32_t* row_outcome,
+                   int64_t* frame_counts, void* stream);
+int gpp_mot_clear_workspace_bytes(int S, size_t* bytes);
+int gpp_mot_clear(const int32_t* match, const int32_t* label_outcome, const int32_t* traj, const int32_t* ids,
+                  const int64_t* frame_counts, int N, int D, int A, const int32_t* seq_start, int S, int max_traj,
+                  int64_t* seq_counts, int32_t* traj_table, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * KITTI keypoint ("mod") labels on the device (csrc/label_prep.hip; DESIGN.md section 4.18 is the specification, utils/label_prep.py the
  * host form): what the reference's label_prep/create_mod_labels.m, computeBox3D.m and projectToImage.m make of a label_2 row and the
  * camera-2 matrix -- the 20 fields that bin/evaluate.py and KittiGenerator read.  Parity with MATLAB itself is UNPINNED.  One launch,
