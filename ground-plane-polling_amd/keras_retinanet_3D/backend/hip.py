@@ -156,6 +156,10 @@ class MotParams(ctypes.Structure):
                 ('max_truncation', ctypes.c_double), ('min_height', ctypes.c_double)]
 
 
+# include/gpp.h, gpp_hota_potential / gpp_hota_match / gpp_hota_reduce
+GPP_HOTA_LEVELS, GPP_HOTA_HIST, GPP_HOTA_FRAME_COLS, GPP_HOTA_SEQ_COLS, GPP_HOTA_TAB_COLS, GPP_HOTA_SEQ_TAB_COLS = 19, 20, 40, 8, 4, 6
+
+
 class AbsmaxClearDesc(ctypes.Structure):
     """ gpp_absmax_clear_desc (include/gpp.h) """
     _fields_ = [('table', c_void_p), ('n', c_int64)]
@@ -206,6 +210,18 @@ def _declare(lib):
         lib.gpp_mot_clear.restype = c_int
         lib.gpp_mot_clear.argtypes = [c_void_p] * 5 + [c_int] * 3 + [ctypes.POINTER(ctypes.c_int32), c_int, c_int] + [c_void_p] * 3 + \
             [c_size_t, c_void_p]
+    # HOTA (include/gpp.h, csrc/hota_eval.hip; absent from an older build named by GPP_LIB: it runs everything but the hota=True scores)
+    if hasattr(lib, 'gpp_hota_potential'):
+        c_ll = ctypes.c_longlong
+        lib.gpp_hota_workspace_bytes.restype = c_int
+        lib.gpp_hota_workspace_bytes.argtypes = [c_ll, c_ll, c_int, c_int, ctypes.POINTER(c_size_t)]
+        lib.gpp_hota_potential.restype = c_int
+        lib.gpp_hota_potential.argtypes = [c_void_p] * 5 + [c_int] * 4 + [ctypes.POINTER(ctypes.c_int32), c_ll, c_ll, c_void_p, c_size_t, c_void_p]
+        lib.gpp_hota_match.restype = c_int
+        lib.gpp_hota_match.argtypes = [c_void_p] * 5 + [c_int] * 4 + [ctypes.POINTER(ctypes.c_int32), c_ll, c_ll, c_void_p, c_void_p, c_void_p,
+                                       c_size_t, c_void_p]
+        lib.gpp_hota_reduce.restype = c_int
+        lib.gpp_hota_reduce.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_ll, c_ll, c_void_p, c_void_p, c_size_t, c_void_p]
     # KITTI's object benchmark (include/gpp.h, csrc/kitti_eval.hip; absent from an older build named by GPP_LIB: it runs everything but
     # evaluate_kitti(device=True) and score_poses_on_frames)
     if hasattr(lib, 'gpp_kitti_overlaps_f64'):
@@ -665,6 +681,93 @@ def mot_clear(match, label_outcome, traj, ids, frame_counts, seq_start, max_traj
     check(lib().gpp_mot_clear(ptr(match), ptr(label_outcome), ptr(traj), ptr(ids), ptr(frame_counts), N, D, A, seq, S, int(max_traj),
                               ptr(seq_counts), ptr(traj_table), ptr(workspace), int(workspace.numel()), stream_ptr()), 'gpp_mot_clear')
     return seq_counts, traj_table
+
+
+def hota_workspace_bytes(cells, vecs, max_frames, S):
+    n = c_size_t(0)
+    check(lib().gpp_hota_workspace_bytes(int(cells), int(vecs), int(max_frames), int(S), ctypes.byref(n)), 'gpp_hota_workspace_bytes')
+    return n.value
+
+
+def hota_workspace(cells, vecs, max_frames, S, device):
+    """ the zeroed workspace of gpp_hota_* for pair tables of `cells` cells and `vecs` counters in all """
+    import torch
+    return torch.zeros((hota_workspace_bytes(cells, vecs, max_frames, S),), dtype=torch.uint8, device=device)
+
+
+def hota_tables(workspace, cells, vecs):
+    """ the views include/gpp.h documents: (P int64 (cells,), A int32 (cells,), hist int32 (cells, 20), counters int32 (vecs,)) """
+    import torch
+    cells, vecs = int(cells), int(vecs)
+    at_hist = (12 * cells + 15) // 16 * 16
+    at_cnt = at_hist + 4 * GPP_HOTA_HIST * cells
+    return (workspace[:8 * cells].view(torch.int64), workspace[8 * cells:12 * cells].view(torch.int32),
+            workspace[at_hist:at_cnt].view(torch.int32).view(cells, GPP_HOTA_HIST), workspace[at_cnt:at_cnt + 4 * vecs].view(torch.int32))
+
+
+def _host_table(what, table, lines, cols):
+    """ a host table of `lines` x `cols` integers as a contiguous int32 array (kept alive by the caller for the call) """
+    import numpy as np
+    out = np.ascontiguousarray(np.asarray(table).reshape(-1), dtype=np.int32)
+    if out.size != lines * cols:
+        raise ValueError('{}: the host table must hold {} lines of {}'.format(what, lines, cols))
+    return out
+
+
+def _table_ptr(table):
+    return table.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+
+
+def _hota_frames(what, overlaps, label_outcome, row_outcome, traj, trk, frame_tab, workspace):
+    import torch
+    if overlaps.dim() != 4:
+        raise ValueError('{}: overlaps must be (N, 4, D, A), got {}'.format(what, tuple(overlaps.shape)))
+    N, D, A = int(overlaps.shape[0]), int(overlaps.shape[2]), int(overlaps.shape[3])
+    dev = overlaps.device
+    want = ((overlaps, torch.float64, (N, 4, D, A)), (label_outcome, torch.int32, (N, A)), (row_outcome, torch.int32, (N, D)),
+            (traj, torch.int32, (N, A)), (trk, torch.int32, (N, D)))
+    for t, dtype, shape in want:
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev:
+            raise ValueError('{}: expected {} {} on {}, got {} {} on {}'.format(what, shape, dtype, dev, tuple(t.shape), t.dtype, t.device))
+    if workspace.dtype != torch.uint8 or workspace.device != dev:
+        raise ValueError('{}: the workspace must be uint8 on {}'.format(what, dev))
+    return N, D, A, _host_table(what, frame_tab, N, GPP_HOTA_TAB_COLS)
+
+
+def hota_potential(overlaps, label_outcome, row_outcome, traj, trk, metric, frame_tab, cells, vecs, workspace):
+    """ gpp_hota_potential on the current stream (pass 1): overlaps (N, 4, D, A) float64, label_outcome and traj (N, A) int32, row_outcome
+    and trk (N, D) int32 on the device, frame_tab N * 4 host integers (cell_base, n_gt, n_trk, vec_base per frame), the workspace of
+    hota_workspace -- adds the frames to the pair tables in the workspace; no synchronisation """
+    N, D, A, tab = _hota_frames('gpp_hota_potential', overlaps, label_outcome, row_outcome, traj, trk, frame_tab, workspace)
+    check(lib().gpp_hota_potential(ptr(overlaps), ptr(label_outcome), ptr(row_outcome), ptr(traj), ptr(trk), N, D, A, int(metric), _table_ptr(tab),
+                                   int(cells), int(vecs), ptr(workspace), int(workspace.numel()), stream_ptr()), 'gpp_hota_potential')
+
+
+def hota_match(overlaps, label_outcome, row_outcome, traj, trk, metric, frame_tab, cells, vecs, workspace):
+    """ gpp_hota_match on the current stream (pass 2, after pass 1 has seen every frame of the sequences): the arguments of hota_potential
+    -> (hota_match (N, A) int32, frame_hota (N, 40) int64) on the device; no synchronisation """
+    import torch
+    N, D, A, tab = _hota_frames('gpp_hota_match', overlaps, label_outcome, row_outcome, traj, trk, frame_tab, workspace)
+    match = torch.full((N, A), -1, dtype=torch.int32, device=overlaps.device)
+    frame_hota = torch.zeros((N, GPP_HOTA_FRAME_COLS), dtype=torch.int64, device=overlaps.device)
+    check(lib().gpp_hota_match(ptr(overlaps), ptr(label_outcome), ptr(row_outcome), ptr(traj), ptr(trk), N, D, A, int(metric), _table_ptr(tab),
+                               int(cells), int(vecs), ptr(match), ptr(frame_hota), ptr(workspace), int(workspace.numel()), stream_ptr()),
+          'gpp_hota_match')
+    return match, frame_hota
+
+
+def hota_reduce(frame_hota, seq_tab, cells, vecs, workspace):
+    """ gpp_hota_reduce on the current stream: frame_hota (N, 40) int64 on the device, seq_tab S * 6 host integers (cell_base, n_gt, n_trk,
+    vec_base, first frame, one past the last) -> seq_hota (S, 19, 8) int64 on the device: TP FN FP SQ ASS ASSRE ASSPR 0; no synchronisation """
+    import torch
+    if frame_hota.dim() != 2 or frame_hota.dtype != torch.int64 or int(frame_hota.shape[1]) != GPP_HOTA_FRAME_COLS:
+        raise ValueError('gpp_hota_reduce: frame_hota must be (N, {}) int64, got {} {}'.format(GPP_HOTA_FRAME_COLS, tuple(frame_hota.shape), frame_hota.dtype))
+    S = len(seq_tab) // GPP_HOTA_SEQ_TAB_COLS
+    tab = _host_table('gpp_hota_reduce', seq_tab, S, GPP_HOTA_SEQ_TAB_COLS)
+    seq_hota = torch.zeros((S, GPP_HOTA_LEVELS, GPP_HOTA_SEQ_COLS), dtype=torch.int64, device=frame_hota.device)
+    check(lib().gpp_hota_reduce(ptr(frame_hota), int(frame_hota.shape[0]), _table_ptr(tab), S, int(cells), int(vecs), ptr(seq_hota), ptr(workspace),
+                                int(workspace.numel()), stream_ptr()), 'gpp_hota_reduce')
+    return seq_hota
 
 
 def label_prep(labels, label_counts, P, trig, det_types=0, own_box=True, detections=True):

@@ -93,9 +93,13 @@ def parse_args(args):
                         help='With --track: the sequence\'s KITTI label_02 file.  tracks.txt is scored against it on the GPU (CLEAR-MOT on the '
                              'optimal assignment of every frame, image overlap >= 0.5, csrc/mot_eval.hip) and the table of '
                              'bin/evaluate_tracking.py is printed.')
+    parser.add_argument('--hota', action='store_true',
+                        help='With --tracking-labels: also score HOTA (csrc/hota_eval.hip) and print its eight columns in the table.')
     parsed = parser.parse_args(args)
     if parsed.tracking_labels is not None and parsed.track is None:
         parser.error('--tracking-labels scores the tracks of --track: it needs --track')
+    if parsed.hota and parsed.tracking_labels is None:
+        parser.error('--hota scores the tracks against --tracking-labels: it needs --tracking-labels')
     if (parsed.track is None) != (parsed.track_threshold is None):
         parser.error('--track and --track-threshold go together: both or neither')
     if parsed.track is not None:
@@ -276,7 +280,7 @@ def main(args=None):
     if args.tracking_labels is not None:
         from ..utils import mot_eval
         print(mot_eval.summary_table(mot_eval.evaluate_tracking(args.tracking_labels, os.path.join(output_dir, 'outputs', 'tracking', 'tracks.txt'),
-                                                                device=True)))
+                                                                device=True, hota=args.hota)))
     if args.range_audit:
         write_range_audit(output_dir, model, audit)
 

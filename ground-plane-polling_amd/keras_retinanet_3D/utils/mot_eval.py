@@ -355,7 +355,7 @@ def _result(packed, params, match, lout, rout, frame_counts, seq_counts, tables,
             'seq_start': np.asarray(packed.seq_start)}
 
 
-def evaluate_packed_np(packed, params, names=None):
+def evaluate_packed_np(packed, params, names=None, hota=False):
     N, A, D = packed.labels.shape[0], packed.labels.shape[1], packed.rows.shape[1]
     match, lout = np.full((N, A), -1, np.int32), np.zeros((N, A), np.int32)
     rout, frame_counts = np.zeros((N, D), np.int32), np.zeros((N, 8), np.int64)
@@ -364,12 +364,18 @@ def evaluate_packed_np(packed, params, names=None):
         o = kitti_eval.image_overlaps(packed.rows[f], packed.labels[f, :c])
         match[f, :c], lout[f, :c], rout[f], frame_counts[f] = frame_np(o, packed.labels[f, :c], packed.rows[f], packed.ids[f], params)
     seq_counts, tables = clear_np(match, lout, packed.traj, packed.ids, frame_counts, packed.seq_start, [t.size for t in packed.traj_ids])
-    return _result(packed, params, match, lout, rout, frame_counts, seq_counts, tables, names)
+    result = _result(packed, params, match, lout, rout, frame_counts, seq_counts, tables, names)
+    if hota:
+        from . import hota_eval
+        hota_eval.add_hota_np(result, packed, params)
+    return result
 
 
-def evaluate_packed_device(packed, params, names=None):
+def evaluate_packed_device(packed, params, names=None, hota=False):
     """ csrc/mot_eval.hip: the frames in chunks whose overlaps stay below utils/kitti_eval.OVERLAP_WORKSPACE_BYTES, one assignment launch
-    per chunk, then one launch for all trajectories; rows and ids that are device tensors already are used where they lie """
+    per chunk, then one launch for all trajectories; rows and ids that are device tensors already are used where they lie.
+    hota: csrc/hota_eval.hip beside it (utils/hota_eval.DeviceRun) -- its pass 1 in this sweep over the chunks, its pass 2 in a second
+    sweep, which recomputes the overlaps unless the call has a single chunk """
     import torch
     from ..backend import hip
     dev = packed.rows.device if _is_tensor(packed.rows) else hip.require_device()
@@ -385,10 +391,18 @@ def evaluate_packed_device(packed, params, names=None):
     counts = torch.as_tensor(packed.label_counts).to(dev, non_blocking=True)
     traj = torch.as_tensor(packed.traj).to(dev, non_blocking=True)
     step = kitti_eval.chunk_images(D, A)
+    hota_run = None
+    if hota:
+        from . import hota_eval
+        hota_run = hota_eval.DeviceRun(packed, params, rows, ids, traj, step)
     parts = []
     for at in range(0, N, step):
         r, g, c, i = rows[at:at + step], labels[at:at + step], counts[at:at + step], ids[at:at + step]
-        parts.append(hip.mot_assign(hip.kitti_overlaps(r, g, c), g, c, r, i, prm))
+        overlaps = hip.kitti_overlaps(r, g, c)
+        parts.append(hip.mot_assign(overlaps, g, c, r, i, prm))
+        if hota_run is not None:
+            hota_run.potential(at, overlaps, parts[-1][1], parts[-1][2], keep=N <= step)
+        del overlaps
     if parts:
         match, lout, rout, frame_counts = [parts[0][k] if len(parts) == 1 else torch.cat([p[k] for p in parts]) for k in range(4)]
     else:
@@ -397,25 +411,30 @@ def evaluate_packed_device(packed, params, names=None):
     seq_counts, table = hip.mot_clear(match, lout, traj, ids, frame_counts, packed.seq_start, n_traj)
     table = table.cpu().numpy()
     tables = [table[s, :t.size].copy() for s, t in enumerate(packed.traj_ids)]
-    return _result(packed, params, match.cpu().numpy(), lout.cpu().numpy(), rout.cpu().numpy(), frame_counts.cpu().numpy(),
-                   seq_counts.cpu().numpy(), tables, names)
+    result = _result(packed, params, match.cpu().numpy(), lout.cpu().numpy(), rout.cpu().numpy(), frame_counts.cpu().numpy(),
+                     seq_counts.cpu().numpy(), tables, names)
+    if hota_run is not None:
+        hota_run.add_to(result, lambda at, n: hip.kitti_overlaps(rows[at:at + n], labels[at:at + n], counts[at:at + n]))
+    return result
 
 
 def evaluate_sequences(labels, tracks, metric='image', min_overlap=0.5, device=False, max_occlusion=2.0, max_truncation=0.0,
-                       min_height=25.0, names=None):
+                       min_height=25.0, names=None, hota=False):
     """ CLEAR-MOT of S sequences.  labels: per sequence (labels_per_frame, track_ids_per_frame); tracks: per sequence (rows, ids) -- see
     the module's text.  Returns {'sequences': [per sequence], 'all': over all sequences, each a dict of the integers tp fp fn n_gt sum_k
     cost ids frag mt pt ml trajectories frames and the ratios mota motp recall precision f1 (None without a denominator);
     'trajectories': per sequence {'track_ids', 'table' (n, 4): counting frames, matched frames, switches, fragmentations};
     'frames': {'match' (N, A), 'label_outcome' (N, A), 'row_outcome' (N, D), 'counts' (N, 8)}; 'names', 'params', 'seq_start'}.
-    device=False: NumPy.  device=True: csrc/mot_eval.hip (up to 1024 trajectories per sequence). """
+    device=False: NumPy.  device=True: csrc/mot_eval.hip (up to 1024 trajectories per sequence).
+    hota=True adds HOTA (utils/hota_eval.py): the key 'hota' in every per-sequence dict and in 'all', and
+    'hota_frames' and 'hota_pairs' in the result; without it the result is as described above. """
     params = check_params(metric, min_overlap, max_occlusion, max_truncation, min_height)
     packed = pack_sequences(labels, tracks)
     if device:
-        return evaluate_packed_device(packed, params, names)
+        return evaluate_packed_device(packed, params, names, hota=hota)
     if _is_tensor(packed.rows):
         raise ValueError('device tensors are scored by the device form: device=True')
-    return evaluate_packed_np(packed, params, names)
+    return evaluate_packed_np(packed, params, names, hota=hota)
 
 
 def evaluate_tracking(label_path, track_path, **options):
@@ -436,18 +455,24 @@ def evaluate_tracking(label_path, track_path, **options):
 
 
 def summary_table(result):
-    """ one line per sequence and one for all of them """
+    """ one line per sequence and one for all of them; a result with HOTA (hota=True) has eight more columns """
     def fmt(v, scale=100.0):
         return '   n/a' if v is None else '{:6.2f}'.format(scale * v)
 
     head = '{:>10s}  MOTA   MOTP   recall prec   F1     TP     FP     FN     IDS   FRAG  MT   PT   ML   GT     frames'.format('sequence')
+    with_hota = 'hota' in result['all']
+    if with_hota:
+        from . import hota_eval
+        head += hota_eval.TABLE_HEAD
     lines = [head]
     for name, e in list(zip(result['names'], result['sequences'])) + [('all', result['all'])]:
         lines.append('{:>10s} {} {} {} {} {} {:6d} {:6d} {:6d} {:6d} {:6d} {:4d} {:4d} {:4d} {:6d} {:6d}'.format(
             str(name)[-10:], fmt(e['mota']), fmt(e['motp']), fmt(e['recall']), fmt(e['precision']), fmt(e['f1']), e['tp'], e['fp'], e['fn'],
             e['ids'], e['frag'], e['mt'], e['pt'], e['ml'], e['n_gt'], e['frames']))
+        if with_hota:
+            lines[-1] += ' ' + hota_eval.table_columns(e)
     p = result['params']
-    return 'CLEAR-MOT, Car, {} overlap >= {}\n'.format(p['metric'], p['min_overlap']) + '\n'.join(lines)
+    return 'CLEAR-MOT{}, Car, {} overlap >= {}\n'.format(' and HOTA' if with_hota else '', p['metric'], p['min_overlap']) + '\n'.join(lines)
 
 
 def result_as_json(result):

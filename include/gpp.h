@@ -923,6 +923,72 @@ int gpp_mot_clear(const int32_t* match, const int32_t* label_outcome, const int3
                   int64_t* seq_counts, int32_t* traj_table, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * HOTA scoring of tracks on the device (csrc/hota_eval.hip; DESIGN.md section 4.30 is the specification -- parity with TrackEval's hota.py
+ * and its KITTI preprocessing is UNPINNED; utils/hota_eval.py is the host form): the alignment score of every (label trajectory, tracker
+ * id) pair of a sequence, per frame the OPTIMAL assignment on costs that this score weighs (section 4.29's routine, csrc/mot_assign.h),
+ * per sequence the detection, association and localisation integers at the GPP_HOTA_LEVELS thresholds j / 20.  Three launches, plain
+ * launches in stream order.  Exact integers: every sum is an integer sum and does not depend on the order.
+ *
+ *   overlaps (N, 4, D, A) float64: gpp_kitti_overlaps_f64's.  label_outcome (N, A) and row_outcome (N, D) int32: gpp_mot_assign's, run
+ *   with the call's metric and limits -- HOTA's preprocessing.  A label COUNTS iff its label_outcome is 1 or 2; a row is KEPT iff its
+ *   row_outcome is 1 or 3; both in ascending index order.
+ *   traj (N, A) int32: as gpp_mot_clear takes it -- a counting label's trajectory g in [0, n_gt) of its sequence.
+ *   trk (N, D) int32: a kept row's tracker t in [0, n_trk) -- the index of its id among the ids of its sequence, ascending -- else -1.
+ *   (A counting label or kept row whose index lies outside its range is treated as not counting / not kept.)
+ *   frame_tab (N, GPP_HOTA_TAB_COLS) int32 on the HOST, one line per frame of the call: cell_base, n_gt, n_trk, vec_base of the frame's
+ *   sequence.  Cell (g, t) of the sequence's pair table is cell_base + g n_trk + t; gc[g] is counter vec_base + g, tc[t] is counter
+ *   vec_base + n_gt + t.  A chunk of frames is a slice of every per-frame array and of frame_tab: no offsets to add.
+ *   metric: the overlaps' plane, 0 image, 1 BEV, 2 3-D.  q = floor(min(o 2^20, 2^20)), 0 for NaN and o <= 0: every (counting label, kept
+ *   row) pair has one; there is no admissibility test.
+ *
+ * workspace: gpp_hota_workspace_bytes(cells, vecs, max_frames, S) bytes on the device, 16-byte aligned, ZEROED by the caller before the
+ *   first gpp_hota_potential; cells and vecs are the totals over all sequences, max_frames the most frames of one call.  Its layout, which
+ *   a test may read: P int64[cells] at byte 0; the alignment A int32[cells] at 8 cells; hist int32[cells][GPP_HOTA_HIST] at 12 cells
+ *   rounded up to 16; the counters gc / tc int32[vecs] behind hist; behind them, rounded up to 16, room for the call's copy of frame_tab
+ *   or seq_tab.
+ *
+ * gpp_hota_potential (pass 1): one frame per workgroup; q, the sums rs[a] = sum_d q and cs[d] = sum_a q in LDS.
+ *   p = floor(q 2^20 / (rs[a] + cs[d] - q)) for q > 0; P[g, t] += p (64-bit integer atomics); gc[g] += 1 per counting label, tc[t] += 1
+ *   per kept row (32-bit).  Call it for EVERY frame of a sequence before gpp_hota_match for any.
+ * gpp_hota_match (pass 2): one frame per workgroup of one wavefront; the matrix in LDS.
+ *   A[g, t] = floor(P 2^20 / ((gc[g] + tc[t]) 2^20 - P)) for P > 0, else 0 (written to the workspace for every pair a frame holds).
+ *   matrix      square, of side n = max(G', T'): the counting labels are its rows, the kept rows its columns; a cell is
+ *               2^20 - ((A[g, t] q) >> 20), every padding cell 2^20.  The assignment is gpp_mot_assign's, operation for operation.
+ *   a real pair (a, d) of the assignment has jm = min(19, (20 q + 19) >> 20), the largest j with floor(j 2^20 / 20) <= q.  If jm >= 1:
+ *               hota_match[a] = d, hist[g, t][jm] += 1 (32-bit atomics), and for j = 1 .. jm: TP_j += 1, SQ_j += q.
+ *   hota_match  (N, A) int32: the row index, -1 for none.
+ *   frame_hota  (N, GPP_HOTA_FRAME_COLS) int64: TP_1 .. TP_19, SQ_1 .. SQ_19, G', T'.
+ * gpp_hota_reduce: one thread per table cell, grid (blocks, S); per wavefront one 64-bit integer atomic per quantity and threshold.
+ *   seq_tab     (S, GPP_HOTA_SEQ_TAB_COLS) int32 on the HOST: cell_base, n_gt, n_trk, vec_base, first frame, one past the last frame.
+ *   mc_j[g, t] = sum over m >= j of hist[g, t][m]; over the cells with mc > 0: ASS_j += floor(mc^2 2^20 / (gc + tc - mc)),
+ *               ASSRE_j += floor(mc^2 2^20 / gc), ASSPR_j += floor(mc^2 2^20 / tc).  TP_j, SQ_j: the sums of frame_hota over the
+ *               sequence's frames; FN_j = sum G' - TP_j, FP_j = sum T' - TP_j.
+ *   seq_hota    (S, GPP_HOTA_LEVELS, GPP_HOTA_SEQ_COLS) int64, ZEROED by the caller: TP, FN, FP, SQ, ASS, ASSRE, ASSPR, 0.
+ *   At most 2^20 frames per sequence keep everything below 2^63 (the caller's to ensure: utils/hota_eval.py raises).
+ *
+ *   GPP_ERR_BAD_ARG, nothing launched: a null pointer that the sizes make necessary (A == 0: label_outcome, traj, hota_match and overlaps
+ *   may be null; D == 0: row_outcome, trk and overlaps), a negative size, a metric other than 0 1 2, a table line with a negative entry,
+ *   with a base below the line before it, or whose cells or counters leave [0, cells) / [0, vecs); a seq_tab whose frame ranges are not
+ *   monotone inside [0, N].  D or A > 128, cells or vecs >= 2^31, S > 65535: GPP_ERR_UNSUPPORTED.  A workspace that is not 16-byte
+ *   aligned: GPP_ERR_ALIGN; too short: GPP_ERR_WORKSPACE.  N == 0 (potential, match) or S == 0 (reduce): GPP_OK, nothing launched.
+ * ---------------------------------------------------------------------------------------- */
+#define GPP_HOTA_LEVELS 19
+#define GPP_HOTA_HIST 20
+#define GPP_HOTA_FRAME_COLS 40
+#define GPP_HOTA_SEQ_COLS 8
+#define GPP_HOTA_TAB_COLS 4
+#define GPP_HOTA_SEQ_TAB_COLS 6
+int gpp_hota_workspace_bytes(long long cells, long long vecs, int max_frames, int S, size_t* bytes);
+int gpp_hota_potential(const double* overlaps, const int32_t* label_outcome, const int32_t* row_outcome, const int32_t* traj,
+                       const int32_t* trk, int N, int D, int A, int metric, const int32_t* frame_tab, long long cells, long long vecs,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int gpp_hota_match(const double* overlaps, const int32_t* label_outcome, const int32_t* row_outcome, const int32_t* traj,
+                   const int32_t* trk, int N, int D, int A, int metric, const int32_t* frame_tab, long long cells, long long vecs,
+                   int32_t* hota_match, int64_t* frame_hota, void* workspace, size_t workspace_bytes, void* stream);
+int gpp_hota_reduce(const int64_t* frame_hota, int N, const int32_t* seq_tab, int S, long long cells, long long vecs,
+                    int64_t* seq_hota, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * KITTI keypoint ("mod") labels on the device (csrc/label_prep.hip; DESIGN.md section 4.18 is the specification, utils/label_prep.py the
  * host form): what the reference's label_prep/create_mod_labels.m, computeBox3D.m and projectToImage.m make of a label_2 row and the
  * camera-2 matrix -- the 20 fields that bin/evaluate.py and KittiGenerator read.  Parity with MATLAB itself is UNPINNED.  One launch,
