@@ -158,6 +158,7 @@ class MotParams(ctypes.Structure):
 
 # include/gpp.h, gpp_hota_potential / gpp_hota_match / gpp_hota_reduce
 GPP_HOTA_LEVELS, GPP_HOTA_HIST, GPP_HOTA_FRAME_COLS, GPP_HOTA_SEQ_COLS, GPP_HOTA_TAB_COLS, GPP_HOTA_SEQ_TAB_COLS = 19, 20, 40, 8, 4, 6
+GPP_IDF1_MAX_IDS, GPP_IDF1_SEQ_COLS = 4096, 8                                         # include/gpp.h, gpp_idf1_count / gpp_idf1_assign
 
 
 class AbsmaxClearDesc(ctypes.Structure):
@@ -222,6 +223,15 @@ def _declare(lib):
                                        c_size_t, c_void_p]
         lib.gpp_hota_reduce.restype = c_int
         lib.gpp_hota_reduce.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_ll, c_ll, c_void_p, c_void_p, c_size_t, c_void_p]
+    # IDF1 (include/gpp.h, csrc/idf1_eval.hip; absent from an older build named by GPP_LIB: it runs everything but the idf1=True scores)
+    if hasattr(lib, 'gpp_idf1_count'):
+        c_ll = ctypes.c_longlong
+        lib.gpp_idf1_workspace_bytes.restype = c_int
+        lib.gpp_idf1_workspace_bytes.argtypes = [c_ll, c_ll, c_int, c_int, ctypes.POINTER(c_size_t)]
+        lib.gpp_idf1_count.restype = c_int
+        lib.gpp_idf1_count.argtypes = [c_void_p] * 5 + [c_int] * 4 + [ctypes.POINTER(ctypes.c_int32), c_ll, c_ll, c_void_p, c_size_t, c_void_p]
+        lib.gpp_idf1_assign.restype = c_int
+        lib.gpp_idf1_assign.argtypes = [ctypes.POINTER(ctypes.c_int32), c_int, c_ll, c_ll, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     # KITTI's object benchmark (include/gpp.h, csrc/kitti_eval.hip; absent from an older build named by GPP_LIB: it runs everything but
     # evaluate_kitti(device=True) and score_poses_on_frames)
     if hasattr(lib, 'gpp_kitti_overlaps_f64'):
@@ -768,6 +778,50 @@ def hota_reduce(frame_hota, seq_tab, cells, vecs, workspace):
     check(lib().gpp_hota_reduce(ptr(frame_hota), int(frame_hota.shape[0]), _table_ptr(tab), S, int(cells), int(vecs), ptr(seq_hota), ptr(workspace),
                                 int(workspace.numel()), stream_ptr()), 'gpp_hota_reduce')
     return seq_hota
+
+
+def idf1_workspace_bytes(cells, vecs, max_frames, S):
+    n = c_size_t(0)
+    check(lib().gpp_idf1_workspace_bytes(int(cells), int(vecs), int(max_frames), int(S), ctypes.byref(n)), 'gpp_idf1_workspace_bytes')
+    return n.value
+
+
+def idf1_workspace(cells, vecs, max_frames, S, device):
+    """ the zeroed workspace of gpp_idf1_* for tables of `cells` cells and `vecs` counters in all """
+    import torch
+    return torch.zeros((idf1_workspace_bytes(cells, vecs, max_frames, S),), dtype=torch.uint8, device=device)
+
+
+def idf1_tables(workspace, cells, vecs):
+    """ the views include/gpp.h documents, to read and to write: (C int32 (cells,), counters int32 (vecs,)) """
+    import torch
+    cells, vecs = int(cells), int(vecs)
+    at_cnt = (4 * cells + 15) // 16 * 16
+    return workspace[:4 * cells].view(torch.int32), workspace[at_cnt:at_cnt + 4 * vecs].view(torch.int32)
+
+
+def idf1_count(overlaps, label_outcome, row_outcome, traj, trk, metric, frame_tab, cells, vecs, workspace):
+    """ gpp_idf1_count on the current stream (pass 1): the arguments of hota_potential, the workspace of idf1_workspace -- adds the frames
+    to the table C and to the counters in the workspace; no synchronisation """
+    N, D, A, tab = _hota_frames('gpp_idf1_count', overlaps, label_outcome, row_outcome, traj, trk, frame_tab, workspace)
+    check(lib().gpp_idf1_count(ptr(overlaps), ptr(label_outcome), ptr(row_outcome), ptr(traj), ptr(trk), N, D, A, int(metric), _table_ptr(tab),
+                               int(cells), int(vecs), ptr(workspace), int(workspace.numel()), stream_ptr()), 'gpp_idf1_count')
+
+
+def idf1_assign(seq_tab, cells, vecs, workspace):
+    """ gpp_idf1_assign on the current stream (pass 2, after pass 1 has seen every frame): seq_tab S * 6 host integers (cell_base, n_gt,
+    n_trk, vec_base, and two that are not read) -> (id_match (vecs,) int32: trajectory g of a sequence at vec_base + g, -1 elsewhere,
+    seq_idf1 (S, 8) int64: IDTP IDFN IDFP sum-gc sum-tc cost G T) on the device; no synchronisation """
+    import torch
+    if workspace.dtype != torch.uint8 or not workspace.is_cuda:
+        raise ValueError('gpp_idf1_assign: the workspace must be uint8 on the device')
+    S = len(seq_tab) // GPP_HOTA_SEQ_TAB_COLS
+    tab = _host_table('gpp_idf1_assign', seq_tab, S, GPP_HOTA_SEQ_TAB_COLS)
+    id_match = torch.full((max(int(vecs), 1),), -1, dtype=torch.int32, device=workspace.device)[:int(vecs)]
+    seq_idf1 = torch.zeros((S, GPP_IDF1_SEQ_COLS), dtype=torch.int64, device=workspace.device)
+    check(lib().gpp_idf1_assign(_table_ptr(tab), S, int(cells), int(vecs), ptr(id_match), ptr(seq_idf1), ptr(workspace), int(workspace.numel()),
+                                stream_ptr()), 'gpp_idf1_assign')
+    return id_match, seq_idf1
 
 
 def label_prep(labels, label_counts, P, trig, det_types=0, own_box=True, detections=True):

@@ -5,13 +5,14 @@ Score tracks against KITTI tracking labels (not in the reference): CLEAR-MOT for
 fragmentations, mostly tracked / mostly lost -- on the optimal assignment of every frame.  Parity with the KITTI
 tracking devkit is UNPINNED.
 
-    evaluate_tracking.py label_02/ tracks/ [--device] [--metric image|bev|3d] [--min-overlap 0.5] [--hota] [--json out.json]
+    evaluate_tracking.py label_02/ tracks/ [--device] [--metric image|bev|3d] [--min-overlap 0.5] [--hota] [--idf1] [--json out.json]
 
 The two arguments are directories -- every `.txt` file of the label directory is a sequence, scored against the file of the same name in
 the track directory -- or two single files.  Labels are label_02 lines, tracks the lines bin/track_results.py and bin/run_network.py
 --track write.  NumPy by default; --device runs csrc/mot_eval.hip.  --hota adds HOTA (parity with TrackEval is
 UNPINNED): the columns HOTA DetA AssA DetRe DetPr AssRe AssPr LocA in the table, the per-threshold integers and ratios in --json; with
---device on csrc/hota_eval.hip.
+--device on csrc/hota_eval.hip.  --idf1 adds the identity scores (parity with TrackEval is UNPINNED): the columns
+IDF1 IDR IDP in the table, after HOTA's when both are given, and IDTP IDFN IDFP in --json; with --device on csrc/idf1_eval.hip.
 """
 
 import argparse
@@ -36,6 +37,8 @@ def add_scoring_arguments(parser, prefix=''):
                         help='A row and a label can be paired when they overlap by at least this much.')
     parser.add_argument('--hota', action='store_true',
                         help='Also score HOTA: eight more columns in the table, the integers of the 19 thresholds in --json.')
+    parser.add_argument('--idf1', action='store_true',
+                        help='Also score identity: the columns IDF1 IDR IDP in the table, the integers IDTP IDFN IDFP in --json.')
 
 
 def parse_args(args):
@@ -58,7 +61,7 @@ def parse_args(args):
 def main(args=None):
     args = parse_args(sys.argv[1:] if args is None else args)
     result = mot_eval.evaluate_tracking(args.label_path, args.track_path, metric=args.mot_metric, min_overlap=args.mot_min_overlap,
-                                        device=args.device, hota=args.hota)
+                                        device=args.device, hota=args.hota, idf1=args.idf1)
     print(mot_eval.summary_table(result))
     if args.json_path:
         with open(args.json_path, 'w') as f:

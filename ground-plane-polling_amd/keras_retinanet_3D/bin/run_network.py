@@ -95,11 +95,15 @@ def parse_args(args):
                              'bin/evaluate_tracking.py is printed.')
     parser.add_argument('--hota', action='store_true',
                         help='With --tracking-labels: also score HOTA (csrc/hota_eval.hip) and print its eight columns in the table.')
+    parser.add_argument('--idf1', action='store_true',
+                        help='With --tracking-labels: also score identity (csrc/idf1_eval.hip) and print IDF1 IDR IDP in the table.')
     parsed = parser.parse_args(args)
     if parsed.tracking_labels is not None and parsed.track is None:
         parser.error('--tracking-labels scores the tracks of --track: it needs --track')
     if parsed.hota and parsed.tracking_labels is None:
         parser.error('--hota scores the tracks against --tracking-labels: it needs --tracking-labels')
+    if parsed.idf1 and parsed.tracking_labels is None:
+        parser.error('--idf1 scores the tracks against --tracking-labels: it needs --tracking-labels')
     if (parsed.track is None) != (parsed.track_threshold is None):
         parser.error('--track and --track-threshold go together: both or neither')
     if parsed.track is not None:
@@ -280,7 +284,7 @@ def main(args=None):
     if args.tracking_labels is not None:
         from ..utils import mot_eval
         print(mot_eval.summary_table(mot_eval.evaluate_tracking(args.tracking_labels, os.path.join(output_dir, 'outputs', 'tracking', 'tracks.txt'),
-                                                                device=True, hota=args.hota)))
+                                                                device=True, hota=args.hota, idf1=args.idf1)))
     if args.range_audit:
         write_range_audit(output_dir, model, audit)
 

@@ -11,11 +11,11 @@ threshold can be swept.  On the GPU by default (csrc/track.hip: one launch for t
 (utils/track.track_rows_np) and, without --smooth, writes the same bytes.
 
     track_results.py result_dir/ tracks.txt --metric dist --threshold 2.0 [--max-age 2] [--min-hits 1] [--smooth] [--host]
-                     [--labels label_02/0000.txt [--score-metric image] [--score-min-overlap 0.5] [--hota]]
+                     [--labels label_02/0000.txt [--score-metric image] [--score-min-overlap 0.5] [--hota] [--idf1]]
 
 --labels scores the tracks just written against the sequence's label_02 file (CLEAR-MOT; on the GPU unless
 --host) and prints the table of bin/evaluate_tracking.py: a threshold sweep is one loop of this one command.  --hota adds the HOTA columns
-(section 4.30).
+(section 4.30), --idf1 the columns IDF1 IDR IDP (section 4.31).
 """
 
 import argparse
@@ -85,7 +85,7 @@ def main(args=None):
     print('{} frames, {} tracks, {} births dropped -> {}'.format(len(names), int(state['next_id']), int(state['dropped']), args.tracks_path))
     if args.labels:
         result = mot_eval.evaluate_tracking(args.labels, args.tracks_path, metric=args.mot_metric, min_overlap=args.mot_min_overlap,
-                                            device=not args.host, hota=args.hota)
+                                            device=not args.host, hota=args.hota, idf1=args.idf1)
         print(mot_eval.summary_table(result))
         return result
 

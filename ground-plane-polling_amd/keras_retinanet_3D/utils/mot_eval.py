@@ -355,7 +355,7 @@ def _result(packed, params, match, lout, rout, frame_counts, seq_counts, tables,
             'seq_start': np.asarray(packed.seq_start)}
 
 
-def evaluate_packed_np(packed, params, names=None, hota=False):
+def evaluate_packed_np(packed, params, names=None, hota=False, idf1=False):
     N, A, D = packed.labels.shape[0], packed.labels.shape[1], packed.rows.shape[1]
     match, lout = np.full((N, A), -1, np.int32), np.zeros((N, A), np.int32)
     rout, frame_counts = np.zeros((N, D), np.int32), np.zeros((N, 8), np.int64)
@@ -368,14 +368,18 @@ def evaluate_packed_np(packed, params, names=None, hota=False):
     if hota:
         from . import hota_eval
         hota_eval.add_hota_np(result, packed, params)
+    if idf1:
+        from . import idf1_eval
+        idf1_eval.add_idf1_np(result, packed, params)
     return result
 
 
-def evaluate_packed_device(packed, params, names=None, hota=False):
+def evaluate_packed_device(packed, params, names=None, hota=False, idf1=False):
     """ csrc/mot_eval.hip: the frames in chunks whose overlaps stay below utils/kitti_eval.OVERLAP_WORKSPACE_BYTES, one assignment launch
     per chunk, then one launch for all trajectories; rows and ids that are device tensors already are used where they lie.
     hota: csrc/hota_eval.hip beside it (utils/hota_eval.DeviceRun) -- its pass 1 in this sweep over the chunks, its pass 2 in a second
-    sweep, which recomputes the overlaps unless the call has a single chunk """
+    sweep, which recomputes the overlaps unless the call has a single chunk.
+    idf1: csrc/idf1_eval.hip (utils/idf1_eval.DeviceRun) -- its count in this sweep over the chunks, its one assignment after it """
     import torch
     from ..backend import hip
     dev = packed.rows.device if _is_tensor(packed.rows) else hip.require_device()
@@ -395,6 +399,10 @@ def evaluate_packed_device(packed, params, names=None, hota=False):
     if hota:
         from . import hota_eval
         hota_run = hota_eval.DeviceRun(packed, params, rows, ids, traj, step)
+    idf1_run = None
+    if idf1:
+        from . import idf1_eval
+        idf1_run = idf1_eval.DeviceRun(packed, params, rows, ids, traj, step, hota_run)
     parts = []
     for at in range(0, N, step):
         r, g, c, i = rows[at:at + step], labels[at:at + step], counts[at:at + step], ids[at:at + step]
@@ -402,6 +410,8 @@ def evaluate_packed_device(packed, params, names=None, hota=False):
         parts.append(hip.mot_assign(overlaps, g, c, r, i, prm))
         if hota_run is not None:
             hota_run.potential(at, overlaps, parts[-1][1], parts[-1][2], keep=N <= step)
+        if idf1_run is not None:
+            idf1_run.count(at, overlaps, parts[-1][1], parts[-1][2])
         del overlaps
     if parts:
         match, lout, rout, frame_counts = [parts[0][k] if len(parts) == 1 else torch.cat([p[k] for p in parts]) for k in range(4)]
@@ -415,11 +425,13 @@ def evaluate_packed_device(packed, params, names=None, hota=False):
                      seq_counts.cpu().numpy(), tables, names)
     if hota_run is not None:
         hota_run.add_to(result, lambda at, n: hip.kitti_overlaps(rows[at:at + n], labels[at:at + n], counts[at:at + n]))
+    if idf1_run is not None:
+        idf1_run.add_to(result)
     return result
 
 
 def evaluate_sequences(labels, tracks, metric='image', min_overlap=0.5, device=False, max_occlusion=2.0, max_truncation=0.0,
-                       min_height=25.0, names=None, hota=False):
+                       min_height=25.0, names=None, hota=False, idf1=False):
     """ CLEAR-MOT of S sequences.  labels: per sequence (labels_per_frame, track_ids_per_frame); tracks: per sequence (rows, ids) -- see
     the module's text.  Returns {'sequences': [per sequence], 'all': over all sequences, each a dict of the integers tp fp fn n_gt sum_k
     cost ids frag mt pt ml trajectories frames and the ratios mota motp recall precision f1 (None without a denominator);
@@ -427,14 +439,17 @@ def evaluate_sequences(labels, tracks, metric='image', min_overlap=0.5, device=F
     'frames': {'match' (N, A), 'label_outcome' (N, A), 'row_outcome' (N, D), 'counts' (N, 8)}; 'names', 'params', 'seq_start'}.
     device=False: NumPy.  device=True: csrc/mot_eval.hip (up to 1024 trajectories per sequence).
     hota=True adds HOTA (utils/hota_eval.py): the key 'hota' in every per-sequence dict and in 'all', and
-    'hota_frames' and 'hota_pairs' in the result; without it the result is as described above. """
+    'hota_frames' and 'hota_pairs' in the result; without it the result is as described above.
+    idf1=True adds the identity scores (utils/idf1_eval.py): the key 'idf1' in every per-sequence dict and in 'all'
+    -- {'idf1', 'idr', 'idp', 'integers': {'idtp', 'idfn', 'idfp'}} -- and 'idf1_pairs' in the result, per sequence {'C', 'gc', 'tc',
+    'match'}; without it the result is as described above. """
     params = check_params(metric, min_overlap, max_occlusion, max_truncation, min_height)
     packed = pack_sequences(labels, tracks)
     if device:
-        return evaluate_packed_device(packed, params, names, hota=hota)
+        return evaluate_packed_device(packed, params, names, hota=hota, idf1=idf1)
     if _is_tensor(packed.rows):
         raise ValueError('device tensors are scored by the device form: device=True')
-    return evaluate_packed_np(packed, params, names, hota=hota)
+    return evaluate_packed_np(packed, params, names, hota=hota, idf1=idf1)
 
 
 def evaluate_tracking(label_path, track_path, **options):
@@ -455,7 +470,8 @@ def evaluate_tracking(label_path, track_path, **options):
 
 
 def summary_table(result):
-    """ one line per sequence and one for all of them; a result with HOTA (hota=True) has eight more columns """
+    """ one line per sequence and one for all of them; a result with HOTA (hota=True) has eight more columns, one with the identity
+    scores (idf1=True) three more after them """
     def fmt(v, scale=100.0):
         return '   n/a' if v is None else '{:6.2f}'.format(scale * v)
 
@@ -464,6 +480,10 @@ def summary_table(result):
     if with_hota:
         from . import hota_eval
         head += hota_eval.TABLE_HEAD
+    with_idf1 = 'idf1' in result['all']
+    if with_idf1:
+        from . import idf1_eval
+        head += idf1_eval.TABLE_HEAD
     lines = [head]
     for name, e in list(zip(result['names'], result['sequences'])) + [('all', result['all'])]:
         lines.append('{:>10s} {} {} {} {} {} {:6d} {:6d} {:6d} {:6d} {:6d} {:4d} {:4d} {:4d} {:6d} {:6d}'.format(
@@ -471,8 +491,11 @@ def summary_table(result):
             e['ids'], e['frag'], e['mt'], e['pt'], e['ml'], e['n_gt'], e['frames']))
         if with_hota:
             lines[-1] += ' ' + hota_eval.table_columns(e)
+        if with_idf1:
+            lines[-1] += ' ' + idf1_eval.table_columns(e)
     p = result['params']
-    return 'CLEAR-MOT{}, Car, {} overlap >= {}\n'.format(' and HOTA' if with_hota else '', p['metric'], p['min_overlap']) + '\n'.join(lines)
+    also = {(True, False): ' and HOTA', (False, True): ' and Identity', (True, True): ', HOTA and Identity'}.get((with_hota, with_idf1), '')
+    return 'CLEAR-MOT{}, Car, {} overlap >= {}\n'.format(also, p['metric'], p['min_overlap']) + '\n'.join(lines)
 
 
 def result_as_json(result):

@@ -989,6 +989,55 @@ int gpp_hota_reduce(const int64_t* frame_hota, int N, const int32_t* seq_tab, in
                     int64_t* seq_hota, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Identity scoring of tracks on the device -- IDF1, IDR, IDP (csrc/idf1_eval.hip; DESIGN.md section 4.31 is the specification -- parity
+ * with TrackEval's identity.py is UNPINNED; utils/idf1_eval.py is the host form): per sequence the table C of how often every (label
+ * trajectory, tracker id) pair overlaps by at least one half, then ONE optimal assignment per sequence of the trajectories to the tracker
+ * ids on that table (section 4.29's rule in its rectangular form).  Two launches, plain launches in stream order.  Exact integers.
+ *
+ *   overlaps, label_outcome, row_outcome, traj, trk, frame_tab, seq_tab, metric, cells, vecs: exactly gpp_hota_potential's and
+ *   gpp_hota_reduce's (above) -- the same arrays serve both scores.  frame_tab and seq_tab lie on the HOST.  q = floor(min(o 2^20, 2^20)),
+ *   0 for NaN and o <= 0.
+ *
+ * workspace: gpp_idf1_workspace_bytes(cells, vecs, max_frames, S) bytes on the device, 16-byte aligned, ZEROED by the caller before the
+ *   first gpp_idf1_count; max_frames is the most frames of one gpp_idf1_count call.  Its layout, which a test may read AND WRITE -- the
+ *   assignment takes whatever table lies there, frames or no frames --: C int32[cells] at byte 0, cell (g, t) of a sequence at
+ *   cell_base + g n_trk + t; the counters gc / tc int32[vecs] at 4 cells rounded up to 16, gc[g] at vec_base + g and tc[t] at
+ *   vec_base + n_gt + t; behind them, rounded up to 16, room for the call's copy of frame_tab or seq_tab.
+ *
+ * gpp_idf1_count (pass 1): one frame per workgroup.  For every (counting label a, kept row d) of the frame with q(a, d) >= 2^19 -- the
+ *   same as o >= 0.5: an overlap of exactly one half counts --, C[traj[a], trk[d]] += 1; there is no one-to-one rule inside a frame.
+ *   gc[g] += 1 per counting label, tc[t] += 1 per kept row: section 4.30's counters.  32-bit integer atomics.  Call it for EVERY frame of
+ *   a sequence before gpp_idf1_assign.
+ * gpp_idf1_assign (pass 2): one sequence per workgroup of ONE wavefront; the table stays in device memory, the column state lies in LDS
+ *   (24 bytes a column and 8 a row of the launch's largest sequence: 104 KiB at the limits).  Columns 4 and 5 of a seq_tab line are not read.
+ *   matrix      G = n_gt rows by n = max(n_gt, n_trk) columns: the cell is 2^20 - C[g, t] for t < n_trk and 2^20 in every padding column.
+ *   assignment  gpp_mot_assign's, operation for operation, for the rows i = 0 .. G - 1 in order: u = v = 0 at the start, int64
+ *               potentials, strict < in the relaxation, the FIRST column on ties, the rows handed back along way.
+ *   id_match    int32, vecs entries: id_match[vec_base + g] = the column of trajectory g if it is < n_trk and C[g, column] > 0, else -1
+ *               (pairing a trajectory with an id it never met costs what leaving both alone costs).  The entries from vec_base + n_gt on
+ *               are not written.
+ *   seq_idf1    (S, GPP_IDF1_SEQ_COLS) int64: IDTP = the sum of C[g, id_match[g]], IDFN = sum gc - IDTP, IDFP = sum tc - IDTP, sum gc,
+ *               sum tc, the assignment's total cost G 2^20 - IDTP, G, T.  Every entry is written.
+ *   C <= 2^20 (at most 2^20 frames per sequence, the caller's to ensure: utils/hota_eval.tables raises) keeps every cell >= 0 and every
+ *   potential below 2^33; the arg-min's packed key is minv << 13 | column.
+ *
+ *   GPP_ERR_BAD_ARG, nothing launched: a null pointer that the sizes make necessary (A == 0: label_outcome, traj and overlaps may be null;
+ *   D == 0: row_outcome, trk and overlaps; no trajectory in any sequence: id_match), a negative size, a metric other than 0 1 2, a table
+ *   line with a negative entry, with a base below the line before it, or whose cells or counters leave [0, cells) / [0, vecs).
+ *   D or A > 128, cells or vecs >= 2^31, a sequence with n_gt > GPP_MOT_MAX_TRAJECTORIES or max(n_gt, n_trk) > GPP_IDF1_MAX_IDS:
+ *   GPP_ERR_UNSUPPORTED.  A workspace that is not 16-byte aligned: GPP_ERR_ALIGN; too short: GPP_ERR_WORKSPACE.  N == 0 (count) or S == 0
+ *   (assign): GPP_OK, nothing launched.  A sequence with n_gt == 0 or n_trk == 0: GPP_OK, IDTP 0, every id_match -1.
+ * ---------------------------------------------------------------------------------------- */
+#define GPP_IDF1_MAX_IDS 4096
+#define GPP_IDF1_SEQ_COLS 8
+int gpp_idf1_workspace_bytes(long long cells, long long vecs, int max_frames, int S, size_t* bytes);
+int gpp_idf1_count(const double* overlaps, const int32_t* label_outcome, const int32_t* row_outcome, const int32_t* traj,
+                   const int32_t* trk, int N, int D, int A, int metric, const int32_t* frame_tab, long long cells, long long vecs,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int gpp_idf1_assign(const int32_t* seq_tab, int S, long long cells, long long vecs, int32_t* id_match, int64_t* seq_idf1,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * KITTI keypoint ("mod") labels on the device (csrc/label_prep.hip; DESIGN.md section 4.18 is the specification, utils/label_prep.py the
  * host form): what the reference's label_prep/create_mod_labels.m, computeBox3D.m and projectToImage.m make of a label_2 row and the
  * camera-2 matrix -- the 20 fields that bin/evaluate.py and KittiGenerator read.  Parity with MATLAB itself is UNPINNED.  One launch,
