@@ -235,6 +235,14 @@ int main(int argc, char** argv)
                                    (int32_t*)(uintptr_t)r.d[0].bias, (int32_t*)(uintptr_t)r.d[0].bias, r.d[0].out, (size_t)r.d[0].partial_bytes, nullptr));
                 note(gpp_track_f64((const float*)r.d[0].in, 8, (int)(r.b % 128) + 1, seq, 2, r.d[0].in, r.d[0].out, &tp, (float*)r.d[0].out,
                                    (int32_t*)(uintptr_t)r.d[0].bias, (int32_t*)(uintptr_t)r.d[0].bias, (void*)((uintptr_t)r.d[0].out | 8), 0, nullptr));
+                // (the optimal assignment's entry point shares every check: the same three calls)
+                note(gpp_track_optimal_f64(nullptr, (int)r.a, (int)r.b, seq, 2, nullptr, nullptr, &tp, nullptr, nullptr, nullptr, nullptr, 0, nullptr));
+                note(gpp_track_optimal_f64((const float*)r.d[0].in, 8, 129 + (int)(r.b % 2000), seq, 2, r.d[0].in, r.d[0].out, &tp, (float*)r.d[0].out,
+                                           (int32_t*)(uintptr_t)r.d[0].bias, (int32_t*)(uintptr_t)r.d[0].bias, r.d[0].out, (size_t)r.d[0].partial_bytes,
+                                           nullptr));
+                note(gpp_track_optimal_f64((const float*)r.d[0].in, 8, (int)(r.b % 128) + 1, seq, 2, r.d[0].in, r.d[0].out, &tp, (float*)r.d[0].out,
+                                           (int32_t*)(uintptr_t)r.d[0].bias, (int32_t*)(uintptr_t)r.d[0].bias, (void*)((uintptr_t)r.d[0].out | 8), 0,
+                                           nullptr));
             }
             // the tracking score: fuzzed parameters, sizes and sequence starts against null pointers, more rows or trajectories than the kernels
             // take, and a workspace of no bytes -- all end before any launch or copy (seq_start is the one host array gpp_mot_clear reads)

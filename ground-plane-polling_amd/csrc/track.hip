@@ -30,12 +30,23 @@
 // barrier, or from kernel arguments).
 //
 // Arithmetic: float64, every operation separate (this file is compiled with -ffp-contract=off), as cuboid_nms.hip.
+//
+//   track_kernel<true>   gpp_track_optimal_f64: the same kernel with another phase 4 -- the optimal one-to-one
+//                  assignment of the frame.  Phases 1, 2, 5 and 6 are the statements above.  Behind phase 2 all 128 threads fill an n x n
+//                  int32 matrix in LDS (n = max(slots, rows) listed, stride n) with 2^20; phase 3 writes a candidate's integer cell at
+//                  (a, c), its place in the two lists, instead of its key into the table; in phase 4 wavefront 0 runs
+//                  gpp_mot::assign_rows (csrc/mot_assign.h, section 4.29's routine) on it while wavefront 1 waits at the barrier, and lane
+//                  l then writes the matches of its columns l and l + 64: a column's row is a match iff their cell is below 2^20.
+//                  The matrix is 64 KiB beside the 81 KiB of the greedy form: 145 KiB of the 160 KiB a workgroup may have, so it is
+//                  declared on its own and overlays nothing.  There is no table in HBM in this form: the workspace holds seq_start only.
+//                  The greedy instantiation has none of these statements (if constexpr) and no matrix.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
 
 #include "gpp.h"
+#include "mot_assign.h"
 #include "rot_iou.h"
 
 namespace {
@@ -49,10 +60,13 @@ constexpr int kChunk = 4096;                         // pairs gated per round
 constexpr double kPi = 3.141592653589793238462643383279502884;
 constexpr double kTwoPi = 2.0 * kPi;
 constexpr size_t kSeqBytes = 256;                    // the workspace starts with seq_start's copy, padded to a multiple of this
+constexpr int32_t kScale = 1 << GPP_MOT_SCALE_BITS;  // section 4.32: the cell of a pair that is no candidate, and of padding
+constexpr int kSide = kSlots > kMaxD ? kSlots : kMaxD;                 // the largest matrix of section 4.32
 
 static_assert(kThreads == kSlots && kThreads >= kMaxD, "one thread per slot and per row");
 static_assert(kChunk <= 65536, "a pair's offset into its chunk is 16 bits");
 static_assert(sizeof(gpp_track_state) % 8 == 0, "states are laid out back to back");
+static_assert(kSide <= 2 * gpp_mot::kWave, "assign_rows: a lane owns two columns");
 
 enum { FX = 0, FY, FZ, FRY, FH, FW, FL, FVX, FVY, FVZ };
 
@@ -81,6 +95,7 @@ __device__ __forceinline__ int block_rank(bool flag, int tid, int* s_wave, int& 
 
 size_t seq_bytes(int S) { return ((size_t)(S + 1) * sizeof(int32_t) + kSeqBytes - 1) / kSeqBytes * kSeqBytes; }
 
+template <bool kOptimal>
 __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, int N, int D, const int32_t* __restrict__ seq_start,
                                                          const gpp_track_state* states_in, gpp_track_state* states_out,
                                                          gpp_track_params prm, float* rows_out, int32_t* track_ids, int32_t* track_hits,
@@ -100,13 +115,22 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
     __shared__ uint16_t s_pairs[kChunk];
     __shared__ unsigned long long s_closed[2], s_gone[2];             // phase 4: the slots taken this round, the rows taken so far
     __shared__ int s_wave[2], s_listed;
+    int32_t* s_cost = nullptr;                           // section 4.32: the frame's n x n matrix, stride n
+    if constexpr (kOptimal) {
+        __shared__ int32_t s_matrix[kSide * kSide];
+        s_cost = s_matrix;
+    }
 
     const int seq = blockIdx.x, tid = threadIdx.x;
     int f0 = seq_start[seq], f1 = seq_start[seq + 1];
     f0 = f0 < 0 ? 0 : f0;                                // (the host has checked the ranges; no frame index leaves [0, N) whatever arrives)
     f1 = f1 > N ? N : f1;
-    double* tab = tables + (size_t)seq * 2 * kSlots * kMaxD;         // [slot][row]: a row's thread walks its column, coalesced over the rows
-    double* tab_dt = tab + kSlots * kMaxD;                           // [row][slot], the same keys: a slot's thread walks its line, coalesced
+    double* tab = nullptr;                                           // [slot][row]: a row's thread walks its column, coalesced over the rows
+    double* tab_dt = nullptr;                                        // [row][slot], the same keys: a slot's thread walks its line, coalesced
+    if constexpr (!kOptimal) {
+        tab = tables + (size_t)seq * 2 * kSlots * kMaxD;
+        tab_dt = tab + kSlots * kMaxD;
+    }
     const bool iou = prm.metric != GPP_TRACK_DIST;
     const double thr2 = prm.threshold * prm.threshold;
 
@@ -162,11 +186,13 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
                     t_area[tid] = l * w;
                 }
             }
-            if (tid < D)                                 // (id1 changes in phase 5 only: every thread sees the same slots here)
-                for (int t = 0; t < kSlots; ++t)
-                    if (st.id1[t] != 0) tab[t * kMaxD + tid] = INFINITY;
-            if (st.id1[tid] != 0)
-                for (int d = 0; d < D; ++d) tab_dt[d * kSlots + tid] = INFINITY;
+            if constexpr (!kOptimal) {
+                if (tid < D)                             // (id1 changes in phase 5 only: every thread sees the same slots here)
+                    for (int t = 0; t < kSlots; ++t)
+                        if (st.id1[t] != 0) tab[t * kMaxD + tid] = INFINITY;
+                if (st.id1[tid] != 0)
+                    for (int d = 0; d < D; ++d) tab_dt[d * kSlots + tid] = INFINITY;
+            }
         }
         __syncthreads();
 
@@ -181,6 +207,14 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
         }
         __syncthreads();
 
+        // ---- (optimal) the matrix, all of it "no candidate": n, nT and nR are the same in every thread, n = 0 takes the barrier too
+        int n = 0;
+        if constexpr (kOptimal) {
+            n = nT > nR ? nT : nR;
+            for (int k = tid; k < n * n; k += kThreads) s_cost[k] = kScale;
+            __syncthreads();
+        }
+
         // ---- 3: the candidates.  Pair p = a * nR + c: slot tlist[a], row rlist[c]
         const int pairs = nT * nR;
         if (!iou) {
@@ -188,7 +222,16 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
                 const int t = s_tlist[p / nR], d = s_rlist[p % nR];
                 const double dx = r_f[FX][d] - st.box[FX][t], dz = r_f[FZ][d] - st.box[FZ][t];
                 const double q = dx * dx + dz * dz;
-                if (q < thr2) { tab[t * kMaxD + d] = q; tab_dt[d * kSlots + t] = q; }
+                if (q < thr2) {
+                    if constexpr (kOptimal) {
+                        const double r = q / thr2;
+                        const double x = r * 1048576.0;
+                        const double cell = floor(x);
+                        s_cost[(p / nR) * n + p % nR] = cell < (double)(kScale - 1) ? (int32_t)cell : kScale - 1;
+                    } else {
+                        tab[t * kMaxD + d] = q; tab_dt[d * kSlots + t] = q;
+                    }
+                }
             }
         } else {
             for (int base = 0; base < pairs; base += kChunk) {
@@ -225,7 +268,15 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
                         const double vol_d = area_d * dh, vol_g = area_g * gh;
                         o = iv / (vol_d + vol_g - iv);
                     }
-                    if (o > prm.threshold) { tab[t * kMaxD + d] = -o; tab_dt[d * kSlots + t] = -o; }
+                    if (o > prm.threshold) {
+                        if constexpr (kOptimal) {
+                            const double scaled = o * 1048576.0;
+                            const int32_t cell = kScale - (int32_t)floor(scaled < 1048576.0 ? scaled : 1048576.0);
+                            s_cost[(p / nR) * n + p % nR] = cell < kScale - 1 ? cell : kScale - 1;
+                        } else {
+                            tab[t * kMaxD + d] = -o; tab_dt[d * kSlots + t] = -o;
+                        }
+                    }
                 }
                 __syncthreads();
             }
@@ -236,7 +287,25 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
         // the smaller row) AND the slot is the best open slot of the row (ties: the smaller slot): no candidate before it in the order
         // (key, slot, row) shares its slot or its row with it, so the serial rule takes it too; the best candidate of all that are left
         // is always such a pair, so every round takes at least one.  A thread keeps what it found until its partner has gone
-        {
+        if constexpr (kOptimal) {
+            // ---- 4 (optimal): one wavefront on the matrix, the other waits at the barrier below.  Lane l holds the matrix rows of its
+            // columns l and l + 64; a column below nR whose row's cell is below 2^20 is a match (padding and non-candidates hold 2^20).
+            // Without slots or without rows every cell is 2^20 and nothing can match: such a frame (the first of every sequence) is
+            // not walked
+            if (tid < gpp_mot::kWave && pairs > 0) {
+                int p[2];
+                gpp_mot::assign_rows(s_cost, n, tid, p);
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const int c = tid + gpp_mot::kWave * s;
+                    if (c < nR && s_cost[p[s] * n + c] < kScale) {
+                        const int t = s_tlist[p[s]], d = s_rlist[c];
+                        s_mrow[t] = (int16_t)d;
+                        s_mslot[d] = (int16_t)t;
+                    }
+                }
+            }
+        } else {
             const bool is_slot = st.id1[tid] != 0, is_row = r_flag[tid] == 1;
             bool open = is_slot, unmatched = is_row, scan_line = is_slot, scan_column = is_row;
             unsigned long long free_lo = ~0ull, free_hi = ~0ull;     // the free rows and the open slots, kept by every thread alike
@@ -404,9 +473,11 @@ extern "C" int gpp_track_workspace_bytes(int S, size_t* bytes)
     return GPP_OK;
 }
 
-extern "C" int gpp_track_f64(const float* rows_in, int N, int D, const int32_t* seq_start, int S, const void* state_in, void* state_out,
-                             const gpp_track_params* params, float* rows_out, int32_t* track_ids, int32_t* track_hits,
-                             void* workspace, size_t workspace_bytes, void* stream)
+// both entry points: the checks of the contract in their order, then the one launch.  The optimal form asks for the same workspace and
+// uses seq_start's copy only
+static int track(bool optimal, const float* rows_in, int N, int D, const int32_t* seq_start, int S, const void* state_in, void* state_out,
+                 const gpp_track_params* params, float* rows_out, int32_t* track_ids, int32_t* track_hits, void* workspace,
+                 size_t workspace_bytes, void* stream)
 {
     if (N < 0 || D < 0 || S < 0 || !params || !seq_start) return GPP_ERR_BAD_ARG;
     const gpp_track_params& p = *params;
@@ -433,9 +504,27 @@ extern "C" int gpp_track_f64(const float* rows_in, int N, int D, const int32_t* 
     if (workspace_bytes < seq_bytes(S) + (size_t)S * 2 * kSlots * kMaxD * sizeof(double)) return GPP_ERR_WORKSPACE;
     hipError_t e = hipMemcpyAsync(workspace, seq_start, (size_t)(S + 1) * sizeof(int32_t), hipMemcpyHostToDevice, q);
     if (e != hipSuccess) return (int)e;
-    track_kernel<<<dim3((unsigned)S), dim3(kThreads), 0, q>>>(rows_in, N, D, (const int32_t*)workspace, (const gpp_track_state*)state_in,
-                                                             (gpp_track_state*)state_out, p, rows_out, track_ids, track_hits,
-                                                             (double*)((char*)workspace + seq_bytes(S)));
+    if (optimal)
+        track_kernel<true><<<dim3((unsigned)S), dim3(kThreads), 0, q>>>(rows_in, N, D, (const int32_t*)workspace, (const gpp_track_state*)state_in,
+                                                                       (gpp_track_state*)state_out, p, rows_out, track_ids, track_hits, nullptr);
+    else
+        track_kernel<false><<<dim3((unsigned)S), dim3(kThreads), 0, q>>>(rows_in, N, D, (const int32_t*)workspace, (const gpp_track_state*)state_in,
+                                                                        (gpp_track_state*)state_out, p, rows_out, track_ids, track_hits,
+                                                                        (double*)((char*)workspace + seq_bytes(S)));
     e = hipGetLastError();
     return e == hipSuccess ? GPP_OK : (int)e;
+}
+
+extern "C" int gpp_track_f64(const float* rows_in, int N, int D, const int32_t* seq_start, int S, const void* state_in, void* state_out,
+                             const gpp_track_params* params, float* rows_out, int32_t* track_ids, int32_t* track_hits,
+                             void* workspace, size_t workspace_bytes, void* stream)
+{
+    return track(false, rows_in, N, D, seq_start, S, state_in, state_out, params, rows_out, track_ids, track_hits, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gpp_track_optimal_f64(const float* rows_in, int N, int D, const int32_t* seq_start, int S, const void* state_in, void* state_out,
+                                     const gpp_track_params* params, float* rows_out, int32_t* track_ids, int32_t* track_hits,
+                                     void* workspace, size_t workspace_bytes, void* stream)
+{
+    return track(true, rows_in, N, D, seq_start, S, state_in, state_out, params, rows_out, track_ids, track_hits, workspace, workspace_bytes, stream);
 }

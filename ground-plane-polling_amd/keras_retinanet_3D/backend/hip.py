@@ -201,6 +201,11 @@ def _declare(lib):
         lib.gpp_track_f64.restype = c_int
         lib.gpp_track_f64.argtypes = [c_void_p, c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_void_p, c_void_p,
                                       ctypes.POINTER(TrackParams), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    # the tracker's optimal assignment (include/gpp.h, csrc/track.hip; absent from an older build named by GPP_LIB: it runs everything but
+    # track models with 'assign': 'optimal')
+    if hasattr(lib, 'gpp_track_optimal_f64'):
+        lib.gpp_track_optimal_f64.restype = c_int
+        lib.gpp_track_optimal_f64.argtypes = lib.gpp_track_f64.argtypes
     # the tracking score (include/gpp.h, csrc/mot_eval.hip; absent from an older build named by GPP_LIB: it runs everything but
     # evaluate_tracking(device=True))
     if hasattr(lib, 'gpp_mot_assign'):
@@ -612,8 +617,9 @@ def track_workspace_bytes(S):
     return n.value
 
 
-def track(rows, state_in, params, seq_start=None, state_out=None, out=None, ids=None, hits=None, workspace=None):
-    """ gpp_track_f64 on the current stream: rows (N, D, 36) float32 on the device -- the rows of gpp_pose_f32 of N frames --, state_in
+def track(rows, state_in, params, seq_start=None, state_out=None, out=None, ids=None, hits=None, workspace=None, optimal=False):
+    """ gpp_track_f64 (optimal: gpp_track_optimal_f64, the same arguments) on the current stream: rows (N, D, 36) float32 on the device --
+    the rows of gpp_pose_f32 of N frames --, state_in
     (S, gpp_track_state bytes) uint8 on the device, params a TrackParams, seq_start (S + 1) host integers (default: one sequence of all N
     frames) -> (rows_out (N, D, 36) float32, ids (N, D) int32, hits (N, D) int32, state_out) on the device; no synchronisation.
     out: where the rows go (default: a new tensor; `rows` itself: in place); state_out: default a new tensor (`state_in` itself: in place) """
@@ -641,8 +647,11 @@ def track(rows, state_in, params, seq_start=None, state_out=None, out=None, ids=
             raise ValueError('gpp_track_f64: expected {} {} on {}, got {} {} on {}'.format(shape, dtype, dev, tuple(t.shape), t.dtype, t.device))
     if workspace.dtype != torch.uint8 or workspace.device != dev:
         raise ValueError('gpp_track_f64: the workspace must be uint8 on {}'.format(dev))
-    check(lib().gpp_track_f64(ptr(rows), N, D, seq, S, ptr(state_in), ptr(state_out), ctypes.byref(params), ptr(out), ptr(ids), ptr(hits),
-                              ptr(workspace), int(workspace.numel()), stream_ptr()), 'gpp_track_f64')
+    name = 'gpp_track_optimal_f64' if optimal else 'gpp_track_f64'
+    if not hasattr(lib(), name):
+        raise GppError('{} is not in {}: there is no other path for this assignment'.format(name, LIB_PATH))
+    check(getattr(lib(), name)(ptr(rows), N, D, seq, S, ptr(state_in), ptr(state_out), ctypes.byref(params), ptr(out), ptr(ids), ptr(hits),
+                               ptr(workspace), int(workspace.numel()), stream_ptr()), name)
     return out, ids, hits, state_out
 
 

@@ -86,6 +86,9 @@ def parse_args(args):
                         help='The threshold of --track.  No default: it depends on the checkpoint and the frame rate.')
     parser.add_argument('--track-max-age', type=int, default=track_utils.DEFAULTS['max_age'],
                         help='Frames a track survives without a detection.')
+    parser.add_argument('--track-assign', choices=list(track_utils.ASSIGNS), default='greedy',
+                        help='How --track associates: greedy (candidates best first) or optimal, the one-to-one assignment of the least total '
+                             'cost per frame (gpp_track_optimal_f64, DESIGN.md section 4.32).')
     parser.add_argument('--track-min-hits', type=int, default=1, help='Only tracks seen in at least this many frames are written to tracks.txt.')
     parser.add_argument('--track-smooth', action='store_true',
                         help='Write the filtered cuboid (position, size, r_y, alpha) of tracked detections instead of the detector\'s.')
@@ -128,7 +131,10 @@ def track_option(args):
     """ the model's `track` option of the command line, or None """
     if args.track is None:
         return None
-    return {'metric': args.track, 'threshold': args.track_threshold, 'max_age': args.track_max_age, 'smooth': args.track_smooth}
+    option = {'metric': args.track, 'threshold': args.track_threshold, 'max_age': args.track_max_age, 'smooth': args.track_smooth}
+    if args.track_assign == 'optimal':
+        option['assign'] = 'optimal'
+    return option
 
 
 def make_output_tree(args):

@@ -8,9 +8,11 @@ an identity that persists from frame to frame and the t
 
 The network does not run again: the result files of bin/run_network.py --kitti are read (utils/kitti_eval.read_result_file), so a
 threshold can be swept.  On the GPU by default (csrc/track.hip: one launch for the whole sequence); --host uses the NumPy form
-(utils/track.track_rows_np) and, without --smooth, writes the same bytes.
+(utils/track.track_rows_np) and, without --smooth, writes the same bytes.  --track-assign optimal replaces the greedy association by the
+optimal one-to-one assignment of every frame, on the GPU and with --host alike.
 
     track_results.py result_dir/ tracks.txt --metric dist --threshold 2.0 [--max-age 2] [--min-hits 1] [--smooth] [--host]
+                     [--track-assign greedy|optimal]
                      [--labels label_02/0000.txt [--score-metric image] [--score-min-overlap 0.5] [--hota] [--idf1]]
 
 --labels scores the tracks just written against the sequence's label_02 file (CLEAR-MOT; on the GPU unless
@@ -49,13 +51,16 @@ def parse_args(args):
     parser.add_argument('--birth-score', type=float, default=track_utils.DEFAULTS['birth_score'],
                         help='Only detections with at least this score start a track.')
     parser.add_argument('--smooth', action='store_true', help='Write the filtered cuboid of tracked detections instead of the detector\'s.')
+    parser.add_argument('--track-assign', choices=list(track_utils.ASSIGNS), default='greedy',
+                        help='greedy: candidates best first (section 4.28).  optimal: the one-to-one assignment of the least total cost '
+                             'per frame (section 4.32): a track does not lose its detection to a neighbour that has another.')
     parser.add_argument('--host', action='store_true', help='The NumPy form instead of the GPU.')
     parser.add_argument('--labels', help='The sequence\'s label_02 file: score the tracks just written and print the CLEAR-MOT table.')
     evaluate_tracking.add_scoring_arguments(parser, 'score-')
     parsed = parser.parse_args(args)
     try:
         parsed.option = track_utils.check_option({'metric': parsed.metric, 'threshold': parsed.threshold, 'max_age': parsed.max_age,
-                                                  'birth_score': parsed.birth_score, 'smooth': parsed.smooth})
+                                                  'birth_score': parsed.birth_score, 'smooth': parsed.smooth, 'assign': parsed.track_assign})
         mot_eval.check_params(parsed.mot_metric, parsed.mot_min_overlap)
     except ValueError as e:
         parser.error(str(e))

@@ -95,13 +95,14 @@ def load_model(filepath, backbone_name='resnet50', convert=False, nms=True, clas
     the rows (predict_poses_*, score_poses_on_frames, predict_composites_on_frames) sees the suppressed set; model.cuboid_suppressors()
     says which row removed which.  There is no default threshold: it depends on the checkpoint.  predict_on_batch is unchanged.
     `track` (not in the reference; default None; needs pose=True): a pair (metric, threshold) or a dict {'metric': 'bev' | '3d' | 'dist',
-    'threshold': T, 'max_age': 2, 'gains': (a, b, c), 'birth_score': 0.0, 'smooth': False} -- the model gets predict_tracks_on_frames /
+    'threshold': T, 'max_age': 2, 'gains': (a, b, c), 'birth_score': 0.0, 'smooth': False, 'assign': 'greedy'} -- the model gets predict_tracks_on_frames /
     predict_tracks_on_batch, which follow the plan with one more launch (gpp_track_f64): the rows of every image
     are associated greedily with the cuboids carried over from the frames before (overlap above T for 'bev' / '3d', centre distance on the
     ground below T metres for 'dist') and get an identity that persists; a fixed-gain filter carries each cuboid.  The images of a call
     are consecutive frames of the model's one sequence and a later call continues it; model.reset_tracks() starts a new one,
     model.track_state() reads the state.  There is no default threshold: it depends on the checkpoint and the frame rate; the default
-    gains and max_age come from synthetic scenes only.  Every other method is unchanged and does not touch the tracker.  FramePipeline and
+    gains and max_age come from synthetic scenes only.  'assign': 'optimal' launches gpp_track_optimal_f64 instead (section 4.32): the
+    optimal one-to-one assignment of every frame in the place of the greedy pass, all else the same step.  Every other method is unchanged and does not touch the tracker.  FramePipeline and
     ShardedModel refuse such a model: they reorder or split the frames.
     """
     import os

@@ -818,6 +818,7 @@ class RetinaNet3D(object):
             self._track_state = [state[0], state[1]]
             self._track_work = torch.empty((hip.track_workspace_bytes(1),), dtype=torch.uint8, device=self.device)
             self._track_params = track_utils.params_of(self.track)
+            self._track_optimal = track_utils.is_optimal(self.track)     # 'assign': 'optimal' -> gpp_track_optimal_f64 (section 4.32)
         return self._track_state
 
     def reset_tracks(self):
@@ -843,7 +844,7 @@ class RetinaNet3D(object):
         def rows_and_tracks(model, p):
             # (smooth: the plan's rows stay what predict_poses_* reads; otherwise the kernel's bit copy lands where it came from)
             hip.track(p.pose_rows, state, self._track_params, state_out=nxt, out=out if smooth else p.pose_rows, ids=tags[0], hits=tags[1],
-                      workspace=self._track_work)
+                      workspace=self._track_work, optimal=self._track_optimal)
             (rows, counts), count = self.read_poses(model, p)
             if smooth:
                 rows = out.cpu().numpy()

@@ -1,19 +1,22 @@
 """
 Tracking of cuboids across frames: the pose rows of one frame are associated greedily with the cuboids carried over from the frames
 before, and every carried cuboid is a fixed-gain (alpha-beta) filter -- DESIGN.md section 4.28 is the specification, include/gpp.h
-(gpp_track_f64, gpp_track_state) the contract.  An identity per car that persists from frame to frame, and optionally a pose that does
-not jump by the detector's depth jitter.  There is no default threshold: it depends on the checkpoint and the frame rate.
+(gpp_track_f64, gpp_track_state) the contract.  With 'assign': 'optimal' the association is the optimal one-to-one assignment of the
+frame instead (gpp_track_optimal_f64); everything else is the same step.  An identity per car that persists from
+frame to frame, and optionally a pose that does not jump by the detector's depth jitter.  There is no default threshold: it depends on
+the checkpoint and the frame rate.
 
 Two forms of one computation:
     track_rows_np        NumPy, no GPU and no library: the candidates of a frame at once (the clipping of utils/kitti_eval.py), the
-                         greedy pass serial over the sorted candidates, as the rule demands.
+                         greedy pass serial over the sorted candidates, as the rule demands ('optimal': utils/mot_eval.assign_np on the
+                         frame's integer cells).
     track_rows_device    csrc/track.hip: one launch, one workgroup per sequence.
 
 The state is one record of STATE_DTYPE, byte for byte the gpp_track_state of include/gpp.h; all zero bytes is the empty tracker.
 """
 import numpy as np
 
-from . import gpp_utils, kitti_eval
+from . import gpp_utils, kitti_eval, mot_eval
 
 METRICS = ('bev', '3d', 'dist')             # include/gpp.h: GPP_TRACK_BEV 0, GPP_TRACK_3D 1, GPP_TRACK_DIST 2
 POSE_COLS = kitti_eval.POSE_COLS
@@ -26,6 +29,8 @@ STATE_DTYPE = np.dtype([('id1', '<i4', (MAX_TRACKS,)), ('hits', '<i4', (MAX_TRAC
                         ('next_id', '<i4'), ('frames', '<i4'), ('dropped', '<i4'), ('reserved', '<i4')])
 # gains and max_age: chosen on synthetic constant-velocity scenes only (tests/track_oracle.py); no real sequence has been measured
 DEFAULTS = {'max_age': 2, 'gains': (0.5, 0.25, 0.25), 'birth_score': 0.0, 'smooth': False}
+ASSIGNS = ('greedy', 'optimal')             # gpp_track_f64, gpp_track_optimal_f64; 'greedy' is the default and is not carried in the option
+SCALE = mot_eval.SCALE                      # 2^20 (GPP_MOT_SCALE_BITS): the cell of a pair that is no candidate
 PI = float(np.pi)
 TWO_PI = 2.0 * PI
 TRACKING_FORMAT = '%d %d ' + gpp_utils.KITTI_FORMAT
@@ -39,13 +44,14 @@ def metric_code(metric):
 
 def check_option(option):
     """ the `track` option of load_model / RetinaNet3D: None, a pair (metric, threshold), or a dict with 'metric' and 'threshold' and
-    optionally 'max_age', 'gains' (a, b, c), 'birth_score', 'smooth' -> None or the complete dict """
+    optionally 'max_age', 'gains' (a, b, c), 'birth_score', 'smooth', 'assign' ('greedy' | 'optimal') -> None or the complete dict; it
+    carries 'assign' only when that is 'optimal' """
     if option is None:
         return None
     if isinstance(option, dict):
-        unknown = sorted(set(option) - {'metric', 'threshold'} - set(DEFAULTS))
+        unknown = sorted(set(option) - {'metric', 'threshold', 'assign'} - set(DEFAULTS))
         if unknown or 'metric' not in option or 'threshold' not in option:
-            raise ValueError("track: a dict needs 'metric' and 'threshold' and may have {}; got {!r}".format(sorted(DEFAULTS), option))
+            raise ValueError("track: a dict needs 'metric' and 'threshold' and may have {}; got {!r}".format(sorted(DEFAULTS) + ['assign'], option))
         opt = dict(DEFAULTS, **option)
     else:
         try:
@@ -70,8 +76,14 @@ def check_option(option):
     birth = float(opt['birth_score'])
     if np.isnan(birth):
         raise ValueError('track: birth_score must not be NaN')
-    return {'metric': opt['metric'], 'threshold': thr, 'max_age': int(opt['max_age']), 'gains': (a, b, c), 'birth_score': birth,
-            'smooth': bool(opt['smooth'])}
+    assign = opt.get('assign', 'greedy')
+    if not isinstance(assign, str) or assign not in ASSIGNS:
+        raise ValueError("track: assign must be 'greedy' or 'optimal', got {!r}".format(assign))
+    out = {'metric': opt['metric'], 'threshold': thr, 'max_age': int(opt['max_age']), 'gains': (a, b, c), 'birth_score': birth,
+           'smooth': bool(opt['smooth'])}
+    if assign == 'optimal':
+        out['assign'] = assign
+    return out
 
 
 def empty_state(S=None):
@@ -156,6 +168,40 @@ def greedy(keys):
     return out
 
 
+def cost_cells(keys, occupied, valid, metric, threshold):
+    """ the matrix of section 4.32 from a frame's candidate table: (cost (n, n) int32 with n = max(T, R), the T occupied slots ascending
+    -- the matrix's rows --, the R live, non-blind rows ascending -- its columns).  A candidate's cell lies in [0, SCALE - 1]:
+    floor(q / threshold^2 * 2^20) for 'dist', 2^20 - floor(min(o * 2^20, 2^20)) otherwise; every other cell is SCALE """
+    ts, ds = np.flatnonzero(occupied), np.flatnonzero(valid)
+    n = max(ts.size, ds.size)
+    cost = np.full((n, n), SCALE, np.int32)
+    if ts.size and ds.size:
+        sub = keys[np.ix_(ts, ds)]
+        cand = np.isfinite(sub)
+        value = np.where(cand, sub, 0.0)
+        if metric == 'dist':
+            t2 = threshold * threshold
+            r = value / t2
+            x = r * 1048576.0
+            cell = np.minimum(np.floor(x), SCALE - 1)
+        else:
+            k = np.floor(np.minimum(-value * 1048576.0, 1048576.0))
+            cell = np.minimum(SCALE - k, SCALE - 1)
+        cost[:ts.size, :ds.size] = np.where(cand, cell, SCALE).astype(np.int32)
+    return cost, ts, ds
+
+
+def optimal(keys, occupied, valid, metric, threshold):
+    """ the assignment of the least total over cost_cells' matrix (mot_eval.assign_np: rows in order, one shortest augmenting path each,
+    ties to the first column); a slot and a row are matched iff they are assigned to each other AND are a candidate
+    -> [(slot, row)] in slot order """
+    cost, ts, ds = cost_cells(keys, occupied, valid, metric, threshold)
+    if ts.size == 0 or ds.size == 0:                     # (every cell is SCALE: whatever is assigned, nothing is matched)
+        return []
+    col, _ = mot_eval.assign_np(cost)
+    return [(int(ts[i]), int(ds[col[i]])) for i in range(ts.size) if col[i] < ds.size and cost[i, col[i]] < SCALE]
+
+
 def step_np(state, rows, opt, keys_out=None):
     """ one frame step on `state` (one writable STATE_DTYPE record, changed in place) -> (rows_out (D, 36) float32, ids (D,) int32,
     hits (D,) int32).  keys_out: a list that receives the frame's candidate table (the tests' margins) """
@@ -172,7 +218,10 @@ def step_np(state, rows, opt, keys_out=None):
     keys = candidate_keys(box, occupied, rows, valid, opt['metric'], opt['threshold'])              # 3 candidates
     if keys_out is not None:
         keys_out.append(keys)
-    pairs = greedy(keys)                                                                            # 4 greedy
+    if opt.get('assign') == 'optimal':                                                              # 4 greedy, or section 4.32's assignment
+        pairs = optimal(keys, occupied, valid, opt['metric'], opt['threshold'])
+    else:
+        pairs = greedy(keys)
     row_slot = np.full(D, -1, np.int64)
     if pairs:                                                                                       # 5 update
         t, d = np.array([p[0] for p in pairs]), np.array([p[1] for p in pairs])
@@ -246,6 +295,11 @@ def params_of(options):
     return hip.TrackParams(metric_code(opt['metric']), opt['max_age'], int(opt['smooth']), 0, opt['threshold'], a, b, c, opt['birth_score'])
 
 
+def is_optimal(options):
+    """ whether the option asks for gpp_track_optimal_f64 (the entry point, not a field of the parameters, carries the choice) """
+    return check_option(options).get('assign') == 'optimal'
+
+
 def state_tensor(state, device, S=1):
     """ None (S empty trackers), STATE_DTYPE records or a uint8 tensor -> the (S, bytes) uint8 tensor gpp_track_f64 takes """
     import torch
@@ -256,24 +310,25 @@ def state_tensor(state, device, S=1):
 
 
 def track_rows_device(rows, options, state=None, seq_start=None, out=None, state_out=None):
-    """ csrc/track.hip: rows (N, D, 36), the frames of S sequences (seq_start (S + 1,), default one sequence of all frames): a NumPy array
+    """ csrc/track.hip (gpp_track_f64, or gpp_track_optimal_f64 for 'assign': 'optimal'): rows (N, D, 36), the frames of S sequences
+    (seq_start (S + 1,), default one sequence of all frames): a NumPy array
     -> NumPy results and STATE_DTYPE state(s), or a float32 device tensor -> device tensors with the state as (S, bytes) uint8 (no
     synchronisation; read_state reads it).  state: None (empty), STATE_DTYPE record(s) or such a tensor.  out / state_out (tensors only):
     where the rows and the state go -- `rows` and `state` themselves are allowed.
     Returns (rows_out, ids (N, D) int32, hits (N, D) int32, state).  D <= 128. """
     import torch
     from ..backend import hip
-    params = params_of(options)
+    params, best = params_of(options), is_optimal(options)
     S = 1 if seq_start is None else len(seq_start) - 1
     if isinstance(rows, torch.Tensor):
         if rows.dim() != 3 or not rows.is_contiguous():
             raise ValueError('track_rows_device: rows must be a dense (N, D, {}) tensor, got {}'.format(POSE_COLS, tuple(rows.shape)))
-        return hip.track(rows, state_tensor(state, rows.device, S), params, seq_start, state_out=state_out, out=out)
+        return hip.track(rows, state_tensor(state, rows.device, S), params, seq_start, state_out=state_out, out=out, optimal=best)
     host = np.ascontiguousarray(rows, np.float32)
     if host.ndim != 3 or host.shape[2] != POSE_COLS:
         raise ValueError('track_rows_device: rows must be (N, D, {}), got {}'.format(POSE_COLS, host.shape))
     dev = hip.require_device()
-    res = hip.track(torch.as_tensor(host).to(dev), state_tensor(state, dev, S), params, seq_start)
+    res = hip.track(torch.as_tensor(host).to(dev), state_tensor(state, dev, S), params, seq_start, optimal=best)
     new = read_state(res[3])
     return res[0].cpu().numpy(), res[1].cpu().numpy(), res[2].cpu().numpy(), (new[0] if seq_start is None else new)
 

@@ -848,6 +848,34 @@ int gpp_track_f64(const float* rows_in, int N, int D, const int32_t* seq_start, 
                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Tracking with an OPTIMAL one-to-one assignment per frame (csrc/track.hip, the same kernel with another step 4; DESIGN.md section 4.32 is
+ * the specification, utils/track.py with 'assign': 'optimal' the host form).  The signature, the structs, the state's layout, the
+ * workspace, every error and the N * D == 0 / S == 0 behaviour are gpp_track_f64's; so are the steps 1 - 3 and 5 - 7 of the frame step,
+ * operation for operation, and the candidates are the same pairs.  gpp_track_params has no field for the choice (reserved != 0 is refused
+ * by both): the entry point is the choice.  Step 4 is:
+ *
+ *   matrix      square, int32, of side n = max(T, R): the T occupied slots in ascending slot order are its rows, the R live, non-blind rows
+ *               of the frame in ascending row order its columns.  n == 0: nothing to do.
+ *   cells       with S = 2^20 (GPP_MOT_SCALE_BITS).  GPP_TRACK_DIST: t2 = threshold * threshold, r = q / t2, x = r * 2^20 (three separate
+ *               float64 operations); the cell is min(floor(x), S - 1).  GPP_TRACK_BEV / GPP_TRACK_3D: k = floor(min(o * 2^20, 2^20)); the
+ *               cell is min(S - k, S - 1).  A pair that is no candidate has S, and so has every padding cell: a candidate's cell lies in
+ *               [0, S - 1], so taking it is always better than leaving both sides alone.
+ *   objective   the minimum total of the n assigned cells, that is the largest sum of (S - cell) over the candidates taken.  This is NOT
+ *               gpp_mot_assign's GPP_MOT_BIG form ("most pairs first"): an unmatched pair costs what a pair at the threshold costs, and a
+ *               near pair is given up for two farther ones only when those two together cost less than the near pair and one miss.
+ *   assignment  gpp_mot_assign's paragraph "assignment" below, word for word: the rows in order, one shortest augmenting path each, int64
+ *               potentials that start at zero, ties to the first column (csrc/mot_assign.h, gpp_mot::assign_rows, run by one wavefront on
+ *               the matrix in LDS).  Everything behind the cells is integer: the three forms are equal with ==, ties included.
+ *   pairs       slot i and row j are matched iff column j is assigned to row i and (i, j) is a candidate (its cell is below S).
+ *
+ *   workspace   gpp_track_workspace_bytes(S) bytes as gpp_track_f64 takes them (one buffer serves both entry points); only seq_start's copy
+ *               is used: the matrix lies in LDS, 64 KiB at n = 128 beside the 81 KiB of the rest.
+ * ---------------------------------------------------------------------------------------- */
+int gpp_track_optimal_f64(const float* rows_in, int N, int D, const int32_t* seq_start, int S, const void* state_in, void* state_out,
+                          const gpp_track_params* params, float* rows_out, int32_t* track_ids, int32_t* track_hits,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CLEAR-MOT scoring of tracks on the device (csrc/mot_eval.hip; DESIGN.md section 4.29 is the specification, a restatement of the KITTI
  * tracking devkit's CLEAR-MOT -- parity with the devkit itself is UNPINNED; utils/mot_eval.py is the host form): per frame the OPTIMAL
  * one-to-one assignment of the tracker's rows to the labels (the Hungarian method, shortest augmenting paths, exact integers), then per
