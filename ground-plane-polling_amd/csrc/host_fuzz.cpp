@@ -243,6 +243,21 @@ int main(int argc, char** argv)
                 note(gpp_track_optimal_f64((const float*)r.d[0].in, 8, (int)(r.b % 128) + 1, seq, 2, r.d[0].in, r.d[0].out, &tp, (float*)r.d[0].out,
                                            (int32_t*)(uintptr_t)r.d[0].bias, (int32_t*)(uintptr_t)r.d[0].bias, (void*)((uintptr_t)r.d[0].out | 8), 0,
                                            nullptr));
+                // the ego records are the second host array a call reads: 8 of them (seq_start never passes 8 here), one word fuzzed to a
+                // NaN, an infinity or a padding word that is not 0 -- the frames inside a sequence are read, and only those
+                double ego[8 * GPP_TRACK_EGO_FIELDS] = {0.0};
+                for (int f = 0; f < 8; ++f) ego[f * GPP_TRACK_EGO_FIELDS] = ego[f * GPP_TRACK_EGO_FIELDS + 4] = ego[f * GPP_TRACK_EGO_FIELDS + 8] = 1.0;
+                const double odd[4] = {0.0, __builtin_nan(""), __builtin_inf(), 1.0};
+                ego[(r.a % 8) * GPP_TRACK_EGO_FIELDS + r.b % GPP_TRACK_EGO_FIELDS] = odd[r.c % 4];
+                note(gpp_track_ego_workspace_bytes((int)r.a, (int)r.b, &tb));
+                note(gpp_track_ego_workspace_bytes((int)(r.a % 64), (int)(r.b % 64), nullptr));
+                note(gpp_track_ego_f64(nullptr, 8, (int)r.b, seq, 2, nullptr, nullptr, &tp, ego, (int)(r.c % 4) - 1, nullptr, nullptr, nullptr, nullptr, 0,
+                                       nullptr));
+                note(gpp_track_ego_f64(nullptr, (int)r.a, (int)r.b, seq, 2, nullptr, nullptr, &tp, nullptr, (int)(r.c & 1), nullptr, nullptr, nullptr,
+                                       nullptr, 0, nullptr));
+                note(gpp_track_ego_f64((const float*)r.d[0].in, 8, (int)(r.b % 128) + 1, seq, 2, r.d[0].in, r.d[0].out, &tp, ego, (int)(r.c & 1),
+                                       (float*)r.d[0].out, (int32_t*)(uintptr_t)r.d[0].bias, (int32_t*)(uintptr_t)r.d[0].bias,
+                                       (void*)((uintptr_t)r.d[0].out | 8), 0, nullptr));
             }
             // the tracking score: fuzzed parameters, sizes and sequence starts against null pointers, more rows or trajectories than the kernels
             // take, and a workspace of no bytes -- all end before any launch or copy (seq_start is the one host array gpp_mot_clear reads)

@@ -40,6 +40,12 @@
 //                  The matrix is 64 KiB beside the 81 KiB of the greedy form: 145 KiB of the 160 KiB a workgroup may have, so it is
 //                  declared on its own and overlays nothing.  There is no table in HBM in this form: the workspace holds seq_start only.
 //                  The greedy instantiation has none of these statements (if constexpr) and no matrix.
+//
+//   track_kernel<*, true>   gpp_track_ego_f64: either kernel with step 1b between the prediction and the
+//                  predicted corners -- the slot's thread carries its position, its velocity and r_y into the frame's camera coordinates
+//                  by the frame's ego record.  The entry point has checked the records on the host and copied them into the workspace
+//                  behind everything else; every thread takes the frame's 13 words from there (the address is uniform) and a slot's
+//                  thread uses them.  No barrier, no loop and no LDS word more; the <*, false> instantiations have none of it.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -62,6 +68,7 @@ constexpr double kTwoPi = 2.0 * kPi;
 constexpr size_t kSeqBytes = 256;                    // the workspace starts with seq_start's copy, padded to a multiple of this
 constexpr int32_t kScale = 1 << GPP_MOT_SCALE_BITS;  // section 4.32: the cell of a pair that is no candidate, and of padding
 constexpr int kSide = kSlots > kMaxD ? kSlots : kMaxD;                 // the largest matrix of section 4.32
+constexpr int kEgoFields = GPP_TRACK_EGO_FIELDS;     // section 4.33: R row-major (9), t (3), dyaw (1), three words that are 0
 
 static_assert(kThreads == kSlots && kThreads >= kMaxD, "one thread per slot and per row");
 static_assert(kChunk <= 65536, "a pair's offset into its chunk is 16 bits");
@@ -94,12 +101,13 @@ __device__ __forceinline__ int block_rank(bool flag, int tid, int* s_wave, int& 
 }
 
 size_t seq_bytes(int S) { return ((size_t)(S + 1) * sizeof(int32_t) + kSeqBytes - 1) / kSeqBytes * kSeqBytes; }
+size_t plain_bytes(int S) { return seq_bytes(S) + (size_t)S * 2 * kSlots * kMaxD * sizeof(double); }     // gpp_track_workspace_bytes
 
-template <bool kOptimal>
+template <bool kOptimal, bool kEgo>
 __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, int N, int D, const int32_t* __restrict__ seq_start,
                                                          const gpp_track_state* states_in, gpp_track_state* states_out,
                                                          gpp_track_params prm, float* rows_out, int32_t* track_ids, int32_t* track_hits,
-                                                         double* tables)
+                                                         double* tables, const double* __restrict__ ego)
 {
     __shared__ double s_x[2][rot_iou::kMaxVerts][kThreads];
     __shared__ double s_z[2][rot_iou::kMaxVerts][kThreads];
@@ -172,10 +180,26 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
             s_mslot[tid] = -1;
             r_slot[tid] = -1;
             s_mrow[tid] = -1;
+            double e[13];                                // (ego) the frame's record: R row-major, t, dyaw
+            if constexpr (kEgo) {
+#pragma unroll
+                for (int k = 0; k < 13; ++k) e[k] = ego[(size_t)f * kEgoFields + k];
+            }
             if (st.id1[tid] != 0) {
-                const double x = st.box[FX][tid] + st.box[FVX][tid];
-                const double y = st.box[FY][tid] + st.box[FVY][tid];
-                const double z = st.box[FZ][tid] + st.box[FVZ][tid];
+                double x = st.box[FX][tid] + st.box[FVX][tid];
+                double y = st.box[FY][tid] + st.box[FVY][tid];
+                double z = st.box[FZ][tid] + st.box[FVZ][tid];
+                if constexpr (kEgo) {                    // 1b: into this frame's camera coordinates, all from the predicted x y z
+                    const double px = x, py = y, pz = z;
+                    const double vx = st.box[FVX][tid], vy = st.box[FVY][tid], vz = st.box[FVZ][tid];
+                    x = ((e[0] * px + e[1] * py) + e[2] * pz) + e[9];
+                    y = ((e[3] * px + e[4] * py) + e[5] * pz) + e[10];
+                    z = ((e[6] * px + e[7] * py) + e[8] * pz) + e[11];
+                    st.box[FVX][tid] = (e[0] * vx + e[1] * vy) + e[2] * vz;
+                    st.box[FVY][tid] = (e[3] * vx + e[4] * vy) + e[5] * vz;
+                    st.box[FVZ][tid] = (e[6] * vx + e[7] * vy) + e[8] * vz;
+                    st.box[FRY][tid] = wrap(st.box[FRY][tid] + e[12]);
+                }
                 st.box[FX][tid] = x; st.box[FY][tid] = y; st.box[FZ][tid] = z;
                 if (iou) {
                     const double ry = st.box[FRY][tid], l = st.box[FL][tid], w = st.box[FW][tid];
@@ -469,15 +493,23 @@ extern "C" int gpp_track_state_bytes(size_t* bytes)
 extern "C" int gpp_track_workspace_bytes(int S, size_t* bytes)
 {
     if (S < 0 || !bytes) return GPP_ERR_BAD_ARG;
-    *bytes = seq_bytes(S) + (size_t)S * 2 * kSlots * kMaxD * sizeof(double);
+    *bytes = plain_bytes(S);
     return GPP_OK;
 }
 
-// both entry points: the checks of the contract in their order, then the one launch.  The optimal form asks for the same workspace and
-// uses seq_start's copy only
-static int track(bool optimal, const float* rows_in, int N, int D, const int32_t* seq_start, int S, const void* state_in, void* state_out,
-                 const gpp_track_params* params, float* rows_out, int32_t* track_ids, int32_t* track_hits, void* workspace,
-                 size_t workspace_bytes, void* stream)
+extern "C" int gpp_track_ego_workspace_bytes(int S, int N, size_t* bytes)
+{
+    if (S < 0 || N < 0 || !bytes) return GPP_ERR_BAD_ARG;
+    *bytes = plain_bytes(S) + (size_t)N * kEgoFields * sizeof(double);          // (plain_bytes is a multiple of 8: the records are aligned)
+    return GPP_OK;
+}
+
+// the entry points: the checks of the contract in their order, then the one launch.  The optimal form asks for the same workspace and
+// uses seq_start's copy only.  with_ego: gpp_track_ego_f64 -- the records of the frames inside a sequence are checked here, on the host,
+// and copied behind the plain workspace
+static int track(bool optimal, bool with_ego, const double* ego, const float* rows_in, int N, int D, const int32_t* seq_start, int S,
+                 const void* state_in, void* state_out, const gpp_track_params* params, float* rows_out, int32_t* track_ids,
+                 int32_t* track_hits, void* workspace, size_t workspace_bytes, void* stream)
 {
     if (N < 0 || D < 0 || S < 0 || !params || !seq_start) return GPP_ERR_BAD_ARG;
     const gpp_track_params& p = *params;
@@ -490,6 +522,17 @@ static int track(bool optimal, const float* rows_in, int N, int D, const int32_t
         const int32_t lo = s == 0 ? 0 : seq_start[s - 1];
         if (seq_start[s] < lo || seq_start[s] > N) return GPP_ERR_BAD_ARG;
     }
+    const int f_lo = seq_start[0], f_hi = seq_start[S];              // the frames inside a sequence: seq_start is monotone
+    if (with_ego) {
+        if (N > 0 && !ego) return GPP_ERR_BAD_ARG;
+        for (int f = f_lo; f < f_hi; ++f) {
+            const double* e = ego + (size_t)f * kEgoFields;
+            for (int k = 0; k < 13; ++k)
+                if (!__builtin_isfinite(e[k])) return GPP_ERR_BAD_ARG;
+            for (int k = 13; k < kEgoFields; ++k)
+                if (!(e[k] == 0.0)) return GPP_ERR_BAD_ARG;          // (a NaN is not zero either)
+        }
+    }
     if (D > kMaxD) return GPP_ERR_UNSUPPORTED;
     if (S > 0 && (!state_in || !state_out)) return GPP_ERR_BAD_ARG;
     hipStream_t q = (hipStream_t)stream;
@@ -501,16 +544,28 @@ static int track(bool optimal, const float* rows_in, int N, int D, const int32_t
     }
     if (!rows_in || !rows_out || !track_ids || !track_hits || !workspace) return GPP_ERR_BAD_ARG;
     if (((uintptr_t)workspace | (uintptr_t)state_in | (uintptr_t)state_out) & 7u) return GPP_ERR_ALIGN;
-    if (workspace_bytes < seq_bytes(S) + (size_t)S * 2 * kSlots * kMaxD * sizeof(double)) return GPP_ERR_WORKSPACE;
+    if (workspace_bytes < plain_bytes(S) + (with_ego ? (size_t)N * kEgoFields * sizeof(double) : 0)) return GPP_ERR_WORKSPACE;
     hipError_t e = hipMemcpyAsync(workspace, seq_start, (size_t)(S + 1) * sizeof(int32_t), hipMemcpyHostToDevice, q);
     if (e != hipSuccess) return (int)e;
-    if (optimal)
-        track_kernel<true><<<dim3((unsigned)S), dim3(kThreads), 0, q>>>(rows_in, N, D, (const int32_t*)workspace, (const gpp_track_state*)state_in,
-                                                                       (gpp_track_state*)state_out, p, rows_out, track_ids, track_hits, nullptr);
+    double* ego_copy = (double*)((char*)workspace + plain_bytes(S));                // record f at its own place f: the kernel indexes by frame
+    if (with_ego && f_hi > f_lo) {
+        e = hipMemcpyAsync(ego_copy + (size_t)f_lo * kEgoFields, ego + (size_t)f_lo * kEgoFields,
+                           (size_t)(f_hi - f_lo) * kEgoFields * sizeof(double), hipMemcpyHostToDevice, q);
+        if (e != hipSuccess) return (int)e;
+    }
+    const int32_t* seq = (const int32_t*)workspace;
+    const gpp_track_state* in = (const gpp_track_state*)state_in;
+    gpp_track_state* out = (gpp_track_state*)state_out;
+    double* tables = (double*)((char*)workspace + seq_bytes(S));
+    const dim3 grid((unsigned)S), block(kThreads);
+    if (optimal && with_ego)
+        track_kernel<true, true><<<grid, block, 0, q>>>(rows_in, N, D, seq, in, out, p, rows_out, track_ids, track_hits, nullptr, ego_copy);
+    else if (with_ego)
+        track_kernel<false, true><<<grid, block, 0, q>>>(rows_in, N, D, seq, in, out, p, rows_out, track_ids, track_hits, tables, ego_copy);
+    else if (optimal)
+        track_kernel<true, false><<<grid, block, 0, q>>>(rows_in, N, D, seq, in, out, p, rows_out, track_ids, track_hits, nullptr, nullptr);
     else
-        track_kernel<false><<<dim3((unsigned)S), dim3(kThreads), 0, q>>>(rows_in, N, D, (const int32_t*)workspace, (const gpp_track_state*)state_in,
-                                                                        (gpp_track_state*)state_out, p, rows_out, track_ids, track_hits,
-                                                                        (double*)((char*)workspace + seq_bytes(S)));
+        track_kernel<false, false><<<grid, block, 0, q>>>(rows_in, N, D, seq, in, out, p, rows_out, track_ids, track_hits, tables, nullptr);
     e = hipGetLastError();
     return e == hipSuccess ? GPP_OK : (int)e;
 }
@@ -519,12 +574,23 @@ extern "C" int gpp_track_f64(const float* rows_in, int N, int D, const int32_t* 
                              const gpp_track_params* params, float* rows_out, int32_t* track_ids, int32_t* track_hits,
                              void* workspace, size_t workspace_bytes, void* stream)
 {
-    return track(false, rows_in, N, D, seq_start, S, state_in, state_out, params, rows_out, track_ids, track_hits, workspace, workspace_bytes, stream);
+    return track(false, false, nullptr, rows_in, N, D, seq_start, S, state_in, state_out, params, rows_out, track_ids, track_hits, workspace,
+                 workspace_bytes, stream);
 }
 
 extern "C" int gpp_track_optimal_f64(const float* rows_in, int N, int D, const int32_t* seq_start, int S, const void* state_in, void* state_out,
                                      const gpp_track_params* params, float* rows_out, int32_t* track_ids, int32_t* track_hits,
                                      void* workspace, size_t workspace_bytes, void* stream)
 {
-    return track(true, rows_in, N, D, seq_start, S, state_in, state_out, params, rows_out, track_ids, track_hits, workspace, workspace_bytes, stream);
+    return track(true, false, nullptr, rows_in, N, D, seq_start, S, state_in, state_out, params, rows_out, track_ids, track_hits, workspace,
+                 workspace_bytes, stream);
+}
+
+extern "C" int gpp_track_ego_f64(const float* rows_in, int N, int D, const int32_t* seq_start, int S, const void* state_in, void* state_out,
+                                 const gpp_track_params* params, const double* ego, int assign, float* rows_out, int32_t* track_ids,
+                                 int32_t* track_hits, void* workspace, size_t workspace_bytes, void* stream)
+{
+    if (assign != GPP_TRACK_ASSIGN_GREEDY && assign != GPP_TRACK_ASSIGN_OPTIMAL) return GPP_ERR_BAD_ARG;
+    return track(assign == GPP_TRACK_ASSIGN_OPTIMAL, true, ego, rows_in, N, D, seq_start, S, state_in, state_out, params, rows_out, track_ids,
+                 track_hits, workspace, workspace_bytes, stream);
 }

@@ -129,6 +129,7 @@ class AbsmaxDesc(ctypes.Structure):
 
 
 GPP_TRACK_MAX_TRACKS, GPP_TRACK_FIELDS = 128, 10   # include/gpp.h, gpp_track_state
+GPP_TRACK_EGO_FIELDS = 16                          # gpp_track_ego_f64: one record per frame
 
 
 class TrackState(ctypes.Structure):
@@ -206,6 +207,15 @@ def _declare(lib):
     if hasattr(lib, 'gpp_track_optimal_f64'):
         lib.gpp_track_optimal_f64.restype = c_int
         lib.gpp_track_optimal_f64.argtypes = lib.gpp_track_f64.argtypes
+    # the tracker's ego-motion compensation (include/gpp.h, csrc/track.hip; absent from an older build named by GPP_LIB: it runs everything
+    # but tracking with ego records)
+    if hasattr(lib, 'gpp_track_ego_f64'):
+        lib.gpp_track_ego_workspace_bytes.restype = c_int
+        lib.gpp_track_ego_workspace_bytes.argtypes = [c_int, c_int, ctypes.POINTER(c_size_t)]
+        lib.gpp_track_ego_f64.restype = c_int
+        lib.gpp_track_ego_f64.argtypes = [c_void_p, c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_void_p, c_void_p,
+                                          ctypes.POINTER(TrackParams), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                          c_void_p]
     # the tracking score (include/gpp.h, csrc/mot_eval.hip; absent from an older build named by GPP_LIB: it runs everything but
     # evaluate_tracking(device=True))
     if hasattr(lib, 'gpp_mot_assign'):
@@ -617,12 +627,22 @@ def track_workspace_bytes(S):
     return n.value
 
 
-def track(rows, state_in, params, seq_start=None, state_out=None, out=None, ids=None, hits=None, workspace=None, optimal=False):
+def track_ego_workspace_bytes(S, N):
+    if not hasattr(lib(), 'gpp_track_ego_f64'):
+        raise GppError('gpp_track_ego_f64 is not in {}: there is no other path for ego records'.format(LIB_PATH))
+    n = c_size_t(0)
+    check(lib().gpp_track_ego_workspace_bytes(int(S), int(N), ctypes.byref(n)), 'gpp_track_ego_workspace_bytes')
+    return n.value
+
+
+def track(rows, state_in, params, seq_start=None, state_out=None, out=None, ids=None, hits=None, workspace=None, optimal=False, ego=None):
     """ gpp_track_f64 (optimal: gpp_track_optimal_f64, the same arguments) on the current stream: rows (N, D, 36) float32 on the device --
     the rows of gpp_pose_f32 of N frames --, state_in
     (S, gpp_track_state bytes) uint8 on the device, params a TrackParams, seq_start (S + 1) host integers (default: one sequence of all N
     frames) -> (rows_out (N, D, 36) float32, ids (N, D) int32, hits (N, D) int32, state_out) on the device; no synchronisation.
-    out: where the rows go (default: a new tensor; `rows` itself: in place); state_out: default a new tensor (`state_in` itself: in place) """
+    out: where the rows go (default: a new tensor; `rows` itself: in place); state_out: default a new tensor (`state_in` itself: in place).
+    ego: None, or the (N, 16) float64 HOST records of the frames (a NumPy array): gpp_track_ego_f64 with assign = optimal, and a workspace
+    of track_ego_workspace_bytes(S, N) """
     import torch
     if rows.dim() != 3 or rows.dtype != torch.float32 or rows.shape[2] != GPP_POSE_COLS:
         raise ValueError('gpp_track_f64: rows must be (N, D, {}) float32, got {} {}'.format(GPP_POSE_COLS, tuple(rows.shape), rows.dtype))
@@ -638,7 +658,12 @@ def track(rows, state_in, params, seq_start=None, state_out=None, out=None, ids=
     ids = torch.full((N, D), -1, dtype=torch.int32, device=dev) if ids is None else ids
     hits = torch.zeros((N, D), dtype=torch.int32, device=dev) if hits is None else hits
     state_out = torch.empty_like(state_in) if state_out is None else state_out
-    need = track_workspace_bytes(S)
+    if ego is not None:
+        import numpy as np
+        ego = np.ascontiguousarray(ego, np.float64)
+        if ego.shape != (N, GPP_TRACK_EGO_FIELDS):
+            raise ValueError('gpp_track_ego_f64: ego must be ({}, {}) float64 on the host, got {}'.format(N, GPP_TRACK_EGO_FIELDS, ego.shape))
+    need = track_workspace_bytes(S) if ego is None else track_ego_workspace_bytes(S, N)
     workspace = torch.empty((need,), dtype=torch.uint8, device=dev) if workspace is None else workspace
     want = ((out, torch.float32, (N, D, GPP_POSE_COLS)), (ids, torch.int32, (N, D)), (hits, torch.int32, (N, D)),
             (state_out, torch.uint8, (S, nbytes)))
@@ -647,9 +672,14 @@ def track(rows, state_in, params, seq_start=None, state_out=None, out=None, ids=
             raise ValueError('gpp_track_f64: expected {} {} on {}, got {} {} on {}'.format(shape, dtype, dev, tuple(t.shape), t.dtype, t.device))
     if workspace.dtype != torch.uint8 or workspace.device != dev:
         raise ValueError('gpp_track_f64: the workspace must be uint8 on {}'.format(dev))
-    name = 'gpp_track_optimal_f64' if optimal else 'gpp_track_f64'
+    name = 'gpp_track_ego_f64' if ego is not None else 'gpp_track_optimal_f64' if optimal else 'gpp_track_f64'
     if not hasattr(lib(), name):
         raise GppError('{} is not in {}: there is no other path for this assignment'.format(name, LIB_PATH))
+    if ego is not None:
+        check(lib().gpp_track_ego_f64(ptr(rows), N, D, seq, S, ptr(state_in), ptr(state_out), ctypes.byref(params),
+                                      ego.ctypes.data_as(c_void_p), int(bool(optimal)), ptr(out), ptr(ids), ptr(hits), ptr(workspace),
+                                      int(workspace.numel()), stream_ptr()), name)
+        return out, ids, hits, state_out
     check(getattr(lib(), name)(ptr(rows), N, D, seq, S, ptr(state_in), ptr(state_out), ctypes.byref(params), ptr(out), ptr(ids), ptr(hits),
                                ptr(workspace), int(workspace.numel()), stream_ptr()), name)
     return out, ids, hits, state_out

@@ -89,6 +89,12 @@ def parse_args(args):
     parser.add_argument('--track-assign', choices=list(track_utils.ASSIGNS), default='greedy',
                         help='How --track associates: greedy (candidates best first) or optimal, the one-to-one assignment of the least total '
                              'cost per frame (gpp_track_optimal_f64, DESIGN.md section 4.32).')
+    parser.add_argument('--track-oxts', default=None,
+                        help='With --track: the sequence\'s KITTI oxts file (oxts/<seq>.txt), one line per image of the sorted list.  The '
+                             'carried cuboids are moved into every frame\'s camera coordinates before they are matched '
+                             '(gpp_track_ego_f64, DESIGN.md section 4.33): a parked car keeps its id from a driving camera.  Needs --track-calib.')
+    parser.add_argument('--track-calib', default=None,
+                        help='With --track-oxts: the sequence\'s tracking calibration file (calib/<seq>.txt: R_rect, Tr_velo_cam, Tr_imu_velo).')
     parser.add_argument('--track-min-hits', type=int, default=1, help='Only tracks seen in at least this many frames are written to tracks.txt.')
     parser.add_argument('--track-smooth', action='store_true',
                         help='Write the filtered cuboid (position, size, r_y, alpha) of tracked detections instead of the detector\'s.')
@@ -109,6 +115,10 @@ def parse_args(args):
         parser.error('--idf1 scores the tracks against --tracking-labels: it needs --tracking-labels')
     if (parsed.track is None) != (parsed.track_threshold is None):
         parser.error('--track and --track-threshold go together: both or neither')
+    if (parsed.track_oxts is None) != (parsed.track_calib is None):
+        parser.error('--track-oxts and --track-calib go together: both or neither')
+    if parsed.track_oxts is not None and parsed.track is None:
+        parser.error('--track-oxts compensates the tracker of --track: it needs --track')
     if parsed.track is not None:
         if not parsed.device_pose:
             parser.error('--track follows the pose stage on the GPU: it needs --device-pose')
@@ -134,6 +144,8 @@ def track_option(args):
     option = {'metric': args.track, 'threshold': args.track_threshold, 'max_age': args.track_max_age, 'smooth': args.track_smooth}
     if args.track_assign == 'optimal':
         option['assign'] = 'optimal'
+    if args.track_oxts is not None:
+        option['ego'] = True
     return option
 
 
@@ -231,6 +243,10 @@ def main(args=None):
         args = sys.argv[1:]
     args = parse_args(args)
 
+    ego = None
+    if args.track_oxts is not None:              # (before the model is loaded and the output tree is made: a wrong line count ends here)
+        from ..utils import oxts
+        ego = oxts.records_for(args.track_oxts, args.track_calib, len(os.listdir(args.calib_dir)))
     model = models.load_model(args.model_path, backbone_name=args.backbone, dtype=args.dtype, pose=args.device_pose, range_audit=args.range_audit,
                               cuboid_nms=(args.cuboid_nms, args.cuboid_nms_threshold) if args.device_pose and args.cuboid_nms is not None else None,
                               track=track_option(args))
@@ -256,7 +272,10 @@ def main(args=None):
                 frames = stack([it['raw_image'] for it in group])
                 pictures = [None] * len(group)
                 if args.track is not None:
-                    (rows, counts, ids, hits), _ = model.predict_tracks_on_frames(frames, P_inv, planes)
+                    if ego is None:
+                        (rows, counts, ids, hits), _ = model.predict_tracks_on_frames(frames, P_inv, planes)
+                    else:
+                        (rows, counts, ids, hits), _ = model.predict_tracks_on_frames(frames, P_inv, planes, ego=ego[j:j + len(group)])
                     for k in range(len(group)):
                         tracks.write(track_utils.tracking_lines(j + k, rows[k], ids[k], hits[k], args.track_min_hits))
                 elif args.save_images:

@@ -9,10 +9,12 @@ an identity that persists from frame to frame and the t
 The network does not run again: the result files of bin/run_network.py --kitti are read (utils/kitti_eval.read_result_file), so a
 threshold can be swept.  On the GPU by default (csrc/track.hip: one launch for the whole sequence); --host uses the NumPy form
 (utils/track.track_rows_np) and, without --smooth, writes the same bytes.  --track-assign optimal replaces the greedy association by the
-optimal one-to-one assignment of every frame, on the GPU and with --host alike.
+optimal one-to-one assignment of every frame, on the GPU and with --host alike.  --oxts FILE --calib FILE (the
+sequence's oxts/<seq>.txt and calib/<seq>.txt, one oxts line per result file) move the carried cuboids into every frame's camera
+coordinates before they are matched (gpp_track_ego_f64): a parked car keeps its id from a driving camera.
 
     track_results.py result_dir/ tracks.txt --metric dist --threshold 2.0 [--max-age 2] [--min-hits 1] [--smooth] [--host]
-                     [--track-assign greedy|optimal]
+                     [--track-assign greedy|optimal] [--oxts oxts/0000.txt --calib calib/0000.txt]
                      [--labels label_02/0000.txt [--score-metric image] [--score-min-overlap 0.5] [--hota] [--idf1]]
 
 --labels scores the tracks just written against the sequence's label_02 file (CLEAR-MOT; on the GPU unless
@@ -35,6 +37,7 @@ if __name__ == "__main__" and __package__ is None:
 from . import evaluate_tracking
 from ..utils import kitti_eval
 from ..utils import mot_eval
+from ..utils import oxts
 from ..utils import track as track_utils
 
 
@@ -54,10 +57,15 @@ def parse_args(args):
     parser.add_argument('--track-assign', choices=list(track_utils.ASSIGNS), default='greedy',
                         help='greedy: candidates best first (section 4.28).  optimal: the one-to-one assignment of the least total cost '
                              'per frame (section 4.32): a track does not lose its detection to a neighbour that has another.')
+    parser.add_argument('--oxts', default=None, help='The sequence\'s KITTI oxts file, one line per result file: compensate the ego-motion '
+                                                     '(section 4.33).  Needs --calib.')
+    parser.add_argument('--calib', default=None, help='With --oxts: the sequence\'s tracking calibration file (R_rect, Tr_velo_cam, Tr_imu_velo).')
     parser.add_argument('--host', action='store_true', help='The NumPy form instead of the GPU.')
     parser.add_argument('--labels', help='The sequence\'s label_02 file: score the tracks just written and print the CLEAR-MOT table.')
     evaluate_tracking.add_scoring_arguments(parser, 'score-')
     parsed = parser.parse_args(args)
+    if (parsed.oxts is None) != (parsed.calib is None):
+        parser.error('--oxts and --calib go together: both or neither')
     try:
         parsed.option = track_utils.check_option({'metric': parsed.metric, 'threshold': parsed.threshold, 'max_age': parsed.max_age,
                                                   'birth_score': parsed.birth_score, 'smooth': parsed.smooth, 'assign': parsed.track_assign})
@@ -83,7 +91,10 @@ def main(args=None):
     args = parse_args(sys.argv[1:] if args is None else args)
     names, frames = read_sequence(args.result_dir)
     run = track_utils.track_rows_np if args.host else track_utils.track_rows_device
-    rows, ids, hits, state = run(frames, args.option)
+    if args.oxts is None:
+        rows, ids, hits, state = run(frames, args.option)
+    else:
+        rows, ids, hits, state = run(frames, args.option, ego=oxts.records_for(args.oxts, args.calib, len(names)))
     with open(args.tracks_path, 'w') as f:
         for k in range(len(names)):
             f.write(track_utils.tracking_lines(k, rows[k], ids[k], hits[k], args.min_hits))

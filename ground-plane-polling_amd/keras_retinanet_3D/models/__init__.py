@@ -102,7 +102,11 @@ def load_model(filepath, backbone_name='resnet50', convert=False, nms=True, clas
     are consecutive frames of the model's one sequence and a later call continues it; model.reset_tracks() starts a new one,
     model.track_state() reads the state.  There is no default threshold: it depends on the checkpoint and the frame rate; the default
     gains and max_age come from synthetic scenes only.  'assign': 'optimal' launches gpp_track_optimal_f64 instead (section 4.32): the
-    optimal one-to-one assignment of every frame in the place of the greedy pass, all else the same step.  Every other method is unchanged and does not touch the tracker.  FramePipeline and
+    optimal one-to-one assignment of every frame in the place of the greedy pass, all else the same step.  'ego': True (section 4.33): the two
+    methods take ego=records, (B, 16) float64 -- utils.track.ego_records of the camera-from-previous-camera transforms, or
+    utils.oxts.camera_ego from KITTI's oxts and calib files -- and launch gpp_track_ego_f64: the carried cuboids are moved into every
+    frame's camera coordinates before they are matched, so a parked car keeps its id from a driving camera; a missing ego on such a model
+    and a given one on any other are refused.  Every other method is unchanged and does not touch the tracker.  FramePipeline and
     ShardedModel refuse such a model: they reorder or split the frames.
     """
     import os

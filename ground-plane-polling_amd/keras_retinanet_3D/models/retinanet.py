@@ -85,7 +85,8 @@ class RetinaNet3D(object):
             raise ValueError('cuboid_nms={!r} suppresses pose rows: it needs pose=True'.format(cuboid_nms))
         # track=(metric, threshold) or a dict (utils/track.check_option; pose=True only): predict_tracks_on_frames / _on_batch follow the plan
         # with ONE more launch, gpp_track_f64 -- not a plan op: every plan and every other method is what it was.
-        # The images of a call are consecutive frames of the model's one sequence; the state lives in HBM between the calls
+        # The images of a call are consecutive frames of the model's one sequence; the state lives in HBM between the calls.  With
+        # 'ego': True the two methods take the frames' ego records and the launch is gpp_track_ego_f64 (section 4.33)
         self.track = track_utils.check_option(track)
         if self.track is not None and not self.pose:
             raise ValueError('track={!r} associates pose rows: it needs pose=True'.format(track))
@@ -819,7 +820,24 @@ class RetinaNet3D(object):
             self._track_work = torch.empty((hip.track_workspace_bytes(1),), dtype=torch.uint8, device=self.device)
             self._track_params = track_utils.params_of(self.track)
             self._track_optimal = track_utils.is_optimal(self.track)     # 'assign': 'optimal' -> gpp_track_optimal_f64 (section 4.32)
+            self._track_ego_work = None          # 'ego': True -> gpp_track_ego_f64 (section 4.33): (B, workspace), sized with the plan's B
         return self._track_state
+
+    def _track_ego(self, ego, frames, what):
+        """ the `ego` argument of predict_tracks_on_*: None on a model without 'ego', the checked (B, 16) records on a model with it --
+        a missing or a superfluous one is refused before anything is staged """
+        wants = self.track is not None and self.track.get('ego', False)
+        if wants and ego is None:
+            raise hip.GppError("{}: this model compensates ego-motion (track={{..., 'ego': True}}): it needs ego=records, one per frame "
+                               "(utils.track.ego_records, utils.oxts.camera_ego)".format(what))
+        if not wants and ego is not None:
+            raise hip.GppError("{}: ego records were given, but this model was not loaded with track={{..., 'ego': True}}".format(what))
+        if ego is None:
+            return None
+        try:
+            return track_utils.check_ego(ego, frames)
+        except ValueError as e:
+            raise hip.GppError('{}: {}'.format(what, e))
 
     def reset_tracks(self):
         """ start a new sequence: the empty tracker (the next birth gets id 0) """
@@ -829,14 +847,20 @@ class RetinaNet3D(object):
         """ the tracker's state as one utils.track.STATE_DTYPE record (include/gpp.h, gpp_track_state).  One copy (synchronises). """
         return track_utils.read_state(self._track_buffers()[0])[0]
 
-    def fetch_tracks(self, plan, what='predict_tracks_on_batch'):
+    def fetch_tracks(self, plan, what='predict_tracks_on_batch', ego=None):
         """ ((rows, counts, ids, hits)) of the plan's last run: fetch_poses + the tracker's frame steps over the images of the batch, in
         order.  The launch follows the plan (and its cuboid NMS) on the stream and is no plan op; it goes from the current state to a
         second buffer, because _range_event calls the reader a second time on the float32 twin: the model commits by swapping the two
-        only after _answer has returned -- the state advances once per answered call, by the rows that answered it. """
+        only after _answer has returned -- the state advances once per answered call, by the rows that answered it.  ego: the checked
+        (B, 16) records of an 'ego' model (_track_ego): the launch is gpp_track_ego_f64, and the twin's second call takes the same ones. """
         torch = self.torch
         state, nxt = self._track_buffers()
         B, D = int(plan.pose_rows.shape[0]), int(plan.pose_rows.shape[1])
+        work = self._track_work
+        if ego is not None:
+            if self._track_ego_work is None or self._track_ego_work[0] != B:
+                self._track_ego_work = (B, torch.empty((hip.track_ego_workspace_bytes(1, B),), dtype=torch.uint8, device=self.device))
+            work = self._track_ego_work[1]
         smooth = self.track['smooth']
         out = torch.empty((B, D, hip.GPP_POSE_COLS), dtype=torch.float32, device=self.device) if smooth else None
         tags = torch.empty((2, B, D), dtype=torch.int32, device=self.device)
@@ -844,7 +868,7 @@ class RetinaNet3D(object):
         def rows_and_tracks(model, p):
             # (smooth: the plan's rows stay what predict_poses_* reads; otherwise the kernel's bit copy lands where it came from)
             hip.track(p.pose_rows, state, self._track_params, state_out=nxt, out=out if smooth else p.pose_rows, ids=tags[0], hits=tags[1],
-                      workspace=self._track_work, optimal=self._track_optimal)
+                      workspace=work, optimal=self._track_optimal, ego=ego)
             (rows, counts), count = self.read_poses(model, p)
             if smooth:
                 rows = out.cpu().numpy()
@@ -855,27 +879,31 @@ class RetinaNet3D(object):
         self._track_state = [nxt, state]
         return result
 
-    def predict_tracks_on_batch(self, inputs, scales, image_shapes, heights=None):
+    def predict_tracks_on_batch(self, inputs, scales, image_shapes, heights=None, ego=None):
         """ predict_poses_on_batch + the tracker: the images of the call are consecutive frames of the model's one sequence, a later call
         continues it (reset_tracks starts a new one).  Returns (rows (B, 100, 36) float32, counts (B,) int32, ids (B, 100) int32, hits
         (B, 100) int32): ids[b, d] is the identity of row d of image b, -1 for padding rows, rows with a NaN among their cuboid's fields
         and rows below the option's birth_score that matched nothing; hits the frames that identity has been seen in.  With smooth the
-        cuboid's columns of rows that carry an id are the filter's (include/gpp.h, gpp_track_f64). """
+        cuboid's columns of rows that carry an id are the filter's (include/gpp.h, gpp_track_f64).  ego: on a model loaded with
+        track={..., 'ego': True} the (B, 16) records of the frames (utils.track.ego_records; include/gpp.h, gpp_track_ego_f64) -- the
+        first relates to the last frame of the call before; on any other model it must be None. """
         self._require_pose()
         self._track_buffers()
+        ego = self._track_ego(ego, len(inputs[0]), 'predict_tracks_on_batch')
         plan = self.stage_inputs(inputs) if heights is None else self.stage_canvas(inputs, heights)
         self.put_frame_info(plan, scales, image_shapes)
         self.run_plan(plan)
-        return self.fetch_tracks(plan)
+        return self.fetch_tracks(plan, ego=ego)
 
-    def predict_tracks_on_frames(self, frames_u8, P_inv, planes):
+    def predict_tracks_on_frames(self, frames_u8, P_inv, planes, ego=None):
         """ predict_tracks_on_batch for raw uint8 BGR frames (predict_on_frames): returns ((rows, counts, ids, hits), scale) """
         self._require_pose()
         self._track_buffers()
+        ego = self._track_ego(ego, len(frames_u8), 'predict_tracks_on_frames')
         plan, scale = self.stage_frames(frames_u8, P_inv, planes)
         self.put_frame_info(plan, scale, self._frame_shapes(frames_u8))
         self.run_plan(plan)
-        return self.fetch_tracks(plan, 'predict_tracks_on_frames'), scale
+        return self.fetch_tracks(plan, 'predict_tracks_on_frames', ego), scale
 
     def score_poses_on_frames(self, frames_u8, P_inv, planes, labels):
         """ predict_poses_on_frames + the overlaps of KITTI's object benchmark (csrc/kitti_eval.hip) without the

@@ -2,7 +2,9 @@
 Tracking of cuboids across frames: the pose rows of one frame are associated greedily with the cuboids carried over from the frames
 before, and every carried cuboid is a fixed-gain (alpha-beta) filter -- DESIGN.md section 4.28 is the specification, include/gpp.h
 (gpp_track_f64, gpp_track_state) the contract.  With 'assign': 'optimal' the association is the optimal one-to-one assignment of the
-frame instead (gpp_track_optimal_f64); everything else is the same step.  An identity per car that persists from
+frame instead (gpp_track_optimal_f64); everything else is the same step.  With `ego` records (DESIGN.md section 4.33,
+gpp_track_ego_f64) the carried cuboids are moved into every frame's camera coordinates before they are matched: the camera of a driving car
+moves, and a parked car must not.  An identity per car that persists from
 frame to frame, and optionally a pose that does not jump by the detector's depth jitter.  There is no default threshold: it depends on
 the checkpoint and the frame rate.
 
@@ -34,6 +36,7 @@ SCALE = mot_eval.SCALE                      # 2^20 (GPP_MOT_SCALE_BITS): the cel
 PI = float(np.pi)
 TWO_PI = 2.0 * PI
 TRACKING_FORMAT = '%d %d ' + gpp_utils.KITTI_FORMAT
+EGO_FIELDS = 16                             # GPP_TRACK_EGO_FIELDS: R row-major (9), t (3), dyaw (1), three words that are 0
 
 
 def metric_code(metric):
@@ -44,14 +47,15 @@ def metric_code(metric):
 
 def check_option(option):
     """ the `track` option of load_model / RetinaNet3D: None, a pair (metric, threshold), or a dict with 'metric' and 'threshold' and
-    optionally 'max_age', 'gains' (a, b, c), 'birth_score', 'smooth', 'assign' ('greedy' | 'optimal') -> None or the complete dict; it
-    carries 'assign' only when that is 'optimal' """
+    optionally 'max_age', 'gains' (a, b, c), 'birth_score', 'smooth', 'assign' ('greedy' | 'optimal'), 'ego' (True | False: the model
+    takes ego records, section 4.33) -> None or the complete dict; it carries 'assign' only when that is 'optimal' and 'ego' only when
+    that is true """
     if option is None:
         return None
     if isinstance(option, dict):
-        unknown = sorted(set(option) - {'metric', 'threshold', 'assign'} - set(DEFAULTS))
+        unknown = sorted(set(option) - {'metric', 'threshold', 'assign', 'ego'} - set(DEFAULTS))
         if unknown or 'metric' not in option or 'threshold' not in option:
-            raise ValueError("track: a dict needs 'metric' and 'threshold' and may have {}; got {!r}".format(sorted(DEFAULTS) + ['assign'], option))
+            raise ValueError("track: a dict needs 'metric' and 'threshold' and may have {}; got {!r}".format(sorted(DEFAULTS) + ['assign', 'ego'], option))
         opt = dict(DEFAULTS, **option)
     else:
         try:
@@ -81,8 +85,13 @@ def check_option(option):
         raise ValueError("track: assign must be 'greedy' or 'optimal', got {!r}".format(assign))
     out = {'metric': opt['metric'], 'threshold': thr, 'max_age': int(opt['max_age']), 'gains': (a, b, c), 'birth_score': birth,
            'smooth': bool(opt['smooth'])}
+    ego = opt.get('ego', False)
+    if not isinstance(ego, (bool, np.bool_)):
+        raise ValueError("track: ego must be True or False, got {!r}".format(ego))
     if assign == 'optimal':
         out['assign'] = assign
+    if ego:
+        out['ego'] = True
     return out
 
 
@@ -120,6 +129,33 @@ def wrap(a):
     a = np.where(a < 0.0, a + TWO_PI, a)
     a = np.where(a >= TWO_PI, a - TWO_PI, a)
     return np.where(a >= PI, a - TWO_PI, a)
+
+
+def ego_records(poses):
+    """ (N, 4, 4) or (N, 3, 4) transforms -- a point p in the previous frame's camera coordinates lies at R p + t in this frame's -- ->
+    the (N, 16) float64 records of gpp_track_ego_f64: R row-major, t, dyaw = atan2(R02 - R20, R00 + R22) (exact for a rotation about
+    the camera's Y axis, the nearest yaw otherwise), three zeros """
+    poses = np.asarray(poses, np.float64)
+    if poses.ndim != 3 or poses.shape[1] not in (3, 4) or poses.shape[2] != 4:
+        raise ValueError('ego_records: poses must be (N, 4, 4) or (N, 3, 4), got {}'.format(poses.shape))
+    out = np.zeros((poses.shape[0], EGO_FIELDS))
+    out[:, 0:9] = poses[:, :3, :3].reshape(-1, 9)
+    out[:, 9:12] = poses[:, :3, 3]
+    out[:, 12] = np.arctan2(poses[:, 0, 2] - poses[:, 2, 0], poses[:, 0, 0] + poses[:, 2, 2])
+    return check_ego(out, poses.shape[0])
+
+
+def check_ego(ego, N):
+    """ the records of N frames -> a C-contiguous (N, 16) float64 array; ValueError for another shape, a value that is not finite or a
+    padding word that is not 0 (what gpp_track_ego_f64 refuses with GPP_ERR_BAD_ARG) """
+    ego = np.ascontiguousarray(ego, np.float64)
+    if ego.shape != (int(N), EGO_FIELDS):
+        raise ValueError('track: ego must be ({}, {}) -- one record per frame --, got {}'.format(int(N), EGO_FIELDS, ego.shape))
+    if not np.isfinite(ego).all():
+        raise ValueError('track: an ego record holds a value that is not finite (frame {})'.format(int(np.argwhere(~np.isfinite(ego))[0][0])))
+    if (ego[:, 13:] != 0.0).any():
+        raise ValueError('track: the last three words of an ego record must be 0 (frame {})'.format(int(np.argwhere(ego[:, 13:] != 0.0)[0][0])))
+    return ego
 
 
 def candidate_keys(box, occupied, rows, valid, metric, threshold):
@@ -202,9 +238,10 @@ def optimal(keys, occupied, valid, metric, threshold):
     return [(int(ts[i]), int(ds[col[i]])) for i in range(ts.size) if col[i] < ds.size and cost[i, col[i]] < SCALE]
 
 
-def step_np(state, rows, opt, keys_out=None):
+def step_np(state, rows, opt, keys_out=None, ego=None):
     """ one frame step on `state` (one writable STATE_DTYPE record, changed in place) -> (rows_out (D, 36) float32, ids (D,) int32,
-    hits (D,) int32).  keys_out: a list that receives the frame's candidate table (the tests' margins) """
+    hits (D,) int32).  keys_out: a list that receives the frame's candidate table (the tests' margins); ego: the frame's record (16,),
+    checked by the caller (check_ego) -- step 1b of section 4.33 """
     rows = np.asarray(rows, np.float32).reshape(-1, POSE_COLS)
     D = rows.shape[0]
     if D > MAX_DETECTIONS:
@@ -213,6 +250,16 @@ def step_np(state, rows, opt, keys_out=None):
     box, id1, hits, misses, score = state['box'], state['id1'], state['hits'], state['misses'], state['score']
     occupied = id1 != 0
     box[0:3, occupied] = box[0:3, occupied] + box[7:10, occupied]                                  # 1 predict
+    if ego is not None:                                                                             # 1b ego
+        # the products are written out, one NumPy operation per float64 operation of the rule and in its association: `@`, dot and
+        # einsum go through BLAS, which may fuse a multiply with an add or sum in another order
+        e = [float(v) for v in np.asarray(ego, np.float64).reshape(EGO_FIELDS)]
+        x, y, z = box[0, occupied].copy(), box[1, occupied].copy(), box[2, occupied].copy()
+        vx, vy, vz = box[7, occupied].copy(), box[8, occupied].copy(), box[9, occupied].copy()
+        for k in range(3):
+            box[k, occupied] = ((e[3 * k] * x + e[3 * k + 1] * y) + e[3 * k + 2] * z) + e[9 + k]
+            box[7 + k, occupied] = (e[3 * k] * vx + e[3 * k + 1] * vy) + e[3 * k + 2] * vz
+        box[3, occupied] = wrap(box[3, occupied] + e[12])
     live = rows[:, 14] >= 0.0                                                                       # 2 rows
     valid = live & ~np.isnan(rows[:, ROW_COLS]).any(axis=1)
     keys = candidate_keys(box, occupied, rows, valid, opt['metric'], opt['threshold'])              # 3 candidates
@@ -270,18 +317,21 @@ def step_np(state, rows, opt, keys_out=None):
     return out, ids, out_hits
 
 
-def track_rows_np(rows_per_frame, options, state=None, keys_out=None):
+def track_rows_np(rows_per_frame, options, state=None, keys_out=None, ego=None):
     """ the NumPy form: rows_per_frame (N, D, 36) float32 (or a list of (D_f, 36) arrays), the consecutive frames of one sequence; options:
     what check_option takes; state: one STATE_DTYPE record (None: the empty tracker; it is not changed) -> (rows_out, ids, hits, state):
-    arrays (N, D, 36), (N, D), (N, D) (lists for a list) and the new state.  As the device form, N * D == 0 leaves the state as it is. """
+    arrays (N, D, 36), (N, D), (N, D) (lists for a list) and the new state.  As the device form, N * D == 0 leaves the state as it is.
+    ego: None, or the (N, 16) records of the frames (ego_records; section 4.33); the first relates to the last frame `state` has seen. """
     opt = check_option(options)
+    if ego is not None:
+        ego = check_ego(ego, len(rows_per_frame))
     state = empty_state() if state is None else np.array(state, STATE_DTYPE).reshape(())
     state = state.copy()
     as_list = isinstance(rows_per_frame, (list, tuple))
     frames = [np.asarray(r, np.float32).reshape(-1, POSE_COLS) for r in rows_per_frame] if as_list else np.asarray(rows_per_frame, np.float32)
     if not as_list and frames.size == 0:
         return frames.copy(), np.zeros(frames.shape[:2], np.int32), np.zeros(frames.shape[:2], np.int32), state
-    res = [step_np(state, r, opt, keys_out) for r in frames]
+    res = [step_np(state, r, opt, keys_out, None if ego is None else ego[f]) for f, r in enumerate(frames)]
     if as_list:
         return [x[0] for x in res], [x[1] for x in res], [x[2] for x in res], state
     return np.stack([x[0] for x in res]), np.stack([x[1] for x in res]), np.stack([x[2] for x in res]), state
@@ -309,26 +359,29 @@ def state_tensor(state, device, S=1):
     return torch.as_tensor(np.ascontiguousarray(host).view(np.uint8).reshape(host.shape[0], STATE_DTYPE.itemsize).copy()).to(device)
 
 
-def track_rows_device(rows, options, state=None, seq_start=None, out=None, state_out=None):
+def track_rows_device(rows, options, state=None, seq_start=None, out=None, state_out=None, ego=None):
     """ csrc/track.hip (gpp_track_f64, or gpp_track_optimal_f64 for 'assign': 'optimal'): rows (N, D, 36), the frames of S sequences
     (seq_start (S + 1,), default one sequence of all frames): a NumPy array
     -> NumPy results and STATE_DTYPE state(s), or a float32 device tensor -> device tensors with the state as (S, bytes) uint8 (no
     synchronisation; read_state reads it).  state: None (empty), STATE_DTYPE record(s) or such a tensor.  out / state_out (tensors only):
-    where the rows and the state go -- `rows` and `state` themselves are allowed.
+    where the rows and the state go -- `rows` and `state` themselves are allowed.  ego: None, or the (N, 16) HOST records of the frames
+    (section 4.33): gpp_track_ego_f64 with the option's assignment.
     Returns (rows_out, ids (N, D) int32, hits (N, D) int32, state).  D <= 128. """
     import torch
     from ..backend import hip
     params, best = params_of(options), is_optimal(options)
     S = 1 if seq_start is None else len(seq_start) - 1
+    if ego is not None:
+        ego = check_ego(ego, len(rows))
     if isinstance(rows, torch.Tensor):
         if rows.dim() != 3 or not rows.is_contiguous():
             raise ValueError('track_rows_device: rows must be a dense (N, D, {}) tensor, got {}'.format(POSE_COLS, tuple(rows.shape)))
-        return hip.track(rows, state_tensor(state, rows.device, S), params, seq_start, state_out=state_out, out=out, optimal=best)
+        return hip.track(rows, state_tensor(state, rows.device, S), params, seq_start, state_out=state_out, out=out, optimal=best, ego=ego)
     host = np.ascontiguousarray(rows, np.float32)
     if host.ndim != 3 or host.shape[2] != POSE_COLS:
         raise ValueError('track_rows_device: rows must be (N, D, {}), got {}'.format(POSE_COLS, host.shape))
     dev = hip.require_device()
-    res = hip.track(torch.as_tensor(host).to(dev), state_tensor(state, dev, S), params, seq_start, optimal=best)
+    res = hip.track(torch.as_tensor(host).to(dev), state_tensor(state, dev, S), params, seq_start, optimal=best, ego=ego)
     new = read_state(res[3])
     return res[0].cpu().numpy(), res[1].cpu().numpy(), res[2].cpu().numpy(), (new[0] if seq_start is None else new)
 

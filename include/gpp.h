@@ -876,6 +876,42 @@ int gpp_track_optimal_f64(const float* rows_in, int N, int D, const int32_t* seq
                           void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Tracking with EGO-MOTION compensation (csrc/track.hip, either kernel with a step 1b; DESIGN.md section 4.33 is the specification,
+ * utils/track.py with `ego` the host form, utils/oxts.py makes the records from KITTI's oxts and calib files).  The camera of a driving
+ * car moves: without this step a parked car leaves its prediction by the ego displacement of every frame.  The state's layout,
+ * gpp_track_params, every error and the N * D == 0 / S == 0 behaviour are gpp_track_f64's; steps 2 - 8 are those of the chosen
+ * assignment, operation for operation.
+ *
+ *   ego         (N, GPP_TRACK_EGO_FIELDS) float64 on the HOST, like seq_start: one record per frame of the call -- R row-major (9),
+ *               t (3), dyaw (1), then three words that must be 0.  A point p in the camera coordinates of the frame BEFORE f in its
+ *               sequence lies at R p + t in the camera coordinates of frame f.  A call may continue an earlier one: the record of a
+ *               call's first frame relates to the last frame of the call before.  With an empty tracker a record has no effect.
+ *   assign      GPP_TRACK_ASSIGN_GREEDY: step 4 of gpp_track_f64; GPP_TRACK_ASSIGN_OPTIMAL: step 4 of gpp_track_optimal_f64.
+ *   frame step  step 1 becomes, for every occupied slot, in this order:
+ *     1a predict   as gpp_track_f64: x += vx, y += vy, z += vz.
+ *     1b ego       x' = ((R00 x + R01 y) + R02 z) + t0, y' and z' likewise from rows 1 and 2 of R, all three from the old x y z;
+ *                  vx' = (R00 vx + R01 vy) + R02 vz, vy' and vz' likewise; r_y' = wrap(r_y + dyaw), the wrap of gpp_pose_f32.  Every
+ *                  multiply and every add is one separate float64 operation in exactly this association.  h w l are untouched.
+ *               Velocity thereby means the object's own displacement per frame in the current camera's axes: a parked car has v = 0.
+ *               dyaw is GIVEN, not derived from R: the host form derives it as atan2(R02 - R20, R00 + R22), which is exact for a
+ *               rotation about the camera's Y axis and the nearest yaw otherwise.  Pitch and roll move positions and velocities through
+ *               the full R; r_y only takes the yaw.  Smoothed rows are in the frame's own camera coordinates, as before.
+ *   workspace   gpp_track_ego_workspace_bytes(S, N) bytes on the device, 8-byte aligned: gpp_track_workspace_bytes(S) and behind them
+ *               the records' copy, 128 bytes per frame of the call (the entry point copies `ego` there as it copies seq_start).
+ *
+ *   GPP_ERR_BAD_ARG, nothing launched and nothing written, beyond gpp_track_f64's: a null `ego` when N > 0; an unknown `assign`; a
+ *   non-finite value among the 13 words of the record of any frame inside a sequence; a padding word that is not 0.  The records are
+ *   checked on the host, so that no NaN enters a slot through them.  Frames outside every sequence are neither checked nor read.
+ * ---------------------------------------------------------------------------------------- */
+#define GPP_TRACK_EGO_FIELDS 16
+#define GPP_TRACK_ASSIGN_GREEDY 0
+#define GPP_TRACK_ASSIGN_OPTIMAL 1
+int gpp_track_ego_workspace_bytes(int S, int N, size_t* bytes);
+int gpp_track_ego_f64(const float* rows_in, int N, int D, const int32_t* seq_start, int S, const void* state_in, void* state_out,
+                      const gpp_track_params* params, const double* ego, int assign, float* rows_out, int32_t* track_ids,
+                      int32_t* track_hits, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CLEAR-MOT scoring of tracks on the device (csrc/mot_eval.hip; DESIGN.md section 4.29 is the specification, a restatement of the KITTI
  * tracking devkit's CLEAR-MOT -- parity with the devkit itself is UNPINNED; utils/mot_eval.py is the host form): per frame the OPTIMAL
  * one-to-one assignment of the tracker's rows to the labels (the Hungarian method, shortest augmenting paths, exact integers), then per
