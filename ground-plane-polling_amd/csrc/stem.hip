@@ -215,6 +215,10 @@ extern "C" int gpp_stem_pack_weights_f16x3(const float* host_weight_147x64, void
         for (int k = 0; k < 147; ++k) amax = fmaxf(amax, fabsf(host_weight_147x64[k * 64 + n]));
         int e = 0;
         if (amax > 0.0f) { (void)frexpf(amax, &e); e = 14 - e; }          // amax = m * 2^(14 - e_new), m in [0.5, 1) -> amax * 2^e in [2^13, 2^14)
+        // bounded as layers/conv.py::weight_scale bounds its exponent, to the range in which 2^e and 2^-e are both normal float32 numbers:
+        // a channel whose largest weight is below 2^-113 (a dead BN gamma) keeps a finite scale and lands below 2^13 (e was up to 162:
+        // 2^e = inf, the halves inf and NaN).  e >= -114 for every float32 amax, so the lower bound never acts.
+        e = e > 126 ? 126 : (e < -126 ? -126 : e);
         const float sc = ldexpf(1.0f, e);
         out_scale[n] = ldexpf(1.0f, -e);
         for (int k = 0; k < MW_PITCH; ++k) {

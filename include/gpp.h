@@ -421,7 +421,8 @@ int gpp_stem_pool_fused_mfma(const float* in, const void* packed_weight_f16, con
 /* The stem of the float32-storage "x3" types (GPP_F16X3 / GPP_BF16X3 models): conv1 + bn_conv1 + ReLU on the matrix pipe at
  * (almost) float32 precision -- input pixels and weights split into two IEEE halves each, three matrix products per float32 product,
  * float32 output (B, Ho, Wo, 64).  packed_weight_x3 = what the HOST-side helper gpp_stem_pack_weights_f16x3 writes from the folded
- * [147][64] kernel: 2 * 64 * 232 halfs + 64 float32 (59 648 bytes). */
+ * [147][64] kernel: 2 * 64 * 232 halfs + 64 float32 (59 648 bytes).
+ * The per-channel exponent is bounded to +-126 (scale and out_scale stay normal float32): a channel below 2^-113 packs finite, at fewer bits. */
 int gpp_stem_pack_weights_f16x3(const float* host_weight_147x64, void* host_packed, size_t packed_bytes);
 int gpp_stem_conv7x7_bn_relu_x3(const float* in, const void* packed_weight_x3, const float* bias, float* out,
                                 int B, int H, int W, void* stream);
