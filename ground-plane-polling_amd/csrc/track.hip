@@ -46,6 +46,17 @@
 //                  by the frame's ego record.  The entry point has checked the records on the host and copied them into the workspace
 //                  behind everything else; every thread takes the frame's 13 words from there (the address is uniform) and a slot's
 //                  thread uses them.  No barrier, no loop and no LDS word more; the <*, false> instantiations have none of it.
+//
+//   track_kernel<*, *, true>   gpp_track_kf_f64: any of the four with a Kalman filter on (x, z, vx, vz) of every
+//                  slot.  Thread t keeps the ten covariance words of slot t in registers from the call's first frame to its last (cov_in
+//                  is read and cov_out written by the slot's own thread only: the two may be one buffer).  LDS holds what phases 3 and 5
+//                  read of OTHER threads: the predicted A of every slot (3 KiB) and the noise R of every row (3 KiB), declared on their
+//                  own beside everything else -- 89 536 bytes declared in the greedy forms (83 392 without the filter), 154 784 of
+//                  163 840 in the optimal ones (148 640 without); none of the four uses scratch (193 - 195 VGPRs against 169).  A birth is
+//                  written by the row's thread, the covariance lives with the slot's: the row leaves its number in s_mrow[slot] (idle
+//                  behind phase 5) and the slot's thread takes R from there behind the barrier the births end with.  No barrier more
+//                  than before, and none inside a divergent branch; no loop more.  kEgo here means "records were given".  The
+//                  <*, *, false> instantiations have none of it (if constexpr).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -76,6 +87,36 @@ static_assert(sizeof(gpp_track_state) % 8 == 0, "states are laid out back to bac
 static_assert(kSide <= 2 * gpp_mot::kWave, "assign_rows: a lane owns two columns");
 
 enum { FX = 0, FY, FZ, FRY, FH, FW, FL, FVX, FVY, FVZ };
+enum { AXX = 0, AXZ, AZZ, BXX, BXZ, BZX, BZZ, CXX, CXZ, CZZ };       // gpp_track_cov's fields
+constexpr int kCov = GPP_TRACK_COV_FIELDS;
+static_assert(sizeof(gpp_track_cov) == (size_t)kCov * kSlots * sizeof(double), "field-major, back to back");
+
+// section 4.34, what the Kalman instantiations take beyond the others
+struct kf_args {
+    const gpp_track_cov* cov_in;
+    gpp_track_cov* cov_out;
+    gpp_track_kf_params p;
+};
+
+// section 4.34, "ego": X -> Rg X Rg^T for a general 2 x 2 block (xx xz zx zz), every product and sum separate
+__device__ __forceinline__ void turn(double g00, double g01, double g10, double g11, double xx, double xz, double zx, double zz,
+                                     double& oxx, double& oxz, double& ozx, double& ozz)
+{
+    const double mxx = (g00 * xx) + (g01 * zx), mxz = (g00 * xz) + (g01 * zz);
+    const double mzx = (g10 * xx) + (g11 * zx), mzz = (g10 * xz) + (g11 * zz);
+    oxx = (mxx * g00) + (mxz * g01);
+    oxz = (mxx * g10) + (mxz * g11);
+    ozx = (mzx * g00) + (mzz * g01);
+    ozz = (mzx * g10) + (mzz * g11);
+}
+
+// section 4.34, "births": A = R of the row, B = 0, C = birth_speed^2 I
+__device__ __forceinline__ void born_cov(double (&P)[kCov], double rxx, double rxz, double rzz, double speed)
+{
+    P[AXX] = rxx; P[AXZ] = rxz; P[AZZ] = rzz;
+    P[BXX] = 0.0; P[BXZ] = 0.0; P[BZX] = 0.0; P[BZZ] = 0.0;
+    P[CXX] = speed * speed; P[CXZ] = 0.0; P[CZZ] = speed * speed;
+}
 
 // pose.hip's wrap: into [-pi, pi)
 __device__ __forceinline__ double wrap(double a)
@@ -103,11 +144,11 @@ __device__ __forceinline__ int block_rank(bool flag, int tid, int* s_wave, int& 
 size_t seq_bytes(int S) { return ((size_t)(S + 1) * sizeof(int32_t) + kSeqBytes - 1) / kSeqBytes * kSeqBytes; }
 size_t plain_bytes(int S) { return seq_bytes(S) + (size_t)S * 2 * kSlots * kMaxD * sizeof(double); }     // gpp_track_workspace_bytes
 
-template <bool kOptimal, bool kEgo>
+template <bool kOptimal, bool kEgo, bool kKf>
 __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, int N, int D, const int32_t* __restrict__ seq_start,
                                                          const gpp_track_state* states_in, gpp_track_state* states_out,
                                                          gpp_track_params prm, float* rows_out, int32_t* track_ids, int32_t* track_hits,
-                                                         double* tables, const double* __restrict__ ego)
+                                                         double* tables, const double* __restrict__ ego, kf_args kfa)
 {
     __shared__ double s_x[2][rot_iou::kMaxVerts][kThreads];
     __shared__ double s_z[2][rot_iou::kMaxVerts][kThreads];
@@ -128,6 +169,14 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
         __shared__ int32_t s_matrix[kSide * kSide];
         s_cost = s_matrix;
     }
+    double (*s_A)[kSlots] = nullptr;                     // section 4.34: the predicted Axx Axz Azz of every slot ...
+    double (*s_R)[kMaxD] = nullptr;                      // ... and Rxx Rxz Rzz of every live, non-blind row
+    if constexpr (kKf) {
+        __shared__ double s_cov_a[3][kSlots];
+        __shared__ double s_noise[3][kMaxD];
+        s_A = s_cov_a;
+        s_R = s_noise;
+    }
 
     const int seq = blockIdx.x, tid = threadIdx.x;
     int f0 = seq_start[seq], f1 = seq_start[seq + 1];
@@ -139,8 +188,18 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
         tab = tables + (size_t)seq * 2 * kSlots * kMaxD;
         tab_dt = tab + kSlots * kMaxD;
     }
-    const bool iou = prm.metric != GPP_TRACK_DIST;
+    bool iou = prm.metric != GPP_TRACK_DIST;
+    bool maha = false;
+    if constexpr (kKf) {
+        maha = prm.metric == GPP_TRACK_MAHA;
+        iou = iou && !maha;
+    }
     const double thr2 = prm.threshold * prm.threshold;
+    double P[kCov];                                      // (Kalman) the slot's covariance, here for the whole call
+    if constexpr (kKf) {
+#pragma unroll
+        for (int k = 0; k < kCov; ++k) P[k] = kfa.cov_in[seq].p[k][tid];
+    }
 
     // ---- the state into LDS, all of it before anything is written: states_out may be states_in
     {
@@ -174,6 +233,19 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
                         r_rad[tid] = sqrt(hl * hl + hw * hw);
                         r_area[tid] = l * w;
                     }
+                    if constexpr (kKf) {
+                        if (!(flag & 2)) {               // the row's noise: along and across its viewing ray
+                            const double rho = sqrt((x * x) + (z * z));
+                            double ux = 0.0, uz = 1.0;
+                            if (rho != 0.0) { ux = x / rho; uz = z / rho; }
+                            const double sr = kfa.p.radial0 + (kfa.p.radial1 * rho), sg = kfa.p.tangential0 + (kfa.p.tangential1 * rho);
+                            const double vr = sr * sr, vt = sg * sg;
+                            const double dv = vr - vt;
+                            s_R[0][tid] = vt + (dv * (ux * ux));
+                            s_R[1][tid] = dv * (ux * uz);
+                            s_R[2][tid] = vt + (dv * (uz * uz));
+                        }
+                    }
                 }
             }
             r_flag[tid] = flag;
@@ -201,6 +273,22 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
                     st.box[FRY][tid] = wrap(st.box[FRY][tid] + e[12]);
                 }
                 st.box[FX][tid] = x; st.box[FY][tid] = y; st.box[FZ][tid] = z;
+                if constexpr (kKf) {                     // 1: P = F P F^T + Q, all from the old values
+                    const double axx = ((P[AXX] + (P[BXX] + P[BXX])) + P[CXX]) + kfa.p.q_pos;
+                    const double axz = (P[AXZ] + (P[BXZ] + P[BZX])) + P[CXZ];
+                    const double azz = ((P[AZZ] + (P[BZZ] + P[BZZ])) + P[CZZ]) + kfa.p.q_pos;
+                    const double bxx = P[BXX] + P[CXX], bxz = P[BXZ] + P[CXZ], bzx = P[BZX] + P[CXZ], bzz = P[BZZ] + P[CZZ];
+                    P[AXX] = axx; P[AXZ] = axz; P[AZZ] = azz;
+                    P[BXX] = bxx; P[BXZ] = bxz; P[BZX] = bzx; P[BZZ] = bzz;
+                    P[CXX] = P[CXX] + kfa.p.q_vel; P[CZZ] = P[CZZ] + kfa.p.q_vel;
+                    if constexpr (kEgo) {                // 1b: the ground part of the record's rotation on every block
+                        double unused;                   // (the lower triangle of a symmetric block is not kept)
+                        turn(e[0], e[2], e[6], e[8], P[AXX], P[AXZ], P[AXZ], P[AZZ], P[AXX], P[AXZ], unused, P[AZZ]);
+                        turn(e[0], e[2], e[6], e[8], P[BXX], P[BXZ], P[BZX], P[BZZ], P[BXX], P[BXZ], P[BZX], P[BZZ]);
+                        turn(e[0], e[2], e[6], e[8], P[CXX], P[CXZ], P[CXZ], P[CZZ], P[CXX], P[CXZ], unused, P[CZZ]);
+                    }
+                    s_A[0][tid] = P[AXX]; s_A[1][tid] = P[AXZ]; s_A[2][tid] = P[AZZ];
+                }
                 if (iou) {
                     const double ry = st.box[FRY][tid], l = st.box[FL][tid], w = st.box[FW][tid];
                     const double c = cos(ry), s = sin(ry), hl = l / 2.0, hw = w / 2.0;
@@ -245,8 +333,17 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
             for (int p = tid; p < pairs; p += kThreads) {
                 const int t = s_tlist[p / nR], d = s_rlist[p % nR];
                 const double dx = r_f[FX][d] - st.box[FX][t], dz = r_f[FZ][d] - st.box[FZ][t];
-                const double q = dx * dx + dz * dz;
-                if (q < thr2) {
+                double q = dx * dx + dz * dz;
+                bool cand = q < thr2;
+                if constexpr (kKf) {
+                    if (maha) {                          // q is the squared Mahalanobis distance under S = A + R
+                        const double sxx = s_A[0][t] + s_R[0][d], sxz = s_A[1][t] + s_R[1][d], szz = s_A[2][t] + s_R[2][d];
+                        const double det = (sxx * szz) - (sxz * sxz);
+                        q = ((((szz * dx) * dx) - ((2.0 * (sxz * dx)) * dz)) + ((sxx * dz) * dz)) / det;
+                        cand = det > 0.0 && q < thr2;
+                    }
+                }
+                if (cand) {
                     if constexpr (kOptimal) {
                         const double r = q / thr2;
                         const double x = r * 1048576.0;
@@ -390,8 +487,44 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
         if (st.id1[tid] != 0) {
             const int d = s_mrow[tid];
             if (d >= 0) {
+                bool kalman = false;
+                if constexpr (kKf) {
+                    const double rxx = s_R[0][d], rxz = s_R[1][d], rzz = s_R[2][d];
+                    const double sxx = P[AXX] + rxx, sxz = P[AXZ] + rxz, szz = P[AZZ] + rzz;
+                    const double det = (sxx * szz) - (sxz * sxz);
+                    kalman = det > 0.0;
+                    if (kalman) {
+                        const double px = st.box[FX][tid], pz = st.box[FZ][tid];
+                        const double dx = r_f[FX][d] - px, dz = r_f[FZ][d] - pz;
+                        const double ixx = szz / det, ixz = -(sxz / det), izz = sxx / det;
+                        const double kxx = (P[AXX] * ixx) + (P[AXZ] * ixz), kxz = (P[AXX] * ixz) + (P[AXZ] * izz);
+                        const double kzx = (P[AXZ] * ixx) + (P[AZZ] * ixz), kzz = (P[AXZ] * ixz) + (P[AZZ] * izz);
+                        const double lxx = (P[BXX] * ixx) + (P[BZX] * ixz), lxz = (P[BXX] * ixz) + (P[BZX] * izz);
+                        const double lzx = (P[BXZ] * ixx) + (P[BZZ] * ixz), lzz = (P[BXZ] * ixz) + (P[BZZ] * izz);
+                        st.box[FX][tid] = px + ((kxx * dx) + (kxz * dz));
+                        st.box[FZ][tid] = pz + ((kzx * dx) + (kzz * dz));
+                        st.box[FVX][tid] = st.box[FVX][tid] + ((lxx * dx) + (lxz * dz));
+                        st.box[FVZ][tid] = st.box[FVZ][tid] + ((lzx * dx) + (lzz * dz));
+                        const double axx = P[AXX] - ((kxx * P[AXX]) + (kxz * P[AXZ]));
+                        const double axz = P[AXZ] - ((kxx * P[AXZ]) + (kxz * P[AZZ]));
+                        const double azz = P[AZZ] - ((kzx * P[AXZ]) + (kzz * P[AZZ]));
+                        const double bxx = P[BXX] - ((kxx * P[BXX]) + (kxz * P[BZX]));
+                        const double bxz = P[BXZ] - ((kxx * P[BXZ]) + (kxz * P[BZZ]));
+                        const double bzx = P[BZX] - ((kzx * P[BXX]) + (kzz * P[BZX]));
+                        const double bzz = P[BZZ] - ((kzx * P[BXZ]) + (kzz * P[BZZ]));
+                        const double cxx = P[CXX] - ((lxx * P[BXX]) + (lxz * P[BZX]));
+                        const double cxz = P[CXZ] - ((lxx * P[BXZ]) + (lxz * P[BZZ]));
+                        const double czz = P[CZZ] - ((lzx * P[BXZ]) + (lzz * P[BZZ]));
+                        P[AXX] = axx; P[AXZ] = axz; P[AZZ] = azz;
+                        P[BXX] = bxx; P[BXZ] = bxz; P[BZX] = bzx; P[BZZ] = bzz;
+                        P[CXX] = cxx; P[CXZ] = cxz; P[CZZ] = czz;
+                    } else {
+                        born_cov(P, rxx, rxz, rzz, kfa.p.birth_speed);
+                    }
+                }
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
+                    if (kalman && k != 1) continue;      // (Kalman) x z vx vz are done; y and vy keep the fixed gains
                     const double pred = st.box[FX + k][tid];
                     const double r = r_f[FX + k][d] - pred;
                     st.box[FX + k][tid] = pred + prm.gain_a * r;
@@ -418,6 +551,10 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
                     st.id1[tid] = 0; st.hits[tid] = 0; st.misses[tid] = 0; st.score[tid] = 0.0f;
 #pragma unroll
                     for (int k = 0; k < GPP_TRACK_FIELDS; ++k) st.box[k][tid] = 0.0;
+                    if constexpr (kKf) {
+#pragma unroll
+                        for (int k = 0; k < kCov; ++k) P[k] = 0.0;
+                    }
                 }
             }
         }
@@ -440,8 +577,15 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
                 for (int k = 0; k < 7; ++k) st.box[k][t] = r_f[k][tid];
                 st.box[FVX][t] = 0.0; st.box[FVY][t] = 0.0; st.box[FVZ][t] = 0.0;
                 r_slot[tid] = (int16_t)t;
+                if constexpr (kKf) s_mrow[t] = (int16_t)tid;         // (idle behind phase 5: the slot's thread finds its row here)
             }
             __syncthreads();                             // (everyone has read next_id)
+            if constexpr (kKf) {
+                if (is_free && st.id1[tid] != 0) {       // born into this slot: the covariance lives with the slot's thread
+                    const int d = s_mrow[tid];
+                    born_cov(P, s_R[0][d], s_R[1][d], s_R[2][d], kfa.p.birth_speed);
+                }
+            }
             if (tid == 0) {
                 st.next_id = next_id + (n_born < n_free ? n_born : n_free);
                 st.dropped += n_born > n_free ? n_born - n_free : 0;
@@ -477,6 +621,10 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
         uint32_t* to = (uint32_t*)(states_out + seq);
         for (int k = tid; k < (int)(sizeof(gpp_track_state) / 4); k += kThreads) to[k] = from[k];
     }
+    if constexpr (kKf) {
+#pragma unroll
+        for (int k = 0; k < kCov; ++k) kfa.cov_out[seq].p[k][tid] = P[k];
+    }
 }
 
 bool unit(double v, bool open_low) { return (open_low ? v > 0.0 : v >= 0.0) && v <= 1.0; }   // (false for NaN)
@@ -506,18 +654,38 @@ extern "C" int gpp_track_ego_workspace_bytes(int S, int N, size_t* bytes)
 
 // the entry points: the checks of the contract in their order, then the one launch.  The optimal form asks for the same workspace and
 // uses seq_start's copy only.  with_ego: gpp_track_ego_f64 -- the records of the frames inside a sequence are checked here, on the host,
-// and copied behind the plain workspace
-static int track(bool optimal, bool with_ego, const double* ego, const float* rows_in, int N, int D, const int32_t* seq_start, int S,
+// and copied behind the plain workspace.  kalman: gpp_track_kf_f64 -- not null, and then with_ego says whether records were given; the
+// workspace is the ego form's either way
+struct kf_host {
+    const void* cov_in;
+    void* cov_out;
+    const gpp_track_kf_params* kf;
+};
+
+static bool positive(double v) { return v > 0.0 && __builtin_isfinite(v); }             // (false for NaN)
+static bool not_negative(double v) { return v >= 0.0 && __builtin_isfinite(v); }
+
+static int track(bool optimal, bool with_ego, const kf_host* kalman, const double* ego, const float* rows_in, int N, int D,
+                 const int32_t* seq_start, int S,
                  const void* state_in, void* state_out, const gpp_track_params* params, float* rows_out, int32_t* track_ids,
                  int32_t* track_hits, void* workspace, size_t workspace_bytes, void* stream)
 {
     if (N < 0 || D < 0 || S < 0 || !params || !seq_start) return GPP_ERR_BAD_ARG;
     const gpp_track_params& p = *params;
-    if (p.metric != GPP_TRACK_BEV && p.metric != GPP_TRACK_3D && p.metric != GPP_TRACK_DIST) return GPP_ERR_BAD_ARG;
-    if (p.metric == GPP_TRACK_DIST ? !(p.threshold > 0.0 && __builtin_isfinite(p.threshold)) : !(p.threshold >= 0.0 && p.threshold < 1.0))
+    if (p.metric != GPP_TRACK_BEV && p.metric != GPP_TRACK_3D && p.metric != GPP_TRACK_DIST && !(kalman && p.metric == GPP_TRACK_MAHA))
+        return GPP_ERR_BAD_ARG;
+    const bool metres_or_sigmas = p.metric == GPP_TRACK_DIST || p.metric == GPP_TRACK_MAHA;
+    if (metres_or_sigmas ? !(p.threshold > 0.0 && __builtin_isfinite(p.threshold)) : !(p.threshold >= 0.0 && p.threshold < 1.0))
         return GPP_ERR_BAD_ARG;
     if (!unit(p.gain_a, true) || !unit(p.gain_b, false) || !unit(p.gain_c, false)) return GPP_ERR_BAD_ARG;
     if (p.max_age < 0 || (p.smooth != 0 && p.smooth != 1) || p.reserved != 0 || __builtin_isnan(p.birth_score)) return GPP_ERR_BAD_ARG;
+    if (kalman) {
+        if (!kalman->kf) return GPP_ERR_BAD_ARG;
+        const gpp_track_kf_params& k = *kalman->kf;
+        if (!positive(k.radial0) || !positive(k.tangential0) || !positive(k.birth_speed)) return GPP_ERR_BAD_ARG;
+        if (!not_negative(k.radial1) || !not_negative(k.tangential1) || !not_negative(k.q_pos) || !not_negative(k.q_vel)) return GPP_ERR_BAD_ARG;
+        if (k.reserved != 0) return GPP_ERR_BAD_ARG;
+    }
     for (int s = 0; s <= S; ++s) {
         const int32_t lo = s == 0 ? 0 : seq_start[s - 1];
         if (seq_start[s] < lo || seq_start[s] > N) return GPP_ERR_BAD_ARG;
@@ -535,16 +703,22 @@ static int track(bool optimal, bool with_ego, const double* ego, const float* ro
     }
     if (D > kMaxD) return GPP_ERR_UNSUPPORTED;
     if (S > 0 && (!state_in || !state_out)) return GPP_ERR_BAD_ARG;
+    if (S > 0 && kalman && (!kalman->cov_in || !kalman->cov_out)) return GPP_ERR_BAD_ARG;
     hipStream_t q = (hipStream_t)stream;
     if (S == 0) return GPP_OK;
     if ((size_t)N * (size_t)D == 0) {
+        if (kalman && kalman->cov_out != kalman->cov_in) {
+            hipError_t e = hipMemcpyAsync(kalman->cov_out, kalman->cov_in, (size_t)S * sizeof(gpp_track_cov), hipMemcpyDeviceToDevice, q);
+            if (e != hipSuccess) return (int)e;
+        }
         if (state_out == state_in) return GPP_OK;
         hipError_t e = hipMemcpyAsync(state_out, state_in, (size_t)S * sizeof(gpp_track_state), hipMemcpyDeviceToDevice, q);
         return e == hipSuccess ? GPP_OK : (int)e;
     }
     if (!rows_in || !rows_out || !track_ids || !track_hits || !workspace) return GPP_ERR_BAD_ARG;
     if (((uintptr_t)workspace | (uintptr_t)state_in | (uintptr_t)state_out) & 7u) return GPP_ERR_ALIGN;
-    if (workspace_bytes < plain_bytes(S) + (with_ego ? (size_t)N * kEgoFields * sizeof(double) : 0)) return GPP_ERR_WORKSPACE;
+    if (kalman && (((uintptr_t)kalman->cov_in | (uintptr_t)kalman->cov_out) & 7u)) return GPP_ERR_ALIGN;
+    if (workspace_bytes < plain_bytes(S) + (with_ego || kalman ? (size_t)N * kEgoFields * sizeof(double) : 0)) return GPP_ERR_WORKSPACE;
     hipError_t e = hipMemcpyAsync(workspace, seq_start, (size_t)(S + 1) * sizeof(int32_t), hipMemcpyHostToDevice, q);
     if (e != hipSuccess) return (int)e;
     double* ego_copy = (double*)((char*)workspace + plain_bytes(S));                // record f at its own place f: the kernel indexes by frame
@@ -558,14 +732,21 @@ static int track(bool optimal, bool with_ego, const double* ego, const float* ro
     gpp_track_state* out = (gpp_track_state*)state_out;
     double* tables = (double*)((char*)workspace + seq_bytes(S));
     const dim3 grid((unsigned)S), block(kThreads);
-    if (optimal && with_ego)
-        track_kernel<true, true><<<grid, block, 0, q>>>(rows_in, N, D, seq, in, out, p, rows_out, track_ids, track_hits, nullptr, ego_copy);
-    else if (with_ego)
-        track_kernel<false, true><<<grid, block, 0, q>>>(rows_in, N, D, seq, in, out, p, rows_out, track_ids, track_hits, tables, ego_copy);
-    else if (optimal)
-        track_kernel<true, false><<<grid, block, 0, q>>>(rows_in, N, D, seq, in, out, p, rows_out, track_ids, track_hits, nullptr, nullptr);
-    else
-        track_kernel<false, false><<<grid, block, 0, q>>>(rows_in, N, D, seq, in, out, p, rows_out, track_ids, track_hits, tables, nullptr);
+    kf_args kfa = {nullptr, nullptr, {}};
+    if (kalman) kfa = {(const gpp_track_cov*)kalman->cov_in, (gpp_track_cov*)kalman->cov_out, *kalman->kf};
+#define GPP_TRACK_LAUNCH(OPT, EGO, KF) \
+    track_kernel<OPT, EGO, KF><<<grid, block, 0, q>>>(rows_in, N, D, seq, in, out, p, rows_out, track_ids, track_hits, OPT ? nullptr : tables, \
+                                                      EGO ? ego_copy : nullptr, kfa)
+    if (kalman) {
+        if (optimal && with_ego) GPP_TRACK_LAUNCH(true, true, true);
+        else if (with_ego) GPP_TRACK_LAUNCH(false, true, true);
+        else if (optimal) GPP_TRACK_LAUNCH(true, false, true);
+        else GPP_TRACK_LAUNCH(false, false, true);
+    } else if (optimal && with_ego) GPP_TRACK_LAUNCH(true, true, false);
+    else if (with_ego) GPP_TRACK_LAUNCH(false, true, false);
+    else if (optimal) GPP_TRACK_LAUNCH(true, false, false);
+    else GPP_TRACK_LAUNCH(false, false, false);
+#undef GPP_TRACK_LAUNCH
     e = hipGetLastError();
     return e == hipSuccess ? GPP_OK : (int)e;
 }
@@ -574,15 +755,15 @@ extern "C" int gpp_track_f64(const float* rows_in, int N, int D, const int32_t* 
                              const gpp_track_params* params, float* rows_out, int32_t* track_ids, int32_t* track_hits,
                              void* workspace, size_t workspace_bytes, void* stream)
 {
-    return track(false, false, nullptr, rows_in, N, D, seq_start, S, state_in, state_out, params, rows_out, track_ids, track_hits, workspace,
-                 workspace_bytes, stream);
+    return track(false, false, nullptr, nullptr, rows_in, N, D, seq_start, S, state_in, state_out, params, rows_out, track_ids, track_hits,
+                 workspace, workspace_bytes, stream);
 }
 
 extern "C" int gpp_track_optimal_f64(const float* rows_in, int N, int D, const int32_t* seq_start, int S, const void* state_in, void* state_out,
                                      const gpp_track_params* params, float* rows_out, int32_t* track_ids, int32_t* track_hits,
                                      void* workspace, size_t workspace_bytes, void* stream)
 {
-    return track(true, false, nullptr, rows_in, N, D, seq_start, S, state_in, state_out, params, rows_out, track_ids, track_hits, workspace,
+    return track(true, false, nullptr, nullptr, rows_in, N, D, seq_start, S, state_in, state_out, params, rows_out, track_ids, track_hits, workspace,
                  workspace_bytes, stream);
 }
 
@@ -591,6 +772,24 @@ extern "C" int gpp_track_ego_f64(const float* rows_in, int N, int D, const int32
                                  int32_t* track_hits, void* workspace, size_t workspace_bytes, void* stream)
 {
     if (assign != GPP_TRACK_ASSIGN_GREEDY && assign != GPP_TRACK_ASSIGN_OPTIMAL) return GPP_ERR_BAD_ARG;
-    return track(assign == GPP_TRACK_ASSIGN_OPTIMAL, true, ego, rows_in, N, D, seq_start, S, state_in, state_out, params, rows_out, track_ids,
-                 track_hits, workspace, workspace_bytes, stream);
+    return track(assign == GPP_TRACK_ASSIGN_OPTIMAL, true, nullptr, ego, rows_in, N, D, seq_start, S, state_in, state_out, params, rows_out,
+                 track_ids, track_hits, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gpp_track_cov_bytes(size_t* bytes)
+{
+    if (!bytes) return GPP_ERR_BAD_ARG;
+    *bytes = sizeof(gpp_track_cov);
+    return GPP_OK;
+}
+
+extern "C" int gpp_track_kf_f64(const float* rows_in, int N, int D, const int32_t* seq_start, int S, const void* state_in, void* state_out,
+                                const void* cov_in, void* cov_out, const gpp_track_params* params, const gpp_track_kf_params* kf,
+                                const double* ego, int assign, float* rows_out, int32_t* track_ids, int32_t* track_hits, void* workspace,
+                                size_t workspace_bytes, void* stream)
+{
+    if (assign != GPP_TRACK_ASSIGN_GREEDY && assign != GPP_TRACK_ASSIGN_OPTIMAL) return GPP_ERR_BAD_ARG;
+    const kf_host kalman = {cov_in, cov_out, kf};
+    return track(assign == GPP_TRACK_ASSIGN_OPTIMAL, ego != nullptr, &kalman, ego, rows_in, N, D, seq_start, S, state_in, state_out, params,
+                 rows_out, track_ids, track_hits, workspace, workspace_bytes, stream);
 }

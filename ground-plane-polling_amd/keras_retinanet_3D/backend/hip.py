@@ -130,6 +130,7 @@ class AbsmaxDesc(ctypes.Structure):
 
 GPP_TRACK_MAX_TRACKS, GPP_TRACK_FIELDS = 128, 10   # include/gpp.h, gpp_track_state
 GPP_TRACK_EGO_FIELDS = 16                          # gpp_track_ego_f64: one record per frame
+GPP_TRACK_MAHA, GPP_TRACK_COV_FIELDS = 3, 10       # gpp_track_kf_f64: the fourth metric, gpp_track_cov's fields
 
 
 class TrackState(ctypes.Structure):
@@ -145,6 +146,12 @@ class TrackParams(ctypes.Structure):
     _fields_ = [('metric', ctypes.c_int32), ('max_age', ctypes.c_int32), ('smooth', ctypes.c_int32), ('reserved', ctypes.c_int32),
                 ('threshold', ctypes.c_double), ('gain_a', ctypes.c_double), ('gain_b', ctypes.c_double), ('gain_c', ctypes.c_double),
                 ('birth_score', ctypes.c_double)]
+
+
+class TrackKfParams(ctypes.Structure):
+    """ gpp_track_kf_params (include/gpp.h) """
+    _fields_ = [(n, ctypes.c_double) for n in ('radial0', 'radial1', 'tangential0', 'tangential1', 'q_pos', 'q_vel', 'birth_speed')] + \
+               [('reserved', c_int64)]
 
 
 GPP_MOT_SCALE_BITS, GPP_MOT_BIG, GPP_MOT_MAX_TRAJECTORIES = 20, 1 << 28, 1024      # include/gpp.h, gpp_mot_assign / gpp_mot_clear
@@ -216,6 +223,15 @@ def _declare(lib):
         lib.gpp_track_ego_f64.argtypes = [c_void_p, c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_void_p, c_void_p,
                                           ctypes.POINTER(TrackParams), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                           c_void_p]
+    # the tracker's Kalman filter (include/gpp.h, csrc/track.hip; absent from an older build named by GPP_LIB: it runs everything but
+    # tracking with 'filter': 'kalman')
+    if hasattr(lib, 'gpp_track_kf_f64'):
+        lib.gpp_track_cov_bytes.restype = c_int
+        lib.gpp_track_cov_bytes.argtypes = [ctypes.POINTER(c_size_t)]
+        lib.gpp_track_kf_f64.restype = c_int
+        lib.gpp_track_kf_f64.argtypes = [c_void_p, c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         ctypes.POINTER(TrackParams), ctypes.POINTER(TrackKfParams), c_void_p, c_int, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_size_t, c_void_p]
     # the tracking score (include/gpp.h, csrc/mot_eval.hip; absent from an older build named by GPP_LIB: it runs everything but
     # evaluate_tracking(device=True))
     if hasattr(lib, 'gpp_mot_assign'):
@@ -635,14 +651,26 @@ def track_ego_workspace_bytes(S, N):
     return n.value
 
 
-def track(rows, state_in, params, seq_start=None, state_out=None, out=None, ids=None, hits=None, workspace=None, optimal=False, ego=None):
+def track_cov_bytes():
+    if not hasattr(lib(), 'gpp_track_kf_f64'):
+        raise GppError("gpp_track_kf_f64 is not in {}: there is no other path for 'filter': 'kalman'".format(LIB_PATH))
+    n = c_size_t(0)
+    check(lib().gpp_track_cov_bytes(ctypes.byref(n)), 'gpp_track_cov_bytes')
+    return n.value
+
+
+def track(rows, state_in, params, seq_start=None, state_out=None, out=None, ids=None, hits=None, workspace=None, optimal=False, ego=None,
+          kf=None, cov_in=None, cov_out=None):
     """ gpp_track_f64 (optimal: gpp_track_optimal_f64, the same arguments) on the current stream: rows (N, D, 36) float32 on the device --
     the rows of gpp_pose_f32 of N frames --, state_in
     (S, gpp_track_state bytes) uint8 on the device, params a TrackParams, seq_start (S + 1) host integers (default: one sequence of all N
     frames) -> (rows_out (N, D, 36) float32, ids (N, D) int32, hits (N, D) int32, state_out) on the device; no synchronisation.
     out: where the rows go (default: a new tensor; `rows` itself: in place); state_out: default a new tensor (`state_in` itself: in place).
     ego: None, or the (N, 16) float64 HOST records of the frames (a NumPy array): gpp_track_ego_f64 with assign = optimal, and a workspace
-    of track_ego_workspace_bytes(S, N) """
+    of track_ego_workspace_bytes(S, N).
+    kf: None, or a TrackKfParams: gpp_track_kf_f64 (with or without `ego`; the workspace is track_ego_workspace_bytes(S, N) either way)
+    with cov_in (S, gpp_track_cov bytes) uint8 on the device and cov_out (default: a new tensor; `cov_in` itself: in place)
+    -> (rows_out, ids, hits, state_out, cov_out) """
     import torch
     if rows.dim() != 3 or rows.dtype != torch.float32 or rows.shape[2] != GPP_POSE_COLS:
         raise ValueError('gpp_track_f64: rows must be (N, D, {}) float32, got {} {}'.format(GPP_POSE_COLS, tuple(rows.shape), rows.dtype))
@@ -663,7 +691,16 @@ def track(rows, state_in, params, seq_start=None, state_out=None, out=None, ids=
         ego = np.ascontiguousarray(ego, np.float64)
         if ego.shape != (N, GPP_TRACK_EGO_FIELDS):
             raise ValueError('gpp_track_ego_f64: ego must be ({}, {}) float64 on the host, got {}'.format(N, GPP_TRACK_EGO_FIELDS, ego.shape))
-    need = track_workspace_bytes(S) if ego is None else track_ego_workspace_bytes(S, N)
+    need = track_workspace_bytes(S) if ego is None and kf is None else track_ego_workspace_bytes(S, N)
+    if kf is not None:
+        cbytes = track_cov_bytes()
+        if cov_in is None or cov_in.dim() != 2 or cov_in.dtype != torch.uint8 or tuple(cov_in.shape) != (S, cbytes) or cov_in.device != dev:
+            raise ValueError('gpp_track_kf_f64: the covariance must be ({}, {}) uint8 on {}'.format(S, cbytes, dev))
+        cov_out = torch.empty_like(cov_in) if cov_out is None else cov_out
+        if cov_out.dtype != torch.uint8 or tuple(cov_out.shape) != (S, cbytes) or cov_out.device != dev:
+            raise ValueError('gpp_track_kf_f64: cov_out must be ({}, {}) uint8 on {}'.format(S, cbytes, dev))
+    elif cov_in is not None or cov_out is not None:
+        raise ValueError('gpp_track_f64: a covariance belongs to gpp_track_kf_f64 (kf=TrackKfParams)')
     workspace = torch.empty((need,), dtype=torch.uint8, device=dev) if workspace is None else workspace
     want = ((out, torch.float32, (N, D, GPP_POSE_COLS)), (ids, torch.int32, (N, D)), (hits, torch.int32, (N, D)),
             (state_out, torch.uint8, (S, nbytes)))
@@ -672,9 +709,14 @@ def track(rows, state_in, params, seq_start=None, state_out=None, out=None, ids=
             raise ValueError('gpp_track_f64: expected {} {} on {}, got {} {} on {}'.format(shape, dtype, dev, tuple(t.shape), t.dtype, t.device))
     if workspace.dtype != torch.uint8 or workspace.device != dev:
         raise ValueError('gpp_track_f64: the workspace must be uint8 on {}'.format(dev))
-    name = 'gpp_track_ego_f64' if ego is not None else 'gpp_track_optimal_f64' if optimal else 'gpp_track_f64'
+    name = 'gpp_track_kf_f64' if kf is not None else 'gpp_track_ego_f64' if ego is not None else 'gpp_track_optimal_f64' if optimal else 'gpp_track_f64'
     if not hasattr(lib(), name):
         raise GppError('{} is not in {}: there is no other path for this assignment'.format(name, LIB_PATH))
+    if kf is not None:
+        check(lib().gpp_track_kf_f64(ptr(rows), N, D, seq, S, ptr(state_in), ptr(state_out), ptr(cov_in), ptr(cov_out), ctypes.byref(params),
+                                     ctypes.byref(kf), None if ego is None else ego.ctypes.data_as(c_void_p), int(bool(optimal)), ptr(out),
+                                     ptr(ids), ptr(hits), ptr(workspace), int(workspace.numel()), stream_ptr()), name)
+        return out, ids, hits, state_out, cov_out
     if ego is not None:
         check(lib().gpp_track_ego_f64(ptr(rows), N, D, seq, S, ptr(state_in), ptr(state_out), ctypes.byref(params),
                                       ego.ctypes.data_as(c_void_p), int(bool(optimal)), ptr(out), ptr(ids), ptr(hits), ptr(workspace),

@@ -76,12 +76,14 @@ def parse_args(args):
                              'stage of the plan on the GPU (cuboid_nms=(metric, threshold)), otherwise applied on the host before the results are written.')
     parser.add_argument('--cuboid-nms-threshold', type=float, default=None,
                         help='The overlap above which --cuboid-nms drops a detection, inside (0, 1).  No default: it depends on the checkpoint.')
-    parser.add_argument('--track', choices=['bev', '3d', 'dist'], default=None,
+    parser.add_argument('--track', choices=list(track_utils.KF_METRICS), default=None,
                         help='Track the cuboids across the images (not in the reference CLI; needs --device-pose): the sorted image list is one '
                              'sequence, every detection gets an identity that persists from frame to frame (csrc/track.hip, on the GPU behind '
                              'the plan) and <output_dir>/<model name>/outputs/tracking/tracks.txt is written in KITTI\'s tracking format.  A '
                              'detection continues a track when their cuboids overlap by more than --track-threshold in the bird\'s-eye view '
-                             '(bev) or in 3-D (3d), or when their centres lie closer than --track-threshold metres on the ground (dist).')
+                             '(bev) or in 3-D (3d), when their centres lie closer than --track-threshold metres on the ground (dist), or within '
+                             '--track-threshold standard deviations of the track\'s predicted position (maha: needs --track-filter kalman).')
+    track_utils.add_filter_arguments(parser)
     parser.add_argument('--track-threshold', type=float, default=None,
                         help='The threshold of --track.  No default: it depends on the checkpoint and the frame rate.')
     parser.add_argument('--track-max-age', type=int, default=track_utils.DEFAULTS['max_age'],
@@ -119,6 +121,9 @@ def parse_args(args):
         parser.error('--track-oxts and --track-calib go together: both or neither')
     if parsed.track_oxts is not None and parsed.track is None:
         parser.error('--track-oxts compensates the tracker of --track: it needs --track')
+    if parsed.track is None and (parsed.track_filter != 'fixed' or parsed.track_noise is not None or parsed.track_process is not None
+                                 or parsed.track_birth_speed is not None):
+        parser.error('--track-filter, --track-noise, --track-process and --track-birth-speed set the tracker of --track: they need --track')
     if parsed.track is not None:
         if not parsed.device_pose:
             parser.error('--track follows the pose stage on the GPU: it needs --device-pose')
@@ -146,6 +151,7 @@ def track_option(args):
         option['assign'] = 'optimal'
     if args.track_oxts is not None:
         option['ego'] = True
+    option.update(track_utils.filter_option(args))
     return option
 
 

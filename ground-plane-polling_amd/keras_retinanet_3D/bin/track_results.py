@@ -12,9 +12,12 @@ threshold can be swept.  On the GPU by default (csrc/track.hip: one launch for t
 optimal one-to-one assignment of every frame, on the GPU and with --host alike.  --oxts FILE --calib FILE (the
 sequence's oxts/<seq>.txt and calib/<seq>.txt, one oxts line per result file) move the carried cuboids into every frame's camera
 coordinates before they are matched (gpp_track_ego_f64): a parked car keeps its id from a driving camera.
+--track-filter kalman with --track-noise, --track-process and --track-birth-speed gives every track the covariance of its ground-plane
+position and velocity (gpp_track_kf_f64), and --metric maha gates at --threshold standard deviations.
 
     track_results.py result_dir/ tracks.txt --metric dist --threshold 2.0 [--max-age 2] [--min-hits 1] [--smooth] [--host]
                      [--track-assign greedy|optimal] [--oxts oxts/0000.txt --calib calib/0000.txt]
+                     [--track-filter kalman --track-noise R0 R1 T0 T1 --track-process QP QV --track-birth-speed V0 [--metric maha]]
                      [--labels label_02/0000.txt [--score-metric image] [--score-min-overlap 0.5] [--hota] [--idf1]]
 
 --labels scores the tracks just written against the sequence's label_02 file (CLEAR-MOT; on the GPU unless
@@ -45,9 +48,11 @@ def parse_args(args):
     parser = argparse.ArgumentParser(description='Track the cuboids of a directory of KITTI result files.')
     parser.add_argument('result_dir', help='Directory of KITTI result files, one per frame; their sorted names are the sequence.')
     parser.add_argument('tracks_path', help='The file to write, in KITTI\'s tracking format.')
-    parser.add_argument('--metric', choices=list(track_utils.METRICS), required=True,
+    parser.add_argument('--metric', '--track', dest='metric', choices=list(track_utils.KF_METRICS), required=True,
                         help='bev / 3d: a detection continues a track when their cuboids overlap by more than --threshold in the bird\'s-eye '
-                             'view / in 3-D; dist: when their centres lie closer than --threshold metres on the ground.')
+                             'view / in 3-D; dist: when their centres lie closer than --threshold metres on the ground; maha: within --threshold standard '
+                             'deviations of the track\'s predicted position (needs --track-filter kalman).')
+    track_utils.add_filter_arguments(parser)
     parser.add_argument('--threshold', type=float, required=True, help='No default: it depends on the checkpoint and the frame rate.')
     parser.add_argument('--max-age', type=int, default=track_utils.DEFAULTS['max_age'], help='Frames a track survives without a detection.')
     parser.add_argument('--min-hits', type=int, default=1, help='Only tracks seen in at least this many frames are written.')
@@ -67,8 +72,9 @@ def parse_args(args):
     if (parsed.oxts is None) != (parsed.calib is None):
         parser.error('--oxts and --calib go together: both or neither')
     try:
-        parsed.option = track_utils.check_option({'metric': parsed.metric, 'threshold': parsed.threshold, 'max_age': parsed.max_age,
-                                                  'birth_score': parsed.birth_score, 'smooth': parsed.smooth, 'assign': parsed.track_assign})
+        parsed.option = track_utils.check_option(dict({'metric': parsed.metric, 'threshold': parsed.threshold, 'max_age': parsed.max_age,
+                                                       'birth_score': parsed.birth_score, 'smooth': parsed.smooth,
+                                                       'assign': parsed.track_assign}, **track_utils.filter_option(parsed)))
         mot_eval.check_params(parsed.mot_metric, parsed.mot_min_overlap)
     except ValueError as e:
         parser.error(str(e))
@@ -92,9 +98,9 @@ def main(args=None):
     names, frames = read_sequence(args.result_dir)
     run = track_utils.track_rows_np if args.host else track_utils.track_rows_device
     if args.oxts is None:
-        rows, ids, hits, state = run(frames, args.option)
+        rows, ids, hits, state = run(frames, args.option)[:4]
     else:
-        rows, ids, hits, state = run(frames, args.option, ego=oxts.records_for(args.oxts, args.calib, len(names)))
+        rows, ids, hits, state = run(frames, args.option, ego=oxts.records_for(args.oxts, args.calib, len(names)))[:4]
     with open(args.tracks_path, 'w') as f:
         for k in range(len(names)):
             f.write(track_utils.tracking_lines(k, rows[k], ids[k], hits[k], args.min_hits))

@@ -106,7 +106,10 @@ def load_model(filepath, backbone_name='resnet50', convert=False, nms=True, clas
     methods take ego=records, (B, 16) float64 -- utils.track.ego_records of the camera-from-previous-camera transforms, or
     utils.oxts.camera_ego from KITTI's oxts and calib files -- and launch gpp_track_ego_f64: the carried cuboids are moved into every
     frame's camera coordinates before they are matched, so a parked car keeps its id from a driving camera; a missing ego on such a model
-    and a given one on any other are refused.  Every other method is unchanged and does not touch the tracker.  FramePipeline and
+    and a given one on any other are refused.  'filter': 'kalman' with 'noise': {'radial': (r0, r1), 'tangential': (t0, t1), 'process':
+    (q_pos, q_vel), 'birth_speed': v0} (section 4.34; no defaults: nothing here has seen a real sequence) launches gpp_track_kf_f64: every
+    carried cuboid keeps the covariance of (x, z, vx, vz), a row's noise grows with its range along the viewing ray, and the fourth
+    metric 'maha' gates at T standard deviations; model.track_covariance() reads the covariances.  Every other method is unchanged and does not touch the tracker.  FramePipeline and
     ShardedModel refuse such a model: they reorder or split the frames.
     """
     import os

@@ -91,6 +91,7 @@ class RetinaNet3D(object):
         if self.track is not None and not self.pose:
             raise ValueError('track={!r} associates pose rows: it needs pose=True'.format(track))
         self._track_state = None             # (current, next): two (1, gpp_track_state) buffers, swapped after every answered call
+        self._track_cov = None               # 'filter': 'kalman' (section 4.34): (current, next), two (1, gpp_track_cov) buffers, swapped with them
         self._answered = None                # (model, plan) that answered the last call of the pose family
         # 'throughput' | 'latency' (models.load_model): which layers split their K loop (layers/conv.latency_split)
         self.plan_mode = plan or os.environ.get('GPP_PLAN', 'throughput')
@@ -821,6 +822,10 @@ class RetinaNet3D(object):
             self._track_params = track_utils.params_of(self.track)
             self._track_optimal = track_utils.is_optimal(self.track)     # 'assign': 'optimal' -> gpp_track_optimal_f64 (section 4.32)
             self._track_ego_work = None          # 'ego': True -> gpp_track_ego_f64 (section 4.33): (B, workspace), sized with the plan's B
+            self._track_kf = track_utils.kf_params_of(self.track)        # 'filter': 'kalman' -> gpp_track_kf_f64 (section 4.34), or None
+            if self._track_kf is not None:       # (its workspace is the ego form's, with or without records)
+                cov = torch.zeros((2, 1, hip.track_cov_bytes()), dtype=torch.uint8, device=self.device)
+                self._track_cov = [cov[0], cov[1]]
         return self._track_state
 
     def _track_ego(self, ego, frames, what):
@@ -840,24 +845,38 @@ class RetinaNet3D(object):
             raise hip.GppError('{}: {}'.format(what, e))
 
     def reset_tracks(self):
-        """ start a new sequence: the empty tracker (the next birth gets id 0) """
+        """ start a new sequence: the empty tracker (the next birth gets id 0), and with 'filter': 'kalman' its zero covariances """
         self._track_buffers()[0].zero_()
+        if self._track_cov is not None:
+            self._track_cov[0].zero_()
 
     def track_state(self):
         """ the tracker's state as one utils.track.STATE_DTYPE record (include/gpp.h, gpp_track_state).  One copy (synchronises). """
         return track_utils.read_state(self._track_buffers()[0])[0]
+
+    def track_covariance(self):
+        """ the covariances that belong to track_state(), (10, 128) float64 -- utils.track.COV_FIELDS by slot (include/gpp.h,
+        gpp_track_cov) -- on a model loaded with track={..., 'filter': 'kalman'}.  One copy (synchronises). """
+        self._track_buffers()
+        if self._track_cov is None:
+            raise hip.GppError("this model's tracker keeps no covariance: load it with track={..., 'filter': 'kalman', 'noise': {...}}")
+        return track_utils.read_cov(self._track_cov[0])[0]
 
     def fetch_tracks(self, plan, what='predict_tracks_on_batch', ego=None):
         """ ((rows, counts, ids, hits)) of the plan's last run: fetch_poses + the tracker's frame steps over the images of the batch, in
         order.  The launch follows the plan (and its cuboid NMS) on the stream and is no plan op; it goes from the current state to a
         second buffer, because _range_event calls the reader a second time on the float32 twin: the model commits by swapping the two
         only after _answer has returned -- the state advances once per answered call, by the rows that answered it.  ego: the checked
-        (B, 16) records of an 'ego' model (_track_ego): the launch is gpp_track_ego_f64, and the twin's second call takes the same ones. """
+        (B, 16) records of an 'ego' model (_track_ego): the launch is gpp_track_ego_f64, and the twin's second call takes the same ones.
+        With 'filter': 'kalman' the launch is gpp_track_kf_f64 and the covariances go the state's way: from the current buffer to a
+        second one, swapped together with the states -- a range event advances both once. """
         torch = self.torch
         state, nxt = self._track_buffers()
         B, D = int(plan.pose_rows.shape[0]), int(plan.pose_rows.shape[1])
         work = self._track_work
-        if ego is not None:
+        kf = self._track_kf
+        cov, nxt_cov = self._track_cov if kf is not None else (None, None)
+        if ego is not None or kf is not None:
             if self._track_ego_work is None or self._track_ego_work[0] != B:
                 self._track_ego_work = (B, torch.empty((hip.track_ego_workspace_bytes(1, B),), dtype=torch.uint8, device=self.device))
             work = self._track_ego_work[1]
@@ -868,7 +887,7 @@ class RetinaNet3D(object):
         def rows_and_tracks(model, p):
             # (smooth: the plan's rows stay what predict_poses_* reads; otherwise the kernel's bit copy lands where it came from)
             hip.track(p.pose_rows, state, self._track_params, state_out=nxt, out=out if smooth else p.pose_rows, ids=tags[0], hits=tags[1],
-                      workspace=work, optimal=self._track_optimal, ego=ego)
+                      workspace=work, optimal=self._track_optimal, ego=ego, kf=kf, cov_in=cov, cov_out=nxt_cov)
             (rows, counts), count = self.read_poses(model, p)
             if smooth:
                 rows = out.cpu().numpy()
@@ -877,6 +896,8 @@ class RetinaNet3D(object):
 
         result = self._answer(plan, what, rows_and_tracks)
         self._track_state = [nxt, state]
+        if kf is not None:
+            self._track_cov = [nxt_cov, cov]
         return result
 
     def predict_tracks_on_batch(self, inputs, scales, image_shapes, heights=None, ego=None):

@@ -913,6 +913,62 @@ int gpp_track_ego_f64(const float* rows_in, int N, int D, const int32_t* seq_sta
                       int32_t* track_hits, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Tracking with a KALMAN FILTER on the ground plane (csrc/track.hip, either kernel of either assignment with a covariance per slot;
+ * DESIGN.md section 4.34 is the specification -- every expression below is written out there, fully parenthesised --, utils/track.py with
+ * 'filter': 'kalman' the host form).  Every carried cuboid keeps the 4 x 4 covariance of (x, z, vx, vz); a row's measurement noise grows
+ * with its range along the viewing ray and stays small across it; a matched pair is updated with the Kalman gain of the two, and the
+ * fourth metric GPP_TRACK_MAHA gates and ranks by the squared Mahalanobis distance.  The state's layout, gpp_track_params, every error
+ * and the N * D == 0 / S == 0 behaviour are gpp_track_ego_f64's; the three entry points above go on refusing GPP_TRACK_MAHA.
+ *
+ *   cov_in, cov_out (S, gpp_track_cov) on the device, 8-byte aligned: per slot the upper triangle of the symmetric covariance as three
+ *               blocks, field-major like `box` -- A (position-position) Axx Axz Azz, B (position-velocity, a general 2 x 2: B[p][v])
+ *               Bxx Bxz Bzx Bzz, C (velocity-velocity) Cxx Cxz Czz.  All zero for a free slot.  cov_out == cov_in is allowed, otherwise
+ *               the two do not overlap.
+ *   kf          radial0 + radial1 rho and tangential0 + tangential1 rho are the standard deviations of a row at range rho along and
+ *               across its viewing ray (metres, metres per metre); q_pos, q_vel the process variances per frame step; birth_speed the
+ *               standard deviation of a born track's velocity per component.
+ *   ego         as gpp_track_ego_f64 takes it, or null: no records, no step 1b.
+ *   frame step  that of gpp_track_ego_f64 (without 1b for a null `ego`) with:
+ *     row noise    once per live, non-blind row: rho = sqrt(x x + z z), u = (x, z) / rho (u = (0, 1) for rho == 0),
+ *                  R = st^2 I + (sr^2 - st^2) u u^T with sr = radial0 + radial1 rho, st = tangential0 + tangential1 rho.
+ *     1 predict    the mean as before; A += B + B^T + C + q_pos I, B += C, C += q_vel I, all from the old values.
+ *     1b ego       the mean as before; A, B and C each go to Rg X Rg^T with Rg = [[R00, R02], [R20, R22]] of the record.  What pitch and
+ *                  roll mix in from y is left out.
+ *     3 candidates GPP_TRACK_MAHA: S = A + R, det = Sxx Szz - Sxz Sxz, m = r^T S^-1 r for r = row - predicted in (x, z); a candidate
+ *                  iff det > 0 and m < threshold * threshold (threshold: standard deviations, finite and > 0); the smaller m is
+ *                  better; the key and the optimal form's cell are GPP_TRACK_DIST's with m in the place of q.  The other three metrics
+ *                  gate and rank as before.
+ *     5 update     S and det of the matched pair as above.  det > 0: K = [A; B^T] S^-1, (x, z, vx, vz) += K r, P -= K [A B] (upper
+ *                  triangle).  Otherwise (only under BEV / 3D / DIST, from a caller's covariance): x z vx vz take the fixed gains and
+ *                  the covariance is set as at a birth from the matched row.  y, vy, h w l and r_y keep their fixed gains always.
+ *     6 deaths     the freed slot's covariance is zeroed.
+ *     7 births     A = R of the row, B = 0, C = birth_speed^2 I.
+ *   workspace   gpp_track_ego_workspace_bytes(S, N) bytes, with or without records.
+ *
+ *   GPP_ERR_BAD_ARG, nothing launched and nothing written, beyond gpp_track_ego_f64's (whose null `ego` is no error here): a null `kf`;
+ *   radial0, tangential0 or birth_speed not finite and > 0; radial1, tangential1, q_pos or q_vel not finite and >= 0; kf->reserved != 0;
+ *   a GPP_TRACK_MAHA threshold that is not finite and > 0; a null cov_in or cov_out when S > 0.  cov_in or cov_out not 8-byte aligned:
+ *   GPP_ERR_ALIGN.  N * D == 0 (S > 0): state_in is copied to state_out and cov_in to cov_out.
+ * ---------------------------------------------------------------------------------------- */
+#define GPP_TRACK_MAHA 3
+#define GPP_TRACK_COV_FIELDS 10          /* Axx Axz Azz  Bxx Bxz Bzx Bzz  Cxx Cxz Czz */
+typedef struct gpp_track_cov {
+    double p[GPP_TRACK_COV_FIELDS][GPP_TRACK_MAX_TRACKS];    /* field-major: p[f][slot] */
+} gpp_track_cov;
+typedef struct gpp_track_kf_params {
+    double radial0, radial1;             /* sigma along the viewing ray: radial0 + radial1 * range */
+    double tangential0, tangential1;     /* sigma across it */
+    double q_pos, q_vel;                 /* process variances per frame step */
+    double birth_speed;                  /* sigma of a born track's velocity */
+    int64_t reserved;                    /* must be 0 */
+} gpp_track_kf_params;
+int gpp_track_cov_bytes(size_t* bytes);                       /* sizeof(gpp_track_cov) */
+int gpp_track_kf_f64(const float* rows_in, int N, int D, const int32_t* seq_start, int S, const void* state_in, void* state_out,
+                     const void* cov_in, void* cov_out, const gpp_track_params* params, const gpp_track_kf_params* kf,
+                     const double* ego /* may be null */, int assign, float* rows_out, int32_t* track_ids, int32_t* track_hits,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CLEAR-MOT scoring of tracks on the device (csrc/mot_eval.hip; DESIGN.md section 4.29 is the specification, a restatement of the KITTI
  * tracking devkit's CLEAR-MOT -- parity with the devkit itself is UNPINNED; utils/mot_eval.py is the host form): per frame the OPTIMAL
  * one-to-one assignment of the tracker's rows to the labels (the Hungarian method, shortest augmenting paths, exact integers), then per
