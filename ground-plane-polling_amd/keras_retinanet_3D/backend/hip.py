@@ -31,6 +31,10 @@ c_int = ctypes.c_int
 c_float = ctypes.c_float
 c_size_t = ctypes.c_size_t
 c_int64 = ctypes.c_int64
+c_double = ctypes.c_double
+c_uint32 = ctypes.c_uint32
+c_ll = ctypes.c_longlong
+_P = ctypes.POINTER
 
 
 GPP_BF16 = 1
@@ -174,276 +178,194 @@ class AbsmaxClearDesc(ctypes.Structure):
     _fields_ = [('table', c_void_p), ('n', c_int64)]
 
 
+# argument lists that several entry points of include/gpp.h share
+_SIZE_OUT = _P(c_size_t)                   # where a *_bytes entry point leaves its answer
+_HOST_I32 = _P(ctypes.c_int32)             # a host table of int32: seq_start, frame_tab, seq_tab
+_CONV = _P(ConvDesc)
+_STEM = [c_void_p] * 4 + [c_int] * 4 + [c_void_p]
+_STEM_RAGGED = [c_void_p] * 4 + [c_int] * 5 + [c_void_p] * 2
+_STEM_X3_RAGGED = [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 3
+_PACK = [c_void_p, c_void_p, c_size_t]
+_WORK = [c_void_p, c_size_t, c_void_p]       # workspace, its bytes, stream
+_TILES = [_P(c_int), c_int, _P(c_int)]
+_AUTOTUNE = [c_int, c_void_p, _P(c_float)]
+_REGISTER, _RELEASE, _RUN = [_P(ctypes.c_int32)], [ctypes.c_int32], [ctypes.c_int32, c_int, c_void_p]
+_DETECT_BYTES = [c_int, c_int64, _SIZE_OUT]
+_DETECT = [c_void_p] * 4 + [c_int, c_int64, c_int, c_int, c_float, c_float, c_int] + [c_void_p] * 7 + _WORK
+_TRACK_HEAD = [c_void_p, c_int, c_int, _HOST_I32, c_int, c_void_p, c_void_p]        # rows, N, D, seq_start, S, state_in, state_out
+_TRACK_TAIL = [c_void_p] * 3 + _WORK                                                # out, ids, hits
+_TRACK = _TRACK_HEAD + [_P(TrackParams)] + _TRACK_TAIL
+_PAIR_BYTES = [c_ll, c_ll, c_int, c_int, _SIZE_OUT]
+_FRAME_HEAD = [c_void_p] * 5 + [c_int] * 4 + [_HOST_I32, c_ll, c_ll]                # five maps, N, D, A, metric, frame_tab, cells, vecs
+_COST_TABLE = [c_int64, c_int64] + _WORK                                            # pitch, row_offset
+_ROAD_FRAMES = [c_void_p] * 4 + [c_uint32, c_void_p] + [c_int] * 4 + [c_double]      # q ... frame_id, seed, winner, F ... H, tq2
+
+# The C ABI of include/gpp.h, in groups: (probe, what a build without it cannot run, {entry point: argument types}).  A group whose probe
+# symbol is absent from the loaded library is left unbound: GPP_LIB may name an older build for a same-box A/B (tools/ab_bench.sh), and it
+# runs everything but that.  Every entry point returns int, gpp_version its string.  A new entry point is one line in its feature's group
+# (a new feature: a new group, probed by its launching function); tests/test_binding_cpu.py holds each line to the header's prototype.
+_SIGNATURES = [
+    (None, None, {
+        'gpp_version': [],
+        'gpp_poll_workspace_bytes': [c_int, c_int, c_int, _SIZE_OUT],
+        'gpp_poll_f32': [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_float] + [c_void_p] * 4 + _WORK,
+        'gpp_pose_f32': [c_void_p] * 8 + [c_int, c_int, c_float] + [c_void_p] * 3,
+        'gpp_conv2d_igemm': [_CONV, c_void_p],
+        'gpp_conv2d_flops': [_CONV, _P(c_double)],
+        'gpp_conv2d_split_rule': [_CONV, _P(c_int)],
+        'gpp_conv2d_workspace_bytes': [_CONV, _SIZE_OUT],
+        'gpp_conv2d_tile_candidates': [_CONV] + _TILES,
+        'gpp_conv2d_autotune': [_CONV] + _AUTOTUNE,
+        'gpp_bottleneck_tail': [_CONV, _CONV, c_int, c_void_p],
+        'gpp_bottleneck_block': [_CONV, _CONV, _CONV, c_int, c_void_p],
+        'gpp_bottleneck_block_proj': [_CONV, _CONV, _CONV, _CONV, c_int, c_void_p],
+        'gpp_stem_conv7x7_bn_relu': _STEM,
+        'gpp_stem_conv7x7_bn_relu_mfma': _STEM,
+        'gpp_stem_pool_fused_mfma': _STEM,
+        'gpp_stem_pack_weights_f16': _PACK,
+        'gpp_stem_pack_weights_f16x3': _PACK,
+        'gpp_stem_conv7x7_bn_relu_x3': [c_void_p] * 4 + [c_int] * 3 + [c_void_p],
+        'gpp_stem_conv7x7_bn_relu_x3_rc': [c_void_p] * 4 + [c_int] * 3 + [c_void_p] * 2,
+        'gpp_stem_pool_fused_x3': [c_void_p] * 4 + [c_int] * 3 + [c_void_p] * 2,
+        'gpp_maxpool3x3s2_same': [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p],
+        'gpp_relu': [c_void_p, c_void_p, c_int, c_int64, c_void_p],
+        'gpp_relu_strided': [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int64, c_void_p],
+        'gpp_preprocess_u8_bgr': [c_void_p] * 8 + [c_int] * 5 + [c_float] * 3 + [c_void_p],
+        # DenseNet: the pre-activation 1x1 conv and the two pools that write into a channel slice
+        'gpp_conv2d_preact': [_CONV, c_void_p, c_void_p, c_void_p],
+        'gpp_conv2d_preact_tile_candidates': [_CONV] + _TILES,
+        'gpp_conv2d_preact_autotune': [_CONV, c_void_p, c_void_p] + _AUTOTUNE,
+        'gpp_maxpool3x3s2_pad_f32': [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p],
+        'gpp_avgpool2x2_f32': [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p],
+        # MobileNet: the fused depthwise-separable block and the 3x3 / 2 stem
+        'gpp_mobilenet_block': [_P(MobileNetBlockDesc), c_void_p],
+        'gpp_mobilenet_block_tile_candidates': [_P(MobileNetBlockDesc)] + _TILES,
+        'gpp_mobilenet_block_autotune': [_P(MobileNetBlockDesc)] + _AUTOTUNE,
+        'gpp_mobilenet_stem': [c_void_p] * 4 + [c_int] * 5 + [c_void_p],
+        'gpp_mobilenet_depthwise': [c_void_p] * 4 + [c_int] * 7 + [c_void_p],
+        # the decode, its one-sort-per-frame form and its stages
+        'gpp_detect_workspace_bytes': _DETECT_BYTES,
+        'gpp_detect_osf_workspace_bytes': _DETECT_BYTES,
+        'gpp_detect_f32': _DETECT,
+        'gpp_detect_osf_f32': _DETECT,
+        'gpp_detect_stages_f32': [c_int] + _DETECT,
+        'gpp_pack_detections': [c_void_p] * 8 + [c_int, c_int, c_void_p, c_void_p],
+        'gpp_plan_run': [c_void_p, c_int, c_void_p, c_void_p, c_int],
+        'gpp_event_create': [_P(c_void_p)],
+        'gpp_event_destroy': [c_void_p],
+        'gpp_event_elapsed_ms': [c_void_p, c_void_p, _P(c_float)],
+        'gpp_x3_range_events': [_P(ctypes.c_uint64), c_int],
+        'gpp_x3_range_snapshot': [c_void_p, c_void_p],
+        'gpp_x3_range_snapshot_of': [c_void_p, c_void_p, c_void_p],
+    }),
+    ('gpp_draw_build', 'the pictures of --save-images (csrc/draw.hip)', {
+        'gpp_draw_workspace_bytes': [c_int, c_int, _SIZE_OUT, _SIZE_OUT],
+        'gpp_draw_build': [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
+        'gpp_draw_raster': [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    }),
+    ('gpp_eval_match_f32', 'evaluate(device=True) (csrc/eval.hip)', {
+        'gpp_eval_match_f32': [c_void_p] * 8 + [c_int] * 4 + [c_float, c_int, c_double] + [c_void_p] * 4,
+    }),
+    ('gpp_cuboid_nms_f64', 'cuboid_nms models (csrc/cuboid_nms.hip)', {
+        'gpp_cuboid_nms_f64': [c_void_p, c_int, c_int, c_int, c_double, c_void_p, c_void_p, c_void_p, c_void_p],
+    }),
+    ('gpp_track_f64', 'track models (csrc/track.hip)', {
+        'gpp_track_state_bytes': [_SIZE_OUT],
+        'gpp_track_workspace_bytes': [c_int, _SIZE_OUT],
+        'gpp_track_f64': _TRACK,
+    }),
+    ('gpp_track_optimal_f64', "track models with 'assign': 'optimal'", {
+        'gpp_track_optimal_f64': _TRACK,
+    }),
+    ('gpp_track_ego_f64', 'tracking with ego records', {
+        'gpp_track_ego_workspace_bytes': [c_int, c_int, _SIZE_OUT],
+        'gpp_track_ego_f64': _TRACK_HEAD + [_P(TrackParams), c_void_p, c_int] + _TRACK_TAIL,
+    }),
+    ('gpp_track_kf_f64', "tracking with 'filter': 'kalman'", {
+        'gpp_track_cov_bytes': [_SIZE_OUT],
+        'gpp_track_kf_f64': _TRACK_HEAD + [c_void_p, c_void_p, _P(TrackParams), _P(TrackKfParams), c_void_p, c_int] + _TRACK_TAIL,
+    }),
+    ('gpp_mot_assign', 'evaluate_tracking(device=True) (csrc/mot_eval.hip)', {
+        'gpp_mot_assign': [c_void_p] * 5 + [c_int] * 3 + [_P(MotParams)] + [c_void_p] * 5,
+        'gpp_mot_clear_workspace_bytes': [c_int, _SIZE_OUT],
+        'gpp_mot_clear': [c_void_p] * 5 + [c_int] * 3 + [_HOST_I32, c_int, c_int] + [c_void_p] * 2 + _WORK,
+    }),
+    ('gpp_hota_potential', 'the hota=True scores (csrc/hota_eval.hip)', {
+        'gpp_hota_workspace_bytes': _PAIR_BYTES,
+        'gpp_hota_potential': _FRAME_HEAD + _WORK,
+        'gpp_hota_match': _FRAME_HEAD + [c_void_p] * 2 + _WORK,
+        'gpp_hota_reduce': [c_void_p, c_int, _HOST_I32, c_int, c_ll, c_ll, c_void_p] + _WORK,
+    }),
+    ('gpp_idf1_count', 'the idf1=True scores (csrc/idf1_eval.hip)', {
+        'gpp_idf1_workspace_bytes': _PAIR_BYTES,
+        'gpp_idf1_count': _FRAME_HEAD + _WORK,
+        'gpp_idf1_assign': [_HOST_I32, c_int, c_ll, c_ll, c_void_p, c_void_p] + _WORK,
+    }),
+    ('gpp_kitti_overlaps_f64', 'evaluate_kitti(device=True) and score_poses_on_frames (csrc/kitti_eval.hip)', {
+        'gpp_kitti_overlaps_f64': [c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 2,
+        'gpp_kitti_stats_f64': [c_void_p] * 4 + [_P(c_double)] + [c_void_p] * 2 + [c_int] * 4 + [c_void_p] * 5,
+    }),
+    ('gpp_label_prep_f64', 'prepare_device and polling_ceiling (csrc/label_prep.hip)', {
+        'gpp_label_prep_f64': [c_void_p] * 4 + [c_int, c_int, ctypes.c_uint, c_int] + [c_void_p] * 7,
+    }),
+    ('gpp_poll_costs_u16', "utils/plane_db's device entry points (csrc/plane_db.hip)", {
+        'gpp_poll_costs_workspace_bytes': [c_int, _SIZE_OUT],
+        'gpp_poll_costs_u16': [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p] + _COST_TABLE,
+        'gpp_plane_select_workspace_bytes': [c_int, _SIZE_OUT],
+        'gpp_plane_select': [c_void_p, c_int, c_int, c_int64, c_int] + [c_void_p] * 4 + _WORK,
+    }),
+    ('gpp_pose_costs_u16', "utils/plane_db's objective='location' (DESIGN.md 4.23)", {
+        'gpp_pose_costs_u16': [c_void_p] * 6 + [c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p] + _COST_TABLE,
+        'gpp_plane_select_polled_workspace_bytes': [c_int, _SIZE_OUT],
+        'gpp_plane_select_polled': [c_void_p, c_void_p, c_int, c_int, c_int64, c_int] + [c_void_p] * 5 + _WORK,
+    }),
+    ('gpp_road_score', "utils/road_fit's device entry points (csrc/road_fit.hip)", {
+        'gpp_road_points_i32': [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 3,
+        'gpp_road_score': [c_void_p] * 4 + [c_uint32] + [c_int] * 4 + [c_double] * 4 + [c_void_p] * 2,
+        'gpp_road_winner': [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p],
+        'gpp_road_moments': _ROAD_FRAMES + [c_void_p, c_void_p],
+    }),
+    ('gpp_road_peel_i32', 'several road planes per frame (DESIGN.md 4.24)', {
+        'gpp_road_peel_workspace_bytes': [c_int, c_int, _SIZE_OUT],
+        'gpp_road_peel_i32': _ROAD_FRAMES + [c_void_p] * 2 + _WORK,
+    }),
+    ('gpp_detect_pixel_lists', 'plans with sparse head outputs (csrc/decode.hip)', {
+        'gpp_detect_pixel_lists': [_P(PixelListDesc), c_void_p],
+    }),
+    ('gpp_detect_deep_lists', 'plans of GPP_SPARSE_TOWER_DEPTH >= 2, which do not build without the deep lists (csrc/decode.hip)', {
+        'gpp_detect_deep_lists': [_P(DeepListDesc), c_void_p],
+        'gpp_detect_deep_lists_register': [_P(DeepListDesc)] + _REGISTER,
+        'gpp_detect_deep_lists_release': _RELEASE,
+        'gpp_detect_deep_lists_run': _RUN,
+    }),
+    ('gpp_conv2d_deferred_register', 'plans of GPP_SPARSE_TOWER_DEPTH >= 4: the layer gpp_conv_desc.conv_after names (csrc/conv_igemm.hip)', {
+        'gpp_conv2d_deferred_register': [_CONV] + _REGISTER,
+        'gpp_conv2d_deferred_release': _RELEASE,
+        'gpp_conv2d_deferred_run': _RUN,
+    }),
+    ('gpp_channel_absmax', "the range audit of dtype='f16x3': an audit model's plans, whose ops it refuses", {
+        'gpp_channel_absmax': [_P(AbsmaxDesc), c_void_p],
+        'gpp_absmax_clear': [c_void_p, c_int64, c_void_p],
+    }),
+    ('gpp_stem_pool_fused_x3_ragged', 'ragged plans (per-image heights read from a device table), whose ops it refuses', {
+        'gpp_stem_conv7x7_bn_relu_ragged': _STEM_RAGGED,
+        'gpp_stem_conv7x7_bn_relu_mfma_ragged': _STEM_RAGGED,
+        'gpp_stem_pool_fused_mfma_ragged': _STEM_RAGGED,
+        'gpp_stem_conv7x7_bn_relu_x3_rc_ragged': _STEM_X3_RAGGED,
+        'gpp_stem_pool_fused_x3_ragged': _STEM_X3_RAGGED,
+        'gpp_maxpool3x3s2_same_ragged': [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_void_p],
+        'gpp_preprocess_u8_bgr_ragged': [c_void_p] * 10 + [c_int] * 6 + [c_float] * 3 + [c_void_p],
+    }),
+]
+
+
 def _declare(lib):
-    lib.gpp_version.restype = ctypes.c_char_p
-    lib.gpp_version.argtypes = []
-    lib.gpp_poll_workspace_bytes.restype = c_int
-    lib.gpp_poll_workspace_bytes.argtypes = [c_int, c_int, c_int, ctypes.POINTER(c_size_t)]
-    lib.gpp_poll_f32.restype = c_int
-    lib.gpp_poll_f32.argtypes = [c_void_p] * 5 + [c_int, c_int, c_int, c_int, c_float] + [c_void_p] * 4 + \
-        [c_void_p, c_size_t, c_void_p]
-    lib.gpp_pose_f32.restype = c_int
-    lib.gpp_pose_f32.argtypes = [c_void_p] * 8 + [c_int, c_int, c_float] + [c_void_p] * 3
-    # the --save-images composite (include/gpp.h, csrc/draw.hip; absent from an older build named by GPP_LIB: it runs everything but the pictures)
-    if hasattr(lib, 'gpp_draw_build'):
-        lib.gpp_draw_workspace_bytes.restype = c_int
-        lib.gpp_draw_workspace_bytes.argtypes = [c_int, c_int, ctypes.POINTER(c_size_t), ctypes.POINTER(c_size_t)]
-        lib.gpp_draw_build.restype = c_int
-        lib.gpp_draw_build.argtypes = [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]
-        lib.gpp_draw_raster.restype = c_int
-        lib.gpp_draw_raster.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]
-    # the evaluation's matching (include/gpp.h, csrc/eval.hip; absent from an older build named by GPP_LIB: it runs everything but evaluate(device=True))
-    if hasattr(lib, 'gpp_eval_match_f32'):
-        lib.gpp_eval_match_f32.restype = c_int
-        lib.gpp_eval_match_f32.argtypes = [c_void_p] * 8 + [c_int] * 4 + [c_float, c_int, ctypes.c_double] + [c_void_p] * 4
-    # the cuboid NMS (include/gpp.h, csrc/cuboid_nms.hip; absent from an older build named by GPP_LIB: it runs everything but cuboid_nms models)
-    if hasattr(lib, 'gpp_cuboid_nms_f64'):
-        lib.gpp_cuboid_nms_f64.restype = c_int
-        lib.gpp_cuboid_nms_f64.argtypes = [c_void_p, c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]
-    # the tracker (include/gpp.h, csrc/track.hip; absent from an older build named by GPP_LIB: it runs everything but track models)
-    if hasattr(lib, 'gpp_track_f64'):
-        lib.gpp_track_state_bytes.restype = c_int
-        lib.gpp_track_state_bytes.argtypes = [ctypes.POINTER(c_size_t)]
-        lib.gpp_track_workspace_bytes.restype = c_int
-        lib.gpp_track_workspace_bytes.argtypes = [c_int, ctypes.POINTER(c_size_t)]
-        lib.gpp_track_f64.restype = c_int
-        lib.gpp_track_f64.argtypes = [c_void_p, c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_void_p, c_void_p,
-                                      ctypes.POINTER(TrackParams), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-    # the tracker's optimal assignment (include/gpp.h, csrc/track.hip; absent from an older build named by GPP_LIB: it runs everything but
-    # track models with 'assign': 'optimal')
-    if hasattr(lib, 'gpp_track_optimal_f64'):
-        lib.gpp_track_optimal_f64.restype = c_int
-        lib.gpp_track_optimal_f64.argtypes = lib.gpp_track_f64.argtypes
-    # the tracker's ego-motion compensation (include/gpp.h, csrc/track.hip; absent from an older build named by GPP_LIB: it runs everything
-    # but tracking with ego records)
-    if hasattr(lib, 'gpp_track_ego_f64'):
-        lib.gpp_track_ego_workspace_bytes.restype = c_int
-        lib.gpp_track_ego_workspace_bytes.argtypes = [c_int, c_int, ctypes.POINTER(c_size_t)]
-        lib.gpp_track_ego_f64.restype = c_int
-        lib.gpp_track_ego_f64.argtypes = [c_void_p, c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_void_p, c_void_p,
-                                          ctypes.POINTER(TrackParams), c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                          c_void_p]
-    # the tracker's Kalman filter (include/gpp.h, csrc/track.hip; absent from an older build named by GPP_LIB: it runs everything but
-    # tracking with 'filter': 'kalman')
-    if hasattr(lib, 'gpp_track_kf_f64'):
-        lib.gpp_track_cov_bytes.restype = c_int
-        lib.gpp_track_cov_bytes.argtypes = [ctypes.POINTER(c_size_t)]
-        lib.gpp_track_kf_f64.restype = c_int
-        lib.gpp_track_kf_f64.argtypes = [c_void_p, c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                         ctypes.POINTER(TrackParams), ctypes.POINTER(TrackKfParams), c_void_p, c_int, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_size_t, c_void_p]
-    # the tracking score (include/gpp.h, csrc/mot_eval.hip; absent from an older build named by GPP_LIB: it runs everything but
-    # evaluate_tracking(device=True))
-    if hasattr(lib, 'gpp_mot_assign'):
-        lib.gpp_mot_assign.restype = c_int
-        lib.gpp_mot_assign.argtypes = [c_void_p] * 5 + [c_int] * 3 + [ctypes.POINTER(MotParams)] + [c_void_p] * 5
-        lib.gpp_mot_clear_workspace_bytes.restype = c_int
-        lib.gpp_mot_clear_workspace_bytes.argtypes = [c_int, ctypes.POINTER(c_size_t)]
-        lib.gpp_mot_clear.restype = c_int
-        lib.gpp_mot_clear.argtypes = [c_void_p] * 5 + [c_int] * 3 + [ctypes.POINTER(ctypes.c_int32), c_int, c_int] + [c_void_p] * 3 + \
-            [c_size_t, c_void_p]
-    # HOTA (include/gpp.h, csrc/hota_eval.hip; absent from an older build named by GPP_LIB: it runs everything but the hota=True scores)
-    if hasattr(lib, 'gpp_hota_potential'):
-        c_ll = ctypes.c_longlong
-        lib.gpp_hota_workspace_bytes.restype = c_int
-        lib.gpp_hota_workspace_bytes.argtypes = [c_ll, c_ll, c_int, c_int, ctypes.POINTER(c_size_t)]
-        lib.gpp_hota_potential.restype = c_int
-        lib.gpp_hota_potential.argtypes = [c_void_p] * 5 + [c_int] * 4 + [ctypes.POINTER(ctypes.c_int32), c_ll, c_ll, c_void_p, c_size_t, c_void_p]
-        lib.gpp_hota_match.restype = c_int
-        lib.gpp_hota_match.argtypes = [c_void_p] * 5 + [c_int] * 4 + [ctypes.POINTER(ctypes.c_int32), c_ll, c_ll, c_void_p, c_void_p, c_void_p,
-                                       c_size_t, c_void_p]
-        lib.gpp_hota_reduce.restype = c_int
-        lib.gpp_hota_reduce.argtypes = [c_void_p, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_ll, c_ll, c_void_p, c_void_p, c_size_t, c_void_p]
-    # IDF1 (include/gpp.h, csrc/idf1_eval.hip; absent from an older build named by GPP_LIB: it runs everything but the idf1=True scores)
-    if hasattr(lib, 'gpp_idf1_count'):
-        c_ll = ctypes.c_longlong
-        lib.gpp_idf1_workspace_bytes.restype = c_int
-        lib.gpp_idf1_workspace_bytes.argtypes = [c_ll, c_ll, c_int, c_int, ctypes.POINTER(c_size_t)]
-        lib.gpp_idf1_count.restype = c_int
-        lib.gpp_idf1_count.argtypes = [c_void_p] * 5 + [c_int] * 4 + [ctypes.POINTER(ctypes.c_int32), c_ll, c_ll, c_void_p, c_size_t, c_void_p]
-        lib.gpp_idf1_assign.restype = c_int
-        lib.gpp_idf1_assign.argtypes = [ctypes.POINTER(ctypes.c_int32), c_int, c_ll, c_ll, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-    # KITTI's object benchmark (include/gpp.h, csrc/kitti_eval.hip; absent from an older build named by GPP_LIB: it runs everything but
-    # evaluate_kitti(device=True) and score_poses_on_frames)
-    if hasattr(lib, 'gpp_kitti_overlaps_f64'):
-        lib.gpp_kitti_overlaps_f64.restype = c_int
-        lib.gpp_kitti_overlaps_f64.argtypes = [c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 2
-        lib.gpp_kitti_stats_f64.restype = c_int
-        lib.gpp_kitti_stats_f64.argtypes = [c_void_p] * 4 + [ctypes.POINTER(ctypes.c_double)] + [c_void_p] * 2 + [c_int] * 4 + [c_void_p] * 5
-    # the keypoint labels (include/gpp.h, csrc/label_prep.hip; absent from an older build named by GPP_LIB: it runs everything but
-    # prepare_device and polling_ceiling)
-    if hasattr(lib, 'gpp_label_prep_f64'):
-        lib.gpp_label_prep_f64.restype = c_int
-        lib.gpp_label_prep_f64.argtypes = [c_void_p] * 4 + [c_int, c_int, ctypes.c_uint, c_int] + [c_void_p] * 7
-    # the plane-database distillation (include/gpp.h, csrc/plane_db.hip; absent from an older build named by GPP_LIB: it runs everything but
-    # utils/plane_db's device entry points)
-    if hasattr(lib, 'gpp_poll_costs_u16'):
-        lib.gpp_poll_costs_workspace_bytes.restype = c_int
-        lib.gpp_poll_costs_workspace_bytes.argtypes = [c_int, ctypes.POINTER(c_size_t)]
-        lib.gpp_poll_costs_u16.restype = c_int
-        lib.gpp_poll_costs_u16.argtypes = [c_void_p] * 5 + [c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_int64, c_int64,
-                                           c_void_p, c_size_t, c_void_p]
-        lib.gpp_plane_select_workspace_bytes.restype = c_int
-        lib.gpp_plane_select_workspace_bytes.argtypes = [c_int, ctypes.POINTER(c_size_t)]
-        lib.gpp_plane_select.restype = c_int
-        lib.gpp_plane_select.argtypes = [c_void_p, c_int, c_int, c_int64, c_int] + [c_void_p] * 4 + [c_void_p, c_size_t, c_void_p]
-    # the distillation for the polled location error (absent from an older build: utils/plane_db's objective='location' needs it)
-    if hasattr(lib, 'gpp_pose_costs_u16'):
-        lib.gpp_pose_costs_u16.restype = c_int
-        lib.gpp_pose_costs_u16.argtypes = [c_void_p] * 6 + [c_int, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int64,
-                                           c_void_p, c_size_t, c_void_p]
-        lib.gpp_plane_select_polled_workspace_bytes.restype = c_int
-        lib.gpp_plane_select_polled_workspace_bytes.argtypes = [c_int, ctypes.POINTER(c_size_t)]
-        lib.gpp_plane_select_polled.restype = c_int
-        lib.gpp_plane_select_polled.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int64, c_int] + [c_void_p] * 5 + [c_void_p, c_size_t, c_void_p]
-    # the per-frame road-plane fit (include/gpp.h, csrc/road_fit.hip; absent from an older build named by GPP_LIB: it runs everything but
-    # utils/road_fit's device entry points)
-    if hasattr(lib, 'gpp_road_score'):
-        c_double, c_uint32 = ctypes.c_double, ctypes.c_uint32
-        lib.gpp_road_points_i32.restype = c_int
-        lib.gpp_road_points_i32.argtypes = [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 3
-        lib.gpp_road_score.restype = c_int
-        lib.gpp_road_score.argtypes = [c_void_p] * 4 + [c_uint32] + [c_int] * 4 + [c_double] * 4 + [c_void_p] * 2
-        lib.gpp_road_winner.restype = c_int
-        lib.gpp_road_winner.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
-        lib.gpp_road_moments.restype = c_int
-        lib.gpp_road_moments.argtypes = [c_void_p] * 4 + [c_uint32, c_void_p] + [c_int] * 4 + [c_double, c_void_p, c_void_p]
-    # several planes per frame (absent from a build older than that section)
-    if hasattr(lib, 'gpp_road_peel_i32'):
-        lib.gpp_road_peel_workspace_bytes.restype = c_int
-        lib.gpp_road_peel_workspace_bytes.argtypes = [c_int, c_int, ctypes.POINTER(c_size_t)]
-        lib.gpp_road_peel_i32.restype = c_int
-        lib.gpp_road_peel_i32.argtypes = [c_void_p] * 4 + [c_uint32, c_void_p] + [c_int] * 4 + [c_double] + [c_void_p] * 3 + [c_size_t, c_void_p]
-    if hasattr(lib, 'gpp_detect_pixel_lists'):
-        lib.gpp_detect_pixel_lists.restype = c_int
-        lib.gpp_detect_pixel_lists.argtypes = [ctypes.POINTER(PixelListDesc), c_void_p]
-    # the deep lists of the sparse regression tower (include/gpp.h, csrc/decode.hip; absent from an older build named by GPP_LIB: it runs
-    # every plan but one of GPP_SPARSE_TOWER_DEPTH >= 2, which does not build on it)
-    if hasattr(lib, 'gpp_detect_deep_lists'):
-        lib.gpp_detect_deep_lists.restype = c_int
-        lib.gpp_detect_deep_lists.argtypes = [ctypes.POINTER(DeepListDesc), c_void_p]
-        lib.gpp_detect_deep_lists_register.restype = c_int
-        lib.gpp_detect_deep_lists_register.argtypes = [ctypes.POINTER(DeepListDesc), ctypes.POINTER(ctypes.c_int32)]
-        lib.gpp_detect_deep_lists_release.restype = c_int
-        lib.gpp_detect_deep_lists_release.argtypes = [ctypes.c_int32]
-        lib.gpp_detect_deep_lists_run.restype = c_int
-        lib.gpp_detect_deep_lists_run.argtypes = [ctypes.c_int32, c_int, c_void_p]
-    # ... and the layer gpp_conv_desc.conv_after names (csrc/conv_igemm.hip; a plan of GPP_SPARSE_TOWER_DEPTH >= 4 does not build without it)
-    if hasattr(lib, 'gpp_conv2d_deferred_register'):
-        lib.gpp_conv2d_deferred_register.restype = c_int
-        lib.gpp_conv2d_deferred_register.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_int32)]
-        lib.gpp_conv2d_deferred_release.restype = c_int
-        lib.gpp_conv2d_deferred_release.argtypes = [ctypes.c_int32]
-        lib.gpp_conv2d_deferred_run.restype = c_int
-        lib.gpp_conv2d_deferred_run.argtypes = [ctypes.c_int32, c_int, c_void_p]
-    lib.gpp_conv2d_igemm.restype = c_int
-    lib.gpp_conv2d_igemm.argtypes = [ctypes.POINTER(ConvDesc), c_void_p]
-    lib.gpp_stem_conv7x7_bn_relu.restype = c_int
-    lib.gpp_stem_conv7x7_bn_relu.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
-    lib.gpp_stem_conv7x7_bn_relu_mfma.restype = c_int
-    lib.gpp_stem_conv7x7_bn_relu_mfma.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
-    lib.gpp_stem_pack_weights_f16.restype = c_int
-    lib.gpp_stem_pack_weights_f16.argtypes = [c_void_p, c_void_p, c_size_t]
-    lib.gpp_stem_pack_weights_f16x3.restype = c_int
-    lib.gpp_stem_pack_weights_f16x3.argtypes = [c_void_p, c_void_p, c_size_t]
-    lib.gpp_stem_conv7x7_bn_relu_x3.restype = c_int
-    lib.gpp_stem_conv7x7_bn_relu_x3.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
-    lib.gpp_stem_pool_fused_mfma.restype = c_int
-    lib.gpp_stem_pool_fused_mfma.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
-    lib.gpp_maxpool3x3s2_same.restype = c_int
-    lib.gpp_maxpool3x3s2_same.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]
-    # DenseNet (include/gpp.h): the pre-activation 1x1 conv and the two pools that write into a channel slice
-    lib.gpp_conv2d_preact.restype = c_int
-    lib.gpp_conv2d_preact.argtypes = [ctypes.POINTER(ConvDesc), c_void_p, c_void_p, c_void_p]
-    lib.gpp_conv2d_preact_tile_candidates.restype = c_int
-    lib.gpp_conv2d_preact_tile_candidates.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_int)]
-    lib.gpp_conv2d_preact_autotune.restype = c_int
-    lib.gpp_conv2d_preact_autotune.argtypes = [ctypes.POINTER(ConvDesc), c_void_p, c_void_p, c_int, c_void_p, ctypes.POINTER(c_float)]
-    lib.gpp_maxpool3x3s2_pad_f32.restype = c_int
-    lib.gpp_maxpool3x3s2_pad_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
-    lib.gpp_avgpool2x2_f32.restype = c_int
-    lib.gpp_avgpool2x2_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]
-    # MobileNet (include/gpp.h): the fused depthwise-separable block and the 3x3 / 2 stem
-    lib.gpp_mobilenet_block.restype = c_int
-    lib.gpp_mobilenet_block.argtypes = [ctypes.POINTER(MobileNetBlockDesc), c_void_p]
-    lib.gpp_mobilenet_block_tile_candidates.restype = c_int
-    lib.gpp_mobilenet_block_tile_candidates.argtypes = [ctypes.POINTER(MobileNetBlockDesc), ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_int)]
-    lib.gpp_mobilenet_block_autotune.restype = c_int
-    lib.gpp_mobilenet_block_autotune.argtypes = [ctypes.POINTER(MobileNetBlockDesc), c_int, c_void_p, ctypes.POINTER(c_float)]
-    lib.gpp_mobilenet_stem.restype = c_int
-    lib.gpp_mobilenet_stem.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]
-    lib.gpp_mobilenet_depthwise.restype = c_int
-    lib.gpp_mobilenet_depthwise.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
-    # the range audit of dtype='f16x3' (include/gpp.h): per-channel abs-max of one map, and the clearing of its table
-    # (GPP_LIB may name an older build for a same-box A/B, tools/ab_bench.sh: it runs every plan but an audit model's, whose ops it refuses)
-    if hasattr(lib, 'gpp_channel_absmax'):
-        lib.gpp_channel_absmax.restype = c_int
-        lib.gpp_channel_absmax.argtypes = [ctypes.POINTER(AbsmaxDesc), c_void_p]
-        lib.gpp_absmax_clear.restype = c_int
-        lib.gpp_absmax_clear.argtypes = [c_void_p, c_int64, c_void_p]
-    # ragged batches (include/gpp.h): the stem, pool1 and the preprocessing with per-image heights read from a device table
-    # (absent from an older build named by GPP_LIB: it runs every plan but a ragged one, whose ops it refuses)
-    if hasattr(lib, 'gpp_stem_pool_fused_x3_ragged'):
-        for name in ('gpp_stem_conv7x7_bn_relu_ragged', 'gpp_stem_conv7x7_bn_relu_mfma_ragged', 'gpp_stem_pool_fused_mfma_ragged'):
-            getattr(lib, name).restype = c_int
-            getattr(lib, name).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
-        for name in ('gpp_stem_conv7x7_bn_relu_x3_rc_ragged', 'gpp_stem_pool_fused_x3_ragged'):
-            getattr(lib, name).restype = c_int
-            getattr(lib, name).argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
-        lib.gpp_maxpool3x3s2_same_ragged.restype = c_int
-        lib.gpp_maxpool3x3s2_same_ragged.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
-        lib.gpp_preprocess_u8_bgr_ragged.restype = c_int
-        lib.gpp_preprocess_u8_bgr_ragged.argtypes = [c_void_p] * 10 + [c_int] * 6 + [c_float] * 3 + [c_void_p]
-    lib.gpp_relu.restype = c_int
-    lib.gpp_relu.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_void_p]
-    lib.gpp_preprocess_u8_bgr.restype = c_int
-    lib.gpp_preprocess_u8_bgr.argtypes = [c_void_p] * 8 + [c_int] * 5 + [c_float] * 3 + [c_void_p]
-    lib.gpp_detect_workspace_bytes.restype = c_int
-    lib.gpp_detect_workspace_bytes.argtypes = [c_int, c_int64, ctypes.POINTER(c_size_t)]
-    lib.gpp_detect_f32.restype = c_int
-    lib.gpp_detect_f32.argtypes = [c_void_p] * 4 + [c_int, c_int64, c_int, c_int, c_float, c_float, c_int] + \
-        [c_void_p] * 7 + [c_void_p, c_size_t, c_void_p]
-    lib.gpp_detect_osf_workspace_bytes.restype = c_int
-    lib.gpp_detect_osf_workspace_bytes.argtypes = lib.gpp_detect_workspace_bytes.argtypes
-    lib.gpp_detect_osf_f32.restype = c_int
-    lib.gpp_detect_osf_f32.argtypes = lib.gpp_detect_f32.argtypes
-    lib.gpp_pack_detections.restype = c_int
-    lib.gpp_pack_detections.argtypes = [c_void_p] * 8 + [c_int, c_int, c_void_p, c_void_p]
-    lib.gpp_detect_stages_f32.restype = c_int
-    lib.gpp_detect_stages_f32.argtypes = [c_int] + lib.gpp_detect_f32.argtypes
-    lib.gpp_conv2d_flops.restype = c_int
-    lib.gpp_conv2d_flops.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_double)]
-    lib.gpp_conv2d_split_rule.restype = c_int
-    lib.gpp_conv2d_split_rule.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(c_int)]
-    lib.gpp_conv2d_workspace_bytes.restype = c_int
-    lib.gpp_conv2d_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(c_size_t)]
-    lib.gpp_plan_run.restype = c_int
-    lib.gpp_plan_run.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int]
-    lib.gpp_event_create.restype = c_int
-    lib.gpp_event_create.argtypes = [ctypes.POINTER(c_void_p)]
-    lib.gpp_event_destroy.restype = c_int
-    lib.gpp_event_destroy.argtypes = [c_void_p]
-    lib.gpp_event_elapsed_ms.restype = c_int
-    lib.gpp_event_elapsed_ms.argtypes = [c_void_p, c_void_p, ctypes.POINTER(c_float)]
-    lib.gpp_conv2d_tile_candidates.restype = c_int
-    lib.gpp_conv2d_tile_candidates.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_int)]
-    lib.gpp_x3_range_events.restype = c_int
-    lib.gpp_x3_range_events.argtypes = [ctypes.POINTER(ctypes.c_uint64), c_int]
-    lib.gpp_x3_range_snapshot.restype = c_int
-    lib.gpp_x3_range_snapshot.argtypes = [c_void_p, c_void_p]
-    lib.gpp_x3_range_snapshot_of.restype = c_int
-    lib.gpp_x3_range_snapshot_of.argtypes = [c_void_p, c_void_p, c_void_p]
-    lib.gpp_stem_conv7x7_bn_relu_x3_rc.restype = c_int
-    lib.gpp_stem_conv7x7_bn_relu_x3_rc.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
-    lib.gpp_stem_pool_fused_x3.restype = c_int
-    lib.gpp_stem_pool_fused_x3.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
-    lib.gpp_bottleneck_block.restype = c_int
-    lib.gpp_bottleneck_block.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), c_int, c_void_p]
-    lib.gpp_bottleneck_block_proj.restype = c_int
-    lib.gpp_bottleneck_block_proj.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc),
-                                              c_int, c_void_p]
-    lib.gpp_conv2d_autotune.restype = c_int
-    lib.gpp_conv2d_autotune.argtypes = [ctypes.POINTER(ConvDesc), c_int, c_void_p, ctypes.POINTER(c_float)]
+    for probe, _, functions in _SIGNATURES:
+        if probe is None or hasattr(lib, probe):
+            for name, argtypes in functions.items():
+                fn = getattr(lib, name)
+                fn.restype = ctypes.c_char_p if name == 'gpp_version' else c_int
+                fn.argtypes = argtypes
 
 
 def build(verbose=False):
@@ -504,6 +426,30 @@ def ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _entry(name):
+    """ The entry point `name` of the loaded library; GppError when the build lacks it (there is no other path). """
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        what = next(what for _, what, functions in _SIGNATURES if name in functions)
+        raise GppError('{} is not in {}: that build runs everything but {}'.format(name, LIB_PATH, what))
+    return fn
+
+
+def _bytes(name, *args):
+    """ What the entry point `name`, whose last argument is a size_t*, answers for `args`. """
+    n = c_size_t(0)
+    check(_entry(name)(*(args + (ctypes.byref(n),))), name)
+    return n.value
+
+
+def _check_tensors(what, dev, want, contiguous=False):
+    """ ValueError unless every (tensor, dtype, shape) of `want` is that, on `dev` (and dense, where the entry point `what` needs it) """
+    for t, dtype, shape in want:
+        if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev or (contiguous and not t.is_contiguous()):
+            raise ValueError('{}: expected {}{} {} on {}, got {} {} on {}'.format(what, 'contiguous ' if contiguous else '', shape, dtype, dev,
+                                                                                 tuple(t.shape), t.dtype, t.device))
+
+
 def draw_workspace_bytes(B, D):
     """ (bytes of the primitive table, bytes of the raster's workspace) for B images of D rows each """
     prims, work = c_size_t(0), c_size_t(0)
@@ -544,12 +490,10 @@ def eval_match(boxes, dims, scores, labels, orientations, scales, annotations, a
     import torch
     B, D = int(scores.shape[0]), int(scores.shape[1])
     A = int(annotations.shape[1])
-    want = ((boxes, torch.float32, (B, D, 12)), (dims, torch.float32, (B, D, 3)), (scores, torch.float32, (B, D)), (labels, torch.int32, (B, D)),
-            (orientations, torch.int32, (B, D)), (scales, torch.float32, (B,)), (annotations, torch.float64, (B, A, GPP_EVAL_ANN_COLS)),
-            (ann_counts, torch.int32, (B,)))
-    for t, dtype, shape in want:
-        if t.dtype != dtype or tuple(t.shape) != shape or t.device != scores.device:
-            raise ValueError('gpp_eval_match_f32: expected {} {} on {}, got {} {} on {}'.format(shape, dtype, scores.device, tuple(t.shape), t.dtype, t.device))
+    _check_tensors('gpp_eval_match_f32', scores.device, (
+        (boxes, torch.float32, (B, D, 12)), (dims, torch.float32, (B, D, 3)), (scores, torch.float32, (B, D)), (labels, torch.int32, (B, D)),
+        (orientations, torch.int32, (B, D)), (scales, torch.float32, (B,)), (annotations, torch.float64, (B, A, GPP_EVAL_ANN_COLS)),
+        (ann_counts, torch.int32, (B,))))
     table = torch.empty((B, D, 3), dtype=torch.int32, device=scores.device)
     errors = torch.empty((B, D, GPP_EVAL_ERR_COLS), dtype=torch.float64, device=scores.device)
     counts = torch.empty((B,), dtype=torch.int32, device=scores.device)
@@ -565,10 +509,8 @@ def _kitti_check(rows, labels, label_counts, what):
         raise ValueError('{}: rows must be (B, D, {}) and labels (B, A, {}), got {} and {}'.format(
             what, GPP_POSE_COLS, GPP_KITTI_LABEL_COLS, tuple(rows.shape), tuple(labels.shape)))
     B, D, A = int(rows.shape[0]), int(rows.shape[1]), int(labels.shape[1])
-    want = ((rows, torch.float32, (B, D, GPP_POSE_COLS)), (labels, torch.float64, (B, A, GPP_KITTI_LABEL_COLS)), (label_counts, torch.int32, (B,)))
-    for t, dtype, shape in want:
-        if t.dtype != dtype or tuple(t.shape) != shape or t.device != rows.device:
-            raise ValueError('{}: expected {} {} on {}, got {} {} on {}'.format(what, shape, dtype, rows.device, tuple(t.shape), t.dtype, t.device))
+    _check_tensors(what, rows.device, ((rows, torch.float32, (B, D, GPP_POSE_COLS)), (labels, torch.float64, (B, A, GPP_KITTI_LABEL_COLS)),
+                                       (label_counts, torch.int32, (B,))))
     return B, D, A
 
 
@@ -589,10 +531,9 @@ def kitti_stats(rows, labels, label_counts, overlaps, min_overlap, thresholds=No
     similarity (B, 3, 3, T) float64).  Everything stays on the device; no synchronisation """
     import torch
     B, D, A = _kitti_check(rows, labels, label_counts, 'gpp_kitti_stats_f64')
-    if overlaps.dtype != torch.float64 or tuple(overlaps.shape) != (B, 4, D, A) or overlaps.device != rows.device:
-        raise ValueError('gpp_kitti_stats_f64: overlaps must be {} float64, got {} {}'.format((B, 4, D, A), tuple(overlaps.shape), overlaps.dtype))
-    mo = (ctypes.c_double * 3)(*[float(v) for v in min_overlap])
     dev = rows.device
+    _check_tensors('gpp_kitti_stats_f64', dev, ((overlaps, torch.float64, (B, 4, D, A)),))
+    mo = (ctypes.c_double * 3)(*[float(v) for v in min_overlap])
     if thresholds is None:
         tp_scores = torch.full((B, 3, 3, A), float('nan'), dtype=torch.float32, device=dev)
         n_gt = torch.zeros((B, 3, 3), dtype=torch.int32, device=dev)
@@ -600,9 +541,7 @@ def kitti_stats(rows, labels, label_counts, overlaps, min_overlap, thresholds=No
                                         ptr(tp_scores), ptr(n_gt), None, None, stream_ptr()), 'gpp_kitti_stats_f64')
         return tp_scores, n_gt
     T = int(thresholds.shape[2])
-    if thresholds.dtype != torch.float32 or tuple(thresholds.shape) != (3, 3, T) or n_thresholds.dtype != torch.int32 or \
-            tuple(n_thresholds.shape) != (3, 3) or thresholds.device != dev or n_thresholds.device != dev:
-        raise ValueError('gpp_kitti_stats_f64: thresholds must be (3, 3, T) float32 and n_thresholds (3, 3) int32 on {}'.format(dev))
+    _check_tensors('gpp_kitti_stats_f64', dev, ((thresholds, torch.float32, (3, 3, T)), (n_thresholds, torch.int32, (3, 3))))
     stats = torch.zeros((B, 3, 3, T, 3), dtype=torch.int32, device=dev)
     similarity = torch.zeros((B, 3, 3, T), dtype=torch.float64, device=dev)
     check(lib().gpp_kitti_stats_f64(ptr(rows), ptr(labels), ptr(label_counts), ptr(overlaps), mo, ptr(thresholds), ptr(n_thresholds),
@@ -622,41 +561,27 @@ def cuboid_nms(rows, metric, threshold, out=None, counts=None, suppressor=None):
     out = torch.empty_like(rows) if out is None else out
     counts = torch.zeros((B,), dtype=torch.int32, device=dev) if counts is None else counts
     suppressor = torch.full((B, D), -1, dtype=torch.int32, device=dev) if suppressor is None else suppressor
-    want = ((out, torch.float32, (B, D, GPP_POSE_COLS)), (counts, torch.int32, (B,)), (suppressor, torch.int32, (B, D)))
-    for t, dtype, shape in want:
-        if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev:
-            raise ValueError('gpp_cuboid_nms_f64: expected {} {} on {}, got {} {} on {}'.format(shape, dtype, dev, tuple(t.shape), t.dtype, t.device))
+    _check_tensors('gpp_cuboid_nms_f64', dev, ((out, torch.float32, (B, D, GPP_POSE_COLS)), (counts, torch.int32, (B,)),
+                                               (suppressor, torch.int32, (B, D))))
     check(lib().gpp_cuboid_nms_f64(ptr(rows), B, D, int(metric), float(threshold), ptr(out), ptr(counts), ptr(suppressor), stream_ptr()),
           'gpp_cuboid_nms_f64')
     return out, counts, suppressor
 
 
 def track_state_bytes():
-    n = c_size_t(0)
-    check(lib().gpp_track_state_bytes(ctypes.byref(n)), 'gpp_track_state_bytes')
-    return n.value
+    return _bytes('gpp_track_state_bytes')
 
 
 def track_workspace_bytes(S):
-    n = c_size_t(0)
-    check(lib().gpp_track_workspace_bytes(int(S), ctypes.byref(n)), 'gpp_track_workspace_bytes')
-    return n.value
+    return _bytes('gpp_track_workspace_bytes', int(S))
 
 
 def track_ego_workspace_bytes(S, N):
-    if not hasattr(lib(), 'gpp_track_ego_f64'):
-        raise GppError('gpp_track_ego_f64 is not in {}: there is no other path for ego records'.format(LIB_PATH))
-    n = c_size_t(0)
-    check(lib().gpp_track_ego_workspace_bytes(int(S), int(N), ctypes.byref(n)), 'gpp_track_ego_workspace_bytes')
-    return n.value
+    return _bytes('gpp_track_ego_workspace_bytes', int(S), int(N))
 
 
 def track_cov_bytes():
-    if not hasattr(lib(), 'gpp_track_kf_f64'):
-        raise GppError("gpp_track_kf_f64 is not in {}: there is no other path for 'filter': 'kalman'".format(LIB_PATH))
-    n = c_size_t(0)
-    check(lib().gpp_track_cov_bytes(ctypes.byref(n)), 'gpp_track_cov_bytes')
-    return n.value
+    return _bytes('gpp_track_cov_bytes')
 
 
 def track(rows, state_in, params, seq_start=None, state_out=None, out=None, ids=None, hits=None, workspace=None, optimal=False, ego=None,
@@ -694,37 +619,31 @@ def track(rows, state_in, params, seq_start=None, state_out=None, out=None, ids=
     need = track_workspace_bytes(S) if ego is None and kf is None else track_ego_workspace_bytes(S, N)
     if kf is not None:
         cbytes = track_cov_bytes()
-        if cov_in is None or cov_in.dim() != 2 or cov_in.dtype != torch.uint8 or tuple(cov_in.shape) != (S, cbytes) or cov_in.device != dev:
+        if cov_in is None:
             raise ValueError('gpp_track_kf_f64: the covariance must be ({}, {}) uint8 on {}'.format(S, cbytes, dev))
         cov_out = torch.empty_like(cov_in) if cov_out is None else cov_out
-        if cov_out.dtype != torch.uint8 or tuple(cov_out.shape) != (S, cbytes) or cov_out.device != dev:
-            raise ValueError('gpp_track_kf_f64: cov_out must be ({}, {}) uint8 on {}'.format(S, cbytes, dev))
+        _check_tensors('gpp_track_kf_f64', dev, ((cov_in, torch.uint8, (S, cbytes)), (cov_out, torch.uint8, (S, cbytes))))
     elif cov_in is not None or cov_out is not None:
         raise ValueError('gpp_track_f64: a covariance belongs to gpp_track_kf_f64 (kf=TrackKfParams)')
     workspace = torch.empty((need,), dtype=torch.uint8, device=dev) if workspace is None else workspace
-    want = ((out, torch.float32, (N, D, GPP_POSE_COLS)), (ids, torch.int32, (N, D)), (hits, torch.int32, (N, D)),
-            (state_out, torch.uint8, (S, nbytes)))
-    for t, dtype, shape in want:
-        if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev:
-            raise ValueError('gpp_track_f64: expected {} {} on {}, got {} {} on {}'.format(shape, dtype, dev, tuple(t.shape), t.dtype, t.device))
+    _check_tensors('gpp_track_f64', dev, ((out, torch.float32, (N, D, GPP_POSE_COLS)), (ids, torch.int32, (N, D)), (hits, torch.int32, (N, D)),
+                                          (state_out, torch.uint8, (S, nbytes))))
     if workspace.dtype != torch.uint8 or workspace.device != dev:
         raise ValueError('gpp_track_f64: the workspace must be uint8 on {}'.format(dev))
     name = 'gpp_track_kf_f64' if kf is not None else 'gpp_track_ego_f64' if ego is not None else 'gpp_track_optimal_f64' if optimal else 'gpp_track_f64'
-    if not hasattr(lib(), name):
-        raise GppError('{} is not in {}: there is no other path for this assignment'.format(name, LIB_PATH))
+    fn = _entry(name)
+    # the four argument lists of include/gpp.h differ in the middle: the head and the tail are one
+    args = [ptr(rows), N, D, seq, S, ptr(state_in), ptr(state_out)]
     if kf is not None:
-        check(lib().gpp_track_kf_f64(ptr(rows), N, D, seq, S, ptr(state_in), ptr(state_out), ptr(cov_in), ptr(cov_out), ctypes.byref(params),
-                                     ctypes.byref(kf), None if ego is None else ego.ctypes.data_as(c_void_p), int(bool(optimal)), ptr(out),
-                                     ptr(ids), ptr(hits), ptr(workspace), int(workspace.numel()), stream_ptr()), name)
-        return out, ids, hits, state_out, cov_out
-    if ego is not None:
-        check(lib().gpp_track_ego_f64(ptr(rows), N, D, seq, S, ptr(state_in), ptr(state_out), ctypes.byref(params),
-                                      ego.ctypes.data_as(c_void_p), int(bool(optimal)), ptr(out), ptr(ids), ptr(hits), ptr(workspace),
-                                      int(workspace.numel()), stream_ptr()), name)
-        return out, ids, hits, state_out
-    check(getattr(lib(), name)(ptr(rows), N, D, seq, S, ptr(state_in), ptr(state_out), ctypes.byref(params), ptr(out), ptr(ids), ptr(hits),
-                               ptr(workspace), int(workspace.numel()), stream_ptr()), name)
-    return out, ids, hits, state_out
+        args += [ptr(cov_in), ptr(cov_out)]
+    args.append(ctypes.byref(params))
+    if kf is not None:
+        args.append(ctypes.byref(kf))
+    if kf is not None or ego is not None:
+        args += [None if ego is None else ego.ctypes.data_as(c_void_p), int(bool(optimal))]
+    args += [ptr(out), ptr(ids), ptr(hits), ptr(workspace), int(workspace.numel()), stream_ptr()]
+    check(fn(*args), name)
+    return (out, ids, hits, state_out) if kf is None else (out, ids, hits, state_out, cov_out)
 
 
 def mot_assign(overlaps, labels, label_counts, rows, ids, params):
@@ -734,9 +653,7 @@ def mot_assign(overlaps, labels, label_counts, rows, ids, params):
     import torch
     N, D, A = _kitti_check(rows, labels, label_counts, 'gpp_mot_assign')
     dev = rows.device
-    for t, dtype, shape in ((overlaps, torch.float64, (N, 4, D, A)), (ids, torch.int32, (N, D))):
-        if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev:
-            raise ValueError('gpp_mot_assign: expected {} {} on {}, got {} {} on {}'.format(shape, dtype, dev, tuple(t.shape), t.dtype, t.device))
+    _check_tensors('gpp_mot_assign', dev, ((overlaps, torch.float64, (N, 4, D, A)), (ids, torch.int32, (N, D))))
     match = torch.full((N, A), -1, dtype=torch.int32, device=dev)
     label_outcome = torch.zeros((N, A), dtype=torch.int32, device=dev)
     row_outcome = torch.zeros((N, D), dtype=torch.int32, device=dev)
@@ -747,9 +664,7 @@ def mot_assign(overlaps, labels, label_counts, rows, ids, params):
 
 
 def mot_clear_workspace_bytes(S):
-    n = c_size_t(0)
-    check(lib().gpp_mot_clear_workspace_bytes(int(S), ctypes.byref(n)), 'gpp_mot_clear_workspace_bytes')
-    return n.value
+    return _bytes('gpp_mot_clear_workspace_bytes', int(S))
 
 
 def mot_clear(match, label_outcome, traj, ids, frame_counts, seq_start, max_traj):
@@ -759,11 +674,8 @@ def mot_clear(match, label_outcome, traj, ids, frame_counts, seq_start, max_traj
     import torch
     N, A, D = int(match.shape[0]), int(match.shape[1]), int(ids.shape[1])
     dev = match.device
-    want = ((match, torch.int32, (N, A)), (label_outcome, torch.int32, (N, A)), (traj, torch.int32, (N, A)), (ids, torch.int32, (N, D)),
-            (frame_counts, torch.int64, (N, GPP_MOT_FRAME_COUNTS)))
-    for t, dtype, shape in want:
-        if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev:
-            raise ValueError('gpp_mot_clear: expected {} {} on {}, got {} {} on {}'.format(shape, dtype, dev, tuple(t.shape), t.dtype, t.device))
+    _check_tensors('gpp_mot_clear', dev, ((match, torch.int32, (N, A)), (label_outcome, torch.int32, (N, A)), (traj, torch.int32, (N, A)),
+                                          (ids, torch.int32, (N, D)), (frame_counts, torch.int64, (N, GPP_MOT_FRAME_COUNTS))))
     S = len(seq_start) - 1
     seq = (ctypes.c_int32 * (S + 1))(*[int(v) for v in seq_start])
     seq_counts = torch.zeros((S, GPP_MOT_SEQ_COUNTS), dtype=torch.int64, device=dev)
@@ -775,9 +687,7 @@ def mot_clear(match, label_outcome, traj, ids, frame_counts, seq_start, max_traj
 
 
 def hota_workspace_bytes(cells, vecs, max_frames, S):
-    n = c_size_t(0)
-    check(lib().gpp_hota_workspace_bytes(int(cells), int(vecs), int(max_frames), int(S), ctypes.byref(n)), 'gpp_hota_workspace_bytes')
-    return n.value
+    return _bytes('gpp_hota_workspace_bytes', int(cells), int(vecs), int(max_frames), int(S))
 
 
 def hota_workspace(cells, vecs, max_frames, S, device):
@@ -806,7 +716,7 @@ def _host_table(what, table, lines, cols):
 
 
 def _table_ptr(table):
-    return table.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+    return table.ctypes.data_as(_HOST_I32)
 
 
 def _hota_frames(what, overlaps, label_outcome, row_outcome, traj, trk, frame_tab, workspace):
@@ -815,11 +725,8 @@ def _hota_frames(what, overlaps, label_outcome, row_outcome, traj, trk, frame_ta
         raise ValueError('{}: overlaps must be (N, 4, D, A), got {}'.format(what, tuple(overlaps.shape)))
     N, D, A = int(overlaps.shape[0]), int(overlaps.shape[2]), int(overlaps.shape[3])
     dev = overlaps.device
-    want = ((overlaps, torch.float64, (N, 4, D, A)), (label_outcome, torch.int32, (N, A)), (row_outcome, torch.int32, (N, D)),
-            (traj, torch.int32, (N, A)), (trk, torch.int32, (N, D)))
-    for t, dtype, shape in want:
-        if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev:
-            raise ValueError('{}: expected {} {} on {}, got {} {} on {}'.format(what, shape, dtype, dev, tuple(t.shape), t.dtype, t.device))
+    _check_tensors(what, dev, ((overlaps, torch.float64, (N, 4, D, A)), (label_outcome, torch.int32, (N, A)), (row_outcome, torch.int32, (N, D)),
+                               (traj, torch.int32, (N, A)), (trk, torch.int32, (N, D))))
     if workspace.dtype != torch.uint8 or workspace.device != dev:
         raise ValueError('{}: the workspace must be uint8 on {}'.format(what, dev))
     return N, D, A, _host_table(what, frame_tab, N, GPP_HOTA_TAB_COLS)
@@ -862,9 +769,7 @@ def hota_reduce(frame_hota, seq_tab, cells, vecs, workspace):
 
 
 def idf1_workspace_bytes(cells, vecs, max_frames, S):
-    n = c_size_t(0)
-    check(lib().gpp_idf1_workspace_bytes(int(cells), int(vecs), int(max_frames), int(S), ctypes.byref(n)), 'gpp_idf1_workspace_bytes')
-    return n.value
+    return _bytes('gpp_idf1_workspace_bytes', int(cells), int(vecs), int(max_frames), int(S))
 
 
 def idf1_workspace(cells, vecs, max_frames, S, device):
@@ -914,12 +819,9 @@ def label_prep(labels, label_counts, P, trig, det_types=0, own_box=True, detecti
     if labels.dim() != 3:
         raise ValueError('gpp_label_prep_f64: labels must be (B, A, {}), got {}'.format(GPP_KITTI_LABEL_COLS, tuple(labels.shape)))
     B, A = int(labels.shape[0]), int(labels.shape[1])
-    want = ((labels, torch.float64, (B, A, GPP_KITTI_LABEL_COLS)), (label_counts, torch.int32, (B,)), (P, torch.float64, (B, 3, 4)),
-            (trig, torch.float64, (B, A, 2)))
-    for t, dtype, shape in want:
-        if t.dtype != dtype or tuple(t.shape) != shape or t.device != labels.device:
-            raise ValueError('gpp_label_prep_f64: expected {} {} on {}, got {} {} on {}'.format(shape, dtype, labels.device, tuple(t.shape), t.dtype, t.device))
     dev = labels.device
+    _check_tensors('gpp_label_prep_f64', dev, ((labels, torch.float64, (B, A, GPP_KITTI_LABEL_COLS)), (label_counts, torch.int32, (B,)),
+                                               (P, torch.float64, (B, 3, 4)), (trig, torch.float64, (B, A, 2))))
     mod = torch.empty((B, A, GPP_LABEL_MOD_COLS), dtype=torch.float64, device=dev)
     det = None
     if detections:
@@ -953,16 +855,12 @@ def poll_costs(boxes, dims, orient, P_inv, planes, table, row_index=None, row_of
     if row_index is not None:
         O = int(row_index.numel())
         want.append((row_index, torch.int32, (O,)))
-    for t, dtype, shape in want:
-        if t.dtype != dtype or tuple(t.shape) != shape or t.device != boxes.device:
-            raise ValueError('gpp_poll_costs_u16: expected {} {} on {}, got {} {} on {}'.format(shape, dtype, boxes.device, tuple(t.shape), t.dtype, t.device))
+    _check_tensors('gpp_poll_costs_u16', boxes.device, want)
     rows, pitch = int(table.shape[0]), int(table.shape[1])
     if int(row_offset) < 0 or int(row_offset) + O > rows or pitch < M or pitch % 8:
         raise ValueError('gpp_poll_costs_u16: rows [{}, {}) of {} planes do not fit a table of {} rows, pitch {} (pitch >= M, a multiple of 8)'.format(
             int(row_offset), int(row_offset) + O, M, rows, pitch))
-    need = c_size_t(0)
-    check(lib().gpp_poll_costs_workspace_bytes(M, ctypes.byref(need)), 'gpp_poll_costs_workspace_bytes')
-    workspace = torch.empty((max(int(need.value), 16),), dtype=torch.uint8, device=boxes.device)
+    workspace = torch.empty((max(_bytes('gpp_poll_costs_workspace_bytes', M), 16),), dtype=torch.uint8, device=boxes.device)
     check(lib().gpp_poll_costs_u16(ptr(boxes), ptr(dims), ptr(orient), ptr(P_inv), ptr(planes), B, D, M, float(thr), ptr(row_index), O,
                                    ptr(table), pitch, int(row_offset), ptr(workspace), workspace.numel(), stream_ptr()), 'gpp_poll_costs_u16')
     return O
@@ -982,9 +880,7 @@ def plane_select(table, M, K):
     trace = torch.empty((K + 1,), dtype=torch.int64, device=dev)
     best = torch.empty((O,), dtype=torch.int16, device=dev)
     count = torch.empty((1,), dtype=torch.int32, device=dev)
-    need = c_size_t(0)
-    check(lib().gpp_plane_select_workspace_bytes(M, ctypes.byref(need)), 'gpp_plane_select_workspace_bytes')
-    workspace = torch.empty((int(need.value),), dtype=torch.uint8, device=dev)
+    workspace = torch.empty((_bytes('gpp_plane_select_workspace_bytes', M),), dtype=torch.uint8, device=dev)
     check(lib().gpp_plane_select(ptr(table), O, M, pitch, K, ptr(chosen), ptr(trace), ptr(best), ptr(count), ptr(workspace), workspace.numel(),
                                  stream_ptr()), 'gpp_plane_select')
     return chosen, trace, best, count
@@ -1006,16 +902,12 @@ def pose_costs(boxes, dims, orient, P_inv, want, planes, keys, errs, row_index=N
     if row_index is not None:
         O = int(row_index.numel())
         expect.append((row_index, torch.int32, (O,)))
-    for t, dtype, shape in expect:
-        if t.dtype != dtype or tuple(t.shape) != shape or t.device != boxes.device or not t.is_contiguous():
-            raise ValueError('gpp_pose_costs_u16: expected contiguous {} {} on {}, got {} {} on {}'.format(shape, dtype, boxes.device, tuple(t.shape), t.dtype, t.device))
+    _check_tensors('gpp_pose_costs_u16', boxes.device, expect, contiguous=True)
     rows, pitch = int(keys.shape[0]), int(keys.shape[1])
     if int(row_offset) < 0 or int(row_offset) + O > rows or pitch < M or pitch % 8:
         raise ValueError('gpp_pose_costs_u16: rows [{}, {}) of {} planes do not fit tables of {} rows, pitch {} (pitch >= M, a multiple of 8)'.format(
             int(row_offset), int(row_offset) + O, M, rows, pitch))
-    need = c_size_t(0)
-    check(lib().gpp_poll_costs_workspace_bytes(M, ctypes.byref(need)), 'gpp_poll_costs_workspace_bytes')
-    workspace = torch.empty((max(int(need.value), 16),), dtype=torch.uint8, device=boxes.device)
+    workspace = torch.empty((max(_bytes('gpp_poll_costs_workspace_bytes', M), 16),), dtype=torch.uint8, device=boxes.device)
     check(lib().gpp_pose_costs_u16(ptr(boxes), ptr(dims), ptr(orient), ptr(P_inv), ptr(want), ptr(planes), B, D, M, float(thr), ptr(row_index), O,
                                    ptr(keys), ptr(errs), pitch, int(row_offset), ptr(workspace), workspace.numel(), stream_ptr()), 'gpp_pose_costs_u16')
     return O
@@ -1026,10 +918,10 @@ def plane_select_polled(keys, errs, M, K):
     the planes, K picks -> (chosen (K,) int32, trace (K + 1,) int64, best (O,), cur (O,) int16 holding uint16 values, count (1,) int32) on
     the device; no synchronisation """
     import torch
-    if keys.dim() != 2 or keys.dtype != torch.int16 or errs.dtype != torch.int16 or tuple(errs.shape) != tuple(keys.shape) or \
-            errs.device != keys.device or not keys.is_contiguous() or not errs.is_contiguous():
-        raise ValueError('gpp_plane_select_polled: keys and errs must be contiguous (O, pitch) int16 of one shape on one device, got {} {} and {} {}'.format(
-            tuple(keys.shape), keys.dtype, tuple(errs.shape), errs.dtype))
+    if keys.dim() != 2:
+        raise ValueError('gpp_plane_select_polled: keys and errs must be (O, pitch), got {} and {}'.format(tuple(keys.shape), tuple(errs.shape)))
+    _check_tensors('gpp_plane_select_polled', keys.device, ((keys, torch.int16, tuple(keys.shape)), (errs, torch.int16, tuple(keys.shape))),
+                   contiguous=True)
     O, pitch, M, K = int(keys.shape[0]), int(keys.shape[1]), int(M), int(K)
     if O < 1 or M < 1 or pitch < M or pitch % 8 or K < 1 or K > M:
         raise ValueError('gpp_plane_select_polled: O = {}, M = {}, pitch = {}, K = {}: needs O >= 1, 1 <= K <= M <= pitch, pitch a multiple of 8'.format(O, M, pitch, K))
@@ -1039,18 +931,10 @@ def plane_select_polled(keys, errs, M, K):
     best = torch.empty((O,), dtype=torch.int16, device=dev)
     cur = torch.empty((O,), dtype=torch.int16, device=dev)
     count = torch.empty((1,), dtype=torch.int32, device=dev)
-    need = c_size_t(0)
-    check(lib().gpp_plane_select_polled_workspace_bytes(M, ctypes.byref(need)), 'gpp_plane_select_polled_workspace_bytes')
-    workspace = torch.empty((int(need.value),), dtype=torch.uint8, device=dev)
+    workspace = torch.empty((_bytes('gpp_plane_select_polled_workspace_bytes', M),), dtype=torch.uint8, device=dev)
     check(lib().gpp_plane_select_polled(ptr(keys), ptr(errs), O, M, pitch, K, ptr(chosen), ptr(trace), ptr(best), ptr(cur), ptr(count), ptr(workspace),
                                         workspace.numel(), stream_ptr()), 'gpp_plane_select_polled')
     return chosen, trace, best, cur, count
-
-
-def _road_check(what, want, dev):
-    for t, dtype, shape in want:
-        if t.dtype != dtype or tuple(t.shape) != shape or t.device != dev:
-            raise ValueError('{}: expected {} {} on {}, got {} {} on {}'.format(what, shape, dtype, dev, tuple(t.shape), t.dtype, t.device))
 
 
 def road_points(points, offsets, T, max_points, region_q):
@@ -1061,7 +945,7 @@ def road_points(points, offsets, T, max_points, region_q):
     if points.dim() != 2 or offsets.dim() != 1 or offsets.numel() < 1:
         raise ValueError('gpp_road_points_i32: points must be (total, 4) and offsets (F + 1,), got {} {}'.format(tuple(points.shape), tuple(offsets.shape)))
     total, F = int(points.shape[0]), int(offsets.numel()) - 1
-    _road_check('gpp_road_points_i32', ((points, torch.float32, (total, 4)), (offsets, torch.int32, (F + 1,)), (T, torch.float64, (F, 12))), points.device)
+    _check_tensors('gpp_road_points_i32', points.device, ((points, torch.float32, (total, 4)), (offsets, torch.int32, (F + 1,)), (T, torch.float64, (F, 12))))
     q = torch.zeros((total, 3), dtype=torch.int32, device=points.device)
     kept = torch.zeros((F,), dtype=torch.int32, device=points.device)
     xq, yq, zq = [int(v) for v in region_q]
@@ -1075,8 +959,8 @@ def road_score(q, offsets, kept, frame_id, seed, max_points, H, c2, hlo2, hhi2, 
     ids, on the device -> count (F, H) int32 on the device (-1 = an invalid hypothesis); no synchronisation """
     import torch
     total, F, H = int(q.shape[0]), int(kept.numel()), int(H)
-    _road_check('gpp_road_score', ((q, torch.int32, (total, 3)), (offsets, torch.int32, (F + 1,)), (kept, torch.int32, (F,)),
-                                   (frame_id, torch.int32, (F,))), q.device)
+    _check_tensors('gpp_road_score', q.device, ((q, torch.int32, (total, 3)), (offsets, torch.int32, (F + 1,)), (kept, torch.int32, (F,)),
+                                                (frame_id, torch.int32, (F,))))
     count = torch.empty((F, max(H, 0)), dtype=torch.int32, device=q.device)
     check(lib().gpp_road_score(ptr(q), ptr(offsets), ptr(kept), ptr(frame_id), int(seed) & 0xffffffff, F, total, int(max_points), H,
                                float(c2), float(hlo2), float(hhi2), float(tq2), ptr(count), stream_ptr()), 'gpp_road_score')
@@ -1100,8 +984,8 @@ def road_moments(q, offsets, kept, frame_id, seed, winner, max_points, H, tq2):
     winner's inliers, zero for a frame without a winner; no synchronisation """
     import torch
     total, F = int(q.shape[0]), int(kept.numel())
-    _road_check('gpp_road_moments', ((q, torch.int32, (total, 3)), (offsets, torch.int32, (F + 1,)), (kept, torch.int32, (F,)),
-                                     (frame_id, torch.int32, (F,)), (winner, torch.int32, (F,))), q.device)
+    _check_tensors('gpp_road_moments', q.device, ((q, torch.int32, (total, 3)), (offsets, torch.int32, (F + 1,)), (kept, torch.int32, (F,)),
+                                                  (frame_id, torch.int32, (F,)), (winner, torch.int32, (F,))))
     sums = torch.zeros((F, 10), dtype=torch.int64, device=q.device)
     check(lib().gpp_road_moments(ptr(q), ptr(offsets), ptr(kept), ptr(frame_id), int(seed) & 0xffffffff, ptr(winner), F, total, int(max_points),
                                  int(H), float(tq2), ptr(sums), stream_ptr()), 'gpp_road_moments')
@@ -1113,19 +997,15 @@ def road_peel(q, offsets, kept, frame_id, seed, winner, max_points, H, tq2):
     their order -> (q_out (total, 3) int32, a frame's survivors at the head of its own segment and zeros behind; kept_out (F,) int32) on
     the device, a frame without a winner: kept_out 0.  q is not changed.  No synchronisation """
     import torch
-    if not hasattr(lib(), 'gpp_road_peel_i32'):
-        raise GppError('gpp_road_peel_i32: this build of the library has no peel stage (several planes per frame)')
+    peel = _entry('gpp_road_peel_i32')
     total, F = int(q.shape[0]), int(kept.numel())
-    _road_check('gpp_road_peel_i32', ((q, torch.int32, (total, 3)), (offsets, torch.int32, (F + 1,)), (kept, torch.int32, (F,)),
-                                      (frame_id, torch.int32, (F,)), (winner, torch.int32, (F,))), q.device)
+    _check_tensors('gpp_road_peel_i32', q.device, ((q, torch.int32, (total, 3)), (offsets, torch.int32, (F + 1,)), (kept, torch.int32, (F,)),
+                                                   (frame_id, torch.int32, (F,)), (winner, torch.int32, (F,))))
     q_out = torch.zeros((total, 3), dtype=torch.int32, device=q.device)
     kept_out = torch.zeros((F,), dtype=torch.int32, device=q.device)
-    need = c_size_t(0)
-    check(lib().gpp_road_peel_workspace_bytes(F, int(max_points), ctypes.byref(need)), 'gpp_road_peel_workspace_bytes')
-    workspace = torch.empty((int(need.value),), dtype=torch.uint8, device=q.device)
-    check(lib().gpp_road_peel_i32(ptr(q), ptr(offsets), ptr(kept), ptr(frame_id), int(seed) & 0xffffffff, ptr(winner), F, total, int(max_points),
-                                  int(H), float(tq2), ptr(q_out), ptr(kept_out), ptr(workspace), workspace.numel(), stream_ptr()),
-          'gpp_road_peel_i32')
+    workspace = torch.empty((_bytes('gpp_road_peel_workspace_bytes', F, int(max_points)),), dtype=torch.uint8, device=q.device)
+    check(peel(ptr(q), ptr(offsets), ptr(kept), ptr(frame_id), int(seed) & 0xffffffff, ptr(winner), F, total, int(max_points), int(H), float(tq2),
+               ptr(q_out), ptr(kept_out), ptr(workspace), workspace.numel(), stream_ptr()), 'gpp_road_peel_i32')
     return q_out, kept_out
 
 
