@@ -30,39 +30,27 @@
 
 #include "gpp.h"
 #include "mot_assign.h"
+#include "pair_tables.h"
 
 namespace {
 
 using namespace gpp_mot;                                // kWave, rank_below, wave_sum, assign_rows
+using namespace gpp_pairs;                              // kScaleBits, kScale, kTabCols, kSeqTabCols, quantise and the host checks
 
 constexpr int kMax = GPP_KITTI_MAX_DETECTIONS;          // rows and labels per frame
-constexpr int kScaleBits = GPP_MOT_SCALE_BITS;
-constexpr int kScale = 1 << kScaleBits;
 constexpr int kLevels = GPP_HOTA_LEVELS;                // the thresholds j / 20, j = 1 .. 19
 constexpr int kHist = GPP_HOTA_HIST;                    // counters per cell: index jm, 0 unused
 constexpr int kFrameCols = GPP_HOTA_FRAME_COLS;
 constexpr int kSeqCols = GPP_HOTA_SEQ_COLS;
-constexpr int kTabCols = GPP_HOTA_TAB_COLS;
-constexpr int kSeqTabCols = GPP_HOTA_SEQ_TAB_COLS;
 constexpr int kPotThreads = 256;
 constexpr int kRedThreads = 256;
 constexpr int kTables = 3 * kMax;                       // int32 words the outcome phase needs of the dead matrix
-constexpr long long kMaxCells = 1ll << 31;
 
 static_assert(kMax == GPP_KITTI_MAX_LABELS && kMax == 2 * kWave, "two columns and two rows per lane");
 static_assert(kPotThreads == 2 * kMax, "one thread per label and one per row");
 static_assert(kHist == kLevels + 1 && kHist % 4 == 0, "a cell's counters are five 16-byte words");
 static_assert(kFrameCols == 2 * kLevels + 2, "TP and SQ per threshold, G' and T'");
 static_assert(3 * kMax * kMax + 4 * kMax * 4 <= 65536, "pass 1 stays inside 64 KiB of LDS");
-
-// the similarity: floor(min(o 2^20, 2^20)), 0 for NaN and o <= 0 (section 4.29's k without the admissibility test)
-__device__ __forceinline__ int quantise(double o)
-{
-    if (!(o > 0.0)) return 0;
-    double x = o * (double)kScale;
-    x = x > (double)kScale ? (double)kScale : x;
-    return (int)floor(x);
-}
 
 __device__ __forceinline__ bool bit_of(unsigned long long lo, unsigned long long hi, int i)
 {
@@ -337,73 +325,35 @@ Layout layout_of(long long cells, long long vecs)
     l.hist = (size_t)cells * 12;                         // (a multiple of 16 iff cells is a multiple of 4: rounded below)
     l.hist = (l.hist + 15) / 16 * 16;
     l.cnt = l.hist + (size_t)cells * kHist * 4;
-    l.tab = (l.cnt + (size_t)vecs * 4 + 15) / 16 * 16;
+    l.tab = tab_offset(l.cnt, vecs);
     return l;
-}
-
-bool sizes_bad(long long cells, long long vecs) { return cells < 0 || vecs < 0; }
-bool sizes_unsupported(long long cells, long long vecs) { return cells >= kMaxCells || vecs >= kMaxCells; }
-
-// a table line: cell_base, n_gt, n_trk, vec_base -- monotone bases, the cells and the counters inside the tables
-bool line_ok(const int32_t* line, const int32_t* before, long long cells, long long vecs)
-{
-    const long long cell_base = line[0], n_gt = line[1], n_trk = line[2], vec_base = line[3];
-    if (cell_base < 0 || n_gt < 0 || n_trk < 0 || vec_base < 0) return false;
-    if (before && (cell_base < before[0] || vec_base < before[3])) return false;
-    return cell_base + n_gt * n_trk <= cells && vec_base + n_gt + n_trk <= vecs;
-}
-
-// what gpp_hota_potential and gpp_hota_match check alike; GPP_OK with *launch == false: nothing to do
-int check_frames(const double* overlaps, const int32_t* label_outcome, const int32_t* row_outcome, const int32_t* traj, const int32_t* trk,
-                 int N, int D, int A, int metric, const int32_t* frame_tab, long long cells, long long vecs, void* workspace,
-                 size_t workspace_bytes, bool* launch)
-{
-    *launch = false;
-    if (N < 0 || D < 0 || A < 0 || sizes_bad(cells, vecs) || metric < 0 || metric > 2) return GPP_ERR_BAD_ARG;
-    if (D > kMax || A > kMax || sizes_unsupported(cells, vecs)) return GPP_ERR_UNSUPPORTED;
-    if (N == 0) return GPP_OK;
-    if (!frame_tab || !workspace) return GPP_ERR_BAD_ARG;
-    if (A > 0 && (!label_outcome || !traj)) return GPP_ERR_BAD_ARG;
-    if (D > 0 && (!row_outcome || !trk)) return GPP_ERR_BAD_ARG;
-    if (D > 0 && A > 0 && !overlaps) return GPP_ERR_BAD_ARG;
-    for (int f = 0; f < N; ++f)
-        if (!line_ok(frame_tab + (size_t)f * kTabCols, f ? frame_tab + (size_t)(f - 1) * kTabCols : nullptr, cells, vecs)) return GPP_ERR_BAD_ARG;
-    if ((uintptr_t)workspace & 15u) return GPP_ERR_ALIGN;
-    if (workspace_bytes < layout_of(cells, vecs).tab + (size_t)N * kTabCols * sizeof(int32_t)) return GPP_ERR_WORKSPACE;
-    *launch = true;
-    return GPP_OK;
 }
 
 }  // namespace
 
 extern "C" int gpp_hota_workspace_bytes(long long cells, long long vecs, int max_frames, int S, size_t* bytes)
 {
-    if (sizes_bad(cells, vecs) || max_frames < 0 || S < 0 || !bytes) return GPP_ERR_BAD_ARG;
-    if (sizes_unsupported(cells, vecs)) return GPP_ERR_UNSUPPORTED;
-    const size_t frames = (size_t)max_frames * kTabCols, seqs = (size_t)S * kSeqTabCols;
-    *bytes = (layout_of(cells, vecs).tab + (frames > seqs ? frames : seqs) * sizeof(int32_t) + 255) / 256 * 256;
-    return GPP_OK;
+    return workspace_size(cells, vecs, max_frames, S, layout_of(cells, vecs).tab, bytes);
 }
 
 extern "C" int gpp_hota_potential(const double* overlaps, const int32_t* label_outcome, const int32_t* row_outcome, const int32_t* traj,
                                   const int32_t* trk, int N, int D, int A, int metric, const int32_t* frame_tab, long long cells,
                                   long long vecs, void* workspace, size_t workspace_bytes, void* stream)
 {
+    const Layout l = layout_of(cells, vecs);
     bool launch;
-    const int rc = check_frames(overlaps, label_outcome, row_outcome, traj, trk, N, D, A, metric, frame_tab, cells, vecs, workspace,
+    const int rc = check_frames(overlaps, label_outcome, row_outcome, traj, trk, N, D, A, metric, frame_tab, cells, vecs, l.tab, workspace,
                                 workspace_bytes, &launch);
     if (rc != GPP_OK || !launch) return rc;
-    const Layout l = layout_of(cells, vecs);
     unsigned char* w = (unsigned char*)workspace;
     hipStream_t q = (hipStream_t)stream;
-    hipError_t e = hipMemcpyAsync(w + l.tab, frame_tab, (size_t)N * kTabCols * sizeof(int32_t), hipMemcpyHostToDevice, q);
+    hipError_t e = upload_lines(w, l.tab, frame_tab, N, kTabCols, q);
     if (e != hipSuccess) return (int)e;
     const size_t lds = (size_t)4 * kMax * sizeof(int32_t) + (size_t)3 * D * A;
     potential_kernel<<<dim3((unsigned)N), dim3(kPotThreads), lds, q>>>(overlaps, label_outcome, row_outcome, traj, trk, D, A, metric,
                                                                       (const int32_t*)(w + l.tab), (unsigned long long*)w,
                                                                       (int32_t*)(w + l.cnt));
-    e = hipGetLastError();
-    return e == hipSuccess ? GPP_OK : (int)e;
+    return launched();
 }
 
 extern "C" int gpp_hota_match(const double* overlaps, const int32_t* label_outcome, const int32_t* row_outcome, const int32_t* traj,
@@ -411,23 +361,22 @@ extern "C" int gpp_hota_match(const double* overlaps, const int32_t* label_outco
                               long long vecs, int32_t* hota_match, int64_t* frame_hota, void* workspace, size_t workspace_bytes,
                               void* stream)
 {
+    const Layout l = layout_of(cells, vecs);
     bool launch;
-    const int rc = check_frames(overlaps, label_outcome, row_outcome, traj, trk, N, D, A, metric, frame_tab, cells, vecs, workspace,
+    const int rc = check_frames(overlaps, label_outcome, row_outcome, traj, trk, N, D, A, metric, frame_tab, cells, vecs, l.tab, workspace,
                                 workspace_bytes, &launch);
     if (rc != GPP_OK || !launch) return rc;
     if (!frame_hota || (A > 0 && !hota_match)) return GPP_ERR_BAD_ARG;
-    const Layout l = layout_of(cells, vecs);
     unsigned char* w = (unsigned char*)workspace;
     hipStream_t q = (hipStream_t)stream;
-    hipError_t e = hipMemcpyAsync(w + l.tab, frame_tab, (size_t)N * kTabCols * sizeof(int32_t), hipMemcpyHostToDevice, q);
+    hipError_t e = upload_lines(w, l.tab, frame_tab, N, kTabCols, q);
     if (e != hipSuccess) return (int)e;
     const int side = D > A ? D : A;
     const int words = side * side > kTables ? side * side : kTables;
     match_kernel<<<dim3((unsigned)N), dim3(kWave), (size_t)words * sizeof(int32_t), q>>>(
         overlaps, label_outcome, row_outcome, traj, trk, D, A, metric, (const int32_t*)(w + l.tab), (const unsigned long long*)w,
         (const int32_t*)(w + l.cnt), (int32_t*)(w + l.align), (int32_t*)(w + l.hist), hota_match, frame_hota);
-    e = hipGetLastError();
-    return e == hipSuccess ? GPP_OK : (int)e;
+    return launched();
 }
 
 extern "C" int gpp_hota_reduce(const int64_t* frame_hota, int N, const int32_t* seq_tab, int S, long long cells, long long vecs,
@@ -450,13 +399,12 @@ extern "C" int gpp_hota_reduce(const int64_t* frame_hota, int N, const int32_t* 
     if (workspace_bytes < l.tab + (size_t)S * kSeqTabCols * sizeof(int32_t)) return GPP_ERR_WORKSPACE;
     unsigned char* w = (unsigned char*)workspace;
     hipStream_t q = (hipStream_t)stream;
-    hipError_t e = hipMemcpyAsync(w + l.tab, seq_tab, (size_t)S * kSeqTabCols * sizeof(int32_t), hipMemcpyHostToDevice, q);
+    hipError_t e = upload_lines(w, l.tab, seq_tab, S, kSeqTabCols, q);
     if (e != hipSuccess) return (int)e;
     long long blocks = (most + kRedThreads - 1) / kRedThreads;
     blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
     reduce_kernel<<<dim3((unsigned)blocks, (unsigned)S), dim3(kRedThreads), 0, q>>>(frame_hota, N, (const int32_t*)(w + l.tab),
                                                                                    (const int32_t*)(w + l.hist), (const int32_t*)(w + l.cnt),
                                                                                    (unsigned long long*)seq_hota);
-    e = hipGetLastError();
-    return e == hipSuccess ? GPP_OK : (int)e;
+    return launched();
 }

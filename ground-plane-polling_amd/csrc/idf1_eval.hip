@@ -35,40 +35,28 @@
 
 #include "gpp.h"
 #include "mot_assign.h"
+#include "pair_tables.h"
 
 namespace {
 
 using namespace gpp_mot;                                // kWave, read_lane, wave_min, wave_sum
+using namespace gpp_pairs;                              // kScale, kTabCols, kSeqTabCols, quantise and the host checks
 
 constexpr int kMax = GPP_KITTI_MAX_DETECTIONS;          // rows and labels per frame
-constexpr int kScaleBits = GPP_MOT_SCALE_BITS;
-constexpr int kScale = 1 << kScaleBits;
 constexpr int kHalf = kScale >> 1;
 constexpr int kMaxRows = GPP_MOT_MAX_TRAJECTORIES;
 constexpr int kMaxIds = GPP_IDF1_MAX_IDS;
 constexpr int kSeqCols = GPP_IDF1_SEQ_COLS;
-constexpr int kTabCols = GPP_HOTA_TAB_COLS;
-constexpr int kSeqTabCols = GPP_HOTA_SEQ_TAB_COLS;
 constexpr int kCountThreads = 256;
 constexpr int kKeyBits = 13;                            // the column's bits of the packed key
 constexpr int kBatch = 8;                              // columns of a lane whose reads are in flight together
 constexpr int kColumnBytes = 24;                        // v, minv, way, the row it holds
-constexpr long long kMaxCells = 1ll << 31;
 constexpr size_t kLdsCap = (size_t)kMaxIds * kColumnBytes + (size_t)kMaxRows * 8;
 
 static_assert(kMax == GPP_KITTI_MAX_LABELS && kCountThreads == 2 * kMax, "one thread per label and one per row");
 static_assert(kMaxIds < (1 << kKeyBits) && kMaxIds % (kWave * kBatch) == 0 && kMaxIds / kWave <= 64, "a lane's columns fit a 64-bit mask, in whole batches");
 static_assert(kMaxRows <= kMaxIds && kMaxRows % kWave == 0 && kMaxRows / kWave <= 32, "a lane's rows fit a 32-bit mask");
 static_assert(kLdsCap <= 160 * 1024, "a gfx950 workgroup takes up to 160 KiB of LDS");
-
-// the similarity: floor(min(o 2^20, 2^20)), 0 for NaN and o <= 0 (section 4.30's q)
-__device__ __forceinline__ int quantise(double o)
-{
-    if (!(o > 0.0)) return 0;
-    double x = o * (double)kScale;
-    x = x > (double)kScale ? (double)kScale : x;
-    return (int)floor(x);
-}
 
 __global__ __launch_bounds__(kCountThreads) void count_kernel(const double* __restrict__ overlaps, const int32_t* __restrict__ label_outcome,
                                                               const int32_t* __restrict__ row_outcome, const int32_t* __restrict__ traj,
@@ -254,57 +242,33 @@ Layout layout_of(long long cells, long long vecs)
 {
     Layout l;
     l.cnt = ((size_t)cells * 4 + 15) / 16 * 16;
-    l.tab = (l.cnt + (size_t)vecs * 4 + 15) / 16 * 16;
+    l.tab = tab_offset(l.cnt, vecs);
     return l;
-}
-
-bool sizes_bad(long long cells, long long vecs) { return cells < 0 || vecs < 0; }
-bool sizes_unsupported(long long cells, long long vecs) { return cells >= kMaxCells || vecs >= kMaxCells; }
-
-// a table line: cell_base, n_gt, n_trk, vec_base -- monotone bases, the cells and the counters inside the tables
-bool line_ok(const int32_t* line, const int32_t* before, long long cells, long long vecs)
-{
-    const long long cell_base = line[0], n_gt = line[1], n_trk = line[2], vec_base = line[3];
-    if (cell_base < 0 || n_gt < 0 || n_trk < 0 || vec_base < 0) return false;
-    if (before && (cell_base < before[0] || vec_base < before[3])) return false;
-    return cell_base + n_gt * n_trk <= cells && vec_base + n_gt + n_trk <= vecs;
 }
 
 }  // namespace
 
 extern "C" int gpp_idf1_workspace_bytes(long long cells, long long vecs, int max_frames, int S, size_t* bytes)
 {
-    if (sizes_bad(cells, vecs) || max_frames < 0 || S < 0 || !bytes) return GPP_ERR_BAD_ARG;
-    if (sizes_unsupported(cells, vecs)) return GPP_ERR_UNSUPPORTED;
-    const size_t frames = (size_t)max_frames * kTabCols, seqs = (size_t)S * kSeqTabCols;
-    *bytes = (layout_of(cells, vecs).tab + (frames > seqs ? frames : seqs) * sizeof(int32_t) + 255) / 256 * 256;
-    return GPP_OK;
+    return workspace_size(cells, vecs, max_frames, S, layout_of(cells, vecs).tab, bytes);
 }
 
 extern "C" int gpp_idf1_count(const double* overlaps, const int32_t* label_outcome, const int32_t* row_outcome, const int32_t* traj,
                               const int32_t* trk, int N, int D, int A, int metric, const int32_t* frame_tab, long long cells,
                               long long vecs, void* workspace, size_t workspace_bytes, void* stream)
 {
-    if (N < 0 || D < 0 || A < 0 || sizes_bad(cells, vecs) || metric < 0 || metric > 2) return GPP_ERR_BAD_ARG;
-    if (D > kMax || A > kMax || sizes_unsupported(cells, vecs)) return GPP_ERR_UNSUPPORTED;
-    if (N == 0) return GPP_OK;
-    if (!frame_tab || !workspace) return GPP_ERR_BAD_ARG;
-    if (A > 0 && (!label_outcome || !traj)) return GPP_ERR_BAD_ARG;
-    if (D > 0 && (!row_outcome || !trk)) return GPP_ERR_BAD_ARG;
-    if (D > 0 && A > 0 && !overlaps) return GPP_ERR_BAD_ARG;
-    for (int f = 0; f < N; ++f)
-        if (!line_ok(frame_tab + (size_t)f * kTabCols, f ? frame_tab + (size_t)(f - 1) * kTabCols : nullptr, cells, vecs)) return GPP_ERR_BAD_ARG;
-    if ((uintptr_t)workspace & 15u) return GPP_ERR_ALIGN;
     const Layout l = layout_of(cells, vecs);
-    if (workspace_bytes < l.tab + (size_t)N * kTabCols * sizeof(int32_t)) return GPP_ERR_WORKSPACE;
+    bool launch;
+    const int rc = check_frames(overlaps, label_outcome, row_outcome, traj, trk, N, D, A, metric, frame_tab, cells, vecs, l.tab, workspace,
+                                workspace_bytes, &launch);
+    if (rc != GPP_OK || !launch) return rc;
     unsigned char* w = (unsigned char*)workspace;
     hipStream_t q = (hipStream_t)stream;
-    hipError_t e = hipMemcpyAsync(w + l.tab, frame_tab, (size_t)N * kTabCols * sizeof(int32_t), hipMemcpyHostToDevice, q);
+    hipError_t e = upload_lines(w, l.tab, frame_tab, N, kTabCols, q);
     if (e != hipSuccess) return (int)e;
     count_kernel<<<dim3((unsigned)N), dim3(kCountThreads), 0, q>>>(overlaps, label_outcome, row_outcome, traj, trk, D, A, metric,
                                                                    (const int32_t*)(w + l.tab), (int32_t*)w, (int32_t*)(w + l.cnt));
-    e = hipGetLastError();
-    return e == hipSuccess ? GPP_OK : (int)e;
+    return launched();
 }
 
 extern "C" int gpp_idf1_assign(const int32_t* seq_tab, int S, long long cells, long long vecs, int32_t* id_match, int64_t* seq_idf1,
@@ -346,10 +310,9 @@ extern "C" int gpp_idf1_assign(const int32_t* seq_tab, int S, long long cells, l
     }
     unsigned char* w = (unsigned char*)workspace;
     hipStream_t q = (hipStream_t)stream;
-    e = hipMemcpyAsync(w + l.tab, seq_tab, (size_t)S * kSeqTabCols * sizeof(int32_t), hipMemcpyHostToDevice, q);
+    e = upload_lines(w, l.tab, seq_tab, S, kSeqTabCols, q);
     if (e != hipSuccess) return (int)e;
     assign_kernel<<<dim3((unsigned)S), dim3(kWave), lds, q>>>((const int32_t*)(w + l.tab), (const int32_t*)w, (const int32_t*)(w + l.cnt),
                                                              n_cap, id_match, seq_idf1);
-    e = hipGetLastError();
-    return e == hipSuccess ? GPP_OK : (int)e;
+    return launched();
 }

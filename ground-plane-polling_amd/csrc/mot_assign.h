@@ -1,11 +1,12 @@
 // The assignment routine of DESIGN.md section 4.29 as a __device__ function: the Hungarian method in its shortest-augmenting-path form on a
 // square int32 matrix in LDS, run by ONE wavefront, with the wavefront primitives it needs.  include/gpp.h (gpp_mot_assign, "assignment")
 // states the rule operation for operation; utils/mot_eval.assign_np is its host form.
-// csrc/hota_eval.hip (HOTA, section 4.30) instantiates it.  csrc/mot_eval.hip's assign_kernel still carries the same statements in its own
-// body: built on this header its listing differs from the parent's in several hundred lines (another register allocation and schedule),
-// and alternating with the parent in one session gpp_mot_assign's median on 7 991 KITTI-sized frames was 119.7 - 120.3 us against
-// 115.7 - 118.5 us in each of four repeats (profiles/hota/ab_mot_assign.jsonl) -- beyond the parent's own spread, so that file was left
-// as it is.  The statements below are that body's, unchanged.
+// csrc/hota_eval.hip (HOTA, section 4.30) instantiates it.  The primitives (rank_below .. wave_sum) have this one copy: csrc/mot_eval.hip
+// takes them from here too, with the same device listing.  Only assign_kernel's BODY there still carries assign_rows' statements: built
+// on assign_rows its listing differs from the parent's in several hundred lines (another register allocation and schedule), and
+// alternating with the parent in one session gpp_mot_assign's median on 7 991 KITTI-sized frames was 119.7 - 120.3 us against
+// 115.7 - 118.5 us in each of four repeats (profiles/hota/ab_mot_assign.jsonl) -- beyond the parent's own spread, so that body was left
+// as it is.  The statements of assign_rows below are that body's, unchanged.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -30,13 +30,15 @@
 #include <math.h>
 
 #include "gpp.h"
+#include "mot_assign.h"
 
 namespace {
+
+using namespace gpp_mot;                                // kWave, rank_below, read_lane, read_lane64, wave_min, wave_sum
 
 constexpr int kMax = GPP_KITTI_MAX_DETECTIONS;          // rows and labels per frame
 constexpr int kRow = GPP_POSE_COLS;
 constexpr int kLabel = GPP_KITTI_LABEL_COLS;
-constexpr int kWave = 64;
 constexpr int kScale = 1 << GPP_MOT_SCALE_BITS;
 constexpr int kBig = GPP_MOT_BIG;
 constexpr int kTraj = GPP_MOT_MAX_TRAJECTORIES;
@@ -51,50 +53,6 @@ static_assert(kClearThreads == kMax, "one thread per label slot");
 enum { L_NONE = 0, L_TP, L_FN, L_IGNORED_MATCHED, L_IGNORED_UNMATCHED };
 enum { R_NONE = 0, R_TP, R_IGNORED, R_FP, R_LOW, R_DONTCARE };
 enum { S_COUNTING = 0, S_IGNORED, S_DONTCARE, S_OUT };
-
-__device__ __forceinline__ int rank_below(unsigned long long lo, unsigned long long hi, int i)
-{
-    return i < 64 ? __popcll(lo & ((1ull << i) - 1ull)) : __popcll(lo) + __popcll(hi & ((1ull << (i - 64)) - 1ull));
-}
-
-// the value lane `lane` holds; `lane` is the same in every lane (a scalar read, no trip through the LDS crossbar)
-__device__ __forceinline__ int read_lane(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
-
-__device__ __forceinline__ long long read_lane64(long long v, int lane)
-{
-    const unsigned lo = (unsigned)read_lane((int)(unsigned)v, lane), hi = (unsigned)read_lane((int)(unsigned)((unsigned long long)v >> 32), lane);
-    return (long long)(((unsigned long long)hi << 32) | lo);
-}
-
-// the key of the lane a DPP control names, all ones where the control names none (rows outside kRowMask, lanes shifted in from outside a row)
-template <int kCtrl, int kRowMask>
-__device__ __forceinline__ unsigned long long dpp_key(unsigned long long key)
-{
-    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)(unsigned)key, kCtrl, kRowMask, 0xf, false);
-    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)(unsigned)(key >> 32), kCtrl, kRowMask, 0xf, false);
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-// the smallest key of the wavefront, in every lane: a prefix minimum inside each row of 16 lanes (row_shr 1, 2, 4, 8), then lane 15 of a row
-// into the next row (row_bcast:15, rows 1 and 3) and lane 31 into the upper half (row_bcast:31, rows 2 and 3): lane 63 holds the minimum
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long key)
-{
-    unsigned long long other;
-    other = dpp_key<0x111, 0xf>(key); key = other < key ? other : key;
-    other = dpp_key<0x112, 0xf>(key); key = other < key ? other : key;
-    other = dpp_key<0x114, 0xf>(key); key = other < key ? other : key;
-    other = dpp_key<0x118, 0xf>(key); key = other < key ? other : key;
-    other = dpp_key<0x142, 0xa>(key); key = other < key ? other : key;
-    other = dpp_key<0x143, 0xc>(key); key = other < key ? other : key;
-    return (unsigned long long)read_lane64((long long)key, 63);
-}
-
-__device__ __forceinline__ long long wave_sum(long long v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, kWave);
-    return v;
-}
 
 __global__ __launch_bounds__(kWave) void assign_kernel(const double* __restrict__ overlaps, const double* __restrict__ labels,
                                                        const int32_t* __restrict__ label_counts, const float* __restrict__ rows,

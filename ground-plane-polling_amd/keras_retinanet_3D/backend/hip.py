@@ -686,14 +686,22 @@ def mot_clear(match, label_outcome, traj, ids, frame_counts, seq_start, max_traj
     return seq_counts, traj_table
 
 
-def hota_workspace_bytes(cells, vecs, max_frames, S):
-    return _bytes('gpp_hota_workspace_bytes', int(cells), int(vecs), int(max_frames), int(S))
+def _pair_workspace(score):
+    """ (SCORE_workspace_bytes, SCORE_workspace) of a score that keeps pair tables (csrc/pair_tables.h), 'hota' or 'idf1' """
+    def workspace_bytes(cells, vecs, max_frames, S):
+        return _bytes('gpp_{}_workspace_bytes'.format(score), int(cells), int(vecs), int(max_frames), int(S))
+
+    def workspace(cells, vecs, max_frames, S, device):
+        """ the zeroed workspace of the score's calls for pair tables of `cells` cells and `vecs` counters in all, up to `max_frames`
+        frames a call and S sequences """
+        import torch
+        return torch.zeros((workspace_bytes(cells, vecs, max_frames, S),), dtype=torch.uint8, device=device)
+
+    return workspace_bytes, workspace
 
 
-def hota_workspace(cells, vecs, max_frames, S, device):
-    """ the zeroed workspace of gpp_hota_* for pair tables of `cells` cells and `vecs` counters in all """
-    import torch
-    return torch.zeros((hota_workspace_bytes(cells, vecs, max_frames, S),), dtype=torch.uint8, device=device)
+hota_workspace_bytes, hota_workspace = _pair_workspace('hota')
+idf1_workspace_bytes, idf1_workspace = _pair_workspace('idf1')
 
 
 def hota_tables(workspace, cells, vecs):
@@ -719,7 +727,8 @@ def _table_ptr(table):
     return table.ctypes.data_as(_HOST_I32)
 
 
-def _hota_frames(what, overlaps, label_outcome, row_outcome, traj, trk, frame_tab, workspace):
+def _pair_frames(what, overlaps, label_outcome, row_outcome, traj, trk, frame_tab, workspace):
+    """ what the frame calls on pair tables (gpp_hota_potential, gpp_hota_match, gpp_idf1_count) take alike -> (N, D, A, the host table) """
     import torch
     if overlaps.dim() != 4:
         raise ValueError('{}: overlaps must be (N, 4, D, A), got {}'.format(what, tuple(overlaps.shape)))
@@ -736,7 +745,7 @@ def hota_potential(overlaps, label_outcome, row_outcome, traj, trk, metric, fram
     """ gpp_hota_potential on the current stream (pass 1): overlaps (N, 4, D, A) float64, label_outcome and traj (N, A) int32, row_outcome
     and trk (N, D) int32 on the device, frame_tab N * 4 host integers (cell_base, n_gt, n_trk, vec_base per frame), the workspace of
     hota_workspace -- adds the frames to the pair tables in the workspace; no synchronisation """
-    N, D, A, tab = _hota_frames('gpp_hota_potential', overlaps, label_outcome, row_outcome, traj, trk, frame_tab, workspace)
+    N, D, A, tab = _pair_frames('gpp_hota_potential', overlaps, label_outcome, row_outcome, traj, trk, frame_tab, workspace)
     check(lib().gpp_hota_potential(ptr(overlaps), ptr(label_outcome), ptr(row_outcome), ptr(traj), ptr(trk), N, D, A, int(metric), _table_ptr(tab),
                                    int(cells), int(vecs), ptr(workspace), int(workspace.numel()), stream_ptr()), 'gpp_hota_potential')
 
@@ -745,7 +754,7 @@ def hota_match(overlaps, label_outcome, row_outcome, traj, trk, metric, frame_ta
     """ gpp_hota_match on the current stream (pass 2, after pass 1 has seen every frame of the sequences): the arguments of hota_potential
     -> (hota_match (N, A) int32, frame_hota (N, 40) int64) on the device; no synchronisation """
     import torch
-    N, D, A, tab = _hota_frames('gpp_hota_match', overlaps, label_outcome, row_outcome, traj, trk, frame_tab, workspace)
+    N, D, A, tab = _pair_frames('gpp_hota_match', overlaps, label_outcome, row_outcome, traj, trk, frame_tab, workspace)
     match = torch.full((N, A), -1, dtype=torch.int32, device=overlaps.device)
     frame_hota = torch.zeros((N, GPP_HOTA_FRAME_COLS), dtype=torch.int64, device=overlaps.device)
     check(lib().gpp_hota_match(ptr(overlaps), ptr(label_outcome), ptr(row_outcome), ptr(traj), ptr(trk), N, D, A, int(metric), _table_ptr(tab),
@@ -768,16 +777,6 @@ def hota_reduce(frame_hota, seq_tab, cells, vecs, workspace):
     return seq_hota
 
 
-def idf1_workspace_bytes(cells, vecs, max_frames, S):
-    return _bytes('gpp_idf1_workspace_bytes', int(cells), int(vecs), int(max_frames), int(S))
-
-
-def idf1_workspace(cells, vecs, max_frames, S, device):
-    """ the zeroed workspace of gpp_idf1_* for tables of `cells` cells and `vecs` counters in all """
-    import torch
-    return torch.zeros((idf1_workspace_bytes(cells, vecs, max_frames, S),), dtype=torch.uint8, device=device)
-
-
 def idf1_tables(workspace, cells, vecs):
     """ the views include/gpp.h documents, to read and to write: (C int32 (cells,), counters int32 (vecs,)) """
     import torch
@@ -789,7 +788,7 @@ def idf1_tables(workspace, cells, vecs):
 def idf1_count(overlaps, label_outcome, row_outcome, traj, trk, metric, frame_tab, cells, vecs, workspace):
     """ gpp_idf1_count on the current stream (pass 1): the arguments of hota_potential, the workspace of idf1_workspace -- adds the frames
     to the table C and to the counters in the workspace; no synchronisation """
-    N, D, A, tab = _hota_frames('gpp_idf1_count', overlaps, label_outcome, row_outcome, traj, trk, frame_tab, workspace)
+    N, D, A, tab = _pair_frames('gpp_idf1_count', overlaps, label_outcome, row_outcome, traj, trk, frame_tab, workspace)
     check(lib().gpp_idf1_count(ptr(overlaps), ptr(label_outcome), ptr(row_outcome), ptr(traj), ptr(trk), N, D, A, int(metric), _table_ptr(tab),
                                int(cells), int(vecs), ptr(workspace), int(workspace.numel()), stream_ptr()), 'gpp_idf1_count')
 

@@ -6,8 +6,9 @@ is UNPINNED (TrackEval is not part of this repository).  include/gpp.h (gpp_hota
 form's contract.
 
 HOTA starts where utils/mot_eval.py's assignment ends: that assignment, with the call's metric and limits, is the preprocessing.  A label
-COUNTS iff its label_outcome is 1 or 2, a row is KEPT iff its row_outcome is 1 or 3.  Everything after the similarity
-q = floor(min(overlap * 2^20, 2^20)) is exact integers, so the two forms and the loop-written oracle of the tests are equal with ==:
+COUNTS iff its label_outcome is 1 or 2, a row is KEPT iff its row_outcome is 1 or 3; the tables' geometry and the similarity are
+utils/pair_tables.py's, shared with utils/idf1_eval.py.  Everything after the similarity q = floor(min(overlap * 2^20, 2^20)) is exact
+integers, so the two forms and the loop-written oracle of the tests are equal with ==:
 
     device=False    NumPy: potential_np (pass 1), align_np, match_np (pass 2, on utils/mot_eval.assign_np), reduce_np.
     device=True     csrc/hota_eval.hip: per chunk of frames gpp_hota_potential in a first sweep, gpp_hota_match in a second one -- pass 1
@@ -18,8 +19,8 @@ import math
 
 import numpy as np
 
-from . import kitti_eval
 from . import mot_eval
+from . import pair_tables
 
 SCALE_BITS, SCALE = mot_eval.SCALE_BITS, mot_eval.SCALE
 LEVELS = 19                                 # GPP_HOTA_LEVELS: the thresholds j / 20, j = 1 .. 19
@@ -28,75 +29,12 @@ FRAME_COLS = 40                             # GPP_HOTA_FRAME_COLS: TP_1..19, SQ_
 SEQ_COLS = 8                                # GPP_HOTA_SEQ_COLS
 SEQ_INTEGERS = ('tp', 'fn', 'fp', 'sq', 'ass', 'assre', 'asspr')
 RATIOS = ('hota', 'deta', 'assa', 'detre', 'detpr', 'assre', 'asspr', 'loca')
-MAX_FRAMES = 1 << 20                        # per sequence: keeps every integer below 2^63
-PAIR_TABLE_BYTES = 1 << 30                  # the device form's cap on the pair tables' workspace
-
-
-# ---------------------------------------------------------------------------------------------------- the tables' geometry
-def tracker_index_np(rows, ids, seq_start):
-    """ rows (N, D, 36), ids (N, D) -> (trk (N, D) int32: the index of a live row's id among the ids of its sequence, ascending; -1
-    otherwise, [n_trk per sequence]) """
-    rows, ids = np.asarray(rows), np.asarray(ids)
-    live = (rows[:, :, 14] >= 0) & (ids >= 0)
-    trk, n_trk = np.full(ids.shape, -1, np.int32), []
-    for s in range(len(seq_start) - 1):
-        f0, f1 = int(seq_start[s]), int(seq_start[s + 1])
-        m = live[f0:f1]
-        u, inv = np.unique(ids[f0:f1][m], return_inverse=True)
-        trk[f0:f1][m] = inv.astype(np.int32)
-        n_trk.append(int(u.size))
-    return trk, n_trk
-
-
-def tracker_index_device(rows, ids, seq_start):
-    """ the same with torch ops on device tensors: the ids are not read back, only how many there are """
-    import torch
-    live = (rows[:, :, 14] >= 0) & (ids >= 0)
-    trk, n_trk = torch.full_like(ids, -1), []
-    for s in range(len(seq_start) - 1):
-        f0, f1 = int(seq_start[s]), int(seq_start[s + 1])
-        m = live[f0:f1]
-        u, inv = torch.unique(ids[f0:f1][m], sorted=True, return_inverse=True)
-        trk[f0:f1][m] = inv.to(torch.int32)
-        n_trk.append(int(u.numel()))
-    return trk, n_trk
-
-
-def tables(seq_start, n_gt, n_trk):
-    """ -> (seq_tab (S, 6) int32: cell_base, n_gt, n_trk, vec_base, first frame, one past the last; frame_tab (N, 4) int32: a frame's
-    line is its sequence's first four; cells; vecs) """
-    S = len(seq_start) - 1
-    frames = np.diff(np.asarray(seq_start, np.int64))
-    if frames.size and int(frames.max()) > MAX_FRAMES:
-        raise ValueError('a sequence has {} frames, HOTA takes at most {}'.format(int(frames.max()), MAX_FRAMES))
-    n_gt, n_trk = np.asarray(n_gt, np.int64).reshape(S), np.asarray(n_trk, np.int64).reshape(S)
-    cell_base = np.concatenate([[0], np.cumsum(n_gt * n_trk)])
-    vec_base = np.concatenate([[0], np.cumsum(n_gt + n_trk)])
-    seq_tab = np.stack([cell_base[:-1], n_gt, n_trk, vec_base[:-1], np.asarray(seq_start[:-1], np.int64), np.asarray(seq_start[1:], np.int64)],
-                       axis=1).reshape(S, 6)
-    cells, vecs = int(cell_base[-1]), int(vec_base[-1])
-    if max(cells, vecs) >= 1 << 31:
-        raise ValueError('pair tables of {} cells: HOTA takes fewer than 2^31'.format(cells))
-    seq_tab = seq_tab.astype(np.int32)
-    return seq_tab, np.ascontiguousarray(np.repeat(seq_tab[:, :4], frames, axis=0)), cells, vecs
 
 
 # ---------------------------------------------------------------------------------------------------- one frame on the host
-def similarity_np(plane, label_outcome, row_outcome):
-    """ plane (D, A) float64 -- one plane of the overlaps --, the frame's codes -> (q (G', T') int64, label_index (G',), row_index (T',)):
-    the counting labels are q's rows, the kept rows its columns, both ascending """
-    lout, rout = np.asarray(label_outcome), np.asarray(row_outcome)
-    gl, rl = np.flatnonzero((lout == 1) | (lout == 2)), np.flatnonzero((rout == 1) | (rout == 3))
-    o = np.asarray(plane, np.float64)[np.ix_(rl, gl)].T
-    with np.errstate(invalid='ignore', over='ignore'):
-        x = np.where(o > 0.0, o, 0.0) * float(SCALE)                                    # (NaN and o <= 0: 0)
-        q = np.floor(np.where(x > float(SCALE), float(SCALE), x)).astype(np.int64)
-    return q, gl, rl
-
-
 def potential_np(q, g, t, P, gc, tc):
-    """ pass 1 of one frame, in place: q (G', T') int64, g (G',) the labels' trajectories, t (T',) the rows' tracker indices; P (n_gt, n_trk)
-    int64, gc (n_gt,) and tc (n_trk,) int32 are the sequence's """
+    """ pass 1 of one frame, in place: q (G', T') int64 -- utils/pair_tables.similarity_np's --, g (G',) the labels' trajectories, t (T',)
+    the rows' tracker indices; P (n_gt, n_trk) int64, gc (n_gt,) and tc (n_trk,) int32 are the sequence's """
     q = np.asarray(q, np.int64)
     rs, cs = q.sum(axis=1, keepdims=True), q.sum(axis=0, keepdims=True)
     den = np.where(q > 0, rs + cs - q, 1)
@@ -183,7 +121,7 @@ def summarise_hota(counts):
     return out
 
 
-def _add(result, packed, match, frame_hota, seq_hota, pairs):
+def _add(result, match, frame_hota, seq_hota, pairs):
     for s, e in enumerate(result['sequences']):
         e['hota'] = summarise_hota(seq_hota[s])
     result['all']['hota'] = summarise_hota(seq_hota.sum(axis=0) if seq_hota.shape[0] else np.zeros((LEVELS, SEQ_COLS), np.int64))
@@ -193,22 +131,14 @@ def _add(result, packed, match, frame_hota, seq_hota, pairs):
 
 
 # ---------------------------------------------------------------------------------------------------- the host form
-def add_hota_np(result, packed, params):
+def add_hota_np(result, packed, params, similarities=None):
     """ the NumPy form: adds 'hota' to every summary of utils/mot_eval's result and 'hota_frames' {'match' (N, A) int32, 'counts' (N, 40)
-    int64} and 'hota_pairs' [per sequence {'P' int64, 'A' int32 (n_gt, n_trk), 'hist' int32 (n_gt, n_trk, 20), 'gc', 'tc' int32}] """
+    int64} and 'hota_pairs' [per sequence {'P' int64, 'A' int32 (n_gt, n_trk), 'hist' int32 (n_gt, n_trk, 20), 'gc', 'tc' int32}].
+    similarities: the frames' utils/pair_tables.similarity_np where the caller has them; formed here otherwise """
     N, A = packed.labels.shape[0], packed.labels.shape[1]
-    lout, rout = result['frames']['label_outcome'], result['frames']['row_outcome']
     seq_start = np.asarray(packed.seq_start)
     S = len(seq_start) - 1
-    trk, n_trk = tracker_index_np(packed.rows, packed.ids, seq_start)
-    n_gt = [t.size for t in packed.traj_ids]
-    tables(seq_start, n_gt, n_trk)                                                      # (the frame limit)
-    plane = mot_eval.METRICS.index(params['metric'])
-    frames = []
-    for f in range(N):
-        c = int(packed.label_counts[f])
-        o = kitti_eval.image_overlaps(packed.rows[f], packed.labels[f, :c])[plane]
-        frames.append(similarity_np(o, lout[f, :c], rout[f]))
+    trk, n_gt, n_trk, frames = pair_tables.frames_np(result, packed, params, similarities)
     match, frame_hota = np.full((N, A), -1, np.int32), np.zeros((N, FRAME_COLS), np.int64)
     seq_hota, pairs = np.zeros((S, LEVELS, SEQ_COLS), np.int64), []
     for s in range(S):
@@ -232,42 +162,27 @@ def add_hota_np(result, packed, params):
             frame_hota[f, 2 * LEVELS:] = gl.size, rl.size
         seq_hota[s] = reduce_np(hist, gc, tc, frame_hota[f0:f1])
         pairs.append({'P': P, 'A': align, 'hist': hist, 'gc': gc, 'tc': tc})
-    return _add(result, packed, match, frame_hota, seq_hota, pairs)
+    return _add(result, match, frame_hota, seq_hota, pairs)
 
 
 # ---------------------------------------------------------------------------------------------------- the device form
 class DeviceRun(object):
     """ csrc/hota_eval.hip beside utils/mot_eval.evaluate_packed_device's walk over the chunks: potential() in the first sweep, finish()
-    runs the second sweep and the reduction """
+    runs the second sweep and the reduction.  geo: the call's utils/pair_tables.Geometry """
 
-    def __init__(self, packed, params, rows, ids, traj, step):
+    def __init__(self, geo, step, device):
         from ..backend import hip
-        self.hip, self.packed, self.traj = hip, packed, traj
-        self.metric = mot_eval.METRICS.index(params['metric'])
-        seq_start = np.asarray(packed.seq_start)
-        self.N, self.S = int(seq_start[-1]), len(seq_start) - 1
-        if mot_eval._is_tensor(packed.rows):
-            self.trk, n_trk = tracker_index_device(rows, ids, seq_start)
-        else:
-            import torch
-            trk, n_trk = tracker_index_np(packed.rows, packed.ids, seq_start)
-            self.trk = torch.as_tensor(trk).to(rows.device, non_blocking=True)
-        self.n_gt, self.n_trk = [t.size for t in packed.traj_ids], n_trk
-        self.seq_tab, self.frame_tab, self.cells, self.vecs = tables(seq_start, self.n_gt, n_trk)
-        need = 92 * self.cells + 4 * self.vecs                                          # (before any library call: P, A, hist, the counters)
-        if need > PAIR_TABLE_BYTES or self.cells >= 1 << 31:
+        self.hip, self.geo = hip, geo
+        need = 92 * geo.cells + 4 * geo.vecs                                            # (before any library call: P, A, hist, the counters)
+        if need > pair_tables.PAIR_TABLE_BYTES or geo.cells >= 1 << 31:
             raise ValueError('the pair tables of {} cells need {} bytes, the device form takes {}: use device=False'.format(
-                self.cells, need, PAIR_TABLE_BYTES))
-        self.workspace = hip.hota_workspace(self.cells, self.vecs, min(step, self.N), self.S, rows.device)
+                geo.cells, need, pair_tables.PAIR_TABLE_BYTES))
+        self.workspace = hip.hota_workspace(geo.cells, geo.vecs, min(step, geo.N), geo.S, device)
         self.codes, self.kept = [], None
-
-    def _chunk(self, at, n):
-        return self.traj[at:at + n], self.trk[at:at + n], self.frame_tab[at:at + n].reshape(-1)
 
     def potential(self, at, overlaps, label_outcome, row_outcome, keep):
         """ pass 1 of the chunk that starts at frame `at`; keep: the call has a single chunk, its overlaps serve pass 2 """
-        traj, trk, tab = self._chunk(at, int(overlaps.shape[0]))
-        self.hip.hota_potential(overlaps, label_outcome, row_outcome, traj, trk, self.metric, tab, self.cells, self.vecs, self.workspace)
+        self.hip.hota_potential(overlaps, label_outcome, row_outcome, *self.geo.chunk(at, int(overlaps.shape[0])), self.workspace)
         self.codes.append((at, label_outcome, row_outcome))
         self.kept = overlaps if keep else None
 
@@ -275,35 +190,33 @@ class DeviceRun(object):
         """ pass 2 over the chunks -- overlaps_of(at, n) recomputes a chunk's overlaps --, then the reduction
         -> (match (N, A) int32, frame_hota (N, 40) int64, seq_hota (S, 19, 8) int64) on the device """
         import torch
-        hip, parts = self.hip, []
+        hip, geo, parts = self.hip, self.geo, []
         for at, lout, rout in self.codes:
             n = int(lout.shape[0])
             overlaps = self.kept if self.kept is not None else overlaps_of(at, n)
-            traj, trk, tab = self._chunk(at, n)
-            parts.append(hip.hota_match(overlaps, lout, rout, traj, trk, self.metric, tab, self.cells, self.vecs, self.workspace))
+            parts.append(hip.hota_match(overlaps, lout, rout, *geo.chunk(at, n), self.workspace))
         dev = self.workspace.device
         if parts:
             match, frame_hota = [parts[0][k] if len(parts) == 1 else torch.cat([p[k] for p in parts]) for k in range(2)]
         else:
-            match = torch.zeros((0, int(self.traj.shape[1])), dtype=torch.int32, device=dev)
+            match = torch.zeros((0, int(geo.traj.shape[1])), dtype=torch.int32, device=dev)
             frame_hota = torch.zeros((0, FRAME_COLS), dtype=torch.int64, device=dev)
-        seq_hota = hip.hota_reduce(frame_hota, self.seq_tab.reshape(-1), self.cells, self.vecs, self.workspace)
+        seq_hota = hip.hota_reduce(frame_hota, geo.seq_tab.reshape(-1), geo.cells, geo.vecs, self.workspace)
         return match, frame_hota, seq_hota
 
     def pairs(self):
         """ the pair tables, downloaded: [per sequence {'P', 'A', 'hist', 'gc', 'tc'}] """
-        P, align, hist, cnt = [t.cpu().numpy() for t in self.hip.hota_tables(self.workspace, self.cells, self.vecs)]
+        geo = self.geo
+        P, align, hist, cnt = [t.cpu().numpy() for t in self.hip.hota_tables(self.workspace, geo.cells, geo.vecs)]
         out = []
-        for (cell_base, n_gt, n_trk, vec_base, _, _) in self.seq_tab.tolist():
-            cells = slice(cell_base, cell_base + n_gt * n_trk)
-            out.append({'P': P[cells].reshape(n_gt, n_trk).copy(), 'A': align[cells].reshape(n_gt, n_trk).copy(),
-                        'hist': hist[cells].reshape(n_gt, n_trk, HIST).copy(), 'gc': cnt[vec_base:vec_base + n_gt].copy(),
-                        'tc': cnt[vec_base + n_gt:vec_base + n_gt + n_trk].copy()})
+        for s in range(geo.S):
+            gc, tc = geo.counters_of(s, cnt)
+            out.append({'P': geo.cells_of(s, P), 'A': geo.cells_of(s, align), 'hist': geo.cells_of(s, hist), 'gc': gc, 'tc': tc})
         return out
 
     def add_to(self, result, overlaps_of):
         match, frame_hota, seq_hota = self.finish(overlaps_of)
-        return _add(result, self.packed, match.cpu().numpy(), frame_hota.cpu().numpy(), seq_hota.cpu().numpy(), self.pairs())
+        return _add(result, match.cpu().numpy(), frame_hota.cpu().numpy(), seq_hota.cpu().numpy(), self.pairs())
 
 
 # ---------------------------------------------------------------------------------------------------- the entry point and the table

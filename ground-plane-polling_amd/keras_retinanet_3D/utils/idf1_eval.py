@@ -5,10 +5,10 @@ what it explains (IDTP) against what it leaves (IDFN, IDFP) -- DESIGN.md section
 identity.py is UNPINNED (TrackEval is not part of this repository).  include/gpp.h (gpp_idf1_count, gpp_idf1_assign) is the device form's
 contract.
 
-The inputs are HOTA's (utils/hota_eval.py, section 4.30): utils/mot_eval.py's assignment, with the call's metric and limits, is the
-preprocessing.  A label COUNTS iff its label_outcome is 1 or 2, a row is KEPT iff its row_outcome is 1 or 3; the tables' geometry is
-utils/hota_eval.tables'.  Everything after q = floor(min(overlap * 2^20, 2^20)) is exact integers, so the two forms and the loop-written
-oracle of the tests are equal with ==:
+The inputs are HOTA's: utils/mot_eval.py's assignment, with the call's metric and limits, is the
+preprocessing.  A label COUNTS iff its label_outcome is 1 or 2, a row is KEPT iff its row_outcome is 1 or 3; the tables' geometry and
+the similarity are utils/pair_tables.py's.  Everything after q = floor(min(overlap * 2^20, 2^20)) is exact integers, so the two forms and
+the loop-written oracle of the tests are equal with ==:
 
     device=False    NumPy: count_np (pass 1), assign_table_np (pass 2: section 4.29's rule on a rectangular matrix, vectorised over the
                     columns and serial over the steps).
@@ -18,9 +18,8 @@ Both end in the same host code (summarise_idf1), fed with the same integers.
 """
 import numpy as np
 
-from . import hota_eval
-from . import kitti_eval
 from . import mot_eval
+from . import pair_tables
 
 SCALE_BITS, SCALE = mot_eval.SCALE_BITS, mot_eval.SCALE
 HALF = SCALE >> 1                           # q >= 2^19 is overlap >= 0.5: the scaling is exact
@@ -43,7 +42,7 @@ def check_sides(n_gt, n_trk):
 
 # ---------------------------------------------------------------------------------------------------- the two passes on the host
 def count_np(q, g, t, C, gc, tc):
-    """ pass 1 of one frame, in place: q (G', T') int64 -- utils/hota_eval.similarity_np's --, g (G',) the labels' trajectories, t (T',)
+    """ pass 1 of one frame, in place: q (G', T') int64 -- utils/pair_tables.similarity_np's --, g (G',) the labels' trajectories, t (T',)
     the rows' tracker indices; C (n_gt, n_trk), gc (n_gt,) and tc (n_trk,) int32 are the sequence's.  A label may count with two rows. """
     np.add.at(C, (np.asarray(g)[:, None], np.asarray(t)[None, :]), (np.asarray(q, np.int64) >= HALF).astype(C.dtype))
     np.add.at(gc, g, 1)
@@ -133,26 +132,21 @@ def _add(result, seq_idf1, pairs):
 
 
 # ---------------------------------------------------------------------------------------------------- the host form
-def add_idf1_np(result, packed, params):
+def add_idf1_np(result, packed, params, similarities=None):
     """ the NumPy form: adds 'idf1' to every summary of utils/mot_eval's result and 'idf1_pairs' [per sequence {'C' (n_gt, n_trk), 'gc'
-    (n_gt,), 'tc' (n_trk,), 'match' (n_gt,), all int32}] """
-    lout, rout = result['frames']['label_outcome'], result['frames']['row_outcome']
+    (n_gt,), 'tc' (n_trk,), 'match' (n_gt,), all int32}].
+    similarities: the frames' utils/pair_tables.similarity_np where the caller has them; formed here otherwise """
     seq_start = np.asarray(packed.seq_start)
     S = len(seq_start) - 1
-    trk, n_trk = hota_eval.tracker_index_np(packed.rows, packed.ids, seq_start)
-    n_gt = [t.size for t in packed.traj_ids]
-    hota_eval.tables(seq_start, n_gt, n_trk)                                            # (the frame limit)
+    trk, n_gt, n_trk, frames = pair_tables.frames_np(result, packed, params, similarities)
     for s in range(S):
         check_sides(n_gt[s], n_trk[s])
-    plane = mot_eval.METRICS.index(params['metric'])
     seq_idf1, pairs = np.zeros((S, SEQ_COLS), np.int64), []
     for s in range(S):
         C = np.zeros((n_gt[s], n_trk[s]), np.int32)
         gc, tc = np.zeros(n_gt[s], np.int32), np.zeros(n_trk[s], np.int32)
         for f in range(int(seq_start[s]), int(seq_start[s + 1])):
-            c = int(packed.label_counts[f])
-            o = kitti_eval.image_overlaps(packed.rows[f], packed.labels[f, :c])[plane]
-            q, gl, rl = hota_eval.similarity_np(o, lout[f, :c], rout[f])
+            q, gl, rl = frames[f]
             count_np(q, packed.traj[f, gl], trk[f, rl], C, gc, tc)
         match, seq_idf1[s] = seq_counts_np(C, gc, tc)
         pairs.append({'C': C, 'gc': gc, 'tc': tc, 'match': match})
@@ -162,51 +156,35 @@ def add_idf1_np(result, packed, params):
 # ---------------------------------------------------------------------------------------------------- the device form
 class DeviceRun(object):
     """ csrc/idf1_eval.hip beside utils/mot_eval.evaluate_packed_device's walk over the chunks: count() in the one sweep, add_to() runs the
-    assignment.  hota_run: utils/hota_eval.DeviceRun of the same call -- its tracker indices and tables serve both """
+    assignment.  geo: the call's utils/pair_tables.Geometry, which HOTA's run of the same call works on too """
 
-    def __init__(self, packed, params, rows, ids, traj, step, hota_run=None):
+    def __init__(self, geo, step, device):
         from ..backend import hip
-        self.hip, self.traj = hip, traj
-        self.metric = mot_eval.METRICS.index(params['metric'])
-        seq_start = np.asarray(packed.seq_start)
-        self.N, self.S = int(seq_start[-1]), len(seq_start) - 1
-        if hota_run is not None:
-            self.trk, self.n_gt, self.n_trk = hota_run.trk, hota_run.n_gt, hota_run.n_trk
-            self.seq_tab, self.frame_tab, self.cells, self.vecs = hota_run.seq_tab, hota_run.frame_tab, hota_run.cells, hota_run.vecs
-        else:
-            if mot_eval._is_tensor(packed.rows):
-                self.trk, self.n_trk = hota_eval.tracker_index_device(rows, ids, seq_start)
-            else:
-                import torch
-                trk, self.n_trk = hota_eval.tracker_index_np(packed.rows, packed.ids, seq_start)
-                self.trk = torch.as_tensor(trk).to(rows.device, non_blocking=True)
-            self.n_gt = [t.size for t in packed.traj_ids]
-            self.seq_tab, self.frame_tab, self.cells, self.vecs = hota_eval.tables(seq_start, self.n_gt, self.n_trk)
-        for g, t in zip(self.n_gt, self.n_trk):
+        self.hip, self.geo = hip, geo
+        for g, t in zip(geo.n_gt, geo.n_trk):
             check_sides(g, t)
-        need = 4 * self.cells + 4 * self.vecs                                           # (before any library call: C and the counters)
-        if need > hota_eval.PAIR_TABLE_BYTES:
+        need = 4 * geo.cells + 4 * geo.vecs                                             # (before any library call: C and the counters)
+        if need > pair_tables.PAIR_TABLE_BYTES:
             raise ValueError('the tables of {} cells need {} bytes, the device form takes {}: use device=False'.format(
-                self.cells, need, hota_eval.PAIR_TABLE_BYTES))
-        self.workspace = hip.idf1_workspace(self.cells, self.vecs, min(step, self.N), self.S, rows.device)
+                geo.cells, need, pair_tables.PAIR_TABLE_BYTES))
+        self.workspace = hip.idf1_workspace(geo.cells, geo.vecs, min(step, geo.N), geo.S, device)
 
     def count(self, at, overlaps, label_outcome, row_outcome):
         """ pass 1 of the chunk that starts at frame `at` """
-        n = int(overlaps.shape[0])
-        self.hip.idf1_count(overlaps, label_outcome, row_outcome, self.traj[at:at + n], self.trk[at:at + n], self.metric,
-                            self.frame_tab[at:at + n].reshape(-1), self.cells, self.vecs, self.workspace)
+        self.hip.idf1_count(overlaps, label_outcome, row_outcome, *self.geo.chunk(at, int(overlaps.shape[0])), self.workspace)
 
     def finish(self):
         """ pass 2, after the sweep -> (id_match (vecs,) int32, seq_idf1 (S, 8) int64) on the device """
-        return self.hip.idf1_assign(self.seq_tab.reshape(-1), self.cells, self.vecs, self.workspace)
+        return self.hip.idf1_assign(self.geo.seq_tab.reshape(-1), self.geo.cells, self.geo.vecs, self.workspace)
 
     def add_to(self, result):
+        geo = self.geo
         id_match, seq_idf1 = self.finish()
-        C, cnt = [t.cpu().numpy() for t in self.hip.idf1_tables(self.workspace, self.cells, self.vecs)]
+        C, cnt = [t.cpu().numpy() for t in self.hip.idf1_tables(self.workspace, geo.cells, geo.vecs)]
         id_match, pairs = id_match.cpu().numpy(), []
-        for (cell_base, n_gt, n_trk, vec_base, _, _) in self.seq_tab.tolist():
-            pairs.append({'C': C[cell_base:cell_base + n_gt * n_trk].reshape(n_gt, n_trk).copy(), 'gc': cnt[vec_base:vec_base + n_gt].copy(),
-                          'tc': cnt[vec_base + n_gt:vec_base + n_gt + n_trk].copy(), 'match': id_match[vec_base:vec_base + n_gt].copy()})
+        for s in range(geo.S):
+            gc, tc = geo.counters_of(s, cnt)
+            pairs.append({'C': geo.cells_of(s, C), 'gc': gc, 'tc': tc, 'match': geo.counters_of(s, id_match)[0]})
         return _add(result, seq_idf1.cpu().numpy(), pairs)
 
 

@@ -356,21 +356,27 @@ def _result(packed, params, match, lout, rout, frame_counts, seq_counts, tables,
 
 
 def evaluate_packed_np(packed, params, names=None, hota=False, idf1=False):
+    """ the NumPy form.  A frame's overlaps are computed once: with hota or idf1 its similarity (utils/pair_tables.similarity_np) is formed
+    from them here, behind the frame's codes, and handed to both scores """
     N, A, D = packed.labels.shape[0], packed.labels.shape[1], packed.rows.shape[1]
     match, lout = np.full((N, A), -1, np.int32), np.zeros((N, A), np.int32)
     rout, frame_counts = np.zeros((N, D), np.int32), np.zeros((N, 8), np.int64)
+    from . import pair_tables
+    plane, similarities = METRICS.index(params['metric']), []
     for f in range(N):
         c = int(packed.label_counts[f])
         o = kitti_eval.image_overlaps(packed.rows[f], packed.labels[f, :c])
         match[f, :c], lout[f, :c], rout[f], frame_counts[f] = frame_np(o, packed.labels[f, :c], packed.rows[f], packed.ids[f], params)
+        if hota or idf1:
+            similarities.append(pair_tables.similarity_np(o[plane], lout[f, :c], rout[f]))
     seq_counts, tables = clear_np(match, lout, packed.traj, packed.ids, frame_counts, packed.seq_start, [t.size for t in packed.traj_ids])
     result = _result(packed, params, match, lout, rout, frame_counts, seq_counts, tables, names)
     if hota:
         from . import hota_eval
-        hota_eval.add_hota_np(result, packed, params)
+        hota_eval.add_hota_np(result, packed, params, similarities)
     if idf1:
         from . import idf1_eval
-        idf1_eval.add_idf1_np(result, packed, params)
+        idf1_eval.add_idf1_np(result, packed, params, similarities)
     return result
 
 
@@ -379,7 +385,8 @@ def evaluate_packed_device(packed, params, names=None, hota=False, idf1=False):
     per chunk, then one launch for all trajectories; rows and ids that are device tensors already are used where they lie.
     hota: csrc/hota_eval.hip beside it (utils/hota_eval.DeviceRun) -- its pass 1 in this sweep over the chunks, its pass 2 in a second
     sweep, which recomputes the overlaps unless the call has a single chunk.
-    idf1: csrc/idf1_eval.hip (utils/idf1_eval.DeviceRun) -- its count in this sweep over the chunks, its one assignment after it """
+    idf1: csrc/idf1_eval.hip (utils/idf1_eval.DeviceRun) -- its count in this sweep over the chunks, its one assignment after it.
+    Both work on one utils/pair_tables.Geometry, built once """
     import torch
     from ..backend import hip
     dev = packed.rows.device if _is_tensor(packed.rows) else hip.require_device()
@@ -395,14 +402,16 @@ def evaluate_packed_device(packed, params, names=None, hota=False, idf1=False):
     counts = torch.as_tensor(packed.label_counts).to(dev, non_blocking=True)
     traj = torch.as_tensor(packed.traj).to(dev, non_blocking=True)
     step = kitti_eval.chunk_images(D, A)
-    hota_run = None
+    hota_run = idf1_run = None
+    if hota or idf1:
+        from . import pair_tables
+        geometry = pair_tables.Geometry(packed, params, rows, ids, traj)
     if hota:
         from . import hota_eval
-        hota_run = hota_eval.DeviceRun(packed, params, rows, ids, traj, step)
-    idf1_run = None
+        hota_run = hota_eval.DeviceRun(geometry, step, rows.device)
     if idf1:
         from . import idf1_eval
-        idf1_run = idf1_eval.DeviceRun(packed, params, rows, ids, traj, step, hota_run)
+        idf1_run = idf1_eval.DeviceRun(geometry, step, rows.device)
     parts = []
     for at in range(0, N, step):
         r, g, c, i = rows[at:at + step], labels[at:at + step], counts[at:at + step], ids[at:at + step]

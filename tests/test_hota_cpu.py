@@ -16,6 +16,7 @@ import mot_oracle as O
 from keras_retinanet_3D.backend import hip
 from keras_retinanet_3D.utils import hota_eval as H
 from keras_retinanet_3D.utils import mot_eval as M
+from keras_retinanet_3D.utils import pair_tables as PT
 from test_mot_eval_cpu import write_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -225,24 +226,24 @@ def test_without_hota_the_result_is_todays():
 
 def test_value_errors(monkeypatch):
     labels, tracks = O.scene(21, frames=5, cars=5)
-    monkeypatch.setattr(H, 'MAX_FRAMES', 4)
+    monkeypatch.setattr(PT, 'MAX_FRAMES', 4)
     with pytest.raises(ValueError, match='at most 4'):
         M.evaluate_sequences([labels], [tracks], hota=True)
     assert 'hota' not in M.evaluate_sequences([labels], [tracks])['all']                # (the limit is HOTA's alone)
     with pytest.raises(ValueError, match='at most 4'):
-        H.tables([0, 5], [3], [3])
+        PT.tables([0, 5], [3], [3])
     for bad in (dict(metric='iou'), dict(min_overlap=1.5)):
         with pytest.raises(ValueError):
             H.evaluate_hota_sequences([labels], [tracks], **bad)
 
 
 def test_tables_geometry():
-    seq_tab, frame_tab, cells, vecs = H.tables([0, 2, 2, 5], [3, 0, 2], [4, 0, 5])
+    seq_tab, frame_tab, cells, vecs = PT.tables([0, 2, 2, 5], [3, 0, 2], [4, 0, 5])
     assert seq_tab.tolist() == [[0, 3, 4, 0, 0, 2], [12, 0, 0, 7, 2, 2], [12, 2, 5, 7, 2, 5]] and (cells, vecs) == (22, 14)
     assert frame_tab.tolist() == [[0, 3, 4, 0]] * 2 + [[12, 2, 5, 7]] * 3
     rows = np.full((3, 2, 36), -1.0, np.float32)
     rows[0, :, 14] = rows[1, 0, 14] = rows[2, 1, 14] = 0.0
-    trk, n_trk = H.tracker_index_np(rows, np.array([[9, 4], [7, 4], [-1, 9]], np.int32), [0, 2, 3])
+    trk, n_trk = PT.tracker_index_np(rows, np.array([[9, 4], [7, 4], [-1, 9]], np.int32), [0, 2, 3])
     assert trk.tolist() == [[2, 0], [1, -1], [-1, 0]] and n_trk == [3, 1] and trk.dtype == np.int32
 
 
@@ -287,7 +288,7 @@ def test_header_constants_and_contract():
     assert define('GPP_HOTA_FRAME_COLS') == H.FRAME_COLS == hip.GPP_HOTA_FRAME_COLS == 40
     assert define('GPP_HOTA_SEQ_COLS') == H.SEQ_COLS == hip.GPP_HOTA_SEQ_COLS == 8 and len(H.SEQ_INTEGERS) == 7
     assert define('GPP_HOTA_TAB_COLS') == hip.GPP_HOTA_TAB_COLS == 4 and define('GPP_HOTA_SEQ_TAB_COLS') == hip.GPP_HOTA_SEQ_TAB_COLS == 6
-    assert H.SCALE == HO.S == 1 << define('GPP_MOT_SCALE_BITS') and H.PAIR_TABLE_BYTES == 1 << 30 and H.MAX_FRAMES == 1 << 20
+    assert H.SCALE == HO.S == 1 << define('GPP_MOT_SCALE_BITS') and PT.PAIR_TABLE_BYTES == 1 << 30 and PT.MAX_FRAMES == 1 << 20
     contract = ' '.join(text[text.index('HOTA scoring of tracks on the device'):text.index('#define GPP_HOTA_LEVELS')].replace('\n *', '\n').split())
     for phrase in ('UNPINNED', 'there is no admissibility test', 'operation for operation', 'on the HOST', 'ZEROED by the caller',
                    'EVERY frame of a sequence before gpp_hota_match', 'GPP_ERR_UNSUPPORTED', 'GPP_ERR_WORKSPACE', '(20 q + 19) >> 20'):

@@ -12,6 +12,7 @@ import mot_oracle as O
 from keras_retinanet_3D.utils import hota_eval as H
 from keras_retinanet_3D.utils import kitti_eval
 from keras_retinanet_3D.utils import mot_eval as M
+from keras_retinanet_3D.utils import pair_tables as PT
 from keras_retinanet_3D.utils import track as T
 from test_mot_eval_gpu import drive, same_result
 
@@ -132,7 +133,7 @@ def test_tracker_tensors_are_scored_where_they_lie():
 
 def test_capped_workspace_is_a_value_error(monkeypatch):
     labels, tracks = O.scene(8, frames=3, cars=4)
-    monkeypatch.setattr(H, 'PAIR_TABLE_BYTES', 64)
+    monkeypatch.setattr(PT, 'PAIR_TABLE_BYTES', 64)
     with pytest.raises(ValueError, match='device=False'):
         M.evaluate_sequences([labels], [tracks], device=True, hota=True)
     assert 'hota' not in M.evaluate_sequences([labels], [tracks], device=True)['all']   # (the cap is HOTA's alone)

@@ -14,9 +14,9 @@ import hota_oracle as HO
 import idf1_oracle as IO
 import mot_oracle as O
 from keras_retinanet_3D.backend import hip
-from keras_retinanet_3D.utils import hota_eval as H
 from keras_retinanet_3D.utils import idf1_eval as I
 from keras_retinanet_3D.utils import mot_eval as M
+from keras_retinanet_3D.utils import pair_tables as PT
 from test_mot_eval_cpu import write_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -141,7 +141,7 @@ def test_an_overlap_of_exactly_one_half_counts_and_the_double_below_does_not():
     C, gc, tc = np.zeros((1, 1), np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
     below = np.nextafter(0.5, 0.0)
     for o, want in ((0.5, 1), (below, 1), (1.0, 2), (float('nan'), 2), (0.0, 2)):
-        q, gl, rl = H.similarity_np(np.array([[o]]), [1], [3])
+        q, gl, rl = PT.similarity_np(np.array([[o]]), [1], [3])
         I.count_np(q, [0], [0], C, gc, tc)
         assert int(C[0, 0]) == want, o
     assert gc.tolist() == [5] and tc.tolist() == [5] and int(np.floor(below * S)) == (S >> 1) - 1
@@ -162,6 +162,31 @@ def test_counters_equal_hotas_when_both_are_requested():
         for a, b in zip(got['idf1_pairs'], got['hota_pairs']):
             assert np.array_equal(a['gc'], b['gc']) and np.array_equal(a['tc'], b['tc']) and a['gc'].dtype == b['gc'].dtype
             assert a['C'].shape == b['P'].shape and not (a['C'] > 0)[b['P'] == 0].any()     # (no overlap, no count)
+
+
+def same_tree(a, b):
+    """ two results, key for key: arrays by dtype, shape and value, everything else by == """
+    if isinstance(a, dict):
+        return isinstance(b, dict) and sorted(a) == sorted(b) and all(same_tree(a[k], b[k]) for k in a)
+    if isinstance(a, (list, tuple)):
+        return type(a) is type(b) and len(a) == len(b) and all(same_tree(x, y) for x, y in zip(a, b))
+    if isinstance(a, np.ndarray):
+        return isinstance(b, np.ndarray) and a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b)
+    return a == b
+
+
+def test_the_host_form_computes_a_frames_overlaps_once(monkeypatch):
+    """ with both scores requested the NumPy form walks every frame's overlaps once -- the assignment, HOTA and the identity scores work on
+    the same ones -- and the result is what it is without the counter """
+    labels, tracks, _, options = CASES['empty']          # two sequences, of three frames and of none
+    frames = sum(max(len(g[0]), len(t[0])) for g, t in zip(labels, tracks))
+    assert len(labels) == 2 and frames == 3
+    want = M.evaluate_sequences(labels, tracks, device=False, hota=True, idf1=True, **options)
+    calls = []
+    monkeypatch.setattr(M.kitti_eval, 'image_overlaps', lambda *a, _f=M.kitti_eval.image_overlaps: calls.append(1) or _f(*a))
+    got = M.evaluate_sequences(labels, tracks, device=False, hota=True, idf1=True, **options)
+    assert len(calls) == frames
+    assert {'hota_frames', 'hota_pairs', 'idf1_pairs'} <= set(got) and same_tree(got, want)
 
 
 def test_ignored_and_empty():
@@ -232,7 +257,7 @@ def test_value_errors(monkeypatch):
     with pytest.raises(ValueError, match='at most 2'):
         M.evaluate_sequences([labels], [tracks], idf1=True)
     monkeypatch.setattr(I, 'MAX_TRAJECTORIES', 1024)
-    monkeypatch.setattr(H, 'MAX_FRAMES', 4)
+    monkeypatch.setattr(PT, 'MAX_FRAMES', 4)
     with pytest.raises(ValueError, match='at most 4'):
         M.evaluate_sequences([labels], [tracks], idf1=True)
     for bad in (dict(metric='iou'), dict(min_overlap=1.5)):

@@ -11,10 +11,10 @@ import hota_oracle as HO
 import idf1_oracle as IO
 import mot_oracle as O
 from keras_retinanet_3D.backend import hip
-from keras_retinanet_3D.utils import hota_eval as H
 from keras_retinanet_3D.utils import idf1_eval as I
 from keras_retinanet_3D.utils import kitti_eval
 from keras_retinanet_3D.utils import mot_eval as M
+from keras_retinanet_3D.utils import pair_tables as PT
 from keras_retinanet_3D.utils import track as T
 from test_hota_gpu import same_hota
 from test_mot_eval_gpu import drive, same_result
@@ -115,10 +115,10 @@ def test_without_idf1_the_device_result_is_todays():
 
 def test_capped_workspace_is_a_value_error(monkeypatch):
     labels, tracks = O.scene(8, frames=3, cars=4)
-    monkeypatch.setattr(H, 'PAIR_TABLE_BYTES', 64)
+    monkeypatch.setattr(PT, 'PAIR_TABLE_BYTES', 64)
     with pytest.raises(ValueError, match='device=False'):
         M.evaluate_sequences([labels], [tracks], device=True, idf1=True)
-    monkeypatch.setattr(H, 'PAIR_TABLE_BYTES', 1 << 30)
+    monkeypatch.setattr(PT, 'PAIR_TABLE_BYTES', 1 << 30)
     monkeypatch.setattr(I, 'MAX_IDS', 3)
     with pytest.raises(ValueError, match='at most 3'):
         M.evaluate_sequences([labels], [tracks], device=True, idf1=True)
@@ -130,7 +130,7 @@ def assign_written(tables, seed=0):
     rng = np.random.default_rng(seed)
     counters = [((C.sum(axis=1) + rng.integers(0, 3, C.shape[0])).astype(np.int32), (C.sum(axis=0) + rng.integers(0, 3, C.shape[1])).astype(np.int32))
                 for C in tables]
-    seq_tab, _, cells, vecs = H.tables([0] * (len(tables) + 1), [C.shape[0] for C in tables], [C.shape[1] for C in tables])
+    seq_tab, _, cells, vecs = PT.tables([0] * (len(tables) + 1), [C.shape[0] for C in tables], [C.shape[1] for C in tables])
     workspace = hip.idf1_workspace(cells, vecs, 0, len(tables), torch.device('cuda'))
     table, cnt = hip.idf1_tables(workspace, cells, vecs)
     for C, (gc, tc), (cell_base, n_gt, n_trk, vec_base, _, _) in zip(tables, counters, seq_tab.tolist()):
@@ -208,7 +208,7 @@ def test_count_then_assign_through_the_wrappers():
     overlaps[0, 0] = torch.tensor([[0.5, 0.0], [0.75, 0.5], [float('nan'), np.nextafter(0.5, 0.0)]], dtype=torch.float64)
     lout, rout = torch.tensor([[1, 2]], dtype=torch.int32, device=dev), torch.tensor([[1, 3, 3]], dtype=torch.int32, device=dev)
     traj, trk = torch.tensor([[1, 0]], dtype=torch.int32, device=dev), torch.tensor([[2, 0, 1]], dtype=torch.int32, device=dev)
-    seq_tab, frame_tab, cells, vecs = H.tables([0, 1], [2], [3])
+    seq_tab, frame_tab, cells, vecs = PT.tables([0, 1], [2], [3])
     workspace = hip.idf1_workspace(cells, vecs, 1, 1, dev)
     for _ in range(2):                                   # (the same frame twice: the counts add up)
         hip.idf1_count(overlaps, lout, rout, traj, trk, 0, frame_tab.reshape(-1), cells, vecs, workspace)
@@ -221,7 +221,7 @@ def test_count_then_assign_through_the_wrappers():
 # ---------------------------------------------------------------------------------------------------- validation, nothing launched
 def test_refusals_leave_the_outputs_alone():
     dev = torch.device('cuda')
-    seq_tab, _, cells, vecs = H.tables([0, 0], [2], [3])
+    seq_tab, _, cells, vecs = PT.tables([0, 0], [2], [3])
     workspace = hip.idf1_workspace(cells, vecs, 0, 1, dev)
     id_match = torch.full((vecs,), 7, dtype=torch.int32, device=dev)
     seq_idf1 = torch.full((1, 8), 7, dtype=torch.int64, device=dev)

@@ -35,6 +35,7 @@ from keras_retinanet_3D.backend import hip  # noqa: E402
 from keras_retinanet_3D.utils import hota_eval as H  # noqa: E402
 from keras_retinanet_3D.utils import kitti_eval  # noqa: E402
 from keras_retinanet_3D.utils import mot_eval as M  # noqa: E402
+from keras_retinanet_3D.utils import pair_tables as PT  # noqa: E402
 
 
 def launches(records, name, packed, params):
@@ -48,22 +49,23 @@ def launches(records, name, packed, params):
     with step_limit(180, name + ': launches alone'):
         overlaps = hip.kitti_overlaps(rows, labels, counts)
         _, lout, rout, _ = hip.mot_assign(overlaps, labels, counts, rows, ids, prm)
-        run = H.DeviceRun(packed, params, rows, ids, traj, N)
-        tab = run.frame_tab.reshape(-1)
+        geo = PT.Geometry(packed, params, rows, ids, traj)
+        run = H.DeviceRun(geo, N, dev)
+        tab = geo.frame_tab.reshape(-1)
 
         def potential():
             run.workspace.zero_()                                               # (pass 1 adds: every repeat starts from zero)
-            hip.hota_potential(overlaps, lout, rout, traj, run.trk, 0, tab, run.cells, run.vecs, run.workspace)
+            hip.hota_potential(overlaps, lout, rout, traj, geo.trk, 0, tab, geo.cells, geo.vecs, run.workspace)
 
         def match():                                                            # (hist grows with every repeat: the same atomics, other sums)
-            return hip.hota_match(overlaps, lout, rout, traj, run.trk, 0, tab, run.cells, run.vecs, run.workspace)
+            return hip.hota_match(overlaps, lout, rout, traj, geo.trk, 0, tab, geo.cells, geo.vecs, run.workspace)
 
         potential()
         frame_hota = match()[1]
         zero_med, _ = median_us(lambda: run.workspace.zero_())
         for what, launch in (('gpp_mot_assign', lambda: hip.mot_assign(overlaps, labels, counts, rows, ids, prm)),
                              ('gpp_hota_potential', potential), ('gpp_hota_match', match),
-                             ('gpp_hota_reduce', lambda: hip.hota_reduce(frame_hota, run.seq_tab.reshape(-1), run.cells, run.vecs, run.workspace))):
+                             ('gpp_hota_reduce', lambda: hip.hota_reduce(frame_hota, geo.seq_tab.reshape(-1), geo.cells, geo.vecs, run.workspace))):
             med, low = median_us(launch)
             if what == 'gpp_hota_potential':
                 med, low = round(med - zero_med, 2), round(low - zero_med, 2)
@@ -71,8 +73,8 @@ def launches(records, name, packed, params):
                             'median_us': med, 'min_us': low, 'us_per_frame': round(med / max(N, 1), 3),
                             'note': 'includes the copy of its host table and the allocation of its outputs; potential: the median of '
                                     'zeroing the workspace ({} us) is subtracted'.format(zero_med)})
-        records.append({'what': 'tables', 'workload': name, 'cells': run.cells, 'counters': run.vecs, 'workspace_bytes': int(run.workspace.numel()),
-                        'largest_table': [int(v) for v in max(run.seq_tab[:, 1:3].tolist(), key=lambda s: s[0] * s[1])]})
+        records.append({'what': 'tables', 'workload': name, 'cells': geo.cells, 'counters': geo.vecs, 'workspace_bytes': int(run.workspace.numel()),
+                        'largest_table': [int(v) for v in max(geo.seq_tab[:, 1:3].tolist(), key=lambda s: s[0] * s[1])]})
 
 
 def whole(records, name, labels, tracks, params):

@@ -40,6 +40,7 @@ from keras_retinanet_3D.utils import hota_eval as H  # noqa: E402
 from keras_retinanet_3D.utils import idf1_eval as I  # noqa: E402
 from keras_retinanet_3D.utils import kitti_eval  # noqa: E402
 from keras_retinanet_3D.utils import mot_eval as M  # noqa: E402
+from keras_retinanet_3D.utils import pair_tables as PT  # noqa: E402
 
 SCALE = I.SCALE
 
@@ -103,7 +104,7 @@ def definition_counts(C, gc, tc):
 def tables_on_device(records, steps):
     dev = hip.require_device()
     for name, tables in written_tables():
-        seq_tab, _, cells, vecs = H.tables([0] * (len(tables) + 1), [C.shape[0] for C in tables], [C.shape[1] for C in tables])
+        seq_tab, _, cells, vecs = PT.tables([0] * (len(tables) + 1), [C.shape[0] for C in tables], [C.shape[1] for C in tables])
         with step_limit(240, name):
             workspace = hip.idf1_workspace(cells, vecs, 0, len(tables), dev)
             table, cnt = hip.idf1_tables(workspace, cells, vecs)
@@ -139,17 +140,18 @@ def kitti(records, frames):
     with step_limit(180, 'kitti: launches alone'):
         overlaps = hip.kitti_overlaps(rows, lab, counts)
         _, lout, rout, _ = hip.mot_assign(overlaps, lab, counts, rows, ids, prm)
-        hota = H.DeviceRun(packed, params, rows, ids, traj, N)
-        run = I.DeviceRun(packed, params, rows, ids, traj, N, hota)
-        tab = run.frame_tab.reshape(-1)
+        geo = PT.Geometry(packed, params, rows, ids, traj)
+        hota = H.DeviceRun(geo, N, dev)
+        run = I.DeviceRun(geo, N, dev)
+        tab = geo.frame_tab.reshape(-1)
 
         def potential():
             hota.workspace.zero_()
-            hip.hota_potential(overlaps, lout, rout, traj, hota.trk, 0, tab, hota.cells, hota.vecs, hota.workspace)
+            hip.hota_potential(overlaps, lout, rout, traj, geo.trk, 0, tab, geo.cells, geo.vecs, hota.workspace)
 
         def count():
             run.workspace.zero_()                                               # (pass 1 adds: every repeat starts from zero)
-            hip.idf1_count(overlaps, lout, rout, traj, run.trk, 0, tab, run.cells, run.vecs, run.workspace)
+            hip.idf1_count(overlaps, lout, rout, traj, geo.trk, 0, tab, geo.cells, geo.vecs, run.workspace)
 
         zero = {'gpp_hota_potential': median_us(lambda: hota.workspace.zero_())[0], 'gpp_idf1_count': median_us(lambda: run.workspace.zero_())[0]}
         for what, launch in (('gpp_mot_assign', lambda: hip.mot_assign(overlaps, lab, counts, rows, ids, prm)), ('gpp_hota_potential', potential),
@@ -160,8 +162,8 @@ def kitti(records, frames):
                             'median_us': med, 'min_us': low,
                             'note': 'includes the copy of its host table and the allocation of its outputs; the median of zeroing the '
                                     'workspace ({} us) is subtracted'.format(zero.get(what, 0.0))})
-        sides = run.seq_tab[:, 1:3].tolist()
-        records.append({'what': 'tables', 'workload': 'kitti', 'cells': run.cells, 'counters': run.vecs, 'workspace_bytes': int(run.workspace.numel()),
+        sides = geo.seq_tab[:, 1:3].tolist()
+        records.append({'what': 'tables', 'workload': 'kitti', 'cells': geo.cells, 'counters': geo.vecs, 'workspace_bytes': int(run.workspace.numel()),
                         'largest_table': [int(v) for v in max(sides, key=lambda s: s[0] * s[1])]})
     with step_limit(600, 'kitti: evaluate_sequences'):
         M.evaluate_sequences(labels, tracks, device=True, idf1=True)            # (warm: the library, the allocator)
