@@ -285,6 +285,10 @@ _SIGNATURES = [
         'gpp_track_cov_bytes': [_SIZE_OUT],
         'gpp_track_kf_f64': _TRACK_HEAD + [c_void_p, c_void_p, _P(TrackParams), _P(TrackKfParams), c_void_p, c_int] + _TRACK_TAIL,
     }),
+    ('gpp_track_smooth_f64', 'the offline smoother of finished tracks (csrc/track_smooth.hip)', {
+        'gpp_track_smooth_workspace_bytes': [c_int, c_int, c_ll, _SIZE_OUT],
+        'gpp_track_smooth_f64': [c_void_p, c_int, c_int, _P(c_int64), _HOST_I32, _HOST_I32, c_int, _P(TrackKfParams), c_void_p] + [c_void_p] * 4 + _WORK,
+    }),
     ('gpp_mot_assign', 'evaluate_tracking(device=True) (csrc/mot_eval.hip)', {
         'gpp_mot_assign': [c_void_p] * 5 + [c_int] * 3 + [_P(MotParams)] + [c_void_p] * 5,
         'gpp_mot_clear_workspace_bytes': [c_int, _SIZE_OUT],
@@ -644,6 +648,54 @@ def track(rows, state_in, params, seq_start=None, state_out=None, out=None, ids=
     args += [ptr(out), ptr(ids), ptr(hits), ptr(workspace), int(workspace.numel()), stream_ptr()]
     check(fn(*args), name)
     return (out, ids, hits, state_out) if kf is None else (out, ids, hits, state_out, cov_out)
+
+
+def track_smooth_workspace_bytes(N, n_seg, cells):
+    return _bytes('gpp_track_smooth_workspace_bytes', int(N), int(n_seg), int(cells))
+
+
+def track_smooth(rows, seg_start, seg_frame, cell_row, kf, ego=None, out=None, covariance=True, workspace=None):
+    """ gpp_track_smooth_f64 on the current stream: rows (N, D, 36) float32 on the device -- the RAW rows of a finished run --, the index of
+    utils/track_smooth.segments_of as HOST NumPy arrays (seg_start (n_seg + 1) int64, seg_frame (n_seg) int32, cell_row (cells) int32), kf
+    a TrackKfParams, ego None or the (N, 16) float64 host records -> (rows_out (N, D, 36) float32, row_cov (N, D, 3) float64 or None,
+    fill_rows (fills, 36) float32, fill_cov (fills, 3) float64 or None) on the device; one fill per -1 of cell_row, in its order.  out: where
+    the rows go (default: a new tensor; `rows` itself: in place); covariance False: neither covariance is asked for.  The entry point
+    waits for its copy of the index, not for its launches. """
+    import numpy as np
+    import torch
+    if rows.dim() != 3 or rows.dtype != torch.float32 or rows.shape[2] != GPP_POSE_COLS or not rows.is_contiguous():
+        raise ValueError('gpp_track_smooth_f64: rows must be a dense (N, D, {}) float32 tensor, got {} {}'.format(GPP_POSE_COLS, tuple(rows.shape), rows.dtype))
+    N, D = int(rows.shape[0]), int(rows.shape[1])
+    dev = rows.device
+    seg_start, seg_frame = np.ascontiguousarray(seg_start, np.int64), np.ascontiguousarray(seg_frame, np.int32)
+    cell_row = np.ascontiguousarray(cell_row, np.int32)
+    n_seg = int(seg_frame.shape[0])
+    if seg_start.shape != (n_seg + 1,) or cell_row.ndim != 1 or seg_frame.ndim != 1:
+        raise ValueError('gpp_track_smooth_f64: seg_start must be (n_seg + 1,), seg_frame (n_seg,), cell_row (cells,); got {} {} {}'.format(
+            seg_start.shape, seg_frame.shape, cell_row.shape))
+    cells = int(cell_row.shape[0])
+    if int(seg_start[-1]) != cells:
+        raise ValueError('gpp_track_smooth_f64: seg_start ends at {}, cell_row has {} cells'.format(int(seg_start[-1]), cells))
+    fills = int((cell_row < 0).sum())
+    if ego is not None:
+        ego = np.ascontiguousarray(ego, np.float64)
+        if ego.shape != (N, GPP_TRACK_EGO_FIELDS):
+            raise ValueError('gpp_track_smooth_f64: ego must be ({}, {}) float64 on the host, got {}'.format(N, GPP_TRACK_EGO_FIELDS, ego.shape))
+    out = torch.empty_like(rows) if out is None else out
+    _check_tensors('gpp_track_smooth_f64', dev, ((out, torch.float32, (N, D, GPP_POSE_COLS)),), contiguous=True)
+    row_cov = torch.empty((N, D, 3), dtype=torch.float64, device=dev) if covariance else None
+    fill_rows = torch.empty((fills, GPP_POSE_COLS), dtype=torch.float32, device=dev)
+    fill_cov = torch.empty((fills, 3), dtype=torch.float64, device=dev) if covariance else None
+    need = track_smooth_workspace_bytes(N, n_seg, cells)
+    workspace = torch.empty((max(need, 8),), dtype=torch.uint8, device=dev) if workspace is None else workspace
+    if workspace.dtype != torch.uint8 or workspace.device != dev:
+        raise ValueError('gpp_track_smooth_f64: the workspace must be uint8 on {}'.format(dev))
+    host = lambda a, t: a.ctypes.data_as(_P(t))  # noqa: E731
+    check(_entry('gpp_track_smooth_f64')(ptr(rows), N, D, host(seg_start, c_int64), host(seg_frame, ctypes.c_int32), host(cell_row, ctypes.c_int32),
+                                         n_seg, ctypes.byref(kf), None if ego is None else ego.ctypes.data_as(c_void_p), ptr(out),
+                                         ptr(row_cov), ptr(fill_rows) if fills else None, ptr(fill_cov) if fills else None,
+                                         ptr(workspace), int(workspace.numel()), stream_ptr()), 'gpp_track_smooth_f64')
+    return out, row_cov, fill_rows, fill_cov
 
 
 def mot_assign(overlaps, labels, label_counts, rows, ids, params):

@@ -40,6 +40,7 @@ import scipy.io
 from .. import models
 from ..utils import cuboid_nms, gpp_utils, visualization
 from ..utils import track as track_utils
+from ..utils import track_smooth
 from ..utils.image import compute_resize_scale, preprocess_image, read_image_bgr, resize_image
 
 
@@ -100,6 +101,7 @@ def parse_args(args):
     parser.add_argument('--track-min-hits', type=int, default=1, help='Only tracks seen in at least this many frames are written to tracks.txt.')
     parser.add_argument('--track-smooth', action='store_true',
                         help='Write the filtered cuboid (position, size, r_y, alpha) of tracked detections instead of the detector\'s.')
+    track_smooth.add_arguments(parser, '--track-rts', '--track-max-gap')
     parser.add_argument('--tracking-labels', default=None,
                         help='With --track: the sequence\'s KITTI label_02 file.  tracks.txt is scored against it on the GPU (CLEAR-MOT on the '
                              'optimal assignment of every frame, image overlap >= 0.5, csrc/mot_eval.hip) and the table of '
@@ -130,9 +132,12 @@ def parse_args(args):
         if parsed.save_images:
             parser.error('--track does not draw: the composites carry no identities; run --save-images without it')
         try:
+            parsed.rts_noise = track_smooth.smoother_arguments(parsed, parsed.track_smooth, parsed.track_max_age)
             track_utils.check_option(track_option(parsed))
         except ValueError as e:
             parser.error(str(e))
+    elif parsed.rts or parsed.max_gap is not None:
+        parser.error('--track-rts and --track-max-gap smooth the tracks of --track: they need --track')
     if (parsed.cuboid_nms is None) != (parsed.cuboid_nms_threshold is None):
         parser.error('--cuboid-nms and --cuboid-nms-threshold go together: both or neither')
     if parsed.cuboid_nms is not None and not 0.0 < parsed.cuboid_nms_threshold < 1.0:
@@ -151,8 +156,13 @@ def track_option(args):
         option['assign'] = 'optimal'
     if args.track_oxts is not None:
         option['ego'] = True
-    option.update(track_utils.filter_option(args))
+    option.update(track_smooth.filter_option(args))
     return option
+
+
+def smoother_option(args):
+    """ --track-rts: (the smoother's noise, the largest gap it fills), or None without it """
+    return (args.rts_noise, args.max_gap) if args.track is not None and args.rts else None
 
 
 def make_output_tree(args):
@@ -264,6 +274,7 @@ def main(args=None):
     if args.track is not None:
         files = sorted(files)                    # the sorted image list is one sequence
         tracks = open(os.path.join(output_dir, 'outputs', 'tracking', 'tracks.txt'), 'w')
+        finished = []                            # --track-rts: per frame (rows, ids, hits)
     j = 0
     for start in range(0, len(files), max(args.batch_size, 1)):
         on_device = hasattr(model, 'predict_on_frames')
@@ -283,7 +294,10 @@ def main(args=None):
                     else:
                         (rows, counts, ids, hits), _ = model.predict_tracks_on_frames(frames, P_inv, planes, ego=ego[j:j + len(group)])
                     for k in range(len(group)):
-                        tracks.write(track_utils.tracking_lines(j + k, rows[k], ids[k], hits[k], args.track_min_hits))
+                        if args.rts:                     # the smoother wants the finished run: the lines are written behind the last frame
+                            finished.append((np.array(rows[k], np.float32), np.array(ids[k], np.int32), np.array(hits[k], np.int32)))
+                        else:
+                            tracks.write(track_utils.tracking_lines(j + k, rows[k], ids[k], hits[k], args.track_min_hits))
                 elif args.save_images:
                     P_raw = np.stack([raw_calibration(it) for it in group])
                     (rows, counts), _, pictures = model.predict_composites_on_frames(frames, P_inv, planes, P_raw, args.image_score_threshold)
@@ -311,6 +325,8 @@ def main(args=None):
                 write_results(args, output_dir, it, det)
 
     if args.track is not None:
+        if args.rts and finished:
+            write_smoothed_tracks(tracks, finished, smoother_option(args), ego, args.track_min_hits)
         tracks.close()
     if args.tracking_labels is not None:
         from ..utils import mot_eval
@@ -318,6 +334,21 @@ def main(args=None):
                                                                 device=True, hota=args.hota, idf1=args.idf1)))
     if args.range_audit:
         write_range_audit(output_dir, model, audit)
+
+
+def write_smoothed_tracks(tracks, finished, option, ego, min_hits):
+    """ --track-rts: the finished run's per-frame (rows, ids, hits) through the offline smoother on the device,
+    then the lines of tracks.txt, the fills among them """
+    noise, max_gap = option
+    D = max(len(r) for r, _, _ in finished)
+    rows = np.full((len(finished), D, track_utils.POSE_COLS), -1.0, np.float32)
+    ids, hits = np.full((len(finished), D), -1, np.int32), np.zeros((len(finished), D), np.int32)
+    for f, (r, i, h) in enumerate(finished):
+        rows[f, :len(r)], ids[f, :len(r)], hits[f, :len(r)] = r, i, h
+    rows, ids, hits, fills = track_smooth.smooth_tracks(rows, ids, hits, noise, max_gap, ego=ego)
+    for f in range(len(finished)):
+        tracks.write(track_utils.tracking_lines(f, rows[f], ids[f], hits[f], min_hits))
+    print('tracks smoothed offline: {} fills'.format(fills))
 
 
 def keep_smallest(audit, model):

@@ -14,10 +14,15 @@ sequence's oxts/<seq>.txt and calib/<seq>.txt, one oxts line per result file) mo
 coordinates before they are matched (gpp_track_ego_f64): a parked car keeps its id from a driving camera.
 --track-filter kalman with --track-noise, --track-process and --track-birth-speed gives every track the covariance of its ground-plane
 position and velocity (gpp_track_kf_f64), and --metric maha gates at --threshold standard deviations.
+--rts smooths the finished tracks before they are written (gpp_track_smooth_f64): a backward Rauch-Tung-Striebel
+pass over the same filter gives every tracked detection its smoothed x, z and alpha, and every frame the detector missed inside a track --
+up to --max-gap frames in a row, by default the run's --max-age -- a row of its own.  It needs the three noise arguments and works under
+any --metric and either filter; it wants the raw rows, so it does not go with --smooth.
 
     track_results.py result_dir/ tracks.txt --metric dist --threshold 2.0 [--max-age 2] [--min-hits 1] [--smooth] [--host]
                      [--track-assign greedy|optimal] [--oxts oxts/0000.txt --calib calib/0000.txt]
                      [--track-filter kalman --track-noise R0 R1 T0 T1 --track-process QP QV --track-birth-speed V0 [--metric maha]]
+                     [--rts [--max-gap G] --track-noise R0 R1 T0 T1 --track-process QP QV --track-birth-speed V0]
                      [--labels label_02/0000.txt [--score-metric image] [--score-min-overlap 0.5] [--hota] [--idf1]]
 
 --labels scores the tracks just written against the sequence's label_02 file (CLEAR-MOT; on the GPU unless
@@ -42,6 +47,7 @@ from ..utils import kitti_eval
 from ..utils import mot_eval
 from ..utils import oxts
 from ..utils import track as track_utils
+from ..utils import track_smooth
 
 
 def parse_args(args):
@@ -66,15 +72,17 @@ def parse_args(args):
                                                      '(section 4.33).  Needs --calib.')
     parser.add_argument('--calib', default=None, help='With --oxts: the sequence\'s tracking calibration file (R_rect, Tr_velo_cam, Tr_imu_velo).')
     parser.add_argument('--host', action='store_true', help='The NumPy form instead of the GPU.')
+    track_smooth.add_arguments(parser)
     parser.add_argument('--labels', help='The sequence\'s label_02 file: score the tracks just written and print the CLEAR-MOT table.')
     evaluate_tracking.add_scoring_arguments(parser, 'score-')
     parsed = parser.parse_args(args)
     if (parsed.oxts is None) != (parsed.calib is None):
         parser.error('--oxts and --calib go together: both or neither')
     try:
+        parsed.rts_noise = track_smooth.smoother_arguments(parsed, parsed.smooth, parsed.max_age)
         parsed.option = track_utils.check_option(dict({'metric': parsed.metric, 'threshold': parsed.threshold, 'max_age': parsed.max_age,
                                                        'birth_score': parsed.birth_score, 'smooth': parsed.smooth,
-                                                       'assign': parsed.track_assign}, **track_utils.filter_option(parsed)))
+                                                       'assign': parsed.track_assign}, **track_smooth.filter_option(parsed)))
         mot_eval.check_params(parsed.mot_metric, parsed.mot_min_overlap)
     except ValueError as e:
         parser.error(str(e))
@@ -101,10 +109,15 @@ def main(args=None):
         rows, ids, hits, state = run(frames, args.option)[:4]
     else:
         rows, ids, hits, state = run(frames, args.option, ego=oxts.records_for(args.oxts, args.calib, len(names)))[:4]
+    fills = ''
+    if args.rts:
+        ego = None if args.oxts is None else oxts.records_for(args.oxts, args.calib, len(names))
+        rows, ids, hits, n = track_smooth.smooth_tracks(frames, ids, hits, args.rts_noise, args.max_gap, ego=ego, host=args.host)
+        fills = ', smoothed with {} fills'.format(n)
     with open(args.tracks_path, 'w') as f:
         for k in range(len(names)):
             f.write(track_utils.tracking_lines(k, rows[k], ids[k], hits[k], args.min_hits))
-    print('{} frames, {} tracks, {} births dropped -> {}'.format(len(names), int(state['next_id']), int(state['dropped']), args.tracks_path))
+    print('{} frames, {} tracks, {} births dropped{} -> {}'.format(len(names), int(state['next_id']), int(state['dropped']), fills, args.tracks_path))
     if args.labels:
         result = mot_eval.evaluate_tracking(args.labels, args.tracks_path, metric=args.mot_metric, min_overlap=args.mot_min_overlap,
                                             device=not args.host, hota=args.hota, idf1=args.idf1)

@@ -969,6 +969,58 @@ int gpp_track_kf_f64(const float* rows_in, int N, int D, const int32_t* seq_star
                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * SMOOTHING finished tracks offline: a backward Rauch-Tung-Striebel pass over the forward filter above, and the filling of short gaps
+ * (csrc/track_smooth.hip; DESIGN.md section 4.35 is the specification -- every expression is written out there, fully parenthesised --,
+ * utils/track_smooth.py the host form and the maker of the index).  The tracker writes filtered positions: the cuboid at frame k knows
+ * nothing of the frames behind it.  A finished run is in hand as a whole; this stage runs the filter of gpp_track_kf_f64 forward over
+ * every SEGMENT of an identity -- (x, z, vx, vz), the same row noise, predict, ego step, update and birth -- and then backward, and
+ * gives every detected row of the segment its smoothed x, z and alpha, every frame the detector missed inside the segment a FILL row,
+ * and both the position block of the smoothed covariance.  Two launches, plain float64, every operation separate.
+ *
+ *   rows_in, rows_out (N, D, GPP_POSE_COLS) float32, device: the RAW rows of a finished run (not `smooth`ed ones).  rows_out == rows_in is
+ *               allowed; otherwise the two do not overlap and rows_in is copied first.  D <= GPP_KITTI_MAX_DETECTIONS.
+ *   the index   HOST arrays, like seq_start and the ego records; checked here before any launch and copied behind the workspace.
+ *     seg_start (n_seg + 1) int64: segment s owns the cells [seg_start[s], seg_start[s + 1]); seg_start[0] == 0, ascending, every segment
+ *               has at least one cell, seg_start[n_seg] == cells.
+ *     seg_frame (n_seg) int32: the frame of the segment's first cell; cell c of the segment is frame seg_frame[s] + c, which is < N.
+ *     cell_row  (cells) int32: the flat row index frame * D + d of the cell's detection, which lies in the cell's own frame, or -1 for a
+ *               GAP: the track was alive and no row carried its id.  A segment's first and last cell are detections; no row has two cells.
+ *               The order of the segments is free and no output depends on it (the entry point orders them by length for its lanes).
+ *   kf          the noise of gpp_track_kf_f64.
+ *   ego         (N, GPP_TRACK_EGO_FIELDS) float64 on the host, or null: as gpp_track_kf_f64 takes it; record f carries frame f - 1 to f.
+ *   the rule    per segment, cell 0 is a birth from its row: mean (x, z, 0, 0), A = R of the row, B = 0, C = birth_speed^2 I.  Every later
+ *               cell: predict; with records the ego step (the covariance as above; the mean by the ground part only, x' = (g00 x + g01 z)
+ *               + t0, z' = (g10 x + g11 z) + t2, v through Rg -- what pitch and roll mix in from y is left out); at a detection the
+ *               update, or, when det is not > 0, a restart as at a birth from the row.  Backward from the last cell, whose smoothed state
+ *               is its filtered one: J = P_f(c) Phi^T P_p(c + 1)^-1 with Phi = blockdiag(Rg, Rg) F, the inverse by 2 x 2 blocks (A^-1, the
+ *               Schur complement C - B^T A^-1 B and its inverse); J = 0 when either determinant is not > 0 or the step is a restart;
+ *               x_s(c) = x_f(c) + J (x_s(c + 1) - x_p(c + 1)), P_s(c) = P_f(c) + J (P_s(c + 1) - P_p(c + 1)) J^T.
+ *   rows_out    a detected row of a segment of two or more cells: columns 19 and 21 = x_s, z_s rounded to float32 once, column 25 =
+ *               wrap(r_y - atan2(x_s, z_s)) with the row's own r_y.  Every other column and every other row is a bit copy.
+ *   row_cov     (N, D, 3) float64, device, may be null: Axx Axz Azz of P_s for those rows, zeros everywhere else.
+ *   fill_rows   (fills, GPP_POSE_COLS) float32, device, fills = the number of gaps: one row per gap in cell order.  With a and b the
+ *               detected neighbours before and behind, at cells c0 < c < c1 of the segment, and w = (c - c0) / (c1 - c0): columns 19 21 25
+ *               as above, with the fill's own r_y; column 32 (r_y) = wrap(a + w d), d = wrap(b - a) brought into [-pi/2, pi/2) by a half
+ *               turn; the columns 13 14 33 34 35 hold codes and padding and come from a; every other column is a + w (b - a) in float64,
+ *               rounded once -- y among them, which is NOT ego-compensated.  May be null when there is no gap.
+ *   fill_cov    (fills, 3) float64, device, may be null: Axx Axz Azz of P_s per fill.
+ *   workspace   gpp_track_smooth_workspace_bytes(N, n_seg, cells) bytes on the device, 8-byte aligned: 28 float64 per cell in blocks of
+ *               64 segments, five per cell for the smoothed table, and the copies of the index and the records.
+ *
+ *   GPP_ERR_BAD_ARG, nothing launched and nothing written: a negative N, D, n_seg or cells; D > GPP_KITTI_MAX_DETECTIONS; N * D beyond
+ *   2^31 - 1; a null kf, seg_start, or seg_frame / cell_row / workspace / fill_rows where they are needed, or rows when N * D > 0; the noise
+ *   refusals of gpp_track_kf_f64; offsets that do not ascend as stated; a frame or a row index out of range, a row outside its cell's
+ *   frame or in two cells; a segment whose first or last cell is a gap; cells > 0 with N * D == 0; a non-finite word among the first 13 of
+ *   any record, or a padding word that is not 0.  GPP_ERR_ALIGN: rows, row_cov, fill_rows, fill_cov not 4 / 8-byte aligned, the workspace
+ *   not 8-byte aligned.  GPP_ERR_WORKSPACE.  cells == 0 or N * D == 0: rows_in is copied to rows_out, row_cov is zeroed, nothing is launched.
+ * ---------------------------------------------------------------------------------------- */
+int gpp_track_smooth_workspace_bytes(int N, int n_seg, long long cells, size_t* bytes);
+int gpp_track_smooth_f64(const float* rows_in, int N, int D, const int64_t* seg_start, const int32_t* seg_frame, const int32_t* cell_row,
+                         int n_seg, const gpp_track_kf_params* kf, const double* ego /* may be null */, float* rows_out,
+                         double* row_cov /* may be null */, float* fill_rows, double* fill_cov /* may be null */, void* workspace,
+                         size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * CLEAR-MOT scoring of tracks on the device (csrc/mot_eval.hip; DESIGN.md section 4.29 is the specification, a restatement of the KITTI
  * tracking devkit's CLEAR-MOT -- parity with the devkit itself is UNPINNED; utils/mot_eval.py is the host form): per frame the OPTIMAL
  * one-to-one assignment of the tracker's rows to the labels (the Hungarian method, shortest augmenting paths, exact integers), then per
