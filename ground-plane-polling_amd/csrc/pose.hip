@@ -24,13 +24,15 @@
 #include <math.h>
 
 #include "gpp.h"
+#include "track_kf.h"
 
 namespace {
 
+using gpp_kf::kPi;
+using gpp_kf::wrap;                                  // run_network.py:312-316: a % 2 pi, then into [-pi, pi); the trackers wrap alike
+
 constexpr int kThreads = 128;
 constexpr int kPolarSteps = 12;
-constexpr double kPi = 3.141592653589793238462643383279502884;
-constexpr double kTwoPi = 2.0 * kPi;
 
 struct M3 { double a00, a01, a02, a10, a11, a12, a20, a21, a22; };
 
@@ -72,16 +74,6 @@ __host__ __device__ inline M3 polar(M3 x)
         x.a20 = p * x.a20 + q * c.a20; x.a21 = p * x.a21 + q * c.a21; x.a22 = p * x.a22 + q * c.a22;
     }
     return x;
-}
-
-// run_network.py:312-316: a % 2 pi (Python: the sign of the divisor), then into [-pi, pi)
-__host__ __device__ inline double wrap(double a)
-{
-    a = a - kTwoPi * floor(a / kTwoPi);
-    if (a < 0.0) a += kTwoPi;
-    if (a >= kTwoPi) a -= kTwoPi;
-    if (a >= kPi) a -= kTwoPi;
-    return a;
 }
 
 // one detection above the threshold -> its row (include/gpp.h).  bx: its 12 box values, kp: its 4 x 3 keypoints, width: its dimension w

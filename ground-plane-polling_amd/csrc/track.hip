@@ -56,7 +56,9 @@
 //                  written by the row's thread, the covariance lives with the slot's: the row leaves its number in s_mrow[slot] (idle
 //                  behind phase 5) and the slot's thread takes R from there behind the barrier the births end with.  No barrier more
 //                  than before, and none inside a divergent branch; no loop more.  kEgo here means "records were given".  The
-//                  <*, *, false> instantiations have none of it (if constexpr).
+//                  <*, *, false> instantiations have none of it (if constexpr).  The filter's expressions -- row noise, birth covariance,
+//                  predict, the ground rotation, the update -- are csrc/track_kf.h's, shared with csrc/track_smooth.hip; here stay the
+//                  Mahalanobis key of phase 3 and the 3-D mean of step 1b.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -65,8 +67,11 @@
 #include "gpp.h"
 #include "mot_assign.h"
 #include "rot_iou.h"
+#include "track_kf.h"
 
 namespace {
+
+using namespace gpp_kf;                               // kPi, wrap, AXX .. CZZ, kCov and section 4.34's steps
 
 constexpr int kMaxD = GPP_KITTI_MAX_DETECTIONS;
 constexpr int kSlots = GPP_TRACK_MAX_TRACKS;
@@ -74,8 +79,6 @@ constexpr int kRow = GPP_POSE_COLS;
 constexpr int kThreads = 128;
 constexpr double kGateSlack = 1.0634765625;          // (1 + 1/32)^2, the gate of cuboid_nms.hip
 constexpr int kChunk = 4096;                         // pairs gated per round
-constexpr double kPi = 3.141592653589793238462643383279502884;
-constexpr double kTwoPi = 2.0 * kPi;
 constexpr size_t kSeqBytes = 256;                    // the workspace starts with seq_start's copy, padded to a multiple of this
 constexpr int32_t kScale = 1 << GPP_MOT_SCALE_BITS;  // section 4.32: the cell of a pair that is no candidate, and of padding
 constexpr int kSide = kSlots > kMaxD ? kSlots : kMaxD;                 // the largest matrix of section 4.32
@@ -87,8 +90,6 @@ static_assert(sizeof(gpp_track_state) % 8 == 0, "states are laid out back to bac
 static_assert(kSide <= 2 * gpp_mot::kWave, "assign_rows: a lane owns two columns");
 
 enum { FX = 0, FY, FZ, FRY, FH, FW, FL, FVX, FVY, FVZ };
-enum { AXX = 0, AXZ, AZZ, BXX, BXZ, BZX, BZZ, CXX, CXZ, CZZ };       // gpp_track_cov's fields
-constexpr int kCov = GPP_TRACK_COV_FIELDS;
 static_assert(sizeof(gpp_track_cov) == (size_t)kCov * kSlots * sizeof(double), "field-major, back to back");
 
 // section 4.34, what the Kalman instantiations take beyond the others
@@ -97,36 +98,6 @@ struct kf_args {
     gpp_track_cov* cov_out;
     gpp_track_kf_params p;
 };
-
-// section 4.34, "ego": X -> Rg X Rg^T for a general 2 x 2 block (xx xz zx zz), every product and sum separate
-__device__ __forceinline__ void turn(double g00, double g01, double g10, double g11, double xx, double xz, double zx, double zz,
-                                     double& oxx, double& oxz, double& ozx, double& ozz)
-{
-    const double mxx = (g00 * xx) + (g01 * zx), mxz = (g00 * xz) + (g01 * zz);
-    const double mzx = (g10 * xx) + (g11 * zx), mzz = (g10 * xz) + (g11 * zz);
-    oxx = (mxx * g00) + (mxz * g01);
-    oxz = (mxx * g10) + (mxz * g11);
-    ozx = (mzx * g00) + (mzz * g01);
-    ozz = (mzx * g10) + (mzz * g11);
-}
-
-// section 4.34, "births": A = R of the row, B = 0, C = birth_speed^2 I
-__device__ __forceinline__ void born_cov(double (&P)[kCov], double rxx, double rxz, double rzz, double speed)
-{
-    P[AXX] = rxx; P[AXZ] = rxz; P[AZZ] = rzz;
-    P[BXX] = 0.0; P[BXZ] = 0.0; P[BZX] = 0.0; P[BZZ] = 0.0;
-    P[CXX] = speed * speed; P[CXZ] = 0.0; P[CZZ] = speed * speed;
-}
-
-// pose.hip's wrap: into [-pi, pi)
-__device__ __forceinline__ double wrap(double a)
-{
-    a = a - kTwoPi * floor(a / kTwoPi);
-    if (a < 0.0) a += kTwoPi;
-    if (a >= kTwoPi) a -= kTwoPi;
-    if (a >= kPi) a -= kTwoPi;
-    return a;
-}
 
 // the number of threads below `tid` whose flag is set, and the number of all; two barriers, reached by everyone
 __device__ __forceinline__ int block_rank(bool flag, int tid, int* s_wave, int& total)
@@ -235,15 +206,9 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
                     }
                     if constexpr (kKf) {
                         if (!(flag & 2)) {               // the row's noise: along and across its viewing ray
-                            const double rho = sqrt((x * x) + (z * z));
-                            double ux = 0.0, uz = 1.0;
-                            if (rho != 0.0) { ux = x / rho; uz = z / rho; }
-                            const double sr = kfa.p.radial0 + (kfa.p.radial1 * rho), sg = kfa.p.tangential0 + (kfa.p.tangential1 * rho);
-                            const double vr = sr * sr, vt = sg * sg;
-                            const double dv = vr - vt;
-                            s_R[0][tid] = vt + (dv * (ux * ux));
-                            s_R[1][tid] = dv * (ux * uz);
-                            s_R[2][tid] = vt + (dv * (uz * uz));
+                            double rxx, rxz, rzz;
+                            row_noise(x, z, kfa.p, rxx, rxz, rzz);
+                            s_R[0][tid] = rxx; s_R[1][tid] = rxz; s_R[2][tid] = rzz;
                         }
                     }
                 }
@@ -274,19 +239,8 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
                 }
                 st.box[FX][tid] = x; st.box[FY][tid] = y; st.box[FZ][tid] = z;
                 if constexpr (kKf) {                     // 1: P = F P F^T + Q, all from the old values
-                    const double axx = ((P[AXX] + (P[BXX] + P[BXX])) + P[CXX]) + kfa.p.q_pos;
-                    const double axz = (P[AXZ] + (P[BXZ] + P[BZX])) + P[CXZ];
-                    const double azz = ((P[AZZ] + (P[BZZ] + P[BZZ])) + P[CZZ]) + kfa.p.q_pos;
-                    const double bxx = P[BXX] + P[CXX], bxz = P[BXZ] + P[CXZ], bzx = P[BZX] + P[CXZ], bzz = P[BZZ] + P[CZZ];
-                    P[AXX] = axx; P[AXZ] = axz; P[AZZ] = azz;
-                    P[BXX] = bxx; P[BXZ] = bxz; P[BZX] = bzx; P[BZZ] = bzz;
-                    P[CXX] = P[CXX] + kfa.p.q_vel; P[CZZ] = P[CZZ] + kfa.p.q_vel;
-                    if constexpr (kEgo) {                // 1b: the ground part of the record's rotation on every block
-                        double unused;                   // (the lower triangle of a symmetric block is not kept)
-                        turn(e[0], e[2], e[6], e[8], P[AXX], P[AXZ], P[AXZ], P[AZZ], P[AXX], P[AXZ], unused, P[AZZ]);
-                        turn(e[0], e[2], e[6], e[8], P[BXX], P[BXZ], P[BZX], P[BZZ], P[BXX], P[BXZ], P[BZX], P[BZZ]);
-                        turn(e[0], e[2], e[6], e[8], P[CXX], P[CXZ], P[CXZ], P[CZZ], P[CXX], P[CXZ], unused, P[CZZ]);
-                    }
+                    predict_cov(P, kfa.p.q_pos, kfa.p.q_vel);
+                    if constexpr (kEgo) turn_cov(P, e[0], e[2], e[6], e[8]);     // 1b: the ground part of the record's rotation
                     s_A[0][tid] = P[AXX]; s_A[1][tid] = P[AXZ]; s_A[2][tid] = P[AZZ];
                 }
                 if (iou) {
@@ -490,36 +444,12 @@ __global__ __launch_bounds__(kThreads) void track_kernel(const float* rows_in, i
                 bool kalman = false;
                 if constexpr (kKf) {
                     const double rxx = s_R[0][d], rxz = s_R[1][d], rzz = s_R[2][d];
-                    const double sxx = P[AXX] + rxx, sxz = P[AXZ] + rxz, szz = P[AZZ] + rzz;
-                    const double det = (sxx * szz) - (sxz * sxz);
-                    kalman = det > 0.0;
+                    double x = st.box[FX][tid], z = st.box[FZ][tid], vx = st.box[FVX][tid], vz = st.box[FVZ][tid];
+                    kalman = update(P, rxx, rxz, rzz, r_f[FX][d] - x, r_f[FZ][d] - z, x, z, vx, vz);
                     if (kalman) {
-                        const double px = st.box[FX][tid], pz = st.box[FZ][tid];
-                        const double dx = r_f[FX][d] - px, dz = r_f[FZ][d] - pz;
-                        const double ixx = szz / det, ixz = -(sxz / det), izz = sxx / det;
-                        const double kxx = (P[AXX] * ixx) + (P[AXZ] * ixz), kxz = (P[AXX] * ixz) + (P[AXZ] * izz);
-                        const double kzx = (P[AXZ] * ixx) + (P[AZZ] * ixz), kzz = (P[AXZ] * ixz) + (P[AZZ] * izz);
-                        const double lxx = (P[BXX] * ixx) + (P[BZX] * ixz), lxz = (P[BXX] * ixz) + (P[BZX] * izz);
-                        const double lzx = (P[BXZ] * ixx) + (P[BZZ] * ixz), lzz = (P[BXZ] * ixz) + (P[BZZ] * izz);
-                        st.box[FX][tid] = px + ((kxx * dx) + (kxz * dz));
-                        st.box[FZ][tid] = pz + ((kzx * dx) + (kzz * dz));
-                        st.box[FVX][tid] = st.box[FVX][tid] + ((lxx * dx) + (lxz * dz));
-                        st.box[FVZ][tid] = st.box[FVZ][tid] + ((lzx * dx) + (lzz * dz));
-                        const double axx = P[AXX] - ((kxx * P[AXX]) + (kxz * P[AXZ]));
-                        const double axz = P[AXZ] - ((kxx * P[AXZ]) + (kxz * P[AZZ]));
-                        const double azz = P[AZZ] - ((kzx * P[AXZ]) + (kzz * P[AZZ]));
-                        const double bxx = P[BXX] - ((kxx * P[BXX]) + (kxz * P[BZX]));
-                        const double bxz = P[BXZ] - ((kxx * P[BXZ]) + (kxz * P[BZZ]));
-                        const double bzx = P[BZX] - ((kzx * P[BXX]) + (kzz * P[BZX]));
-                        const double bzz = P[BZZ] - ((kzx * P[BXZ]) + (kzz * P[BZZ]));
-                        const double cxx = P[CXX] - ((lxx * P[BXX]) + (lxz * P[BZX]));
-                        const double cxz = P[CXZ] - ((lxx * P[BXZ]) + (lxz * P[BZZ]));
-                        const double czz = P[CZZ] - ((lzx * P[BXZ]) + (lzz * P[BZZ]));
-                        P[AXX] = axx; P[AXZ] = axz; P[AZZ] = azz;
-                        P[BXX] = bxx; P[BXZ] = bxz; P[BZX] = bzx; P[BZZ] = bzz;
-                        P[CXX] = cxx; P[CXZ] = cxz; P[CZZ] = czz;
+                        st.box[FX][tid] = x; st.box[FZ][tid] = z; st.box[FVX][tid] = vx; st.box[FVZ][tid] = vz;
                     } else {
-                        born_cov(P, rxx, rxz, rzz, kfa.p.birth_speed);
+                        born_cov(P, rxx, rxz, rzz, kfa.p.birth_speed);     // the fixed gains below, P as at birth
                     }
                 }
 #pragma unroll
@@ -662,9 +592,6 @@ struct kf_host {
     const gpp_track_kf_params* kf;
 };
 
-static bool positive(double v) { return v > 0.0 && __builtin_isfinite(v); }             // (false for NaN)
-static bool not_negative(double v) { return v >= 0.0 && __builtin_isfinite(v); }
-
 static int track(bool optimal, bool with_ego, const kf_host* kalman, const double* ego, const float* rows_in, int N, int D,
                  const int32_t* seq_start, int S,
                  const void* state_in, void* state_out, const gpp_track_params* params, float* rows_out, int32_t* track_ids,
@@ -679,13 +606,7 @@ static int track(bool optimal, bool with_ego, const kf_host* kalman, const doubl
         return GPP_ERR_BAD_ARG;
     if (!unit(p.gain_a, true) || !unit(p.gain_b, false) || !unit(p.gain_c, false)) return GPP_ERR_BAD_ARG;
     if (p.max_age < 0 || (p.smooth != 0 && p.smooth != 1) || p.reserved != 0 || __builtin_isnan(p.birth_score)) return GPP_ERR_BAD_ARG;
-    if (kalman) {
-        if (!kalman->kf) return GPP_ERR_BAD_ARG;
-        const gpp_track_kf_params& k = *kalman->kf;
-        if (!positive(k.radial0) || !positive(k.tangential0) || !positive(k.birth_speed)) return GPP_ERR_BAD_ARG;
-        if (!not_negative(k.radial1) || !not_negative(k.tangential1) || !not_negative(k.q_pos) || !not_negative(k.q_vel)) return GPP_ERR_BAD_ARG;
-        if (k.reserved != 0) return GPP_ERR_BAD_ARG;
-    }
+    if (kalman && (!kalman->kf || gpp_kf::kf_params_bad(*kalman->kf))) return GPP_ERR_BAD_ARG;
     for (int s = 0; s <= S; ++s) {
         const int32_t lo = s == 0 ? 0 : seq_start[s - 1];
         if (seq_start[s] < lo || seq_start[s] > N) return GPP_ERR_BAD_ARG;
@@ -693,13 +614,8 @@ static int track(bool optimal, bool with_ego, const kf_host* kalman, const doubl
     const int f_lo = seq_start[0], f_hi = seq_start[S];              // the frames inside a sequence: seq_start is monotone
     if (with_ego) {
         if (N > 0 && !ego) return GPP_ERR_BAD_ARG;
-        for (int f = f_lo; f < f_hi; ++f) {
-            const double* e = ego + (size_t)f * kEgoFields;
-            for (int k = 0; k < 13; ++k)
-                if (!__builtin_isfinite(e[k])) return GPP_ERR_BAD_ARG;
-            for (int k = 13; k < kEgoFields; ++k)
-                if (!(e[k] == 0.0)) return GPP_ERR_BAD_ARG;          // (a NaN is not zero either)
-        }
+        for (int f = f_lo; f < f_hi; ++f)
+            if (gpp_kf::ego_record_bad(ego + (size_t)f * kEgoFields)) return GPP_ERR_BAD_ARG;
     }
     if (D > kMaxD) return GPP_ERR_UNSUPPORTED;
     if (S > 0 && (!state_in || !state_out)) return GPP_ERR_BAD_ARG;

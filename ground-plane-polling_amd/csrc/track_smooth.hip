@@ -2,8 +2,8 @@
 // forward over every segment of an identity, a Rauch-Tung-Striebel pass run backward over what it kept, and a fill row for every frame
 // the detector missed inside a segment.  The specification is DESIGN.md's text: every expression there is one statement here, every
 // + - * / and sqrt one separately rounded float64 operation (-ffp-contract=off), so that utils/track_smooth.py (NumPy) and
-// tests/track_smooth_oracle.py (loops) return the same words.  csrc/track.hip is not touched: the predict, ego and update expressions
-// of section 4.34 are restated below.
+// tests/track_smooth_oracle.py (loops) return the same words.  The row noise, birth covariance, predict, ground rotation and update of
+// section 4.34 are csrc/track_kf.h's, the functions csrc/track.hip calls; the ground-only mean steps and the backward step are here.
 //
 // Two launches.
 //   track_smooth_pass   one LANE per segment of two or more cells.  Forward: per cell the predicted and the filtered (x z vx vz, ten
@@ -28,8 +28,11 @@
 #include <vector>
 
 #include "gpp.h"
+#include "track_kf.h"
 
 namespace {
+
+using namespace gpp_kf;                               // kPi, wrap, AXX .. CZZ, kCov and section 4.34's steps
 
 constexpr int kRow = GPP_POSE_COLS;
 constexpr int kMaxD = GPP_KITTI_MAX_DETECTIONS;
@@ -38,11 +41,6 @@ constexpr int kLanes = 64;                           // segments per block of th
 constexpr int kWords = 28;                           // per cell: predicted (4 + 10), filtered (4 + 10)
 constexpr int kTable = 5;                            // per cell: x_s z_s Axx Axz Azz, laid out [word][cell]
 constexpr int kEmitThreads = 256;
-constexpr double kPi = 3.141592653589793238462643383279502884;
-constexpr double kTwoPi = 2.0 * kPi;
-
-enum { AXX = 0, AXZ, AZZ, BXX, BXZ, BZX, BZZ, CXX, CXZ, CZZ, kCov };      // gpp_track_cov's fields
-static_assert(kCov == GPP_TRACK_COV_FIELDS, "the ten words of section 4.34");
 static_assert(kWords == 2 * (4 + kCov), "predicted and filtered");
 
 struct state { double x, z, vx, vz, P[kCov]; };
@@ -58,50 +56,19 @@ __device__ __forceinline__ m2 sub(const m2 X, const m2 Y) { return {X.xx - Y.xx,
 __device__ __forceinline__ m2 neg(const m2 X) { return {-X.xx, -X.xz, -X.zx, -X.zz}; }
 __device__ __forceinline__ m2 sym(double xx, double xz, double zz) { return {xx, xz, xz, zz}; }
 
-// pose.hip's wrap: into [-pi, pi)
-__device__ __forceinline__ double wrap(double a)
-{
-    a = a - kTwoPi * floor(a / kTwoPi);
-    if (a < 0.0) a += kTwoPi;
-    if (a >= kTwoPi) a -= kTwoPi;
-    if (a >= kPi) a -= kTwoPi;
-    return a;
-}
-
-// section 4.34, "row noise"
-__device__ __forceinline__ void row_noise(double x, double z, const gpp_track_kf_params& kf, double& rxx, double& rxz, double& rzz)
-{
-    const double rho = sqrt((x * x) + (z * z));
-    double ux = 0.0, uz = 1.0;
-    if (rho != 0.0) { ux = x / rho; uz = z / rho; }
-    const double sr = kf.radial0 + (kf.radial1 * rho), st = kf.tangential0 + (kf.tangential1 * rho);
-    const double vr = sr * sr, vt = st * st, dv = vr - vt;
-    rxx = vt + (dv * (ux * ux));
-    rxz = dv * (ux * uz);
-    rzz = vt + (dv * (uz * uz));
-}
-
-// section 4.34, "births": mean (x, z, 0, 0), A = R of the row, B = 0, C = birth_speed^2 I
+// section 4.34, "births": mean (x, z, 0, 0) and born_cov
 __device__ __forceinline__ void born(state& s, double x, double z, double rxx, double rxz, double rzz, double speed)
 {
     s.x = x; s.z = z; s.vx = 0.0; s.vz = 0.0;
-    s.P[AXX] = rxx; s.P[AXZ] = rxz; s.P[AZZ] = rzz;
-    s.P[BXX] = 0.0; s.P[BXZ] = 0.0; s.P[BZX] = 0.0; s.P[BZZ] = 0.0;
-    s.P[CXX] = speed * speed; s.P[CXZ] = 0.0; s.P[CZZ] = speed * speed;
+    born_cov(s.P, rxx, rxz, rzz, speed);
 }
 
 // section 4.34, "1 predict": x += vx, z += vz; P' = F P F^T + Q
 __device__ __forceinline__ void predict(state& s, double q_pos, double q_vel)
 {
-    const double* P = s.P;
     s.x = s.x + s.vx;
     s.z = s.z + s.vz;
-    const double axx = ((P[AXX] + (P[BXX] + P[BXX])) + P[CXX]) + q_pos, axz = (P[AXZ] + (P[BXZ] + P[BZX])) + P[CXZ];
-    const double azz = ((P[AZZ] + (P[BZZ] + P[BZZ])) + P[CZZ]) + q_pos;
-    const double bxx = P[BXX] + P[CXX], bxz = P[BXZ] + P[CXZ], bzx = P[BZX] + P[CXZ], bzz = P[BZZ] + P[CZZ];
-    s.P[AXX] = axx; s.P[AXZ] = axz; s.P[AZZ] = azz;
-    s.P[BXX] = bxx; s.P[BXZ] = bxz; s.P[BZX] = bzx; s.P[BZZ] = bzz;
-    s.P[CXX] = P[CXX] + q_vel; s.P[CZZ] = P[CZZ] + q_vel;
+    predict_cov(s.P, q_pos, q_vel);
 }
 
 // section 4.35, the ego step: the mean by the ground part of the record only, the covariance as section 4.34's 1b
@@ -110,40 +77,7 @@ __device__ __forceinline__ void ego_step(state& s, const m2 g, double t0, double
     const double x = ((g.xx * s.x) + (g.xz * s.z)) + t0, z = ((g.zx * s.x) + (g.zz * s.z)) + t2;
     const double vx = (g.xx * s.vx) + (g.xz * s.vz), vz = (g.zx * s.vx) + (g.zz * s.vz);
     s.x = x; s.z = z; s.vx = vx; s.vz = vz;
-    const m2 gt = tr(g);
-    const m2 a = mul(mul(g, sym(s.P[AXX], s.P[AXZ], s.P[AZZ])), gt);
-    const m2 b = mul(mul(g, m2{s.P[BXX], s.P[BXZ], s.P[BZX], s.P[BZZ]}), gt);
-    const m2 c = mul(mul(g, sym(s.P[CXX], s.P[CXZ], s.P[CZZ])), gt);
-    s.P[AXX] = a.xx; s.P[AXZ] = a.xz; s.P[AZZ] = a.zz;
-    s.P[BXX] = b.xx; s.P[BXZ] = b.xz; s.P[BZX] = b.zx; s.P[BZZ] = b.zz;
-    s.P[CXX] = c.xx; s.P[CXZ] = c.xz; s.P[CZZ] = c.zz;
-}
-
-// section 4.34, "5 update" with the row (xr, zr) and its R; false (nothing changed) when det is not > 0: the caller restarts
-__device__ __forceinline__ bool update(state& s, double xr, double zr, double rxx, double rxz, double rzz)
-{
-    const double* P = s.P;
-    const double sxx = P[AXX] + rxx, sxz = P[AXZ] + rxz, szz = P[AZZ] + rzz;
-    const double det = (sxx * szz) - (sxz * sxz);
-    if (!(det > 0.0)) return false;
-    const double dx = xr - s.x, dz = zr - s.z;
-    const double ixx = szz / det, ixz = -(sxz / det), izz = sxx / det;
-    const double kxx = (P[AXX] * ixx) + (P[AXZ] * ixz), kxz = (P[AXX] * ixz) + (P[AXZ] * izz);
-    const double kzx = (P[AXZ] * ixx) + (P[AZZ] * ixz), kzz = (P[AXZ] * ixz) + (P[AZZ] * izz);
-    const double lxx = (P[BXX] * ixx) + (P[BZX] * ixz), lxz = (P[BXX] * ixz) + (P[BZX] * izz);
-    const double lzx = (P[BXZ] * ixx) + (P[BZZ] * ixz), lzz = (P[BXZ] * ixz) + (P[BZZ] * izz);
-    const double x = s.x + ((kxx * dx) + (kxz * dz)), z = s.z + ((kzx * dx) + (kzz * dz));
-    const double vx = s.vx + ((lxx * dx) + (lxz * dz)), vz = s.vz + ((lzx * dx) + (lzz * dz));
-    const double n[kCov] = {P[AXX] - ((kxx * P[AXX]) + (kxz * P[AXZ])), P[AXZ] - ((kxx * P[AXZ]) + (kxz * P[AZZ])),
-                            P[AZZ] - ((kzx * P[AXZ]) + (kzz * P[AZZ])),
-                            P[BXX] - ((kxx * P[BXX]) + (kxz * P[BZX])), P[BXZ] - ((kxx * P[BXZ]) + (kxz * P[BZZ])),
-                            P[BZX] - ((kzx * P[BXX]) + (kzz * P[BZX])), P[BZZ] - ((kzx * P[BXZ]) + (kzz * P[BZZ])),
-                            P[CXX] - ((lxx * P[BXX]) + (lxz * P[BZX])), P[CXZ] - ((lxx * P[BXZ]) + (lxz * P[BZZ])),
-                            P[CZZ] - ((lzx * P[BXZ]) + (lzz * P[BZZ]))};
-    s.x = x; s.z = z; s.vx = vx; s.vz = vz;
-#pragma unroll
-    for (int k = 0; k < kCov; ++k) s.P[k] = n[k];
-    return true;
+    turn_cov(s.P, g.xx, g.xz, g.zx, g.zz);
 }
 
 // section 4.35, one backward step: sm holds the smoothed state of cell c + 1 and receives that of cell c; pp is the predicted state of
@@ -269,7 +203,7 @@ __global__ __launch_bounds__(kLanes) void track_smooth_pass(const float* __restr
             const double x = (double)r[19], z = (double)r[21];
             double rxx, rxz, rzz;
             row_noise(x, z, kf, rxx, rxz, rzz);
-            if (!update(cur, x, z, rxx, rxz, rzz)) {
+            if (!update(cur.P, rxx, rxz, rzz, x - cur.x, z - cur.z, cur.x, cur.z, cur.vx, cur.vz)) {
                 // a restart: as at a birth from the row.  The step into this cell is skipped on the way back; the predicted covariance
                 // is kept as zeros, whose determinant is not > 0: the backward pass needs no flag of its own
                 born(cur, x, z, rxx, rxz, rzz, kf.birth_speed);
@@ -382,9 +316,6 @@ layout layout_of(int N, int n_seg, long long cells)
     return l;
 }
 
-bool positive(double v) { return v > 0.0 && __builtin_isfinite(v); }             // (false for NaN)
-bool not_negative(double v) { return v >= 0.0 && __builtin_isfinite(v); }
-
 }  // namespace
 
 extern "C" int gpp_track_smooth_workspace_bytes(int N, int n_seg, long long cells, size_t* bytes)
@@ -403,9 +334,7 @@ extern "C" int gpp_track_smooth_f64(const float* rows_in, int N, int D, const in
     if (N < 0 || D < 0 || n_seg < 0 || D > kMaxD || !kf || !seg_start) return GPP_ERR_BAD_ARG;
     const long long rows_total = (long long)N * (long long)D;
     if (rows_total > 0x7fffffffLL) return GPP_ERR_BAD_ARG;
-    if (!positive(kf->radial0) || !positive(kf->tangential0) || !positive(kf->birth_speed)) return GPP_ERR_BAD_ARG;
-    if (!not_negative(kf->radial1) || !not_negative(kf->tangential1) || !not_negative(kf->q_pos) || !not_negative(kf->q_vel)) return GPP_ERR_BAD_ARG;
-    if (kf->reserved != 0) return GPP_ERR_BAD_ARG;
+    if (gpp_kf::kf_params_bad(*kf)) return GPP_ERR_BAD_ARG;
     if (seg_start[0] != 0) return GPP_ERR_BAD_ARG;
     for (int s = 0; s < n_seg; ++s)
         if (seg_start[s + 1] <= seg_start[s]) return GPP_ERR_BAD_ARG;
@@ -429,13 +358,8 @@ extern "C" int gpp_track_smooth_f64(const float* rows_in, int N, int D, const in
         }
     }
     if (ego)
-        for (int f = 0; f < N; ++f) {
-            const double* e = ego + (size_t)f * kEgoFields;
-            for (int k = 0; k < 13; ++k)
-                if (!__builtin_isfinite(e[k])) return GPP_ERR_BAD_ARG;
-            for (int k = 13; k < kEgoFields; ++k)
-                if (!(e[k] == 0.0)) return GPP_ERR_BAD_ARG;          // (a NaN is not zero either)
-        }
+        for (int f = 0; f < N; ++f)
+            if (gpp_kf::ego_record_bad(ego + (size_t)f * kEgoFields)) return GPP_ERR_BAD_ARG;
     if (fills > 0 && !fill_rows) return GPP_ERR_BAD_ARG;
     if (cells > 0 && !workspace) return GPP_ERR_BAD_ARG;
     if (((uintptr_t)rows_in | (uintptr_t)rows_out | (uintptr_t)fill_rows) & 3u) return GPP_ERR_ALIGN;

@@ -20,7 +20,8 @@ The state is one record of STATE_DTYPE, byte for byte the gpp_track_state of inc
 """
 import numpy as np
 
-from . import gpp_utils, kitti_eval, mot_eval
+from . import gpp_utils, kitti_eval, mot_eval, track_kf as KF
+from .track_kf import PI, wrap              # wrap: into [-pi, pi), as csrc/pose.hip; importers of utils.track find both names here
 
 METRICS = ('bev', '3d', 'dist')             # include/gpp.h: GPP_TRACK_BEV 0, GPP_TRACK_3D 1, GPP_TRACK_DIST 2
 POSE_COLS = kitti_eval.POSE_COLS
@@ -35,8 +36,6 @@ STATE_DTYPE = np.dtype([('id1', '<i4', (MAX_TRACKS,)), ('hits', '<i4', (MAX_TRAC
 DEFAULTS = {'max_age': 2, 'gains': (0.5, 0.25, 0.25), 'birth_score': 0.0, 'smooth': False}
 ASSIGNS = ('greedy', 'optimal')             # gpp_track_f64, gpp_track_optimal_f64; 'greedy' is the default and is not carried in the option
 SCALE = mot_eval.SCALE                      # 2^20 (GPP_MOT_SCALE_BITS): the cell of a pair that is no candidate
-PI = float(np.pi)
-TWO_PI = 2.0 * PI
 TRACKING_FORMAT = '%d %d ' + gpp_utils.KITTI_FORMAT
 EGO_FIELDS = 16                             # GPP_TRACK_EGO_FIELDS: R row-major (9), t (3), dyaw (1), three words that are 0
 KF_METRICS = METRICS + ('maha',)            # GPP_TRACK_MAHA 3: only with 'filter': 'kalman' (gpp_track_kf_f64)
@@ -185,14 +184,6 @@ def tracks_of(state):
     return out
 
 
-def wrap(a):
-    """ into [-pi, pi): the wrap of csrc/pose.hip, operation for operation """
-    a = a - TWO_PI * np.floor(a / TWO_PI)
-    a = np.where(a < 0.0, a + TWO_PI, a)
-    a = np.where(a >= TWO_PI, a - TWO_PI, a)
-    return np.where(a >= PI, a - TWO_PI, a)
-
-
 def ego_records(poses):
     """ (N, 4, 4) or (N, 3, 4) transforms -- a point p in the previous frame's camera coordinates lies at R p + t in this frame's -- ->
     the (N, 16) float64 records of gpp_track_ego_f64: R row-major, t, dyaw = atan2(R02 - R20, R00 + R22) (exact for a rotation about
@@ -221,32 +212,9 @@ def check_ego(ego, N):
 
 
 def row_noise(rows, noise):
-    """ section 4.34, "row noise": rows (D, 36) float32 -> (3, D) float64, Rxx Rxz Rzz of every row: sigma radial0 + radial1 rho along the
-    viewing ray on the ground plane, tangential0 + tangential1 rho across it """
-    (r0, r1), (t0, t1) = noise['radial'], noise['tangential']
-    x, z = rows[:, 19].astype(np.float64), rows[:, 21].astype(np.float64)
+    """ section 4.34, "row noise" (utils/track_kf.py): rows (D, 36) float32 -> (3, D) float64, Rxx Rxz Rzz of every row """
     with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
-        rho = np.sqrt((x * x) + (z * z))
-        far = rho != 0.0
-        ux, uz = np.where(far, x / rho, 0.0), np.where(far, z / rho, 1.0)
-        sr, st = r0 + (r1 * rho), t0 + (t1 * rho)
-        vr, vt = sr * sr, st * st
-        dv = vr - vt
-        return np.stack([vt + (dv * (ux * ux)), dv * (ux * uz), vt + (dv * (uz * uz))])
-
-
-def turn_block(g, xx, xz, zx, zz):
-    """ section 4.34, "ego": a 2 x 2 block X -> Rg X Rg^T with g = (g00, g01, g10, g11); one NumPy operation per float64 operation """
-    g00, g01, g10, g11 = g
-    mxx, mxz = (g00 * xx) + (g01 * zx), (g00 * xz) + (g01 * zz)
-    mzx, mzz = (g10 * xx) + (g11 * zx), (g10 * xz) + (g11 * zz)
-    return (mxx * g00) + (mxz * g01), (mxx * g10) + (mxz * g11), (mzx * g00) + (mzz * g01), (mzx * g10) + (mzz * g11)
-
-
-def innovation(cov, noise, t, d):
-    """ S = A + R of the pairs (slot t[k], row d[k]) -> (Sxx, Sxz, Szz, det) """
-    sxx, sxz, szz = cov[0][t] + noise[0][d], cov[1][t] + noise[1][d], cov[2][t] + noise[2][d]
-    return sxx, sxz, szz, (sxx * szz) - (sxz * sxz)
+        return KF.row_noise(rows[:, 19].astype(np.float64), rows[:, 21].astype(np.float64), noise)
 
 
 def candidate_keys(box, occupied, rows, valid, metric, threshold, cov=None, noise=None):
@@ -271,7 +239,7 @@ def candidate_keys(box, occupied, rows, valid, metric, threshold, cov=None, nois
             return keys
         if metric == 'maha':
             dx, dz = gx - sx, gz - sz
-            sxx, sxz, szz, det = innovation(cov, noise, t, d)
+            sxx, sxz, szz, det = KF.innovation(cov[:3, t], noise[:, d])
             m = ((((szz * dx) * dx) - ((2.0 * (sxz * dx)) * dz)) + ((sxx * dz) * dz)) / det
             hit = (det > 0.0) & (m < threshold * threshold)
             keys[t[hit], d[hit]] = m[hit]
@@ -355,12 +323,7 @@ def step_np(state, rows, opt, keys_out=None, ego=None, cov=None):
         speed = opt['noise']['birth_speed']
     box[0:3, occupied] = box[0:3, occupied] + box[7:10, occupied]                                  # 1 predict
     if kalman:
-        P = [cov[k, occupied].copy() for k in range(10)]
-        cov[0, occupied] = ((P[0] + (P[3] + P[3])) + P[7]) + q_pos
-        cov[1, occupied] = (P[1] + (P[4] + P[5])) + P[8]
-        cov[2, occupied] = ((P[2] + (P[6] + P[6])) + P[9]) + q_pos
-        cov[3, occupied], cov[4, occupied], cov[5, occupied], cov[6, occupied] = P[3] + P[7], P[4] + P[8], P[5] + P[8], P[6] + P[9]
-        cov[7, occupied], cov[9, occupied] = P[7] + q_vel, P[9] + q_vel
+        cov[:, occupied] = KF.predict_cov(cov[:, occupied], q_pos, q_vel)
     if ego is not None:                                                                             # 1b ego
         # the products are written out, one NumPy operation per float64 operation of the rule and in its association: `@`, dot and
         # einsum go through BLAS, which may fuse a multiply with an add or sum in another order
@@ -372,11 +335,7 @@ def step_np(state, rows, opt, keys_out=None, ego=None, cov=None):
             box[7 + k, occupied] = (e[3 * k] * vx + e[3 * k + 1] * vy) + e[3 * k + 2] * vz
         box[3, occupied] = wrap(box[3, occupied] + e[12])
         if kalman:                                                                                  # (the ground part of R on every block)
-            g = (e[0], e[2], e[6], e[8])
-            P = [cov[k, occupied].copy() for k in range(10)]
-            cov[0, occupied], cov[1, occupied], _, cov[2, occupied] = turn_block(g, P[0], P[1], P[1], P[2])
-            cov[3, occupied], cov[4, occupied], cov[5, occupied], cov[6, occupied] = turn_block(g, P[3], P[4], P[5], P[6])
-            cov[7, occupied], cov[8, occupied], _, cov[9, occupied] = turn_block(g, P[7], P[8], P[8], P[9])
+            cov[:, occupied] = KF.turn_cov(cov[:, occupied], (e[0], e[2], e[6], e[8]))
     live = rows[:, 14] >= 0.0                                                                       # 2 rows
     valid = live & ~np.isnan(rows[:, ROW_COLS]).any(axis=1)
     noise = row_noise(rows, opt['noise']) if kalman else None
@@ -393,26 +352,10 @@ def step_np(state, rows, opt, keys_out=None, ego=None, cov=None):
         z = rows[d][:, ROW_COLS].astype(np.float64).T                                               # (7, matched)
         r = z[0:3] - box[0:3, t]
         if kalman:
+            R = noise[:, d]
             with np.errstate(invalid='ignore', divide='ignore', over='ignore'):
-                sxx, sxz, szz, det = innovation(cov, noise, t, d)
-                good = det > 0.0                                                                    # otherwise: the fixed gains, P as at birth
-                P = [cov[k, t].copy() for k in range(10)]
-                px, pz, dx, dz = box[0, t].copy(), box[2, t].copy(), r[0], r[2]
-                ixx, ixz, izz = szz / det, -(sxz / det), sxx / det
-                kxx, kxz = (P[0] * ixx) + (P[1] * ixz), (P[0] * ixz) + (P[1] * izz)
-                kzx, kzz = (P[1] * ixx) + (P[2] * ixz), (P[1] * ixz) + (P[2] * izz)
-                lxx, lxz = (P[3] * ixx) + (P[5] * ixz), (P[3] * ixz) + (P[5] * izz)
-                lzx, lzz = (P[4] * ixx) + (P[6] * ixz), (P[4] * ixz) + (P[6] * izz)
-                mean = [px + ((kxx * dx) + (kxz * dz)), pz + ((kzx * dx) + (kzz * dz)),
-                        box[7, t] + ((lxx * dx) + (lxz * dz)), box[9, t] + ((lzx * dx) + (lzz * dz))]
-                new = [P[0] - ((kxx * P[0]) + (kxz * P[1])), P[1] - ((kxx * P[1]) + (kxz * P[2])), P[2] - ((kzx * P[1]) + (kzz * P[2])),
-                       P[3] - ((kxx * P[3]) + (kxz * P[5])), P[4] - ((kxx * P[4]) + (kxz * P[6])),
-                       P[5] - ((kzx * P[3]) + (kzz * P[5])), P[6] - ((kzx * P[4]) + (kzz * P[6])),
-                       P[7] - ((lxx * P[3]) + (lxz * P[5])), P[8] - ((lxx * P[4]) + (lxz * P[6])), P[9] - ((lzx * P[4]) + (lzz * P[6]))]
-            zero = np.zeros(len(t))
-            born = [noise[0][d], noise[1][d], noise[2][d], zero, zero, zero, zero, zero + speed * speed, zero, zero + speed * speed]
-            for k in range(10):
-                cov[k, t] = np.where(good, new[k], born[k])
+                mean, new, good = KF.update(box[[0, 2, 7, 9]][:, t], cov[:, t], R, r[0], r[2])
+            cov[:, t] = np.where(good, new, KF.born_cov(R, speed))                                  # det not > 0: the fixed gains, P as at birth
         box[7:10, t] = box[7:10, t] + b * r
         box[0:3, t] = box[0:3, t] + a * r
         if kalman:
@@ -446,9 +389,7 @@ def step_np(state, rows, opt, keys_out=None, ego=None, cov=None):
     box[0:7, t] = rows[d][:, ROW_COLS].astype(np.float64).T
     box[7:10, t] = 0.0
     if kalman:
-        cov[0:3, t] = noise[:, d]
-        cov[3:10, t] = 0.0
-        cov[7, t] = cov[9, t] = speed * speed
+        cov[:, t] = KF.born_cov(noise[:, d], speed)
     row_slot[d] = t
     state['next_id'] += n
     state['dropped'] += born.size - n

@@ -3,8 +3,8 @@ Smoothing finished tracks offline: a backward Rauch-Tung-Striebel pass over the 
 short gaps -- DESIGN.md section 4.35 is the specification, include/gpp.h (gpp_track_smooth_f64) the contract.  The tracker writes
 filtered positions: the cuboid at frame k knows nothing of the frames behind it, and a frame in which the detector missed a car stays a
 hole in the track file.  Whoever tracks a recorded sequence has all of it in hand: this stage runs section 4.34's filter forward over
-every SEGMENT of an identity -- the state (x, z, vx, vz), the row noise, predict, the ego step, the update and the birth covariance,
-expression for expression -- then backward, and gives every detected row its smoothed x, z and alpha, every missed frame inside a
+every SEGMENT of an identity -- the state (x, z, vx, vz); the row noise, predict, the ground rotation, the update and the birth covariance
+are utils/track_kf.py's, the functions the tracker calls -- then backward, and gives every detected row its smoothed x, z and alpha, every missed frame inside a
 segment a FILL row between its two detected neighbours, and both the position block of the smoothed covariance.
 
     segments_of      ids (N, D) -> the index: segments, their cells, a row or a gap per cell (NumPy, on the host)
@@ -20,6 +20,7 @@ import collections
 import numpy as np
 
 from . import track as T
+from . import track_kf as KF
 
 POSE_COLS = T.POSE_COLS
 CODE_COLS = (13, 14, 33, 34, 35)            # gpp_pose_f32's row: label, orientation class, padding -- codes, not measures: never interpolated
@@ -135,42 +136,26 @@ def sym(xx, xz, zz):
 
 
 def predict(s, q_pos, q_vel):
-    """ section 4.34, 1 predict, on the 14 words x z vx vz Axx Axz Azz Bxx Bxz Bzx Bzz Cxx Cxz Czz (arrays over the segments) """
-    x, z, vx, vz, axx, axz, azz, bxx, bxz, bzx, bzz, cxx, cxz, czz = s
-    return [x + vx, z + vz, vx, vz, ((axx + (bxx + bxx)) + cxx) + q_pos, (axz + (bxz + bzx)) + cxz, ((azz + (bzz + bzz)) + czz) + q_pos,
-            bxx + cxx, bxz + cxz, bzx + cxz, bzz + czz, cxx + q_vel, cxz, czz + q_vel]
+    """ section 4.34, 1 predict, on the 14 words x z vx vz Axx Axz Azz Bxx Bxz Bzx Bzz Cxx Cxz Czz (a list of arrays over the segments) """
+    return [s[0] + s[2], s[1] + s[3], s[2], s[3]] + KF.predict_cov(s[4:], q_pos, q_vel)
 
 
 def ego_step(s, g, t0, t2):
     """ section 4.35, the ego step: the mean by the ground part only, the covariance as section 4.34's 1b; g = (g00, g01, g10, g11) """
     x, z, vx, vz = s[:4]
-    gt = tr(g)
-    a, b, c = mul(mul(g, sym(s[4], s[5], s[6])), gt), mul(mul(g, tuple(s[7:11])), gt), mul(mul(g, sym(s[11], s[12], s[13])), gt)
-    return [((g[0] * x) + (g[1] * z)) + t0, ((g[2] * x) + (g[3] * z)) + t2, (g[0] * vx) + (g[1] * vz), (g[2] * vx) + (g[3] * vz),
-            a[0], a[1], a[3], b[0], b[1], b[2], b[3], c[0], c[1], c[3]]
+    return [((g[0] * x) + (g[1] * z)) + t0, ((g[2] * x) + (g[3] * z)) + t2, (g[0] * vx) + (g[1] * vz), (g[2] * vx) + (g[3] * vz)] + KF.turn_cov(s[4:], g)
 
 
 def born(x, z, R, speed):
     """ section 4.34, 7 births: mean (x, z, 0, 0), A = R of the row, B = 0, C = birth_speed^2 I """
     zero = np.zeros_like(x)
-    return [x, z, zero, zero, R[0], R[1], R[2], zero, zero, zero, zero, zero + speed * speed, zero, zero + speed * speed]
+    return [x, z, zero, zero] + KF.born_cov(R, speed)
 
 
 def update(s, xr, zr, R):
     """ section 4.34, 5 update -> (the 14 words, det > 0); where det is not > 0 the words are not to be used: the caller restarts """
-    x, z, vx, vz, axx, axz, azz, bxx, bxz, bzx, bzz, cxx, cxz, czz = s
-    sxx, sxz, szz = axx + R[0], axz + R[1], azz + R[2]
-    det = (sxx * szz) - (sxz * sxz)
-    dx, dz = xr - x, zr - z
-    ixx, ixz, izz = szz / det, -(sxz / det), sxx / det
-    kxx, kxz, kzx, kzz = (axx * ixx) + (axz * ixz), (axx * ixz) + (axz * izz), (axz * ixx) + (azz * ixz), (axz * ixz) + (azz * izz)
-    lxx, lxz, lzx, lzz = (bxx * ixx) + (bzx * ixz), (bxx * ixz) + (bzx * izz), (bxz * ixx) + (bzz * ixz), (bxz * ixz) + (bzz * izz)
-    new = [x + ((kxx * dx) + (kxz * dz)), z + ((kzx * dx) + (kzz * dz)), vx + ((lxx * dx) + (lxz * dz)), vz + ((lzx * dx) + (lzz * dz)),
-           axx - ((kxx * axx) + (kxz * axz)), axz - ((kxx * axz) + (kxz * azz)), azz - ((kzx * axz) + (kzz * azz)),
-           bxx - ((kxx * bxx) + (kxz * bzx)), bxz - ((kxx * bxz) + (kxz * bzz)), bzx - ((kzx * bxx) + (kzz * bzx)),
-           bzz - ((kzx * bxz) + (kzz * bzz)), cxx - ((lxx * bxx) + (lxz * bzx)), cxz - ((lxx * bxz) + (lxz * bzz)),
-           czz - ((lzx * bxz) + (lzz * bzz))]
-    return new, det > 0.0
+    mean, P, good = KF.update(s[:4], s[4:], R, xr - s[0], zr - s[1])
+    return mean + P, good
 
 
 def smooth_step(sm, pp, pf, g):

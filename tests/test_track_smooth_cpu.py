@@ -85,6 +85,48 @@ def test_the_forward_pass_is_the_trackers(with_records):
     assert np.array_equal(last[4:], cov[:, slot])
 
 
+def test_the_forward_pass_is_the_trackers_on_a_frame_of_cars():
+    """ the same comparison between the two callers of utils/track_kf.py on a frame of four cars, 10 frames under the 'general' records
+    (yaw and pitch in frame 1), car 1 missed in frame 4 and car 2 in frame 6: of every identity the filtered words of the segment's last
+    cell are the slot's state and covariance, all 14, ==.  The rows stand where the records carry the cars, plus a small step of their
+    own.  What makes the two forms one filter here, and is written into the scene:
+      - y = 0 in every row and gain b = 0, so y and vy stay 0 and the pitch's y terms, which the smoother leaves out, are zeros;
+      - the noise is so steep (sigma 1e75 rho) that for the far car, at 200 m, det S overflows to inf - inf in EVERY matched step, while
+        the three cars within 12 m stay finite: the tracker takes its fallback there and the smoother restarts.  With gain a = 1 the
+        fallback's mean is pred + (row - pred) = the row exactly (the two lie within a factor of two: the difference is exact), its
+        velocity has been 0 since birth, and both set P as at a birth from the row: the restart's words;
+      - the birth speed (1e76) is on the noise's scale, so the near cars' velocity gains are of order 1: they end at velocities near
+        their steps, with B and C blocks that every update has moved """
+    N, steps = 10, [(0.125, 0.25), (-0.0625, 0.5), (0.25, -0.125), (0.5, 0.5)]
+    ego = C.records('general', N)
+    where = [(-3.0, 9.0), (2.0, 6.0), (5.0, 10.0), (141.0, 141.0)]           # three near cars, one far: the car of row k
+    missed = {(1, 4), (2, 6)}
+    rows = np.stack([padding(4) for _ in range(N)])
+    for f in range(N):
+        e = ego[f]
+        if f:
+            where = [(e[0] * x + e[2] * z + e[9] + sx, e[6] * x + e[8] * z + e[11] + sz) for (x, z), (sx, sz) in zip(where, steps)]
+        for k, (x, z) in enumerate(where):
+            if (k, f) not in missed:
+                rows[f, k] = row(0.9 - 0.1 * k, x, z, y=0.0)
+    noise = dict(NOISE, radial=(0.1, 1e75), tangential=(0.1, 0.5e75), birth_speed=1e76)
+    opt = K.options('dist', 8.0, noise=noise, gains=(1.0, 0.0, 0.25))
+    _, ids, _, state, cov = T.track_rows_np(rows, opt, ego=ego)
+    assert int(state['next_id']) == 4 and int(state['dropped']) == 0 and (ids >= 0).sum() == 4 * N - 2
+    index = S.segments_of(ids, None, 2, rows)
+    assert index.seg_id.tolist() == [0, 1, 2, 3] and np.diff(index.seg_start).tolist() == [N] * 4 and (index.cell_row < 0).sum() == 2
+    keep = {}
+    S.smooth_np(rows, index, noise, ego, keep=keep)
+    for s, who in enumerate(index.seg_id):
+        last = keep['filtered'][:, index.seg_start[s + 1] - 1]
+        slot = int(np.flatnonzero(state['id1'] == who + 1)[0])
+        assert np.isfinite(last).all()
+        assert [last[0], last[1], last[2], last[3]] == [state['box'][k][slot] for k in (0, 2, 7, 9)]
+        assert np.array_equal(last[4:], cov[:, slot])
+        born = last[2:4].tolist() == [0.0, 0.0] and last[7:].tolist() == [0.0, 0.0, 0.0, 0.0, 1e152, 0.0, 1e152]
+        assert born == (who == 3)                                            # the far car restarted, the near ones were updated
+
+
 # ---------------------------------------------------------------------------------------------------- an independent check
 def least_squares(rows, index, noise, ego):
     """ one segment as a batch weighted least-squares problem over all its states: the birth prior, one process residual per step, one
